@@ -22,6 +22,7 @@ Metric (BASELINE.json): Mpixels/sec encode, `cluster-colors` K=256.
                                 (delta); roofline = the gather kernel, 3 B/px read).  Not the default anywhere.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `roofline` is the K-means assign kernel (dominant kernel), timed live with HIP events
@@ -39,6 +40,34 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FRAME_W, FRAME_H = 1920, 1080
+DUMP_LIMIT_BYTES = 64 * 10 ** 6    # --dump-outputs: everything written, at most
+DUMP_SAMPLE = 12 << 20             # elements kept of a longer byte array (48 MiB as float32, under the limit with the rest)
+DUMP_SEED = 0x636E696963
+
+
+def dump_outputs(dirpath, arrays, numbers):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy.  `arrays`: name -> uint8 tensor (device or
+    host), written as float32 -- whole, or, when it holds more than DUMP_SAMPLE elements, the elements at DUMP_SAMPLE sorted positions
+    drawn from DUMP_SEED and its length (so the same positions for the same length) -- with its length as <name>_length.npy;
+    `numbers`: name -> number or list of numbers, written as float64."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.cpu().numpy().astype(np.float32)
+        out[name + "_length"] = np.array([n], np.float64)
+    for name, v in numbers.items():
+        out[name] = np.asarray(v, np.float64).reshape(-1)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes, over the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def traffic_for(key):
@@ -108,7 +137,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="c2 at N=1: skip the c4_one_gpu and host-buffer legs")
     ap.add_argument("--decode", action="store_true", help="c2 / c5: time Codec::decode of the stream the encode produced (stream and image resident in HBM) "
                                                            "instead of the encode; its own metric (Mpixels/sec decode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step (rank 0's) "
+                                                          "as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries ONE JSON line: everything else a library prints there (RCCL's version banner when a communicator is made)
     # goes to stderr -- file descriptor 1 points at stderr until the line is written
@@ -187,13 +220,16 @@ def main():
             ctx.synth_image(_lib.SYNTH_PHOTO, synth.SEED0 + 4 + first_frame + f, FRAME_W, FRAME_H, out=fr[f])
         return fr
 
-    def run_c4(enc, F, warmup, steps, profile, reduce_max=True):
+    def run_c4(enc, F, warmup, steps, profile, reduce_max=True, dump=False):
         """-> (seconds for `steps` batch encodes, bytes of this rank's streams, stats, distinct colours of this rank, roofline)"""
         frames = make_frames(F, rank * F)
         stride = FRAME_W * FRAME_H  # 1 byte per pixel between streams: K = 256 labels need at most 8 bits each + the tree
         out = torch.empty(stride * F, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize()
         dt, (lens, st) = timed(lambda: enc.encode_frames(frames, FRAME_W, FRAME_H, F, out, stride), warmup, steps, reduce_max)
+        if dump and rank == 0:
+            dump_outputs(args.dump_outputs, {"streams": torch.cat([out[f * stride:f * stride + lens[f]] for f in range(F)])},
+                         {"stream_lengths": lens, "kmeans_iterations": st["iterations"]})
         # the timed streams against the oracle's (configs[3]'s one-GPU share: one palette over these frames, every frame's own stream)
         g4 = golden("c4")
         run_c4.parity = None
@@ -236,7 +272,7 @@ def main():
         ok = got == g.get("sha256") and int(nbytes) == g.get("length") and (iterations is None or g.get("iterations") in (None, int(iterations)))
         return {"case": case, "stream_sha256": got, "matches_oracle": bool(ok)}
 
-    def run_c3(size, warmup, steps):
+    def run_c3(size, warmup, steps, dump=False):
         """configs[2]: voronoi(2048), 5-D position + colour K-means on one size^2 image per GPU (replicas), to convergence.
         roofline = k_xy_assign per iteration, SURVEY 8(d): 7 B/px/iteration (3 B pixel + u16 label read and written)."""
         W = H = size
@@ -252,6 +288,8 @@ def main():
         dt, (nbytes, st) = timed(step, warmup, steps)
         if rank != 0:
             return None
+        if dump:
+            dump_outputs(args.dump_outputs, {"stream": out[:nbytes]}, {"kmeans_iterations": st["iterations"]})
         rc, ln, stp = ctx.encode("voronoi(%d)" % Kv, img, w=W, h=H, out=out, max_iters=args.max_iters, flags=_lib.KM_PROFILE, allow=(_lib.FEW_ACTIVE,))
         ms, n = ctx.kernel_time("kmeans_xyrgb_iter")
         roofline = None
@@ -292,7 +330,7 @@ def main():
                            "parallelism": "1 GPU" if world == 1 else "%d independent images, one per GPU (replicas, no collective)" % world},
                 "roofline": roofline, "cpu_baseline": cpu, "parity": digest_check("v%d" % W, out, nbytes, W, H, st["iterations"])}
 
-    def run_c5(size, warmup, steps):
+    def run_c5(size, warmup, steps, dump=False):
         """configs[4]: `delta` (Hilbert gather + neighbour differences + symbol histogram + Huffman) on one size^2 image per GPU
         (independent images: replicas, no collective).  roofline = the gather kernel, SURVEY 8(d): 3 B/px read."""
         W = H = size
@@ -307,6 +345,8 @@ def main():
         dt, (nbytes, st) = timed(step, warmup, steps)
         if rank != 0:
             return None
+        if dump:
+            dump_outputs(args.dump_outputs, {"stream": out[:nbytes]}, {})
         parity = digest_check("c5", out, nbytes, W, H)
         ctx.encode("delta", img, w=W, h=H, out=out, flags=_lib.KM_PROFILE)  # one more call with the stage timers (HIP events on the ctx stream)
         stages = {}
@@ -347,11 +387,11 @@ def main():
 
     line = None
     if args.decode:
-        line = bench_decode(args, ctx, torch, np, dev, rank, world, timed, config)
+        line = bench_decode(args, ctx, torch, np, dev, rank, world, timed, config, dump=bool(args.dump_outputs))
     elif config == "c4":
         F = args.frames_per_gpu
         enc = ShardedClusterColors(ctx, K, dist, dev, max_iters=args.max_iters, collectives=native)
-        dt, nbytes, st, U, roof = run_c4(enc, F, args.warmup, args.steps, profile=(rank == 0))
+        dt, nbytes, st, U, roof = run_c4(enc, F, args.warmup, args.steps, profile=(rank == 0), dump=bool(args.dump_outputs))
         npx_total = F * FRAME_W * FRAME_H * world
         if rank == 0:
             cpu = None
@@ -372,9 +412,9 @@ def main():
             }
         enc.close()
     elif config == "c3":
-        line = run_c3(args.size, args.warmup, args.steps)
+        line = run_c3(args.size, args.warmup, args.steps, dump=bool(args.dump_outputs))
     elif config == "c5":
-        line = run_c5(args.c5_size, args.warmup, args.steps)
+        line = run_c5(args.c5_size, args.warmup, args.steps, dump=bool(args.dump_outputs))
     else:
         W = H = args.size
         seed = synth.SEED0 + 2 + rank  # config 2 of SURVEY 8(d); one image per rank
@@ -393,6 +433,8 @@ def main():
                 rc, ln, st = ctx.encode(expr, img, w=W, h=H, out=out, max_iters=args.max_iters)
                 return ln, st
         dt, (nbytes, st) = timed(step, args.warmup, args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"stream": out[:nbytes]}, {"kmeans_iterations": st["iterations"]})
         npx_total = W * H * world
         # the timed stream against the oracle's digest at this size (one image, its own palette: the un-sharded step only)
         parity = digest_check("c2", out, nbytes, W, H, st["iterations"]) if not sharded and K == 256 and not args.max_iters else None
@@ -646,7 +688,7 @@ def main():
         dist.destroy_process_group()
 
 
-def bench_decode(args, ctx, torch, np, dev, rank, world, timed, config):
+def bench_decode(args, ctx, torch, np, dev, rank, world, timed, config, dump=False):
     """The other half of the trait (bench.rs:45-46 decodes every image it encodes): Codec::decode of the stream Codec::encode made,
     stream and image both resident in HBM (replicas: one image per GPU, no collective).  roofline = the kernel that decodes the
     payload and writes the symbols (k_hd_write): payload bytes read + the bytes it writes, timed with HIP events around it."""
@@ -673,6 +715,8 @@ def bench_decode(args, ctx, torch, np, dev, rank, world, timed, config):
         assert torch.equal(back.view(H, W, 3), img), "decode(encode(img)) != img"
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(args.dump_outputs, {"image": back}, {})
     mse = float((img.view(-1).to(torch.float32) - back.to(torch.float32)).pow(2).mean().item())   # bench::compute_error (bench.rs:95-104)
     ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
     ctx.decode_into(expr, stream, ln, back)
