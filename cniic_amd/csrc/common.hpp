@@ -110,7 +110,7 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// Knobs of the test-suite, the probes under tools/ and measuring builds (CNIIC_TEST_*, CNIIC_DBG_*, route forcing, tuning constants) are
+// Knobs of the test-suite and the probes under tools/ (CNIIC_TEST_* hooks, route forcing, the persistent launch's timeout) are
 // read from the environment ONLY by the testing build (-DCNIIC_TESTING: libcniic_hip_testing.so, which tests/conftest.py and tools/ ask
 // for with CNIIC_USE_TESTING_LIB=1).  In the release library test_env() is a constant nullptr: no getenv, and the names are not even in
 // the binary (tests/test_abi.py checks `strings`).  What a host may set on a release build are the context options of the ABI, whose
@@ -586,10 +586,7 @@ int synth_image(Ctx *c, int kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t
 int rgb_to_keys(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t *keys_d);
 
 // ---- colour-space cells of the cluster-colors K-means (numbering: cell_of in device_utils.hpp) ----
-#ifndef CNIIC_CELL_SHIFT
-#define CNIIC_CELL_SHIFT 3
-#endif
-constexpr int kCellShift = CNIIC_CELL_SHIFT;                    // 2^shift colours per cell side
+constexpr int kCellShift = 3;                                   // 2^shift colours per cell side
 constexpr uint32_t kCellsPerDim = 256 >> kCellShift;           // 32
 constexpr uint32_t kNumCells = kCellsPerDim * kCellsPerDim * kCellsPerDim;  // 32768
 

@@ -304,16 +304,6 @@ constexpr int kHdRoundsShort = 24;
 // different colours, 51 ms for a ramp.  A list that has kept 97 per cent of its length over three rounds is such a stream at any size.
 __host__ inline uint32_t hd_hopeless_pct(uint64_t nsub) { return nsub <= (1ull << 16) ? 35u : nsub <= (1ull << 19) ? 60u : 97u; }
 constexpr uint64_t kHdPhasesMaxSub = 1ull << 16;   // streams of up to this many subsequences (4 MiB) go to k_hd_phase_maps when the blind checks have not settled them
-// -DCNIIC_HD_PHASES (a measuring build, tools/build_variant.sh): per block of pass 0, thread 0's wall clock (100 MHz) spent staging, in the
-// first decode (until the whole block is through it), in the settle rounds, and the number of rounds; summed over the blocks
-#ifdef CNIIC_HD_PHASES
-__device__ unsigned long long g_hd_phase[8];
-#define HD_T(i) do { if (threadIdx.x == 0 && !end_prev) { const unsigned long long now_ = wall_clock64(); atomicAdd(&g_hd_phase[i], now_ - t_ph_); t_ph_ = now_; } } while (0)
-#define HD_C(i, v) do { if (threadIdx.x == 0 && !end_prev) atomicAdd(&g_hd_phase[i], (unsigned long long)(v)); } while (0)
-#else
-#define HD_T(i) do {} while (0)
-#define HD_C(i, v) do {} while (0)
-#endif
 template <bool WIDE>
 __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg, uint64_t nsub, const uint64_t *__restrict__ end_prev,
                                                         uint64_t *__restrict__ end_out, uint64_t *__restrict__ start, uint32_t *__restrict__ count,
@@ -339,12 +329,8 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
     uint64_t my_start = 0, my_end = 0, base = 0;
     uint32_t my_cnt = 0;
     uint64_t pred0 = 0;      // where the thread before the block's first one ended (pass 0: not known yet -- the first thread trusts its warm-up)
-#ifdef CNIIC_HD_PHASES
-    unsigned long long t_ph_ = wall_clock64();
-#endif
     if (!end_prev) {
         base = hd_stage(S, T.use1 ? T.lut1 : nullptr, lut_s, stage);
-        HD_T(0);
         if (live) {
             uint64_t at = S.bit0;
             if (t) {       // warm-up: from kHdWarm bits before the subsequence to the first boundary inside it
@@ -368,11 +354,7 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
             if (tid == 0) pred0 = s;
             if (!redo) end_out[t] = my_end;   // in step with the thread before: what it found stands (rewritten below if a cure moves it)
         }
-        if (changed[2]) {  // measuring runs (CNIIC_HD_STATS): threads out of step / blocks that stage, per check
-            const int nredo = __syncthreads_count(redo);
-            if (tid == 0 && nredo) { atomicAdd(&changed[3], (uint32_t)nredo); atomicAdd(&changed[4], 1u); }
-            if (!nredo) return;
-        } else if (!__syncthreads_or(redo)) return;
+        if (!__syncthreads_or(redo)) return;
         base = hd_stage(S, T.use1 ? T.lut1 : nullptr, lut_s, stage);
     }
     // ---- the block settles itself
@@ -387,14 +369,12 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
     for (int round = 0; round < max_rounds; round++) {
         if (tid == 0) s_n = 0;
         __syncthreads();                                   // s_end of the round before is in place
-        if (round == 0) HD_T(1); else HD_T(2);
         const uint64_t pred = tid ? s_end[tid - 1] : s_pred0;
         const bool redo = live && pred != my_start;
         if (redo) s_list[atomicAdd(&s_n, 1u)] = (uint16_t)tid;
         __syncthreads();
         const uint32_t nl = s_n;
-        HD_C(4, nl);
-        if (nl == 0) { gave_up = false; HD_C(3, round); HD_C(5, 1); break; }
+        if (nl == 0) { gave_up = false; break; }
         // Does this stream fall into step at all?  Every round re-decodes the listed subsequences from where their predecessors ended; on
         // an ordinary stream that cures four in five of them, on a near-fixed-length code next to none, and the loop becomes a chain of
         // one cure per round.  Curing a fraction p per round costs list / p decodes and ln(list) / p rounds per pass, the phase maps 32
@@ -422,7 +402,6 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
         __syncthreads();                                   // every s_end[j - 1] has been read
         if (redo) { my_start = s_nstart[tid]; my_end = s_nend[tid]; my_cnt = s_ncnt[tid]; s_end[tid] = my_end; }
     }
-    HD_T(2);
     if (!live) return;
     start[t] = my_start;
     end_out[t] = my_end;
@@ -745,7 +724,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     DevBuf lo_d, big_d;
     if (bits2) {
         CNIIC_HIP_TRY(c, lut2_d.alloc(8ull << bits2));
-        if (bits2 > 20 && !test_env("CNIIC_HD_LUT2_SEARCH")) {   // a large table: from the leaves' side (see k_hd_lut_owner)
+        if (bits2 > 20) {   // a large table: from the leaves' side (see k_hd_lut_owner)
             const uint32_t big_cap = (1u << bits2) / kHdOwnMax + 1;   // (leaves that own more than kHdOwnMax prefixes: at most this many)
             CNIIC_HIP_TRY(c, lo_d.alloc(4ull << bits2));
             CNIIC_HIP_TRY(c, big_d.alloc(((uint64_t)big_cap + 1) * 4));
@@ -782,10 +761,8 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     CNIIC_HIP_TRY(c, count.alloc(nsub * 4));
     CNIIC_HIP_TRY(c, off.alloc(nsub * 8));
     CNIIC_HIP_TRY(c, tot.alloc(8));
-    CNIIC_HIP_TRY(c, changed.alloc(32));   // [0] an end moved in this check; [2] statistics wanted, [3] threads out of step, [4] blocks that staged
+    CNIIC_HIP_TRY(c, changed.alloc(32));   // [0] an end moved in this check; [5] pass 0's blocks that gave the stream up
     CNIIC_HIP_TRY(c, hipMemsetAsync(changed.p, 0, 32, c->stream));
-    const bool hd_stats = test_env("CNIIC_HD_STATS") != nullptr;
-    if (hd_stats) { const uint32_t one = 1; CNIIC_HIP_TRY(c, hipMemcpyAsync(changed.as<uint32_t>() + 2, &one, 4, hipMemcpyHostToDevice, c->stream)); }
     CNIIC_HIP_TRY(c, ctx_pinned_u(c));
     volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + 4096;   // (slots of this function's own) [0] total symbols, [1] did the last pass move an end?
     const uint32_t grid = (uint32_t)ceil_div(nsub, kHdThreads);
@@ -793,8 +770,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     const bool wide = lt.max_len > 32;
     const char *ph_env = test_env("CNIIC_HD_PHASES");   // 1: the phase maps whatever the blind checks say (tests); 0: never
     const bool phases_ok = !wide && !(ph_env && !atoi(ph_env)), phases_force = phases_ok && ph_env && atoi(ph_env);
-    const uint64_t phases_max_sub = test_env("CNIIC_HD_PHASES_MAX_SUB") ? strtoull(test_env("CNIIC_HD_PHASES_MAX_SUB"), nullptr, 10) : kHdPhasesMaxSub;   // (for measurements)
-    const bool phases_first = phases_ok && (nsub <= phases_max_sub || phases_force);   // a short stream: instead of more checks
+    const bool phases_first = phases_ok && (nsub <= kHdPhasesMaxSub || phases_force);   // a short stream: instead of more checks
     int pass_rounds = phases_first ? kHdRoundsShort : kHdMaxRounds;
     // a stream that does not fall into step is found out by pass 0 itself (k_hd_pass: blocks whose lists do not shrink count themselves in
     // changed[5]); from a quarter of the blocks on, the checks and the write behind pass 0 return at once and the one look sends the host
@@ -871,29 +847,11 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
         ScopedKernelTimer t0(c, "hd_pass0");   // (stage timers: CNIIC_OPT_STAGE_TIMERS; they synchronise)
         pass(nullptr, cur);
         t0.stop();
-#ifdef CNIIC_HD_PHASES
-        {
-            unsigned long long ph[8], zero[8] = {0};
-            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            CNIIC_HIP_TRY(c, hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_hd_phase), sizeof ph));
-            CNIIC_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(g_hd_phase), zero, sizeof zero));
-            const double nb = (double)grid;
-            fprintf(stderr, "[hd phases] pass 0, %u blocks, warm %u: per block (us) stage %.2f | first decode %.2f | settle rounds %.2f | rounds %.2f, list entries %.1f, blocks that settled %.0f %%\n",
-                    grid, S.warm, ph[0] / nb / 100.0, ph[1] / nb / 100.0, ph[2] / nb / 100.0, ph[3] / nb, ph[4] / nb, 100.0 * ph[5] / nb);
-        }
-#endif
         ScopedKernelTimer t1(c, "hd_check");
         for (int r = 0; r < kHdBlindChecks; r++) {
             CNIIC_HIP_TRY(c, hipMemsetAsync(changed.p, 0, 4, c->stream));
             pass(cur, nxt);
             std::swap(cur, nxt);
-            if (hd_stats) {
-                uint32_t st[5];
-                CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-                CNIIC_HIP_TRY(c, hipMemcpy(st, changed.p, 20, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[hd] check %d: %u of %llu threads out of step, %u of %u blocks staged, an end moved: %u\n", r + 1, st[3], (unsigned long long)nsub, st[4], grid, st[0]);
-                CNIIC_HIP_TRY(c, hipMemsetAsync(changed.as<uint32_t>() + 3, 0, 8, c->stream));
-            }
         }
         t1.stop();
         ScopedKernelTimer t2(c, "hd_write");
@@ -913,13 +871,11 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
         hipLaunchKernelGGL(k_hd_phase_chain, dim3(1), dim3(kHpGroups), 0, c->stream, (const uint8_t *)maps_d.as<uint8_t>(), (const uint16_t *)cnts_d.as<uint16_t>(), nsub, S.nbits,
                            (uint32_t)S.bit0, start_d.as<uint64_t>(), count.as<uint32_t>());
         CNIIC_HIP_TRY(c, hipGetLastError());
-        if (hd_stats) fprintf(stderr, "[hd] not in step: every phase of every subsequence\n");
         CNIIC_TRY(write(false, false));   // (the maps count; they keep nothing)
         CNIIC_TRY(look());
         return CNIIC_OK;
     };
     const bool hopeless = hopeless_min && (uint32_t)pin[2] >= hopeless_min;
-    if (hd_stats) fprintf(stderr, "[hd] blocks of pass 0 that did not fall into step: %u of %u%s\n", (uint32_t)pin[2], grid, hopeless ? " -- given up" : "");
     if (hopeless || (phases_first && ((uint32_t)pin[1] || phases_force))) {
         CNIIC_TRY(phases());   // not in step after the blind checks: no more checks one subsequence at a time
         if (*status == 2) return CNIIC_OK;
@@ -930,7 +886,6 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
             pass(cur, nxt);
             std::swap(cur, nxt);
             CNIIC_TRY(look());
-            if (hd_stats) fprintf(stderr, "[hd] check %d (after a look): an end moved: %u\n", r + 1, (uint32_t)pin[1]);
             if (!(uint32_t)pin[1]) { settled = true; break; }
         }
         if (!settled && !phases_ok) { *status = 2; return CNIIC_OK; }

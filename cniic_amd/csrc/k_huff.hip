@@ -1190,7 +1190,7 @@ int huff_tree_from_runs(Ctx *c, const uint64_t *sorted_d, const uint64_t *counts
     // leaves on, and only when the leaves outnumber the runs four to one -- an image whose colours are nearly all distinct (`hufman`
     // 512^2: 2.5 10^5 leaves, a dozen runs: 0.73 -> 0.40 ms).  CNIIC_HUF_RUNS_MIN moves the line, tests set 0 and take any runs.)
     const char *rm = test_env("CNIIC_HUF_RUNS_MIN");
-    if (n < 2 || n < (rm ? (uint32_t)atoi(rm) : kRunsMinLeaves) || test_env("CNIIC_HUF_HOST_MERGE")) return CNIIC_OK;
+    if (n < 2 || n < (rm ? (uint32_t)atoi(rm) : kRunsMinLeaves)) return CNIIC_OK;
     DevBuf small, runs_d, desc_d, tree_d, par, keys_a, keys_b, z_d, zex_d, tot_d;
     CNIIC_HIP_TRY(c, small.alloc(64));
     CNIIC_HIP_TRY(c, hipMemsetAsync(small.p, 0, 64, c->stream));

@@ -248,22 +248,6 @@ __device__ __forceinline__ uint32_t ps_row_build_table(const uint2 *tab, uint32_
     return pid;
 }
 
-// -DCNIIC_PS_PHASES: wave-clock totals per phase of k_rgbw_persist (a measuring build, never the shipped one):
-// 0 lists, 1 classify, 2 draw + descriptors, 3 mask, 4 point words, 5 sweep, 6 cell tail, 7 flush .. barrier .. update, 8 cells swept;
-// inside a sweep: 10 unpack + one-candidate exit, 11 table reads + scores, 12 who moves, 13 labels, 14 booking
-#ifdef CNIIC_PS_PHASES
-__device__ unsigned long long g_ps_phase[16];
-#define PS_PHASE(i) do { const long long now_ = clock64(); ph_[i] += (unsigned long long)(now_ - t_ph); t_ph = now_; } while (0)
-#define PS_COUNT(i, v) do { ph_[i] += (unsigned long long)(v); } while (0)
-#define PS_PROF_PARAMS , unsigned long long (&ph_)[16], long long &t_ph
-#define PS_PROF_ARGS , ph_, t_ph
-#else
-#define PS_PHASE(i) do {} while (0)
-#define PS_COUNT(i, v) do {} while (0)
-#define PS_PROF_PARAMS
-#define PS_PROF_ARGS
-#endif
-
 // ---------------------------------------------------------------- sweeps
 // best packed key (distance | 255 - id) of every slot's colour over the candidates of the mask: the set bits are walked on the scalar
 // unit, each candidate one broadcast read of the block's table + 3 vector instructions per slot
@@ -335,7 +319,7 @@ __device__ __forceinline__ void ps_scores(const uint32_t (&key)[kSweep], const u
 template <typename StoreLabel>
 __device__ __forceinline__ bool ps_sweep(const uint32_t (&wd)[kSweep], uint32_t base, uint32_t e, uint32_t s0, int lane, const unsigned long long (&nm)[4], uint32_t ncand,
                                          uint32_t cand4, const uint2 *tab, uint32_t K, uint32_t cbk, const uint32_t *__restrict__ cwq, unsigned long long *acc, uint32_t &moved,
-                                         bool agg, StoreLabel store_label PS_PROF_PARAMS) {
+                                         bool agg, StoreLabel store_label) {
     uint32_t key[kSweep], lc[kSweep];
     bool valid[kSweep];
 #pragma unroll
@@ -351,16 +335,14 @@ __device__ __forceinline__ bool ps_sweep(const uint32_t (&wd)[kSweep], uint32_t 
         bool same = true;
 #pragma unroll
         for (int u = 0; u < kSweep; u++) same = same & (!valid[u] | (lc[u] == onlyc));
-        if (__ballot(!same) == 0ull) { PS_PHASE(10); return true; }
+        if (__ballot(!same) == 0ull) return true;
     }
-    PS_PHASE(10);
     uint32_t best[kSweep];
     ps_scores(key, nm, ncand, cand4, tab, best);
-    PS_PHASE(11);
     bool mv[kSweep], any = false;
 #pragma unroll
     for (int u = 0; u < kSweep; u++) { mv[u] = valid[u] & ((best[u] & 255u) != lc[u]); any = any | mv[u]; }
-    if (!__ballot(any)) { PS_PHASE(12); return false; }
+    if (!__ballot(any)) return false;
     any = false;
 #pragma unroll
     for (int u = 0; u < kSweep; u++) {   // (the few whose best candidate is not their own cluster: strictly closer, kmeans.rs:375?)
@@ -369,8 +351,7 @@ __device__ __forceinline__ bool ps_sweep(const uint32_t (&wd)[kSweep], uint32_t 
         mv[u] = mv[u] & ((best[u] >> 8) > (kc >> 8));
         any = any | mv[u];
     }
-    if (!__ballot(any)) { PS_PHASE(12); return false; }
-    PS_PHASE(12);
+    if (!__ballot(any)) return false;
     uint32_t wt[kSweep];
     bool heavy = false;
 #pragma unroll
@@ -383,7 +364,6 @@ __device__ __forceinline__ bool ps_sweep(const uint32_t (&wd)[kSweep], uint32_t 
 #pragma unroll
     for (int u = 0; u < kSweep; u++)
         if (mv[u]) { store_label(base + u * 64 + lane, best[u] & 255u); moved++; }
-    PS_PHASE(13);
     if (agg) {
         static_assert(kSweep == 4, "four slots per lane");
         uint32_t nmv = 0;
@@ -443,7 +423,6 @@ __device__ __forceinline__ bool ps_sweep(const uint32_t (&wd)[kSweep], uint32_t 
             mv[0] = mv[0] & (u != 0); mv[1] = mv[1] & (u != 1); mv[2] = mv[2] & (u != 2); mv[3] = false | (mv[3] & (u != 3));
         }
     }
-    PS_PHASE(14);
     return false;
 }
 
@@ -556,8 +535,6 @@ struct PsArgs {
     uint32_t K, max_skip, agg_iters, test_abort_at, lds_budget;
     uint32_t clean_skip;                  // full schedule: cells none of whose old or new candidates moved are not swept (0: A/B measurements, CNIIC_KM_PS_CLEANSKIP)
     unsigned long long timeout_ticks;
-    unsigned long long *iter_ts;          // block 0's clock (100 MHz) when iteration j's centroids stood, [0] at entry; kPsTsCap entries, or null
-    unsigned long long *blk_ts;           // measuring runs (CNIIC_KM_PS_BLOCK_TRACE): [block][iteration < 128][4] clock at: assign done, flushed, through the barrier, centroids stand
 };
 
 __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
@@ -691,7 +668,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         s_nx = ps_ld(&a.bar->xblocks[x].v);
         s_nxcd = n;
         s_ok = ok;
-        if (blockIdx.x == 0 && a.iter_ts) a.iter_ts[0] = wall_clock64();
     }
     __syncthreads();
     if (!s_ok) {
@@ -699,7 +675,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         return;
     }
     const uint32_t Cres = s_Cres, nslots = s_nslots;
-    if (a.blk_ts && tid == 0) { a.blk_ts[((size_t)blockIdx.x * 128 + 0) * 8 + 7] = C; a.blk_ts[((size_t)blockIdx.x * 128 + 1) * 8 + 7] = cstart[C]; a.blk_ts[((size_t)blockIdx.x * 128 + 2) * 8 + 7] = nslots; }
     const uint32_t row = (uint32_t)lane >> 4, l16 = (uint32_t)lane & 15u;
     // running sums of cluster k = tid (kmeans.rs: the members of every cluster, as sums): registers, the same in every block
     unsigned long long run[5] = {0, 0, 0, 0, 0};
@@ -708,19 +683,12 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     uint32_t j = 0;              // the iteration whose assign step runs
     uint32_t nS = K;             // centroids the last update moved
     unsigned long long reseeds_total = 0, evals_total = 0;
-#ifdef CNIIC_PS_PHASES
-    long long t_ph = clock64();
-    unsigned long long ph_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     for (;;) {
         const bool first = j == 0;
         const bool skip_mode = !first && a.max_skip && nS <= a.max_skip;
-        PS_PHASE(7);
         if (!skip_mode) {
             // ============================================================= FULL schedule: every cell's candidates anew
             ps_build_lists(tab, K, nslots, s_ssup, s_nS, s_lpiv, Sent, wid, lane);
-            if (a.blk_ts && tid == 0 && j < 128) a.blk_ts[((size_t)blockIdx.x * 128 + j) * 8 + 4] = wall_clock64();
-            PS_PHASE(0);
             for (uint32_t i0 = (uint32_t)wid * 4; i0 < C; i0 += kPsWaves * 4) {   // a row of 16 lanes per cell
                 const uint32_t i = i0 + row;
                 if (i < C) {
@@ -778,8 +746,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             }
         }
         __syncthreads();   // the work list is complete
-        if (a.blk_ts && tid == 0 && j < 128) { a.blk_ts[((size_t)blockIdx.x * 128 + j) * 8 + 5] = wall_clock64(); a.blk_ts[((size_t)blockIdx.x * 128 + j) * 8 + 6] = s_qn; }
-        PS_PHASE(1);
         // ------------------------------------------------------------- sweeps: list entry wid, wid + 16, ... is this wave's
         {
             const uint32_t qn = s_qn;
@@ -863,8 +829,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
 #pragma unroll
                     for (int u = 0; u < kSweep; u++) { const uint32_t idx = s + u * 64 + lane; wd[u] = idx < e ? a.pk[gs + (idx - s)] : 0u; }
                 }
-                PS_PHASE(2);
-                PS_COUNT(8, 1);
                 unsigned long long nm[4];
 #pragma unroll
                 for (int w = 0; w < 4; w++)
@@ -877,7 +841,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                 uint32_t *pkc = a.pk + gs;
                 uint32_t *rec = recs + (size_t)kPsRecWords * i;
                 bool uniform = !first;   // every sweep of the cell left through the one-candidate exit: all its points carry that candidate
-                PS_PHASE(3);
                 for (uint32_t base = s; base < e; base += 64 * kSweep) {
                     uint32_t w2[kSweep] = {0, 0, 0, 0};
                     if (base + 64 * kSweep < e) {   // (a cell of more than 256 points: its next sweep's words now)
@@ -889,26 +852,22 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                             for (int u = 0; u < kSweep; u++) { const uint32_t idx = base + 64 * kSweep + u * 64 + lane; w2[u] = idx < e ? pkc[idx - s] : 0u; }
                         }
                     }
-                    PS_PHASE(4);
                     if (res) {
                         auto st = [&](uint32_t idx, uint32_t l) { reinterpret_cast<uint8_t *>(pts)[4 * idx + 3] = (uint8_t)l; };
                         if (first) ps_sweep_first(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, st);
-                        else uniform = ps_sweep(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st PS_PROF_ARGS) && uniform;
+                        else uniform = ps_sweep(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st) && uniform;
                     } else {
                         auto st = [&](uint32_t idx, uint32_t l) { reinterpret_cast<uint8_t *>(pkc)[4 * (size_t)(idx - s) + 3] = (uint8_t)l; };
                         if (first) ps_sweep_first(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, st);
-                        else uniform = ps_sweep(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st PS_PROF_ARGS) && uniform;
+                        else uniform = ps_sweep(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st) && uniform;
                     }
-                    PS_PHASE(5);
 #pragma unroll
                     for (int u = 0; u < kSweep; u++) wd[u] = w2[u];
                 }
                 if (lane == 0) rec[1] = (r1 & ~kPsUlMask) | (uniform && ncand == 1 ? cand4 & 255u : kPsUlMask);
                 evals += (unsigned long long)(e - s) * (ncand + 1);
-                PS_PHASE(6);
             }
         }
-        PS_PHASE(9);
         // ------------------------------------------------------------- this iteration's deltas leave the block
         moved = wave_reduce_sum(moved);
         if (lane == 0) {
@@ -917,7 +876,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         }
         moved = 0; evals = 0;
         __syncthreads();
-        if (a.blk_ts && tid == 0 && j < 128) a.blk_ts[((size_t)blockIdx.x * 128 + j) * 8 + 0] = wall_clock64();
         unsigned long long *Pcur = a.partials + (size_t)(j % 3) * kPsPartWords;
         for (uint32_t i = tid; i < 5 * K; i += kPsThreads) {
             const unsigned long long v = acc[i];
@@ -930,7 +888,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's atomics have been performed before its block arrives
         __syncthreads();
-        if (a.blk_ts && tid == 0 && j < 128) a.blk_ts[((size_t)blockIdx.x * 128 + j) * 8 + 1] = wall_clock64();
         if (tid == 0) {
             bool ok = ps_barrier_xcd(a.bar, ps_xcc_id(), s_nx, s_nxcd, a.timeout_ticks);
 #ifdef CNIIC_TESTING
@@ -943,7 +900,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             if (tid == 0) { a.cold->exit.status = kPsStatusAborted; __threadfence_system(); }
             return;
         }
-        if (a.blk_ts && tid == 0 && j < 128) a.blk_ts[((size_t)blockIdx.x * 128 + j) * 8 + 2] = wall_clock64();
         j++;
         // ------------------------------------------------------------- finish iteration j - 1: Point::mean for ColorCount (clusterc.rs:83-113)
         // + empty-cluster reseed (kmeans.rs:110-137), redundantly in every block: the sums are the same everywhere
@@ -983,7 +939,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             s_pev = ps_aread(&Pcur[5 * (size_t)K + 1]);
         }
         __syncthreads();
-        if (a.blk_ts && tid == 0 && j <= 128) a.blk_ts[((size_t)blockIdx.x * 128 + j - 1) * 8 + 3] = wall_clock64();
         const unsigned long long changed = s_changed;
         nS = s_nmoved;
         reseeds_total += s_reseed;
@@ -993,7 +948,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             KmDevState *sw = a.st_rw;
             sw->changed_ring[(j - 1) % kHistRing] = changed;
             sw->nmoved_ring[(j - 1) % kHistRing] = nS;
-            if (a.iter_ts && j < kPsTsCap) a.iter_ts[j] = wall_clock64();
             if (fin) {
                 sw->moved_last = changed; sw->reseeds = reseeds_total; sw->active = s_active; sw->pair_evals = evals_total; sw->iter = j; sw->done = 1;
                 PsExit *x = &a.cold->exit;
@@ -1002,11 +956,6 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         }
         if (fin) break;   // converged (kmeans.rs:26-32) or the iteration cap: every block sees the same sums and leaves together
     }
-#ifdef CNIIC_PS_PHASES
-    if (lane == 0)
-        for (int i = 0; i < 16; i++)
-            if (ph_[i]) atomicAdd(&g_ps_phase[i], ph_[i]);
-#endif
     // ----------------------------------------------------------------- results
     if (blockIdx.x == 0 && tid < K) {
         const PsCold *cd = a.cold;
@@ -1108,9 +1057,6 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     memset(cold, 0, sizeof *cold);
     PsExit *xh = &cold->exit;
     uint8_t *ar = s->ps_arena.as<uint8_t>();
-    DevBuf ts;
-    const bool want_ts = s->profile || test_env("CNIIC_KM_PS_TRACE");
-    if (want_ts) { CNIIC_HIP_TRY(c, ts.alloc((uint64_t)kPsTsCap * 8)); CNIIC_HIP_TRY(c, hipMemsetAsync(ts.p, 0, (uint64_t)kPsTsCap * 8, c->stream)); }
     PsArgs a{};
     a.ckeys = s->ckeys.as<uint32_t>(); a.cweight = s->cweight.as<uint32_t>(); a.labels = s->labels.as<uint8_t>();
     a.ne_cell = s->ne_cell.as<uint32_t>(); a.ne_start = s->ne_start.as<uint32_t>();
@@ -1121,7 +1067,7 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     cold->cconst_g = s->cconst.as<uint2>(); cold->cent_g = s->cent.as<uint32_t>(); cold->members_out = s->members_last.as<uint64_t>(); cold->wsum_out = s->wsum_last.as<uint64_t>();
     cold->keys = s->keys; cold->gx = s->gidx; cold->seed = s->seed; cold->U = s->gidx.bits ? s->gidx.U : s->U;
     a.st_rw = s->dstate.as<KmDevState>(); a.cold = cold; a.max_iters = s->max_iters;
-    a.K = s->K; a.max_skip = s->no_skip ? 0u : s->max_skip; a.agg_iters = s->agg_launches;
+    a.K = s->K; a.max_skip = s->no_skip ? 0u : s->max_skip; a.agg_iters = kAggLaunches;
     a.test_abort_at = 0;
     if (const char *e = test_env("CNIIC_TEST_PS_ABORT_AT")) a.test_abort_at = (uint32_t)atoi(e);
     a.clean_skip = 1;
@@ -1129,10 +1075,6 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     uint64_t tmo_ms = 2000;
     if (const char *e = test_env("CNIIC_KM_PS_TIMEOUT_MS")) tmo_ms = (uint64_t)atoll(e);
     a.timeout_ticks = tmo_ms * 100000ull;   // 100 MHz
-    a.iter_ts = want_ts ? ts.as<unsigned long long>() : nullptr;
-    DevBuf bts;
-    const char *bt_path = test_env("CNIIC_KM_PS_BLOCK_TRACE");
-    if (bt_path) { CNIIC_HIP_TRY(c, bts.alloc((uint64_t)G * 128 * 8 * 8)); CNIIC_HIP_TRY(c, hipMemsetAsync(bts.p, 0, (uint64_t)G * 128 * 8 * 8, c->stream)); a.blk_ts = bts.as<unsigned long long>(); }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (s->profile) { CNIIC_HIP_TRY(c, hipEventCreate(&e0)); CNIIC_HIP_TRY(c, hipEventCreate(&e1)); }
     hipExtLaunchKernelGGL(k_rgbw_persist, dim3((uint32_t)G), dim3(kPsThreads), kPsDynBytes, c->stream, e0, e1, 0, a);
@@ -1140,7 +1082,7 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     // The caller of an encode goes straight on to the labels of the pixels and to fetching the result block (cc_finish): nothing of
     // that needs the host to have seen how the launch ended, and the look cost the stream 40 us (a wait, a copy, the next launch's
     // way to the GPU).  The verdict is read where the result block is (km_rgbw_result_end -> km_rgbw_persistent_verdict).
-    if (may_defer && !s->profile && !want_ts && !bt_path) {
+    if (may_defer && !s->profile) {
         s->ps_pending = true;
         s->ps_hold = release;
         *ran = true;
@@ -1167,53 +1109,6 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
         KernelTime &ki = c->ktimes["kmeans_rgbw_persist_iters"];   // (launches: the iterations the launch ran, for per-iteration figures)
         ki.ms += ms; ki.launches += xh->iter;
     }
-    if (want_ts) {
-        std::vector<unsigned long long> t(kPsTsCap);
-        CNIIC_HIP_TRY(c, hipMemcpy(t.data(), ts.p, (size_t)kPsTsCap * 8, hipMemcpyDeviceToHost));
-        if (const char *path = test_env("CNIIC_KM_PS_TRACE")) {
-            KmDevState hf;
-            CNIIC_HIP_TRY(c, hipMemcpy(&hf, s->dstate.p, sizeof hf, hipMemcpyDeviceToHost));
-            if (FILE *f = fopen(path, "w")) {
-                fprintf(f, "iteration,us,centroids_moved_before,points_moved\n");
-                for (uint64_t i = 0; i < xh->iter && i + 1 < kPsTsCap; i++) {
-                    const bool in_ring = xh->iter - i <= kHistRing;
-                    const bool prev_in_ring = i >= 1 && xh->iter - (i - 1) <= kHistRing;
-                    fprintf(f, "%llu,%.2f,%lld,%lld\n", (unsigned long long)i, (t[i + 1] - t[i]) / 100.0, prev_in_ring ? (long long)hf.nmoved_ring[(i - 1) % kHistRing] : -1ll,
-                            in_ring ? (long long)hf.changed_ring[i % kHistRing] : -1ll);
-                }
-                fclose(f);
-            }
-        }
-    }
-    if (bt_path) {   // per block and iteration: microseconds in the assign step, the flush, the barrier, the update (the clock starts where the previous iteration's centroids stood)
-        std::vector<unsigned long long> b((size_t)G * 128 * 8);
-        CNIIC_HIP_TRY(c, hipMemcpy(b.data(), bts.p, b.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(bt_path, "w")) {
-            fprintf(f, "# block cells points lists:");
-            for (int g = 0; g < G; g++) fprintf(f, " %d %llu %llu %llu;", g, b[((size_t)g * 128 + 0) * 8 + 7], b[((size_t)g * 128 + 1) * 8 + 7], b[((size_t)g * 128 + 2) * 8 + 7]);
-            fprintf(f, "\n");
-            fprintf(f, "block,iteration,assign_us,flush_us,barrier_us,update_us,lists_us,classify_us,sweeps_us,cells_swept\n");
-            for (int g = 0; g < G; g++)
-                for (uint64_t i = 1; i < xh->iter && i < 128; i++) {
-                    const unsigned long long *r = &b[((size_t)g * 128 + i) * 8], start = b[((size_t)g * 128 + i - 1) * 8 + 3];
-                    const unsigned long long l_end = r[4] ? r[4] : start;   // (skip schedule: no lists)
-                    fprintf(f, "%d,%llu,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f,%llu\n", g, (unsigned long long)i, (r[0] - start) / 100.0, (r[1] - r[0]) / 100.0, (r[2] - r[1]) / 100.0, (r[3] - r[2]) / 100.0,
-                            (l_end - start) / 100.0, (r[5] - l_end) / 100.0, (r[0] - r[5]) / 100.0, r[6]);
-                }
-            fclose(f);
-        }
-    }
-#ifdef CNIIC_PS_PHASES
-    {   // (a measuring build: run it with the per-iteration trace or KM_PROFILE, which wait for the launch)
-        unsigned long long ph[16], zero[16] = {0};
-        CNIIC_HIP_TRY(c, hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_ps_phase), sizeof ph));
-        CNIIC_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(g_ps_phase), zero, sizeof zero));
-        const double w = (double)G * kPsWaves;
-        fprintf(stderr, "persist phases (wave clocks per wave, %llu iterations): lists %.0f classify %.0f | draw+desc %.0f mask %.0f words %.0f sweep %.0f tail %.0f wait-for-others %.0f | sync+update %.0f | cells swept per wave %.1f"
-                        " | in the sweeps: unpack+exit %.0f scores %.0f movers? %.0f labels %.0f booking %.0f\n",
-                (unsigned long long)xh->iter, ph[0] / w, ph[1] / w, ph[2] / w, ph[3] / w, ph[4] / w, ph[5] / w, ph[6] / w, ph[9] / w, ph[7] / w, ph[8] / w, ph[10] / w, ph[11] / w, ph[12] / w, ph[13] / w, ph[14] / w);
-    }
-#endif
     *ran = true;
     return CNIIC_OK;
 }

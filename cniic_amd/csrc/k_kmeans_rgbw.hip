@@ -391,13 +391,9 @@ __device__ __forceinline__ uint32_t build_candidates(const uint2 *list, uint32_t
 // The 64 x kSweep points from `from` on (those below `end`; the others read as 0) as BUFFER loads: the range check is the hardware's, and
 // one load is one vector instruction with an immediate offset -- as flat loads every one of the twelve cost an add, a compare, a select
 // and a 64-bit address (about 60 of a sweep's 120 vector instructions; round 4).  from / end are wave-uniform.
-#ifndef CNIIC_RGBW_BUFLOADS
-#define CNIIC_RGBW_BUFLOADS 1
-#endif
 template <typename LabelT, bool NOWT = false>
 __device__ __forceinline__ void load_points(const uint32_t *__restrict__ ckeys, const LabelT *__restrict__ labels, const uint32_t *__restrict__ cweight,
                                             uint32_t from, uint32_t end, int lane, uint32_t (&p)[kSweep], uint32_t (&cur)[kSweep], uint32_t (&wt)[kSweep]) {
-#if CNIIC_RGBW_BUFLOADS
     // (the descriptors keep the ARRAY's base -- scalar registers the kernel holds anyway -- and end at `end`; the lane's offset carries `from`:
     // a descriptor per range start cost nine more live scalar registers and spilled)
     const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)from), e = (uint32_t)__builtin_amdgcn_readfirstlane((int)end);
@@ -420,15 +416,6 @@ __device__ __forceinline__ void load_points(const uint32_t *__restrict__ ckeys, 
 #pragma unroll
         for (int u = 0; u < kSweep; u++) wt[u] = 0u;
     }
-#else
-#pragma unroll
-    for (int u = 0; u < kSweep; u++) {
-        const uint32_t q = from + u * 64 + lane;
-        p[u] = q < end ? ckeys[q] : 0u;
-        cur[u] = q < end ? (uint32_t)labels[q] : 0u;
-        wt[u] = (!NOWT && q < end) ? cweight[q] : 0u;
-    }
-#endif
 }
 
 // one sweep: the 64 x kSweep points starting at `base` (those < e) against the candidate strip.
@@ -1305,8 +1292,6 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
     s->cells = !(opts && (opts->flags & CNIIC_KM_BRUTE_FORCE));
     s->profile = opts && (opts->flags & CNIIC_KM_PROFILE);
     s->no_skip = opts && (opts->flags & CNIIC_KM_NO_SKIP);
-    if (const char *al = test_env("CNIIC_KM_AGG_LAUNCHES")) s->agg_launches = (uint32_t)atoi(al);
-    if (const char *bb = test_env("CNIIC_KM_BIG_BLOCKS_FROM")) s->big_blocks_from = (uint32_t)atoi(bb);
     if (const char *ms = test_env("CNIIC_KM_MAXSKIP")) s->max_skip = std::min<uint32_t>((uint32_t)atoi(ms), kMaxMovedSkip);
     // (every knob of the loop is read here, once: getenv() per launch raced with tools that set variables between contexts)
     if (const char *fa = test_env("CNIIC_TEST_FAIL_AT_LAUNCH")) s->fail_at = atol(fa);
@@ -1381,15 +1366,12 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
         DevBuf count, cursor, cell_tot;
         KM_ALLOC(count, (uint64_t)kNumCells * 4);
         KM_ALLOC(cell_tot, (uint64_t)kCellGroups * 8 * 2);
-        uint32_t fixed_cost = kCellFixedCost, sweep_cost = kCellSweepCost;
-        if (const char *ev = test_env("CNIIC_CELL_COST")) fixed_cost = (uint32_t)atoi(ev);  // tuning knobs
-        if (const char *ev = test_env("CNIIC_CELL_SWEEP_COST")) sweep_cost = (uint32_t)atoi(ev);
         if (points_follow) {
             // the caller's partition (k_points.hip) writes ckeys / cweight / labels itself, from cell_start
             hipLaunchKernelGGL(k_cell_totals, dim3(kCellGroups), dim3(64), 0, c->stream, cell_count_d, cell_tot.as<uint2>());
             hipLaunchKernelGGL(k_cell_scan, dim3(kCellGroups), dim3(64), 0, c->stream, cell_count_d, (const uint2 *)cell_tot.as<uint2>(), s->cell_start.as<uint32_t>(),
                                (uint32_t *)nullptr, s->ne_cell.as<uint32_t>(), s->ne_start.as<uint32_t>(), s->ne_cost.as<uint32_t>(),
-                               s->ne_count.as<uint32_t>(), fixed_cost, sweep_cost);
+                               s->ne_count.as<uint32_t>(), kCellFixedCost, kCellSweepCost);
         } else if (rank_table_d) {
             // codec path: the dense colour table (key -> canonical rank + 1) is walked cell by cell
             const uint32_t *cnt = cell_count_d;  // counted by the compaction on its way, else one more walk of the table
@@ -1400,7 +1382,7 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
             hipLaunchKernelGGL(k_cell_totals, dim3(kCellGroups), dim3(64), 0, c->stream, cnt, cell_tot.as<uint2>());
             hipLaunchKernelGGL(k_cell_scan, dim3(kCellGroups), dim3(64), 0, c->stream, cnt, (const uint2 *)cell_tot.as<uint2>(), s->cell_start.as<uint32_t>(),
                                (uint32_t *)nullptr, s->ne_cell.as<uint32_t>(), s->ne_start.as<uint32_t>(), s->ne_cost.as<uint32_t>(),
-                               s->ne_count.as<uint32_t>(), fixed_cost, sweep_cost);
+                               s->ne_count.as<uint32_t>(), kCellFixedCost, kCellSweepCost);
             if (s->wide)
                 hipLaunchKernelGGL(k_cells_write_tbl<uint16_t>, dim3(kNumCells), dim3(512), 0, c->stream, rank_table_d, weight_d,
                                    s->cell_start.as<uint32_t>(), Ulist, K, s->ckeys.as<uint32_t>(), s->cweight.as<uint32_t>(),
@@ -1418,7 +1400,7 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
             hipLaunchKernelGGL(k_cell_totals, dim3(kCellGroups), dim3(64), 0, c->stream, count.as<uint32_t>(), cell_tot.as<uint2>());
             hipLaunchKernelGGL(k_cell_scan, dim3(kCellGroups), dim3(64), 0, c->stream, count.as<uint32_t>(), (const uint2 *)cell_tot.as<uint2>(), s->cell_start.as<uint32_t>(),
                                cursor.as<uint32_t>(), s->ne_cell.as<uint32_t>(), s->ne_start.as<uint32_t>(), s->ne_cost.as<uint32_t>(),
-                               s->ne_count.as<uint32_t>(), fixed_cost, sweep_cost);
+                               s->ne_count.as<uint32_t>(), kCellFixedCost, kCellSweepCost);
             hipLaunchKernelGGL(k_cell_scatter, dim3(g), dim3(256), 0, c->stream, keys_d, weight_d, U, cursor.as<uint32_t>(),
                                s->ckeys.as<uint32_t>(), s->cweight.as<uint32_t>(), s->crank.as<uint32_t>());
             // init_assignment (kmeans.rs:61-78) by canonical rank
@@ -1533,16 +1515,16 @@ static void launch_assign(KmRgbwState *s, hipEvent_t ev_start = nullptr, hipEven
                                (const uint32_t *)s->ne_start.as<uint32_t>(), (const uint32_t *)s->wfirst.as<uint32_t>(), s->shard, s->K,
                                (const uint2 *)s->cconst.as<uint2>(), s->labels.as<uint16_t>(), part, st, cs, fz);
         } else {
-            // The same wave ranges in blocks of 12 waves, two per CU, once the run has settled (from launch big_blocks_from):
+            // The same wave ranges in blocks of 12 waves, two per CU, once the run has settled (from launch kBigBlocksFrom):
             // measured on the headline encode, the first ten launches are 5-13 us faster in blocks of 8 (three per CU), every later
             // one 1-3 us faster in blocks of 12.  (The ranges are per wave, so regrouping them needs nothing but a multiple of 12.)
-            const bool big = kCellWaves == 8 && fz.on && fz.launch_no >= s->big_blocks_from && (s->nblocks * (uint32_t)kCellWaves) % kCellWavesBig == 0;
+            const bool big = fz.on && fz.launch_no >= kBigBlocksFrom && (s->nblocks * (uint32_t)kCellWaves) % kCellWavesBig == 0;
             const uint32_t wpb = big ? kCellWavesBig : (uint32_t)kCellWaves, nblk = s->nblocks * (uint32_t)kCellWaves / wpb;
             const size_t lds = (size_t)s->K * (5 * 8 + 8) + (size_t)wpb * (km_scap(s->K) + km_ccap(s->K)) * 8 + (size_t)wpb * ((s->K + 63) / 64) * 8;
             auto kern = big ? k_rgbw_assign_cells<uint8_t, 8, kCellWavesBig, 0>
                         : !fz.on ? k_rgbw_assign_cells<uint8_t, 8, kCellWaves, -1>
                         : fz.launch_no == 0 ? k_rgbw_assign_cells<uint8_t, 8, kCellWaves, 1>
-                        : fz.launch_no <= s->agg_launches ? k_rgbw_assign_cells<uint8_t, 8, kCellWaves, 2>
+                        : fz.launch_no <= kAggLaunches ? k_rgbw_assign_cells<uint8_t, 8, kCellWaves, 2>
                         : k_rgbw_assign_cells<uint8_t, 8, kCellWaves, 0>;
             hipExtLaunchKernelGGL(kern, dim3(nblk), dim3(64 * wpb), (uint32_t)lds,
                                   c->stream, ev_start, ev_stop, 0, (const uint32_t *)s->ckeys.as<uint32_t>(),
@@ -1770,20 +1752,14 @@ static int km_rgbw_run_loop(KmRgbwState *s, Comm *cm, bool may_defer) {
         const char *names[5] = {"first", "full", "skip", "final-update", "no-op"};
         double cms[5] = {0, 0, 0, 0, 0};
         uint64_t cn[5] = {0, 0, 0, 0, 0};
-        FILE *f = nullptr;
-        if (const char *path = test_env("CNIIC_KM_LAUNCH_TRACE")) f = fopen(path, "w");  // one line per launch: number, duration, class, what the iteration before it moved
-        if (f) fprintf(f, "launch,us,class,centroids_moved_before,points_moved\n");
         for (size_t i = 0; i < lt.used / 2; i++) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, lt.ev[2 * i], lt.ev[2 * i + 1]);
             const bool prev_in_ring = i >= 1 && i - 1 < hf.iter && hf.iter - (i - 1) <= kHistRing;
             const long long nmv = prev_in_ring ? (long long)hf.nmoved_ring[(i - 1) % kHistRing] : -1;
-            const bool in_ring = i < hf.iter && hf.iter - i <= kHistRing;
             int cls = i >= working ? 4 : i == 0 ? 0 : (s->fused && i == (size_t)hf.iter) ? 3 : (nmv >= 0 && nmv <= (long long)s->max_skip && !s->no_skip) ? 2 : 1;
             cms[cls] += ms; cn[cls]++;
-            if (f) fprintf(f, "%zu,%.2f,%s,%lld,%lld\n", i, ms * 1e3, names[cls], nmv, in_ring ? (long long)hf.changed_ring[i % kHistRing] : -1ll);
         }
-        if (f) fclose(f);
         for (int k = 0; k < 5; k++) {
             KernelTime &kc = c->ktimes[std::string("kmeans_rgbw_assign_") + names[k]];
             kc.ms += cms[k]; kc.launches += cn[k];

@@ -36,20 +36,14 @@
 namespace cniic {
 
 constexpr int kTW = 64, kTH = 16;          // tile: 64 x 16 pixels = one wave, 16 pixels (a column) per lane
-#ifndef CNIIC_XY_BUFLOADS
-#define CNIIC_XY_BUFLOADS 1
-#endif
-#ifndef CNIIC_XY_STY
-#define CNIIC_XY_STY 4                     // (measuring builds: 2 = super-tiles of 4 x 2 tiles, 8-wave blocks, two per CU while K <= 1024 -- NOTES D)
-#endif
-constexpr int kSTX = 4, kSTY = CNIIC_XY_STY;  // super-tile: 4 x 4 tiles = one block
+constexpr int kSTX = 4, kSTY = 4;          // super-tile: 4 x 4 tiles = one block
 constexpr int kXWaves = kSTX * kSTY;
 constexpr int kXThreads = 64 * kXWaves;    // 1024
 constexpr int kXRows = 4;                  // rows of a tile evaluated together (4 groups per tile)
 constexpr int kXUS = kXWaves / 4;          // dirty tiles in work at a time: wave v takes row group v & 3 of dirty tiles number v >> 2, (v >> 2) + kXUS, ...
-constexpr uint32_t kXMaxK = kSTY == 4 ? 4096 : 2048;
+constexpr uint32_t kXMaxK = 4096;
 constexpr int kXMaxR = kXMaxK / kXThreads; // centroids per thread in the super-tile pass (4)
-constexpr uint32_t kSCap = kSTY == 4 ? 1024 : 512;  // super-tile list capacity; beyond it the super-tile is brute-forced
+constexpr uint32_t kSCap = 1024;  // super-tile list capacity; beyond it the super-tile is brute-forced
 constexpr uint32_t kXMaxMovedSkip = 512;   // skip schedule when at most this many centroids moved
 constexpr uint64_t kSuperPx = (uint64_t)kSTX * kTW * kSTY * kTH;
 
@@ -221,19 +215,7 @@ struct TileState {              // per tile, carried between iterations
     uint32_t dyn;               // the loop with the folded-in update: while at least this many centroids move (0: never), super-tiles beyond a block's first are
                                 // drawn from a counter (word 6 K + 2 of the launch's sums)
     uint32_t sup_cap;           // ... at most this many per block: its u32 accumulators hold what that many super-tiles can add (xy_create: per_block_max)
-    uint32_t tl_launch;         // measuring builds (-DCNIIC_XY_PHASES): 1 + the launch whose blocks write their timeline (CNIIC_XY_TL_LAUNCH)
 };
-
-// -DCNIIC_XY_PHASES: wave-clock totals per phase of k_xy_assign (a measuring build, never the shipped one)
-#ifdef CNIIC_XY_PHASES
-__device__ unsigned long long g_xy_tl[256][8];   // one launch (CNIIC_XY_TL_LAUNCH): per block the 100 MHz clock at entry, set-up loads out, prologue done, loop done, flush done; [5] super-tiles taken, [6] dirty ones
-__device__ unsigned long long g_xy_phase[12];
-#define XY_PHASE(i) do { const long long now_ = clock64(); ph_[i] += (unsigned long long)(now_ - t_ph); t_ph = now_; } while (0)
-#define XY_COUNT(i, v) do { ph_[i] += (unsigned long long)(v); } while (0)
-#else
-#define XY_PHASE(i) do {} while (0)
-#define XY_COUNT(i, v) do {} while (0)
-#endif
 
 __host__ __device__ constexpr uint32_t xy_acc_words(uint32_t K) { return (6 * K + 3) & ~3u; }  // keeps the int4 arrays aligned
 
@@ -311,15 +293,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
             }
         }
     }
-#ifdef CNIIC_XY_PHASES
-    const bool tl_on_ = fz.on && ts.tl_launch == fz.launch_no + 1 && blockIdx.x < 256 && threadIdx.x == 0;
-    unsigned long long tl_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (tl_on_) tl_[0] = wall_clock64();
-    long long t_ph = clock64();
-    unsigned long long ph_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    __shared__ unsigned long long s_ph[12];
-    if (threadIdx.x < 12) s_ph[threadIdx.x] = 0;
-#endif
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const bool first = fz.on ? fz.launch_no == 0 : st->iter == 0;
     uint32_t nS = fz.on ? K : ts.moved[0];
@@ -381,9 +354,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
             }
         }
         if (done) return;   // a launch past convergence
-#ifdef CNIIC_XY_PHASES
-        if (tl_on_) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tl_[1] = wall_clock64(); }
-#endif
         __syncthreads();    // (the accumulators and counters above are in place)
 #pragma unroll
         for (int i = 0; i < kXMaxR; i++) {
@@ -441,16 +411,10 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
         nS = s_nmoved;
     }
     const bool skip_mode = !first && !brute && nS <= ts.max_moved;
-    XY_PHASE(0);
-#ifdef CNIIC_XY_PHASES
-    if (tl_on_) tl_[2] = wall_clock64();
-#endif
 
     const uint64_t npix = (uint64_t)w * h;
-#if CNIIC_XY_BUFLOADS
     const __amdgpu_buffer_rsrc_t rs_rgb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(rgb), 0, (int)(3u * (uint32_t)npix), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_lab = __builtin_amdgcn_make_buffer_rsrc(labels, 0, (int)(2u * (uint32_t)npix), 0x00020000);
-#endif
     uint32_t par = 0, sit = 0;
     // Which super-tiles a block takes.  Statically: every gridDim-th.  The loop with the folded-in update, while centroids still move
     // (dyn): whatever the launch's counter hands out next -- the dirty tiles lie in patches of the image, and a block that met four
@@ -555,9 +519,7 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
         // clean tile works for its neighbours instead of waiting for them.
         // (s_dirty alternates between two copies: with no dirty tile there is no second barrier before the next write)
         if (lane == 0) s_dirty[par][wv] = dirty ? 1u : 0u;
-        XY_PHASE(1);
         __syncthreads();  // (also frees S and the strips of the previous super-tile)
-        XY_PHASE(2);
         const uint32_t dm16 = (uint32_t)__ballot(s_dirty[par][lane & (kXWaves - 1)] != 0u) & ((1u << kXWaves) - 1u);  // wave-uniform
         const uint32_t nd = (uint32_t)__popc(dm16);
         if (nd == 0) continue;
@@ -570,7 +532,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
         // pixel (lane, row j) of the unit: x = first column of the tile + lane, y = first row of the tile + g4 + j
         auto load_unit = [&](uint32_t slot, uint32_t (&p)[kXRows], uint32_t (&c)[kXRows]) {
             const uint32_t ux = (stx + (slot & (kSTX - 1))) * kTW + lane, uy0 = (sty + slot / kSTX) * kTH + g4;
-#if CNIIC_XY_BUFLOADS
             // (round 4) buffer loads: a pixel outside the image gets an offset outside the buffer and reads as 0 -- no exec mask per row -- and
             // a pixel's 32-bit index is its offset (N <= 2^28).  The image's last pixel, whose dword would end a byte behind the buffer, reads
             // the dword a byte earlier and shifts.
@@ -583,17 +544,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
                 p[j] = key_from_le24(last ? v >> 8 : v);
                 c[j] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs_lab, (int)(in ? 2u * idx : 0xffffffffu), 0, 0);
             }
-#else
-#pragma unroll
-            for (int j = 0; j < kXRows; j++) {
-                p[j] = 0; c[j] = 0;
-                if (ux < w && uy0 + j < h) {
-                    const uint64_t idx = (uint64_t)(uy0 + j) * w + ux;
-                    p[j] = rgb_key_at(rgb, idx, npix);
-                    c[j] = labels[idx];
-                }
-            }
-#endif
         };
         // the first unit's pixels and labels are requested now and arrive while the block builds S
         if ((wv >> 2) < nd) load_unit(nth_set_bit(dm16, wv >> 2), px[0], cur[0]);
@@ -652,10 +602,8 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
             nSl = s_n;
             s_over = nSl > kSCap;
         }
-        XY_PHASE(3);
         // ---- candidate strip of this wave's own tile, if dirty: pivot = member of S nearest the tile's box centre,
         // then the dominance test over S
-        if (dirty) XY_COUNT(7, 1);
         if (dirty && !s_over) {
             uint32_t bd = 0xffffffffu, be = 0;
             for (uint32_t e = lane; e < nSl; e += 64) {
@@ -699,9 +647,7 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
             const unsigned long long v = !dirty ? mword : s_over ? ~0ull : my_mask[lane];
             if (v) atomicOr(&s_smask[lane], v);
         }
-        XY_PHASE(4);
         __syncthreads();  // every dirty tile's strip is in LDS
-        XY_PHASE(2);
         if (wv == 0 && lane < MW) ts.smask[(size_t)sup * MW + lane] = s_smask[lane];
 
         // ---- assign, one unit at a time; the next unit's pixels and labels are in flight meanwhile
@@ -712,10 +658,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
             const uint32_t (&p)[kXRows] = px[r & 1];
             const uint32_t (&c)[kXRows] = cur[r & 1];
             const uint32_t slot = nth_set_bit(dm16, ui);
-#ifdef CNIIC_XY_PHASES
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            XY_PHASE(8);
-#endif
             if (ui + kXUS < nd) load_unit(nth_set_bit(dm16, ui + kXUS), px[(r + 1) & 1], cur[(r + 1) & 1]);
             const uint32_t ux0 = (stx + (slot & (kSTX - 1))) * kTW, uy0 = (sty + slot / kSTX) * kTH + g4;
             if (uy0 >= h) continue;  // wave-uniform: the tile ends above this row group
@@ -762,10 +704,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
                     }
                 }
             }
-#ifdef CNIIC_XY_PHASES
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            XY_PHASE(9);
-#endif
 #pragma unroll
             for (int j = 0; j < kXRows; j++) {
                 const bool ok = okx && (uint32_t)j < nrows;
@@ -817,13 +755,8 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
             }
             if (lane == 0) evals += (unsigned long long)(ncand + 1) * ucols * nrows;
         }
-        XY_PHASE(5);
     }
-#ifdef CNIIC_XY_PHASES
-    if (tl_on_) { tl_[3] = wall_clock64(); tl_[5] = sit; }
-#endif
     __syncthreads();
-    XY_PHASE(2);
     // the host sizes the grid so that one block's pixels * max coordinate stays below 2^31: one flush at the end
     for (uint32_t i = threadIdx.x; i < 6 * K; i += kXThreads) {
         const uint32_t v = acc[i];
@@ -841,14 +774,6 @@ __global__ __launch_bounds__(kXThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
         if (moved) atomicAdd(&partials[6 * (size_t)K], (unsigned long long)moved);
         if (s_evals) atomicAdd(&partials[6 * (size_t)K + 1], s_evals);
     }
-    XY_PHASE(6);
-#ifdef CNIIC_XY_PHASES
-    if (tl_on_) { tl_[4] = wall_clock64(); for (int i = 0; i < 8; i++) g_xy_tl[blockIdx.x][i] = tl_[i]; }
-    if (lane == 0)
-        for (int i = 0; i < 12; i++) atomicAdd(&s_ph[i], ph_[i]);
-    __syncthreads();
-    if (threadIdx.x < 12) atomicAdd(&g_xy_phase[threadIdx.x], s_ph[threadIdx.x]);
-#endif
 }
 
 // Point::mean for ColorPos (clusterc.rs:215-247) + empty-cluster reseed (kmeans.rs:110-137).
@@ -963,7 +888,7 @@ static int xy_create(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint3
     const uint32_t MW = (K + 63) / 64;
     // LDS budget (153 KiB dynamic): accumulators, S, the moved list, the masks, then the centroid table if it fits next
     // to at least 64 candidates per wave, and the per-wave strips take what is left (up to 256 entries each)
-    const size_t lds_max = (kSTY == 4 ? 153 : 73) * 1024;  // (160 KiB less the kernel's static arrays: 6.2 KiB with the super-tile filter's lists and the order of issue)
+    const size_t lds_max = 153 * 1024;  // (160 KiB less the kernel's static arrays: 6.2 KiB with the super-tile filter's lists and the order of issue)
     size_t fixed = (size_t)xy_acc_words(K) * 4 + (size_t)kSCap * 18 + (size_t)kXMaxMovedSkip * 16 + (size_t)kXWaves * MW * 8;
     s.use_tab = fixed + (size_t)K * 16 + (size_t)kXWaves * 64 * 18 <= lds_max;
     if (s.use_tab) fixed += (size_t)K * 16;
@@ -1043,8 +968,7 @@ static int xy_assign(KmXyState &s, bool fused = false) {
                        part, s.dstate.as<KmDevState>(), s.wcap, s.use_tab ? 1 : 0, s.brute ? 1 : 0,
                        TileState{s.tile_box.as<uint2>(), s.super_box.as<uint2>(), s.tile_piv.as<int4>(), s.tile_mask.as<unsigned long long>(),
                                  s.moved_list.as<uint32_t>(), s.no_skip ? 0u : kXMaxMovedSkip, s.sup_piv.as<uint32_t>(),
-                                 s.sup_mask.as<unsigned long long>(), s.dyn, s.sup_cap,
-                                 test_env("CNIIC_XY_TL_LAUNCH") ? (uint32_t)atoi(test_env("CNIIC_XY_TL_LAUNCH")) + 1u : 0u}, fz);
+                                 s.sup_mask.as<unsigned long long>(), s.dyn, s.sup_cap}, fz);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }
@@ -1086,28 +1010,6 @@ int km_xyrgb_run(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t 
         if (have && hst.done) break;
     }
     timer.stop(hst.iter);
-#ifdef CNIIC_XY_PHASES
-    {
-        unsigned long long ph[12], zero[12] = {0};
-        CNIIC_HIP_TRY(c, hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_xy_phase), sizeof ph));
-        CNIIC_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(g_xy_phase), zero, sizeof zero));
-        if (test_env("CNIIC_XY_TL_LAUNCH")) {
-            static unsigned long long tl[256][8];
-            CNIIC_HIP_TRY(c, hipMemcpyFromSymbol(tl, HIP_SYMBOL(g_xy_tl), sizeof tl));
-            unsigned long long t0 = ~0ull;
-            for (uint32_t b = 0; b < s.nblocks && b < 256; b++) if (tl[b][0]) t0 = std::min(t0, tl[b][0]);
-            const char *names[5] = {"entry", "set-up loads back", "prologue done", "super-tile loop done", "flush done"};
-            for (int q = 0; q < 5; q++) {
-                std::vector<double> v;
-                for (uint32_t b = 0; b < s.nblocks && b < 256; b++) if (tl[b][q]) v.push_back((double)(tl[b][q] - t0) / 100.0);
-                std::sort(v.begin(), v.end());
-                if (!v.empty()) fprintf(stderr, "xy timeline launch %s: %-22s min %7.2f p50 %7.2f p90 %7.2f max %7.2f us (%zu blocks)\n", test_env("CNIIC_XY_TL_LAUNCH"), names[q], v.front(), v[v.size() / 2], v[v.size() * 9 / 10], v.back(), v.size());
-            }
-        }
-        fprintf(stderr, "xy phases (wave clocks): prologue %llu skiptest %llu barrier %llu S %llu tile %llu eval %llu epilogue %llu | dirty tiles %llu iters %llu | eval: loadwait %llu candloop %llu\n",
-                ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7], (unsigned long long)hst.iter, ph[8], ph[9]);
-    }
-#endif
     std::vector<int4> cent(K);
     CNIIC_HIP_TRY(c, hipMemcpy(cent.data(), s.cent.p, (size_t)K * 16, hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < K; k++) {

@@ -16,23 +16,22 @@ constexpr uint32_t kBias = 1u << 18;  // > max |c|^2 = 195075
 constexpr int kPPT = 8;               // colours per thread per sweep (brute kernel)
 constexpr int kAssignThreads = 256;
 constexpr uint32_t kMaxBlocks = 512;
-#ifndef CNIIC_CELL_WAVES
-#define CNIIC_CELL_WAVES 8
-#endif
-constexpr int kCellWaves = CNIIC_CELL_WAVES;                  // waves per block (narrow labels); they share the block's cell range
+constexpr int kCellWaves = 8;                                 // waves per block (narrow labels); they share the block's cell range
 // LDS strips of a wave: the super-cell list (scap) and the cell's candidates (ccap).  K <= 256: half the table and the whole table -- nothing
 // can overflow.  Larger K (u16 labels): both capped (round 4; whole-table strips left a block TWO waves at K = 2048, 0.27 ms an iteration against
 // 0.07 at K = 1024): a longer list falls back to the table, a longer strip too (the table IS a candidate list: ascending ids, the same records).
 __host__ __device__ constexpr uint32_t km_scap(uint32_t K) { return K <= 256 ? (K + 1) / 2 : (K + 1) / 2 < 512u ? (K + 1) / 2 : 512u; }
 __host__ __device__ constexpr uint32_t km_ccap(uint32_t K) { return K <= 256 ? K : 256u; }
-constexpr uint32_t kCellWavesBig = 12;                        // ... and in the settled part of a run (launch_assign)
-constexpr uint32_t kCellBlocks = 256 * (kCellWaves == 4 ? 6 : kCellWaves == 6 ? 4 : kCellWaves == 8 ? 3 : 2);  // every block resident at once (LDS, K <= 256)
+constexpr uint32_t kCellWavesBig = 12;                        // ... and in the settled part of a run (launch_assign):
+constexpr uint32_t kBigBlocksFrom = 10;                       // launches from this one on run in blocks of kCellWavesBig waves
+constexpr uint32_t kAggLaunches = 3;                          // launches 1 .. kAggLaunches book their movers round by round
+constexpr uint32_t kCellBlocks = 256 * 3;                     // three blocks of kCellWaves per CU: every block resident at once (LDS, K <= 256)
 constexpr int kSweep = 4;                  // points per lane per sweep (cells kernel)
 // The full schedule's split of the cells into ranges of equal estimated cost: a cell costs its candidate build plus one sweep
 // per 256 points (a sweep of 3 points takes as long as one of 256) -- 2 : 1 measured on the headline encode (assign launches
 // 1.87 ms with "1024 + points", 1.825 with 512 + 256 per sweep; 384 / 640 / 768 + 256: 1.87 / 1.84 / 1.85).
-constexpr uint32_t kCellFixedCost = 512;  // per cell (CNIIC_CELL_COST)
-constexpr uint32_t kCellSweepCost = 256;  // per sweep of 64 x kSweep points (CNIIC_CELL_SWEEP_COST; 0: the cell's points count instead)
+constexpr uint32_t kCellFixedCost = 512;  // per cell
+constexpr uint32_t kCellSweepCost = 256;  // per sweep of 64 x kSweep points
 
 struct KmRgbwState {
     Ctx *c = nullptr;
@@ -58,8 +57,6 @@ struct KmRgbwState {
     bool fused = false;
     cniic_kmeans_stats run_stats{};  // the statistics km_rgbw_run ended on
     bool run_stats_valid = false;
-    uint32_t big_blocks_from = 10;  // launches from this one on run in blocks of kCellWavesBig waves (CNIIC_KM_BIG_BLOCKS_FROM; a huge value: never)
-    uint32_t agg_launches = 3;  // launches 1 .. agg_launches book their movers round by round (CNIIC_KM_AGG_LAUNCHES)
     uint32_t max_skip = 64;  // (= kMaxMovedSkip) skip schedule when at most this many centroids moved (CNIIC_KM_MAXSKIP)
     long fail_at = -1;           // fault injection for the multi-rank tests (CNIIC_TEST_FAIL_AT_LAUNCH), read once as well
     uint32_t shard = 0, nshards = 1;
@@ -76,23 +73,16 @@ struct KmRgbwState {
 };
 
 // ---- k_kmeans_persist.hip: the LDS of a block and what the launch shares with its set-up
-#ifndef CNIIC_PS_CHUNKS
-#define CNIIC_PS_CHUNKS 24
-#endif
-constexpr uint32_t kPsChunks = CNIIC_PS_CHUNKS;         // chunks of the cell list a block owns (interleaved with the other blocks').  24 by measurement (16 / 20 / 24 / 28 / 32 / 48 on
+constexpr uint32_t kPsChunks = 24;                      // chunks of the cell list a block owns (interleaved with the other blocks').  24 by measurement (16 / 20 / 24 / 28 / 32 / 48 on
                                                         // six images, profiles/r05_persist_chunks_probe.txt: finer chunks spread a moved centroid's dirty cells over more blocks; beyond ~28 a block's
                                                         // cells lie in more super-cells than it has shared lists)
-#ifndef CNIIC_PS_SLOTS
-#define CNIIC_PS_SLOTS 32
-#endif
-constexpr uint32_t kPsSlotsMax = CNIIC_PS_SLOTS;                    // shared super-cell lists of a block (cells of further super-cells build from the table)
+constexpr uint32_t kPsSlotsMax = 32;                    // shared super-cell lists of a block (cells of further super-cells build from the table)
 constexpr uint32_t kPsScap = 96;                        // members a shared list holds (a longer list: its cells build from the table)
 constexpr uint32_t kPsRecWords = 11;                    // a cell's record: pivot colour, common label | pivot id << 16 | candidates << 24 | kRecComplete, 8 mask words, four candidate ids
 constexpr uint32_t kPsMaxCells = 2048;                  // cells a block may own (two per thread of its set-up)
 constexpr uint32_t kPsOffCell = 5 * 256 * 8 + 256 * 8 + kPsSlotsMax * kPsScap * 4;   // accumulators, table, the shared lists (id << 24 | colour)
 constexpr uint32_t kPsDynBytes = 160 * 1024 - 3072;     // the launch's dynamic LDS (the kernel's static variables take the rest)
 constexpr uint32_t kPsPartWords = 5 * 256 + 8;          // u64 words of one buffer of sums (5K + 2, padded)
-constexpr uint32_t kPsTsCap = 1024;                     // iterations whose end block 0 timestamps
 // per cell (C rounded up to a multiple of 4): first point u32 (own numbering; + 4 words), first point u32 (cell-major), record, id u16, work list u16, list slot u8
 __host__ __device__ constexpr uint32_t ps_cell_bytes(uint32_t C) { return 16u + ((C + 3u) & ~3u) * (4u + 4u + kPsRecWords * 4u + 2u + 2u + 1u); }
 struct alignas(128) PsLine { uint32_t v; uint32_t pad[31]; };
