@@ -13,8 +13,8 @@ Metric (BASELINE.json): Mpixels/sec encode, `cluster-colors` K=256.
                                 on 8 GPUs), ONE palette for the whole batch: every rank partitions its own frames' pixels,
                                 the colour occupancy is all-reduced once and the K partial centroid sums every iteration
                                 (RCCL, in-stream); each frame is then its own Hufman stream.  Weak scaling: per-GPU work is
-                                fixed, the palette is the union's.  A step = the whole batch encode.  EVERY default line also
-                                carries this workload as a block of its own (`c4_one_gpu` at N = 1, `c4` at N > 1 with the
+                                fixed, the palette is the union's.  A step = the whole batch encode.  EVERY --full default line
+                                also carries this workload as a block of its own (`c4_one_gpu` at N = 1, `c4` at N > 1 with the
                                 same run's one-rank timing of rank 0's frames and `efficiency_vs_one_gpu`).
   --config c3                   configs[2]: voronoi(2048) on one 4096x4096 image per GPU (its own metric; roofline = the 5-D
                                 assign per iteration, 7 B/px).  Not the default anywhere.
@@ -23,11 +23,15 @@ Metric (BASELINE.json): Mpixels/sec encode, `cluster-colors` K=256.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
     python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full               # + every figure and check past the headline (below)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  `roofline` is the K-means assign kernel (dominant kernel), timed live with HIP events
-attached to every dispatch on the stream it runs on; `cpu_baseline` is the CPU restatement of the reference algorithm
-(oracle mode R) on a bounded sample, rank 0, N=1 only.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing
+else runs, and `roofline` / `cpu_baseline` are null.  --full adds what takes runs of its own: `roofline` (the K-means assign kernel,
+the dominant kernel, timed live with HIP events attached to every dispatch on the stream it runs on), `cpu_baseline` (the CPU
+restatement of the reference algorithm, oracle mode R, on a bounded sample, rank 0, N=1 only), `parity` against the oracle's
+full-size digests, the decode round-trip check, stage timers, and the blocks of the other configurations (N = 1: host buffers,
+`c4_one_gpu`, `batch_own_palettes`, `c3`, `c5`, `c2_decode`, `c5_decode`; N > 1: `c4`, and `mailbox` on request).
 """
 import argparse
 import json
@@ -133,8 +137,11 @@ def main():
     ap.add_argument("--size", type=int, default=4096, help="c2: image side (default: configs[1], 4096)")
     ap.add_argument("--k", type=int, default=256)
     ap.add_argument("--max-iters", type=int, default=0, help="0 = to convergence, like the reference")
-    ap.add_argument("--cpu-sample", type=int, default=2560, help="side of the crop timed on the CPU (0 = skip every CPU leg)")
-    ap.add_argument("--no-extras", action="store_true", help="c2 at N=1: skip the c4_one_gpu and host-buffer legs")
+    ap.add_argument("--full", action="store_true", help="past the headline: roofline, CPU baselines, parity against the oracle, the other "
+                                                         "configurations' blocks (off: the run does only what the headline figure needs)")
+    ap.add_argument("--cpu-sample", type=int, default=2560, help="--full: side of the crop timed on the CPU (0 = skip every CPU leg)")
+    ap.add_argument("--no-extras", action="store_true", help="--full, c2: skip the blocks of other configurations (N=1: host buffers, "
+                                                              "c4_one_gpu, batch_own_palettes, c3, c5, the decodes; N>1: c4)")
     ap.add_argument("--decode", action="store_true", help="c2 / c5: time Codec::decode of the stream the encode produced (stream and image resident in HBM) "
                                                            "instead of the encode; its own metric (Mpixels/sec decode)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step (rank 0's) "
@@ -221,7 +228,8 @@ def main():
         return fr
 
     def run_c4(enc, F, warmup, steps, profile, reduce_max=True, dump=False):
-        """-> (seconds for `steps` batch encodes, bytes of this rank's streams, stats, distinct colours of this rank, roofline)"""
+        """-> (seconds for `steps` batch encodes, bytes of this rank's streams, stats, distinct colours of this rank, roofline); the last two
+        are None unless `profile`"""
         frames = make_frames(F, rank * F)
         stride = FRAME_W * FRAME_H  # 1 byte per pixel between streams: K = 256 labels need at most 8 bits each + the tree
         out = torch.empty(stride * F, dtype=torch.uint8, device=dev)
@@ -231,14 +239,14 @@ def main():
             dump_outputs(args.dump_outputs, {"streams": torch.cat([out[f * stride:f * stride + lens[f]] for f in range(F)])},
                          {"stream_lengths": lens, "kmeans_iterations": st["iterations"]})
         # the timed streams against the oracle's (configs[3]'s one-GPU share: one palette over these frames, every frame's own stream)
-        g4 = golden("c4")
+        g4 = golden("c4") if args.full else None
         run_c4.parity = None
         if g4 and rank == 0 and world == 1 and enc.dist is None and (g4.get("frames"), g4.get("w"), g4.get("h")) == (F, FRAME_W, FRAME_H) and K == 256 and not args.max_iters:
             import hashlib
             hs = [hashlib.sha256(out[f * stride:f * stride + lens[f]].cpu().numpy().tobytes()).hexdigest() for f in range(F)]
             allh = hashlib.sha256("".join(hs).encode()).hexdigest()
             run_c4.parity = {"case": "c4", "all_frames_sha256": allh, "matches_oracle": bool(allh == g4.get("all_frames_sha256") and int(st["iterations"]) == g4.get("iterations"))}
-        roof, U = None, 0
+        roof, U = None, None
         if profile:
             keys, counts = ctx.hist_rgb24(frames, npx=F * FRAME_W * FRAME_H)
             U = int(keys.size)
@@ -290,36 +298,37 @@ def main():
             return None
         if dump:
             dump_outputs(args.dump_outputs, {"stream": out[:nbytes]}, {"kmeans_iterations": st["iterations"]})
-        rc, ln, stp = ctx.encode("voronoi(%d)" % Kv, img, w=W, h=H, out=out, max_iters=args.max_iters, flags=_lib.KM_PROFILE, allow=(_lib.FEW_ACTIVE,))
-        ms, n = ctx.kernel_time("kmeans_xyrgb_iter")
-        roofline = None
-        if n:
-            it_ms = ms / n
-            algo = 7.0 * W * H
-            traffic3 = None   # PMC passes over a whole run (tools/make_profiles.sh): mean HBM bytes per k_xy_assign launch, 2 * FETCH_SIZE + WRITE_SIZE
-            try:
-                with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-                    t3 = json.load(f).get("c3")
-                if t3 and t3.get("size") == W and t3.get("K") == Kv:
-                    traffic3 = t3.get("hbm_bytes_per_launch")
-            except Exception:
-                pass
-            roofline = {"kernel": "k_xy_assign (+ k_xy_update)", "bound": "hbm", "achieved": round(algo / (it_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS,
-                        "unit": "GB/s", "frac": round(algo / (it_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "traffic": traffic3, "launch_ms": round(it_ms, 5),
-                        "launches": int(n), "algorithmic_bytes_per_launch": algo,
-                        "note": "HIP events around the whole K-means loop of one more encode / its %d iterations (assign + update launches); "
-                                "algorithmic bytes = 7 B/px/iteration (SURVEY 8(d)); tiles nothing changed for are skipped, so late iterations read less" % int(n)}
-        cpu = None
-        if args.cpu_sample > 0:
-            sys.path.insert(0, os.path.join(ROOT, "tests"))
-            import oracle_lib as O
-            s = min(768, W)
-            crop = np.ascontiguousarray(img[:s, :s].cpu().numpy())
-            t0 = time.perf_counter()
-            rc, data, ost = O.encode("voronoi(%d)" % Kv, crop, mode=O.MODE_R)
-            cdt = time.perf_counter() - t0
-            cpu = {"value": round(s * s / cdt / 1e6, 4), "unit": "Mpixels/s", "cores": 1, "kind": "port",
-                   "sample": "%dx%d crop of the same image, voronoi(%d), oracle mode R, %d iterations, %.1f s (rc %d)" % (s, s, Kv, ost.get("iterations", 0), cdt, rc)}
+        roofline, cpu, parity = None, None, None
+        if args.full:
+            rc, ln, stp = ctx.encode("voronoi(%d)" % Kv, img, w=W, h=H, out=out, max_iters=args.max_iters, flags=_lib.KM_PROFILE, allow=(_lib.FEW_ACTIVE,))
+            ms, n = ctx.kernel_time("kmeans_xyrgb_iter")
+            if n:
+                it_ms = ms / n
+                algo = 7.0 * W * H
+                traffic3 = None   # PMC passes over a whole run (tools/make_profiles.sh): mean HBM bytes per k_xy_assign launch, 2 * FETCH_SIZE + WRITE_SIZE
+                try:
+                    with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                        t3 = json.load(f).get("c3")
+                    if t3 and t3.get("size") == W and t3.get("K") == Kv:
+                        traffic3 = t3.get("hbm_bytes_per_launch")
+                except Exception:
+                    pass
+                roofline = {"kernel": "k_xy_assign (+ k_xy_update)", "bound": "hbm", "achieved": round(algo / (it_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS,
+                            "unit": "GB/s", "frac": round(algo / (it_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "traffic": traffic3, "launch_ms": round(it_ms, 5),
+                            "launches": int(n), "algorithmic_bytes_per_launch": algo,
+                            "note": "HIP events around the whole K-means loop of one more encode / its %d iterations (assign + update launches); "
+                                    "algorithmic bytes = 7 B/px/iteration (SURVEY 8(d)); tiles nothing changed for are skipped, so late iterations read less" % int(n)}
+            if args.cpu_sample > 0:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import oracle_lib as O
+                s = min(768, W)
+                crop = np.ascontiguousarray(img[:s, :s].cpu().numpy())
+                t0 = time.perf_counter()
+                rc, data, ost = O.encode("voronoi(%d)" % Kv, crop, mode=O.MODE_R)
+                cdt = time.perf_counter() - t0
+                cpu = {"value": round(s * s / cdt / 1e6, 4), "unit": "Mpixels/s", "cores": 1, "kind": "port",
+                       "sample": "%dx%d crop of the same image, voronoi(%d), oracle mode R, %d iterations, %.1f s (rc %d)" % (s, s, Kv, ost.get("iterations", 0), cdt, rc)}
+            parity = digest_check("v%d" % W, out, nbytes, W, H, st["iterations"])
         return {"metric": "Mpixels/sec encode (voronoi K=%d)" % Kv, "value": round(W * H * world * steps / dt / 1e6, 3), "unit": "Mpixels/s",
                 "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True,
                 "scaling": "weak", "vs_baseline": None, "dtype": "i32/u64", "data": "synthetic",
@@ -328,7 +337,7 @@ def main():
                            "kmeans_iterations": int(st["iterations"]),
                            "centroids_tested_per_px_per_iteration": round(st["pair_evals"] / max(1, st["iterations"]) / (W * H), 2) if "pair_evals" in st else None,
                            "parallelism": "1 GPU" if world == 1 else "%d independent images, one per GPU (replicas, no collective)" % world},
-                "roofline": roofline, "cpu_baseline": cpu, "parity": digest_check("v%d" % W, out, nbytes, W, H, st["iterations"])}
+                "roofline": roofline, "cpu_baseline": cpu, "parity": parity}
 
     def run_c5(size, warmup, steps, dump=False):
         """configs[4]: `delta` (Hilbert gather + neighbour differences + symbol histogram + Huffman) on one size^2 image per GPU
@@ -347,35 +356,35 @@ def main():
             return None
         if dump:
             dump_outputs(args.dump_outputs, {"stream": out[:nbytes]}, {})
-        parity = digest_check("c5", out, nbytes, W, H)
-        ctx.encode("delta", img, w=W, h=H, out=out, flags=_lib.KM_PROFILE)  # one more call with the stage timers (HIP events on the ctx stream)
-        stages = {}
-        for k in ("delta_gather", "delta_hist", "delta_tree", "huff_pack", "delta_finish"):   # in call order; together the whole call (delta_tree: compaction, sort, the host's merge with the GPU idle, codes)
-            ms, n = ctx.kernel_time(k)
-            if n:
-                stages[k + "_ms"] = round(ms / n, 4)
-        g_ms = stages.get("delta_gather_ms")
-        roofline = None
-        if g_ms:
-            algo = 3.0 * W * H
-            roofline = {"kernel": "k_delta_gather_p2", "bound": "hbm", "achieved": round(algo / (g_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                        "frac": round(algo / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "traffic": traffic_for("c5") if (W, H) == (16384, 16384) else None, "launch_ms": g_ms, "launches": 1,
-                        "algorithmic_bytes_per_launch": algo,
-                        "with_symbol_stream": {"bytes_per_launch": 5.0 * W * H, "GBps": round(5.0 * W * H / (g_ms * 1e-3) / 1e9, 2),
-                                               "frac": round(5.0 * W * H / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)},
-                        "note": "HIP events around the gather launch of one more encode (stage timers); algorithmic bytes = 3 B/px read (SURVEY 8(d), "
-                                "Hilbert gather + delta); the kernel also writes the 2 B/px symbol stream the later passes read: with_symbol_stream"}
-        cpu = None
-        if args.cpu_sample > 0:
-            sys.path.insert(0, os.path.join(ROOT, "tests"))
-            import oracle_lib as O
-            s = min(2048, W)
-            crop = np.ascontiguousarray(img[:s, :s].cpu().numpy())
-            t0 = time.perf_counter()
-            rc, data, _ = O.encode("delta", crop)
-            cdt = time.perf_counter() - t0
-            cpu = {"value": round(s * s / cdt / 1e6, 4), "unit": "Mpixels/s", "cores": 1, "kind": "port",
-                   "sample": "%dx%d crop of the same image, the CPU restatement of Delta::encode, %.1f s" % (s, s, cdt), "bytes_per_px": round(len(data) / (s * s), 4)}
+        parity, stages, roofline, cpu = None, None, None, None
+        if args.full:
+            parity = digest_check("c5", out, nbytes, W, H)
+            ctx.encode("delta", img, w=W, h=H, out=out, flags=_lib.KM_PROFILE)  # one more call with the stage timers (HIP events on the ctx stream)
+            stages = {}
+            for k in ("delta_gather", "delta_hist", "delta_tree", "huff_pack", "delta_finish"):   # in call order; together the whole call (delta_tree: compaction, sort, the host's merge with the GPU idle, codes)
+                ms, n = ctx.kernel_time(k)
+                if n:
+                    stages[k + "_ms"] = round(ms / n, 4)
+            g_ms = stages.get("delta_gather_ms")
+            if g_ms:
+                algo = 3.0 * W * H
+                roofline = {"kernel": "k_delta_gather_p2", "bound": "hbm", "achieved": round(algo / (g_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                            "frac": round(algo / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "traffic": traffic_for("c5") if (W, H) == (16384, 16384) else None, "launch_ms": g_ms, "launches": 1,
+                            "algorithmic_bytes_per_launch": algo,
+                            "with_symbol_stream": {"bytes_per_launch": 5.0 * W * H, "GBps": round(5.0 * W * H / (g_ms * 1e-3) / 1e9, 2),
+                                                   "frac": round(5.0 * W * H / (g_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)},
+                            "note": "HIP events around the gather launch of one more encode (stage timers); algorithmic bytes = 3 B/px read (SURVEY 8(d), "
+                                    "Hilbert gather + delta); the kernel also writes the 2 B/px symbol stream the later passes read: with_symbol_stream"}
+            if args.cpu_sample > 0:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import oracle_lib as O
+                s = min(2048, W)
+                crop = np.ascontiguousarray(img[:s, :s].cpu().numpy())
+                t0 = time.perf_counter()
+                rc, data, _ = O.encode("delta", crop)
+                cdt = time.perf_counter() - t0
+                cpu = {"value": round(s * s / cdt / 1e6, 4), "unit": "Mpixels/s", "cores": 1, "kind": "port",
+                       "sample": "%dx%d crop of the same image, the CPU restatement of Delta::encode, %.1f s" % (s, s, cdt), "bytes_per_px": round(len(data) / (s * s), 4)}
         return {"metric": "Mpixels/sec encode (delta)", "value": round(W * H * world * steps / dt / 1e6, 3), "unit": "Mpixels/s", "n_gpus": world,
                 "steps": steps, "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": "u8/u32", "data": "synthetic",
@@ -391,11 +400,11 @@ def main():
     elif config == "c4":
         F = args.frames_per_gpu
         enc = ShardedClusterColors(ctx, K, dist, dev, max_iters=args.max_iters, collectives=native)
-        dt, nbytes, st, U, roof = run_c4(enc, F, args.warmup, args.steps, profile=(rank == 0), dump=bool(args.dump_outputs))
+        dt, nbytes, st, U, roof = run_c4(enc, F, args.warmup, args.steps, profile=(rank == 0 and args.full), dump=bool(args.dump_outputs))
         npx_total = F * FRAME_W * FRAME_H * world
         if rank == 0:
             cpu = None
-            if world == 1 and args.cpu_sample > 0:
+            if args.full and world == 1 and args.cpu_sample > 0:
                 cpu = cpu_all_cores(np, make_frames, expr)
             line = {
                 "metric": "Mpixels/sec encode (cluster-colors K=%d)" % K, "value": round(npx_total * args.steps / dt / 1e6, 3), "unit": "Mpixels/s",
@@ -437,13 +446,13 @@ def main():
             dump_outputs(args.dump_outputs, {"stream": out[:nbytes]}, {"kmeans_iterations": st["iterations"]})
         npx_total = W * H * world
         # the timed stream against the oracle's digest at this size (one image, its own palette: the un-sharded step only)
-        parity = digest_check("c2", out, nbytes, W, H, st["iterations"]) if not sharded and K == 256 and not args.max_iters else None
-        roofline, cpu, extras, U = None, None, {}, 0
+        parity = digest_check("c2", out, nbytes, W, H, st["iterations"]) if args.full and not sharded and K == 256 and not args.max_iters else None
+        roofline, cpu, extras, U = None, None, {}, None
         enc_collectives = enc.collectives if enc is not None else None
         if enc is not None:
             enc.close()
             enc = None
-        if rank == 0:
+        if rank == 0 and args.full:
             keys, counts = ctx.hist_rgb24(img, npx=W * H)
             U = int(keys.size)
             del keys, counts
@@ -466,7 +475,7 @@ def main():
                 "config": {"workload": "configs[1]: cluster-colors(%d) encode of one %dx%d photo-like synthetic RGB image per GPU "
                                        "(seed 0x636E696963+2+rank), to convergence; image and stream HBM-resident" % (K, W, H),
                            "pixels_per_gpu": W * H, "unique_colours": U, "kmeans_iterations": int(st["iterations"]),
-                           "centroids_tested_per_colour_per_iteration": round(st["pair_evals"] / max(1, st["iterations"]) / max(1, U), 2) if "pair_evals" in st else None,
+                           "centroids_tested_per_colour_per_iteration": round(st["pair_evals"] / max(1, st["iterations"]) / max(1, U), 2) if U and "pair_evals" in st else None,
                            "bytes_per_px": round(nbytes / (W * H), 4),
                            "parallelism": "1 GPU" if not sharded else "pixels sharded over %d GPUs (each keeps its own image's colours), shared palette: RCCL "
                                                                        "all-reduce of the colour occupancy (8 MiB, once) and of the K partial sums per iteration (%s)"
@@ -477,7 +486,7 @@ def main():
                 ln["parity"] = parity
             return ln
 
-        # The headline is measured.  Everything below is optional blocks -- at N > 1 code that has never run on more than one device
+        # The headline is measured.  Everything below is --full's optional blocks -- at N > 1 code that has never run on more than one device
         # (ADVICE r03): a watchdog guarantees the line.  If the blocks are not done in time, rank 0 writes the headline with what was
         # finished and every rank leaves (rank 0 first: its peers may be stuck in a collective with it).
         import threading
@@ -526,8 +535,9 @@ def main():
                 os._exit(3)
         watchdog = threading.Timer(limit_s + (0.0 if rank == 0 else 10.0), fire)
         watchdog.daemon = True
-        watchdog.start()
-        if rank == 0 and world == 1 and not sharded:
+        if args.full:
+            watchdog.start()
+        if args.full and rank == 0 and world == 1 and not sharded:
             if not args.no_extras:
                 try:
                     # the trait the reference calls is host image -> host bytes (bench.rs:33-35): the same encode with both buffers in host memory
@@ -620,7 +630,7 @@ def main():
                 cpu["hip_same_crop"] = {"bytes_per_px": round(len(ng) / (s * s), 4) if rcg == 0 else None, "iterations": int(stg["iterations"]) if rcg == 0 else None}
                 prog.rebase(headline())
                 prog.begin(None)
-        if world > 1 and os.environ.get("CNIIC_BENCH_MAILBOX", "0") == "1" and enc_collectives != "mailbox":
+        if args.full and world > 1 and os.environ.get("CNIIC_BENCH_MAILBOX", "0") == "1" and enc_collectives != "mailbox":
             # OPT-IN (CNIIC_BENCH_MAILBOX=1): the exchange has only ever run between processes that share one GPU, and a fault
             # in a never-exercised cross-GPU path must not cost the driver its N > 1 line.
             # the same step with the K partial sums exchanged ONE-SHOT (every rank writes its sums into every peer's mailbox over the
@@ -645,7 +655,7 @@ def main():
                 prog.put("mailbox", {"error": "%s: %s" % (type(e).__name__, e)})
             finally:
                 os.environ.pop("CNIIC_COLLECTIVE_TIMEOUT_MS", None)
-        if world > 1 and not args.no_extras:
+        if args.full and world > 1 and not args.no_extras:
             try:
                 # configs[3] over these N GPUs (128 frames per GPU, one palette for all N x 128), and -- in the same run -- every rank's
                 # own frames clustered by that rank ALONE (no collective; rank 0's is reported): the line is self-contained, its
@@ -691,7 +701,8 @@ def main():
 def bench_decode(args, ctx, torch, np, dev, rank, world, timed, config, dump=False):
     """The other half of the trait (bench.rs:45-46 decodes every image it encodes): Codec::decode of the stream Codec::encode made,
     stream and image both resident in HBM (replicas: one image per GPU, no collective).  roofline = the kernel that decodes the
-    payload and writes the symbols (k_hd_write): payload bytes read + the bytes it writes, timed with HIP events around it."""
+    payload and writes the symbols (k_hd_write): payload bytes read + the bytes it writes, timed with HIP events around it.
+    The round-trip check, the MSE, the stage timers, the host-buffer decode and the CPU leg run with --full only."""
     from cniic_amd import _lib, synth
     if config == "c5":
         W = H = args.c5_size
@@ -711,61 +722,61 @@ def bench_decode(args, ctx, torch, np, dev, rank, world, timed, config, dump=Fal
         return ctx.decode_into(expr, stream, ln, back)
     dt, (rc, dw, dh) = timed(step, args.warmup, args.steps)
     assert (dw, dh) == (W, H)
-    if lossless:
+    if lossless and args.full:
         assert torch.equal(back.view(H, W, 3), img), "decode(encode(img)) != img"
     if rank != 0:
         return None
     if dump:
         dump_outputs(args.dump_outputs, {"image": back}, {})
-    mse = float((img.view(-1).to(torch.float32) - back.to(torch.float32)).pow(2).mean().item())   # bench::compute_error (bench.rs:95-104)
-    ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
-    ctx.decode_into(expr, stream, ln, back)
-    stages = {}
-    for k in ("hd_pass0", "hd_check", "hd_write", "undiff_scatter"):
-        ms, n = ctx.kernel_time(k)
-        if n:
-            stages[k + "_ms"] = round(ms / n, 4)
-    ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
-    himg = np.empty(W * H * 3, np.uint8)
-    hstream = stream[:ln].cpu().numpy()
-    ctx.decode_into(expr, hstream, ln, himg)
-    t0 = time.perf_counter()
-    for _ in range(3):
+    mse, stages, host_ms, roofline, cpu = None, None, None, None, None
+    if args.full:
+        mse = round(float((img.view(-1).to(torch.float32) - back.to(torch.float32)).pow(2).mean().item()), 3)   # bench::compute_error (bench.rs:95-104)
+        ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
+        ctx.decode_into(expr, stream, ln, back)
+        stages = {}
+        for k in ("hd_pass0", "hd_check", "hd_write", "undiff_scatter"):
+            ms, n = ctx.kernel_time(k)
+            if n:
+                stages[k + "_ms"] = round(ms / n, 4)
+        ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
+        himg = np.empty(W * H * 3, np.uint8)
+        hstream = stream[:ln].cpu().numpy()
         ctx.decode_into(expr, hstream, ln, himg)
-    host_ms = (time.perf_counter() - t0) / 3 * 1e3
-    roofline = None
-    w_ms = stages.get("hd_write_ms")
-    if w_ms:
-        sym_bytes = 4 if lossless else 3       # delta: packed differences (u32) for the prefix sum; the RGB codecs: pixels
-        algo = float(ln) + float(sym_bytes) * W * H
-        roofline = {"kernel": "k_hd_compact (+ the offsets scan in front of it; k_hd_write for the subsequences of more than 64 symbols)" if lossless
-                              else "k_hd_write (+ the offsets scan in front of it)", "bound": "hbm", "achieved": round(algo / (w_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS,
-                    "unit": "GB/s", "frac": round(algo / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "traffic": traffic_for("c5_decode" if lossless else "c2_decode") if W == (16384 if lossless else 4096) else None, "launch_ms": w_ms, "launches": 1,
-                    "algorithmic_bytes_per_launch": algo,
-                    "note": "HIP events around the scan + write launches of one more decode (stage timers); algorithmic bytes = the %d-byte stream read once + "
-                            "%d B/symbol written; the boundary passes before it (hd_pass0, hd_check) read the stream again and write 20 B per 1024 bits%s"
-                            % (ln, sym_bytes, " -- and, for this long-coded stream, keep the symbols they meet: the write is a copy of those (k_hd_compact reads 4 B/symbol "
-                                              "of kept rows instead of the stream; `traffic` is that kernel's)" if lossless else "")}
-    cpu = None
-    if args.cpu_sample > 0:
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import oracle_lib as O
-        s = min(2048, W)
-        crop = np.ascontiguousarray(img[:s, :s].cpu().numpy())
-        rc, data, _ = ctx.encode(expr, crop, max_iters=args.max_iters)
         t0 = time.perf_counter()
-        rco, dec = O.decode(expr, data)
-        cdt = time.perf_counter() - t0
-        cpu = {"value": round(s * s / cdt / 1e6, 4), "unit": "Mpixels/s", "cores": 1, "kind": "port",
-               "sample": "the CPU restatement's decode of the %dx%d crop's stream (%d bytes), %.1f s (rc %d)" % (s, s, len(data), cdt, rco)}
+        for _ in range(3):
+            ctx.decode_into(expr, hstream, ln, himg)
+        host_ms = round((time.perf_counter() - t0) / 3 * 1e3, 3)
+        w_ms = stages.get("hd_write_ms")
+        if w_ms:
+            sym_bytes = 4 if lossless else 3       # delta: packed differences (u32) for the prefix sum; the RGB codecs: pixels
+            algo = float(ln) + float(sym_bytes) * W * H
+            roofline = {"kernel": "k_hd_compact (+ the offsets scan in front of it; k_hd_write for the subsequences of more than 64 symbols)" if lossless
+                                  else "k_hd_write (+ the offsets scan in front of it)", "bound": "hbm", "achieved": round(algo / (w_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS,
+                        "unit": "GB/s", "frac": round(algo / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "traffic": traffic_for("c5_decode" if lossless else "c2_decode") if W == (16384 if lossless else 4096) else None, "launch_ms": w_ms, "launches": 1,
+                        "algorithmic_bytes_per_launch": algo,
+                        "note": "HIP events around the scan + write launches of one more decode (stage timers); algorithmic bytes = the %d-byte stream read once + "
+                                "%d B/symbol written; the boundary passes before it (hd_pass0, hd_check) read the stream again and write 20 B per 1024 bits%s"
+                                % (ln, sym_bytes, " -- and, for this long-coded stream, keep the symbols they meet: the write is a copy of those (k_hd_compact reads 4 B/symbol "
+                                                  "of kept rows instead of the stream; `traffic` is that kernel's)" if lossless else "")}
+        if args.cpu_sample > 0:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import oracle_lib as O
+            s = min(2048, W)
+            crop = np.ascontiguousarray(img[:s, :s].cpu().numpy())
+            rc, data, _ = ctx.encode(expr, crop, max_iters=args.max_iters)
+            t0 = time.perf_counter()
+            rco, dec = O.decode(expr, data)
+            cdt = time.perf_counter() - t0
+            cpu = {"value": round(s * s / cdt / 1e6, 4), "unit": "Mpixels/s", "cores": 1, "kind": "port",
+                   "sample": "the CPU restatement's decode of the %dx%d crop's stream (%d bytes), %.1f s (rc %d)" % (s, s, len(data), cdt, rco)}
     return {"metric": "Mpixels/sec decode (%s)" % ("delta" if lossless else "cluster-colors K=%d" % args.k),
             "value": round(W * H * world * args.steps / dt / 1e6, 3), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8/u64", "data": "synthetic",
             "config": {"workload": "%s: %s DECODE of the stream its encode made of one %dx%d photo-like synthetic RGB image per GPU, stream (%d bytes) and image "
-                                   "resident in HBM" % (what, expr, W, H, ln), "pixels_per_gpu": W * H, "stream_bytes": int(ln), "mse_vs_source": round(mse, 3),
+                                   "resident in HBM" % (what, expr, W, H, ln), "pixels_per_gpu": W * H, "stream_bytes": int(ln), "mse_vs_source": mse,
                        "parallelism": "1 GPU" if world == 1 else "%d independent images, one per GPU (replicas, no collective)" % world},
-            "roofline": roofline, "cpu_baseline": cpu, "stages": stages, "host_io_ms_per_step": round(host_ms, 3)}
+            "roofline": roofline, "cpu_baseline": cpu, "stages": stages, "host_io_ms_per_step": host_ms}
 
 
 def cpu_all_cores(np, make_frames, expr):

@@ -57,6 +57,7 @@ def test_bench_dumps_the_stream_of_its_last_timed_step(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
     assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert line["roofline"] is None and "parity" not in line   # a plain run: the timed steps and nothing else (roofline, parity: --full)
     stream = np.load(tmp_path / "stream.npy")
     assert stream.dtype == np.float32 and stream.size == np.load(tmp_path / "stream_length.npy")[0]
     with cniic_amd.Context(0) as ctx:

@@ -675,7 +675,7 @@ def test_native_loop_world2_empty_cluster_reseed(route):
 # ------------------------------------------------------------------ the driver's N > 1 invocation of bench.py, rehearsed
 @pytest.mark.gpu
 def test_bench_two_ranks_same_workload_as_one_rank_and_self_contained_c4_block():
-    """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2` as the driver launches it (two ranks sharing the test
+    """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2` as the driver launches it, with --full (two ranks sharing the test
     box's one GPU, rendezvous over gloo): ONE JSON line on stdout; the top-level workload is configs[1] PER GPU -- the workload
     of the N = 1 line, so the driver's 1/2/4/8 curve is one workload -- and the line carries configs[3] as a block of its own
     with the same run's one-rank timing and an efficiency that needs no other invocation."""
@@ -690,7 +690,7 @@ def test_bench_two_ranks_same_workload_as_one_rank_and_self_contained_c4_block()
                CNIIC_BENCH_MAILBOX="1")                                    # ... and the opt-in mailbox block is asked for
     common = ["--steps", "1", "--warmup", "1", "--size", "1024", "--frames-per-gpu", "2", "--cpu-sample", "0"]
     p2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2"] + common,
+                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--full"] + common,
                         env=env, capture_output=True, text=True, timeout=600)
     assert p2.returncode == 0, p2.stderr[-3000:]
     lines2 = [l for l in p2.stdout.splitlines() if l.strip()]

@@ -1,4 +1,4 @@
-"""The stage timers of a `delta` encode (CNIIC_KM_PROFILE in the call's options; bench.py --config c5 reports them as `stages`): the five
+"""The stage timers of a `delta` encode (CNIIC_KM_PROFILE in the call's options; bench.py --config c5 --full reports them as `stages`): the five
 stages are consecutive and together the whole call, so their sum must account for the call's wall time -- and the stream of a timed
 call (the pack in one piece, every stage synchronised) must be the stream of an untimed one."""
 import time

@@ -38,10 +38,10 @@ json.dump(j, open(O + "/traffic.json", "w"), indent=1)
 print(key, pat, j[key])
 PY
 }
-run c2_persist k_rgbw_persist python3 $R/bench.py --no-extras --cpu-sample 0 --steps 3 --warmup 1
-run c4 k_rgbw_persist python3 $R/bench.py --config c4 --cpu-sample 0 --steps 1 --warmup 1
-run c5 k_delta_gather_p2 python3 $R/bench.py --config c5 --cpu-sample 0 --steps 2 --warmup 1
-run c2_decode k_hd_write python3 $R/bench.py --decode --cpu-sample 0 --steps 2 --warmup 1
-run c5_decode k_hd_compact python3 $R/bench.py --decode --config c5 --cpu-sample 0 --steps 2 --warmup 1
+run c2_persist k_rgbw_persist python3 $R/bench.py --full --no-extras --cpu-sample 0 --steps 3 --warmup 1
+run c4 k_rgbw_persist python3 $R/bench.py --full --config c4 --cpu-sample 0 --steps 1 --warmup 1
+run c5 k_delta_gather_p2 python3 $R/bench.py --full --config c5 --cpu-sample 0 --steps 2 --warmup 1
+run c2_decode k_hd_write python3 $R/bench.py --full --decode --cpu-sample 0 --steps 2 --warmup 1
+run c5_decode k_hd_compact python3 $R/bench.py --full --decode --config c5 --cpu-sample 0 --steps 2 --warmup 1
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 cat $O/traffic.json
