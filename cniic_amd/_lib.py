@@ -32,7 +32,8 @@ SYMBOLS = [
     "cniic_cc_create_local", "cniic_cc_image_begin", "cniic_cc_image_occupancy", "cniic_cc_image_create", "cniic_remap_rgb", "cniic_hilbert_xy",
     "cniic_hilbert_linearize", "cniic_hilbert_delta", "cniic_hilbert_delta_hist", "cniic_huf_encode_all",
     "cniic_huf_size", "cniic_codec_parse", "cniic_codec_name", "cniic_codec_is_lossless", "cniic_codec_encode",
-    "cniic_codec_encode_opts", "cniic_codec_encode_batch", "cniic_codec_decode", "cniic_mse", "cniic_synth_image",
+    "cniic_codec_encode_opts", "cniic_codec_encode_batch", "cniic_codec_decode", "cniic_codec_decode_batch", "cniic_mse", "cniic_mse_batch",
+    "cniic_synth_image",
 ]
 
 
@@ -374,6 +375,26 @@ class Context:
         rc = self._check(self._L.cniic_codec_decode(self.h, expr.encode(), _ptr(data), C.c_uint64(nbytes), _ptr(out), C.c_uint64(cap),
                                                     C.byref(cw), C.byref(ch)), allow)
         return rc, cw.value, ch.value
+
+    def decode_batch(self, expr, streams, stride, lens, F, out, img_stride, allow=()):
+        """cniic_codec_decode_batch: F streams (stream f at streams[f * stride:], lens[f] bytes -- what encode_batch wrote), image f into
+        out[f * img_stride:] (img_stride bytes at most).  streams / out: device tensors, numpy arrays or addresses.
+        -> (rc, list of F widths, list of F heights, list of F per-frame status codes)"""
+        ln = (C.c_uint64 * F)(*[int(x) for x in lens])
+        ws, hs, rcs = (C.c_uint32 * F)(), (C.c_uint32 * F)(), (C.c_int32 * F)()
+        rc = self._check(self._L.cniic_codec_decode_batch(self.h, expr.encode(), _ptr(streams), C.c_uint64(stride), ln, C.c_uint32(F), _ptr(out),
+                                                          C.c_uint64(img_stride), ws, hs, rcs), allow)
+        return rc, [int(x) for x in ws], [int(x) for x in hs], [int(x) for x in rcs]
+
+    def mse_batch(self, a, b, npx, F):
+        """cniic_mse_batch: the MSE of F image pairs of npx pixels each (pair f at a[f * npx * 3:], b[f * npx * 3:]) -> list of F floats"""
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a, np.uint8)
+        if isinstance(b, np.ndarray):
+            b = np.ascontiguousarray(b, np.uint8)
+        v = (C.c_double * max(F, 1))()
+        self._check(self._L.cniic_mse_batch(self.h, _ptr(a), _ptr(b), C.c_uint64(npx), C.c_uint32(F), v))
+        return [float(v[i]) for i in range(F)]
 
     def mse(self, a, b):
         a = np.ascontiguousarray(a, np.uint8)

@@ -902,6 +902,26 @@ int32_t cniic_codec_encode_opts(cniic_ctx *c, const char *expr, const cniic_kmea
     return codec_encode(c, d, in.d, w, h, opts, out, cap, len, stats);
 }
 
+// the first S worker contexts of a batch call (created on first use), with this context's route switches and its injected scan (a view
+// of this context's table)
+static int32_t batch_workers_ready(cniic_ctx *c, uint32_t S, const char *who) {
+    while (c->batch_workers.size() < S) {
+        cniic_ctx *wk = nullptr;
+        const int32_t rc = cniic_ctx_create(c->device, nullptr, &wk);
+        if (rc != CNIIC_OK) return c->fail(rc, "%s: cannot create worker context %zu", who, c->batch_workers.size());
+        c->batch_workers.push_back(wk);
+    }
+    for (uint32_t i = 0; i < S; i++) {
+        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        memcpy(wk->opt_val, c->opt_val, sizeof c->opt_val);
+        wk->opt_set = c->opt_set;
+        wk->scan_xy.release();
+        wk->scan_w = wk->scan_h = 0;
+        if (c->scan_xy.p) { wk->scan_xy.view(c->scan_xy.p, c->scan_xy.bytes); wk->scan_w = c->scan_w; wk->scan_h = c->scan_h; }
+    }
+    return CNIIC_OK;
+}
+
 int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
                                  uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs, cniic_kmeans_stats *stats) {
     LOCK(c);
@@ -912,23 +932,13 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
     if (!rgb || !out || !lens) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_batch: null argument");
     const uint64_t img_bytes = (uint64_t)w * h * 3;
     const uint32_t S = (uint32_t)std::min<uint64_t>(frames, std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
-    while (c->batch_workers.size() < S) {
-        cniic_ctx *wk = nullptr;
-        const int32_t rc = cniic_ctx_create(c->device, nullptr, &wk);
-        if (rc != CNIIC_OK) return c->fail(rc, "codec_encode_batch: cannot create worker context %zu", c->batch_workers.size());
-        c->batch_workers.push_back(wk);
-    }
-    for (uint32_t i = 0; i < S; i++) {  // the workers take this context's route switches
+    CNIIC_TRY(batch_workers_ready(c, S, "codec_encode_batch"));
+    for (uint32_t i = 0; i < S; i++) {
         cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
-        memcpy(wk->opt_val, c->opt_val, sizeof c->opt_val);
-        wk->opt_set = c->opt_set;
         // several images in flight: half-size K-means grids, so that two images' launches are resident together (measured on 64 frames
         // 1920 x 1080 with 8 workers: 768 blocks 0.885 ms per frame, 384: 0.729, 192: 0.80, 96: 1.17)
         if (S > 1 && !((c->opt_set >> CNIIC_OPT_KM_MAX_BLOCKS) & 1u) && !getenv("CNIIC_KM_MAX_BLOCKS")) { wk->opt_val[CNIIC_OPT_KM_MAX_BLOCKS] = 384; wk->opt_set |= 1u << CNIIC_OPT_KM_MAX_BLOCKS; }
         wk->ps_div = S;                        // ... and the persistent K-means launch an S-th of the CUs, so that S of them are resident side by side
-        wk->scan_xy.release();                 // ... and its injected scan, as a view of this context's table
-        wk->scan_w = wk->scan_h = 0;
-        if (c->scan_xy.p) { wk->scan_xy.view(c->scan_xy.p, c->scan_xy.bytes); wk->scan_w = c->scan_w; wk->scan_h = c->scan_h; }
     }
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
     std::atomic<uint32_t> next{0};
@@ -971,6 +981,49 @@ int32_t cniic_codec_decode(cniic_ctx *c, const char *expr, const uint8_t *bytes,
     return codec_decode(c, d, bytes, n, rgb, cap, w, h);  // (the stream may be in host memory or in HBM)
 }
 
+int32_t cniic_codec_decode_batch(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+                                 uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs) {
+    LOCK(c);
+    c->ktimes.clear();
+    CodecDesc d;
+    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    if (!frames) return CNIIC_OK;
+    if (!bytes || !lens || !rgb || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "codec_decode_batch: null argument");
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the streams on this context's stream is done
+    // `hufman` / `cluster-colors`: the frames decoded together (codec_decode_batch_route); the rest, each on its own on the workers
+    std::vector<uint8_t> taken;
+    std::vector<int32_t> status;
+    std::vector<std::string> msg;
+    CNIIC_TRY(codec_decode_batch_route(c, d, bytes, stride, lens, frames, rgb, img_stride, w, h, taken, status, msg));
+    std::vector<uint32_t> rest;
+    for (uint32_t f = 0; f < frames; f++) if (!taken[f]) rest.push_back(f);
+    if (!rest.empty()) {
+        const uint32_t S = (uint32_t)std::min<uint64_t>(rest.size(), std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
+        CNIIC_TRY(batch_workers_ready(c, S, "codec_decode_batch"));
+        std::atomic<uint32_t> next{0};
+        auto run = [&](uint32_t i) {
+            cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+            for (;;) {
+                const uint32_t j = next.fetch_add(1);
+                if (j >= rest.size()) break;
+                const uint32_t f = rest[j];
+                status[f] = cniic_codec_decode(wk, expr, bytes + (uint64_t)f * stride, lens[f], rgb + (uint64_t)f * img_stride, img_stride, &w[f], &h[f]);
+                if (status[f] != CNIIC_OK) msg[f] = wk->err;
+            }
+        };
+        std::vector<std::thread> th;
+        for (uint32_t i = 1; i < S; i++) th.emplace_back(run, i);
+        run(0);
+        for (auto &t : th) t.join();
+    }
+    int32_t first = CNIIC_OK;
+    for (uint32_t f = 0; f < frames; f++) {
+        if (rcs) rcs[f] = status[f];
+        if (status[f] != CNIIC_OK && first == CNIIC_OK) { first = status[f]; c->err = msg[f]; }
+    }
+    return first;
+}
+
 int32_t cniic_mse(cniic_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t npx, double *mse) {
     LOCK(c);
     if (!mse || ((!a || !b) && npx)) return c->fail(CNIIC_ERR_BAD_ARG, "mse: null argument");
@@ -978,6 +1031,16 @@ int32_t cniic_mse(cniic_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t npx
     CNIIC_TRY(ia.bind(c, a, npx * 3));
     CNIIC_TRY(ib.bind(c, b, npx * 3));
     return mse_rgb(c, ia.d, ib.d, npx, mse);
+}
+
+int32_t cniic_mse_batch(cniic_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t npx, uint32_t frames, double *mse) {
+    LOCK(c);
+    if (!frames) return CNIIC_OK;
+    if (!mse || ((!a || !b) && npx)) return c->fail(CNIIC_ERR_BAD_ARG, "mse_batch: null argument");
+    In<uint8_t> ia, ib;
+    CNIIC_TRY(ia.bind(c, a, npx * 3 * frames));
+    CNIIC_TRY(ib.bind(c, b, npx * 3 * frames));
+    return mse_rgb_batch(c, ia.d, ib.d, npx, frames, mse);
 }
 
 int32_t cniic_synth_image(cniic_ctx *c, int32_t kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *rgb) {

@@ -1272,4 +1272,144 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
 
+// ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
+// The heads of all frames come to the host together (one strided copy for streams in HBM), every decoder is parsed there (up to 16
+// threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev).  Whatever this route does
+// not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more than 32
+// bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
+constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
+constexpr size_t kBatchRouteFrames = 4096;          // frames per set of launches
+int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
+                             uint64_t img_stride, uint32_t *w, uint32_t *h, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
+                             std::vector<std::string> &msgs) {
+    taken.assign(F, 0);
+    rcs.assign(F, CNIIC_OK);
+    msgs.assign(F, std::string());
+    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS)) return CNIIC_OK;
+    const bool bytes_dev = is_device_ptr(bytes), dst_dev = is_device_ptr(rgb);
+    std::vector<uint8_t> off_route(F, 0);   // tests (CNIIC_TEST_DECODE_BATCH_OFF=i,j,..): these frames through the single-stream decode
+    if (const char *e = test_env("CNIIC_TEST_DECODE_BATCH_OFF"))
+        for (const char *q = e; *q;) {
+            char *end = nullptr;
+            const unsigned long v = strtoul(q, &end, 10);
+            if (end == q) break;
+            if (v < F) off_route[v] = 1;
+            q = *end ? end + 1 : end;
+        }
+    // ---- the heads: where the host reads frame f (head_p[f], head_n[f] bytes of it)
+    std::vector<const uint8_t *> head_p(F);
+    std::vector<uint64_t> head_n(F);
+    auto fetch = [&](uint64_t W, uint32_t f0, uint32_t f1) -> int {   // the first W bytes of frames [f0, f1] into the pinned block, row f at (f - f0) W
+        CNIIC_HIP_TRY(c, ctx_pinned_huf(c, W * (f1 - f0 + 1)));
+        uint8_t *ph = static_cast<uint8_t *>(c->pinned_huf);
+        const uint32_t last = F >= 2 ? std::min(f1, F - 2) : 0;   // (the batch's last frame may end before W bytes: a copy of its own)
+        if (F >= 2 && f0 <= last)
+            CNIIC_HIP_TRY(c, hipMemcpy2DAsync(ph, W, bytes + (uint64_t)f0 * stride, stride, W, last - f0 + 1, hipMemcpyDeviceToHost, c->stream));
+        if (f1 == F - 1) {
+            const uint64_t n1 = std::min(W, lens[F - 1]);
+            if (n1) CNIIC_HIP_TRY(c, hipMemcpyAsync(ph + (uint64_t)(F - 1 - f0) * W, bytes + (uint64_t)(F - 1) * stride, n1, hipMemcpyDeviceToHost, c->stream));
+        }
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (uint32_t f = f0; f <= f1; f++) { head_p[f] = ph + (uint64_t)(f - f0) * W; head_n[f] = std::min(W, lens[f]); }
+        return CNIIC_OK;
+    };
+    if (bytes_dev) {
+        uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
+        for (uint32_t f = 0; f < F; f++) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
+        W = std::max<uint64_t>(8, std::min({W, stride, kBatchHeadsMax / F}));
+        CNIIC_TRY(fetch(W, 0, F - 1));
+    } else {
+        for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
+    }
+    // ---- the decoders, parsed on the host
+    std::vector<LeafTable> lts(F);
+    std::vector<uint64_t> pay(F);      // where the payload starts
+    std::vector<uint8_t> cand(F, 0);   // 1: on the route; 2: the decoder runs past the head (a second look)
+    auto classify = [&](uint32_t f) {
+        cand[f] = 0;
+        if (off_route[f]) return;
+        uint64_t pos = 0;
+        uint32_t fw, fh;
+        if (!get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) return;
+        const uint64_t n = (uint64_t)fw * fh;
+        if (!n || n >= (1ull << 32) || n * 3 > img_stride) return;
+        LeafTable &lt = lts[f];
+        if (!huff_parse_leaves(CNIIC_SYM_RGB, head_p[f], head_n[f], pos, lt)) { if (head_n[f] < lens[f]) cand[f] = 2; return; }
+        if (lt.too_deep || lt.max_len > 32 || lt.n() >= (1u << 20) || (lt.n() > 1 && pos >= lens[f])) return;
+        w[f] = fw; h[f] = fh;
+        pay[f] = pos;
+        cand[f] = 1;
+    };
+    auto parse_all = [&](const std::vector<uint32_t> &which) {
+        std::atomic<uint32_t> next{0};
+        auto run = [&]() { for (uint32_t i; (i = next.fetch_add(1)) < which.size();) classify(which[i]); };
+        const uint32_t T = (uint32_t)std::min<size_t>(16, which.size());
+        std::vector<std::thread> th;
+        for (uint32_t i = 1; i < T; i++) th.emplace_back(run);
+        run();
+        for (auto &t : th) t.join();
+    };
+    {
+        std::vector<uint32_t> all(F);
+        for (uint32_t f = 0; f < F; f++) all[f] = f;
+        parse_all(all);
+    }
+    std::vector<uint32_t> again;
+    uint64_t W2 = 0;
+    for (uint32_t f = 0; f < F; f++) if (cand[f] == 2) { again.push_back(f); W2 = std::max(W2, std::min<uint64_t>(lens[f], 4ull << 20)); }
+    if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
+        const uint32_t f0 = again.front(), f1 = again.back();
+        W2 = std::min({W2, stride, kBatchHeadsMax / (f1 - f0 + 1)});
+        if (W2 > head_n[f0] || W2 > head_n[f1]) {
+            CNIIC_TRY(fetch(W2, f0, f1));
+            parse_all(again);
+        }
+    }
+    std::vector<uint32_t> route;
+    for (uint32_t f = 0; f < F; f++) if (cand[f] == 1) route.push_back(f);
+    if (route.empty()) return CNIIC_OK;
+    // ---- payloads in HBM, outputs in HBM (4-byte aligned)
+    DevBuf up_d, img_d;
+    const uint8_t *base = bytes;
+    if (!bytes_dev) {   // the streams from the first frame on the route to the last, in one copy
+        const uint64_t lo = (uint64_t)route.front() * stride, hi = (uint64_t)route.back() * stride + lens[route.back()];
+        CNIIC_HIP_TRY(c, up_d.alloc(hi - lo + 16));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+        base = up_d.as<uint8_t>() - lo;
+    }
+    std::vector<HdBatchFrame> bf(route.size());
+    std::vector<uint64_t> img_at(route.size(), ~0ull);
+    uint64_t img_bytes = 0;
+    for (size_t i = 0; i < route.size(); i++) {
+        const uint32_t f = route[i];
+        const uint64_t n = (uint64_t)w[f] * h[f];
+        uint8_t *dst = rgb + (uint64_t)f * img_stride;
+        if (!dst_dev || (reinterpret_cast<uintptr_t>(dst) & 3)) { img_at[i] = img_bytes; img_bytes += (n * 3 + 15) & ~15ull; }
+        bf[i].lt = &lts[f];
+        bf[i].payload = base + (uint64_t)f * stride + pay[f];
+        bf[i].payload_bytes = lens[f] - pay[f];
+        bf[i].nsyms = n;
+        bf[i].out_d = dst;
+    }
+    if (img_bytes) {
+        CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
+        for (size_t i = 0; i < route.size(); i++) if (img_at[i] != ~0ull) bf[i].out_d = img_d.as<uint8_t>() + img_at[i];
+    }
+    for (size_t i0 = 0; i0 < bf.size(); i0 += kBatchRouteFrames) {   // (the frame is a grid dimension of the launches)
+        std::vector<HdBatchFrame> part(bf.begin() + i0, bf.begin() + std::min(bf.size(), i0 + kBatchRouteFrames));
+        CNIIC_TRY(huff_decode_batch_dev(c, part));
+        for (size_t i = 0; i < part.size(); i++) bf[i0 + i].status = part[i].status;
+    }
+    for (size_t i = 0; i < route.size(); i++) {
+        const uint32_t f = route[i];
+        if (bf[i].status == 2) continue;   // not settled: the caller's
+        taken[f] = 1;
+        if (bf[i].status == 1) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "Failed to decode symbol"; continue; }
+        if (img_at[i] != ~0ull)
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(rgb + (uint64_t)f * img_stride, bf[i].out_d, (uint64_t)w[f] * h[f] * 3, dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    }
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
 }  // namespace cniic

@@ -25,6 +25,13 @@ int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, u
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h);
 
+// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` frames of a batch decoded together (stream f at bytes + f *
+// stride, lens[f] bytes; image f to rgb + f * img_stride).  taken[f] = 1: frame f was decoded here (rcs[f], msgs[f], w[f], h[f]); 0: the
+// caller decodes it on its own (codec_decode).
+int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
+                             uint64_t img_stride, uint32_t *w, uint32_t *h, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
+                             std::vector<std::string> &msgs);
+
 // cluster-colors in pieces (see codec.cpp)
 struct CcSession {
     Ctx *c = nullptr;

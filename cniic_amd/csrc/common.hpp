@@ -582,6 +582,7 @@ int label_lut(Ctx *c, const uint32_t *labels_d, uint64_t U, const uint32_t *cent
 int rank_from_keys(Ctx *c, const uint32_t *keys_d, uint64_t U, uint32_t *table_d);
 int voronoi_paint(Ctx *c, const cniic_colorpos *cent_d, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, bool small_coords = false);
 int mse_rgb(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, double *mse_h);
+int mse_rgb_batch(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, uint32_t frames, double *mse_h);  // F pairs, one result each
 int synth_image(Ctx *c, int kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *out_d);
 int rgb_to_keys(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t *keys_d);
 
@@ -597,6 +598,17 @@ struct UdSums { DevBuf buf; bool filled = false; };   // FromDiff's channel sums
 // triples (4-byte aligned).  status: 0 ok, 1 stream ends early, 2 did not settle (decode on the host)
 int huff_decode_dev(Ctx *c, const LeafTable &lt, const uint8_t *payload, bool payload_dev, uint64_t payload_bytes, uint64_t nsyms,
                     int mode, void *out_d, int *status, UdSums *sums = nullptr);
+// many RGB-symbol streams (mode 1) in one set of launches (k_hdecode.hip, cniic_codec_decode_batch): per frame the host's leaf table
+// (not too_deep, codes of at most 32 bits, fewer than 2^20 leaves), the payload in HBM, nsyms > 0 and a 4-byte aligned output in HBM.
+// status (out): 0 = decoded, 1 = the stream ends early, 2 = did not settle (the caller decodes that frame again on its own)
+struct HdBatchFrame {
+    const LeafTable *lt = nullptr;
+    const uint8_t *payload = nullptr;
+    uint64_t payload_bytes = 0, nsyms = 0;
+    uint8_t *out_d = nullptr;
+    int status = 0;
+};
+int huff_decode_batch_dev(Ctx *c, std::vector<HdBatchFrame> &frames);
 // ... with the table of leaves already in HBM (code u64[n] | key u32[n] at off_key | len u8[n] at off_len)
 int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t off_key, uint64_t off_len, uint32_t max_len, uint32_t first_key,
                            const uint8_t *payload, bool payload_dev, uint64_t payload_bytes, uint64_t nsyms, int mode, void *out_d, int *status, UdSums *sums = nullptr);

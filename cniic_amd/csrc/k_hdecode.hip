@@ -80,10 +80,8 @@ struct HdStream {
 };
 
 // table entries for the `bits` top bits p: all 64-bit windows that begin with p lie between base and top
-__global__ void k_hd_build_lut(const uint64_t *__restrict__ code, const uint32_t *__restrict__ key, const uint8_t *__restrict__ len, uint32_t n,
-                               uint32_t bits, uint32_t *__restrict__ lut1, uint2 *__restrict__ lut2) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= (1u << bits)) return;
+__device__ __forceinline__ void hd_build_lut_entry(uint32_t p, const uint64_t *__restrict__ code, const uint32_t *__restrict__ key, const uint8_t *__restrict__ len,
+                                                   uint32_t n, uint32_t bits, uint32_t *__restrict__ lut1, uint2 *__restrict__ lut2) {
     const uint64_t base = (uint64_t)p << (64 - bits), top = base | ((1ull << (64 - bits)) - 1ull);
     auto last_le = [&](uint64_t v) -> uint32_t {  // largest i with code[i] <= v (code[0] = 0: exists)
         uint32_t a = 0, b = n;                    // invariant: code[a] <= v, (b == n or code[b] > v)
@@ -97,6 +95,12 @@ __global__ void k_hd_build_lut(const uint64_t *__restrict__ code, const uint32_t
     const uint32_t hi = p + 1 == (1u << bits) ? n - 1 : (code[lo_next] == top + 1 ? lo_next - 1 : lo_next);
     if (lut1) lut1[p] = lo == hi ? (key[lo] << 5) | ((uint32_t)len[lo] << 1) | 1u : 0u;
     else lut2[p] = lo == hi ? make_uint2(key[lo], kHdDirect | len[lo]) : make_uint2(lo, hi - lo);
+}
+__global__ void k_hd_build_lut(const uint64_t *__restrict__ code, const uint32_t *__restrict__ key, const uint8_t *__restrict__ len, uint32_t n,
+                               uint32_t bits, uint32_t *__restrict__ lut1, uint2 *__restrict__ lut2) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (1u << bits)) return;
+    hd_build_lut_entry(p, code, key, len, n, bits, lut1, lut2);
 }
 
 // The third tables (round 5).  A second-table entry that holds a RANGE of leaves sent its lane into a bisection of the code array
@@ -188,10 +192,11 @@ __device__ __forceinline__ HdSym hd_lookup(const HdTables &T, const uint32_t *lu
 
 // Block prologue: the first table and the block's stretch of the stream into LDS (stage[i] = word i of the stretch, MSB-first).
 // Returns the bit position (stream frame) of stage word 0.
-__device__ __forceinline__ uint64_t hd_stage(const HdStream &S, const uint32_t *__restrict__ lut_g, uint32_t *lut_s, uint32_t *stage) {
+// (blk: the block's place in its stream -- blockIdx.x, or the block's index inside its frame in the batched kernels)
+__device__ __forceinline__ uint64_t hd_stage_at(const HdStream &S, const uint32_t *__restrict__ lut_g, uint32_t *lut_s, uint32_t *stage, uint64_t blk) {
     if (lut_g)
         for (uint32_t i = threadIdx.x; i < (1u << kHdLut); i += kHdThreads) lut_s[i] = lut_g[i];
-    const uint64_t blk_bit = (uint64_t)blockIdx.x * kHdThreads * kHdSub;
+    const uint64_t blk_bit = blk * kHdThreads * kHdSub;
     const int64_t w0 = (int64_t)(blk_bit / 32) - (int64_t)(kHdWarm / 32);   // negative for block 0: those words read as zero
     // (every word of the thread asked for before the first one is waited for: as a loop of load, swap, store the seventeen round trips
     // to memory came one behind the other, 11 us of a block's 146)
@@ -212,6 +217,9 @@ __device__ __forceinline__ uint64_t hd_stage(const HdStream &S, const uint32_t *
     }
     __syncthreads();
     return (uint64_t)(w0 * 32);  // (two's complement: position - base stays right for block 0)
+}
+__device__ __forceinline__ uint64_t hd_stage(const HdStream &S, const uint32_t *__restrict__ lut_g, uint32_t *lut_s, uint32_t *stage) {
+    return hd_stage_at(S, lut_g, lut_s, stage, blockIdx.x);
 }
 
 // A thread's view of the staged stream: the next bits left-aligned in a register, topped up a word at a time -- one LDS read per
@@ -915,6 +923,346 @@ int huff_decode_dev(Ctx *c, const LeafTable &lt, const uint8_t *payload, bool pa
     memcpy(ph + off_len, lt.len.data(), n);
     CNIIC_HIP_TRY(c, hipMemcpyAsync(tab_d.p, c->pinned_huf, tab_bytes, hipMemcpyHostToDevice, c->stream));
     return huff_decode_tables_dev(c, tab_d.as<uint8_t>(), n, off_key, off_len, lt.max_len, lt.key[0], payload, payload_dev, payload_bytes, nsyms, mode, out_d, status, sums);
+}
+
+// ---------------------------------------------------------------- many streams in one set of launches (cniic_codec_decode_batch)
+// The frames of a batch share every launch: a frame's subsequences are numbered from its own payload's first word, as in the
+// single-stream decode, and laid end to end in global arrays (frame f's are [sub0, sub0 + nsub)); a block decodes subsequences of
+// exactly one frame (blk_frame[block], blk0 = the frame's first block), stages that frame's first table and stretch of the stream like
+// k_hd_pass and walks with the same hd_run.  A frame's first subsequence starts at its payload's first bit, and the check of thread t
+// against t - 1 stops there: frames never look into each other.  changed[f] / done[f]: one word each per frame -- a check that moves
+// no end of frame f settles it (k_hdb_settle), and its blocks leave at once from then on.  RGB symbols (mode 1), codes of at most 32
+// bits; no kept rows (the write decodes again) and no phase maps (a frame that does not settle goes back to the single-stream decode).
+constexpr int kHdbMaxPasses = 8;   // checks before a frame that has not settled goes back to the single-stream decode
+struct HdbFrame {
+    HdStream S;
+    HdTables T;
+    uint64_t sub0, nsub, nsyms;
+    uint8_t *out;        // nsyms RGB triples, 4-byte aligned
+    uint32_t blk0, key0; // key0: the one symbol of a one-leaf decoder (T.n == 1: filled, not decoded)
+    int32_t max_rounds;
+    uint32_t pad;
+};
+
+// the first (second = 0) or second table of every frame: the frame on blockIdx.y
+__global__ __launch_bounds__(256) void k_hdb_build_lut(const HdbFrame *__restrict__ fr, uint32_t second) {
+    const HdTables &T = fr[blockIdx.y].T;
+    if (T.n < 2 || (second ? T.bits2 == 0 : !T.use1)) return;
+    const uint32_t bits = second ? T.bits2 : (uint32_t)kHdLut;
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= (1u << bits)) return;
+    hd_build_lut_entry(p, T.code, T.key, T.len, T.n, bits, second ? nullptr : const_cast<uint32_t *>(T.lut1), second ? const_cast<uint2 *>(T.lut2) : nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_hdb_fill(const HdbFrame *__restrict__ fr) {
+    const HdbFrame &F = fr[blockIdx.y];
+    if (F.T.n != 1) return;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < F.nsyms; i += stride) {
+        F.out[3 * i] = (uint8_t)(F.key0 >> 16); F.out[3 * i + 1] = (uint8_t)(F.key0 >> 8); F.out[3 * i + 2] = (uint8_t)F.key0;
+    }
+}
+
+// k_hd_pass for a batch (end_prev == null: pass 0).  Arrays are indexed by global subsequence, positions by the frame's own frame.
+__global__ __launch_bounds__(kHdThreads) void k_hdb_pass(const HdbFrame *__restrict__ fr, const uint32_t *__restrict__ blk_frame, const uint64_t *__restrict__ end_prev,
+                                                         uint64_t *__restrict__ end_out, uint64_t *__restrict__ start, uint32_t *__restrict__ count,
+                                                         uint32_t *__restrict__ changed, const uint32_t *__restrict__ done) {
+    extern __shared__ __align__(16) uint32_t hd_lds[];
+    const uint32_t f = blk_frame[blockIdx.x];
+    if (end_prev && done[f]) return;                       // a settled frame
+    const HdbFrame &F = fr[f];
+    const HdStream &S = F.S;
+    const HdTables &T = F.T;
+    __shared__ unsigned long long s_end[kHdThreads], s_nstart[kHdThreads], s_nend[kHdThreads];
+    __shared__ uint32_t s_ncnt[kHdThreads];
+    __shared__ uint16_t s_list[kHdThreads];
+    __shared__ uint32_t s_n;
+    __shared__ unsigned long long s_pred0;
+    uint32_t *lut_s = hd_lds;
+    uint32_t *stage = hd_lds + (T.use1 ? (1u << kHdLut) : 0u);
+    const uint32_t tid = threadIdx.x, lb = blockIdx.x - F.blk0;
+    const uint64_t t0 = (uint64_t)lb * kHdThreads, t = t0 + tid, g = F.sub0 + t;   // t: in the frame, g: in the batch
+    const bool live = t < F.nsub;
+    const uint64_t lo = max(t * kHdSub, S.bit0), hi = min((t + 1) * kHdSub, S.nbits);
+    uint64_t my_start = 0, my_end = 0, base = 0;
+    uint32_t my_cnt = 0;
+    uint64_t pred0 = 0;
+    if (!end_prev) {
+        base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, lb);
+        if (live) {
+            uint64_t at = S.bit0;
+            if (t) {
+                at = t * kHdSub - S.warm;
+                uint32_t dummy = 0;
+                hd_run<false, false>(T, lut_s, stage, base, S.nbits, at, lo, dummy);
+            }
+            my_start = at;
+            hd_run<false, true>(T, lut_s, stage, base, S.nbits, at, hi, my_cnt);
+            my_end = at;
+        }
+        pred0 = my_start;
+    } else {
+        bool redo = false;
+        if (live) {
+            const uint64_t s = t ? end_prev[g - 1] : S.bit0;   // (the frame's first subsequence: its payload's first bit)
+            my_start = start[g]; my_end = end_prev[g]; my_cnt = count[g];
+            redo = s != my_start;
+            if (tid == 0) pred0 = s;
+            if (!redo) end_out[g] = my_end;
+        }
+        if (!__syncthreads_or(redo)) return;
+        base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, lb);
+    }
+    s_end[tid] = live ? my_end : ~0ull;
+    if (tid == 0) s_pred0 = pred0;
+    const uint64_t end_at_entry = my_end;
+    bool gave_up = true;
+    for (int round = 0; round < F.max_rounds; round++) {
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        const uint64_t pred = tid ? s_end[tid - 1] : s_pred0;
+        const bool redo = live && pred != my_start;
+        if (redo) s_list[atomicAdd(&s_n, 1u)] = (uint16_t)tid;
+        __syncthreads();
+        const uint32_t nl = s_n;
+        if (nl == 0) { gave_up = false; break; }
+        if (tid < nl) {
+            const uint32_t j = s_list[tid];
+            const uint64_t tj = t0 + j, hj = min((tj + 1) * kHdSub, S.nbits);
+            uint64_t at = j ? s_end[j - 1] : s_pred0;
+            uint32_t cn = 0;
+            s_nstart[j] = at;
+            hd_run<false, true>(T, lut_s, stage, base, S.nbits, at, hj, cn);
+            s_nend[j] = at;
+            s_ncnt[j] = cn;
+        }
+        __syncthreads();
+        if (redo) { my_start = s_nstart[tid]; my_end = s_nend[tid]; my_cnt = s_ncnt[tid]; s_end[tid] = my_end; }
+    }
+    if (!live) return;
+    start[g] = my_start;
+    end_out[g] = my_end;
+    count[g] = my_cnt;
+    if (end_prev && (my_end != end_at_entry || gave_up)) changed[f] = 1u;
+}
+
+// after a check: a frame none of whose ends moved is settled for good
+__global__ __launch_bounds__(256) void k_hdb_settle(uint32_t *__restrict__ changed, uint32_t *__restrict__ done, uint32_t nf) {
+    for (uint32_t f = blockIdx.x * 256 + threadIdx.x; f < nf; f += gridDim.x * 256) {
+        if (!changed[f]) done[f] = 1u;
+        changed[f] = 0u;
+    }
+}
+
+// k_hd_write<false, 1> for a batch: the settled frames' symbols (frame f's symbol index = off[g] - off[sub0])
+__global__ __launch_bounds__(kHdThreads) void k_hdb_write(const HdbFrame *__restrict__ fr, const uint32_t *__restrict__ blk_frame, const uint64_t *__restrict__ start,
+                                                          const uint64_t *__restrict__ off, const uint32_t *__restrict__ done) {
+    extern __shared__ __align__(16) uint32_t hd_lds[];
+    const uint32_t f = blk_frame[blockIdx.x];
+    if (!done[f]) return;
+    const HdbFrame &F = fr[f];
+    const HdStream &S = F.S;
+    const HdTables &T = F.T;
+    uint32_t *lut_s = hd_lds;
+    uint32_t *stage = hd_lds + (T.use1 ? (1u << kHdLut) : 0u);
+    const uint32_t lb = blockIdx.x - F.blk0;
+    const uint64_t t = (uint64_t)lb * kHdThreads + threadIdx.x, g = F.sub0 + t;
+    const uint64_t base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, lb);
+    if (t >= F.nsub) return;
+    const uint64_t hi = min((t + 1) * kHdSub, S.nbits), nsyms = F.nsyms;
+    uint64_t at = start[g], idx = off[g] - off[F.sub0], widx = idx;
+    if (at >= hi) return;
+    uint8_t *rgb = F.out;
+    HdBits<false> B;
+    B.seek(stage, (uint32_t)(at - base));
+    auto next = [&](uint32_t &key) -> bool {
+        if (at >= hi || widx >= nsyms) return false;
+        const HdSym sy = hd_lookup<true>(T, lut_s, B.window());
+        if (at + sy.len > S.nbits) { at = hi; return false; }
+        at += sy.len;
+        B.skip(sy.len);
+        widx++;
+        key = sy.key;
+        return true;
+    };
+    auto put1 = [&](uint32_t key) {
+        rgb[3 * idx] = (uint8_t)(key >> 16); rgb[3 * idx + 1] = (uint8_t)(key >> 8); rgb[3 * idx + 2] = (uint8_t)key;
+        idx++;
+    };
+    uint32_t k0, k1, k2, k3;
+    while ((idx & 3) && next(k0)) put1(k0);
+    for (;;) {
+        if (!next(k0)) break;
+        if (!next(k1)) { put1(k0); break; }
+        if (!next(k2)) { put1(k0); put1(k1); break; }
+        if (!next(k3)) { put1(k0); put1(k1); put1(k2); break; }
+        uint32_t *dst = reinterpret_cast<uint32_t *>(rgb + 3 * idx);   // (idx is a multiple of 4 and out 4-byte aligned)
+        dst[0] = ((k0 >> 16) & 255) | (((k0 >> 8) & 255) << 8) | ((k0 & 255) << 16) | (((k1 >> 16) & 255) << 24);
+        dst[1] = ((k1 >> 8) & 255) | ((k1 & 255) << 8) | (((k2 >> 16) & 255) << 16) | (((k2 >> 8) & 255) << 24);
+        dst[2] = (k2 & 255) | (((k3 >> 16) & 255) << 8) | (((k3 >> 8) & 255) << 16) | ((k3 & 255) << 24);
+        idx += 4;
+    }
+}
+
+// per frame: the symbols its payload holds and whether it settled (res[2 f], res[2 f + 1])
+__global__ __launch_bounds__(256) void k_hdb_verdict(const HdbFrame *__restrict__ fr, uint32_t nf, const uint64_t *__restrict__ off, const uint32_t *__restrict__ count,
+                                                     const uint32_t *__restrict__ done, uint64_t *__restrict__ res) {
+    for (uint32_t f = blockIdx.x * 256 + threadIdx.x; f < nf; f += gridDim.x * 256) {
+        const HdbFrame &F = fr[f];
+        if (!F.nsub) { res[2 * f] = F.nsyms; res[2 * f + 1] = 1; continue; }   // (a filled frame)
+        const uint64_t last = F.sub0 + F.nsub - 1;
+        res[2 * f] = off[last] + count[last] - off[F.sub0];
+        res[2 * f + 1] = done[f];
+    }
+}
+
+int huff_decode_batch_dev(Ctx *c, std::vector<HdBatchFrame> &fv) {
+    const uint32_t nf = (uint32_t)fv.size();
+    if (!nf) return CNIIC_OK;
+    // ---- per frame: tables' sizes, subsequences, blocks
+    std::vector<HdbFrame> fr(nf);
+    std::vector<uint64_t> tab_at(nf), lut2_at(nf);
+    uint64_t tab_bytes = 0, lut2_bytes = 0, nsub_all = 0;
+    uint32_t nblk = 0, lut2_grid = 0;
+    for (uint32_t f = 0; f < nf; f++) {
+        const HdBatchFrame &b = fv[f];
+        const LeafTable &lt = *b.lt;
+        const uint64_t n = lt.n();
+        if (n == 0 || n >= (1u << 20) || lt.too_deep || lt.max_len > 32 || !b.nsyms || (n > 1 && !b.payload_bytes) ||
+            (reinterpret_cast<uintptr_t>(b.out_d) & 3))
+            return c->fail(CNIIC_ERR_BAD_ARG, "huff_decode_batch_dev: frame %u is not for this route", f);
+        HdbFrame &F = fr[f];
+        memset(&F, 0, sizeof F);
+        F.nsyms = b.nsyms;
+        F.out = b.out_d;
+        F.key0 = lt.key[0];
+        F.T.n = (uint32_t)n;
+        tab_at[f] = tab_bytes;
+        tab_bytes += ((n * 13 + 15) & ~15ull) + 16;   // code u64[n] | key u32[n] | len u8[n]
+        F.sub0 = nsub_all;
+        F.blk0 = nblk;
+        if (n == 1) continue;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(b.payload);
+        F.S.w = reinterpret_cast<const uint32_t *>(a & ~uintptr_t(3));
+        F.S.bit0 = (a & 3) * 8;
+        F.S.nbits = F.S.bit0 + b.payload_bytes * 8;
+        F.S.nwords = ceil_div(F.S.nbits, 32);
+        F.S.warm = b.payload_bytes * 8 >= b.nsyms * 12 ? 384 : 128;   // (as huff_decode_tables_dev)
+        F.T.bits2 = lt.max_len > (uint32_t)kHdLut ? std::min<uint32_t>(lt.max_len, 18u) : 0u;
+        F.T.use1 = hd_use_first_table(b.payload_bytes * 8, b.nsyms, F.T.bits2) ? 1u : 0u;
+        lut2_at[f] = lut2_bytes;
+        if (F.T.bits2) { lut2_bytes += 8ull << F.T.bits2; lut2_grid = std::max(lut2_grid, (1u << F.T.bits2) / 256); }
+        F.nsub = ceil_div(F.S.nbits, kHdSub);
+        F.max_rounds = F.nsub <= kHdPhasesMaxSub ? kHdRoundsShort : kHdMaxRounds;
+        nsub_all += F.nsub;
+        if (nsub_all > 0xffffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "huff_decode_batch_dev: payloads too long");
+        nblk += (uint32_t)ceil_div(F.nsub, kHdThreads);
+    }
+    // ---- the leaf tables, descriptors and block map: staged in pinned memory, one copy up
+    const uint64_t fr_at = tab_bytes, map_at = fr_at + ((nf * sizeof(HdbFrame) + 15) & ~15ull), up_bytes = map_at + 4ull * nblk + 16;
+    const uint64_t res_at = (up_bytes + 15) & ~15ull;   // (the verdicts come back behind it)
+    DevBuf up_d, lut1_d, lut2_d;
+    CNIIC_HIP_TRY(c, up_d.alloc(up_bytes));
+    CNIIC_HIP_TRY(c, lut1_d.alloc((uint64_t)nf << (kHdLut + 2)));
+    CNIIC_HIP_TRY(c, lut2_d.alloc(std::max<uint64_t>(lut2_bytes, 16)));
+    CNIIC_HIP_TRY(c, ctx_pinned_huf(c, res_at + 16ull * nf));
+    uint8_t *ph = static_cast<uint8_t *>(c->pinned_huf);
+    uint8_t *ud = up_d.as<uint8_t>();
+    for (uint32_t f = 0; f < nf; f++) {
+        const LeafTable &lt = *fv[f].lt;
+        const uint64_t n = lt.n(), at = tab_at[f];
+        memcpy(ph + at, lt.code.data(), n * 8);
+        memcpy(ph + at + n * 8, lt.key.data(), n * 4);
+        memcpy(ph + at + n * 12, lt.len.data(), n);
+        HdbFrame &F = fr[f];
+        F.T.code = reinterpret_cast<const uint64_t *>(ud + at);
+        F.T.key = reinterpret_cast<const uint32_t *>(ud + at + n * 8);
+        F.T.len = ud + at + n * 12;
+        F.T.lut1 = lut1_d.as<uint32_t>() + ((uint64_t)f << kHdLut);
+        F.T.lut2 = F.T.bits2 ? reinterpret_cast<const uint2 *>(lut2_d.as<uint8_t>() + lut2_at[f]) : nullptr;
+        F.T.lut3 = nullptr;
+    }
+    memcpy(ph + fr_at, fr.data(), nf * sizeof(HdbFrame));
+    uint32_t *map_h = reinterpret_cast<uint32_t *>(ph + map_at);
+    for (uint32_t f = 0; f < nf; f++)
+        for (uint32_t b = 0; b < (uint32_t)ceil_div(fr[f].nsub, kHdThreads); b++) map_h[fr[f].blk0 + b] = f;
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(ud, ph, up_bytes, hipMemcpyHostToDevice, c->stream));
+    const HdbFrame *fr_d = reinterpret_cast<const HdbFrame *>(ud + fr_at);
+    const uint32_t *map_d = reinterpret_cast<const uint32_t *>(ud + map_at);
+    // ---- tables (one launch per kind) and the one-leaf frames
+    hipLaunchKernelGGL(k_hdb_build_lut, dim3((1u << kHdLut) / 256, nf), dim3(256), 0, c->stream, fr_d, 0u);
+    if (lut2_grid) hipLaunchKernelGGL(k_hdb_build_lut, dim3(lut2_grid, nf), dim3(256), 0, c->stream, fr_d, 1u);
+    hipLaunchKernelGGL(k_hdb_fill, dim3(64, nf), dim3(256), 0, c->stream, fr_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    volatile uint64_t *res_h = reinterpret_cast<volatile uint64_t *>(ph + res_at);
+    for (uint32_t f = 0; f < nf; f++) fv[f].status = 0;
+    if (!nblk) {   // one-leaf frames only
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CNIIC_OK;
+    }
+    // ---- boundaries: pass 0 and kHdBlindChecks checks, offsets and symbols straight behind, one look
+    DevBuf start_d, end_a, end_b, count_d, off_d, tot_d, flags_d, res_d;
+    CNIIC_HIP_TRY(c, start_d.alloc(nsub_all * 8));
+    CNIIC_HIP_TRY(c, end_a.alloc(nsub_all * 8));
+    CNIIC_HIP_TRY(c, end_b.alloc(nsub_all * 8));
+    CNIIC_HIP_TRY(c, count_d.alloc(nsub_all * 4));
+    CNIIC_HIP_TRY(c, off_d.alloc(nsub_all * 8));
+    CNIIC_HIP_TRY(c, tot_d.alloc(8));
+    CNIIC_HIP_TRY(c, flags_d.alloc(8ull * nf));   // changed[nf] | done[nf]
+    CNIIC_HIP_TRY(c, res_d.alloc(16ull * nf));
+    CNIIC_HIP_TRY(c, hipMemsetAsync(flags_d.p, 0, 8ull * nf, c->stream));
+    uint32_t *changed = flags_d.as<uint32_t>(), *done = changed + nf;
+    const uint32_t sgrid = (uint32_t)std::min<uint64_t>(ceil_div(nf, 256), 1024);
+    uint64_t *cur = end_a.as<uint64_t>(), *nxt = end_b.as<uint64_t>();
+    auto check = [&]() {
+        hipLaunchKernelGGL(k_hdb_pass, dim3(nblk), dim3(kHdThreads), kHdLds, c->stream, fr_d, map_d, (const uint64_t *)cur, nxt, start_d.as<uint64_t>(), count_d.as<uint32_t>(),
+                           changed, (const uint32_t *)done);
+        hipLaunchKernelGGL(k_hdb_settle, dim3(sgrid), dim3(256), 0, c->stream, changed, done, nf);
+        std::swap(cur, nxt);
+    };
+    auto write_look = [&]() -> int {
+        CNIIC_TRY(pack_scan(c, count_d.as<uint32_t>(), (uint32_t)nsub_all, off_d.as<uint64_t>(), tot_d.as<uint64_t>()));
+        hipLaunchKernelGGL(k_hdb_write, dim3(nblk), dim3(kHdThreads), kHdLds, c->stream, fr_d, map_d, (const uint64_t *)start_d.as<uint64_t>(), (const uint64_t *)off_d.as<uint64_t>(),
+                           (const uint32_t *)done);
+        hipLaunchKernelGGL(k_hdb_verdict, dim3(sgrid), dim3(256), 0, c->stream, fr_d, nf, (const uint64_t *)off_d.as<uint64_t>(), (const uint32_t *)count_d.as<uint32_t>(),
+                           (const uint32_t *)done, res_d.as<uint64_t>());
+        CNIIC_HIP_TRY(c, hipGetLastError());
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(const_cast<uint64_t *>(res_h), res_d.p, 16ull * nf, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CNIIC_OK;
+    };
+    {
+        ScopedKernelTimer tp(c, "decode_batch_pass");   // (stage timers: CNIIC_OPT_STAGE_TIMERS; they synchronise)
+        hipLaunchKernelGGL(k_hdb_pass, dim3(nblk), dim3(kHdThreads), kHdLds, c->stream, fr_d, map_d, (const uint64_t *)nullptr, cur, start_d.as<uint64_t>(), count_d.as<uint32_t>(),
+                           changed, (const uint32_t *)done);
+        for (int r = 0; r < kHdBlindChecks; r++) check();
+        CNIIC_HIP_TRY(c, hipGetLastError());
+        tp.stop(1 + kHdBlindChecks);
+    }
+    {
+        ScopedKernelTimer tw(c, "decode_batch_write");
+        CNIIC_TRY(write_look());
+        tw.stop();
+    }
+    // ---- frames that have not settled: further checks, one look at the whole batch per check
+    auto unsettled = [&]() { uint32_t u = 0; for (uint32_t f = 0; f < nf; f++) u += res_h[2 * f + 1] ? 0u : 1u; return u; };
+    if (unsettled()) {
+        for (int r = kHdBlindChecks; r < kHdbMaxPasses; r++) {
+            ScopedKernelTimer tp(c, "decode_batch_pass");
+            check();
+            CNIIC_HIP_TRY(c, hipGetLastError());
+            tp.stop();
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(const_cast<uint64_t *>(res_h), done, 4ull * nf, hipMemcpyDeviceToHost, c->stream));
+            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            const volatile uint32_t *dn = reinterpret_cast<const volatile uint32_t *>(res_h);
+            uint32_t left = 0;
+            for (uint32_t f = 0; f < nf; f++) left += dn[f] || !fr[f].nsub ? 0u : 1u;
+            if (!left) break;
+        }
+        CNIIC_TRY(write_look());   // (the frames settled before are written once more: the same symbols)
+    }
+    for (uint32_t f = 0; f < nf; f++) fv[f].status = !res_h[2 * f + 1] ? 2 : res_h[2 * f] < fv[f].nsyms ? 1 : 0;
+    return CNIIC_OK;
 }
 
 int keys_to_rgb(Ctx *c, const uint32_t *keys_d, uint64_t n, uint8_t *rgb_d) {

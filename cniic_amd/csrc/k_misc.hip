@@ -325,6 +325,38 @@ int mse_rgb(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, double
     return CNIIC_OK;
 }
 
+// the same for F pairs of npx pixels each (pair f at a + f npx 3, b + f npx 3): the pair on blockIdx.y, one total per pair
+__global__ __launch_bounds__(256) void k_sqerr_batch(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint64_t nbytes,
+                                                     unsigned long long *__restrict__ total) {
+    const uint64_t at = (uint64_t)blockIdx.y * nbytes, stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t s = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbytes; i += stride) {
+        int d = (int)a[at + i] - (int)b[at + i];
+        s += (uint32_t)(d * d);
+    }
+    s = wave_reduce_sum64(s);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&total[blockIdx.y], (unsigned long long)s);
+}
+
+int mse_rgb_batch(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, uint32_t frames, double *mse_h) {
+    if (!npx) { for (uint32_t f = 0; f < frames; f++) mse_h[f] = 0.0; return CNIIC_OK; }
+    DevBuf tot;
+    CNIIC_HIP_TRY(c, tot.alloc(8ull * frames));
+    CNIIC_HIP_TRY(c, hipMemsetAsync(tot.p, 0, 8ull * frames, c->stream));
+    // (about as many blocks in all as one image of the batch's total size would get)
+    const uint32_t gx = std::max<uint32_t>(1, grid_for(npx * 3 * frames, 256, 256 * 8) / frames);
+    for (uint32_t f0 = 0; f0 < frames; f0 += 65535) {   // (gridDim.y)
+        const uint64_t at = (uint64_t)f0 * npx * 3;
+        hipLaunchKernelGGL(k_sqerr_batch, dim3(gx, std::min(frames - f0, 65535u)), dim3(256), 0, c->stream, a_d + at, b_d + at, npx * 3, tot.as<unsigned long long>() + f0);
+    }
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    std::vector<unsigned long long> t(frames);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(t.data(), tot.p, 8ull * frames, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t f = 0; f < frames; f++) mse_h[f] = (double)t[f] / (double)npx;   // (as mse_rgb: the exact integer sum over npx)
+    return CNIIC_OK;
+}
+
 // ---------------------------------------------------------------- synthetic images
 // "U": byte k of the splitmix64 stream seeded with `seed` (LSB-first bytes of successive outputs).
 // "P": per channel, integer bilinear interpolation of a hashed 64-px lattice plus +-8 noise.

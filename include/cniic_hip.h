@@ -386,8 +386,19 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
 /* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics. */
 int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t n,
                            uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
+/* Codec::decode of `frames` streams: stream f at bytes + f * stride, lens[f] bytes (exactly what cniic_codec_encode_batch writes).
+ * Image f goes to rgb + f * img_stride (capacity img_stride bytes); its dimensions go to w[f], h[f].  Host or device memory on either
+ * side.  Streams of one batch may carry different dimensions.  `hufman` and `cluster-colors` frames are decoded together in one set of
+ * launches; other codecs, and the frames that route does not take, are decoded one by one on the worker contexts of
+ * cniic_codec_encode_batch (CNIIC_OPT_BATCH_STREAMS at a time).  rcs (may be NULL): per-frame status, identical to what
+ * cniic_codec_decode returns for that stream alone.  The call returns the first failure; cniic_last_error carries that frame's
+ * message.  frames == 0 returns CNIIC_OK. */
+int32_t cniic_codec_decode_batch(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens,
+                                 uint32_t frames, uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* bench::compute_error (src/bench.rs:95-104): MSE between two RGB8 images. */
 int32_t cniic_mse(cniic_ctx *ctx, const uint8_t *a, const uint8_t *b, uint64_t npx, double *mse);
+/* bench::compute_error for `frames` image pairs of npx pixels each (a + f*npx*3, b + f*npx*3): mse[f] == cniic_mse of that pair. */
+int32_t cniic_mse_batch(cniic_ctx *ctx, const uint8_t *a, const uint8_t *b, uint64_t npx, uint32_t frames, double *mse);
 
 /* ------------------------------------------------------------------ synthetic inputs (bench/tests) */
 #define CNIIC_SYNTH_UNIFORM 0  /* "U": splitmix64 byte stream                               */
