@@ -33,7 +33,7 @@ SYMBOLS = [
     "cniic_hilbert_linearize", "cniic_hilbert_delta", "cniic_hilbert_delta_hist", "cniic_huf_encode_all",
     "cniic_huf_size", "cniic_codec_parse", "cniic_codec_name", "cniic_codec_is_lossless", "cniic_codec_encode",
     "cniic_codec_encode_opts", "cniic_codec_encode_batch", "cniic_codec_decode", "cniic_codec_decode_batch", "cniic_mse", "cniic_mse_batch",
-    "cniic_synth_image",
+    "cniic_hilbert_rle_approx_encode", "cniic_synth_image",
 ]
 
 
@@ -339,6 +339,25 @@ class Context:
         if own:
             return rc, (out[:ln.value].tobytes() if rc == OK else b""), st.as_dict()
         return rc, ln.value, st.as_dict()
+
+    def hilbert_rle_approx_encode(self, d, img, w=None, h=None, out=None, allow=()):
+        """cniic_hilbert_rle_approx_encode: Hilbert { compress: RLE(d) }::encode for an f64 d (d == 0.0: the `hilbert(rle)` stream).
+        img: HxWx3 uint8 numpy array, or a device tensor / address with w,h given.  -> (rc, bytes) when out is None, else (rc, length)"""
+        if isinstance(img, np.ndarray):
+            img = np.ascontiguousarray(img, np.uint8)
+            h, w = img.shape[:2]
+        own = out is None
+        if own:
+            cap = 8 + w * h * 12
+            out = np.empty(cap, np.uint8)
+        else:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_hilbert_rle_approx_encode(self.h, C.c_double(d), _ptr(img), C.c_uint32(w), C.c_uint32(h), _ptr(out),
+                                                                 C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
 
     def encode_batch(self, expr, frames, w, h, F, out, stride, seed=0, max_iters=0, flags=0, allow=()):
         """cniic_codec_encode_batch: F images (one contiguous [F][h][w][3] buffer), each encoded on its own (its own palette), image f's

@@ -5,7 +5,12 @@
     data  = codec.encode(img)          # img: HxWx3 uint8
     img2  = codec.decode(data)         # None where the reference returns None / panics
     codec.name(), codec.is_lossless()
+
+    HilbertRleApprox(4.0)               # hilbert(rle(4)): its own class, AnyCodec.from_str does not build it
 """
+import math
+from decimal import Decimal
+
 from . import _lib
 
 
@@ -73,3 +78,40 @@ class AnyCodec(Codec):
     @classmethod
     def from_str(cls, expr, ctx=None):
         return cls(expr, ctx)
+
+
+def rust_f64_display(d):
+    """f64's Display (format!("{}", d)): the shortest digits that read back as d, never an exponent ("1", "0.5", "0.0000001",
+    "1000000000000000000000", "inf", "NaN", "-1", "-0")"""
+    d = float(d)
+    if math.isnan(d):
+        return "NaN"
+    if math.isinf(d):
+        return "inf" if d > 0 else "-inf"
+    s = format(Decimal(repr(d)), "f")   # repr: the shortest round-trip digits
+    if "." in s:
+        s = s.rstrip("0").rstrip(".")
+    return s
+
+
+class HilbertRleApprox(Codec):
+    """Hilbert { compress: RLE(d) } (src/codec/hilbertc.rs:12-98, rle_approx :200-299) for any f64 d.  cniic_codec_parse takes only
+    d == 0 (`hilbert(rle)`), so this codec has its own encode entry point; its streams decode as `hilbert(rle)` (same records)."""
+
+    def __init__(self, d, ctx=None):
+        self.d = float(d)
+        self.expr = "hilbert(rle)"   # the decoder (RleDecoder, hilbertc.rs:304-335)
+        self._ctx = ctx
+        self.last_stats = None
+
+    def encode(self, img, **kw):
+        rc, data = self.ctx.hilbert_rle_approx_encode(self.d, img, **kw)
+        return data
+
+    def name(self):
+        if self.d == 0.0:
+            return "hilbert-rle"                                     # hilbertc.rs:83
+        return "hilbert-rle-approx_%s" % rust_f64_display(self.d)   # :84
+
+    def is_lossless(self):
+        return self.d == 0.0

@@ -890,6 +890,16 @@ int32_t cniic_codec_encode(cniic_ctx *c, const char *expr, const uint8_t *rgb, u
     return codec_encode(c, d, in.d, w, h, nullptr, out, cap, len, stats);
 }
 
+int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *c, double d, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap,
+                                        uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "hilbert_rle_approx_encode: null argument");
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
+    return encode_hilbert_rle_approx(c, d, in.d, w, h, out, cap, len);
+}
+
 int32_t cniic_codec_encode_opts(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w,
                                 uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     LOCK(c);

@@ -1013,6 +1013,31 @@ static int encode_hilbert_rle(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t
     return so.finish();
 }
 
+// ------------------------------------------------------------------ Hilbert{RLE(d)}::encode (hilbertc.rs:26-45): d == 0.0 (-0.0 too) takes the
+// exact branch (:33-39), any other d (negative, NaN and infinite ones included) the running average (:40-45, rle_approx :200-299)
+int encode_hilbert_rle_approx(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len) {
+    if ((uint64_t)w * h >= (1ull << 32)) return c->fail(CNIIC_ERR_BAD_ARG, "image too large");
+    if (d == 0.0) return encode_hilbert_rle(c, rgb_d, w, h, out, cap, len);
+    const uint64_t n = (uint64_t)w * h;
+    std::vector<uint8_t> header;
+    put_u32(header, w);  // img.dimensions().serialize (:27)
+    put_u32(header, h);
+    StreamOut so(c, out, cap, len);
+    if (n == 0) {
+        CNIIC_TRY(so.begin(header, 0));
+        return so.finish();
+    }
+    DevBuf lin;
+    CNIIC_HIP_TRY(c, lin.alloc(n * 3));
+    CNIIC_TRY(hilbert_linearize(c, rgb_d, w, h, lin.as<uint8_t>()));  // hilbert::linearize (:29)
+    RlePlan plan;
+    CNIIC_TRY(rle_approx_plan(c, lin.as<uint8_t>(), n, d, &plan));    // rle_approx (:41)
+    CNIIC_TRY(so.begin_sized(header.size(), plan.nruns * 12, /*zero=*/false));  // count.serialize + color.serialize per run (:42-43)
+    CNIIC_TRY(so.put_header(header));
+    CNIIC_TRY(rle_approx_emit(c, lin.as<uint8_t>(), &plan, reinterpret_cast<uint32_t *>(so.dev + 8)));
+    return so.finish();
+}
+
 int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, uint32_t h, const cniic_kmeans_opts *opts,
                  uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);

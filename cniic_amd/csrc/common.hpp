@@ -624,6 +624,11 @@ struct RlePlan { uint64_t n = 0, nruns = 0; uint32_t nchunks = 0; DevBuf flags, 
 int rle_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, RlePlan *plan);                       // counts the runs (syncs)
 int rle_emit(Ctx *c, const uint8_t *lin_d, const RlePlan *plan, uint32_t *out_words_d);      // 12-byte records
 int rle_expand_dev(Ctx *c, const uint8_t *rec_d, uint64_t R, uint64_t tail_bytes, uint64_t n, uint8_t *lin_d, int *status);  // RleDecoder
+int rle_offsets(Ctx *c, const uint32_t *chunk_runs_d, uint32_t nchunks, uint64_t *run_off_d, uint64_t *total_d);  // runs before each chunk
+// ---- k_rle_approx.hip: run-length coding with the running-average test, d != 0 (hilbertc.rs:200-299); same plan, same records ----
+double rla_threshold(double d);                                                                // largest s with sqrt_rn(s) <= d
+int rle_approx_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, double d, RlePlan *plan);        // counts the runs (syncs)
+int rle_approx_emit(Ctx *c, const uint8_t *lin_d, const RlePlan *plan, uint32_t *out_words_d);  // 12-byte records, average colours
 
 // ---- k_hilbert.hip ----
 int hilbert_xy(Ctx *c, uint32_t w, uint32_t h, uint32_t *xy_d);

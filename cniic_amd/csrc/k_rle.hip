@@ -196,6 +196,15 @@ __global__ __launch_bounds__(kRleThreads) void k_rle_records(const uint8_t *__re
     for (uint32_t i = threadIdx.x; i < 3 * s_total; i += kRleThreads) o[i] = s_rec[i];
 }
 
+// run_off[c] = runs in the chunks before c, *total = all runs (device; enqueued on the context's stream)
+int rle_offsets(Ctx *c, const uint32_t *chunk_runs_d, uint32_t nchunks, uint64_t *run_off_d, uint64_t *total_d) {
+    if (nchunks > 1024)  // (one block walking 64 chunks per thread took 0.11 ms at 16384^2)
+        return pack_scan(c, chunk_runs_d, nchunks, run_off_d, total_d);
+    hipLaunchKernelGGL(k_rle_offsets, dim3(1), dim3(1024), 0, c->stream, chunk_runs_d, nchunks, run_off_d, total_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
 // lin_d: the image in Hilbert order (3 B/px).  Phase 1 counts the runs (host out-param, stream synced) and keeps
 // its scratch in `plan`; phase 2 writes the records at out_words (device, 4-byte aligned).
 int rle_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, RlePlan *plan) {
@@ -225,11 +234,7 @@ int rle_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, RlePlan *plan) {
     }
     hipLaunchKernelGGL(k_rle_flags, dim3(nchunks), dim3(kRleThreads), 0, c->stream, lin_d, n, carry.as<uint64_t>(),
                        plan->flags.as<uint16_t>(), chunk_runs.as<uint32_t>());
-    if (nchunks > 1024)  // (one block walking 64 chunks per thread took 0.11 ms at 16384^2)
-        CNIIC_TRY(pack_scan(c, chunk_runs.as<uint32_t>(), nchunks, plan->run_off.as<uint64_t>(), tot.as<uint64_t>()));
-    else
-        hipLaunchKernelGGL(k_rle_offsets, dim3(1), dim3(1024), 0, c->stream, chunk_runs.as<uint32_t>(), nchunks, plan->run_off.as<uint64_t>(),
-                           tot.as<uint64_t>());
+    CNIIC_TRY(rle_offsets(c, chunk_runs.as<uint32_t>(), nchunks, plan->run_off.as<uint64_t>(), tot.as<uint64_t>()));
     CNIIC_HIP_TRY(c, hipGetLastError());
     uint64_t total = 0;
     CNIIC_HIP_TRY(c, hipMemcpyAsync(&total, tot.p, 8, hipMemcpyDeviceToHost, c->stream));

@@ -363,7 +363,7 @@ int32_t cniic_huf_size(int32_t sym_kind, const uint64_t *counts, uint64_t n, uin
 /* ------------------------------------------------------------------ Codec trait (src/codec.rs:14-19) */
 /* expr is the reference's --codec= expression: "hufman", "cluster-colors(256)" / "ccol(256)",
  * "voronoi(2048)", "delta", "hilbert(rle)" = "hilbert(rle(0))" (src/codec.rs:41-59, FromStr impls of each
- * codec; hilbertc.rs:341-397 for the last one, whose name() is "hilbert-rle"; rle(d != 0) and zip are not built). */
+ * codec; hilbertc.rs:341-397 for the last one, whose name() is "hilbert-rle"; rle(d != 0) has its own entry point, cniic_hilbert_rle_approx_encode; zip is not built). */
 int32_t cniic_codec_parse(const char *expr, int32_t *kind, uint32_t *arg);
 int32_t cniic_codec_name(const char *expr, char *buf, uint64_t cap);   /* Codec::name()        */
 int32_t cniic_codec_is_lossless(const char *expr);                     /* 1 / 0 / negative err */
@@ -383,6 +383,14 @@ int32_t cniic_codec_encode_opts(cniic_ctx *ctx, const char *expr, const cniic_km
  * stats (may be NULL): `frames` entries. */
 int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
                                  uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs, cniic_kmeans_stats *stats);
+/* Hilbert { compress: RLE(d) }::encode (hilbertc.rs:26-45; rle_approx :200-299): runs along the Hilbert scan that a pixel joins while its
+ * distance to the run's running average is <= d, recorded with the rounded average.  d == 0.0 (or -0.0) gives the `hilbert(rle)`
+ * stream; d < 0 or NaN accepts nothing, +inf everything.  cniic_codec_parse does not take `hilbert(rle(d))` for d != 0 (its u32
+ * argument cannot carry the f64): this is that codec's encode.  Host or device buffers; CNIIC_ERR_CAPACITY with *len = bytes needed,
+ * like cniic_codec_encode.  The stream decodes with cniic_codec_decode(ctx, "hilbert(rle)", ...): the records are the same
+ * (RleDecoder, hilbertc.rs:304-335). */
+int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *ctx, double d, const uint8_t *rgb, uint32_t w, uint32_t h,
+                                        uint8_t *out, uint64_t cap, uint64_t *len);
 /* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics. */
 int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t n,
                            uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
