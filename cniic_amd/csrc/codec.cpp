@@ -1341,8 +1341,11 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     if (bytes_dev) {
         uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
         for (uint32_t f = 0; f < F; f++) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
-        W = std::max<uint64_t>(8, std::min({W, stride, kBatchHeadsMax / F}));
-        CNIIC_TRY(fetch(W, 0, F - 1));
+        // (never wider than the stride, which is the source pitch of the strided copy: a stride below a header's 8 bytes reads fewer,
+        // and every frame goes to the single decode)
+        W = std::min<uint64_t>(std::max<uint64_t>(8, std::min(W, kBatchHeadsMax / F)), stride);
+        if (W) CNIIC_TRY(fetch(W, 0, F - 1));
+        else for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes; head_n[f] = 0; }
     } else {
         for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
     }

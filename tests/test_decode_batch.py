@@ -274,3 +274,15 @@ def test_mse_batch_bit_equal_to_mse():
             assert got[0] == 0.0
         assert ctx.mse_batch(a, b, 0, F) == [0.0] * F
         assert ctx.mse_batch(a, b, npx, 0) == []
+
+
+def test_fuzz_decode_batch():
+    """a few seconds of tests/fuzz_decode_batch.py: random batches (codecs, sizes, corruptions, strides, host / device buffers, route
+    knobs) frame by frame against the oracle and the single decode, with nothing written past a frame (CNIIC_FUZZ_SECONDS for longer)"""
+    import os
+    import torch
+    import cniic_amd
+    import fuzz_decode_batch
+    torch.cuda.set_stream(torch.cuda.Stream())   # (a context does not share the NULL stream)
+    with cniic_amd.Context(0, stream=torch.cuda.current_stream().cuda_stream) as ctx:
+        assert fuzz_decode_batch.run(ctx, float(os.environ.get("CNIIC_FUZZ_SECONDS", "6"))) > 0
