@@ -416,10 +416,15 @@ class Context:
         return [float(v[i]) for i in range(F)]
 
     def mse(self, a, b):
-        a = np.ascontiguousarray(a, np.uint8)
-        b = np.ascontiguousarray(b, np.uint8)
+        """cniic_mse of two RGB8 images of the same size: numpy arrays, or uint8 tensors (on the device: read in place, no copy)"""
+        a = a.contiguous() if hasattr(a, "data_ptr") else np.ascontiguousarray(a, np.uint8)
+        b = b.contiguous() if hasattr(b, "data_ptr") else np.ascontiguousarray(b, np.uint8)
+        na = a.numel() if hasattr(a, "numel") else a.size
+        nb = b.numel() if hasattr(b, "numel") else b.size
+        if na != nb:
+            raise ValueError("mse: images of %d and %d bytes" % (na, nb))
         v = C.c_double(0)
-        self._check(self._L.cniic_mse(self.h, _ptr(a), _ptr(b), C.c_uint64(a.size // 3), C.byref(v)))
+        self._check(self._L.cniic_mse(self.h, _ptr(a), _ptr(b), C.c_uint64(na // 3), C.byref(v)))
         return v.value
 
     def synth_image(self, kind, seed, w, h, out=None):

@@ -112,6 +112,9 @@ __global__ __launch_bounds__(256) void k_part_colscan(uint32_t *__restrict__ cou
         counts[(size_t)(idx / kPartCols) * kPartBuckets + k0 + idx % kPartCols] = tile[idx / kPartCols][idx % kPartCols];
 }
 
+// work items of a bucket of t entries (t + kPartSub - 1 would wrap for a bucket of more than 2^32 - kPartSub pixels)
+__device__ inline uint32_t part_items(uint32_t t) { return t / kPartSub + (t % kPartSub != 0); }
+
 // exclusive scans over the buckets: start[k] (entries) and item[k] (work items of k_part_hist); [kPartBuckets] = totals
 __global__ __launch_bounds__(1024) void k_part_starts(const uint32_t *__restrict__ total, uint32_t *__restrict__ start,
                                                       uint32_t *__restrict__ item) {
@@ -119,13 +122,13 @@ __global__ __launch_bounds__(1024) void k_part_starts(const uint32_t *__restrict
     constexpr uint32_t per = kPartBuckets / 1024;
     uint32_t t[per], e = 0, w = 0;
 #pragma unroll
-    for (uint32_t i = 0; i < per; i++) { t[i] = total[threadIdx.x * per + i]; e += t[i]; w += (t[i] + kPartSub - 1) / kPartSub; }
+    for (uint32_t i = 0; i < per; i++) { t[i] = total[threadIdx.x * per + i]; e += t[i]; w += part_items(t[i]); }
     uint32_t es = block_exclusive_scan<1024>(e, wsum);
     uint32_t ws = block_exclusive_scan<1024>(w, wsum);
 #pragma unroll
     for (uint32_t i = 0; i < per; i++) {
         start[threadIdx.x * per + i] = es; item[threadIdx.x * per + i] = ws;
-        es += t[i]; ws += (t[i] + kPartSub - 1) / kPartSub;
+        es += t[i]; ws += part_items(t[i]);
     }
     if (threadIdx.x == 1023) { start[kPartBuckets] = es; item[kPartBuckets] = ws; }
 }
@@ -138,10 +141,12 @@ __global__ __launch_bounds__(256) void k_part_hist(const uint16_t *__restrict__ 
     uint32_t a = 0, b = kPartBuckets;  // last bucket whose first item is <= it (buckets without entries have no items)
     while (b - a > 1) { const uint32_t mid = (a + b) >> 1; if (item[mid] <= it) a = mid; else b = mid; }
     const uint32_t k = a, nsub = item[k + 1] - item[k];
-    const uint32_t e0 = start[k] + (it - item[k]) * kPartSub, e1 = min(e0 + kPartSub, start[k + 1]);
+    // the item's entries counted from its first one: e0 + kPartSub (and e0 + e + 256) pass 2^32 when npx is near it
+    const uint32_t e0 = start[k] + (it - item[k]) * kPartSub, ne = min(kPartSub, start[k + 1] - e0);
+    const uint16_t *pay = payload + e0;
     for (uint32_t i = threadIdx.x; i < kPartBins; i += 256) hist[i] = 0;
     __syncthreads();
-    for (uint32_t e = e0 + threadIdx.x; e < e1; e += 256) atomicAdd(&hist[payload[e]], 1u);
+    for (uint32_t e = threadIdx.x; e < ne; e += 256) atomicAdd(&hist[pay[e]], 1u);
     __syncthreads();
     uint32_t *slice = table + ((size_t)k << kPartBits);
     for (uint32_t i = threadIdx.x; i < kPartBins; i += 256) {
