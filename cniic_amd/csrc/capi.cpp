@@ -261,12 +261,7 @@ int32_t cniic_kmeans_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *we
     CNIIC_TRY(to_caller(c, centroids, cent.data(), cent.size()));
     CNIIC_TRY(to_caller(c, members, mem.data(), mem.size() * 8));
     if (stats) *stats = st;
-    uint64_t min_cc = (uint64_t)(0.99 * (double)K);  // check_enough_active_clusters kmeans.rs:41-57
-    if (U < min_cc) min_cc = U;
-    if (st.active < min_cc)
-        return c->fail(CNIIC_ERR_FEW_ACTIVE, "Not enough active clusters: requested %u, got %llu (min allowed: %llu)", K,
-                       (unsigned long long)st.active, (unsigned long long)min_cc);
-    return CNIIC_OK;
+    return check_enough_active(c, K, U, st.active);   // (the caller has centroids, labels, members and stats of a failed run too)
 }
 
 int32_t cniic_kmeans_step_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *weight, uint64_t U, uint32_t K,
@@ -321,12 +316,7 @@ int32_t cniic_kmeans_xyrgb(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_
     CNIIC_TRY(to_caller(c, centroids, cent.data(), (size_t)K * sizeof(cniic_colorpos)));
     CNIIC_TRY(to_caller(c, members, mem.data(), (size_t)K * 8));
     if (stats) *stats = st;
-    uint64_t min_cc = (uint64_t)(0.99 * (double)K);
-    if (N < min_cc) min_cc = N;
-    if (st.active < min_cc)
-        return c->fail(CNIIC_ERR_FEW_ACTIVE, "Not enough active clusters: requested %u, got %llu (min allowed: %llu)", K,
-                       (unsigned long long)st.active, (unsigned long long)min_cc);
-    return CNIIC_OK;
+    return check_enough_active(c, K, N, st.active);
 }
 
 int32_t cniic_kmeans_step_xyrgb(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t K,
@@ -878,16 +868,22 @@ int32_t cniic_codec_is_lossless(const char *expr) {
     return codec_is_lossless(d) ? 1 : 0;
 }
 
-int32_t cniic_codec_encode(cniic_ctx *c, const char *expr, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap,
-                           uint64_t *len, cniic_kmeans_stats *stats) {
-    LOCK(c);
+// cniic_codec_encode / cniic_codec_encode_opts, the context's mutex held
+static int32_t encode_locked(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
+                             uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     c->ktimes.clear();
     CodecDesc d;
     if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
     if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode: null argument");
     In<uint8_t> in;
     CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
-    return codec_encode(c, d, in.d, w, h, nullptr, out, cap, len, stats);
+    return codec_encode(c, d, in.d, w, h, opts, out, cap, len, stats);
+}
+
+int32_t cniic_codec_encode(cniic_ctx *c, const char *expr, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap,
+                           uint64_t *len, cniic_kmeans_stats *stats) {
+    LOCK(c);
+    return encode_locked(c, expr, nullptr, rgb, w, h, out, cap, len, stats);
 }
 
 int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *c, double d, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap,
@@ -897,19 +893,13 @@ int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *c, double d, const uint8_t *r
     if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "hilbert_rle_approx_encode: null argument");
     In<uint8_t> in;
     CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
-    return encode_hilbert_rle_approx(c, d, in.d, w, h, out, cap, len);
+    return encode_hilbert_rle(c, d, in.d, w, h, out, cap, len);
 }
 
 int32_t cniic_codec_encode_opts(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w,
                                 uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     LOCK(c);
-    c->ktimes.clear();
-    CodecDesc d;
-    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
-    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode: null argument");
-    In<uint8_t> in;
-    CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
-    return codec_encode(c, d, in.d, w, h, opts, out, cap, len, stats);
+    return encode_locked(c, expr, opts, rgb, w, h, out, cap, len, stats);
 }
 
 // the first S worker contexts of a batch call (created on first use), with this context's route switches and its injected scan (a view
@@ -951,22 +941,13 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
         wk->ps_div = S;                        // ... and the persistent K-means launch an S-th of the CUs, so that S of them are resident side by side
     }
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
-    std::atomic<uint32_t> next{0};
     std::vector<int32_t> status(frames, CNIIC_OK);
-    auto run = [&](uint32_t i) {
+    parallel_for(frames, S, [&](uint32_t f, uint32_t i) {
         cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
-        for (;;) {
-            const uint32_t f = next.fetch_add(1);
-            if (f >= frames) break;
-            cniic_kmeans_stats st{};
-            status[f] = cniic_codec_encode_opts(wk, expr, opts, rgb + (uint64_t)f * img_bytes, w, h, out + (uint64_t)f * stride, stride, &lens[f], &st);
-            if (stats) stats[f] = st;
-        }
-    };
-    std::vector<std::thread> th;
-    for (uint32_t i = 1; i < S; i++) th.emplace_back(run, i);
-    run(0);
-    for (auto &t : th) t.join();
+        cniic_kmeans_stats st{};
+        status[f] = cniic_codec_encode_opts(wk, expr, opts, rgb + (uint64_t)f * img_bytes, w, h, out + (uint64_t)f * stride, stride, &lens[f], &st);
+        if (stats) stats[f] = st;
+    });
     int32_t first = CNIIC_OK;
     for (uint32_t f = 0; f < frames; f++) {
         if (rcs) rcs[f] = status[f];
@@ -1010,21 +991,12 @@ int32_t cniic_codec_decode_batch(cniic_ctx *c, const char *expr, const uint8_t *
     if (!rest.empty()) {
         const uint32_t S = (uint32_t)std::min<uint64_t>(rest.size(), std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
         CNIIC_TRY(batch_workers_ready(c, S, "codec_decode_batch"));
-        std::atomic<uint32_t> next{0};
-        auto run = [&](uint32_t i) {
+        parallel_for((uint32_t)rest.size(), S, [&](uint32_t j, uint32_t i) {
             cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
-            for (;;) {
-                const uint32_t j = next.fetch_add(1);
-                if (j >= rest.size()) break;
-                const uint32_t f = rest[j];
-                status[f] = cniic_codec_decode(wk, expr, bytes + (uint64_t)f * stride, lens[f], rgb + (uint64_t)f * img_stride, img_stride, &w[f], &h[f]);
-                if (status[f] != CNIIC_OK) msg[f] = wk->err;
-            }
-        };
-        std::vector<std::thread> th;
-        for (uint32_t i = 1; i < S; i++) th.emplace_back(run, i);
-        run(0);
-        for (auto &t : th) t.join();
+            const uint32_t f = rest[j];
+            status[f] = cniic_codec_decode(wk, expr, bytes + (uint64_t)f * stride, lens[f], rgb + (uint64_t)f * img_stride, img_stride, &w[f], &h[f]);
+            if (status[f] != CNIIC_OK) msg[f] = wk->err;
+        });
     }
     int32_t first = CNIIC_OK;
     for (uint32_t f = 0; f < frames; f++) {

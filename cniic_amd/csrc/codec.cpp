@@ -1,4 +1,4 @@
-// codec.cpp -- host-side mirror of the reference's Codec trait (src/codec.rs:14-19) for the four
+// codec.cpp -- host-side mirror of the reference's Codec trait (src/codec.rs:14-19) for the five
 // codecs on the hot path, driving the HIP kernels.  Same names (Codec::name), same lossless flags,
 // same --codec= expressions (FromStr impls), same wire format, same failure points.
 //
@@ -6,22 +6,20 @@
 //   ClusterColors   src/codec/clusterc.rs:17 dedup -> K-means -> remap -> Hufman
 //   VoronoiCluster  src/codec/clusterc.rs:147 5-D K-means, centroids only; Voronoi repaint on decode
 //   Delta           src/codec/hilbertc.rs:404 Hilbert gather -> neighbour delta -> huf::encode_all
-//   Hilbert{RLE(0)} src/codec/hilbertc.rs:12  Hilbert gather -> exact run-length records
-#include <algorithm>
-#include <atomic>
-#include <thread>
-
+//   Hilbert{RLE(d)} src/codec/hilbertc.rs:12  Hilbert gather -> run-length records: exact for d == 0, else
+//                                             the running average (k_rle_approx.hip; an entry point of its own, not a --codec= expression)
 #include "codec.hpp"
 
 #include <algorithm>
 #include <cctype>
 #include <cstring>
-#include <map>
 #include <memory>
 
 #include "huff_host.hpp"
 
 namespace cniic {
+
+HostTrace &host_trace() { static thread_local HostTrace t; return t; }
 
 // ------------------------------------------------------------------ FromStr (codec.rs:41-59)
 static bool match_fun_u32(const std::string &s, const char *const *names, uint32_t *arg) {
@@ -47,7 +45,8 @@ static bool match_fun_u32(const std::string &s, const char *const *names, uint32
 }
 
 // Hilbert::from_str (hilbertc.rs:341-397): fun_call named ^[Hh]ilbert$ with one argument, `rle` or `rle(<f64>)`.
-// Only the exact method (d == 0.0) is built; rle(d != 0) (a sequential running average) and zip are not.
+// As a --codec= expression only the exact method (d == 0.0) is taken; rle(d != 0) has an entry point of its own
+// (cniic_hilbert_rle_approx_encode), zip is not built.
 static bool match_hilbert_rle(const std::string &s) {
     if (s.compare(0, 8, "hilbert(") != 0 && s.compare(0, 8, "Hilbert(") != 0) return false;
     if (s.size() < 10 || s.back() != ')') return false;
@@ -65,7 +64,7 @@ static bool match_hilbert_rle(const std::string &s) {
 bool parse_codec(const char *expr, CodecDesc *out) {
     if (!expr) return false;
     const std::string s(expr);
-    // alternatives in the order of gen_all! (codec.rs:120-127); Hilbert and Zip are out of scope
+    // alternatives in the order of gen_all! (codec.rs:120-127); Zip is out of scope
     static const char *const cc[] = {"cluster-colors", "cluster-col", "clustercolors", "clustercol",
                                      "c-colors", "c-col", "ccolors", "ccol", nullptr};  // c(?:luster)?-?col(?:ors)?
     static const char *const vo[] = {"voronoi", nullptr};
@@ -138,6 +137,173 @@ struct StreamOut {
     }
 };
 
+// F streams at a fixed distance (cc_finish_frames): assembled where the caller wants them when that is 4-byte aligned device memory,
+// otherwise in a staging buffer that is copied out once.
+struct FramesOut {
+    Ctx *c;
+    uint8_t *out;
+    uint64_t stride;
+    uint32_t F;
+    bool out_dev = false, direct = false;
+    DevBuf staging;
+    uint8_t *dev = nullptr;
+    FramesOut(Ctx *ctx, uint8_t *caller, uint64_t stride_bytes, uint32_t frames) : c(ctx), out(caller), stride(stride_bytes), F(frames) {}
+    int begin() {   // (zero padding behind a header = the pre-zeroed payload)
+        out_dev = is_device_ptr(out);
+        direct = out_dev && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+        dev = out;
+        if (!direct) { CNIIC_HIP_TRY(c, staging.alloc(stride * F + 16)); dev = staging.as<uint8_t>(); }
+        CNIIC_HIP_TRY(c, hipMemsetAsync(dev, 0, stride * F, c->stream));
+        return CNIIC_OK;
+    }
+    // every stream, padded to whole words, must fit between two streams (too_long: somebody has already found one that does not)
+    int check_lens(const uint64_t *lens, bool too_long = false) const {
+        for (uint32_t f = 0; f < F; f++)
+            if (too_long || ((lens[f] + 3) & ~3ull) > stride)
+                return c->fail(CNIIC_ERR_CAPACITY, "encode: stream of frame %u is %llu bytes, %llu between streams", f, (unsigned long long)lens[f], (unsigned long long)stride);
+        return CNIIC_OK;
+    }
+    // packed / predicted: every frame's payload bits as the pack counted them and as its histogram says
+    int finish(const uint64_t *packed, const uint64_t *predicted) {
+        for (uint32_t f = 0; f < F; f++)
+            if (packed[f] != predicted[f])
+                return c->fail(CNIIC_ERR_HIP, "cluster-colors: frame %u packed %llu bits, its histogram predicts %llu", f, (unsigned long long)packed[f], (unsigned long long)predicted[f]);
+        if (!direct) {
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(out, dev, stride * F, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        return CNIIC_OK;
+    }
+};
+
+// ------------------------------------------------------------------ the Huffman code stage: build() and the decoder (huf.rs:31-34)
+// From the dense histogram's compaction to every distinct symbol's code in HBM (len_d / code_d, in the order of keys_d), the
+// payload's bit count, and the serialised decoder.  A large alphabet (a photograph's colours or differences) leaves the host the
+// merge of the tree at most: the leaves come back sorted by (count, key), codes and decoder are the GPU's.  A small one is built
+// on the host.  The callers differ in what they enqueue, and where they wait, between the steps -- so the steps are theirs to call:
+//   begin          the distinct symbols and their counts; large: the leaves sorted, and when the counts come in runs the whole
+//                  tree on the GPU (tree_built); what the host's build reads starts towards pinned memory
+//     (the caller waits for the stream)
+//   build          large: the host's merge, the codes (huff_tree_codes), their totals start towards the host -- totals_pending:
+//                  the caller waits once more before bits().  Small: tree and codes on the host.  tree_built: nothing left.
+//   bits           the payload's bits
+//   upload_codes   small: the host's codes to len_d / code_d (large: they are there)
+//   write_decoder  the stream's header with the serialised decoder behind it, at the start of a StreamOut
+struct HuffCodeStage {
+    Ctx *c;
+    int sym_kind;
+    uint64_t U = 0;   // distinct symbols
+    bool gpu_codes = false, tree_built = false, totals_pending = false;
+    DevBuf keys_d, counts_d, len_d, code_d;
+    HuffCodeStage(Ctx *ctx, int kind) : c(ctx), sym_kind(kind) {}
+    uint64_t decoder_bytes() const { return huff_tree_bytes(sym_kind, U); }   // follows from U alone: U leaves and U - 1 branch tags
+
+    // table_d / plan: the dense histogram after hist_compact_count; n: symbols in the stream
+    int begin(uint32_t *table_d, const CompactPlan *plan, uint64_t n) {
+        U = plan->n_unique;
+        CNIIC_HIP_TRY(c, keys_d.alloc(U * 4));
+        CNIIC_HIP_TRY(c, counts_d.alloc(U * 8));
+        CNIIC_TRY(hist_compact_write(c, table_d, plan, keys_d.as<uint32_t>(), counts_d.as<uint64_t>(), nullptr));
+        CNIIC_HIP_TRY(c, len_d.alloc(U));
+        CNIIC_HIP_TRY(c, code_d.alloc(U * 8));
+        // Counts (and codes) cross the bus through pinned memory.  From 32768 distinct symbols on -- any photograph -- the host only
+        // merges the tree; codes, lengths and the serialised decoder come from the GPU (huff_tree_codes: 0.1 ms of host work less,
+        // and no 0.13-0.28 ms of writing the decoder out beside the pack).  Large: [sorted leaves u64 | left, right, leaves below
+        // each of the U - 1 branches u32].  Small: [counts u64 | code u64 | len u8]; the keys and the decoder in ordinary memory (the
+        // host reads the keys at random and writes the decoder byte by byte: 0.20 ms in pinned memory, 0.12 there).
+        gpu_codes = U >= c->opt(CNIIC_OPT_HUF_GPU_CODES_MIN, "CNIIC_HUF_GPU_CODES_MIN", 32768) && U >= 2 && U < (1ull << 30) && n < (1ull << 32);
+        CNIIC_HIP_TRY(c, ctx_pinned_huf(c, gpu_codes ? U * 8 + 3 * (U - 1) * 4 + 64 : U * 8 + U * 8 + U));
+        counts_h = static_cast<uint64_t *>(c->pinned_huf);
+        left_h = reinterpret_cast<uint32_t *>(counts_h + U);
+        right_h = left_h + (U - 1);
+        nleaves_h = right_h + (U - 1);
+        code_h = counts_h + U;
+        len_h = reinterpret_cast<uint8_t *>(code_h + U);
+        if (!gpu_codes) {
+            keys_h.resize(U);
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(keys_h.data(), keys_d.p, U * 4, hipMemcpyDeviceToHost, c->stream));
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(counts_h, counts_d.p, U * 8, hipMemcpyDeviceToHost, c->stream));
+            return CNIIC_OK;
+        }
+        uint64_t *sorted_d = nullptr;
+        CNIIC_HIP_TRY(c, sort_a.alloc(U * 8));
+        CNIIC_HIP_TRY(c, sort_b.alloc(U * 8));
+        CNIIC_TRY(huff_sort_leaves_dev(c, counts_d.as<uint64_t>(), (uint32_t)U, plan->max_count ? plan->max_count : n, sort_a.as<uint64_t>(), sort_b.as<uint64_t>(), &sorted_d));
+        // (round 3) the tree, the codes and the leaves' places in the decoder without the host's merge, when the counts come in runs
+        CNIIC_HIP_TRY(c, off_d.alloc(U * 8));
+        CNIIC_TRY(huff_tree_from_runs(c, sorted_d, counts_d.as<uint64_t>(), (uint32_t)U, sym_kind, len_d.as<uint8_t>(), code_d.as<uint64_t>(),
+                                      off_d.as<uint64_t>(), &nbits, &tree_built));
+        if (!tree_built) CNIIC_HIP_TRY(c, hipMemcpyAsync(counts_h, sorted_d, U * 8, hipMemcpyDeviceToHost, c->stream));
+        return CNIIC_OK;
+    }
+
+    // totals_d: two u64 of the caller's in HBM (payload bits; "a code is too long"), written by huff_tree_codes
+    int build(uint64_t *totals_d) {
+        if (tree_built) return CNIIC_OK;
+        if (!c->huf_scratch) c->huf_scratch = std::make_shared<HuffScratch>();
+        HuffScratch *scratch = static_cast<HuffScratch *>(c->huf_scratch.get());
+        if (!gpu_codes) {
+            if (!huff_build_tree(counts_h, U, tree, scratch) || !huff_codes_into(tree, len_h, code_h)) return cannot_build();
+            for (uint64_t i = 0; i < U; i++) nbits += counts_h[i] * len_h[i];
+            host_trace().mark("huf: tree + codes (host)");
+            return CNIIC_OK;
+        }
+        uint32_t root = 0;
+        if (!huff_merge_sorted_into(counts_h /* sorted leaves */, U, left_h, right_h, nleaves_h, &root, scratch)) return cannot_build();
+        host_trace().mark("huf: tree (host)");
+        CNIIC_HIP_TRY(c, tree_d.alloc(3 * (U - 1) * 4));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(tree_d.p, left_h, 3 * (U - 1) * 4, hipMemcpyHostToDevice, c->stream));
+        const uint32_t *left_d = tree_d.as<uint32_t>(), *right_d = left_d + (U - 1), *nleaves_d = right_d + (U - 1);
+        CNIIC_TRY(huff_tree_codes(c, left_d, right_d, nleaves_d, counts_d.as<uint64_t>(), (uint32_t)U, root, sym_kind, len_d.as<uint8_t>(),
+                                  code_d.as<uint64_t>(), off_d.as<uint64_t>(), totals_d));
+        CNIIC_HIP_TRY(c, ctx_pinned_u(c));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuHufTotals.at, totals_d, 16, hipMemcpyDeviceToHost, c->stream));
+        totals_pending = true;
+        return CNIIC_OK;
+    }
+
+    int bits(uint64_t *payload_bits) {
+        if (totals_pending) {
+            totals_pending = false;
+            if (c->pinned_u[kPuHufTotals.at + 1]) return cannot_build();
+            nbits = c->pinned_u[kPuHufTotals.at];
+            host_trace().mark("huf: codes (GPU)");
+        }
+        *payload_bits = nbits;
+        return CNIIC_OK;
+    }
+
+    int upload_codes() {
+        if (gpu_codes) return CNIIC_OK;
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(len_d.p, len_h, U, hipMemcpyHostToDevice, c->stream));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(code_d.p, code_h, U * 8, hipMemcpyHostToDevice, c->stream));
+        return CNIIC_OK;
+    }
+
+    // header: whatever the stream starts with (the image's dimensions); so: begun for header.size() + decoder_bytes() + the payload.
+    // Small alphabet: the decoder is appended to `header` on the host.
+    int write_decoder(StreamOut &so, std::vector<uint8_t> &header) {
+        const uint64_t head = header.size();
+        if (!gpu_codes) huff_serialize_tree(tree, sym_kind, keys_h.data(), header);
+        CNIIC_TRY(so.put_header(header));
+        if (gpu_codes) CNIIC_TRY(huff_tree_serialize_dev(c, keys_d.as<uint32_t>(), off_d.as<uint64_t>(), (uint32_t)U, sym_kind, so.dev + head, decoder_bytes()));
+        host_trace().mark("huf: serialise trie");
+        return CNIIC_OK;
+    }
+
+    void release_tree() { tree_d.release(); off_d.release(); }   // (once the stream has been waited for behind write_decoder)
+
+private:
+    DevBuf sort_a, sort_b, tree_d, off_d;   // off_d: every leaf's place in the serialised decoder
+    uint64_t nbits = 0;
+    uint64_t *counts_h = nullptr, *code_h = nullptr;
+    uint32_t *left_h = nullptr, *right_h = nullptr, *nleaves_h = nullptr;
+    uint8_t *len_h = nullptr;
+    std::vector<uint32_t> keys_h;
+    HuffTree tree;
+    int cannot_build() { return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U); }
+};
+
 // ------------------------------------------------------------------ huf::encode_all (huf.rs:22-43)
 // Symbols come either as pixels (rgb_d) or as packed keys (syms_d).  table_d holds the dense
 // histogram on entry when have_hist, otherwise it is built here.
@@ -154,46 +320,9 @@ int huf_encode_all_dev(Ctx *c, int sym_kind, const uint8_t *rgb_d, uint32_t *sym
     }
     CompactPlan plan;
     CNIIC_TRY(hist_compact_count(c, table_d, bits, &plan));
-    const uint64_t U = plan.n_unique;
-    DevBuf keys_d, counts_d;
-    CNIIC_HIP_TRY(c, keys_d.alloc(U * 4));
-    CNIIC_HIP_TRY(c, counts_d.alloc(U * 8));
-    CNIIC_TRY(hist_compact_write(c, table_d, &plan, keys_d.as<uint32_t>(), counts_d.as<uint64_t>(), nullptr));
-    // A large alphabet (a photograph's colours): the host only merges the tree; codes and the serialised decoder are the
-    // GPU's (huff_tree_codes).  The counts land in pinned memory, the tree's arrays are written there, the keys stay put.
-    const bool gpu_codes = U >= c->opt(CNIIC_OPT_HUF_GPU_CODES_MIN, "CNIIC_HUF_GPU_CODES_MIN", 32768) && U >= 2 && U < (1ull << 30) && n < (1ull << 32);
-    std::vector<uint32_t> keys(gpu_codes ? 0 : U);
-    std::vector<uint64_t> counts_v(gpu_codes ? 0 : U);
-    uint64_t *counts = counts_v.data();
-    uint32_t *left_h = nullptr, *right_h = nullptr, *nl_h = nullptr;
-    if (gpu_codes) {
-        CNIIC_HIP_TRY(c, ctx_pinned_huf(c, U * 8 + 3 * (U - 1) * 4 + 64));
-        counts = static_cast<uint64_t *>(c->pinned_huf);
-        left_h = reinterpret_cast<uint32_t *>(counts + U);
-        right_h = left_h + (U - 1);
-        nl_h = right_h + (U - 1);
-    } else {
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(keys.data(), keys_d.p, U * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    // (large alphabet: the leaves come back sorted by (count, key) -- huff_sort_leaves_dev -- and the host only merges)
-    DevBuf sort_a, sort_b, len_d, code_d, off_run_d;
-    uint64_t nbits_runs = 0;
-    bool tree_built = false;
-    if (gpu_codes) {
-        uint64_t *sorted_d = nullptr;
-        CNIIC_HIP_TRY(c, sort_a.alloc(U * 8));
-        CNIIC_HIP_TRY(c, sort_b.alloc(U * 8));
-        CNIIC_TRY(huff_sort_leaves_dev(c, counts_d.as<uint64_t>(), (uint32_t)U, plan.max_count ? plan.max_count : n, sort_a.as<uint64_t>(), sort_b.as<uint64_t>(), &sorted_d));
-        // (round 3) the tree, the codes and the leaves' places in the decoder without the host's merge, when the counts come in runs
-        CNIIC_HIP_TRY(c, len_d.alloc(U));
-        CNIIC_HIP_TRY(c, code_d.alloc(U * 8));
-        CNIIC_HIP_TRY(c, off_run_d.alloc(U * 8));
-        CNIIC_TRY(huff_tree_from_runs(c, sorted_d, counts_d.as<uint64_t>(), (uint32_t)U, sym_kind, len_d.as<uint8_t>(), code_d.as<uint64_t>(),
-                                      off_run_d.as<uint64_t>(), &nbits_runs, &tree_built));
-        if (!tree_built) CNIIC_HIP_TRY(c, hipMemcpyAsync(counts, sorted_d, U * 8, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(counts, counts_d.p, U * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+    HuffCodeStage st(c, sym_kind);
+    CNIIC_TRY(st.begin(table_d, &plan, n));
+    const uint64_t U = st.U;
     if (!c->huf_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->huf_ev, hipEventDisableTiming));
     CNIIC_HIP_TRY(c, hipEventRecord(c->huf_ev, c->stream));
     // `delta` symbols on a buffer of ours: nothing to do while the host builds the tree -- the pack looks (length, code) up
@@ -202,89 +331,47 @@ int huf_encode_all_dev(Ctx *c, int sym_kind, const uint8_t *rgb_d, uint32_t *sym
     // rank + 1), which needs no code -- in place over the symbol stream when it is ours; the pack then reads that stream
     // and the small per-rank length / code tables.
     const bool hot_route = sym_kind == CNIIC_SYM_SIGNED && syms_d && syms_scratch && U < (1ull << 26) && (reinterpret_cast<uintptr_t>(syms_d) & 15) == 0;
-    DevBuf ranks_own;
+    DevBuf ranks_own, totals_d;
     uint32_t *ranks = syms_d;
     const bool inline_codes = U < (1ull << 26);  // (len, code) of a symbol in one u32 looked up by rank; else per-rank tables
     // (round 3) with the tree on the GPU there is nothing for that pass to hide behind: the pack's first pass looks every symbol up in the
     // dense table itself, once it holds (length, code) words -- one random read per symbol instead of two (hufman 4096^2: -0.25 ms)
-    const bool direct = gpu_codes && !hot_route && inline_codes;
+    const bool direct = st.gpu_codes && !hot_route && inline_codes;
     if (!hot_route) {
         if (!syms_d || !syms_scratch) { CNIIC_HIP_TRY(c, ranks_own.alloc(n * 4 + 16)); ranks = ranks_own.as<uint32_t>(); }
         if (!direct) CNIIC_TRY(huff_rank_stream(c, syms_d, rgb_d, n, table_d, ranks, !inline_codes));
     }
     CNIIC_HIP_TRY(c, hipEventSynchronize(c->huf_ev));
     host_trace().mark("huf: hist + compaction + D2H");
-    // build() (huf.rs:31) and the serialised decoder (huf.rs:34)
-    if (!c->huf_scratch) c->huf_scratch = std::make_shared<HuffScratch>();
-    HuffScratch *scratch = static_cast<HuffScratch *>(c->huf_scratch.get());
-    if (!len_d.p) CNIIC_HIP_TRY(c, len_d.alloc(U));
-    if (!code_d.p) CNIIC_HIP_TRY(c, code_d.alloc(U * 8));
-    uint64_t nbits = 0, header_bytes = 0;
+    // 2. build() (huf.rs:31)
+    CNIIC_HIP_TRY(c, totals_d.alloc(16));
+    CNIIC_TRY(st.build(totals_d.as<uint64_t>()));
+    if (st.totals_pending) CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint64_t nbits = 0;
+    CNIIC_TRY(st.bits(&nbits));
+    // 3. the serialised decoder (huf.rs:34); the payload (huf.rs:37-41) is packed in place behind it
+    const uint64_t header_bytes = header.size() + st.decoder_bytes();
     StreamOut so(c, out, cap, len);
-    if (gpu_codes) {
-        DevBuf tree_d, off_d, totals_d;
-        const uint64_t *off_use = off_run_d.as<uint64_t>();
-        if (tree_built) {
-            nbits = nbits_runs;
-        } else {
-            uint32_t root = 0;
-            if (!huff_merge_sorted_into(counts /* sorted leaves */, U, left_h, right_h, nl_h, &root, scratch))
-                return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U);
-            host_trace().mark("huf: tree (host)");
-            CNIIC_HIP_TRY(c, tree_d.alloc(3 * (U - 1) * 4));
-            CNIIC_HIP_TRY(c, off_d.alloc(U * 8));
-            CNIIC_HIP_TRY(c, totals_d.alloc(16));
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(tree_d.p, left_h, 3 * (U - 1) * 4, hipMemcpyHostToDevice, c->stream));
-            const uint32_t *left_d = tree_d.as<uint32_t>(), *right_d = left_d + (U - 1), *nl_d = right_d + (U - 1);
-            CNIIC_TRY(huff_tree_codes(c, left_d, right_d, nl_d, counts_d.as<uint64_t>(), (uint32_t)U, root, sym_kind, len_d.as<uint8_t>(),
-                                      code_d.as<uint64_t>(), off_d.as<uint64_t>(), totals_d.as<uint64_t>()));
-            CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(&c->pinned_u[2], totals_d.p, 16, hipMemcpyDeviceToHost, c->stream));
-            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->pinned_u[3]) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U);
-            nbits = c->pinned_u[2];
-            off_use = off_d.as<uint64_t>();
-        }
-        host_trace().mark("huf: codes (GPU)");
-        const uint64_t trie_bytes = huff_tree_bytes(sym_kind, U), head = header.size();
-        CNIIC_TRY(so.begin_sized(head + trie_bytes, (nbits + 7) / 8));
-        CNIIC_TRY(so.put_header(header));
-        CNIIC_TRY(huff_tree_serialize_dev(c, keys_d.as<uint32_t>(), off_use, (uint32_t)U, sym_kind, so.dev + head, trie_bytes));
-        header_bytes = head + trie_bytes;  // (what the pack below starts behind; the decoder's bytes are on the device)
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));  // tree_d / off_d go back to the pool
-        host_trace().mark("huf: serialise trie (GPU)");
-    } else {
-        HuffTree tree;
-        std::vector<uint8_t> clen;
-        std::vector<uint64_t> code;
-        if (!huff_build_tree(counts, U, tree, scratch) || !huff_codes(tree, clen, code))
-            return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U);
-        host_trace().mark("huf: tree + codes (host)");
-        huff_serialize_tree(tree, sym_kind, keys.data(), header);
-        host_trace().mark("huf: serialise trie (host)");
-        // 3. payload (huf.rs:37-41), packed in place behind the header
-        for (uint64_t i = 0; i < U; i++) nbits += counts[i] * clen[i];
-        CNIIC_TRY(so.begin(header, (nbits + 7) / 8));
-        header_bytes = header.size();
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(len_d.p, clen.data(), U, hipMemcpyHostToDevice, c->stream));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(code_d.p, code.data(), U * 8, hipMemcpyHostToDevice, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));  // (clen / code are locals of this branch)
-    }
+    CNIIC_TRY(so.begin_sized(header_bytes, (nbits + 7) / 8));
+    CNIIC_TRY(st.write_decoder(so, header));
+    CNIIC_TRY(st.upload_codes());
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));  // the stage's tree goes back to the pool before the pack asks it for memory
+    st.release_tree();
     uint64_t packed_bits = 0;
     ScopedKernelTimer timer(c, "huff_pack");
+    uint32_t *const keys_d = st.keys_d.as<uint32_t>();
+    const uint8_t *const len_d = st.len_d.as<uint8_t>();
+    const uint64_t *const code_d = st.code_d.as<uint64_t>();
     if (hot_route) {
-        CNIIC_TRY(huff_pack_code32_hot(c, syms_d, n, table_d, keys_d.as<uint32_t>(), len_d.as<uint8_t>(), code_d.as<uint64_t>(), U, syms_d, so.dev,
-                                       header_bytes * 8, &packed_bits));
+        CNIIC_TRY(huff_pack_code32_hot(c, syms_d, n, table_d, keys_d, len_d, code_d, U, syms_d, so.dev, header_bytes * 8, &packed_bits));
     } else if (direct) {
-        CNIIC_TRY(huff_pack_code32(c, syms_d, rgb_d, n, table_d, keys_d.as<uint32_t>(), len_d.as<uint8_t>(), code_d.as<uint64_t>(), U, ranks,
-                                   so.dev, header_bytes * 8, &packed_bits));
+        CNIIC_TRY(huff_pack_code32(c, syms_d, rgb_d, n, table_d, keys_d, len_d, code_d, U, ranks, so.dev, header_bytes * 8, &packed_bits));
     } else if (inline_codes) {
         DevBuf code32;
         CNIIC_HIP_TRY(c, code32.alloc(U * 4));
-        CNIIC_TRY(huff_pack_code32(c, ranks, nullptr, n, code32.as<uint32_t>(), nullptr, len_d.as<uint8_t>(), code_d.as<uint64_t>(), U, ranks,
-                                   so.dev, header_bytes * 8, &packed_bits));
+        CNIIC_TRY(huff_pack_code32(c, ranks, nullptr, n, code32.as<uint32_t>(), nullptr, len_d, code_d, U, ranks, so.dev, header_bytes * 8, &packed_bits));
     } else {
-        CNIIC_TRY(huff_pack_ranks(c, ranks, n, len_d.as<uint8_t>(), code_d.as<uint64_t>(), so.dev, header_bytes * 8, &packed_bits));
+        CNIIC_TRY(huff_pack_ranks(c, ranks, n, len_d, code_d, so.dev, header_bytes * 8, &packed_bits));
     }
     timer.stop(1);
     host_trace().mark("huf: pack");
@@ -315,8 +402,6 @@ static int encode_hufman(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, u
 //   (K-means loop: km_rgbw_run on one GPU, or assign / all-reduce / update driven by the caller)
 //   cc_finish   clusters -> colour lookup -> Hufman.encode of the reduced image (clusterc.rs:31-52)
 CcSession::~CcSession() { if (km) km_rgbw_destroy(km); }
-HostTrace &host_trace() { static thread_local HostTrace t; return t; }
-
 
 int cc_prepare(Ctx *c, uint32_t *table_counts_d, uint32_t K, const cniic_kmeans_opts *opts, uint32_t shard, uint32_t nshards,
                void *partials_dev, CcSession **out, const uint32_t *occ_d) {
@@ -395,7 +480,7 @@ int cc_image_create(CcSession *s, const uint32_t *occ_d, uint32_t K, const cniic
     // this image's own colour count) stay on the device while the state is set up -- sized for the most there can be, the
     // set-up kernels read the counts where they are -- and the host fetches both once everything is enqueued.
     CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    uint64_t *Ug_h = c->pinned_u + 1;
+    uint64_t *Ug_h = c->pinned_u + kPuPointCount.at;
     CNIIC_TRY(gidx_build(c, occ_d, s->gbits, s->gprefix, Ug_h, &s->gtotal));
     const uint64_t Umax = std::min<uint64_t>(s->sp.npx, 1ull << 24);
     const uint64_t *Ug_dev = s->gtotal.as<uint64_t>();
@@ -405,16 +490,53 @@ int cc_image_create(CcSession *s, const uint32_t *occ_d, uint32_t K, const cniic
     km_rgbw_cell_arrays(s->km, &cell_start, &ckeys, &cweight);
     CNIIC_TRY(sp_emit(c, &s->sp, cell_start, ckeys, cweight, km_rgbw_labels_internal(s->km, nullptr), km_rgbw_is_wide(s->km), K, s->gbits.p,
                       s->gprefix.as<uint32_t>(), 0, Ug_dev));
-    // this image's own colour count, fetched again here: the context's pinned slot sp_build copied it to may have been
+    // this image's own colour count, fetched again here: the word sp_build copied it to (kPuSpCount) may have been
     // rewritten since by another session of the same context (a second cniic_cc_image_begin, a plain encode)
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + 2, s->sp.total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuImageCount.at, s->sp.total.p, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the all-reduced occupancy had to arrive anyway)
     const uint64_t Ug = *Ug_h;
-    s->sp.U = c->pinned_u[2];
+    s->sp.U = c->pinned_u[kPuImageCount.at];
     s->U = s->sp.U;
     if (Ug / K == 0 || s->U == 0)
         return c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu distinct colours for %u clusters (src/kmeans.rs:68)", (unsigned long long)Ug, K);
     return km_rgbw_set_points(s->km, s->U, Ug);
+}
+
+// The Hufman stream of a colour-reduced image, from its palette (clusterc.rs:52 -> hufc.rs:12-17).  The histogram count_freqs would
+// find there (huf.rs:30) is the image's pixels per centroid COLOUR -- two clusters with one mean are one symbol; from it the tree,
+// the stream's header (dimensions + serialised decoder), the payload's bits and every cluster's code: reduced_colors.get(original
+// colour) (clusterc.rs:43-47) fused with Enc::encode (huf.rs:137-148).  cent: K centroids, 3 bytes each; pixels[k]: this image's
+// pixels in cluster k (a cluster without any gets no code); clen / ccode: K entries.  false: no code can be built.
+template <class Count>
+static bool palette_code(const uint8_t *cent, const Count *pixels, uint32_t K, uint32_t w, uint32_t h, std::vector<uint8_t> &header,
+                         uint8_t *clen, uint64_t *ccode, uint64_t *nbits) {
+    auto colour = [&](uint32_t k) { return ((uint32_t)cent[3 * k] << 16) | ((uint32_t)cent[3 * k + 1] << 8) | cent[3 * k + 2]; };
+    std::vector<std::pair<uint32_t, uint64_t>> kc;
+    kc.reserve(K);
+    for (uint32_t k = 0; k < K; k++)
+        if (pixels[k]) kc.emplace_back(colour(k), pixels[k]);
+    std::sort(kc.begin(), kc.end());  // ascending colour, equal colours adjacent
+    std::vector<uint32_t> skeys;
+    std::vector<uint64_t> scounts;
+    for (auto &e : kc) {
+        if (!skeys.empty() && skeys.back() == e.first) scounts.back() += e.second;
+        else { skeys.push_back(e.first); scounts.push_back(e.second); }
+    }
+    HuffTree tree;
+    std::vector<uint8_t> slen;
+    std::vector<uint64_t> scode;
+    if (!huff_build_tree(scounts.data(), scounts.size(), tree) || !huff_codes(tree, slen, scode)) return false;
+    put_u32(header, w);
+    put_u32(header, h);
+    huff_serialize_tree(tree, CNIIC_SYM_RGB, skeys.data(), header);
+    *nbits = 0;
+    for (size_t i = 0; i < scounts.size(); i++) *nbits += scounts[i] * slen[i];
+    for (uint32_t k = 0; k < K; k++) {
+        const size_t si = std::lower_bound(skeys.begin(), skeys.end(), colour(k)) - skeys.begin();
+        clen[k] = pixels[k] ? slen[si] : 0;
+        ccode[k] = pixels[k] ? scode[si] : 0;
+    }
+    return true;
 }
 
 int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const uint32_t *local_counts_d, uint8_t *out,
@@ -441,14 +563,14 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     if (s->sp_mode) {  // every pixel's label from the partition: no table of 2^24 entries, no random read
         uint32_t *cell_start, *ckeys, *cweight;
         km_rgbw_cell_arrays(km, &cell_start, &ckeys, &cweight);
-        if (s->local_points && K <= 4096) {
+        if (s->local_points && K <= kPuPaletteWeights.words) {
             // shared palette: THIS image's pixels per cluster (below) -- asked for first, so that the answer travels while
             // the pixel labels are computed instead of stalling the stream after them
             CNIIC_HIP_TRY(c, ctx_pinned_u(c));
             CNIIC_HIP_TRY(c, lw.alloc((uint64_t)K * 8));
             CNIIC_HIP_TRY(c, hipMemsetAsync(lw.p, 0, (uint64_t)K * 8, c->stream));
             CNIIC_TRY(local_cluster_weights(c, ckeys, km_rgbw_labels_internal(km, nullptr), wide, U, nullptr, K, lw.as<uint64_t>(), cweight));
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + 8, lw.p, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuPaletteWeights.at, lw.p, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
             if (!c->u_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->u_ev, hipEventDisableTiming));
             CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
             lw_early = true;
@@ -469,18 +591,13 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     }
     host_trace().mark("km_result");
     if (stats) *stats = st;
-    // check_enough_active_clusters (kmeans.rs:41-57)
-    uint64_t min_cc = (uint64_t)(0.99 * (double)K);
-    if (U < min_cc) min_cc = U;
-    if (st.active < min_cc)
-        return c->fail(CNIIC_ERR_FEW_ACTIVE, "Not enough active clusters: requested %u, got %llu (min allowed: %llu)", K,
-                       (unsigned long long)st.active, (unsigned long long)min_cc);
+    CNIIC_TRY(check_enough_active(c, K, U, st.active));
+    // wsum: the pixels per cluster of the image Hufman.encode sees (clusterc.rs:52).  One image: the member weights' sums, as they came.
     if (lw_early) {
         CNIIC_HIP_TRY(c, hipEventSynchronize(c->u_ev));
-        for (uint32_t k = 0; k < K; k++) { wsum[k] = c->pinned_u[8 + k]; members[k] = wsum[k] ? 1 : 0; }
+        for (uint32_t k = 0; k < K; k++) wsum[k] = c->pinned_u[kPuPaletteWeights.at + k];
     } else if (local_counts_d || s->local_points) {
-        // shared palette over several images: THIS image's pixels per cluster (its reduced image is
-        // what Hufman.encode sees, clusterc.rs:52), from its own colour counts
+        // shared palette over several images: THIS image's pixels per cluster, from its own colour counts
         CNIIC_HIP_TRY(c, lw.alloc((uint64_t)K * 8));
         CNIIC_HIP_TRY(c, hipMemsetAsync(lw.p, 0, (uint64_t)K * 8, c->stream));
         if (s->sp_mode) {  // cell-major colours, labels and pixel counts of this image: any common order will do
@@ -493,45 +610,12 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
         }
         CNIIC_HIP_TRY(c, hipMemcpyAsync(wsum.data(), lw.p, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (uint32_t k = 0; k < K; k++) members[k] = wsum[k] ? 1 : 0;
     }
-    // Histogram of the colour-reduced image = per-centroid-colour sum of member weights
-    // (what count_freqs inside Hufman.encode would find, clusterc.rs:52 -> huf.rs:30).
-    std::vector<std::pair<uint32_t, uint64_t>> kc;
-    kc.reserve(K);
-    for (uint32_t k = 0; k < K; k++)
-        if (members[k]) kc.emplace_back(((uint32_t)cent[3 * k] << 16) | ((uint32_t)cent[3 * k + 1] << 8) | cent[3 * k + 2], wsum[k]);
-    std::sort(kc.begin(), kc.end());  // ascending colour, equal colours (two clusters with one mean) adjacent in cluster order
-    std::vector<uint32_t> skeys;
-    std::vector<uint64_t> scounts;
-    for (auto &e : kc) {
-        if (!skeys.empty() && skeys.back() == e.first) scounts.back() += e.second;
-        else { skeys.push_back(e.first); scounts.push_back(e.second); }
-    }
-    host_trace().mark("map");
-    HuffTree tree;
-    std::vector<uint8_t> slen;
-    std::vector<uint64_t> scode;
-    if (!huff_build_tree(scounts.data(), scounts.size(), tree) || !huff_codes(tree, slen, scode))
-        return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
-    host_trace().mark("build+codes");
-    std::vector<uint8_t> header;
-    put_u32(header, w);
-    put_u32(header, h);
-    huff_serialize_tree(tree, CNIIC_SYM_RGB, skeys.data(), header);
+    std::vector<uint8_t> header, clen(K);
+    std::vector<uint64_t> ccode(K);
     uint64_t nbits = 0;
-    for (size_t i = 0; i < scounts.size(); i++) nbits += scounts[i] * slen[i];
-    // per-cluster code; every pixel reaches it through a dense colour -> cluster-label table:
-    // reduced_colors.get(original_colour) (clusterc.rs:43-47) fused with Enc::encode (huf.rs:137-148)
-    std::vector<uint8_t> clen(K, 0);
-    std::vector<uint64_t> ccode(K, 0);
-    for (uint32_t k = 0; k < K; k++) {
-        if (!members[k]) continue;
-        uint32_t key = ((uint32_t)cent[3 * k] << 16) | ((uint32_t)cent[3 * k + 1] << 8) | cent[3 * k + 2];
-        size_t si = std::lower_bound(skeys.begin(), skeys.end(), key) - skeys.begin();
-        clen[k] = slen[si];
-        ccode[k] = scode[si];
-    }
+    if (!palette_code(cent.data(), wsum.data(), K, w, h, header, clen.data(), ccode.data(), &nbits))
+        return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
     host_trace().mark("tree+codes (host)");
     StreamOut so(c, out, cap, len);
     CNIIC_TRY(so.begin(header, (nbits + 7) / 8));
@@ -611,135 +695,69 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
     host_trace().mark("frames: hist enqueued");
     CNIIC_TRY(km_rgbw_result_end(km, cent.data(), members.data(), wsum.data(), &st));
     if (stats) *stats = st;
-    uint64_t min_cc = (uint64_t)(0.99 * (double)K);  // check_enough_active_clusters (kmeans.rs:41-57)
-    if (U < min_cc) min_cc = U;
-    if (st.active < min_cc)
-        return c->fail(CNIIC_ERR_FEW_ACTIVE, "Not enough active clusters: requested %u, got %llu (min allowed: %llu)", K,
-                       (unsigned long long)st.active, (unsigned long long)min_cc);
+    CNIIC_TRY(check_enough_active(c, K, U, st.active));
     host_trace().mark("frames: result_end (sync)");
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
     host_trace().mark("frames: wait for the histograms");
+    FramesOut fo(c, out, stride, F);
+    DevBuf clen_d, ccode_d;
+    CNIIC_HIP_TRY(c, clen_d.alloc((size_t)F * K));
+    CNIIC_HIP_TRY(c, ccode_d.alloc((size_t)F * K * 8));
+    std::vector<uint64_t> totals(F, 0);
     if (gpu_trees) {
         // ---- K <= 256: codes, code tables and stream headers of all frames by one kernel (k_frame_trees); the host sees the
         // lengths (it owes them to the caller and must hold them against the stride before anything is packed) and nothing else
-        const bool direct = is_device_ptr(out) && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-        DevBuf staging, clen_d, ccode_d, meta_d;
-        uint8_t *dev = out;
-        if (!direct) { CNIIC_HIP_TRY(c, staging.alloc(stride * F + 16)); dev = staging.as<uint8_t>(); }
-        CNIIC_HIP_TRY(c, hipMemsetAsync(dev, 0, stride * F, c->stream));
-        CNIIC_HIP_TRY(c, clen_d.alloc((size_t)F * K));
-        CNIIC_HIP_TRY(c, ccode_d.alloc((size_t)F * K * 8));
+        CNIIC_TRY(fo.begin());
+        DevBuf meta_d;
         CNIIC_HIP_TRY(c, meta_d.alloc((size_t)F * 24 + 8));  // bit base, payload bits, stream length per frame; error word
         uint64_t *bb_d = meta_d.as<uint64_t>(), *nb_d = bb_d + F, *ln_d = nb_d + F;
         uint32_t *err_d = reinterpret_cast<uint32_t *>(ln_d + F);
         CNIIC_HIP_TRY(c, hipMemsetAsync(err_d, 0, 8, c->stream));
-        CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), km_rgbw_centroids_dev(km), F, K, w, h, dev, stride, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d));
+        CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), km_rgbw_centroids_dev(km), F, K, w, h, fo.dev, stride, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d));
         std::vector<uint64_t> meta((size_t)F * 3 + 1);
         CNIIC_HIP_TRY(c, hipMemcpyAsync(meta.data(), meta_d.p, (size_t)F * 24 + 8, hipMemcpyDeviceToHost, c->stream));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
         host_trace().mark("frames: trees, codes, headers (GPU) + lengths back");
         const uint32_t err = (uint32_t)meta[(size_t)F * 3];
         if (err & 3u) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
-        for (uint32_t f = 0; f < F; f++) {
-            lens[f] = meta[2 * (size_t)F + f];
-            if ((err & 4u) || ((lens[f] + 3) & ~3ull) > stride)
-                return c->fail(CNIIC_ERR_CAPACITY, "encode: stream of frame %u is %llu bytes, %llu between streams", f, (unsigned long long)lens[f], (unsigned long long)stride);
-        }
-        std::vector<uint64_t> totals(F, 0);
-        CNIIC_TRY(huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), dev, stride, nullptr, totals.data(), bb_d));
+        std::copy_n(meta.data() + 2 * (size_t)F, F, lens);
+        CNIIC_TRY(fo.check_lens(lens, (err & 4u) != 0));
+        CNIIC_TRY(huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, nullptr, totals.data(), bb_d));
         host_trace().mark("frames: pack (+sync)");
-        for (uint32_t f = 0; f < F; f++)
-            if (totals[f] != meta[(size_t)F + f])
-                return c->fail(CNIIC_ERR_HIP, "cluster-colors: frame %u packed %llu bits, its histogram predicts %llu", f, (unsigned long long)totals[f], (unsigned long long)meta[(size_t)F + f]);
-        if (!direct) {
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(out, dev, stride * F, is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
+        CNIIC_TRY(fo.finish(totals.data(), meta.data() + F));
         host_trace().dump();
         return CNIIC_OK;
     }
-    // ---- per frame on the host: histogram of the reduced frame = its pixels per centroid COLOUR (two clusters with one mean
-    // are one symbol), tree, serialised decoder, per-cluster code
+    // ---- per frame on the host, on a few threads: tree, stream header and per-cluster codes from the frame's pixels per cluster
     std::vector<std::vector<uint8_t>> headers(F);
-    std::vector<uint8_t> clen((size_t)F * K, 0);
-    std::vector<uint64_t> ccode((size_t)F * K, 0), nbits(F, 0);
+    std::vector<uint8_t> clen((size_t)F * K);
+    std::vector<uint64_t> ccode((size_t)F * K), nbits(F, 0);
     std::atomic<int> bad{0};
-    auto one_frame = [&](uint32_t f) {
-        const uint32_t *fc = cnt.data() + (size_t)f * K;
-        std::vector<std::pair<uint32_t, uint64_t>> kc;
-        kc.reserve(K);
-        for (uint32_t k = 0; k < K; k++)
-            if (fc[k]) kc.emplace_back(((uint32_t)cent[3 * k] << 16) | ((uint32_t)cent[3 * k + 1] << 8) | cent[3 * k + 2], fc[k]);
-        std::sort(kc.begin(), kc.end());
-        std::vector<uint32_t> skeys;
-        std::vector<uint64_t> scounts;
-        for (auto &e : kc) {
-            if (!skeys.empty() && skeys.back() == e.first) scounts.back() += e.second;
-            else { skeys.push_back(e.first); scounts.push_back(e.second); }
-        }
-        HuffTree tree;
-        std::vector<uint8_t> slen;
-        std::vector<uint64_t> scode;
-        if (!huff_build_tree(scounts.data(), scounts.size(), tree) || !huff_codes(tree, slen, scode)) { bad = 1; return; }
-        std::vector<uint8_t> &hd = headers[f];
-        put_u32(hd, w);
-        put_u32(hd, h);
-        huff_serialize_tree(tree, CNIIC_SYM_RGB, skeys.data(), hd);
-        uint64_t nb = 0;
-        for (size_t i = 0; i < scounts.size(); i++) nb += scounts[i] * slen[i];
-        nbits[f] = nb;
-        for (uint32_t k = 0; k < K; k++) {
-            if (!fc[k]) continue;
-            const uint32_t key = ((uint32_t)cent[3 * k] << 16) | ((uint32_t)cent[3 * k + 1] << 8) | cent[3 * k + 2];
-            const size_t si = std::lower_bound(skeys.begin(), skeys.end(), key) - skeys.begin();
-            clen[(size_t)f * K + k] = slen[si];
-            ccode[(size_t)f * K + k] = scode[si];
-        }
-    };
-    {
-        const uint32_t nthr = std::max(1u, std::min({F, 16u, std::thread::hardware_concurrency()}));
-        std::atomic<uint32_t> next{0};
-        auto work = [&]() { for (uint32_t f; (f = next.fetch_add(1)) < F;) one_frame(f); };
-        std::vector<std::thread> pool;
-        for (uint32_t t = 1; t < nthr; t++) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-    }
+    parallel_for(F, std::max(1u, std::min({F, 16u, std::thread::hardware_concurrency()})), [&](uint32_t f, uint32_t) {
+        if (!palette_code(cent.data(), cnt.data() + (size_t)f * K, K, w, h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K], &nbits[f])) bad = 1;
+    });
     host_trace().mark("frames: trees, codes, headers (host threads)");
     if (bad) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
     uint64_t hmax = 0;
     for (uint32_t f = 0; f < F; f++) {
         lens[f] = headers[f].size() + (nbits[f] + 7) / 8;
-        if (((lens[f] + 3) & ~3ull) > stride)
-            return c->fail(CNIIC_ERR_CAPACITY, "encode: stream of frame %u is %llu bytes, %llu between streams", f, (unsigned long long)lens[f], (unsigned long long)stride);
         hmax = std::max<uint64_t>(hmax, headers[f].size());
     }
+    CNIIC_TRY(fo.check_lens(lens));
     hmax = (hmax + 3) & ~3ull;
-    // ---- output: device memory is written in place, a host buffer through a staging copy
-    const bool direct = is_device_ptr(out) && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-    DevBuf staging, hdr_d, clen_d, ccode_d;
-    uint8_t *dev = out;
-    if (!direct) { CNIIC_HIP_TRY(c, staging.alloc(stride * F + 16)); dev = staging.as<uint8_t>(); }
-    CNIIC_HIP_TRY(c, hipMemsetAsync(dev, 0, stride * F, c->stream));
+    CNIIC_TRY(fo.begin());
+    DevBuf hdr_d;
     std::vector<uint8_t> hdr_all(hmax * F, 0);
-    std::vector<uint64_t> bit_base(F), totals(F, 0);
+    std::vector<uint64_t> bit_base(F);
     for (uint32_t f = 0; f < F; f++) { memcpy(hdr_all.data() + hmax * f, headers[f].data(), headers[f].size()); bit_base[f] = headers[f].size() * 8; }
     CNIIC_HIP_TRY(c, hdr_d.alloc(hdr_all.size()));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(hdr_d.p, hdr_all.data(), hdr_all.size(), hipMemcpyHostToDevice, c->stream));
-    CNIIC_HIP_TRY(c, hipMemcpy2DAsync(dev, stride, hdr_d.p, hmax, hmax, F, hipMemcpyDeviceToDevice, c->stream));  // (zero padding behind a header = the pre-zeroed payload)
-    CNIIC_HIP_TRY(c, clen_d.alloc(clen.size()));
-    CNIIC_HIP_TRY(c, ccode_d.alloc(ccode.size() * 8));
+    CNIIC_HIP_TRY(c, hipMemcpy2DAsync(fo.dev, stride, hdr_d.p, hmax, hmax, F, hipMemcpyDeviceToDevice, c->stream));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(clen_d.p, clen.data(), clen.size(), hipMemcpyHostToDevice, c->stream));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(ccode_d.p, ccode.data(), ccode.size() * 8, hipMemcpyHostToDevice, c->stream));
-    CNIIC_TRY(huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), dev, stride, bit_base.data(), totals.data()));
+    CNIIC_TRY(huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bit_base.data(), totals.data()));
     host_trace().mark("frames: copies + pack (+sync)");
-    for (uint32_t f = 0; f < F; f++)
-        if (totals[f] != nbits[f])
-            return c->fail(CNIIC_ERR_HIP, "cluster-colors: frame %u packed %llu bits, its histogram predicts %llu", f, (unsigned long long)totals[f], (unsigned long long)nbits[f]);
-    if (!direct) {
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(out, dev, stride * F, is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    CNIIC_TRY(fo.finish(totals.data(), nbits.data()));
     host_trace().dump();
     return CNIIC_OK;
 }
@@ -789,12 +807,7 @@ static int encode_voronoi(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, 
     cniic_kmeans_stats st{};
     CNIIC_TRY(km_xyrgb_run(c, rgb_d, w, h, K, opts, cent.data(), nullptr, nullptr, &st));
     if (stats) *stats = st;
-    const uint64_t N = (uint64_t)w * h;
-    uint64_t min_cc = (uint64_t)(0.99 * (double)K);
-    if (N < min_cc) min_cc = N;
-    if (st.active < min_cc)
-        return c->fail(CNIIC_ERR_FEW_ACTIVE, "Not enough active clusters: requested %u, got %llu (min allowed: %llu)", K,
-                       (unsigned long long)st.active, (unsigned long long)min_cc);
+    CNIIC_TRY(check_enough_active(c, K, (uint64_t)w * h, st.active));
     std::vector<uint8_t> header;
     put_u32(header, w);            // clusterc.rs:156-158
     put_u32(header, h);
@@ -844,12 +857,13 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
     CNIIC_HIP_TRY(c, hot16.alloc(delta_stream_len(n) * 2));
     CNIIC_HIP_TRY(c, coldkeys.alloc(nchunks * 64 * 4));  // (written where cold symbols are)
     CNIIC_HIP_TRY(c, chunk_cold.alloc(nchunks));
-    CNIIC_HIP_TRY(c, small.alloc(32));  // u64 [0]: a chunk with more than 64 cold symbols, [2]: bits packed
+    CNIIC_HIP_TRY(c, small.alloc(32));  // u64 [0]: a chunk with more than 64 cold symbols, [2]: the codes' totals, then bits packed, [3]: a code is too long
     CNIIC_HIP_TRY(c, hipMemsetAsync(small.p, 0, 32, c->stream));
+    uint64_t *const packed_d = small.as<uint64_t>() + 2;
     CNIIC_TRY(delta_gather_hist(c, rgb_d, w, h, hot16.as<uint16_t>(), table, pages, coldkeys.as<uint32_t>(), chunk_cold.as<uint8_t>(),
                                 small.as<uint32_t>()));
     CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(&c->pinned_u[2], small.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuDeltaOverflow.at, small.p, 8, hipMemcpyDeviceToHost, c->stream));
     host_trace().mark("delta: gather + hist enqueued");
     // (stage timers, bench.py --config c5: everything between the histogram and the pack -- compaction, the leaves' sort, the host's merge with
     // the GPU idle, the codes -- as ONE stage, so that the stages account for the whole call)
@@ -857,168 +871,79 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
     CompactPlan plan;
     CNIIC_TRY(hist_compact_count(c, table, 27, &plan, nullptr, pages));  // (waits for the stream)
     host_trace().mark("delta: ... + count of the distinct (wait)");
-    const uint64_t U = plan.n_unique;
-    const bool overflow = c->pinned_u[2] != 0;
-    if (host_trace().on) fprintf(stderr, "[host] delta: %llu symbols, %llu distinct%s\n", (unsigned long long)n, (unsigned long long)U,
+    const bool overflow = c->pinned_u[kPuDeltaOverflow.at] != 0;
+    if (host_trace().on) fprintf(stderr, "[host] delta: %llu symbols, %llu distinct%s\n", (unsigned long long)n, (unsigned long long)plan.n_unique,
                                  overflow ? " (a chunk with more than 64 symbols outside the cube: the 32-bit route)" : "");
-    if (U >= (1ull << 26) || overflow) {
+    if (plan.n_unique >= (1ull << 26) || overflow) {
         CNIIC_TRY(delta_table_clean(c));
         return encode_delta_syms32(c, rgb_d, w, h, header, out, cap, len);
     }
-    DevBuf keys_d, counts_d;
-    CNIIC_HIP_TRY(c, keys_d.alloc(U * 4));
-    CNIIC_HIP_TRY(c, counts_d.alloc(U * 8));
-    CNIIC_TRY(hist_compact_write(c, table, &plan, keys_d.as<uint32_t>(), counts_d.as<uint64_t>(), nullptr));
-    // Counts (and codes) cross the bus through pinned memory.  From 32768 distinct symbols on -- any photograph -- the host only
-    // merges the tree; codes, lengths and the serialised decoder come from the GPU (huff_tree_codes: 0.1 ms of host work less,
-    // and no 0.13-0.28 ms of writing the decoder out beside the pack).  Below: [counts u64 | code u64 | len u8], the keys and
-    // the decoder in ordinary memory (the host reads the keys at random and writes the decoder byte by byte: 0.20 ms in pinned
-    // memory, 0.12 there).
-    const uint64_t decoder_bytes = huff_tree_bytes(CNIIC_SYM_SIGNED, U), header_bytes = header.size() + decoder_bytes;
-    const bool gpu_codes = U >= c->opt(CNIIC_OPT_HUF_GPU_CODES_MIN, "CNIIC_HUF_GPU_CODES_MIN", 32768) && U >= 2;
-    const uint64_t off_code = U * 8, off_len = off_code + U * 8;
-    CNIIC_HIP_TRY(c, ctx_pinned_huf(c, gpu_codes ? U * 8 + 3 * (U - 1) * 4 + 64 : off_len + U));
-    uint8_t *const pin = static_cast<uint8_t *>(c->pinned_huf);
-    uint64_t *const counts = reinterpret_cast<uint64_t *>(pin);
-    std::vector<uint32_t> keys_v(gpu_codes ? 0 : U);
-    DevBuf sort_a, sort_b, len_d, code_d, tree_d, off_d;
-    uint64_t nbits = 0;
-    bool tree_built = false;
-    if (gpu_codes) {  // the leaves come back sorted by (count, key): the host only merges
-        uint64_t *sorted_d = nullptr;
-        CNIIC_HIP_TRY(c, sort_a.alloc(U * 8));
-        CNIIC_HIP_TRY(c, sort_b.alloc(U * 8));
-        CNIIC_TRY(huff_sort_leaves_dev(c, counts_d.as<uint64_t>(), (uint32_t)U, plan.max_count ? plan.max_count : n, sort_a.as<uint64_t>(), sort_b.as<uint64_t>(), &sorted_d));
-        // (round 3) the tree, the codes and the leaves' places in the decoder without the host's merge, when the counts come in runs
-        CNIIC_HIP_TRY(c, len_d.alloc(U));
-        CNIIC_HIP_TRY(c, code_d.alloc(U * 8));
-        CNIIC_HIP_TRY(c, off_d.alloc(U * 8));
-        CNIIC_TRY(huff_tree_from_runs(c, sorted_d, counts_d.as<uint64_t>(), (uint32_t)U, CNIIC_SYM_SIGNED, len_d.as<uint8_t>(), code_d.as<uint64_t>(),
-                                      off_d.as<uint64_t>(), &nbits, &tree_built));
-        if (!tree_built) CNIIC_HIP_TRY(c, hipMemcpyAsync(counts, sorted_d, U * 8, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(keys_v.data(), keys_d.p, U * 4, hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(counts, counts_d.p, U * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+    HuffCodeStage st(c, CNIIC_SYM_SIGNED);
+    CNIIC_TRY(st.begin(table, &plan, n));
+    const uint64_t U = st.U, header_bytes = header.size() + st.decoder_bytes();
+    uint32_t *const keys_d = st.keys_d.as<uint32_t>();
+    const uint8_t *const len_d = st.len_d.as<uint8_t>();
+    const uint64_t *const code_d = st.code_d.as<uint64_t>();
     CNIIC_HIP_TRY(c, ctx_spin_sync(c));
     host_trace().mark("delta: compaction + D2H (wait)");
-    // 2. build() (huf.rs:31); 3. the payload (huf.rs:37-41) behind the serialised decoder (huf.rs:34), whose size follows
-    //    from U alone: U leaves of 1 + 6 bytes and U - 1 branch tags
-    if (!c->huf_scratch) c->huf_scratch = std::make_shared<HuffScratch>();
-    HuffScratch *hscratch = static_cast<HuffScratch *>(c->huf_scratch.get());
-    if (!len_d.p) CNIIC_HIP_TRY(c, len_d.alloc(U));
-    if (!code_d.p) CNIIC_HIP_TRY(c, code_d.alloc(U * 8));
-    HuffTree tree;
+    // 2. build() (huf.rs:31); 3. the payload (huf.rs:37-41) behind the serialised decoder (huf.rs:34)
+    CNIIC_TRY(st.build(packed_d));
     DeltaPackScratch scratch;
     bool counted = false;   // the first half of the pack is already in the stream
-    if (gpu_codes && !tree_built) {
-        uint32_t *left_h = reinterpret_cast<uint32_t *>(counts + U), *right_h = left_h + (U - 1), *nl_h = right_h + (U - 1), root = 0;
-        if (!huff_merge_sorted_into(counts /* sorted leaves */, U, left_h, right_h, nl_h, &root, hscratch))
-            return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U);
-        host_trace().mark("delta: tree (host)");
-        CNIIC_HIP_TRY(c, tree_d.alloc(3 * (U - 1) * 4));
-        if (!off_d.p) CNIIC_HIP_TRY(c, off_d.alloc(U * 8));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(tree_d.p, left_h, 3 * (U - 1) * 4, hipMemcpyHostToDevice, c->stream));
-        const uint32_t *left_d = tree_d.as<uint32_t>(), *right_d = left_d + (U - 1), *nl_d = right_d + (U - 1);
-        CNIIC_TRY(huff_tree_codes(c, left_d, right_d, nl_d, counts_d.as<uint64_t>(), (uint32_t)U, root, CNIIC_SYM_SIGNED, len_d.as<uint8_t>(),
-                                  code_d.as<uint64_t>(), off_d.as<uint64_t>(), small.as<uint64_t>() + 2));  // small[2] bits, [3] too long
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(&c->pinned_u[4], small.as<uint64_t>() + 2, 16, hipMemcpyDeviceToHost, c->stream));
+    if (st.totals_pending) {
         // (round 4) the payload's size is on its way to the host: the first half of the pack, which wants the codes and nothing else, is
         // enqueued behind it, and the host waits for the size while the GPU counts
         if (!c->res_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->res_ev, hipEventDisableTiming));
         CNIIC_HIP_TRY(c, hipEventRecord(c->res_ev, c->stream));
         if (!c->timers) {   // (with the stage timers on the whole pack is timed as one stage below)
-            CNIIC_HIP_TRY(c, hipMemsetAsync(small.as<uint64_t>() + 2, 0, 8, c->stream));
-            CNIIC_TRY(delta_pack16_count(c, hot16.as<uint16_t>(), n, coldkeys.as<uint32_t>(), chunk_cold.as<uint8_t>(), table, keys_d.as<uint32_t>(),
-                                         len_d.as<uint8_t>(), code_d.as<uint64_t>(), U, small.as<uint64_t>() + 2, &scratch));
+            CNIIC_HIP_TRY(c, hipMemsetAsync(packed_d, 0, 8, c->stream));
+            CNIIC_TRY(delta_pack16_count(c, hot16.as<uint16_t>(), n, coldkeys.as<uint32_t>(), chunk_cold.as<uint8_t>(), table, keys_d, len_d, code_d, U, packed_d, &scratch));
             counted = true;
         }
-        {
-            hipError_t e;
-            while ((e = hipEventQuery(c->res_ev)) == hipErrorNotReady) {}
-            CNIIC_HIP_TRY(c, e);
-        }
-        if (c->pinned_u[5]) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U);
-        nbits = c->pinned_u[4];
-        host_trace().mark("delta: codes (GPU)");
-    } else if (!gpu_codes) {
-        uint64_t *const code = reinterpret_cast<uint64_t *>(pin + off_code);
-        uint8_t *const clen = pin + off_len;
-        if (!huff_build_tree(counts, U, tree, hscratch) || !huff_codes_into(tree, clen, code))
-            return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code (alphabet %llu)", (unsigned long long)U);
-        host_trace().mark("delta: tree + codes (host)");
-        for (uint64_t i = 0; i < U; i++) nbits += counts[i] * clen[i];
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(len_d.p, clen, U, hipMemcpyHostToDevice, c->stream));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(code_d.p, code, U * 8, hipMemcpyHostToDevice, c->stream));
+        hipError_t e;
+        while ((e = hipEventQuery(c->res_ev)) == hipErrorNotReady) {}
+        CNIIC_HIP_TRY(c, e);
     }
+    uint64_t nbits = 0;
+    CNIIC_TRY(st.bits(&nbits));
+    CNIIC_TRY(st.upload_codes());
     StreamOut so(c, out, cap, len);
     CNIIC_TRY(so.begin_sized(header_bytes, (nbits + 7) / 8, /*zero=*/false));  // (the pack stores every word of the payload)
-    if (!counted) CNIIC_HIP_TRY(c, hipMemsetAsync(small.as<uint64_t>() + 2, 0, 8, c->stream));
+    if (!counted) CNIIC_HIP_TRY(c, hipMemsetAsync(packed_d, 0, 8, c->stream));
     timer_tree.stop(1);
     if (nbits) {  // (a single symbol: the zero-length code and no payload, huf.rs:140-142)
         ScopedKernelTimer timer(c, "huff_pack");   // (with the count already enqueued this times the second half alone; bench.py's stage figure says so)
         if (!counted)
-            CNIIC_TRY(delta_pack16_count(c, hot16.as<uint16_t>(), n, coldkeys.as<uint32_t>(), chunk_cold.as<uint8_t>(), table, keys_d.as<uint32_t>(),
-                                         len_d.as<uint8_t>(), code_d.as<uint64_t>(), U, small.as<uint64_t>() + 2, &scratch));
-        CNIIC_TRY(delta_pack16_write(c, hot16.as<uint16_t>(), n, coldkeys.as<uint32_t>(), len_d.as<uint8_t>(), code_d.as<uint64_t>(), so.dev, header_bytes * 8,
-                                     &scratch));
+            CNIIC_TRY(delta_pack16_count(c, hot16.as<uint16_t>(), n, coldkeys.as<uint32_t>(), chunk_cold.as<uint8_t>(), table, keys_d, len_d, code_d, U, packed_d, &scratch));
+        CNIIC_TRY(delta_pack16_write(c, hot16.as<uint16_t>(), n, coldkeys.as<uint32_t>(), len_d, code_d, so.dev, header_bytes * 8, &scratch));
         timer.stop(1);
     }
     ScopedKernelTimer timer_fin(c, "delta_finish");   // (the table's sweep, the header, the decoder, the last wait)
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(&c->pinned_u[3], small.as<uint64_t>() + 2, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuDeltaPacked.at, packed_d, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_TRY(delta_table_clean(c));
     host_trace().mark("delta: pack enqueued");
     // the decoder goes in AFTER the pack, whose first word comes out with zeros where the decoder's last bytes are
-    if (gpu_codes) {
-        const uint64_t head = header.size();
-        CNIIC_TRY(so.put_header(header));
-        CNIIC_TRY(huff_tree_serialize_dev(c, keys_d.as<uint32_t>(), off_d.as<uint64_t>(), (uint32_t)U, CNIIC_SYM_SIGNED, so.dev + head, decoder_bytes));
-    } else {
-        huff_serialize_tree(tree, CNIIC_SYM_SIGNED, keys_v.data(), header);  // (the GPU packs meanwhile)
-        host_trace().mark("delta: serialise trie (host)");
-        if (header.size() != header_bytes) return c->fail(CNIIC_ERR_HIP, "delta: decoder of %llu bytes, expected %llu", (unsigned long long)header.size(),
-                                                          (unsigned long long)header_bytes);
-        CNIIC_TRY(so.put_header(header));
-    }
-    host_trace().mark("delta: header");
+    // (a small alphabet's is written out by the host here, while the GPU packs)
+    CNIIC_TRY(st.write_decoder(so, header));
+    if (!st.gpu_codes && header.size() != header_bytes)
+        return c->fail(CNIIC_ERR_HIP, "delta: decoder of %llu bytes, expected %llu", (unsigned long long)header.size(), (unsigned long long)header_bytes);
     const int rc_fin = so.finish();  // (waits for the stream)
     timer_fin.stop(1);
     host_trace().mark("delta: pack + finish");
     host_trace().dump();
     if (rc_fin != CNIIC_OK) return rc_fin;
-    if (c->pinned_u[3] != nbits)
-        return c->fail(CNIIC_ERR_HIP, "huffman: packed %llu bits, histogram predicts %llu", (unsigned long long)c->pinned_u[3], (unsigned long long)nbits);
+    const uint64_t packed_bits = c->pinned_u[kPuDeltaPacked.at];
+    if (packed_bits != nbits)
+        return c->fail(CNIIC_ERR_HIP, "huffman: packed %llu bits, histogram predicts %llu", (unsigned long long)packed_bits, (unsigned long long)nbits);
     return CNIIC_OK;
-}
-
-// ------------------------------------------------------------------ Hilbert{RLE(0.0)}::encode (hilbertc.rs:26-39)
-static int encode_hilbert_rle(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len) {
-    const uint64_t n = (uint64_t)w * h;
-    std::vector<uint8_t> header;
-    put_u32(header, w);  // img.dimensions().serialize (:27)
-    put_u32(header, h);
-    StreamOut so(c, out, cap, len);
-    if (n == 0) {
-        CNIIC_TRY(so.begin(header, 0));
-        return so.finish();
-    }
-    DevBuf lin;
-    CNIIC_HIP_TRY(c, lin.alloc(n * 3));
-    CNIIC_TRY(hilbert_linearize(c, rgb_d, w, h, lin.as<uint8_t>()));  // hilbert::linearize (:29)
-    RlePlan plan;
-    CNIIC_TRY(rle_plan(c, lin.as<uint8_t>(), n, &plan));             // rle_exact (:34)
-    CNIIC_TRY(so.begin_sized(header.size(), plan.nruns * 12, /*zero=*/false));  // count.serialize + color.serialize per run (:35-36):
-    CNIIC_TRY(so.put_header(header));                                            // three whole words each, nothing left to clear
-    CNIIC_TRY(rle_emit(c, lin.as<uint8_t>(), &plan, reinterpret_cast<uint32_t *>(so.dev + 8)));
-    return so.finish();
 }
 
 // ------------------------------------------------------------------ Hilbert{RLE(d)}::encode (hilbertc.rs:26-45): d == 0.0 (-0.0 too) takes the
 // exact branch (:33-39), any other d (negative, NaN and infinite ones included) the running average (:40-45, rle_approx :200-299)
-int encode_hilbert_rle_approx(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len) {
-    if ((uint64_t)w * h >= (1ull << 32)) return c->fail(CNIIC_ERR_BAD_ARG, "image too large");
-    if (d == 0.0) return encode_hilbert_rle(c, rgb_d, w, h, out, cap, len);
+int encode_hilbert_rle(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len) {
     const uint64_t n = (uint64_t)w * h;
+    if (n >= (1ull << 32)) return c->fail(CNIIC_ERR_BAD_ARG, "image too large");
+    const bool exact = d == 0.0;
     std::vector<uint8_t> header;
     put_u32(header, w);  // img.dimensions().serialize (:27)
     put_u32(header, h);
@@ -1031,10 +956,11 @@ int encode_hilbert_rle_approx(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w
     CNIIC_HIP_TRY(c, lin.alloc(n * 3));
     CNIIC_TRY(hilbert_linearize(c, rgb_d, w, h, lin.as<uint8_t>()));  // hilbert::linearize (:29)
     RlePlan plan;
-    CNIIC_TRY(rle_approx_plan(c, lin.as<uint8_t>(), n, d, &plan));    // rle_approx (:41)
-    CNIIC_TRY(so.begin_sized(header.size(), plan.nruns * 12, /*zero=*/false));  // count.serialize + color.serialize per run (:42-43)
-    CNIIC_TRY(so.put_header(header));
-    CNIIC_TRY(rle_approx_emit(c, lin.as<uint8_t>(), &plan, reinterpret_cast<uint32_t *>(so.dev + 8)));
+    CNIIC_TRY(exact ? rle_plan(c, lin.as<uint8_t>(), n, &plan) : rle_approx_plan(c, lin.as<uint8_t>(), n, d, &plan));  // rle_exact (:34) / rle_approx (:41)
+    CNIIC_TRY(so.begin_sized(header.size(), plan.nruns * 12, /*zero=*/false));  // count.serialize + color.serialize per run (:35-36, :42-43):
+    CNIIC_TRY(so.put_header(header));                                            // three whole words each, nothing left to clear
+    uint32_t *const records = reinterpret_cast<uint32_t *>(so.dev + header.size());
+    CNIIC_TRY(exact ? rle_emit(c, lin.as<uint8_t>(), &plan, records) : rle_approx_emit(c, lin.as<uint8_t>(), &plan, records));
     return so.finish();
 }
 
@@ -1052,7 +978,7 @@ int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, u
     case CODEC_CLUSTER_COLORS: return encode_cluster_colors(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats);
     case CODEC_VORONOI: return encode_voronoi(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats);
     case CODEC_DELTA: return encode_delta(c, rgb_d, w, h, out, cap, len);
-    case CODEC_HILBERT_RLE: return encode_hilbert_rle(c, rgb_d, w, h, out, cap, len);
+    case CODEC_HILBERT_RLE: return encode_hilbert_rle(c, 0.0, rgb_d, w, h, out, cap, len);
     }
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
@@ -1369,13 +1295,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         cand[f] = 1;
     };
     auto parse_all = [&](const std::vector<uint32_t> &which) {
-        std::atomic<uint32_t> next{0};
-        auto run = [&]() { for (uint32_t i; (i = next.fetch_add(1)) < which.size();) classify(which[i]); };
-        const uint32_t T = (uint32_t)std::min<size_t>(16, which.size());
-        std::vector<std::thread> th;
-        for (uint32_t i = 1; i < T; i++) th.emplace_back(run);
-        run();
-        for (auto &t : th) t.join();
+        parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t) { classify(which[i]); });
     };
     {
         std::vector<uint32_t> all(F);

@@ -22,8 +22,8 @@ bool        codec_is_lossless(const CodecDesc &d);          // Codec::is_lossles
 int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, uint32_t h, const cniic_kmeans_opts *opts,
                  uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats);
 // Hilbert { compress: RLE(d) }::encode for any d (d == 0.0: the `hilbert(rle)` stream); rgb_d is device memory, out host or device.
-int encode_hilbert_rle_approx(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
-// bytes is HOST memory.
+int encode_hilbert_rle(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
+// bytes may be host or device memory: of a stream in HBM only the head comes to the host, the payload is decoded where it lies.
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h);
 

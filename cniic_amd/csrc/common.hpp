@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -153,12 +154,11 @@ struct Ctx {
     void  *pinned_res = nullptr;  // pinned landing area of K-means result blocks (grown on demand)
     uint64_t pinned_res_bytes = 0;
     hipEvent_t res_ev = nullptr;
-    uint64_t *pinned_u = nullptr;  // 64 KiB of pinned host memory: [0] sp_build's distinct-colour count, [1] the point list's length,
-                                   // [8 ..] this image's pixels per cluster (shared palette); u_ev: behind the copy of [0]
-    hipEvent_t u_ev = nullptr;
+    uint64_t *pinned_u = nullptr;  // 64 KiB of pinned host memory for small answers from the GPU: who owns which words is the PuSlot table below
+    hipEvent_t u_ev = nullptr;     // behind a copy into pinned_u that the host waits for later (kPuSpCount, kPuPaletteWeights)
     std::shared_ptr<void> trie_scratch; // the decoder's parsed leaf table (LeafTable, codec.cpp), kept between calls: 90 MB of fresh pages cost 25 ms
     std::shared_ptr<void> huf_scratch;  // host arrays of the Huffman tree build, kept between calls (HuffScratch, codec.cpp)
-    void  *pinned_huf = nullptr;  // pinned host memory of a `delta` encode: distinct symbols, counts, codes, the serialised decoder
+    void  *pinned_huf = nullptr;  // pinned host memory, grown on demand: the Huffman code stage's counts, tree and codes (HuffCodeStage, codec.cpp); a decode's stream heads
     uint64_t pinned_huf_bytes = 0;
     hipEvent_t huf_ev = nullptr;   // behind the D2H copies of the compacted histogram (huf_encode_all_dev)
     std::shared_ptr<void> scan_leaves;  // the built-in scan of large rectangles: per image size, the recursion's leaves and class tables (k_hilbert.hip)
@@ -204,9 +204,36 @@ inline hipError_t ctx_pinned_huf(Ctx *c, uint64_t bytes) {  // at least `bytes` 
     return e;
 }
 
+// Ctx::pinned_u in u64 words.  Every user has words of its own: a copy into one may still be on its way for one session of a context
+// (cc_image_begin ... cc_finish) when another call on that context starts, so no two meanings share a word.
+struct PuSlot { uint32_t at, words; };
+constexpr uint32_t kPinnedUWords = 64 * 1024 / 8;
+constexpr PuSlot kPuSpCount{0, 1};            // sp_build: distinct colours of the image (k_points.hip)
+constexpr PuSlot kPuPointCount{1, 1};         // cc_image_create: length of the point list, the colours of all images
+constexpr PuSlot kPuImageCount{2, 1};         // cc_image_create: this image's own distinct colours, fetched again
+constexpr PuSlot kPuHufTotals{3, 2};          // the Huffman code stage: payload bits, "a code is too long" (huff_tree_codes)
+constexpr PuSlot kPuDeltaOverflow{5, 1};      // encode_delta: a chunk with more than 64 symbols outside the cube
+constexpr PuSlot kPuDeltaPacked{6, 1};        // encode_delta: bits the pack wrote
+constexpr PuSlot kPuPaletteWeights{8, 4096};  // cc_finish: this image's pixels per cluster (shared palette, K <= 4096)
+constexpr PuSlot kPuHdecode{4104, 3};         // huff_decode_dev: total symbols, "an end moved", blocks that gave the stream up (k_hdecode.hip)
+constexpr PuSlot kPuTrieTotals{4108, 6};      // huff_parse_leaves_dev: TpTotals (k_trieparse.hip)
+constexpr PuSlot kPuLeafRuns{4114, 3};        // huff_tree_from_runs: number of runs, then bits / too long / longest (k_huff.hip)
+constexpr PuSlot kPuSlots[] = {kPuSpCount, kPuPointCount, kPuImageCount, kPuHufTotals, kPuDeltaOverflow, kPuDeltaPacked,
+                               kPuPaletteWeights, kPuHdecode, kPuTrieTotals, kPuLeafRuns};   // in ascending order
+constexpr bool pu_slots_disjoint() {
+    uint32_t end = 0;
+    for (const PuSlot &s : kPuSlots) {
+        if (s.at < end || s.words == 0) return false;
+        end = s.at + s.words;
+    }
+    return end <= kPinnedUWords;
+}
+static_assert(pu_slots_disjoint(), "Ctx::pinned_u: two slots overlap, or the last one ends behind the 64 KiB block");
+static_assert(kPuPaletteWeights.words >= 4096, "Ctx::pinned_u: the shared-palette weights need room for K = 4096");
+
 inline hipError_t ctx_pinned_u(Ctx *c) {
     if (c->pinned_u) return hipSuccess;
-    return hipHostMalloc(reinterpret_cast<void **>(&c->pinned_u), 64 * 1024, hipHostMallocDefault);
+    return hipHostMalloc(reinterpret_cast<void **>(&c->pinned_u), kPinnedUWords * 8, hipHostMallocDefault);
 }
 
 #define CNIIC_TRY(expr)              \
@@ -263,6 +290,25 @@ template <class T> struct Out {
 };
 
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+
+// check_enough_active_clusters (kmeans.rs:41-57): at least 99 % of the K clusters (or every one of fewer points) must have members
+inline int check_enough_active(Ctx *c, uint32_t K, uint64_t npoints, uint64_t active) {
+    const uint64_t min_cc = std::min<uint64_t>((uint64_t)(0.99 * (double)K), npoints);
+    if (active < min_cc)
+        return c->fail(CNIIC_ERR_FEW_ACTIVE, "Not enough active clusters: requested %u, got %llu (min allowed: %llu)", K,
+                       (unsigned long long)active, (unsigned long long)min_cc);
+    return CNIIC_OK;
+}
+
+// body(i, t) for every i in [0, count), dealt out one at a time to `threads` threads; t: which thread (0 is the caller's)
+template <class Body> void parallel_for(uint32_t count, uint32_t threads, Body body) {
+    std::atomic<uint32_t> next{0};
+    auto work = [&](uint32_t t) { for (uint32_t i; (i = next.fetch_add(1)) < count;) body(i, t); };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < threads; t++) pool.emplace_back(work, t);
+    work(0);
+    for (auto &th : pool) th.join();
+}
 
 // Device-resident state of a K-means loop (kmeans.rs:21-39): lets iterations be enqueued back to
 // back; kernels of iterations past convergence exit on `done`.

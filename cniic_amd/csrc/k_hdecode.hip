@@ -772,7 +772,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     CNIIC_HIP_TRY(c, changed.alloc(32));   // [0] an end moved in this check; [5] pass 0's blocks that gave the stream up
     CNIIC_HIP_TRY(c, hipMemsetAsync(changed.p, 0, 32, c->stream));
     CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + 4096;   // (slots of this function's own) [0] total symbols, [1] did the last pass move an end?
+    volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + kPuHdecode.at;   // [0] total symbols, [1] did the last pass move an end?, [2] pass 0's blocks that gave the stream up
     const uint32_t grid = (uint32_t)ceil_div(nsub, kHdThreads);
     const size_t lds = use1 ? kHdLds : (size_t)kHdStageAlloc * 4;
     const bool wide = lt.max_len > 32;

@@ -1199,7 +1199,7 @@ int huff_tree_from_runs(Ctx *c, const uint64_t *sorted_d, const uint64_t *counts
     const uint32_t g = std::min<uint32_t>(ceil_div(n, 256u), 2048u);
     hipLaunchKernelGGL(k_leaf_run_count, dim3(g), dim3(256), 0, c->stream, sorted_d, n, nruns_d);
     CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + 4300;   // (slots of this function's own)
+    volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + kPuLeafRuns.at;
     CNIIC_HIP_TRY(c, hipMemcpyAsync(const_cast<uint64_t *>(pin), nruns_d, 4, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
     const uint32_t R = (uint32_t)pin[0];

@@ -498,14 +498,14 @@ int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan) {
                        blocktot.as<uint32_t>());
     CNIIC_TRY(gidx_finish(c, plan->wprefix.as<uint32_t>(), blocktot.as<uint32_t>(), plan->total.as<uint64_t>()));
     CNIIC_HIP_TRY(c, hipGetLastError());
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
     return CNIIC_OK;
 }
 
 int sp_wait_count(Ctx *c, SpPlan *plan) {
     CNIIC_HIP_TRY(c, hipEventSynchronize(c->u_ev));
-    plan->U = *c->pinned_u;
+    plan->U = c->pinned_u[kPuSpCount.at];
     return CNIIC_OK;
 }
 

@@ -40,6 +40,7 @@ struct TpTotals {
     uint32_t too_deep;       // a stack deeper than kTpMaxP or a leaf deeper than kLeafMaxLen
     uint32_t max_len, min_len;
 };
+static_assert(sizeof(TpTotals) <= kPuTrieTotals.words * 8, "TpTotals must fit its words of Ctx::pinned_u");
 
 __device__ __forceinline__ uint32_t tp_byte(const uint8_t *__restrict__ b, uint64_t nbytes, uint64_t at) { return at < nbytes ? b[at] : 0xffu; }
 
@@ -344,7 +345,7 @@ int huff_parse_leaves_dev(Ctx *c, int sym_kind, const uint8_t *stream_d, uint64_
     CNIIC_HIP_TRY(c, picked.alloc((uint64_t)nchunks * sizeof(TpInfo)));
     CNIIC_HIP_TRY(c, tot_d.alloc(sizeof(TpTotals)));
     CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    TpTotals *th = reinterpret_cast<TpTotals *>(c->pinned_u + 4200);   // (slots of this function's own)
+    TpTotals *th = reinterpret_cast<TpTotals *>(c->pinned_u + kPuTrieTotals.at);
     TpTotals init{};
     init.end_chunk = 0xffffffffu; init.min_len = 0xffffffffu;
     *th = init;
