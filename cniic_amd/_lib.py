@@ -34,6 +34,7 @@ SYMBOLS = [
     "cniic_huf_size", "cniic_codec_parse", "cniic_codec_name", "cniic_codec_is_lossless", "cniic_codec_encode",
     "cniic_codec_encode_opts", "cniic_codec_encode_batch", "cniic_codec_decode", "cniic_codec_decode_batch", "cniic_mse", "cniic_mse_batch",
     "cniic_hilbert_rle_approx_encode", "cniic_synth_image",
+    "cniic_codec_encode_batch_var", "cniic_mse_batch_var", "cniic_codec_measure_batch",
 ]
 
 
@@ -52,6 +53,16 @@ class KmStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MeasureRow(C.Structure):
+    """cniic_measure_row: one row of bench::measure_all's CSV (bench.rs:68-75) + status"""
+    _fields_ = [("compressed_size", C.c_uint64), ("compression_ratio", C.c_double), ("error", C.c_double), ("rc", C.c_int32),
+                ("lossless_mismatch", C.c_uint32), ("kmeans", KmStats)]
+
+    def as_dict(self):
+        return dict(compressed_size=int(self.compressed_size), compression_ratio=float(self.compression_ratio), error=float(self.error),
+                    rc=int(self.rc), lossless_mismatch=int(self.lossless_mismatch), kmeans=self.kmeans.as_dict())
 
 
 COLORPOS = np.dtype([("x", "<u4"), ("y", "<u4"), ("rgb", "u1", (3,)), ("pad", "u1")])
@@ -369,6 +380,48 @@ class Context:
         rc = self._check(self._L.cniic_codec_encode_batch(self.h, expr.encode(), C.byref(o), _ptr(frames), C.c_uint32(w), C.c_uint32(h), C.c_uint32(F),
                                                           _ptr(out), C.c_uint64(stride), lens, rcs, sts), allow)
         return rc, [int(x) for x in lens], [int(x) for x in rcs], [s.as_dict() for s in sts]
+
+    def encode_batch_var(self, expr, images, offs, ws, hs, out, stride, seed=0, max_iters=0, flags=0, allow=()):
+        """cniic_codec_encode_batch_var: len(offs) images of different sizes in one buffer (image f is ws[f] x hs[f] at images[offs[f]:]),
+        each encoded on its own, image f's stream at out[f * stride:].  images / out: device tensors, numpy arrays or addresses.
+        -> (rc, list of lengths, list of per-image status codes, list of stats dicts)"""
+        F = len(offs)
+        n = max(F, 1)
+        off = (C.c_uint64 * n)(*[int(x) for x in offs])
+        w = (C.c_uint32 * n)(*[int(x) for x in ws])
+        h = (C.c_uint32 * n)(*[int(x) for x in hs])
+        lens, rcs, sts = (C.c_uint64 * n)(), (C.c_int32 * n)(), (KmStats * n)()
+        o = self._opts(seed, max_iters, flags)
+        rc = self._check(self._L.cniic_codec_encode_batch_var(self.h, expr.encode(), C.byref(o), _ptr(images), off, w, h, C.c_uint32(F), _ptr(out),
+                                                              C.c_uint64(stride), lens, rcs, sts), allow)
+        return rc, [int(lens[f]) for f in range(F)], [int(rcs[f]) for f in range(F)], [sts[f].as_dict() for f in range(F)]
+
+    def mse_batch_var(self, a, a_offs, b, b_offs, npx):
+        """cniic_mse_batch_var: the MSE of len(npx) pairs of different sizes (pair f: npx[f] pixels at a[a_offs[f]:] and b[b_offs[f]:])
+        -> list of floats"""
+        F = len(npx)
+        n = max(F, 1)
+        ao = (C.c_uint64 * n)(*[int(x) for x in a_offs])
+        bo = (C.c_uint64 * n)(*[int(x) for x in b_offs])
+        px = (C.c_uint64 * n)(*[int(x) for x in npx])
+        v = (C.c_double * n)()
+        self._check(self._L.cniic_mse_batch_var(self.h, _ptr(a), ao, _ptr(b), bo, px, C.c_uint32(F), v))
+        return [float(v[f]) for f in range(F)]
+
+    def measure_batch(self, expr, images, offs, ws, hs, out=None, stride=0, seed=0, max_iters=0, flags=0, allow=()):
+        """cniic_codec_measure_batch: encode, size, ratio, decode, MSE and the lossless check of every image in one call (the body of
+        bench::measure_all's loop).  out (optional): stream f is copied to out[f * stride:].
+        -> (rc, list of row dicts, list of stream lengths)"""
+        F = len(offs)
+        n = max(F, 1)
+        off = (C.c_uint64 * n)(*[int(x) for x in offs])
+        w = (C.c_uint32 * n)(*[int(x) for x in ws])
+        h = (C.c_uint32 * n)(*[int(x) for x in hs])
+        rows, lens = (MeasureRow * n)(), (C.c_uint64 * n)()
+        o = self._opts(seed, max_iters, flags)
+        rc = self._check(self._L.cniic_codec_measure_batch(self.h, expr.encode(), C.byref(o), _ptr(images), off, w, h, C.c_uint32(F), rows, _ptr(out),
+                                                           C.c_uint64(stride), lens), allow)
+        return rc, [rows[f].as_dict() for f in range(F)], [int(lens[f]) for f in range(F)]
 
     def decode(self, expr, data, allow=()):
         raw = np.frombuffer(bytes(data), np.uint8)

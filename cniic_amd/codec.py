@@ -67,6 +67,58 @@ class Codec:
             imgs.append(out[f * img_stride:f * img_stride + n * 3].reshape(hs[f], ws[f], 3).copy())
         return imgs
 
+    @staticmethod
+    def _packed(imgs):
+        """images of any sizes back to back in one host buffer -> (buffer, offsets, widths, heights)"""
+        import numpy as np
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        for im in imgs:
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("images are HxWx3 uint8 arrays, not %r" % (im.shape,))
+        offs = [0]
+        for im in imgs:
+            offs.append(offs[-1] + im.size)
+        buf = np.concatenate([im.reshape(-1) for im in imgs] + [np.zeros(1, np.uint8)])
+        return buf, offs[:-1], [im.shape[1] for im in imgs], [im.shape[0] for im in imgs]
+
+    ENCODE_FAILURES = (_lib.BAD_ARG, _lib.TOO_FEW_POINTS, _lib.FEW_ACTIVE, _lib.CAPACITY)
+
+    def encode_batch(self, imgs, **kw):
+        """encode of several images of any sizes at once (cniic_codec_encode_batch_var): a list of HxWx3 uint8 arrays -> a list of byte
+        strings (None where that image's encode failed); last_stats: the list of their stats"""
+        import numpy as np
+        if len(imgs) == 0:
+            return []
+        buf, offs, ws, hs = self._packed(imgs)
+        F = len(offs)
+        data, stats = [None] * F, [None] * F
+        todo = list(range(F))
+        stride = (max(max(w * h for w, h in zip(ws, hs)) * 2, 1 << 16) + 3) & ~3   # a first guess; a frame that needs more says how much
+        while todo:
+            out = np.empty(stride * len(todo), np.uint8)
+            rc, lens, rcs, sts = self.ctx.encode_batch_var(self.expr, buf, [offs[f] for f in todo], [ws[f] for f in todo], [hs[f] for f in todo],
+                                                           out, stride, allow=self.ENCODE_FAILURES, **kw)
+            again = []
+            for j, f in enumerate(todo):
+                stats[f] = sts[j]
+                if rcs[j] == _lib.OK:
+                    data[f] = out[j * stride:j * stride + lens[j]].tobytes()
+                elif rcs[j] == _lib.CAPACITY and lens[j] > stride:
+                    again.append((f, lens[j]))
+            todo = [f for f, _ in again]
+            stride = (max([n for _, n in again], default=0) + 3) & ~3
+        self.last_stats = stats
+        return data
+
+    def measure(self, imgs, **kw):
+        """bench::measure_all's loop over a list of images of any sizes (cniic_codec_measure_batch): a list of dicts with the reference's
+        CSV columns compressed_size, compression_ratio, error (bench.rs:68-75) plus rc (and lossless_mismatch, kmeans)"""
+        if len(imgs) == 0:
+            return []
+        buf, offs, ws, hs = self._packed(imgs)
+        rc, rows, _ = self.ctx.measure_batch(self.expr, buf, offs, ws, hs, allow=self.ENCODE_FAILURES + (_lib.DECODE,), **kw)
+        return rows
+
     def name(self):
         return _lib.codec_name(self.expr)
 
@@ -107,6 +159,13 @@ class HilbertRleApprox(Codec):
     def encode(self, img, **kw):
         rc, data = self.ctx.hilbert_rle_approx_encode(self.d, img, **kw)
         return data
+
+    def encode_batch(self, imgs, **kw):
+        """the batch calls take the expressions of cniic_codec_parse, which has no rle(d): one cniic_hilbert_rle_approx_encode per image"""
+        return [self.encode(im, **kw) for im in imgs]
+
+    def measure(self, imgs, **kw):
+        raise NotImplementedError("cniic_codec_measure_batch takes the codecs of cniic_codec_parse; hilbert(rle(d)) is not one of them")
 
     def name(self):
         if self.d == 0.0:

@@ -3,6 +3,8 @@
 // error code.  Nothing here computes on the CPU what the reference computes per pixel.
 #include <algorithm>
 #include <cstring>
+#include <limits>
+#include <map>
 #include <memory>
 
 #include "codec.hpp"
@@ -89,6 +91,7 @@ void cniic_ctx_destroy(cniic_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     c->dense.release();
+    c->batch_stage.release();
     c->scan_xy.release();
     c->scan_leaves.reset();   // (device tables of the scan of large rectangles)
     c->pool.trim();
@@ -868,6 +871,9 @@ int32_t cniic_codec_is_lossless(const char *expr) {
     return codec_is_lossless(d) ? 1 : 0;
 }
 
+static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+                                   uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs_out);
+
 // cniic_codec_encode / cniic_codec_encode_opts, the context's mutex held
 static int32_t encode_locked(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
                              uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
@@ -922,6 +928,17 @@ static int32_t batch_workers_ready(cniic_ctx *c, uint32_t S, const char *who) {
     return CNIIC_OK;
 }
 
+// S workers encode side by side: what each gives up so that the others fit
+static void batch_workers_share(cniic_ctx *c, uint32_t S) {
+    for (uint32_t i = 0; i < S; i++) {
+        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        // several images in flight: half-size K-means grids, so that two images' launches are resident together (measured on 64 frames
+        // 1920 x 1080 with 8 workers: 768 blocks 0.885 ms per frame, 384: 0.729, 192: 0.80, 96: 1.17)
+        if (S > 1 && !((c->opt_set >> CNIIC_OPT_KM_MAX_BLOCKS) & 1u) && !getenv("CNIIC_KM_MAX_BLOCKS")) { wk->opt_val[CNIIC_OPT_KM_MAX_BLOCKS] = 384; wk->opt_set |= 1u << CNIIC_OPT_KM_MAX_BLOCKS; }
+        wk->ps_div = S;                        // ... and the persistent K-means launch an S-th of the CUs, so that S of them are resident side by side
+    }
+}
+
 int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
                                  uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs, cniic_kmeans_stats *stats) {
     LOCK(c);
@@ -933,13 +950,7 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
     const uint64_t img_bytes = (uint64_t)w * h * 3;
     const uint32_t S = (uint32_t)std::min<uint64_t>(frames, std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
     CNIIC_TRY(batch_workers_ready(c, S, "codec_encode_batch"));
-    for (uint32_t i = 0; i < S; i++) {
-        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
-        // several images in flight: half-size K-means grids, so that two images' launches are resident together (measured on 64 frames
-        // 1920 x 1080 with 8 workers: 768 blocks 0.885 ms per frame, 384: 0.729, 192: 0.80, 96: 1.17)
-        if (S > 1 && !((c->opt_set >> CNIIC_OPT_KM_MAX_BLOCKS) & 1u) && !getenv("CNIIC_KM_MAX_BLOCKS")) { wk->opt_val[CNIIC_OPT_KM_MAX_BLOCKS] = 384; wk->opt_set |= 1u << CNIIC_OPT_KM_MAX_BLOCKS; }
-        wk->ps_div = S;                        // ... and the persistent K-means launch an S-th of the CUs, so that S of them are resident side by side
-    }
+    batch_workers_share(c, S);
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
     std::vector<int32_t> status(frames, CNIIC_OK);
     parallel_for(frames, S, [&](uint32_t f, uint32_t i) {
@@ -962,6 +973,112 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
     return first;
 }
 
+// ---- images of different sizes (cniic_codec_encode_batch_var, cniic_codec_measure_batch)
+struct VarFrame {
+    const uint8_t *src = nullptr;   // the image (host or device memory, any alignment)
+    uint32_t w = 0, h = 0;
+    uint8_t *out = nullptr;         // where its stream goes, cap bytes at most
+    uint64_t cap = 0;
+    uint64_t len = 0;               // results: what cniic_codec_encode_opts answers for this image alone
+    int32_t rc = CNIIC_OK;
+    cniic_kmeans_stats st{};
+    std::string msg;
+};
+
+// One frame on a worker context.  A DEVICE image that does not start on a 16-byte boundary would leave the pixel partition of
+// cluster-colors and the 16-byte tile reads of `delta` (same bytes, slower routes): it is copied into the worker's aligned scratch
+// first, so that a frame costs what it costs alone at an aligned address wherever it lies in the caller's buffer.  (A host image is
+// staged into fresh, aligned HBM by the single call already.)
+static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kmeans_opts *opts, bool src_dev, VarFrame &fr) {
+    LOCK(wk);
+    const uint64_t npx = (uint64_t)fr.w * fr.h;
+    if (npx >= (1ull << 32)) return wk->fail(CNIIC_ERR_BAD_ARG, "image too large");   // (codec_encode's answer, before anything is staged)
+    const uint8_t *src = fr.src;
+    const bool stage = src_dev && npx && (reinterpret_cast<uintptr_t>(src) & 15);
+    if (stage) {
+        if (wk->batch_stage.bytes < npx * 3) {   // (the largest frames come first: grown once or twice in a batch)
+            DevPool *saved = current_pool();
+            current_pool() = nullptr;            // lives as long as the worker
+            const hipError_t e = wk->batch_stage.alloc(npx * 3);
+            current_pool() = saved;
+            CNIIC_HIP_TRY(wk, e);
+        }
+        CNIIC_HIP_TRY(wk, hipMemcpyAsync(wk->batch_stage.p, src, npx * 3, hipMemcpyDeviceToDevice, wk->stream));
+        src = wk->batch_stage.as<uint8_t>();
+    }
+    const int32_t rc = encode_locked(wk, expr, opts, src, fr.w, fr.h, fr.out, fr.cap, &fr.len, &fr.st);
+    if (stage && wk->timers) wk->ktimes["batch_stage"].launches++;
+    return rc;
+}
+
+// Every frame of the list encoded exactly as cniic_codec_encode_opts would, on the worker contexts of cniic_codec_encode_batch.  The
+// frames are handed out from one queue, LARGEST FIRST: with sizes that differ the last worker to finish then holds a small frame, and
+// frames of one size follow one another, which keeps the few scan tables a context caches (`delta`, `hilbert(rle)`) in use.  Which
+// worker takes which frame shows in no output.  With the stage timers on, the workers' timers are on too and the context's kernel
+// times are the sums over all frames.
+static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
+    const uint32_t n = (uint32_t)fr.size();
+    if (!n) return CNIIC_OK;
+    const uint32_t S = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
+    CNIIC_TRY(batch_workers_ready(c, S, who));
+    batch_workers_share(c, S);
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const uint64_t px = (uint64_t)fr[x].w * fr[x].h, py = (uint64_t)fr[y].w * fr[y].h;
+        if (px != py) return px > py;
+        if (fr[x].w != fr[y].w) return fr[x].w > fr[y].w;
+        return x < y;
+    });
+    std::vector<uint8_t> saved_timers(S);
+    for (uint32_t i = 0; i < S; i++) {
+        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        saved_timers[i] = wk->timers;
+        wk->timers = wk->timers || c->timers;
+    }
+    std::mutex kt_mu;
+    std::map<std::string, KernelTime> kt;
+    parallel_for(n, S, [&](uint32_t j, uint32_t i) {
+        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        VarFrame &f = fr[order[j]];
+        f.rc = encode_var_frame(wk, expr, opts, src_dev, f);
+        if (f.rc != CNIIC_OK) f.msg = wk->err;
+        if (c->timers) {
+            std::lock_guard<std::mutex> lk(kt_mu);
+            for (const auto &e : wk->ktimes) { kt[e.first].ms += e.second.ms; kt[e.first].launches += e.second.launches; }
+        }
+    });
+    for (uint32_t i = 0; i < S; i++) static_cast<cniic_ctx *>(c->batch_workers[i])->timers = saved_timers[i] != 0;
+    if (c->timers) c->ktimes.swap(kt);
+    return CNIIC_OK;
+}
+
+int32_t cniic_codec_encode_batch_var(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                     const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
+                                     int32_t *rcs, cniic_kmeans_stats *stats) {
+    LOCK(c);
+    c->ktimes.clear();
+    CodecDesc d;
+    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    if (!frames) return CNIIC_OK;
+    if (!rgb || !img_off || !w || !h || !out || !lens) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_batch_var: null argument");
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
+    std::vector<VarFrame> fr(frames);
+    for (uint32_t f = 0; f < frames; f++) {
+        fr[f].src = rgb + img_off[f]; fr[f].w = w[f]; fr[f].h = h[f];
+        fr[f].out = out + (uint64_t)f * stride; fr[f].cap = stride;
+    }
+    CNIIC_TRY(encode_frames(c, expr, opts, fr, is_device_ptr(rgb), "codec_encode_batch_var"));
+    int32_t first = CNIIC_OK;
+    for (uint32_t f = 0; f < frames; f++) {
+        lens[f] = fr[f].len;
+        if (rcs) rcs[f] = fr[f].rc;
+        if (stats) stats[f] = fr[f].st;
+        if (fr[f].rc != CNIIC_OK && first == CNIIC_OK) { first = fr[f].rc; c->err = fr[f].msg; }
+    }
+    return first;
+}
+
 int32_t cniic_codec_decode(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w,
                            uint32_t *h) {
     LOCK(c);
@@ -975,6 +1092,12 @@ int32_t cniic_codec_decode(cniic_ctx *c, const char *expr, const uint8_t *bytes,
 int32_t cniic_codec_decode_batch(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
                                  uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs) {
     LOCK(c);
+    return decode_batch_locked(c, expr, bytes, stride, lens, frames, rgb, img_stride, w, h, rcs, nullptr);
+}
+
+// cniic_codec_decode_batch, the context's mutex held (msgs_out: every frame's own message)
+static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+                                   uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs_out) {
     c->ktimes.clear();
     CodecDesc d;
     if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
@@ -1003,6 +1126,7 @@ int32_t cniic_codec_decode_batch(cniic_ctx *c, const char *expr, const uint8_t *
         if (rcs) rcs[f] = status[f];
         if (status[f] != CNIIC_OK && first == CNIIC_OK) { first = status[f]; c->err = msg[f]; }
     }
+    if (msgs_out) msgs_out->swap(msg);
     return first;
 }
 
@@ -1023,6 +1147,190 @@ int32_t cniic_mse_batch(cniic_ctx *c, const uint8_t *a, const uint8_t *b, uint64
     CNIIC_TRY(ia.bind(c, a, npx * 3 * frames));
     CNIIC_TRY(ib.bind(c, b, npx * 3 * frames));
     return mse_rgb_batch(c, ia.d, ib.d, npx, frames, mse);
+}
+
+// cniic_mse_batch_var, the context's mutex held.  A host side is staged as ONE range, from its first pair's first byte to its last pair's last.
+static int32_t mse_batch_var_locked(cniic_ctx *c, const uint8_t *a, const uint64_t *a_off, const uint8_t *b, const uint64_t *b_off, const uint64_t *npx,
+                                    uint32_t frames, double *mse) {
+    uint64_t lo[2] = {~0ull, ~0ull}, hi[2] = {0, 0};
+    for (uint32_t f = 0; f < frames; f++) {
+        if (npx[f] >= (1ull << 61)) return c->fail(CNIIC_ERR_BAD_ARG, "mse_batch_var: pair %u has too many pixels", f);
+        if (!npx[f]) continue;
+        lo[0] = std::min(lo[0], a_off[f]); hi[0] = std::max(hi[0], a_off[f] + npx[f] * 3);
+        lo[1] = std::min(lo[1], b_off[f]); hi[1] = std::max(hi[1], b_off[f] + npx[f] * 3);
+    }
+    if (hi[0] == 0) { for (uint32_t f = 0; f < frames; f++) mse[f] = 0.0; return CNIIC_OK; }
+    if (!a || !b) return c->fail(CNIIC_ERR_BAD_ARG, "mse_batch_var: null argument");
+    // (the kernel reads a + off: a staged side starts at lo, its offsets move down by lo)
+    In<uint8_t> in[2];
+    const uint8_t *base[2] = {a, b};
+    const uint64_t *off[2] = {a_off, b_off};
+    std::vector<uint64_t> moved[2];
+    for (int s = 0; s < 2; s++) {
+        if (is_device_ptr(base[s])) continue;
+        CNIIC_TRY(in[s].bind(c, base[s] + lo[s], hi[s] - lo[s]));
+        moved[s].assign(off[s], off[s] + frames);
+        for (uint32_t f = 0; f < frames; f++) moved[s][f] = npx[f] ? moved[s][f] - lo[s] : 0;
+        base[s] = in[s].d;
+        off[s] = moved[s].data();
+    }
+    return mse_rgb_batch_var(c, base[0], base[1], off[0], off[1], npx, frames, mse);
+}
+
+int32_t cniic_mse_batch_var(cniic_ctx *c, const uint8_t *a, const uint64_t *a_off, const uint8_t *b, const uint64_t *b_off, const uint64_t *npx,
+                            uint32_t frames, double *mse) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!frames) return CNIIC_OK;
+    if (!mse || !a_off || !b_off || !npx) return c->fail(CNIIC_ERR_BAD_ARG, "mse_batch_var: null argument");
+    return mse_batch_var_locked(c, a, a_off, b, b_off, npx, frames, mse);
+}
+
+// ---- bench::measure_all's loop body for a whole folder (cniic_codec_measure_batch)
+// Scratch HBM one chunk of frames may take (streams + decoded images, + the images themselves when they come from host memory); the
+// header states it.  Tests make it small (CNIIC_TEST_MEASURE_BUDGET, bytes) so that a handful of small images takes several chunks.
+constexpr uint64_t kMeasureBudget = 2ull << 30;
+static uint64_t measure_budget() {
+    const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET");
+    return e ? strtoull(e, nullptr, 10) : kMeasureBudget;
+}
+// room for any stream of an image of npx pixels (what the Python mirror gives a single encode; a stream that is longer all the same
+// is encoded again with the size it asked for)
+static uint64_t measure_stream_room(uint64_t npx) { return (64 + npx * 16 + (1ull << 16) + 3) & ~3ull; }
+
+struct MeasureJob {
+    cniic_ctx *c; const char *expr; const cniic_kmeans_opts *opts; bool lossless, src_dev;
+    const uint8_t *rgb; const uint64_t *img_off; const uint32_t *w, *h;
+    cniic_measure_row *rows; uint8_t *out; uint64_t stride; uint64_t *lens;
+    std::vector<std::string> msg;
+    // frames `which` (largest first), `room` bytes for each stream: encode -> decode -> MSE with everything in HBM; frames whose stream
+    // wants more room are left for the caller in `again` with rows[f].compressed_size = the bytes needed
+    int32_t chunk(const std::vector<uint32_t> &which, uint64_t room, std::vector<uint32_t> *again) {
+        const uint32_t n = (uint32_t)which.size();
+        const uint64_t img_stride = std::max<uint64_t>(16, ((uint64_t)w[which[0]] * h[which[0]] * 3 + 15) & ~15ull);
+        DevBuf sbuf, ibuf, hbuf;
+        CNIIC_HIP_TRY(c, sbuf.alloc(room * n));
+        CNIIC_HIP_TRY(c, ibuf.alloc(img_stride * n));
+        std::vector<uint64_t> a_off(n), b_off(n), npx(n), slen(n);
+        const uint8_t *a_base = rgb;
+        if (!src_dev) {   // host images: uploaded once, 16-byte aligned, for the encode and for the MSE
+            CNIIC_HIP_TRY(c, hbuf.alloc(img_stride * n));
+            for (uint32_t j = 0; j < n; j++) {
+                const uint64_t bytes = (uint64_t)w[which[j]] * h[which[j]] * 3;
+                a_off[j] = img_stride * j;
+                if (bytes < (3ull << 32))
+                    CNIIC_HIP_TRY(c, hipMemcpyAsync(hbuf.as<uint8_t>() + a_off[j], rgb + img_off[which[j]], bytes, hipMemcpyHostToDevice, c->stream));
+            }
+            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            a_base = hbuf.as<uint8_t>();
+        } else {
+            for (uint32_t j = 0; j < n; j++) a_off[j] = img_off[which[j]];
+        }
+        std::vector<VarFrame> fr(n);
+        for (uint32_t j = 0; j < n; j++) {
+            fr[j].src = a_base + a_off[j]; fr[j].w = w[which[j]]; fr[j].h = h[which[j]];
+            fr[j].out = sbuf.as<uint8_t>() + room * j; fr[j].cap = room;
+        }
+        CNIIC_TRY(encode_frames(c, expr, opts, fr, true, "codec_measure_batch"));
+        for (uint32_t j = 0; j < n; j++) slen[j] = fr[j].rc == CNIIC_OK ? fr[j].len : 0;
+        std::vector<uint32_t> w2(n), h2(n);
+        std::vector<int32_t> drc(n, CNIIC_OK);
+        std::vector<std::string> dmsg;
+        (void)decode_batch_locked(c, expr, sbuf.as<uint8_t>(), room, slen.data(), n, ibuf.as<uint8_t>(), img_stride, w2.data(), h2.data(), drc.data(), &dmsg);
+        if (dmsg.size() != n) return CNIIC_ERR_HIP;   // (the batch as a whole failed: the message is the context's)
+        for (uint32_t j = 0; j < n; j++) {
+            b_off[j] = img_stride * j;
+            npx[j] = fr[j].rc == CNIIC_OK && drc[j] == CNIIC_OK ? (uint64_t)fr[j].w * fr[j].h : 0;
+        }
+        std::vector<double> err(n);
+        CNIIC_TRY(mse_batch_var_locked(c, a_base, a_off.data(), ibuf.as<uint8_t>(), b_off.data(), npx.data(), n, err.data()));
+        const bool out_dev = out && is_device_ptr(out);
+        for (uint32_t j = 0; j < n; j++) {
+            const uint32_t f = which[j];
+            cniic_measure_row &r = rows[f];
+            r.compressed_size = fr[j].len;
+            r.kmeans = fr[j].st;
+            if (fr[j].rc == CNIIC_ERR_CAPACITY && again) { again->push_back(f); continue; }
+            if (lens) lens[f] = fr[j].len;
+            r.rc = fr[j].rc != CNIIC_OK ? fr[j].rc : drc[j];
+            msg[f] = fr[j].rc != CNIIC_OK ? fr[j].msg : dmsg[j];
+            if (r.rc != CNIIC_OK) { if (fr[j].rc != CNIIC_OK) r.compressed_size = 0; continue; }
+            r.compression_ratio = (double)fr[j].len / ((double)((uint64_t)fr[j].w * fr[j].h) * 24.0) * 100.0;
+            r.error = err[j];
+            r.lossless_mismatch = lossless && err[j] != 0.0;
+            if (out) {
+                if (fr[j].len > stride) {
+                    r.rc = CNIIC_ERR_CAPACITY;
+                    char buf[160];
+                    snprintf(buf, sizeof buf, "measure: stream of frame %u is %llu bytes, %llu between streams", f, (unsigned long long)fr[j].len, (unsigned long long)stride);
+                    msg[f] = buf;
+                } else if (fr[j].len) {
+                    CNIIC_HIP_TRY(c, hipMemcpyAsync(out + (uint64_t)f * stride, fr[j].out, fr[j].len, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+                }
+            }
+        }
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CNIIC_OK;
+    }
+};
+
+int32_t cniic_codec_measure_batch(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                  const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows, uint8_t *out, uint64_t stride,
+                                  uint64_t *lens) {
+    LOCK(c);
+    c->ktimes.clear();
+    CodecDesc d;
+    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    if (!frames) return CNIIC_OK;
+    if (!rgb || !img_off || !w || !h || !rows) return c->fail(CNIIC_ERR_BAD_ARG, "codec_measure_batch: null argument");
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
+    MeasureJob job{c, expr, opts, codec_is_lossless(d), is_device_ptr(rgb), rgb, img_off, w, h, rows, out, stride, lens, std::vector<std::string>(frames)};
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<uint32_t> order, big;
+    for (uint32_t f = 0; f < frames; f++) {
+        memset(&rows[f], 0, sizeof rows[f]);
+        rows[f].compression_ratio = rows[f].error = nan;
+        if (lens) lens[f] = 0;
+        if ((uint64_t)w[f] * h[f] >= (1ull << 32)) { rows[f].rc = CNIIC_ERR_BAD_ARG; job.msg[f] = "image too large"; continue; }
+        order.push_back(f);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const uint64_t px = (uint64_t)w[x] * h[x], py = (uint64_t)w[y] * h[y];
+        return px != py ? px > py : w[x] != w[y] ? w[x] > w[y] : x < y;
+    });
+    // chunks of the list, largest frames first: as many frames as the budget holds at the size of the chunk's first (one at least)
+    const uint64_t budget = measure_budget();
+    std::vector<uint32_t> again;
+    for (size_t i = 0; i < order.size();) {
+        const uint64_t npx0 = (uint64_t)w[order[i]] * h[order[i]], room = measure_stream_room(npx0);
+        const uint64_t per = room + (job.src_dev ? 1 : 2) * std::max<uint64_t>(16, (npx0 * 3 + 15) & ~15ull);
+        const size_t n = (size_t)std::min<uint64_t>(order.size() - i, std::max<uint64_t>(1, budget / per));
+        CNIIC_TRY(job.chunk(std::vector<uint32_t>(order.begin() + i, order.begin() + i + n), room, &again));
+        i += n;
+    }
+    // streams that outgrew their room, with the room they asked for
+    std::sort(again.begin(), again.end(), [&](uint32_t x, uint32_t y) { return rows[x].compressed_size != rows[y].compressed_size ? rows[x].compressed_size > rows[y].compressed_size : x < y; });
+    for (size_t i = 0; i < again.size();) {
+        const uint64_t room = (rows[again[i]].compressed_size + 3) & ~3ull;
+        uint64_t img = 0;
+        size_t n = 0;
+        while (i + n < again.size()) {
+            const uint64_t m = std::max(img, std::max<uint64_t>(16, ((uint64_t)w[again[i + n]] * h[again[i + n]] * 3 + 15) & ~15ull));
+            if (n && (n + 1) * (room + (job.src_dev ? 1 : 2) * m) > budget) break;
+            img = m;
+            n++;
+        }
+        std::vector<uint32_t> part(again.begin() + i, again.begin() + i + n);
+        std::sort(part.begin(), part.end(), [&](uint32_t x, uint32_t y) {
+            const uint64_t px = (uint64_t)w[x] * h[x], py = (uint64_t)w[y] * h[y];
+            return px != py ? px > py : x < y;
+        });
+        CNIIC_TRY(job.chunk(part, room, nullptr));
+        i += n;
+    }
+    for (uint32_t f = 0; f < frames; f++)
+        if (rows[f].rc != CNIIC_OK) { c->err = job.msg[f]; return rows[f].rc; }
+    return CNIIC_OK;
 }
 
 int32_t cniic_synth_image(cniic_ctx *c, int32_t kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *rgb) {

@@ -771,6 +771,7 @@ static int encode_cluster_colors(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint3
     const uint64_t n = (uint64_t)w * h;
     host_trace().mark("enter");
     if (n >= sp_min_pixels(c) && (reinterpret_cast<uintptr_t>(rgb_d) & 15) == 0 && !(opts && (opts->flags & CNIIC_KM_BRUTE_FORCE))) {
+        if (c->timers) c->ktimes["cc_pixel_partition"].launches++;   // (stage timers: which route the call took; no duration)
         CcSession *raw = nullptr;
         CNIIC_TRY(cc_prepare_image(c, rgb_d, n, K, opts, &raw));
         std::unique_ptr<CcSession> s(raw);

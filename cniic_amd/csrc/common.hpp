@@ -165,6 +165,7 @@ struct Ctx {
     DevBuf scan_xy;         // cniic_ctx_set_scan: an injected scan of scan_w x scan_h images, (x, y) per position (uint2[w h])
     uint32_t scan_w = 0, scan_h = 0;
     std::vector<void *> batch_workers;  // cniic_codec_encode_batch: worker contexts (cniic_ctx *), created on first use
+    DevBuf batch_stage;     // a worker of cniic_codec_encode_batch_var: the 16-byte aligned copy of a frame that lies at another address
     const void *poll_owner = nullptr;  // the K-means state whose lagged polls own `pinned` / poll_ev (one loop at a time per context)
 
     int fail(int code, const char *fmt, ...) {
@@ -629,6 +630,9 @@ int rank_from_keys(Ctx *c, const uint32_t *keys_d, uint64_t U, uint32_t *table_d
 int voronoi_paint(Ctx *c, const cniic_colorpos *cent_d, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, bool small_coords = false);
 int mse_rgb(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, double *mse_h);
 int mse_rgb_batch(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, uint32_t frames, double *mse_h);  // F pairs, one result each
+// pairs of different sizes in one launch: pair f is npx[f] pixels at a_d + a_off[f], b_d + b_off[f] (host arrays of `frames` entries)
+int mse_rgb_batch_var(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, const uint64_t *a_off, const uint64_t *b_off, const uint64_t *npx,
+                      uint32_t frames, double *mse_h);
 int synth_image(Ctx *c, int kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *out_d);
 int rgb_to_keys(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t *keys_d);
 

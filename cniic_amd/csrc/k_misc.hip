@@ -357,6 +357,142 @@ int mse_rgb_batch(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, 
     return CNIIC_OK;
 }
 
+// ---------------------------------------------------------------- MSE of pairs of DIFFERENT sizes (cniic_mse_batch_var)
+// One launch for all pairs, whatever their number.  A pair's bytes are cut into chunks of kSqvChunk; the chunks of all pairs, numbered
+// through (first[f]: the first chunk of pair f, built by the host), are dealt to the blocks in contiguous runs, so a block finds its
+// first pair by one search in `first` and walks on from there.  It keeps a running sum while it stays within a pair and gives it up in
+// ONE atomic when it leaves the pair: a pair is never met twice by a block.
+// a + a_off[f] and b + b_off[f] have unrelated alignments.  Every chunk starts a multiple of 16 bytes into its pair, so one pair has one
+// misalignment per side: up to 15 head bytes bring the a side to a 16-byte boundary (byte loads, one thread each), from there a is read
+// in aligned 16-byte words; b is then off its boundary by mb bytes and is read as the two ALIGNED words around each piece, shifted
+// together in registers (the neighbouring lane reads the second word as its first: it comes from the L1, not from HBM).  No load is
+// ever misaligned, and none leaves a 16-byte word that holds a byte of the pair.  (x - y)^2 summed over the four bytes of a word is
+// x.x + y.y - 2 x.y: three v_dot4_u32_u8 instead of four extract / subtract / multiply-add chains, exact in integers.
+constexpr uint32_t kSqvChunk = 32768;   // 256 threads x 16 bytes x 8 steps
+struct SqvFrame { uint64_t a_off, b_off, nbytes; };
+
+__device__ __forceinline__ void sqv_acc(const uint4 &x, const uint4 &y, uint32_t &pos, uint32_t &neg) {
+    // (per thread and chunk at most 8 x 4 words: pos <= 32 * 8 * 65025 < 2^25)
+    pos = __builtin_amdgcn_udot4(x.x, x.x, pos, false); pos = __builtin_amdgcn_udot4(y.x, y.x, pos, false); neg = __builtin_amdgcn_udot4(x.x, y.x, neg, false);
+    pos = __builtin_amdgcn_udot4(x.y, x.y, pos, false); pos = __builtin_amdgcn_udot4(y.y, y.y, pos, false); neg = __builtin_amdgcn_udot4(x.y, y.y, neg, false);
+    pos = __builtin_amdgcn_udot4(x.z, x.z, pos, false); pos = __builtin_amdgcn_udot4(y.z, y.z, pos, false); neg = __builtin_amdgcn_udot4(x.z, y.z, neg, false);
+    pos = __builtin_amdgcn_udot4(x.w, x.w, pos, false); pos = __builtin_amdgcn_udot4(y.w, y.w, pos, false); neg = __builtin_amdgcn_udot4(x.w, y.w, neg, false);
+}
+
+__global__ __launch_bounds__(256) void k_sqerr_var(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, const SqvFrame *__restrict__ fr,
+                                                   const uint32_t *__restrict__ first /* [frames + 1] */, uint32_t frames, uint32_t nchunks,
+                                                   unsigned long long *__restrict__ total) {
+    __shared__ uint64_t wsum[256 / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (uint32_t)(((uint64_t)nchunks + gridDim.x - 1) / gridDim.x);
+    const uint32_t c0 = (uint32_t)min((uint64_t)blockIdx.x * per, (uint64_t)nchunks), c1 = (uint32_t)min((uint64_t)c0 + per, (uint64_t)nchunks);
+    if (c0 >= c1) return;
+    // the pair of chunk c0: the LAST f with first[f] <= c0 (a pair without bytes has no chunk and is never the last)
+    uint32_t f = 0;
+    for (uint32_t hi = frames; hi - f > 1;) {   // first[f] <= c0 < first[hi]
+        const uint32_t mid = f + (hi - f) / 2;
+        if (first[mid] <= c0) f = mid; else hi = mid;
+    }
+    // (everything that steers the loop depends on the block alone: the barriers are met by all threads)
+    auto flush = [&](uint64_t s) {
+        s = wave_reduce_sum64(s);
+        if ((tid & 63) == 0) wsum[tid >> 6] = s;
+        __syncthreads();
+        if (tid == 0) {
+            const uint64_t t = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+            if (t) atomicAdd(&total[f], (unsigned long long)t);
+        }
+        __syncthreads();
+    };
+    uint64_t s = 0;
+    for (uint32_t c = c0; c < c1; c++) {
+        if (c >= first[f + 1]) {
+            flush(s);
+            s = 0;
+            do f++; while (c >= first[f + 1]);
+        }
+        const SqvFrame F = fr[f];
+        const uint64_t at = (uint64_t)(c - first[f]) * kSqvChunk;
+        const uint32_t len = (uint32_t)min((uint64_t)kSqvChunk, F.nbytes - at);
+        const uint8_t *pa = a + F.a_off + at, *pb = b + F.b_off + at;
+        const uint32_t head = min(len, (uint32_t)((0 - reinterpret_cast<uintptr_t>(pa)) & 15));
+        const uint32_t nvec = (len - head) >> 4, tail = (len - head) & 15;
+        if (tid < head) {
+            const int d = (int)pa[tid] - (int)pb[tid];
+            s += (uint32_t)(d * d);
+        } else if (tid >= 64 && tid - 64 < tail) {   // (head < 16: other threads than the head's)
+            const uint32_t i = head + 16 * nvec + (tid - 64);
+            const int d = (int)pa[i] - (int)pb[i];
+            s += (uint32_t)(d * d);
+        }
+        const uint4 *va = reinterpret_cast<const uint4 *>(pa + head);
+        const uint32_t mb = (uint32_t)(reinterpret_cast<uintptr_t>(pb + head) & 15);
+        const uint4 *vb = reinterpret_cast<const uint4 *>(pb + head - mb);
+        uint32_t pos = 0, neg = 0;
+        if (mb == 0) {
+#pragma unroll 2
+            for (uint32_t i = tid; i < nvec; i += 256) sqv_acc(va[i], vb[i], pos, neg);
+        } else {
+            const uint32_t q = mb >> 2, r = (mb & 3) * 8;
+#pragma unroll 2
+            for (uint32_t i = tid; i < nvec; i += 256) {
+                const uint4 x = va[i], l = vb[i], h = vb[i + 1];   // (word i + 1 holds the piece's last byte: inside the pair)
+                uint32_t w[8] = {l.x, l.y, l.z, l.w, h.x, h.y, h.z, h.w};
+                if (q & 1) {
+#pragma unroll
+                    for (int j = 0; j < 7; j++) w[j] = w[j + 1];
+                }
+                if (q & 2) {
+#pragma unroll
+                    for (int j = 0; j < 5; j++) w[j] = w[j + 2];
+                }
+                const uint4 y = make_uint4(__builtin_amdgcn_alignbit(w[1], w[0], r), __builtin_amdgcn_alignbit(w[2], w[1], r),
+                                           __builtin_amdgcn_alignbit(w[3], w[2], r), __builtin_amdgcn_alignbit(w[4], w[3], r));
+                sqv_acc(x, y, pos, neg);
+            }
+        }
+        s += (uint64_t)pos - 2 * (uint64_t)neg;   // (this thread's bytes alone: a sum of squares, never negative)
+    }
+    flush(s);
+}
+
+// a_off / b_off / npx: host arrays of `frames` entries; pair f is npx[f] pixels at a_d + a_off[f], b_d + b_off[f]
+int mse_rgb_batch_var(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, const uint64_t *a_off, const uint64_t *b_off, const uint64_t *npx,
+                      uint32_t frames, double *mse_h) {
+    std::vector<SqvFrame> fr(frames);
+    std::vector<uint32_t> first((size_t)frames + 1);
+    uint64_t nchunks = 0;
+    for (uint32_t f = 0; f < frames; f++) {
+        fr[f] = {a_off[f], b_off[f], npx[f] * 3};
+        first[f] = (uint32_t)nchunks;
+        nchunks += ceil_div(fr[f].nbytes, kSqvChunk);
+        if (nchunks > 0xffffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "mse_batch_var: too many bytes in one call");
+    }
+    first[frames] = (uint32_t)nchunks;
+    if (!nchunks) { for (uint32_t f = 0; f < frames; f++) mse_h[f] = 0.0; return CNIIC_OK; }
+    // one block of scratch: the totals | the pairs | the chunk table
+    const uint64_t off_fr = 8ull * frames, off_first = off_fr + sizeof(SqvFrame) * (uint64_t)frames;
+    DevBuf buf;
+    CNIIC_HIP_TRY(c, buf.alloc(off_first + 4ull * (frames + 1)));
+    uint8_t *p = buf.as<uint8_t>();
+    CNIIC_HIP_TRY(c, hipMemsetAsync(p, 0, off_fr, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(p + off_fr, fr.data(), sizeof(SqvFrame) * (uint64_t)frames, hipMemcpyHostToDevice, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(p + off_first, first.data(), 4ull * (frames + 1), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedKernelTimer t(c, "sqerr_batch_var");
+        hipLaunchKernelGGL(k_sqerr_var, dim3((uint32_t)std::min<uint64_t>(nchunks, 256 * 8)), dim3(256), 0, c->stream, a_d, b_d,
+                           reinterpret_cast<const SqvFrame *>(p + off_fr), reinterpret_cast<const uint32_t *>(p + off_first), frames, (uint32_t)nchunks,
+                           reinterpret_cast<unsigned long long *>(p));
+        CNIIC_HIP_TRY(c, hipGetLastError());
+        t.stop(1);
+    }
+    std::vector<unsigned long long> t(frames);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(t.data(), p, off_fr, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t f = 0; f < frames; f++) mse_h[f] = npx[f] ? (double)t[f] / (double)npx[f] : 0.0;   // (as mse_rgb: the exact integer sum over npx)
+    return CNIIC_OK;
+}
+
 // ---------------------------------------------------------------- synthetic images
 // "U": byte k of the splitmix64 stream seeded with `seed` (LSB-first bytes of successive outputs).
 // "P": per channel, integer bilinear interpolation of a hashed 64-px lattice plus +-8 noise.

@@ -374,7 +374,8 @@ int32_t cniic_codec_encode(cniic_ctx *ctx, const char *expr, const uint8_t *rgb,
 int32_t cniic_codec_encode_opts(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb,
                                 uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len,
                                 cniic_kmeans_stats *stats);
-/* The harness's many-images loop (src/bench.rs:24-35: `paths.into_par_iter()`, one Codec::encode per rayon worker) as ONE call:
+/* The harness's many-images loop (src/bench.rs:24-35: `paths.into_par_iter()`, one Codec::encode per rayon worker) as ONE call, for
+ * EQUALLY SIZED images (cniic_codec_encode_batch_var below takes a folder of any sizes):
  * `frames` images of w x h, contiguous in memory (image f at rgb + f * w * h * 3), each encoded on its own exactly as
  * cniic_codec_encode would -- its own histogram, its own palette, its own stream (byte for byte; tests) -- written at
  * out + f * stride with its length in lens[f].  The images are dealt to CNIIC_OPT_BATCH_STREAMS worker contexts of this context
@@ -383,6 +384,22 @@ int32_t cniic_codec_encode_opts(cniic_ctx *ctx, const char *expr, const cniic_km
  * stats (may be NULL): `frames` entries. */
 int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
                                  uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs, cniic_kmeans_stats *stats);
+/* The same loop (src/bench.rs:24-35) over images of DIFFERENT sizes, which is what the folder the harness was written for holds (DIV2K's
+ * validation set, reference Makefile:14-18): image f is w[f] x h[f] and starts at rgb + img_off[f] (bytes; any alignment; rgb is host or
+ * device memory; the images may not overlap the output).  img_off, w, h, lens, rcs and stats are HOST arrays of `frames` entries.  Stream
+ * f is written at out + f * stride (any stride, like cniic_codec_decode_batch, which reads exactly this layout) and its length to
+ * lens[f]; stream, rcs[f] and stats[f] are byte for byte what cniic_codec_encode_opts gives for image f alone, whatever img_off[f] is.
+ * A stream longer than stride: rcs[f] = CNIIC_ERR_CAPACITY, lens[f] = bytes needed, the other frames are unaffected.  w[f] * h[f] >=
+ * 2^32: rcs[f] = CNIIC_ERR_BAD_ARG, as the single call.  The frames are dealt to the worker contexts of cniic_codec_encode_batch
+ * (CNIIC_OPT_BATCH_STREAMS, the same K-means grid shares) from one queue, largest first; a device image that does not start on a
+ * 16-byte boundary is copied into aligned worker scratch first, so that it takes the routes it takes alone at an aligned address
+ * (the pixel partition of cluster-colors, the tile reads of `delta`).  With CNIIC_OPT_STAGE_TIMERS on, cniic_last_kernel_time answers
+ * with the SUMS over all frames, and knows two more names (launches only, no duration): "cc_pixel_partition" = cluster-colors encodes
+ * that took the pixel partition, "batch_stage" = frames that were copied to aligned scratch.  rcs / stats may be NULL; the call returns
+ * the first failure (lowest f) with that frame's message in cniic_last_error; frames == 0 returns CNIIC_OK. */
+int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                     const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
+                                     int32_t *rcs, cniic_kmeans_stats *stats);
 /* Hilbert { compress: RLE(d) }::encode (hilbertc.rs:26-45; rle_approx :200-299): runs along the Hilbert scan that a pixel joins while its
  * distance to the run's running average is <= d, recorded with the rounded average.  d == 0.0 (or -0.0) gives the `hilbert(rle)`
  * stream; d < 0 or NaN accepts nothing, +inf everything.  cniic_codec_parse does not take `hilbert(rle(d))` for d != 0 (its u32
@@ -407,6 +424,33 @@ int32_t cniic_codec_decode_batch(cniic_ctx *ctx, const char *expr, const uint8_t
 int32_t cniic_mse(cniic_ctx *ctx, const uint8_t *a, const uint8_t *b, uint64_t npx, double *mse);
 /* bench::compute_error for `frames` image pairs of npx pixels each (a + f*npx*3, b + f*npx*3): mse[f] == cniic_mse of that pair. */
 int32_t cniic_mse_batch(cniic_ctx *ctx, const uint8_t *a, const uint8_t *b, uint64_t npx, uint32_t frames, double *mse);
+/* bench::compute_error (src/bench.rs:95-104) for `frames` pairs of DIFFERENT sizes in one launch, whatever their number: pair f is
+ * npx[f] pixels, a + a_off[f] against b + b_off[f] (bytes, any alignment on either side; a and b are host or device memory, a_off /
+ * b_off / npx / mse HOST arrays).  mse[f] is bit-equal to cniic_mse of that pair (the exact integer sum over npx[f]); npx[f] == 0
+ * gives 0.0.  One pair may be longer than 2^32 bytes.  Stage timers: "sqerr_batch_var". */
+int32_t cniic_mse_batch_var(cniic_ctx *ctx, const uint8_t *a, const uint64_t *a_off, const uint8_t *b, const uint64_t *b_off,
+                            const uint64_t *npx, uint32_t frames, double *mse);
+/* The body of bench::measure_all's loop (src/bench.rs:28-76) for a whole folder in ONE call: encode, size, ratio, decode, MSE and
+ * the lossless check, = cniic_codec_encode_batch_var -> cniic_codec_decode_batch -> cniic_mse_batch_var with the streams and the
+ * decoded images staying in HBM.  Row f equals what cniic_codec_encode_opts, cniic_codec_decode and cniic_mse give for image f alone.
+ * The folder is worked through largest image first in chunks of at most 2 GiB of scratch HBM (streams with room for the worst case +
+ * decoded images; an image that needs more on its own is a chunk of its own), so a folder of any size works.  A frame that fails has
+ * its rc set, compressed_size = 0 and compression_ratio = error = NaN, and the others go on (bench.rs:78 prints the error and
+ * continues); the call returns the first failure (lowest f) with its message in cniic_last_error.
+ * out / stride / lens (HOST array) may be NULL / 0 / NULL when the caller does not want the streams; with out, stream f is copied to
+ * out + f * stride (host or device memory) if it fits, otherwise that row's rc is CNIIC_ERR_CAPACITY (its measurements are
+ * still filled in) and lens[f] says what it needs. */
+typedef struct {
+    uint64_t compressed_size;    /* bench.rs:37                                                        */
+    double   compression_ratio;  /* bench.rs:43,74: size / (w * h * 24) * 100, computed in 64 bits      */
+    double   error;              /* bench.rs:48, = cniic_mse(image, decoded)                           */
+    int32_t  rc;                 /* CNIIC_OK, or what the encode / the decode of this image returned   */
+    uint32_t lossless_mismatch;  /* bench.rs:57-59: 1 = a lossless codec whose decode differs          */
+    cniic_kmeans_stats kmeans;   /* of the encode                                                      */
+} cniic_measure_row;
+int32_t cniic_codec_measure_batch(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                  const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows,
+                                  uint8_t *out, uint64_t stride, uint64_t *lens);
 
 /* ------------------------------------------------------------------ synthetic inputs (bench/tests) */
 #define CNIIC_SYNTH_UNIFORM 0  /* "U": splitmix64 byte stream                               */

@@ -10,6 +10,9 @@
 // binary PPM (P6) files or synthetic specs "synth:P:4096x4096:2" / "synth:U:512x512:1" (kind, size, seed offset).
 // The raw size is computed in 64 bits (the reference's u32 h*w*24 wraps above 13377^2 pixels).
 // Images run one per worker thread, each with its own cniic_ctx (the reference uses rayon, bench.rs:24-28).
+//   cniic_bench --codec=<expr> --one-call <image>...
+// loads all the images first (back to back in one device buffer) and hands the whole loop to ONE cniic_codec_measure_batch: the same
+// CSV, rows in argument order, the same exit status.
 #include <sys/stat.h>
 #include <zlib.h>
 
@@ -122,9 +125,62 @@ static bool parse_synth(const std::string &s, Image &im) {  // synth:P:4096x4096
     return true;
 }
 
+// --one-call: bench::measure_all's loop (bench.rs:24-83) as one cniic_codec_measure_batch over all the images
+static int run_one_call(const std::string &expr, const char *name, const std::vector<std::string> &paths, FILE *csv) {
+    cniic_ctx *ctx = nullptr;
+    if (cniic_ctx_create(0, nullptr, &ctx) != CNIIC_OK) { fprintf(stderr, "no usable MI355X\n"); return 1; }
+    int failures = 0;
+    std::vector<Image> ims;
+    std::vector<std::string> names;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> w, h;
+    uint64_t total = 0;
+    for (const std::string &p : paths) {
+        Image im;
+        if (!parse_synth(p, im) && !read_png(p, im) && !read_ppm(p, im)) {
+            fprintf(stderr, "%s: cannot read image (PNG, binary PPM or synth:<P|U>:<w>x<h>[:seed]) ()\n", p.c_str());
+            failures++;
+            continue;
+        }
+        names.push_back(p); off.push_back(total); w.push_back(im.w); h.push_back(im.h);
+        total += (uint64_t)im.w * im.h * 3;
+        ims.push_back(std::move(im));
+    }
+    const uint32_t F = (uint32_t)ims.size();
+    void *dimg = nullptr;
+    if (F && cniic_dev_alloc(ctx, total, &dimg) != CNIIC_OK) { fprintf(stderr, "device allocation (%s)\n", cniic_last_error(ctx)); cniic_ctx_destroy(ctx); return 1; }
+    for (uint32_t f = 0; f < F; f++) {
+        uint8_t *at = (uint8_t *)dimg + off[f];
+        if (ims[f].synth) cniic_synth_image(ctx, ims[f].kind, ims[f].seed, w[f], h[f], at);
+        else cniic_memcpy(ctx, at, ims[f].rgb.data(), ims[f].rgb.size());
+        std::vector<uint8_t>().swap(ims[f].rgb);
+    }
+    std::vector<cniic_measure_row> rows(F);
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = cniic_codec_measure_batch(ctx, expr.c_str(), nullptr, (const uint8_t *)dimg, off.data(), w.data(), h.data(), F, rows.data(), nullptr, 0, nullptr);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != CNIIC_OK) fprintf(stderr, "first failure: %s\n", cniic_last_error(ctx));
+    const bool lossless = cniic_codec_is_lossless(expr.c_str()) == 1;
+    bool wrote_header = false;
+    uint64_t npx_all = 0;
+    for (uint32_t f = 0; f < F; f++) {
+        if (rows[f].rc != CNIIC_OK) { fprintf(stderr, "%s: encode / decode failed (status %d)\n", names[f].c_str(), rows[f].rc); failures++; continue; }
+        if (lossless && rows[f].lossless_mismatch) { fprintf(stderr, "%s: Decoded image doesn't match\n", names[f].c_str()); failures++; continue; }
+        if (!wrote_header) { fprintf(csv, "name,compressed_size,compression_ratio,error\n"); printf("name,compressed_size,compression_ratio,error,iters\n"); wrote_header = true; }
+        fprintf(csv, "%s,%llu,%.17g,%.17g\n", names[f].c_str(), (unsigned long long)rows[f].compressed_size, rows[f].compression_ratio, rows[f].error);
+        printf("%s,%llu,%.6f,%.4f,%llu\n", names[f].c_str(), (unsigned long long)rows[f].compressed_size, rows[f].compression_ratio, rows[f].error,
+               (unsigned long long)rows[f].kmeans.iterations);
+        npx_all += (uint64_t)w[f] * h[f];
+    }
+    printf("# %s: %u images, %.1f Mpix, one call of %.1f ms (encode + decode + MSE)\n", name, F, npx_all / 1e6, ms);
+    if (dimg) cniic_dev_free(ctx, dimg);
+    cniic_ctx_destroy(ctx);
+    return failures ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 3 || strncmp(argv[1], "--codec=", 8) != 0) {
-        fprintf(stderr, "Usage: cniic_bench --codec=<codec> [<img file>..]\nAvailable codecs:\n  hufman\n  cluster-colors(<ncolors>)\n  voronoi(<k>)\n  delta\n  hilbert(rle)\n");
+        fprintf(stderr, "Usage: cniic_bench --codec=<codec> [--one-call] [<img file>..]\nAvailable codecs:\n  hufman\n  cluster-colors(<ncolors>)\n  voronoi(<k>)\n  delta\n  hilbert(rle)\n");
         return 2;
     }
     const std::string expr = argv[1] + 8;
@@ -138,7 +194,17 @@ int main(int argc, char **argv) {
     std::mutex mu;
     bool wrote_header = false;
     int failures = 0;
-    std::vector<std::string> paths(argv + 2, argv + argc);
+    std::vector<std::string> paths;
+    bool one_call = false;
+    for (int i = 2; i < argc; i++) {
+        if (!strcmp(argv[i], "--one-call")) one_call = true;
+        else paths.push_back(argv[i]);
+    }
+    if (one_call) {
+        const int rc = run_one_call(expr, name, paths, csv);
+        fclose(csv);
+        return rc;
+    }
     const unsigned nthreads = std::min<unsigned>((unsigned)paths.size(), std::max(1u, std::min(4u, std::thread::hardware_concurrency())));
     std::vector<std::thread> pool;
     size_t next = 0;
