@@ -34,7 +34,7 @@ SYMBOLS = [
     "cniic_huf_size", "cniic_codec_parse", "cniic_codec_name", "cniic_codec_is_lossless", "cniic_codec_encode",
     "cniic_codec_encode_opts", "cniic_codec_encode_batch", "cniic_codec_decode", "cniic_codec_decode_batch", "cniic_mse", "cniic_mse_batch",
     "cniic_hilbert_rle_approx_encode", "cniic_synth_image",
-    "cniic_codec_encode_batch_var", "cniic_mse_batch_var", "cniic_codec_measure_batch",
+    "cniic_codec_encode_batch_var", "cniic_mse_batch_var", "cniic_codec_measure_batch", "cniic_codec_parse_f64",
 ]
 
 
@@ -495,9 +495,23 @@ def codec_parse(expr):
     return kind.value, arg.value
 
 
+def codec_parse_f64(expr):
+    """cniic_codec_parse_f64: every expression, hilbert(rle(d)) included -> (kind, u32 argument, d), or None"""
+    kind, arg, darg = C.c_int32(0), C.c_uint32(0), C.c_double(0.0)
+    rc = lib().cniic_codec_parse_f64(expr.encode(), C.byref(kind), C.byref(arg), C.byref(darg))
+    if rc != OK:
+        return None
+    return kind.value, arg.value, darg.value
+
+
 def codec_name(expr):
-    buf = C.create_string_buffer(64)
-    rc = lib().cniic_codec_name(expr.encode(), buf, C.c_uint64(64))
+    cap = 64
+    while True:   # (hilbert-rle-approx_<d> spells d without an exponent: 5e-324 takes more than 330 characters)
+        buf = C.create_string_buffer(cap)
+        rc = lib().cniic_codec_name(expr.encode(), buf, C.c_uint64(cap))
+        if rc != CAPACITY or cap >= 1 << 16:
+            break
+        cap *= 8
     if rc != OK:
         raise CniicError(rc, "Malformed codec argument: %s" % expr)
     return buf.value.decode()

@@ -6,7 +6,8 @@
     img2  = codec.decode(data)         # None where the reference returns None / panics
     codec.name(), codec.is_lossless()
 
-    HilbertRleApprox(4.0)               # hilbert(rle(4)): its own class, AnyCodec.from_str does not build it
+    AnyCodec.from_str("hilbert(rle(4))")   # the lossy running-average RLE is an expression like the others
+    HilbertRleApprox(4.0)                   # the same codec for a caller that holds d as a float
 """
 import math
 from decimal import Decimal
@@ -18,7 +19,7 @@ class Codec:
     """encode / decode / name / is_lossless, like `trait Codec` (src/codec.rs:14-19)."""
 
     def __init__(self, expr, ctx=None):
-        if _lib.codec_parse(expr) is None:
+        if _lib.codec_parse_f64(expr) is None:
             raise ValueError("Malformed codec argument: %r" % expr)  # main.rs:62-63
         self.expr = expr
         self._ctx = ctx
@@ -146,26 +147,25 @@ def rust_f64_display(d):
     return s
 
 
+def rust_f64_expr(d):
+    """an <f64> that Rust's f64::from_str (and cniic_codec_parse_f64) reads back as exactly d: repr ("4.0", "1e-07", "inf", "nan")"""
+    return repr(float(d))
+
+
 class HilbertRleApprox(Codec):
-    """Hilbert { compress: RLE(d) } (src/codec/hilbertc.rs:12-98, rle_approx :200-299) for any f64 d.  cniic_codec_parse takes only
-    d == 0 (`hilbert(rle)`), so this codec has its own encode entry point; its streams decode as `hilbert(rle)` (same records)."""
+    """Hilbert { compress: RLE(d) } (src/codec/hilbertc.rs:12-98, rle_approx :200-299) for any f64 d: the codec of the expression
+    hilbert(rle(<d>)), built from the float.  encode goes through cniic_hilbert_rle_approx_encode (the same bytes), everything else
+    through the expression."""
 
     def __init__(self, d, ctx=None):
         self.d = float(d)
-        self.expr = "hilbert(rle)"   # the decoder (RleDecoder, hilbertc.rs:304-335)
+        self.expr = "hilbert(rle(%s))" % rust_f64_expr(self.d)
         self._ctx = ctx
         self.last_stats = None
 
     def encode(self, img, **kw):
         rc, data = self.ctx.hilbert_rle_approx_encode(self.d, img, **kw)
         return data
-
-    def encode_batch(self, imgs, **kw):
-        """the batch calls take the expressions of cniic_codec_parse, which has no rle(d): one cniic_hilbert_rle_approx_encode per image"""
-        return [self.encode(im, **kw) for im in imgs]
-
-    def measure(self, imgs, **kw):
-        raise NotImplementedError("cniic_codec_measure_batch takes the codecs of cniic_codec_parse; hilbert(rle(d)) is not one of them")
 
     def name(self):
         if self.d == 0.0:

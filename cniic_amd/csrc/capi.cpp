@@ -850,9 +850,18 @@ int32_t cniic_huf_size(int32_t sym_kind, const uint64_t *counts, uint64_t n, uin
 // ------------------------------------------------------------------ Codec trait
 int32_t cniic_codec_parse(const char *expr, int32_t *kind, uint32_t *arg) {
     CodecDesc d;
+    if (!parse_codec(expr, &d) || d.darg != 0.0) return CNIIC_ERR_BAD_ARG;   // (kind, arg) cannot say hilbert(rle(d)), d != 0: cniic_codec_parse_f64
+    if (kind) *kind = d.kind;
+    if (arg) *arg = d.arg;
+    return CNIIC_OK;
+}
+
+int32_t cniic_codec_parse_f64(const char *expr, int32_t *kind, uint32_t *arg, double *darg) {
+    CodecDesc d;
     if (!parse_codec(expr, &d)) return CNIIC_ERR_BAD_ARG;
     if (kind) *kind = d.kind;
     if (arg) *arg = d.arg;
+    if (darg) *darg = d.darg;
     return CNIIC_OK;
 }
 
@@ -1104,7 +1113,7 @@ static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t
     if (!frames) return CNIIC_OK;
     if (!bytes || !lens || !rgb || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "codec_decode_batch: null argument");
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the streams on this context's stream is done
-    // `hufman` / `cluster-colors`: the frames decoded together (codec_decode_batch_route); the rest, each on its own on the workers
+    // `hufman` / `cluster-colors` / `hilbert(rle)`: the frames decoded together (codec_decode_batch_route); the rest, each on its own on the workers
     std::vector<uint8_t> taken;
     std::vector<int32_t> status;
     std::vector<std::string> msg;

@@ -7,11 +7,12 @@
 //   VoronoiCluster  src/codec/clusterc.rs:147 5-D K-means, centroids only; Voronoi repaint on decode
 //   Delta           src/codec/hilbertc.rs:404 Hilbert gather -> neighbour delta -> huf::encode_all
 //   Hilbert{RLE(d)} src/codec/hilbertc.rs:12  Hilbert gather -> run-length records: exact for d == 0, else
-//                                             the running average (k_rle_approx.hip; an entry point of its own, not a --codec= expression)
+//                                             the running average (k_rle_approx.hip): `hilbert(rle)` and `hilbert(rle(<f64>))`
 #include "codec.hpp"
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -44,19 +45,54 @@ static bool match_fun_u32(const std::string &s, const char *const *names, uint32
     return false;
 }
 
-// Hilbert::from_str (hilbertc.rs:341-397): fun_call named ^[Hh]ilbert$ with one argument, `rle` or `rle(<f64>)`.
-// As a --codec= expression only the exact method (d == 0.0) is taken; rle(d != 0) has an entry point of its own
-// (cniic_hilbert_rle_approx_encode), zip is not built.
-static bool match_hilbert_rle(const std::string &s) {
+// <f64> as Rust's f64::from_str reads it (hilbertc.rs:376): an optional sign, then `inf`, `infinity` or `nan` in any letter case, or
+// decimal digits with an optional `.` and an optional e/E exponent -- at least one mantissa digit, at least one exponent digit; no
+// blanks, no hex, no suffix, no nan(...).  The value is strtod's of that string: correctly rounded, out-of-range magnitudes to inf or 0.
+static bool parse_rust_f64(const std::string &t, double *out) {
+    size_t p = 0;
+    if (p < t.size() && (t[p] == '+' || t[p] == '-')) p++;
+    std::string rest = t.substr(p);
+    std::transform(rest.begin(), rest.end(), rest.begin(), [](unsigned char ch) { return (char)tolower(ch); });
+    if (rest != "inf" && rest != "infinity" && rest != "nan") {
+        size_t q = p, digits = 0;
+        while (q < t.size() && isdigit((unsigned char)t[q])) { q++; digits++; }
+        if (q < t.size() && t[q] == '.') {
+            q++;
+            while (q < t.size() && isdigit((unsigned char)t[q])) { q++; digits++; }
+        }
+        if (!digits) return false;
+        if (q < t.size() && (t[q] == 'e' || t[q] == 'E')) {
+            q++;
+            if (q < t.size() && (t[q] == '+' || t[q] == '-')) q++;
+            size_t ed = 0;
+            while (q < t.size() && isdigit((unsigned char)t[q])) { q++; ed++; }
+            if (!ed) return false;
+        }
+        if (q != t.size()) return false;
+    }
+    *out = strtod(t.c_str(), nullptr);
+    return true;
+}
+
+// Hilbert::from_str (hilbertc.rs:341-397): fun_call named ^[Hh]ilbert$ with one argument, `rle` or `rle(<f64>)`; zip is not built.
+// *d: 0 for the exact method (`rle`, and d == 0.0 or -0.0: hilbertc.rs:33,82,91 compare with == 0.0), else d as written.
+static bool match_hilbert_rle(const std::string &s, double *d) {
+    *d = 0.0;
     if (s.compare(0, 8, "hilbert(") != 0 && s.compare(0, 8, "Hilbert(") != 0) return false;
     if (s.size() < 10 || s.back() != ')') return false;
     const std::string arg = s.substr(8, s.size() - 9);
     if (arg == "rle") return true;
     if (arg.size() > 5 && arg.compare(0, 4, "rle(") == 0 && arg.back() == ')') {
         const std::string num = arg.substr(4, arg.size() - 5);
+        double v = 0.0;
+        if (parse_rust_f64(num, &v)) {
+            if (v != 0.0) *d = v;   // (NaN is "not zero")
+            return true;
+        }
+        // (spellings of zero that strtod alone used to decide, a hex 0x0 or a leading blank among them, stay what they were: `hilbert(rle)`)
         char *end = nullptr;
-        const double d = strtod(num.c_str(), &end);
-        return end && *end == 0 && !num.empty() && d == 0.0;
+        v = strtod(num.c_str(), &end);
+        return end && *end == 0 && !num.empty() && v == 0.0;
     }
     return false;
 }
@@ -69,16 +105,41 @@ bool parse_codec(const char *expr, CodecDesc *out) {
                                      "c-colors", "c-col", "ccolors", "ccol", nullptr};  // c(?:luster)?-?col(?:ors)?
     static const char *const vo[] = {"voronoi", nullptr};
     uint32_t k = 0;
-    if (match_fun_u32(s, cc, &k)) { *out = {CODEC_CLUSTER_COLORS, k}; return true; }
-    if (match_fun_u32(s, vo, &k)) { *out = {CODEC_VORONOI, k}; return true; }
-    if (s == "delta") { *out = {CODEC_DELTA, 0}; return true; }  // prs::expect_name: ^delta$
-    if (match_hilbert_rle(s)) { *out = {CODEC_HILBERT_RLE, 0}; return true; }
+    double dv = 0.0;
+    if (match_fun_u32(s, cc, &k)) { *out = {CODEC_CLUSTER_COLORS, k, 0.0}; return true; }
+    if (match_fun_u32(s, vo, &k)) { *out = {CODEC_VORONOI, k, 0.0}; return true; }
+    if (s == "delta") { *out = {CODEC_DELTA, 0, 0.0}; return true; }  // prs::expect_name: ^delta$
+    if (match_hilbert_rle(s, &dv)) { *out = {CODEC_HILBERT_RLE, 0, dv}; return true; }
     if (s.size() == 6) {                                         // hufc.rs:54-59 eq_ignore_ascii_case
         std::string t = s;
         std::transform(t.begin(), t.end(), t.begin(), [](unsigned char ch) { return (char)tolower(ch); });
-        if (t == "hufman") { *out = {CODEC_HUFMAN, 0}; return true; }
+        if (t == "hufman") { *out = {CODEC_HUFMAN, 0, 0.0}; return true; }
     }
     return false;
+}
+
+// f64's Display (format!("{}", d), hilbertc.rs:84): the shortest digits that read back as d, never an exponent; inf, -inf, NaN
+std::string rust_f64_display(double d) {
+    if (std::isnan(d)) return "NaN";
+    if (std::isinf(d)) return d > 0 ? "inf" : "-inf";
+    char buf[40];
+    int prec = 1;
+    for (; prec < 17; prec++) {   // (17 significant digits always read back)
+        snprintf(buf, sizeof buf, "%.*e", prec - 1, d);
+        if (strtod(buf, nullptr) == d) break;
+    }
+    snprintf(buf, sizeof buf, "%.*e", prec - 1, std::fabs(d));
+    std::string digits;
+    const char *q = buf;
+    for (; *q && *q != 'e'; q++) if (isdigit((unsigned char)*q)) digits.push_back(*q);
+    const int e10 = atoi(q + 1);   // d = digits[0] . digits[1..] x 10^e10
+    while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+    const int nd = (int)digits.size();
+    std::string out = std::signbit(d) ? "-" : "";
+    if (d == 0.0) return out + "0";
+    if (e10 >= nd - 1) return out + digits + std::string((size_t)(e10 - (nd - 1)), '0');
+    if (e10 >= 0) return out + digits.substr(0, (size_t)e10 + 1) + "." + digits.substr((size_t)e10 + 1);
+    return out + "0." + std::string((size_t)(-e10 - 1), '0') + digits;
 }
 
 std::string codec_name(const CodecDesc &d) {
@@ -87,12 +148,14 @@ std::string codec_name(const CodecDesc &d) {
     case CODEC_CLUSTER_COLORS: return "cluster-colors_" + std::to_string(d.arg);  // clusterc.rs:59-61
     case CODEC_VORONOI: return "voronoi_" + std::to_string(d.arg);        // clusterc.rs:191-193
     case CODEC_DELTA: return "delta";                                     // hilbertc.rs:433-435
-    case CODEC_HILBERT_RLE: return "hilbert-rle";                         // hilbertc.rs:83-85
+    case CODEC_HILBERT_RLE: return d.darg == 0.0 ? "hilbert-rle" : "hilbert-rle-approx_" + rust_f64_display(d.darg);  // hilbertc.rs:80-86
     }
     return "";
 }
 
-bool codec_is_lossless(const CodecDesc &d) { return d.kind == CODEC_HUFMAN || d.kind == CODEC_DELTA || d.kind == CODEC_HILBERT_RLE; }
+bool codec_is_lossless(const CodecDesc &d) {   // (hilbertc.rs:88-93: RLE(d) is lossless iff d == 0.0 -- NaN is not)
+    return d.kind == CODEC_HUFMAN || d.kind == CODEC_DELTA || (d.kind == CODEC_HILBERT_RLE && d.darg == 0.0);
+}
 
 // ------------------------------------------------------------------ output assembly
 // The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in
@@ -979,7 +1042,7 @@ int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, u
     case CODEC_CLUSTER_COLORS: return encode_cluster_colors(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats);
     case CODEC_VORONOI: return encode_voronoi(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats);
     case CODEC_DELTA: return encode_delta(c, rgb_d, w, h, out, cap, len);
-    case CODEC_HILBERT_RLE: return encode_hilbert_rle(c, 0.0, rgb_d, w, h, out, cap, len);
+    case CODEC_HILBERT_RLE: return encode_hilbert_rle(c, d.darg, rgb_d, w, h, out, cap, len);
     }
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
@@ -1224,20 +1287,107 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
 
+// ------------------------------------------------------------------ `hilbert(rle)` frames of a batch (whatever d they were written with)
+// The same 12-byte records at a fixed place behind the 8-byte header: nothing to parse.  A frame is taken when its header is there
+// (lens[f] >= 8), 0 < w h <= kRleBatchMaxPx and the image fits img_stride; the others are the caller's (its single decode answers for
+// them).  kRleBatchMaxPx is where the route stopped paying when it was measured against the worker contexts on batches of one frame
+// size (tools/batch_var_probe.py --hilbert --sweep, profiles/batch_var_probe_hilbert.json): 5.3x at 64 x 64, 3.9x at 256 x 256 and 1.23x
+// at 512 x 384 (196 608 pixels), but 0.92x at 800 x 600 (480 000) and 0.87x on 100 images of DIV2K's sizes -- from there on a frame's
+// time is its scatter along the scan, which this route runs one after the other on one stream and eight workers run side by side.  The
+// taken frames are worked through in sets -- at most kBatchRouteFrames frames and kRleSetScratch bytes of scratch (records' offsets +
+// colours in scan order; a frame that needs more is a set of its own) -- each of them ONE set of launches for the expansion
+// (rle_expand_batch_dev), then a scatter per frame along its scan on the same stream (an injected scan applies to the frames of its
+// size), the copies out, and one wait.
+constexpr size_t kBatchRouteFrames = 4096;          // frames per set of launches
+constexpr uint64_t kRleSetScratch = 2ull << 30;
+constexpr uint64_t kRleBatchMaxPx = 1ull << 18;   // 2^18 = 262 144 pixels: between the last size that won and the first that lost
+static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, bool dst_dev,
+                                  uint64_t img_stride, uint32_t *w, uint32_t *h, const std::vector<const uint8_t *> &head_p, const std::vector<uint64_t> &head_n,
+                                  const std::vector<uint8_t> &off_route, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs, std::vector<std::string> &msgs) {
+    std::vector<uint32_t> route;
+    for (uint32_t f = 0; f < F; f++) {
+        if (off_route[f] || lens[f] < 8) continue;
+        uint64_t pos = 0;
+        uint32_t fw, fh;
+        if (!get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) continue;
+        const uint64_t n = (uint64_t)fw * fh;
+        if (!n || n > kRleBatchMaxPx || n * 3 > img_stride) continue;
+        w[f] = fw; h[f] = fh;
+        route.push_back(f);
+    }
+    auto scratch_of = [&](uint32_t f) {   // offsets (4 bytes per record) + colours + a staged image, each rounded up
+        const uint64_t n = (uint64_t)w[f] * h[f];
+        return (lens[f] - 8) / 12 * 4 + 2 * ((n * 3 + 15) & ~15ull) + (bytes_dev ? 0 : lens[f]);
+    };
+    for (size_t i0 = 0; i0 < route.size();) {
+        size_t i1 = i0;
+        uint64_t need = 0;
+        while (i1 < route.size() && i1 - i0 < kBatchRouteFrames && (i1 == i0 || need + scratch_of(route[i1]) <= kRleSetScratch)) need += scratch_of(route[i1++]);
+        const size_t S = i1 - i0;
+        // ---- the streams in HBM (a host batch: from the set's first frame to its last, in one copy), the colours and staged images
+        DevBuf up_d, lin_d, img_d;
+        const uint8_t *base = bytes;
+        if (!bytes_dev) {
+            const uint64_t lo = (uint64_t)route[i0] * stride, hi = (uint64_t)route[i1 - 1] * stride + lens[route[i1 - 1]];
+            CNIIC_HIP_TRY(c, up_d.alloc(hi - lo + 16));
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+            base = up_d.as<uint8_t>() - lo;
+        }
+        std::vector<RleBatchFrame> bf(S);
+        std::vector<uint64_t> img_at(S, ~0ull);
+        uint64_t lin_bytes = 0, img_bytes = 0;
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            const uint64_t n = (uint64_t)w[f] * h[f], body = lens[f] - 8;
+            bf[i].rec_d = base + (uint64_t)f * stride + 8;
+            bf[i].R = body / 12; bf[i].tail_bytes = body % 12; bf[i].n = n;
+            lin_bytes += (n * 3 + 15) & ~15ull;
+            if (!dst_dev) { img_at[i] = img_bytes; img_bytes += (n * 3 + 15) & ~15ull; }
+        }
+        CNIIC_HIP_TRY(c, lin_d.alloc(lin_bytes));
+        if (img_bytes) CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
+        uint64_t at = 0;
+        for (size_t i = 0; i < S; i++) { bf[i].lin_d = lin_d.as<uint8_t>() + at; at += (bf[i].n * 3 + 15) & ~15ull; }
+        RleBatchScratch keep;
+        ScopedKernelTimer timer(c, "rle_dec_batch");
+        CNIIC_TRY(rle_expand_batch_dev(c, bf, &keep));
+        for (size_t i = 0; i < S; i++) {   // follow the traversal (hilbertc.rs:58-61)
+            const uint32_t f = route[i0 + i];
+            uint8_t *dst = img_at[i] != ~0ull ? img_d.as<uint8_t>() + img_at[i] : rgb + (uint64_t)f * img_stride;
+            CNIIC_TRY(hilbert_scatter(c, bf[i].lin_d, w[f], h[f], dst));
+        }
+        timer.stop(S);
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            if (img_at[i] != ~0ull)
+                CNIIC_HIP_TRY(c, hipMemcpyAsync(rgb + (uint64_t)f * img_stride, img_d.as<uint8_t>() + img_at[i], bf[i].n * 3, hipMemcpyDeviceToHost, c->stream));
+        }
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        rle_expand_batch_status(bf, &keep);
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            taken[f] = 1;
+            if (bf[i].status) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "hilbert-rle: bad run record (assert!(count > 0) / unwrap, hilbertc.rs:327-328)"; }
+        }
+        i0 = i1;
+    }
+    return CNIIC_OK;
+}
+
 // ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
 // The heads of all frames come to the host together (one strided copy for streams in HBM), every decoder is parsed there (up to 16
-// threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev).  Whatever this route does
+// threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev); `hilbert(rle)` frames have
+// no decoder to parse and go to rle_decode_batch_route with their dimensions.  Whatever this route does
 // not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more than 32
 // bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
 constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
-constexpr size_t kBatchRouteFrames = 4096;          // frames per set of launches
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
                              uint64_t img_stride, uint32_t *w, uint32_t *h, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
                              std::vector<std::string> &msgs) {
     taken.assign(F, 0);
     rcs.assign(F, CNIIC_OK);
     msgs.assign(F, std::string());
-    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS)) return CNIIC_OK;
+    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE)) return CNIIC_OK;
     const bool bytes_dev = is_device_ptr(bytes), dst_dev = is_device_ptr(rgb);
     std::vector<uint8_t> off_route(F, 0);   // tests (CNIIC_TEST_DECODE_BATCH_OFF=i,j,..): these frames through the single-stream decode
     if (const char *e = test_env("CNIIC_TEST_DECODE_BATCH_OFF"))
@@ -1265,6 +1415,15 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         for (uint32_t f = f0; f <= f1; f++) { head_p[f] = ph + (uint64_t)(f - f0) * W; head_n[f] = std::min(W, lens[f]); }
         return CNIIC_OK;
     };
+    if (d.kind == CODEC_HILBERT_RLE) {   // the records follow the dimensions: the host reads those 8 bytes and nothing else
+        if (bytes_dev) {
+            if (stride >= 8 || F == 1) CNIIC_TRY(fetch(8, 0, F - 1));
+            else for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes; head_n[f] = 0; }   // (headers that overlap: every frame to the single decode)
+        } else {
+            for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
+        }
+        return rle_decode_batch_route(c, bytes, bytes_dev, stride, lens, F, rgb, dst_dev, img_stride, w, h, head_p, head_n, off_route, taken, rcs, msgs);
+    }
     if (bytes_dev) {
         uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
         for (uint32_t f = 0; f < F; f++) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));

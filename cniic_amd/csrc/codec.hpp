@@ -12,10 +12,12 @@ enum CodecKind { CODEC_HUFMAN = 1, CODEC_CLUSTER_COLORS = 2, CODEC_VORONOI = 3, 
 struct CodecDesc {
     int      kind;
     uint32_t arg;  // K for cluster-colors / voronoi
+    double   darg; // d of hilbert(rle(d)); 0 for `hilbert(rle)` (and for d == 0.0 or -0.0, which is the same codec) and every other kind
 };
 
 bool        parse_codec(const char *expr, CodecDesc *out);  // AnyCodec::from_str (codec.rs:41-59)
 std::string codec_name(const CodecDesc &d);                 // Codec::name
+std::string rust_f64_display(double d);                     // format!("{}", d) of an f64, as Codec::name of hilbert(rle(d)) prints it
 bool        codec_is_lossless(const CodecDesc &d);          // Codec::is_lossless
 
 // rgb_d is device memory; out / rgb_out may be host or device.
@@ -27,7 +29,7 @@ int encode_hilbert_rle(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint3
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h);
 
-// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` frames of a batch decoded together (stream f at bytes + f *
+// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames of a batch decoded together (stream f at bytes + f *
 // stride, lens[f] bytes; image f to rgb + f * img_stride).  taken[f] = 1: frame f was decoded here (rcs[f], msgs[f], w[f], h[f]); 0: the
 // caller decodes it on its own (codec_decode).
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,

@@ -674,6 +674,16 @@ struct RlePlan { uint64_t n = 0, nruns = 0; uint32_t nchunks = 0; DevBuf flags, 
 int rle_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, RlePlan *plan);                       // counts the runs (syncs)
 int rle_emit(Ctx *c, const uint8_t *lin_d, const RlePlan *plan, uint32_t *out_words_d);      // 12-byte records
 int rle_expand_dev(Ctx *c, const uint8_t *rec_d, uint64_t R, uint64_t tail_bytes, uint64_t n, uint8_t *lin_d, int *status);  // RleDecoder
+// ... of many streams in one set of launches (cniic_codec_decode_batch): enqueued, not waited for; the statuses after the caller's wait
+struct RleBatchFrame {
+    const uint8_t *rec_d = nullptr;   // the complete records in HBM, any alignment
+    uint64_t R = 0, tail_bytes = 0, n = 0;   // 0 < n < 2^32
+    uint8_t *lin_d = nullptr;         // n colours in scan order (16-byte aligned)
+    int status = 0;                   // 0 ok, 1 bad, as rle_expand_dev's (a bad frame's colours are zeros)
+};
+struct RleBatchScratch { DevBuf buf; std::vector<uint8_t> table, verdicts; };   // kept by the caller until it has waited for the stream
+int rle_expand_batch_dev(Ctx *c, std::vector<RleBatchFrame> &frames, RleBatchScratch *keep);
+void rle_expand_batch_status(std::vector<RleBatchFrame> &frames, const RleBatchScratch *keep);
 int rle_offsets(Ctx *c, const uint32_t *chunk_runs_d, uint32_t nchunks, uint64_t *run_off_d, uint64_t *total_d);  // runs before each chunk
 // ---- k_rle_approx.hip: run-length coding with the running-average test, d != 0 (hilbertc.rs:200-299); same plan, same records ----
 double rla_threshold(double d);                                                                // largest s with sqrt_rn(s) <= d

@@ -265,20 +265,32 @@ int rle_emit(Ctx *c, const uint8_t *lin_d, const RlePlan *plan, uint32_t *out_wo
 //                     to 4097 records that cover the stretch into LDS (start relative to the stretch, colour), every thread its 16
 //                     consecutive colours: one search in LDS, then a walk; 48 bytes out as three 16-byte stores.
 constexpr uint32_t kRdBlock = 1024, kRdStretch = 4096, kRdThreads = 256, kRdPer = kRdStretch / kRdThreads;
-__global__ __launch_bounds__(kRdBlock) void k_rle_dec_counts(const uint32_t *__restrict__ recw, uint64_t R, uint32_t *__restrict__ offl, uint32_t *__restrict__ blocksum,
-                                                             unsigned long long *__restrict__ first_bad) {
-    __shared__ uint32_t wsum[kRdBlock / 64];
-    const uint64_t r = (uint64_t)blockIdx.x * kRdBlock + threadIdx.x;
+// word i of the records at rec: where they lie when that is 4-byte aligned (al), else put together from bytes (the frames of a batch
+// start wherever stride and header leave them)
+__device__ __forceinline__ uint32_t rd_word(const uint8_t *__restrict__ rec, uint64_t i, bool al) {
+    if (al) return reinterpret_cast<const uint32_t *>(rec)[i];
+    const uint8_t *p = rec + 4 * i;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+// block `blk` of a stream's records: offl / first_bad are the stream's own, *blocksum this block's
+__device__ __forceinline__ void rd_counts_block(const uint8_t *__restrict__ rec, bool al, uint64_t R, uint32_t blk, uint32_t *__restrict__ offl,
+                                                uint32_t *__restrict__ blocksum, unsigned long long *__restrict__ first_bad, uint32_t *wsum) {
+    const uint64_t r = (uint64_t)blk * kRdBlock + threadIdx.x;
     uint32_t cnt = 0;
     if (r < R) {
-        const uint32_t w0 = recw[3 * r], w1 = recw[3 * r + 1], w2 = recw[3 * r + 2];
+        const uint32_t w0 = rd_word(rec, 3 * r, al), w1 = rd_word(rec, 3 * r + 1, al), w2 = rd_word(rec, 3 * r + 2, al);
         cnt = w0 & 255u;
         // count > 0 (assert!, hilbertc.rs:327); the colour's length is the u64 3 (unwrap, :328): bytes 1..8 = 3, 0, 0, 0, 0, 0, 0, 0
         if (cnt == 0 || (w0 >> 8) != 3u || w1 != 0u || (w2 & 255u) != 0u) atomicMin(first_bad, (unsigned long long)r);
     }
     const uint32_t ex = block_exclusive_scan<kRdBlock>(cnt, wsum);
     if (r < R) offl[r] = ex;
-    if (threadIdx.x == kRdBlock - 1) blocksum[blockIdx.x] = ex + cnt;
+    if (threadIdx.x == kRdBlock - 1) *blocksum = ex + cnt;
+}
+__global__ __launch_bounds__(kRdBlock) void k_rle_dec_counts(const uint32_t *__restrict__ recw, uint64_t R, uint32_t *__restrict__ offl, uint32_t *__restrict__ blocksum,
+                                                             unsigned long long *__restrict__ first_bad) {
+    __shared__ uint32_t wsum[kRdBlock / 64];
+    rd_counts_block(reinterpret_cast<const uint8_t *>(recw), true, R, blockIdx.x, offl, blocksum + blockIdx.x, first_bad, wsum);
 }
 __global__ void k_rle_dec_verdict(const unsigned long long *__restrict__ first_bad, const uint32_t *__restrict__ offl, const uint64_t *__restrict__ blockoff, uint64_t R,
                                   uint64_t n, const uint64_t *__restrict__ total, uint64_t *__restrict__ out /* [0] total, [1] bad */) {
@@ -286,29 +298,30 @@ __global__ void k_rle_dec_verdict(const unsigned long long *__restrict__ first_b
     out[0] = *total;
     out[1] = (fb < R && blockoff[fb / kRdBlock] + offl[fb] < n) ? 1u : 0u;   // a bad record is an error only if the decoder gets to read it
 }
-__global__ __launch_bounds__(kRdThreads) void k_rle_dec_expand(const uint32_t *__restrict__ recw, uint64_t R, const uint32_t *__restrict__ offl,
-                                                               const uint64_t *__restrict__ blockoff, uint32_t nb, uint64_t total, uint64_t n, uint8_t *__restrict__ lin) {
-    __shared__ uint32_t s_rel[kRdStretch + 2], s_col[kRdStretch + 2];
-    __shared__ unsigned long long s_r0;
-    const uint64_t c0 = (uint64_t)blockIdx.x * kRdStretch;
+// stretch `st` (4096 colours) of a stream.  blockoff[b] - g0: the first colour index of the stream's block b of records (g0: a batch
+// scans the blocks of all its frames in one go, and the frame's own sums start at its first block's)
+__device__ __forceinline__ void rd_expand_stretch(const uint8_t *__restrict__ rec, bool al, uint64_t R, const uint32_t *__restrict__ offl,
+                                                  const uint64_t *__restrict__ blockoff, uint64_t g0, uint32_t nb, uint64_t total, uint64_t n, uint8_t *__restrict__ lin,
+                                                  uint32_t st, uint32_t *s_rel, uint32_t *s_col, unsigned long long *s_r0) {
+    const uint64_t c0 = (uint64_t)st * kRdStretch;
     if (threadIdx.x == 0 && c0 < total) {
         uint32_t a = 0, b = nb;   // last block whose first colour index is <= c0 (block 0's is 0)
-        while (b - a > 1) { const uint32_t m = a + (b - a) / 2; if (blockoff[m] <= c0) a = m; else b = m; }
-        const uint64_t base = blockoff[a], rb = (uint64_t)a * kRdBlock;
+        while (b - a > 1) { const uint32_t m = a + (b - a) / 2; if (blockoff[m] - g0 <= c0) a = m; else b = m; }
+        const uint64_t base = blockoff[a] - g0, rb = (uint64_t)a * kRdBlock;
         uint32_t lo = 0, hi = (uint32_t)min<uint64_t>(kRdBlock, R - rb);   // ... and the last record in it that starts at or before c0
         while (hi - lo > 1) { const uint32_t m = lo + (hi - lo) / 2; if (base + offl[rb + m] <= c0) lo = m; else hi = m; }
-        s_r0 = rb + lo;
+        *s_r0 = rb + lo;
     }
     __syncthreads();
     if (c0 < total) {
-        const uint64_t r0 = s_r0;
+        const uint64_t r0 = *s_r0;
         for (uint32_t k = threadIdx.x; k < kRdStretch + 2; k += kRdThreads) {
             const uint64_t r = r0 + k;
             uint32_t rel = kRdStretch, col = 0;
             if (r < R) {
-                const uint64_t at = blockoff[r / kRdBlock] + offl[r];
+                const uint64_t at = blockoff[r / kRdBlock] - g0 + offl[r];
                 rel = at <= c0 ? 0u : (uint32_t)min<uint64_t>(at - c0, kRdStretch);
-                col = recw[3 * r + 2] >> 8;   // r | g << 8 | b << 16
+                col = rd_word(rec, 3 * r + 2, al) >> 8;   // r | g << 8 | b << 16
             }
             s_rel[k] = rel; s_col[k] = col;
         }
@@ -354,6 +367,12 @@ __global__ __launch_bounds__(kRdThreads) void k_rle_dec_expand(const uint32_t *_
         for (uint32_t j = 0; j < kRdPer && c0 + p0 + j < n; j++) { o[3 * j] = (uint8_t)px[j]; o[3 * j + 1] = (uint8_t)(px[j] >> 8); o[3 * j + 2] = (uint8_t)(px[j] >> 16); }
     }
 }
+__global__ __launch_bounds__(kRdThreads) void k_rle_dec_expand(const uint32_t *__restrict__ recw, uint64_t R, const uint32_t *__restrict__ offl,
+                                                               const uint64_t *__restrict__ blockoff, uint32_t nb, uint64_t total, uint64_t n, uint8_t *__restrict__ lin) {
+    __shared__ uint32_t s_rel[kRdStretch + 2], s_col[kRdStretch + 2];
+    __shared__ unsigned long long s_r0;
+    rd_expand_stretch(reinterpret_cast<const uint8_t *>(recw), true, R, offl, blockoff, 0, nb, total, n, lin, blockIdx.x, s_rel, s_col, &s_r0);
+}
 
 // rec_d: R complete records on the device, 4-byte aligned -> lin_d: n colours in scan order.  *status: 0 ok, 1 a record that is read is
 // bad or (tail_bytes != 0 and the complete records do not reach n colours: the next record is cut)
@@ -392,6 +411,121 @@ int rle_expand_dev(Ctx *c, const uint8_t *rec_d, uint64_t R, uint64_t tail_bytes
     CNIIC_HIP_TRY(c, hipGetLastError());
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return CNIIC_OK;
+}
+
+// ---------------------------------------------------------------- the same for the frames of a batch in one set of launches
+// (cniic_codec_decode_batch).  A frame table in HBM says where every frame's records lie and where its colours go; the blocks of a
+// launch are dealt to the frames by two prefix lists (first[f] = the blocks of the frames before f; a block never spans two frames):
+// one search per block, then 64-bit offsets.
+//   k_rle_decb_counts   k_rle_dec_counts' block for every 1024 records of every frame
+//   pack_scan           over the block totals of ALL frames: a frame's own sums are those minus the sum at its first block
+//   k_rle_decb_verdict  a thread per frame: colours in its complete records; bad iff a record that would be read is malformed or has
+//                       count 0, or the tail is cut before n colours are out (rle_expand_dev's rules)
+//   k_rle_decb_expand   k_rle_dec_expand's block for every 4096 colours of every frame (zeros for a bad frame)
+struct RdbFrame {
+    const uint8_t *rec;    // the complete records (any alignment)
+    uint8_t *lin;          // n colours in scan order
+    uint64_t R, n, offl0;  // complete records; pixels; where the frame's part of offl starts
+    uint32_t tail, cb0, nb, pad;   // bytes behind the last complete record; the frame's first block of records, and how many it has
+};
+struct RdbVerdict { uint64_t total; uint32_t bad, pad; };
+
+// the frame block b belongs to: the last f with first[f] <= b (first[F] = all blocks > b; frames without blocks repeat their successor's value)
+__device__ __forceinline__ uint32_t rdb_frame_of(const uint32_t *__restrict__ first, uint32_t F, uint32_t b) {
+    uint32_t lo = 0, hi = F;
+    while (hi - lo > 1) { const uint32_t m = lo + (hi - lo) / 2; if (first[m] <= b) lo = m; else hi = m; }
+    return lo;
+}
+__global__ __launch_bounds__(kRdBlock) void k_rle_decb_counts(const RdbFrame *__restrict__ fr, const uint32_t *__restrict__ cfirst, uint32_t F, uint32_t *__restrict__ offl,
+                                                              uint32_t *__restrict__ blocksum, unsigned long long *__restrict__ first_bad) {
+    __shared__ uint32_t wsum[kRdBlock / 64];
+    __shared__ uint32_t s_f;
+    if (threadIdx.x == 0) s_f = rdb_frame_of(cfirst, F, blockIdx.x);
+    __syncthreads();
+    const uint32_t f = s_f;
+    const RdbFrame q = fr[f];
+    rd_counts_block(q.rec, (reinterpret_cast<uintptr_t>(q.rec) & 3) == 0, q.R, blockIdx.x - q.cb0, offl + q.offl0, blocksum + blockIdx.x, first_bad + f, wsum);
+}
+__global__ __launch_bounds__(256) void k_rle_decb_verdict(const RdbFrame *__restrict__ fr, uint32_t F, const unsigned long long *__restrict__ first_bad,
+                                                          const uint32_t *__restrict__ offl, const uint64_t *__restrict__ gsum, RdbVerdict *__restrict__ out) {
+    const uint32_t f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    const RdbFrame q = fr[f];
+    const uint64_t g0 = gsum[q.cb0], total = gsum[q.cb0 + q.nb] - g0;
+    const unsigned long long fb = first_bad[f];
+    bool bad = fb < q.R && gsum[q.cb0 + fb / kRdBlock] - g0 + offl[q.offl0 + fb] < q.n;   // a bad record is an error only if the decoder gets to read it
+    if (total < q.n && q.tail) bad = true;                                                 // the decoder starts one more record and runs out of bytes
+    out[f].total = bad ? 0 : total;
+    out[f].bad = bad ? 1u : 0u;
+    out[f].pad = 0;
+}
+__global__ __launch_bounds__(kRdThreads) void k_rle_decb_expand(const RdbFrame *__restrict__ fr, const uint32_t *__restrict__ efirst, uint32_t F,
+                                                                const uint32_t *__restrict__ offl, const uint64_t *__restrict__ gsum, const RdbVerdict *__restrict__ verdict) {
+    __shared__ uint32_t s_rel[kRdStretch + 2], s_col[kRdStretch + 2];
+    __shared__ unsigned long long s_r0;
+    __shared__ uint32_t s_f;
+    if (threadIdx.x == 0) s_f = rdb_frame_of(efirst, F, blockIdx.x);
+    __syncthreads();
+    const uint32_t f = s_f;
+    const RdbFrame q = fr[f];
+    rd_expand_stretch(q.rec, (reinterpret_cast<uintptr_t>(q.rec) & 3) == 0, q.R, offl + q.offl0, gsum + q.cb0, gsum[q.cb0], q.nb, verdict[f].total, q.n, q.lin,
+                      blockIdx.x - efirst[f], s_rel, s_col, &s_r0);
+}
+
+// frames[i]: rec_d (complete records, device memory, any alignment), R, tail_bytes, n (0 < n < 2^32) and lin_d (16-byte aligned) in;
+// status out as rle_expand_dev's -- known once the caller has waited for the stream: everything here is enqueued, nothing waited for.
+// The caller keeps `keep` until then.
+int rle_expand_batch_dev(Ctx *c, std::vector<RleBatchFrame> &frames, RleBatchScratch *keep) {
+    const uint32_t F = (uint32_t)frames.size();
+    if (!F) return CNIIC_OK;
+    std::vector<RdbFrame> fr(F);
+    std::vector<uint32_t> first(2 * ((size_t)F + 1));   // cfirst | efirst
+    uint32_t *cfirst = first.data(), *efirst = first.data() + F + 1;
+    uint64_t cb = 0, eb = 0, nrec = 0;
+    for (uint32_t f = 0; f < F; f++) {
+        const RleBatchFrame &in = frames[f];
+        const uint64_t nb = ceil_div(in.R, (uint64_t)kRdBlock);
+        fr[f] = RdbFrame{in.rec_d, in.lin_d, in.R, in.n, nrec, (uint32_t)in.tail_bytes, (uint32_t)cb, (uint32_t)nb, 0u};
+        cfirst[f] = (uint32_t)cb; efirst[f] = (uint32_t)eb;
+        cb += nb; eb += ceil_div(in.n, (uint64_t)kRdStretch); nrec += in.R;
+        if (cb > 0x7fffffffull || eb > 0x7fffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "hilbert-rle: too many records or pixels in one set of frames");
+    }
+    cfirst[F] = (uint32_t)cb; efirst[F] = (uint32_t)eb;
+    // one block of scratch: first bad record per frame | verdicts | block sums (scanned, + the total) | frame table | prefix lists | block totals | offl
+    const uint64_t o_bad = 0, o_ver = o_bad + 8ull * F, o_g = o_ver + sizeof(RdbVerdict) * (uint64_t)F, o_fr = o_g + 8 * (cb + 1),
+                   o_first = o_fr + sizeof(RdbFrame) * (uint64_t)F, o_bs = o_first + 4ull * first.size(), o_offl = (o_bs + 4 * std::max<uint64_t>(cb, 1) + 15) & ~15ull;
+    CNIIC_HIP_TRY(c, keep->buf.alloc(o_offl + 4 * std::max<uint64_t>(nrec, 1)));
+    uint8_t *p = keep->buf.as<uint8_t>();
+    keep->table.resize(sizeof(RdbFrame) * (size_t)F + 4 * first.size());   // (pageable host memory: it must outlive the copy)
+    memcpy(keep->table.data(), fr.data(), sizeof(RdbFrame) * (size_t)F);
+    memcpy(keep->table.data() + sizeof(RdbFrame) * (size_t)F, first.data(), 4 * first.size());
+    CNIIC_HIP_TRY(c, hipMemsetAsync(p + o_bad, 0xff, 8ull * F, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(p + o_fr, keep->table.data(), keep->table.size(), hipMemcpyHostToDevice, c->stream));
+    const RdbFrame *fr_d = reinterpret_cast<const RdbFrame *>(p + o_fr);
+    const uint32_t *cfirst_d = reinterpret_cast<const uint32_t *>(p + o_first), *efirst_d = cfirst_d + F + 1;
+    unsigned long long *bad_d = reinterpret_cast<unsigned long long *>(p + o_bad);
+    uint64_t *g_d = reinterpret_cast<uint64_t *>(p + o_g);
+    uint32_t *bs_d = reinterpret_cast<uint32_t *>(p + o_bs), *offl_d = reinterpret_cast<uint32_t *>(p + o_offl);
+    RdbVerdict *ver_d = reinterpret_cast<RdbVerdict *>(p + o_ver);
+    if (cb) {
+        hipLaunchKernelGGL(k_rle_decb_counts, dim3((uint32_t)cb), dim3(kRdBlock), 0, c->stream, fr_d, cfirst_d, F, offl_d, bs_d, bad_d);
+        CNIIC_TRY(pack_scan(c, bs_d, (uint32_t)cb, g_d, g_d + cb));
+    } else {
+        CNIIC_HIP_TRY(c, hipMemsetAsync(g_d, 0, 8, c->stream));
+    }
+    hipLaunchKernelGGL(k_rle_decb_verdict, dim3((F + 255) / 256), dim3(256), 0, c->stream, fr_d, F, (const unsigned long long *)bad_d, (const uint32_t *)offl_d,
+                       (const uint64_t *)g_d, ver_d);
+    hipLaunchKernelGGL(k_rle_decb_expand, dim3((uint32_t)eb), dim3(kRdThreads), 0, c->stream, fr_d, efirst_d, F, (const uint32_t *)offl_d, (const uint64_t *)g_d,
+                       (const RdbVerdict *)ver_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    keep->verdicts.resize((size_t)F * sizeof(RdbVerdict));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(keep->verdicts.data(), ver_d, keep->verdicts.size(), hipMemcpyDeviceToHost, c->stream));
+    return CNIIC_OK;
+}
+// after the caller's wait for the stream
+void rle_expand_batch_status(std::vector<RleBatchFrame> &frames, const RleBatchScratch *keep) {
+    const RdbVerdict *v = reinterpret_cast<const RdbVerdict *>(keep->verdicts.data());
+    for (size_t f = 0; f < frames.size(); f++) frames[f].status = v[f].bad ? 1 : 0;
 }
 
 }  // namespace cniic

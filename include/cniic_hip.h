@@ -362,9 +362,16 @@ int32_t cniic_huf_size(int32_t sym_kind, const uint64_t *counts, uint64_t n, uin
 
 /* ------------------------------------------------------------------ Codec trait (src/codec.rs:14-19) */
 /* expr is the reference's --codec= expression: "hufman", "cluster-colors(256)" / "ccol(256)",
- * "voronoi(2048)", "delta", "hilbert(rle)" = "hilbert(rle(0))" (src/codec.rs:41-59, FromStr impls of each
- * codec; hilbertc.rs:341-397 for the last one, whose name() is "hilbert-rle"; rle(d != 0) has its own entry point, cniic_hilbert_rle_approx_encode; zip is not built). */
+ * "voronoi(2048)", "delta", "hilbert(rle)" = "hilbert(rle(0))", "hilbert(rle(4))" (src/codec.rs:41-59, FromStr impls of each
+ * codec; hilbertc.rs:341-397 for the last two: rle(<f64>) takes what Rust's f64::from_str takes -- "4", "+4", "4.", ".5", "1e-3",
+ * "inf", "-infinity", "nan" -- and its name() is "hilbert-rle" for d == 0, else "hilbert-rle-approx_" + d as Rust's Display prints
+ * it, which can be longer than 300 characters; zip is not built).  Every entry point below that takes an expression takes all of
+ * them.
+ * cniic_codec_parse describes a codec as (kind, u32 argument), which cannot carry the f64: it answers CNIIC_ERR_BAD_ARG for
+ * hilbert(rle(d)) with d != 0.  cniic_codec_parse_f64 takes every expression; darg is d (0 for d == 0.0 and -0.0, for `hilbert(rle)`
+ * and for the other codecs).  Any out-parameter may be NULL. */
 int32_t cniic_codec_parse(const char *expr, int32_t *kind, uint32_t *arg);
+int32_t cniic_codec_parse_f64(const char *expr, int32_t *kind, uint32_t *arg, double *darg);
 int32_t cniic_codec_name(const char *expr, char *buf, uint64_t cap);   /* Codec::name()        */
 int32_t cniic_codec_is_lossless(const char *expr);                     /* 1 / 0 / negative err */
 /* Codec::encode: appends nothing, writes the whole stream to out[0..*len). */
@@ -402,10 +409,9 @@ int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cni
                                      int32_t *rcs, cniic_kmeans_stats *stats);
 /* Hilbert { compress: RLE(d) }::encode (hilbertc.rs:26-45; rle_approx :200-299): runs along the Hilbert scan that a pixel joins while its
  * distance to the run's running average is <= d, recorded with the rounded average.  d == 0.0 (or -0.0) gives the `hilbert(rle)`
- * stream; d < 0 or NaN accepts nothing, +inf everything.  cniic_codec_parse does not take `hilbert(rle(d))` for d != 0 (its u32
- * argument cannot carry the f64): this is that codec's encode.  Host or device buffers; CNIIC_ERR_CAPACITY with *len = bytes needed,
- * like cniic_codec_encode.  The stream decodes with cniic_codec_decode(ctx, "hilbert(rle)", ...): the records are the same
- * (RleDecoder, hilbertc.rs:304-335). */
+ * stream; d < 0 or NaN accepts nothing, +inf everything.  The same bytes as cniic_codec_encode(ctx, "hilbert(rle(<d>))", ...), for
+ * a caller that holds d as a double.  Host or device buffers; CNIIC_ERR_CAPACITY with *len = bytes needed, like cniic_codec_encode.
+ * The stream decodes with "hilbert(rle)" or "hilbert(rle(<any d>))": the records are the same (RleDecoder, hilbertc.rs:304-335). */
 int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *ctx, double d, const uint8_t *rgb, uint32_t w, uint32_t h,
                                         uint8_t *out, uint64_t cap, uint64_t *len);
 /* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics. */
@@ -413,8 +419,10 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
                            uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
 /* Codec::decode of `frames` streams: stream f at bytes + f * stride, lens[f] bytes (exactly what cniic_codec_encode_batch writes).
  * Image f goes to rgb + f * img_stride (capacity img_stride bytes); its dimensions go to w[f], h[f].  Host or device memory on either
- * side.  Streams of one batch may carry different dimensions.  `hufman` and `cluster-colors` frames are decoded together in one set of
- * launches; other codecs, and the frames that route does not take, are decoded one by one on the worker contexts of
+ * side.  Streams of one batch may carry different dimensions.  `hufman` and `cluster-colors` frames, and `hilbert(rle)` /
+ * `hilbert(rle(d))` frames of up to 2^18 pixels (larger ones measured no faster that way), are decoded together in one set of launches
+ * (stage timers: "rle_dec_batch" for the last, launches = the frames decoded that way; a frame that fails there may leave zeros in
+ * its own w * h * 3 bytes); other codecs, and the frames that route does not take, are decoded one by one on the worker contexts of
  * cniic_codec_encode_batch (CNIIC_OPT_BATCH_STREAMS at a time).  rcs (may be NULL): per-frame status, identical to what
  * cniic_codec_decode returns for that stream alone.  The call returns the first failure; cniic_last_error carries that frame's
  * message.  frames == 0 returns CNIIC_OK. */

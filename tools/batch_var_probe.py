@@ -4,8 +4,15 @@
   cniic_mse_batch_var            against a loop of cniic_mse, and its bytes per second against cniic_mse of ONE pair of the same total size
   cniic_codec_measure_batch      against the loop of cniic_codec_encode, cniic_codec_decode and cniic_mse
 One JSON line per case (median / min / max of --reps timed runs after --warmup untimed ones); --out FILE also writes them there.
-    python tools/batch_var_probe.py [--out profiles/batch_var_probe.json] [--reps 5] [--warmup 1] [--only mse|encode]
---only: one batched call and nothing else (for a profiler run of its own)."""
+    python tools/batch_var_probe.py [--out profiles/batch_var_probe.json] [--reps 5] [--warmup 1] [--only mse|encode|rle-decode]
+--only: one batched call and nothing else (for a profiler run of its own).
+
+  --hilbert [--against OTHER.so]   the Hilbert-RLE rules of the reference's Makefile on the same 100 images: cniic_codec_decode_batch of
+                                 `hilbert(rle)`, `hilbert(rle(4))` and `hilbert(rle(16))` streams (the approximate ones written by
+                                 cniic_hilbert_rle_approx_encode, decoded as `hilbert(rle)`: every build of the library takes that) and
+                                 cniic_codec_measure_batch where the library takes the expression.  --against names another build of the
+                                 library in cniic_amd/ (CNIIC_LIB_FILE): the two are then timed in child processes in alternation, --rounds
+                                 times --reps runs each, and the medians compared."""
 import argparse
 import ctypes as C
 import json
@@ -15,6 +22,8 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if "--lib-file" in sys.argv:   # (before the package loads the library)
+    os.environ["CNIIC_LIB_FILE"] = sys.argv[sys.argv.index("--lib-file") + 1]
 import torch
 
 import cniic_amd
@@ -58,13 +67,140 @@ def mse1(ctx, a, b, npx):
     return v.value
 
 
+HILBERT_D = (0.0, 4.0, 16.0)
+SWEEP = ((64, 64, 256), (256, 256, 256), (512, 384, 256), (800, 600, 128), (1024, 1000, 100), (1024, 1024, 100), (1200, 900, 100), (2040, 1356, 100))
+
+
+def hilbert_times(a):
+    """this library's raw times (ms) per case, as one JSON line"""
+    dev = torch.device("cuda", 0)
+    out = {}
+    if a.sweep:   # frames of ONE size per batch, d = 4 only: where the batched decode stops paying
+        for w, h, F in SWEEP:
+            hilbert_case(a, dev, "%dx%d x%d " % (w, h, F), [(w, h)] * F, (4.0,), out)
+    else:
+        hilbert_case(a, dev, "", div2k_like_sizes(), HILBERT_D, out)
+    print("HILBERT " + json.dumps(out), flush=True)
+
+
+def hilbert_case(a, dev, tag, sizes, ds, out):
+    F = len(sizes)
+    ws, hs = [w for w, _ in sizes], [h for _, h in sizes]
+    nbytes = [3 * w * h for w, h in sizes]
+    offs = [sum(nbytes[:f]) for f in range(F)]
+    with cniic_amd.Context(0) as ctx:
+        src = torch.empty(offs[-1] + nbytes[-1] + 16, dtype=torch.uint8, device=dev)
+        for f, (w, h) in enumerate(sizes):
+            ctx.synth_image(_lib.SYNTH_PHOTO, synth.SEED0 + 6000 + f, w, h, src[offs[f]:])
+        img_stride = max(nbytes)
+        back = torch.zeros(img_stride * F, dtype=torch.uint8, device=dev)
+        for d in ds:
+            name = "hilbert(rle)" if d == 0.0 else "hilbert(rle(%g))" % d
+            lens, streams = [], []
+            for f in range(F):
+                one = torch.empty(8 + 4 * nbytes[f], dtype=torch.uint8, device=dev)
+                rc, n = ctx.hilbert_rle_approx_encode(d, src[offs[f]:], ws[f], hs[f], out=one)
+                lens.append(n); streams.append(one[:n])
+            stride = (max(lens) + 3) & ~3
+            enc = torch.zeros(stride * F, dtype=torch.uint8, device=dev)
+            for f in range(F):
+                enc[f * stride:f * stride + lens[f]] = streams[f]
+            del streams
+            torch.cuda.synchronize()
+            res = {}
+
+            def decode():
+                res["d"] = ctx.decode_batch("hilbert(rle)", enc, stride, lens, F, back, img_stride)
+            if a.only == "rle-decode":   # (with --sweep: the batches of small frames, which take the batched route)
+                decode()
+                continue
+            out[tag + "decode_batch " + name] = raw_times(decode, a.reps, a.warmup)
+            assert res["d"][0] == 0
+            if a.sweep:
+                continue
+            if d == 0.0 or hasattr(_lib.lib(), "cniic_codec_parse_f64"):   # (a build from before hilbert(rle(d)) was an expression measures the exact codec only)
+                def measure():
+                    res["m"] = ctx.measure_batch(name, src, offs, ws, hs)
+                out["measure_batch " + name] = raw_times(measure, a.reps, a.warmup)
+                assert res["m"][0] == 0 and [r["compressed_size"] for r in res["m"][1]] == lens
+            ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
+            decode()
+            out["rle_dec_batch frames " + name] = ctx.kernel_time("rle_dec_batch")[1]
+            ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
+            del enc
+
+
+def raw_times(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(round((time.perf_counter() - t) * 1e3, 3))
+    return ts
+
+
+def stats(ts):
+    return dict(median_ms=round(statistics.median(ts), 3), min_ms=round(min(ts), 3), max_ms=round(max(ts), 3), runs=len(ts))
+
+
+def hilbert_ab(a):
+    """children in alternation: this library, the other, this, the other, ..."""
+    import subprocess
+    got = {"this": {}, "other": {}}
+    libs = [("this", None)] + ([("other", a.against)] if a.against else [])
+    for _ in range(a.rounds):
+        for who, lib in libs:
+            cmd = [sys.executable, os.path.abspath(__file__), "--hilbert-child", "--reps", str(a.reps), "--warmup", str(a.warmup)] + (["--sweep"] if a.sweep else [])
+            if lib:
+                cmd += ["--lib-file", lib]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            if r.returncode != 0:
+                raise SystemExit("child failed (%s): %s" % (who, r.stderr[-2000:]))
+            line = [l for l in r.stdout.split("\n") if l.startswith("HILBERT ")][-1]
+            for k, v in json.loads(line[8:]).items():
+                if isinstance(v, list):
+                    got[who].setdefault(k, []).extend(v)
+                else:
+                    got[who][k] = v
+    rows = []
+    for k, v in got["this"].items():
+        if not isinstance(v, list):
+            rows.append(dict(case=k, this=v, other=got["other"].get(k)))
+            continue
+        row = dict(case=k, this=stats(v))
+        if isinstance(got["other"].get(k), list):
+            row["other"] = stats(got["other"][k])
+            sp = (row["this"]["max_ms"] - row["this"]["min_ms"]) + (row["other"]["max_ms"] - row["other"]["min_ms"])
+            row.update(ratio_other_over_this=round(row["other"]["median_ms"] / row["this"]["median_ms"], 3), spreads_ms=round(sp, 3),
+                       faster_by_more_than_the_spreads=bool(row["this"]["median_ms"] + sp < row["other"]["median_ms"]))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", choices=("mse", "encode"))
+    ap.add_argument("--only", choices=("mse", "encode", "rle-decode"))
+    ap.add_argument("--hilbert", action="store_true")
+    ap.add_argument("--hilbert-child", action="store_true")
+    ap.add_argument("--against")
+    ap.add_argument("--lib-file")
+    ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--sweep", action="store_true", help="--hilbert: batches of one frame size each (SWEEP) instead of the 100 images")
     a = ap.parse_args()
+    if a.hilbert:
+        return hilbert_ab(a)
+    if a.hilbert_child or a.only == "rle-decode":
+        return hilbert_times(a)
     dev = torch.device("cuda", 0)
     rows = []
 
