@@ -14,6 +14,7 @@ ERR = {-1: "BAD_ARG", -2: "TOO_FEW_POINTS", -3: "FEW_ACTIVE", -4: "HIP", -5: "RC
        -8: "CAPACITY", -9: "UNSUPPORTED"}
 BAD_ARG, TOO_FEW_POINTS, FEW_ACTIVE, HIP, RCCL, DECODE, NOMEM, CAPACITY, UNSUPPORTED = range(-1, -10, -1)
 SYM_RGB, SYM_SIGNED = 1, 2
+KIND_ZIP_DICT = 6   # cniic_codec_parse's kind of zip(dict)
 SYNTH_UNIFORM, SYNTH_PHOTO = 0, 1
 KM_BRUTE_FORCE, KM_PROFILE, KM_NO_SKIP = 1, 2, 4
 OPT_SP_MIN_PIXELS, OPT_HUF_GPU_CODES_MIN, OPT_GPU_DECODE_MIN, OPT_DELTA_ROUTE, OPT_STAGE_TIMERS, OPT_FRAME_TREES_HOST, OPT_BATCH_STREAMS, OPT_KM_MAX_BLOCKS, OPT_KM_LOOP = range(1, 10)
@@ -35,6 +36,7 @@ SYMBOLS = [
     "cniic_codec_encode_opts", "cniic_codec_encode_batch", "cniic_codec_decode", "cniic_codec_decode_batch", "cniic_mse", "cniic_mse_batch",
     "cniic_hilbert_rle_approx_encode", "cniic_synth_image",
     "cniic_codec_encode_batch_var", "cniic_mse_batch_var", "cniic_codec_measure_batch", "cniic_codec_parse_f64",
+    "cniic_zip_dict_encode", "cniic_zip_dict_decode", "cniic_zip_dict_dims", "cniic_hilbert_zip_encode", "cniic_hilbert_zip_decode",
 ]
 
 
@@ -370,6 +372,80 @@ class Context:
             return rc, (out[:ln.value].tobytes() if rc == OK else b"")
         return rc, ln.value
 
+    # ---- the dictionary coder
+    def zip_dict_encode(self, data, n=None, out=None, allow=()):
+        """cniic_zip_dict_encode: data = bytes / numpy array (host), or a device tensor / address with n given.
+        -> (rc, bytes) when out is None, else (rc, length)"""
+        if isinstance(data, (bytes, bytearray)):
+            data = np.frombuffer(bytes(data), np.uint8)
+        if n is None:
+            n = data.numel() if hasattr(data, "numel") else data.size
+        own = out is None
+        if own:
+            cap = 2 * n + 4
+            out = np.empty(cap, np.uint8)
+        else:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_zip_dict_encode(self.h, _ptr(data) if n else None, C.c_uint64(n), _ptr(out), C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
+
+    def zip_dict_decode(self, data, n=None, out=None, cap=None, allow=()):
+        """cniic_zip_dict_decode -> (rc, bytes) when out is None (cap: the most bytes the text may have, default 64 MiB), else (rc, length;
+        with CAPACITY: the bytes needed)"""
+        if isinstance(data, (bytes, bytearray)):
+            data = np.frombuffer(bytes(data), np.uint8)
+        if n is None:
+            n = data.numel() if hasattr(data, "numel") else data.size
+        own = out is None
+        if own:
+            cap = (64 << 20) if cap is None else cap
+            out = np.empty(max(cap, 1), np.uint8)
+        elif cap is None:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_zip_dict_decode(self.h, _ptr(data) if n else None, C.c_uint64(n), _ptr(out), C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
+
+    def hilbert_zip_encode(self, img, w=None, h=None, out=None, allow=()):
+        """cniic_hilbert_zip_encode.  img: HxWx3 uint8 numpy array, or a device tensor / address with w,h given.
+        -> (rc, bytes) when out is None, else (rc, length)"""
+        if isinstance(img, np.ndarray):
+            img = np.ascontiguousarray(img, np.uint8)
+            h, w = img.shape[:2]
+        own = out is None
+        if own:
+            cap = 8 + w * h * 22 + 4
+            out = np.empty(cap, np.uint8)
+        else:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_hilbert_zip_encode(self.h, _ptr(img), C.c_uint32(w), C.c_uint32(h), _ptr(out), C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
+
+    def hilbert_zip_decode(self, data, allow=()):
+        """cniic_hilbert_zip_decode of a host stream -> (rc, HxWx3 image or None)"""
+        raw = np.frombuffer(bytes(data), np.uint8)
+        if raw.size < 8:
+            return DECODE, None
+        w = int.from_bytes(raw[0:4].tobytes(), "little")
+        h = int.from_bytes(raw[4:8].tobytes(), "little")
+        if w * h > (1 << 28):
+            return CAPACITY, None
+        out = np.zeros((max(w * h, 1), 3), np.uint8)
+        cw, ch = C.c_uint32(0), C.c_uint32(0)
+        rc = self._check(self._L.cniic_hilbert_zip_decode(self.h, _ptr(raw), C.c_uint64(raw.size), _ptr(out), C.c_uint64(out.size), C.byref(cw),
+                                                          C.byref(ch)), allow)
+        if rc != OK:
+            return rc, None
+        return rc, out[:w * h].reshape(h, w, 3)
+
     def encode_batch(self, expr, frames, w, h, F, out, stride, seed=0, max_iters=0, flags=0, allow=()):
         """cniic_codec_encode_batch: F images (one contiguous [F][h][w][3] buffer), each encoded on its own (its own palette), image f's
         stream at out[f * stride:].  -> (rc, list of F lengths, list of F per-image status codes, list of F stats dicts)"""
@@ -425,10 +501,10 @@ class Context:
 
     def decode(self, expr, data, allow=()):
         raw = np.frombuffer(bytes(data), np.uint8)
-        if raw.size < 8:
+        dims = stream_dims(expr, raw)
+        if dims is None:
             return DECODE, None
-        w = int.from_bytes(raw[0:4].tobytes(), "little")
-        h = int.from_bytes(raw[4:8].tobytes(), "little")
+        w, h = dims
         if w * h > (1 << 28):
             return CAPACITY, None
         out = np.zeros((max(w * h, 1), 3), np.uint8)
@@ -485,6 +561,24 @@ class Context:
             out = np.empty((h, w, 3), np.uint8)
         self._check(self._L.cniic_synth_image(self.h, kind, C.c_uint64(seed), C.c_uint32(w), C.c_uint32(h), _ptr(out)))
         return out
+
+
+def zip_dict_dims(data):
+    """cniic_zip_dict_dims: (w, h) from the first pairs of a zip(dict) stream in host memory, or None"""
+    raw = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    rc = lib().cniic_zip_dict_dims(_ptr(raw) if raw.size else None, C.c_uint64(raw.size), C.byref(w), C.byref(h))
+    return (w.value, h.value) if rc == OK else None
+
+
+def stream_dims(expr, data):
+    """(w, h) of a stream of codec `expr` in host memory, or None: its first 8 bytes -- for zip(dict), the first 8 bytes of its text"""
+    p = codec_parse_f64(expr)
+    if p is not None and p[0] == KIND_ZIP_DICT:
+        return zip_dict_dims(data)
+    if len(data) < 8:
+        return None
+    return int.from_bytes(bytes(data[0:4]), "little"), int.from_bytes(bytes(data[4:8]), "little")
 
 
 def codec_parse(expr):

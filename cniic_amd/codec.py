@@ -8,6 +8,8 @@
 
     AnyCodec.from_str("hilbert(rle(4))")   # the lossy running-average RLE is an expression like the others
     HilbertRleApprox(4.0)                   # the same codec for a caller that holds d as a float
+    AnyCodec.from_str("zip(dict)")          # the dictionary coder over the serialised image
+    HilbertZip()                            # Hilbert { compress: Zip }: not an expression here, a class of its own
 """
 import math
 from decimal import Decimal
@@ -54,8 +56,9 @@ class Codec:
             buf[f * stride:f * stride + len(s)] = np.frombuffer(bytes(s), np.uint8)
         npx = 0
         for s in streams:
-            if len(s) >= 8:
-                npx = max(npx, int.from_bytes(bytes(s[0:4]), "little") * int.from_bytes(bytes(s[4:8]), "little"))
+            dims = _lib.stream_dims(self.expr, s)
+            if dims is not None:
+                npx = max(npx, dims[0] * dims[1])
         img_stride = max(min(npx, 1 << 28) * 3, 3)
         out = np.zeros(img_stride * F, np.uint8)
         rc, ws, hs, rcs = self.ctx.decode_batch(self.expr, buf, stride, lens, F, out, img_stride, allow=(_lib.DECODE, _lib.CAPACITY))
@@ -174,3 +177,37 @@ class HilbertRleApprox(Codec):
 
     def is_lossless(self):
         return self.d == 0.0
+
+
+class HilbertZip(Codec):
+    """Hilbert { compress: Zip } (src/codec/hilbertc.rs:27-29,47-49,67-77): the dimensions, then the dictionary coder over the 11-byte
+    records of the pixels in scan order.  `hilbert(zip)` is not an expression of this library: encode and decode go through
+    cniic_hilbert_zip_encode / cniic_hilbert_zip_decode."""
+
+    def __init__(self, ctx=None):
+        self.expr = None
+        self._ctx = ctx
+        self.last_stats = None
+
+    def encode(self, img, **kw):
+        rc, data = self.ctx.hilbert_zip_encode(img, **kw)
+        return data
+
+    def decode(self, data):
+        rc, img = self.ctx.hilbert_zip_decode(data, allow=(_lib.DECODE,))
+        return img if rc == _lib.OK else None
+
+    def decode_batch(self, streams):
+        return [self.decode(s) for s in streams]
+
+    def encode_batch(self, imgs, **kw):
+        return [self.encode(im, **kw) for im in imgs]
+
+    def measure(self, imgs, **kw):
+        raise NotImplementedError("hilbert-zip has no expression: cniic_codec_measure_batch cannot name it")
+
+    def name(self):
+        return "hilbert-zip"      # hilbertc.rs:85
+
+    def is_lossless(self):
+        return True               # :92

@@ -911,6 +911,47 @@ int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *c, double d, const uint8_t *r
     return encode_hilbert_rle(c, d, in.d, w, h, out, cap, len);
 }
 
+// ------------------------------------------------------------------ the dictionary coder (zipdict.cpp, k_zipdict.hip)
+int32_t cniic_zip_dict_encode(cniic_ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!bytes && n) || (!out && n)) return c->fail(CNIIC_ERR_BAD_ARG, "zip_dict_encode: null argument");
+    *len = 0;
+    if (!n) return CNIIC_OK;   // (no input, no pair: dict.rs:69-75)
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, bytes, n));
+    return zip_dict_encode_text(c, in.d, in.d == bytes ? nullptr : bytes, n, {}, out, cap, len);
+}
+
+int32_t cniic_zip_dict_decode(cniic_ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!bytes && n) || (!out && cap)) return c->fail(CNIIC_ERR_BAD_ARG, "zip_dict_decode: null argument");
+    *len = 0;
+    return zip_dict_decode_bytes(c, bytes, n, out, cap, len);
+}
+
+int32_t cniic_zip_dict_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint32_t *h) {
+    if ((!bytes && n) || !w || !h) return CNIIC_ERR_BAD_ARG;
+    return zip_dict_dims(bytes, n, w, h);
+}
+
+int32_t cniic_hilbert_zip_encode(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "hilbert_zip_encode: null argument");
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
+    return encode_hilbert_zip(c, in.d, w, h, out, cap, len);
+}
+
+int32_t cniic_hilbert_zip_decode(cniic_ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!bytes || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "hilbert_zip_decode: null argument");
+    return decode_hilbert_zip(c, bytes, n, rgb, cap, w, h);
+}
+
 int32_t cniic_codec_encode_opts(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w,
                                 uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     LOCK(c);

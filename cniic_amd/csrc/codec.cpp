@@ -8,6 +8,7 @@
 //   Delta           src/codec/hilbertc.rs:404 Hilbert gather -> neighbour delta -> huf::encode_all
 //   Hilbert{RLE(d)} src/codec/hilbertc.rs:12  Hilbert gather -> run-length records: exact for d == 0, else
 //                                             the running average (k_rle_approx.hip): `hilbert(rle)` and `hilbert(rle(<f64>))`
+//   Zip::Dict       src/codec/zipc.rs         `zip(dict)`: the dictionary coder over the serialised image (zipdict.cpp, k_zipdict.hip)
 #include "codec.hpp"
 
 #include <algorithm>
@@ -100,7 +101,7 @@ static bool match_hilbert_rle(const std::string &s, double *d) {
 bool parse_codec(const char *expr, CodecDesc *out) {
     if (!expr) return false;
     const std::string s(expr);
-    // alternatives in the order of gen_all! (codec.rs:120-127); Zip is out of scope
+    // alternatives in the order of gen_all! (codec.rs:120-127); of Zip, zip(dict)
     static const char *const cc[] = {"cluster-colors", "cluster-col", "clustercolors", "clustercol",
                                      "c-colors", "c-col", "ccolors", "ccol", nullptr};  // c(?:luster)?-?col(?:ors)?
     static const char *const vo[] = {"voronoi", nullptr};
@@ -110,6 +111,9 @@ bool parse_codec(const char *expr, CodecDesc *out) {
     if (match_fun_u32(s, vo, &k)) { *out = {CODEC_VORONOI, k, 0.0}; return true; }
     if (s == "delta") { *out = {CODEC_DELTA, 0, 0.0}; return true; }  // prs::expect_name: ^delta$
     if (match_hilbert_rle(s, &dv)) { *out = {CODEC_HILBERT_RLE, 0, dv}; return true; }
+    // Zip::from_str (zipc.rs:62-80): fun_call named ^zip$ with the one argument `dict` (`back` is not built).  hilbert(zip) is reached through
+    // cniic_hilbert_zip_encode / _decode, not through an expression.
+    if (s == "zip(dict)") { *out = {CODEC_ZIP_DICT, 0, 0.0}; return true; }
     if (s.size() == 6) {                                         // hufc.rs:54-59 eq_ignore_ascii_case
         std::string t = s;
         std::transform(t.begin(), t.end(), t.begin(), [](unsigned char ch) { return (char)tolower(ch); });
@@ -149,56 +153,14 @@ std::string codec_name(const CodecDesc &d) {
     case CODEC_VORONOI: return "voronoi_" + std::to_string(d.arg);        // clusterc.rs:191-193
     case CODEC_DELTA: return "delta";                                     // hilbertc.rs:433-435
     case CODEC_HILBERT_RLE: return d.darg == 0.0 ? "hilbert-rle" : "hilbert-rle-approx_" + rust_f64_display(d.darg);  // hilbertc.rs:80-86
+    case CODEC_ZIP_DICT: return "zip-dict";                               // zipc.rs:50-55
     }
     return "";
 }
 
 bool codec_is_lossless(const CodecDesc &d) {   // (hilbertc.rs:88-93: RLE(d) is lossless iff d == 0.0 -- NaN is not)
-    return d.kind == CODEC_HUFMAN || d.kind == CODEC_DELTA || (d.kind == CODEC_HILBERT_RLE && d.darg == 0.0);
+    return d.kind == CODEC_HUFMAN || d.kind == CODEC_DELTA || d.kind == CODEC_ZIP_DICT || (d.kind == CODEC_HILBERT_RLE && d.darg == 0.0);
 }
-
-// ------------------------------------------------------------------ output assembly
-// The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in
-// the caller's buffer when that is 4-byte aligned device memory, otherwise in a staging buffer
-// that is copied out once.
-struct StreamOut {
-    Ctx *c;
-    uint8_t *caller;
-    uint64_t cap;
-    uint64_t *len;
-    bool direct = false;
-    DevBuf staging;
-    uint8_t *dev = nullptr;
-    uint64_t total = 0;
-    StreamOut(Ctx *ctx, uint8_t *out, uint64_t capacity, uint64_t *len_out) : c(ctx), caller(out), cap(capacity), len(len_out) {}
-    int begin(const std::vector<uint8_t> &header, uint64_t payload_bytes) {
-        CNIIC_TRY(begin_sized(header.size(), payload_bytes));
-        return put_header(header);
-    }
-    // the header's bytes may follow the payload (put_header): its size is enough to place the payload
-    int put_header(const std::vector<uint8_t> &header) {
-        if (!header.empty()) CNIIC_HIP_TRY(c, hipMemcpyAsync(dev, header.data(), header.size(), hipMemcpyHostToDevice, c->stream));
-        return CNIIC_OK;
-    }
-    int begin_sized(uint64_t header_bytes, uint64_t payload_bytes, bool zero = true) {
-        total = header_bytes + payload_bytes;
-        *len = total;
-        if (total > cap) return c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu",
-                                        (unsigned long long)total, (unsigned long long)cap);
-        const uint64_t padded = (total + 3) & ~3ull;
-        direct = is_device_ptr(caller) && (reinterpret_cast<uintptr_t>(caller) & 3) == 0 && padded <= cap;
-        if (direct) dev = caller;
-        else { CNIIC_HIP_TRY(c, staging.alloc(padded + 16)); dev = staging.as<uint8_t>(); }
-        if (zero) CNIIC_HIP_TRY(c, hipMemsetAsync(dev, 0, padded, c->stream));
-        return CNIIC_OK;
-    }
-    int finish() {
-        if (!direct && total)
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(caller, dev, total, is_device_ptr(caller) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return CNIIC_OK;
-    }
-};
 
 // F streams at a fixed distance (cc_finish_frames): assembled where the caller wants them when that is 4-byte aligned device memory,
 // otherwise in a staging buffer that is copied out once.
@@ -1043,6 +1005,7 @@ int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, u
     case CODEC_VORONOI: return encode_voronoi(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats);
     case CODEC_DELTA: return encode_delta(c, rgb_d, w, h, out, cap, len);
     case CODEC_HILBERT_RLE: return encode_hilbert_rle(c, d.darg, rgb_d, w, h, out, cap, len);
+    case CODEC_ZIP_DICT: return encode_zip_dict(c, rgb_d, w, h, out, cap, len);
     }
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
@@ -1087,6 +1050,7 @@ static int stream_head(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t nb
 constexpr uint64_t kTrieSecondLook = 512ull << 10;   // bytes of a `delta` stream the host parses before the GPU is asked (~7 10^4 leaves)
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h) {
+    if (d.kind == CODEC_ZIP_DICT) return decode_zip_dict(c, bytes, nbytes, rgb_out, cap, w, h);   // (its dimensions are inside the compressed text)
     const bool bytes_dev = is_device_ptr(bytes);
     StreamHead head;
     // (the serialised decoder of a Huffman stream is at most a few per cent of it, for the images these codecs are meant for)
@@ -1251,6 +1215,7 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
         if (!dst_dev) return put_image(c, dst, true, n * 3, rgb_out);
         return CNIIC_OK;
     }
+    case CODEC_ZIP_DICT: break;   // (taken above)
     case CODEC_VORONOI: {  // clusterc.rs:168-189
         CNIIC_TRY(stream_head(c, bytes, bytes_dev, nbytes, nbytes, &head));  // 16 + 19 K bytes: parsed on the host
         const uint8_t *hb = head.p;

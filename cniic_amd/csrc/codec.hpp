@@ -7,7 +7,7 @@
 
 namespace cniic {
 
-enum CodecKind { CODEC_HUFMAN = 1, CODEC_CLUSTER_COLORS = 2, CODEC_VORONOI = 3, CODEC_DELTA = 4, CODEC_HILBERT_RLE = 5 };
+enum CodecKind { CODEC_HUFMAN = 1, CODEC_CLUSTER_COLORS = 2, CODEC_VORONOI = 3, CODEC_DELTA = 4, CODEC_HILBERT_RLE = 5, CODEC_ZIP_DICT = 6 };
 
 struct CodecDesc {
     int      kind;
@@ -28,6 +28,61 @@ int encode_hilbert_rle(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint3
 // bytes may be host or device memory: of a stream in HBM only the head comes to the host, the payload is decoded where it lies.
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h);
+
+// ---- output assembly
+// The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in
+// the caller's buffer when that is 4-byte aligned device memory, otherwise in a staging buffer
+// that is copied out once.
+struct StreamOut {
+    Ctx *c;
+    uint8_t *caller;
+    uint64_t cap;
+    uint64_t *len;
+    bool direct = false;
+    DevBuf staging;
+    uint8_t *dev = nullptr;
+    uint64_t total = 0;
+    StreamOut(Ctx *ctx, uint8_t *out, uint64_t capacity, uint64_t *len_out) : c(ctx), caller(out), cap(capacity), len(len_out) {}
+    int begin(const std::vector<uint8_t> &header, uint64_t payload_bytes) {
+        CNIIC_TRY(begin_sized(header.size(), payload_bytes));
+        return put_header(header);
+    }
+    // the header's bytes may follow the payload (put_header): its size is enough to place the payload
+    int put_header(const std::vector<uint8_t> &header) {
+        if (!header.empty()) CNIIC_HIP_TRY(c, hipMemcpyAsync(dev, header.data(), header.size(), hipMemcpyHostToDevice, c->stream));
+        return CNIIC_OK;
+    }
+    int begin_sized(uint64_t header_bytes, uint64_t payload_bytes, bool zero = true) {
+        total = header_bytes + payload_bytes;
+        *len = total;
+        if (total > cap) return c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu",
+                                        (unsigned long long)total, (unsigned long long)cap);
+        const uint64_t padded = (total + 3) & ~3ull;
+        direct = is_device_ptr(caller) && (reinterpret_cast<uintptr_t>(caller) & 3) == 0 && padded <= cap;
+        if (direct) dev = caller;
+        else { CNIIC_HIP_TRY(c, staging.alloc(padded + 16)); dev = staging.as<uint8_t>(); }
+        if (zero) CNIIC_HIP_TRY(c, hipMemsetAsync(dev, 0, padded, c->stream));
+        return CNIIC_OK;
+    }
+    int finish() {
+        if (!direct && total)
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(caller, dev, total, is_device_ptr(caller) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CNIIC_OK;
+    }
+};
+
+// ---- zipdict.cpp: the dictionary coder (src/zip/dict.rs) and its two codecs.  The stream of a text is u16 symbols in pairs.
+// text_d: the coder's input in HBM; text_h: the same bytes in host memory, when the caller has them there (else null); head: bytes the
+// stream starts with, outside the coder.  out: host or device.
+int zip_dict_encode_text(Ctx *c, const uint8_t *text_d, const uint8_t *text_h, uint64_t N, const std::vector<uint8_t> &head, uint8_t *out, uint64_t cap,
+                         uint64_t *len);
+int zip_dict_decode_bytes(Ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);   // the whole text; bytes / out: host or device
+int zip_dict_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint32_t *h);   // host memory: the first 8 bytes of the text
+int encode_zip_dict(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
+int decode_zip_dict(Ctx *c, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap, uint32_t *w, uint32_t *h);
+int encode_hilbert_zip(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
+int decode_hilbert_zip(Ctx *c, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap, uint32_t *w, uint32_t *h);
 
 // cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames of a batch decoded together (stream f at bytes + f *
 // stride, lens[f] bytes; image f to rgb + f * img_stride).  taken[f] = 1: frame f was decoded here (rcs[f], msgs[f], w[f], h[f]); 0: the

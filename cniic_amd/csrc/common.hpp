@@ -690,6 +690,37 @@ double rla_threshold(double d);                                                 
 int rle_approx_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, double d, RlePlan *plan);        // counts the runs (syncs)
 int rle_approx_emit(Ctx *c, const uint8_t *lin_d, const RlePlan *plan, uint32_t *out_words_d);  // 12-byte records, average colours
 
+// the scan of the maps (k_rla_compose / k_rla_down over levels of 64): maps0_d holds a map of 256 u8 per piece -- the offset in the next
+// piece at which a chain that enters this piece at offset e (0..254) arrives; *ent0_d: every piece's entry offset, the chain starting at
+// offset 0 of piece 0.  Enqueued; `keep` holds the levels until the caller is done with *ent0_d.
+struct RlaLevels { std::vector<DevBuf> maps, ent; };
+int rla_chain_entries(Ctx *c, const uint8_t *maps0_d, uint32_t npieces, RlaLevels *keep, const uint8_t **ent0_d);
+
+// ---- k_zipdict.hip: the dictionary coder of zip(dict) (src/zip/dict.rs) once its dictionary is full; zipdict.cpp has the part before ----
+// an edge of the frozen trie in the open-addressed table: key = node << 8 | byte (kZdEmpty: free slot), child node (0: none), symbol
+// (kZdNoSym: the text that ends here has none)
+struct ZdEdge { uint32_t key, child, sym, pad; };
+constexpr uint32_t kZdEmpty = 0xffffffffu, kZdNoSym = 0xffffu;
+constexpr uint32_t kZdMaxNodes = (1u << 24) - 2;   // node ids must leave room for the byte in the key (and for kZdEmpty)
+// k_zd_match walks an entry's whole length at every position where the text spells it: a stretch of one colour behind the hand-over costs
+// its length times the longest entry.  Entries beyond this (a flat stretch of 64 KB of text, six rows of a 1024-wide image, BEFORE the
+// dictionary filled) keep the coder on the host to the end of the text.
+constexpr uint64_t kZdMaxEntry = 32768;
+constexpr uint64_t kZdSat = 1ull << 62;            // where the decoder's sums of text lengths stop growing
+constexpr uint64_t kZdLenClamp = 1ull << 38;       // ... and what a single text's length is cut to in the device table (no buffer is that long)
+__host__ __device__ inline uint32_t zd_hash(uint32_t key, uint32_t bits) { return (key * 2654435761u) >> (32 - bits); }
+// text = [w, h as u32 when dims] + 11 bytes per pixel (u64 3, r, g, b); and back: *first_bad_h = the first record whose length is not 3 (npx: none)
+int zd_serialize(Ctx *c, const uint8_t *px_d, uint64_t npx, bool dims, uint32_t w, uint32_t h, uint8_t *text_d);
+int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, uint64_t *first_bad_h);
+// the greedy parse of text_d[P0, N) against the frozen trie (table_h: 2^bits edges, at most half of them used; max_entry: its longest text)
+struct ZdFrozen { uint64_t M = 0, nsyms = 0; uint32_t nchunks = 0; bool windowed = false; DevBuf sym, mark, chunk_off; };
+int zd_frozen_plan(Ctx *c, const uint8_t *text_d, uint64_t N, uint64_t P0, const ZdEdge *table_h, uint32_t bits, uint64_t max_entry, ZdFrozen *plan);  // counts the symbols (syncs)
+int zd_frozen_emit(Ctx *c, const ZdFrozen *plan, uint16_t *out_d);   // nsyms symbols, and 0xFFFF behind an odd number of them
+// the texts of nsym symbols read with a full dictionary (syms_d: 2 nsym bytes in HBM, any alignment; tab_*_h: 65536 entries each)
+struct ZdExpand { uint64_t nsym = 0, total = 0; uint32_t nchunks = 0; const uint8_t *syms_d = nullptr; DevBuf tab, chunk_off; };
+int zd_expand_plan(Ctx *c, const uint8_t *syms_d, uint64_t nsym, const uint64_t *tab_off_h, const uint64_t *tab_len_h, ZdExpand *plan);   // total (saturating; syncs)
+int zd_expand_copy(Ctx *c, const ZdExpand *plan, uint64_t base, uint8_t *out_d, uint64_t limit);
+
 // ---- k_hilbert.hip ----
 int hilbert_xy(Ctx *c, uint32_t w, uint32_t h, uint32_t *xy_d);
 int hilbert_linearize(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out_d);

@@ -268,6 +268,28 @@ double rla_threshold(double d) {
     return t;
 }
 
+// The scan of the maps: level 0 = the pieces' maps, level l + 1 = level l's in groups of 64, up to a level of <= 64; then every
+// group's entry offset down the levels again.  (k_zipdict.hip chains its parse through the same maps.)
+int rla_chain_entries(Ctx *c, const uint8_t *maps0_d, uint32_t npieces, RlaLevels *keep, const uint8_t **ent0_d) {
+    std::vector<uint32_t> cnt{npieces};
+    while (cnt.back() > kRlaGroup) cnt.push_back((uint32_t)ceil_div(cnt.back(), kRlaGroup));
+    keep->maps.resize(cnt.size());
+    keep->ent.resize(cnt.size());
+    std::vector<const uint8_t *> maps(cnt.size(), maps0_d);
+    for (size_t l = 0; l < cnt.size(); l++) {
+        if (l) { CNIIC_HIP_TRY(c, keep->maps[l].alloc((uint64_t)cnt[l] * kRlaPiece)); maps[l] = keep->maps[l].as<uint8_t>(); }
+        CNIIC_HIP_TRY(c, keep->ent[l].alloc(cnt[l]));
+    }
+    for (size_t l = 0; l + 1 < cnt.size(); l++)
+        hipLaunchKernelGGL(k_rla_compose, dim3(cnt[l + 1]), dim3(kRlaThreads), 0, c->stream, maps[l], cnt[l], keep->maps[l + 1].as<uint8_t>());
+    for (size_t l = cnt.size(); l-- > 0;)
+        hipLaunchKernelGGL(k_rla_down, dim3((uint32_t)ceil_div(cnt[l], kRlaGroup)), dim3(kRlaThreads), 0, c->stream, maps[l], cnt[l],
+                           l + 1 < cnt.size() ? (const uint8_t *)keep->ent[l + 1].as<uint8_t>() : (const uint8_t *)nullptr, keep->ent[l].as<uint8_t>());
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    *ent0_d = keep->ent[0].as<uint8_t>();
+    return CNIIC_OK;
+}
+
 int rle_approx_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, double d, RlePlan *plan) {
     plan->n = n;
     plan->nruns = 0;
@@ -279,28 +301,18 @@ int rle_approx_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, double d, RlePlan 
     plan->nchunks = nchunks;
     const double T = rla_threshold(d);
     const int mode = T < 0.0 ? 1 : T >= 3.0 * 255.0 * 255.0 ? 2 : 0;
-    // the levels of the scan: level 0 = the pieces' maps, level l + 1 = level l's in groups of 64, up to a level of <= 64
-    std::vector<uint32_t> cnt{npieces};
-    while (cnt.back() > kRlaGroup) cnt.push_back((uint32_t)ceil_div(cnt.back(), kRlaGroup));
-    std::vector<DevBuf> maps(cnt.size()), ent(cnt.size());
-    DevBuf L, chunk_runs, tot;
+    DevBuf L, maps0, chunk_runs, tot;
+    RlaLevels levels;
     CNIIC_HIP_TRY(c, L.alloc(n));
-    for (size_t l = 0; l < cnt.size(); l++) {
-        CNIIC_HIP_TRY(c, maps[l].alloc((uint64_t)cnt[l] * kRlaPiece));
-        CNIIC_HIP_TRY(c, ent[l].alloc(cnt[l]));
-    }
+    CNIIC_HIP_TRY(c, maps0.alloc((uint64_t)npieces * kRlaPiece));
     CNIIC_HIP_TRY(c, chunk_runs.alloc((uint64_t)nchunks * 4));
     CNIIC_HIP_TRY(c, tot.alloc(8));
     CNIIC_HIP_TRY(c, plan->flags.alloc((uint64_t)nchunks * kRlaThreads * 2));
     CNIIC_HIP_TRY(c, plan->run_off.alloc((uint64_t)nchunks * 8));
-    hipLaunchKernelGGL(k_rla_len_maps, dim3(npieces), dim3(kRlaThreads), 0, c->stream, lin_d, n, T, mode, L.as<uint8_t>(), maps[0].as<uint8_t>());
-    for (size_t l = 0; l + 1 < cnt.size(); l++)
-        hipLaunchKernelGGL(k_rla_compose, dim3(cnt[l + 1]), dim3(kRlaThreads), 0, c->stream, (const uint8_t *)maps[l].as<uint8_t>(), cnt[l],
-                           maps[l + 1].as<uint8_t>());
-    for (size_t l = cnt.size(); l-- > 0;)
-        hipLaunchKernelGGL(k_rla_down, dim3((uint32_t)ceil_div(cnt[l], kRlaGroup)), dim3(kRlaThreads), 0, c->stream, (const uint8_t *)maps[l].as<uint8_t>(),
-                           cnt[l], l + 1 < cnt.size() ? (const uint8_t *)ent[l + 1].as<uint8_t>() : (const uint8_t *)nullptr, ent[l].as<uint8_t>());
-    hipLaunchKernelGGL(k_rla_flags, dim3(nchunks), dim3(kRlaThreads), 0, c->stream, (const uint8_t *)L.as<uint8_t>(), n, (const uint8_t *)ent[0].as<uint8_t>(),
+    hipLaunchKernelGGL(k_rla_len_maps, dim3(npieces), dim3(kRlaThreads), 0, c->stream, lin_d, n, T, mode, L.as<uint8_t>(), maps0.as<uint8_t>());
+    const uint8_t *ent0 = nullptr;
+    CNIIC_TRY(rla_chain_entries(c, maps0.as<uint8_t>(), npieces, &levels, &ent0));
+    hipLaunchKernelGGL(k_rla_flags, dim3(nchunks), dim3(kRlaThreads), 0, c->stream, (const uint8_t *)L.as<uint8_t>(), n, ent0,
                        plan->flags.as<uint16_t>(), chunk_runs.as<uint32_t>());
     CNIIC_TRY(rle_offsets(c, chunk_runs.as<uint32_t>(), nchunks, plan->run_off.as<uint64_t>(), tot.as<uint64_t>()));
     CNIIC_HIP_TRY(c, hipGetLastError());

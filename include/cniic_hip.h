@@ -365,8 +365,9 @@ int32_t cniic_huf_size(int32_t sym_kind, const uint64_t *counts, uint64_t n, uin
  * "voronoi(2048)", "delta", "hilbert(rle)" = "hilbert(rle(0))", "hilbert(rle(4))" (src/codec.rs:41-59, FromStr impls of each
  * codec; hilbertc.rs:341-397 for the last two: rle(<f64>) takes what Rust's f64::from_str takes -- "4", "+4", "4.", ".5", "1e-3",
  * "inf", "-infinity", "nan" -- and its name() is "hilbert-rle" for d == 0, else "hilbert-rle-approx_" + d as Rust's Display prints
- * it, which can be longer than 300 characters; zip is not built).  Every entry point below that takes an expression takes all of
- * them.
+ * it, which can be longer than 300 characters), "zip(dict)" (zipc.rs:62-80: exactly that; name() "zip-dict", lossless; zip(back) is
+ * not built, and hilbert(zip) is not an expression here: cniic_hilbert_zip_encode / _decode below).  Every entry point below that
+ * takes an expression takes all of them.  The dimensions of a zip(dict) stream are inside its compressed text: cniic_zip_dict_dims.
  * cniic_codec_parse describes a codec as (kind, u32 argument), which cannot carry the f64: it answers CNIIC_ERR_BAD_ARG for
  * hilbert(rle(d)) with d != 0.  cniic_codec_parse_f64 takes every expression; darg is d (0 for d == 0.0 and -0.0, for `hilbert(rle)`
  * and for the other codecs).  Any out-parameter may be NULL. */
@@ -414,7 +415,33 @@ int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cni
  * The stream decodes with "hilbert(rle)" or "hilbert(rle(<any d>))": the records are the same (RleDecoder, hilbertc.rs:304-335). */
 int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *ctx, double d, const uint8_t *rgb, uint32_t w, uint32_t h,
                                         uint8_t *out, uint64_t cap, uint64_t *len);
-/* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics. */
+/* The dictionary coder on plain bytes (zip::zip_dict_encode / zip_dict_decode, src/zip/dict.rs).  The stream is what the reference
+ * writes: u16 little-endian symbols in pairs -- 0..255 the single bytes, 0xFFFF the empty text, 0x100.. the two texts of a pair joined,
+ * one new symbol per pair until 0xFFFE has been handed out (65 279 pairs), after which the dictionary stays as it is.  Up to there the
+ * coder is a serial walk and runs on the host; from there on the GPU parses the rest of the text against the frozen trie (encode) and
+ * copies every symbol's text out of the part already decoded (decode).  A text whose dictionary never fills (a flat image: entries
+ * double in length), or fills with an entry of more than 32 768 bytes or a trie of more than 2^24 nodes, is coded on the host to its
+ * end (seconds for tens of megabytes).  Host or device buffers; CNIIC_ERR_CAPACITY with *len = bytes needed.
+ * Decode answers CNIIC_ERR_DECODE where the reference panics: a symbol that has not been handed out yet, a first symbol without a
+ * second.  0xFFFF is legal anywhere; a single byte behind the last whole pair ends the stream.  No memory is allocated from a size a
+ * stream claims before the lengths have been summed and held against cap.
+ * Stage timers (cniic_last_kernel_time): "zd_fill_host", "zd_table_host", "zd_match", "zd_chain" or "zd_chain_plain" (the longest
+ * entry has more than 255 bytes), "zd_compact"; "zd_prefix_host", "zd_scan", "zd_copy"; the codecs add "zd_serialize". */
+int32_t cniic_zip_dict_encode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
+int32_t cniic_zip_dict_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
+/* The dimensions of a zip(dict) stream: the first 8 bytes of its text, decoded from its first pairs.  HOST memory, no context.
+ * CNIIC_ERR_DECODE when the stream is malformed before it has spelt 8 bytes, or ends there. */
+int32_t cniic_zip_dict_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint32_t *h);
+/* Hilbert { compress: Zip } (hilbertc.rs:27-29,47-49,67-77; name "hilbert-zip", lossless): the 8 raw bytes of dimensions, then the
+ * dictionary coder over the 11-byte records (u64 3, r, g, b) of the pixels in scan order -- cniic_hilbert_linearize's, injected scans
+ * included.  Decode: CNIIC_ERR_DECODE where the coder's stream is malformed within the w h records the traversal asks for; colours the
+ * text does not reach stay zero, as do those from a record on whose length is not 3 (the reference then reads that many items more
+ * before it gives up: what is malformed behind such a record is not reported here).  Host or device buffers. */
+int32_t cniic_hilbert_zip_encode(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
+int32_t cniic_hilbert_zip_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
+/* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics.  zip(dict): the reader is lazy (zipc.rs:28-36) -- exactly
+ * 8 + 11 w h bytes of text are pulled, whole pairs as they are needed, and nothing behind the pair that completes the last pixel is
+ * looked at; fewer bytes, or a pixel record whose length is not 3, is CNIIC_ERR_DECODE. */
 int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t n,
                            uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
 /* Codec::decode of `frames` streams: stream f at bytes + f * stride, lens[f] bytes (exactly what cniic_codec_encode_batch writes).
