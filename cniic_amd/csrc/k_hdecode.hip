@@ -218,9 +218,6 @@ __device__ __forceinline__ uint64_t hd_stage_at(const HdStream &S, const uint32_
     __syncthreads();
     return (uint64_t)(w0 * 32);  // (two's complement: position - base stays right for block 0)
 }
-__device__ __forceinline__ uint64_t hd_stage(const HdStream &S, const uint32_t *__restrict__ lut_g, uint32_t *lut_s, uint32_t *stage) {
-    return hd_stage_at(S, lut_g, lut_s, stage, blockIdx.x);
-}
 
 // A thread's view of the staged stream: the next bits left-aligned in a register, topped up a word at a time -- one LDS read per
 // 32 bits consumed instead of two or three per symbol.  WIDE (codes of more than 32 bits): the window is rebuilt from three
@@ -312,16 +309,17 @@ constexpr int kHdRoundsShort = 24;
 // different colours, 51 ms for a ramp.  A list that has kept 97 per cent of its length over three rounds is such a stream at any size.
 __host__ inline uint32_t hd_hopeless_pct(uint64_t nsub) { return nsub <= (1ull << 16) ? 35u : nsub <= (1ull << 19) ? 60u : 97u; }
 constexpr uint64_t kHdPhasesMaxSub = 1ull << 16;   // streams of up to this many subsequences (4 MiB) go to k_hd_phase_maps when the blind checks have not settled them
+// One block of one stream, for the single-stream kernel and the batch's alike.  blk: the block's place in its stream; positions
+// (S.bit0, start, end) are in the stream's own frame, subsequence t of the stream is entry g0 + t of end_prev / end_out / start /
+// count (g0 = 0 for a single stream, the frame's first subsequence in a batch) and is compared with t - 1 only for t > 0: the
+// streams of a batch never look into each other.  *moved: the one word that a moved end sets.  hopeless_min, hopeless_pct, hopeless
+// (the count of the blocks that gave the stream up, see the settle loop) and keep (the kept-symbol rows, hd_keep_col) may be 0 /
+// null: the batch passes them as literals and has none of those branches.
 template <bool WIDE>
-__global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg, uint64_t nsub, const uint64_t *__restrict__ end_prev,
-                                                        uint64_t *__restrict__ end_out, uint64_t *__restrict__ start, uint32_t *__restrict__ count,
-                                                        uint32_t *__restrict__ changed, int max_rounds, uint32_t hopeless_min, uint32_t hopeless_pct,
-                                                        uint32_t *__restrict__ keep /* the kept-symbol rows (hd_keep_col), or null */) {
+__device__ __forceinline__ void hd_pass_block(const HdStream &S, const HdTables &T, uint32_t blk, uint64_t g0, uint64_t nsub, const uint64_t *__restrict__ end_prev,
+                                              uint64_t *__restrict__ end_out, uint64_t *__restrict__ start, uint32_t *__restrict__ count, uint32_t *moved,
+                                              int max_rounds, uint32_t hopeless_min, uint32_t hopeless_pct, uint32_t *hopeless, uint32_t *__restrict__ keep) {
     extern __shared__ __align__(16) uint32_t hd_lds[];
-    // (hopeless_min != 0: pass 0 counts in changed[5] the blocks whose threads do not fall into step -- see the settle loop -- and once
-    // that many have said so, the checks and the write behind it return at once: the host takes k_hd_phase_maps after its one look)
-    if (hopeless_min && end_prev && changed[5] >= hopeless_min) return;
-    const HdTables &T = Tg;
     __shared__ unsigned long long s_end[kHdThreads], s_nstart[kHdThreads], s_nend[kHdThreads];
     __shared__ uint32_t s_ncnt[kHdThreads];
     __shared__ uint16_t s_list[kHdThreads];
@@ -331,14 +329,14 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
     uint32_t *stage = hd_lds + (T.use1 ? (1u << kHdLut) : 0u);   // (without the first table the launch brought LDS for the stream alone)
     static_assert(kHdSub - kHdWarm >= 32, "a warm-up never starts before the stream's first bit");
     const uint32_t tid = threadIdx.x;
-    const uint64_t t0 = (uint64_t)blockIdx.x * kHdThreads, t = t0 + tid;
+    const uint64_t t0 = (uint64_t)blk * kHdThreads, t = t0 + tid, g = g0 + t;   // t: in the stream, g: in the boundary arrays
     const bool live = t < nsub;
     const uint64_t lo = max(t * kHdSub, S.bit0), hi = min((t + 1) * kHdSub, S.nbits);
     uint64_t my_start = 0, my_end = 0, base = 0;
     uint32_t my_cnt = 0;
     uint64_t pred0 = 0;      // where the thread before the block's first one ended (pass 0: not known yet -- the first thread trusts its warm-up)
     if (!end_prev) {
-        base = hd_stage(S, T.use1 ? T.lut1 : nullptr, lut_s, stage);
+        base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, blk);
         if (live) {
             uint64_t at = S.bit0;
             if (t) {       // warm-up: from kHdWarm bits before the subsequence to the first boundary inside it
@@ -356,14 +354,14 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
         // a check: who is out of step with the thread before?  Nobody, as a rule -- then the block is done without staging anything
         bool redo = false;
         if (live) {
-            const uint64_t s = t ? end_prev[t - 1] : S.bit0;
-            my_start = start[t]; my_end = end_prev[t]; my_cnt = count[t];
+            const uint64_t s = t ? end_prev[g - 1] : S.bit0;   // (the stream's first subsequence: its payload's first bit)
+            my_start = start[g]; my_end = end_prev[g]; my_cnt = count[g];
             redo = s != my_start;
             if (tid == 0) pred0 = s;
-            if (!redo) end_out[t] = my_end;   // in step with the thread before: what it found stands (rewritten below if a cure moves it)
+            if (!redo) end_out[g] = my_end;   // in step with the thread before: what it found stands (rewritten below if a cure moves it)
         }
         if (!__syncthreads_or(redo)) return;
-        base = hd_stage(S, T.use1 ? T.lut1 : nullptr, lut_s, stage);
+        base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, blk);
     }
     // ---- the block settles itself
     s_end[tid] = live ? my_end : ~0ull;
@@ -392,7 +390,7 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
             else if ((round == 3 && nl0 >= 64 && nl * 100 > nl0 * hopeless_pct) ||
                      (round == kHdRoundsShort && nl0 >= 64 && nl * 2 > nl0)) {   // (round 4: ... or half of it over 24 rounds: codes of nearly one length
                                                                                  // cure a few entries a round, and the block would chain through all 256)
-                if (tid == 0) atomicAdd(&changed[5], 1u);
+                if (tid == 0) atomicAdd(hopeless, 1u);
                 break;
             }
         }
@@ -411,12 +409,22 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables Tg,
         if (redo) { my_start = s_nstart[tid]; my_end = s_nend[tid]; my_cnt = s_ncnt[tid]; s_end[tid] = my_end; }
     }
     if (!live) return;
-    start[t] = my_start;
-    end_out[t] = my_end;
-    count[t] = my_cnt;
+    start[g] = my_start;
+    end_out[g] = my_end;
+    count[g] = my_cnt;
     // Only a moved END matters to anybody outside the block.  If no end moves in a pass, every thread's start equals its
     // predecessor's end and the chain from the first bit is exact.
-    if (end_prev && (my_end != end_at_entry || gave_up)) *changed = 1u;
+    if (end_prev && (my_end != end_at_entry || gave_up)) *moved = 1u;
+}
+template <bool WIDE>
+__global__ __launch_bounds__(kHdThreads) void k_hd_pass(HdStream S, HdTables T, uint64_t nsub, const uint64_t *__restrict__ end_prev,
+                                                        uint64_t *__restrict__ end_out, uint64_t *__restrict__ start, uint32_t *__restrict__ count,
+                                                        uint32_t *__restrict__ changed, int max_rounds, uint32_t hopeless_min, uint32_t hopeless_pct,
+                                                        uint32_t *__restrict__ keep /* the kept-symbol rows (hd_keep_col), or null */) {
+    // (hopeless_min != 0: pass 0 counts in changed[5] the blocks whose threads do not fall into step -- see the settle loop -- and once
+    // that many have said so, the checks and the write behind it return at once: the host takes k_hd_phase_maps after its one look)
+    if (hopeless_min && end_prev && changed[5] >= hopeless_min) return;
+    hd_pass_block<WIDE>(S, T, blockIdx.x, 0, nsub, end_prev, end_out, start, count, changed, max_rounds, hopeless_min, hopeless_pct, changed + 5, keep);
 }
 
 // ---------------------------------------------------------------- streams that do not fall into step (round 3)
@@ -496,27 +504,39 @@ __device__ __forceinline__ void ud_unpack(uint32_t key, int32_t d[3]) {
     d[0] = (int32_t)((key >> 18) & 511) - 255; d[1] = (int32_t)((key >> 9) & 511) - 255; d[2] = (int32_t)(key & 511) - 255;
 }
 
+// symbol i of an RGB output: the key's three bytes
+__device__ __forceinline__ void hd_put_rgb(uint8_t *rgb, uint64_t i, uint32_t key) {
+    rgb[3 * i] = (uint8_t)(key >> 16); rgb[3 * i + 1] = (uint8_t)(key >> 8); rgb[3 * i + 2] = (uint8_t)key;
+}
+// symbols i .. i + 3, i a multiple of 4 and rgb 4-byte aligned: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3 as three little-endian words
+__device__ __forceinline__ void hd_put_rgb4(uint8_t *rgb, uint64_t i, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3) {
+    uint32_t *dst = reinterpret_cast<uint32_t *>(rgb + 3 * i);
+    const uint32_t w0 = ((k0 >> 16) & 255) | (((k0 >> 8) & 255) << 8) | ((k0 & 255) << 16) | (((k1 >> 16) & 255) << 24);
+    const uint32_t w1 = ((k1 >> 8) & 255) | ((k1 & 255) << 8) | (((k2 >> 16) & 255) << 16) | (((k2 >> 8) & 255) << 24);
+    const uint32_t w2 = (k2 & 255) | (((k3 >> 16) & 255) << 8) | (((k3 >> 8) & 255) << 16) | ((k3 & 255) << 24);
+    dst[0] = w0; dst[1] = w1; dst[2] = w2;
+}
+
 // every thread decodes its symbols once more and writes them: MODE 0 = packed keys (u32 each), 1 = RGB bytes (3 each).
 // Four symbols leave together (16 / 12 bytes at an aligned address) where the symbol index allows: a store per symbol is one
 // L2 request per lane, 16.7 M of them at 4096^2.
+// One block of one stream (blk, g0: as in hd_pass_block; sym0 = off[g0], the offset of the stream's first symbol: 0 for a single
+// stream).  only_long (counts: only the subsequences of more than kHdKeep symbols, the others were copied) and chunk_sum (MODE 0:
+// see above) may be null: the batch passes literals.
 template <bool WIDE, int MODE>
-__global__ __launch_bounds__(kHdThreads) void k_hd_write(HdStream S, HdTables Tg, uint64_t nsub, const uint64_t *__restrict__ start,
-                                                         const uint64_t *__restrict__ off, uint64_t nsyms, void *__restrict__ out,
-                                                         const uint32_t *__restrict__ hopeless /* null, or the count and its bound: see k_hd_pass */, uint32_t hopeless_min,
-                                                         const uint32_t *__restrict__ only_long = nullptr /* counts: only the subsequences of more than kHdKeep symbols (the others were copied) */,
-                                                         int32_t *__restrict__ chunk_sum = nullptr /* MODE 0: see above */) {
+__device__ __forceinline__ void hd_write_block(const HdStream &S, const HdTables &T, uint32_t blk, uint64_t g0, uint64_t sym0, uint64_t nsub, const uint64_t *__restrict__ start,
+                                               const uint64_t *__restrict__ off, uint64_t nsyms, void *__restrict__ out, const uint32_t *__restrict__ only_long,
+                                               int32_t *__restrict__ chunk_sum) {
     extern __shared__ __align__(16) uint32_t hd_lds[];
-    if (hopeless && *hopeless >= hopeless_min) return;
-    const HdTables &T = Tg;
     uint32_t *lut_s = hd_lds;
     uint32_t *stage = hd_lds + (T.use1 ? (1u << kHdLut) : 0u);
-    const uint64_t t = (uint64_t)blockIdx.x * kHdThreads + threadIdx.x;
-    if (only_long && !__syncthreads_or(t < nsub && only_long[t] > kHdKeep)) return;   // (the rule: nobody -- nothing is staged)
-    const uint64_t base = hd_stage(S, T.use1 ? T.lut1 : nullptr, lut_s, stage);
+    const uint64_t t = (uint64_t)blk * kHdThreads + threadIdx.x, g = g0 + t;
+    if (only_long && !__syncthreads_or(t < nsub && only_long[g] > kHdKeep)) return;   // (the rule: nobody -- nothing is staged)
+    const uint64_t base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, blk);
     if (t >= nsub) return;
-    if (only_long && only_long[t] <= kHdKeep) return;
+    if (only_long && only_long[g] <= kHdKeep) return;
     const uint64_t hi = min((t + 1) * kHdSub, S.nbits);
-    uint64_t at = start[t], idx = off[t], widx = idx;   // idx: next symbol to be stored, widx: next to be decoded
+    uint64_t at = start[g], idx = off[g] - sym0, widx = idx;   // idx: next symbol to be stored, widx: next to be decoded
     if (at >= hi) return;
     uint32_t *keys = static_cast<uint32_t *>(out);
     uint8_t *rgb = static_cast<uint8_t *>(out);
@@ -548,7 +568,7 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_write(HdStream S, HdTables Tg
     };
     auto put1 = [&](uint32_t key) {
         if (MODE == 0) keys[idx] = key;
-        else { rgb[3 * idx] = (uint8_t)(key >> 16); rgb[3 * idx + 1] = (uint8_t)(key >> 8); rgb[3 * idx + 2] = (uint8_t)key; }
+        else hd_put_rgb(rgb, idx, key);
         idx++;
     };
     uint32_t k0, k1, k2, k3;
@@ -559,18 +579,19 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_write(HdStream S, HdTables Tg
         if (!next(k2)) { put1(k0); put1(k1); break; }
         if (!next(k3)) { put1(k0); put1(k1); put1(k2); break; }
         // (next() advanced `at` and widx only: idx is still the first of the four)
-        if (MODE == 0) {
-            *reinterpret_cast<uint4 *>(keys + idx) = make_uint4(k0, k1, k2, k3);
-        } else {  // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3, little-endian words
-            uint32_t *dst = reinterpret_cast<uint32_t *>(rgb + 3 * idx);
-            const uint32_t w0 = ((k0 >> 16) & 255) | (((k0 >> 8) & 255) << 8) | ((k0 & 255) << 16) | (((k1 >> 16) & 255) << 24);
-            const uint32_t w1 = ((k1 >> 8) & 255) | ((k1 & 255) << 8) | (((k2 >> 16) & 255) << 16) | (((k2 >> 8) & 255) << 24);
-            const uint32_t w2 = (k2 & 255) | (((k3 >> 16) & 255) << 8) | (((k3 >> 8) & 255) << 16) | ((k3 & 255) << 24);
-            dst[0] = w0; dst[1] = w1; dst[2] = w2;
-        }
+        if (MODE == 0) *reinterpret_cast<uint4 *>(keys + idx) = make_uint4(k0, k1, k2, k3);
+        else hd_put_rgb4(rgb, idx, k0, k1, k2, k3);
         idx += 4;
     }
     if (MODE == 0 && chunk_sum) cs_flush();
+}
+template <bool WIDE, int MODE>
+__global__ __launch_bounds__(kHdThreads) void k_hd_write(HdStream S, HdTables T, uint64_t nsub, const uint64_t *__restrict__ start,
+                                                         const uint64_t *__restrict__ off, uint64_t nsyms, void *__restrict__ out,
+                                                         const uint32_t *__restrict__ hopeless /* null, or the count and its bound: see k_hd_pass */, uint32_t hopeless_min,
+                                                         const uint32_t *__restrict__ only_long, int32_t *__restrict__ chunk_sum) {
+    if (hopeless && *hopeless >= hopeless_min) return;
+    hd_write_block<WIDE, MODE>(S, T, blockIdx.x, 0, 0, nsub, start, off, nsyms, out, only_long, chunk_sum);
 }
 
 // The kept symbols to their places (round 5): block b = the subsequences [256 b, 256 b + 256), whose symbols are the output positions
@@ -632,19 +653,13 @@ __global__ __launch_bounds__(kHdThreads) void k_hd_compact(const uint32_t *__res
         }
         if (have[0] && have[1] && have[2] && have[3]) {
             if (MODE == 0) *reinterpret_cast<uint4 *>(keys + p0) = make_uint4(k[0], k[1], k[2], k[3]);
-            else {
-                uint32_t *dst = reinterpret_cast<uint32_t *>(rgb + 3 * p0);
-                dst[0] = ((k[0] >> 16) & 255) | (((k[0] >> 8) & 255) << 8) | ((k[0] & 255) << 16) | (((k[1] >> 16) & 255) << 24);
-                dst[1] = ((k[1] >> 8) & 255) | ((k[1] & 255) << 8) | (((k[2] >> 16) & 255) << 16) | (((k[2] >> 8) & 255) << 24);
-                dst[2] = (k[2] & 255) | (((k[3] >> 16) & 255) << 8) | (((k[3] >> 8) & 255) << 16) | ((k[3] & 255) << 24);
-            }
+            else hd_put_rgb4(rgb, p0, k[0], k[1], k[2], k[3]);
         } else {
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (!have[u]) continue;
-                const uint64_t p = p0 + u;
-                if (MODE == 0) keys[p] = k[u];
-                else { rgb[3 * p] = (uint8_t)(k[u] >> 16); rgb[3 * p + 1] = (uint8_t)(k[u] >> 8); rgb[3 * p + 2] = (uint8_t)k[u]; }
+                if (MODE == 0) keys[p0 + u] = k[u];
+                else hd_put_rgb(rgb, p0 + u, k[u]);
             }
         }
     }
@@ -654,23 +669,40 @@ __global__ void k_hd_fill(uint32_t *__restrict__ keys, uint64_t n, uint32_t key)
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) keys[i] = key;
 }
-__global__ void k_hd_fill_rgb(uint8_t *__restrict__ rgb, uint64_t n, uint32_t key) {
+// n RGB symbols of one key, by the blocks of the grid's x dimension (k_hd_fill_rgb; k_hdb_fill: a frame per blockIdx.y)
+__device__ __forceinline__ void hd_fill_rgb(uint8_t *__restrict__ rgb, uint64_t n, uint32_t key) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        rgb[3 * i] = (uint8_t)(key >> 16); rgb[3 * i + 1] = (uint8_t)(key >> 8); rgb[3 * i + 2] = (uint8_t)key;
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) hd_put_rgb(rgb, i, key);
 }
+__global__ void k_hd_fill_rgb(uint8_t *__restrict__ rgb, uint64_t n, uint32_t key) { hd_fill_rgb(rgb, n, key); }
 
 // packed RGB keys -> interleaved bytes
 __global__ void k_keys_to_rgb(const uint32_t *__restrict__ keys, uint64_t n, uint8_t *__restrict__ rgb) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t k = keys[i];
-        rgb[3 * i] = (uint8_t)(k >> 16); rgb[3 * i + 1] = (uint8_t)(k >> 8); rgb[3 * i + 2] = (uint8_t)k;
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) hd_put_rgb(rgb, i, keys[i]);
 }
 
 struct LeafMeta { uint32_t max_len; };
+
+// The stream of a payload anywhere in HBM (any alignment: it is read as words from the 4-byte boundary below it), with the warm-up
+// its code lengths ask for.  A thread that has not fallen into step by the time it enters its subsequence is decoded again in the
+// block's settle loop, and a RUN of such threads one round per member: every round is a chain as long as the whole first decode with
+// a handful of lanes at work.  Codes of 14 bits need ~300 bits to fall into step: 128 bits of warm-up left a third of the threads for
+// the rounds.
+static HdStream hd_stream(const uint8_t *payload_d, uint64_t payload_bytes, uint64_t nsyms) {
+    HdStream S{};
+    const uintptr_t a = reinterpret_cast<uintptr_t>(payload_d);
+    S.w = reinterpret_cast<const uint32_t *>(a & ~uintptr_t(3));
+    S.bit0 = (a & 3) * 8;
+    S.nbits = S.bit0 + payload_bytes * 8;
+    S.nwords = ceil_div(S.nbits, 32);
+    S.warm = payload_bytes * 8 >= nsyms * 12 ? 384 : 128;   // 384: long codes (the differences of a photograph)
+    return S;
+}
+// bits of the second table: the longest code's length up to `cap`, or 0 when the first table answers every code
+static uint32_t hd_lut2_bits(uint32_t max_len, uint32_t cap) {
+    return max_len > (uint32_t)kHdLut ? std::min<uint32_t>(max_len, std::max(cap, (uint32_t)kHdLut + 1)) : 0u;
+}
 
 // The decoder as a table of leaves already in HBM (tab_d: code u64[n] | key u32[n] at off_key | len u8[n] at off_len).
 // payload: the bit stream, in HOST memory or -- payload_dev -- anywhere in HBM (any alignment: it is read as words from the 4-byte
@@ -692,24 +724,11 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     if ((reinterpret_cast<uintptr_t>(out_d) & (mode == 0 ? 15u : 3u)) != 0) return c->fail(CNIIC_ERR_BAD_ARG, "huff_decode_dev: misaligned output");
     // ---- the stream as aligned words
     DevBuf w_d;
-    HdStream S{};
-    if (payload_dev) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(payload);
-        S.w = reinterpret_cast<const uint32_t *>(a & ~uintptr_t(3));
-        S.bit0 = (a & 3) * 8;
-    } else {
+    if (!payload_dev) {
         CNIIC_HIP_TRY(c, w_d.alloc((payload_bytes + 3) & ~3ull));
         CNIIC_HIP_TRY(c, hipMemcpyAsync(w_d.p, payload, payload_bytes, hipMemcpyHostToDevice, c->stream));
-        S.w = w_d.as<uint32_t>();
-        S.bit0 = 0;
     }
-    S.nbits = S.bit0 + payload_bytes * 8;
-    S.nwords = ceil_div(S.nbits, 32);
-    // The warm-up.  A thread that has not fallen into step by the time it enters its subsequence is decoded again in the block's settle
-    // loop, and a RUN of such threads one round per member: every round is a chain as long as the whole first decode with a handful of
-    // lanes at work.  Codes of 14 bits need ~300 bits to fall into step: 128 bits of warm-up left a third of the threads for the rounds.
-    S.warm = 128;
-    if (payload_bytes * 8 >= nsyms * 12) S.warm = 384;   // long codes (the differences of a photograph)
+    HdStream S = hd_stream(payload_dev ? payload : w_d.as<uint8_t>(), payload_bytes, nsyms);
     if (const char *e = test_env("CNIIC_HD_WARM")) S.warm = std::min<uint32_t>(kHdWarm, std::max(32, atoi(e)) & ~31u);
     // ---- the look-up tables
     // The second table, measured (round 3): 2^18 entries = 2 MiB, which stays in an XCD's L2 -- `delta` 16384^2 (54 K leaves, 14.5 bits a
@@ -717,7 +736,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     // 2^24 entries = 128 MiB -- there even 20 bits leave half a dozen leaves per entry, i.e. a few more dependent reads for EVERY symbol:
     // `hufman` 4096^2 (6.8 M leaves) 7.0 / 5.3 / 4.6 / 4.6 ms with 20 / 22 / 24 / 26.  CNIIC_HD_LUT2_BITS: the cap, for measurements.
     const uint32_t cap2 = test_env("CNIIC_HD_LUT2_BITS") ? (uint32_t)atoi(test_env("CNIIC_HD_LUT2_BITS")) : (n >= (1u << 20) ? 24u : 18u);
-    const uint32_t bits2 = max_len > (uint32_t)kHdLut ? std::min<uint32_t>(max_len, std::max(cap2, (uint32_t)kHdLut + 1)) : 0u;
+    const uint32_t bits2 = hd_lut2_bits(max_len, cap2);
     DevBuf lut1_d, lut2_d, lut3_d, cnt_d;
     CNIIC_HIP_TRY(c, lut1_d.alloc((4ull << kHdLut)));
     CNIIC_HIP_TRY(c, cnt_d.alloc(4));   // the third tables' cursor
@@ -805,6 +824,11 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
         const uint64_t *st = start_d.as<uint64_t>(), *of = off.as<uint64_t>();
         const uint32_t *hp = guarded && hopeless_min ? changed.as<uint32_t>() + 5 : nullptr;
         if (sums) sums->filled = false;
+        // (a wide code has no verdict: phases_ok is false, so hopeless_min is 0 and hp null)
+        auto decode = [&](const uint32_t *only_long, int32_t *chunk_sum) {
+            auto kern = wide ? (mode == 0 ? k_hd_write<true, 0> : k_hd_write<true, 1>) : (mode == 0 ? k_hd_write<false, 0> : k_hd_write<false, 1>);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, hp, hopeless_min, only_long, chunk_sum);
+        };
         if (kept && keep_p) {   // a copy, and one more decode of the few subsequences of more than kHdKeep symbols
             const uint32_t *cn = count.as<uint32_t>();
             int32_t *cs = nullptr;   // packed differences: FromDiff's chunk sums on the way (a write that is repeated starts them again)
@@ -817,23 +841,8 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
             }
             if (mode == 0) hipLaunchKernelGGL(k_hd_compact<0>, dim3(grid), dim3(kHdThreads), 0, c->stream, (const uint32_t *)keep_p, of, cn, nsub, nsyms, out_d, hp, hopeless_min, cs);
             else hipLaunchKernelGGL(k_hd_compact<1>, dim3(grid), dim3(kHdThreads), 0, c->stream, (const uint32_t *)keep_p, of, cn, nsub, nsyms, out_d, hp, hopeless_min, (int32_t *)nullptr);
-            if (wide) {
-                if (mode == 0) hipLaunchKernelGGL((k_hd_write<true, 0>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, (const uint32_t *)nullptr, 0u, cn, cs);
-                else hipLaunchKernelGGL((k_hd_write<true, 1>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, (const uint32_t *)nullptr, 0u, cn, (int32_t *)nullptr);
-            } else {
-                if (mode == 0) hipLaunchKernelGGL((k_hd_write<false, 0>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, hp, hopeless_min, cn, cs);
-                else hipLaunchKernelGGL((k_hd_write<false, 1>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, hp, hopeless_min, cn, (int32_t *)nullptr);
-            }
-            CNIIC_HIP_TRY(c, hipGetLastError());
-            return CNIIC_OK;
-        }
-        if (wide) {
-            if (mode == 0) hipLaunchKernelGGL((k_hd_write<true, 0>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, (const uint32_t *)nullptr, 0u);
-            else hipLaunchKernelGGL((k_hd_write<true, 1>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, (const uint32_t *)nullptr, 0u);
-        } else {
-            if (mode == 0) hipLaunchKernelGGL((k_hd_write<false, 0>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, hp, hopeless_min);
-            else hipLaunchKernelGGL((k_hd_write<false, 1>), dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, st, of, nsyms, out_d, hp, hopeless_min);
-        }
+            decode(cn, cs);   // (cs: null unless mode 0)
+        } else decode(nullptr, nullptr);
         CNIIC_HIP_TRY(c, hipGetLastError());
         return CNIIC_OK;
     };
@@ -926,13 +935,12 @@ int huff_decode_dev(Ctx *c, const LeafTable &lt, const uint8_t *payload, bool pa
 }
 
 // ---------------------------------------------------------------- many streams in one set of launches (cniic_codec_decode_batch)
-// The frames of a batch share every launch: a frame's subsequences are numbered from its own payload's first word, as in the
-// single-stream decode, and laid end to end in global arrays (frame f's are [sub0, sub0 + nsub)); a block decodes subsequences of
-// exactly one frame (blk_frame[block], blk0 = the frame's first block), stages that frame's first table and stretch of the stream like
-// k_hd_pass and walks with the same hd_run.  A frame's first subsequence starts at its payload's first bit, and the check of thread t
-// against t - 1 stops there: frames never look into each other.  changed[f] / done[f]: one word each per frame -- a check that moves
-// no end of frame f settles it (k_hdb_settle), and its blocks leave at once from then on.  RGB symbols (mode 1), codes of at most 32
-// bits; no kept rows (the write decodes again) and no phase maps (a frame that does not settle goes back to the single-stream decode).
+// The frames of a batch share every launch, and every block runs the single-stream decoder's hd_pass_block / hd_write_block on one
+// frame.  The frame table (HdbFrame) holds each frame's stream and tables; its subsequences lie end to end in the boundary arrays
+// (frame f's are [sub0, sub0 + nsub)), and blk_frame[block] names the frame a block belongs to (blk0 = the frame's first block).
+// changed[f] / done[f]: one word each per frame -- a check that moves no end of frame f settles it (k_hdb_settle), and its blocks
+// leave at once from then on.  RGB symbols (mode 1), codes of at most 32 bits; no kept rows (the write decodes again) and no phase
+// maps (a frame that does not settle goes back to the single-stream decode).
 constexpr int kHdbMaxPasses = 8;   // checks before a frame that has not settled goes back to the single-stream decode
 struct HdbFrame {
     HdStream S;
@@ -957,93 +965,17 @@ __global__ __launch_bounds__(256) void k_hdb_build_lut(const HdbFrame *__restric
 __global__ __launch_bounds__(256) void k_hdb_fill(const HdbFrame *__restrict__ fr) {
     const HdbFrame &F = fr[blockIdx.y];
     if (F.T.n != 1) return;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < F.nsyms; i += stride) {
-        F.out[3 * i] = (uint8_t)(F.key0 >> 16); F.out[3 * i + 1] = (uint8_t)(F.key0 >> 8); F.out[3 * i + 2] = (uint8_t)F.key0;
-    }
+    hd_fill_rgb(F.out, F.nsyms, F.key0);
 }
 
-// k_hd_pass for a batch (end_prev == null: pass 0).  Arrays are indexed by global subsequence, positions by the frame's own frame.
+// a pass over every frame that has not settled (end_prev == null: pass 0)
 __global__ __launch_bounds__(kHdThreads) void k_hdb_pass(const HdbFrame *__restrict__ fr, const uint32_t *__restrict__ blk_frame, const uint64_t *__restrict__ end_prev,
                                                          uint64_t *__restrict__ end_out, uint64_t *__restrict__ start, uint32_t *__restrict__ count,
                                                          uint32_t *__restrict__ changed, const uint32_t *__restrict__ done) {
-    extern __shared__ __align__(16) uint32_t hd_lds[];
     const uint32_t f = blk_frame[blockIdx.x];
     if (end_prev && done[f]) return;                       // a settled frame
     const HdbFrame &F = fr[f];
-    const HdStream &S = F.S;
-    const HdTables &T = F.T;
-    __shared__ unsigned long long s_end[kHdThreads], s_nstart[kHdThreads], s_nend[kHdThreads];
-    __shared__ uint32_t s_ncnt[kHdThreads];
-    __shared__ uint16_t s_list[kHdThreads];
-    __shared__ uint32_t s_n;
-    __shared__ unsigned long long s_pred0;
-    uint32_t *lut_s = hd_lds;
-    uint32_t *stage = hd_lds + (T.use1 ? (1u << kHdLut) : 0u);
-    const uint32_t tid = threadIdx.x, lb = blockIdx.x - F.blk0;
-    const uint64_t t0 = (uint64_t)lb * kHdThreads, t = t0 + tid, g = F.sub0 + t;   // t: in the frame, g: in the batch
-    const bool live = t < F.nsub;
-    const uint64_t lo = max(t * kHdSub, S.bit0), hi = min((t + 1) * kHdSub, S.nbits);
-    uint64_t my_start = 0, my_end = 0, base = 0;
-    uint32_t my_cnt = 0;
-    uint64_t pred0 = 0;
-    if (!end_prev) {
-        base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, lb);
-        if (live) {
-            uint64_t at = S.bit0;
-            if (t) {
-                at = t * kHdSub - S.warm;
-                uint32_t dummy = 0;
-                hd_run<false, false>(T, lut_s, stage, base, S.nbits, at, lo, dummy);
-            }
-            my_start = at;
-            hd_run<false, true>(T, lut_s, stage, base, S.nbits, at, hi, my_cnt);
-            my_end = at;
-        }
-        pred0 = my_start;
-    } else {
-        bool redo = false;
-        if (live) {
-            const uint64_t s = t ? end_prev[g - 1] : S.bit0;   // (the frame's first subsequence: its payload's first bit)
-            my_start = start[g]; my_end = end_prev[g]; my_cnt = count[g];
-            redo = s != my_start;
-            if (tid == 0) pred0 = s;
-            if (!redo) end_out[g] = my_end;
-        }
-        if (!__syncthreads_or(redo)) return;
-        base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, lb);
-    }
-    s_end[tid] = live ? my_end : ~0ull;
-    if (tid == 0) s_pred0 = pred0;
-    const uint64_t end_at_entry = my_end;
-    bool gave_up = true;
-    for (int round = 0; round < F.max_rounds; round++) {
-        if (tid == 0) s_n = 0;
-        __syncthreads();
-        const uint64_t pred = tid ? s_end[tid - 1] : s_pred0;
-        const bool redo = live && pred != my_start;
-        if (redo) s_list[atomicAdd(&s_n, 1u)] = (uint16_t)tid;
-        __syncthreads();
-        const uint32_t nl = s_n;
-        if (nl == 0) { gave_up = false; break; }
-        if (tid < nl) {
-            const uint32_t j = s_list[tid];
-            const uint64_t tj = t0 + j, hj = min((tj + 1) * kHdSub, S.nbits);
-            uint64_t at = j ? s_end[j - 1] : s_pred0;
-            uint32_t cn = 0;
-            s_nstart[j] = at;
-            hd_run<false, true>(T, lut_s, stage, base, S.nbits, at, hj, cn);
-            s_nend[j] = at;
-            s_ncnt[j] = cn;
-        }
-        __syncthreads();
-        if (redo) { my_start = s_nstart[tid]; my_end = s_nend[tid]; my_cnt = s_ncnt[tid]; s_end[tid] = my_end; }
-    }
-    if (!live) return;
-    start[g] = my_start;
-    end_out[g] = my_end;
-    count[g] = my_cnt;
-    if (end_prev && (my_end != end_at_entry || gave_up)) changed[f] = 1u;
+    hd_pass_block<false>(F.S, F.T, blockIdx.x - F.blk0, F.sub0, F.nsub, end_prev, end_out, start, count, &changed[f], F.max_rounds, 0u, 0u, nullptr, nullptr);
 }
 
 // after a check: a frame none of whose ends moved is settled for good
@@ -1054,54 +986,13 @@ __global__ __launch_bounds__(256) void k_hdb_settle(uint32_t *__restrict__ chang
     }
 }
 
-// k_hd_write<false, 1> for a batch: the settled frames' symbols (frame f's symbol index = off[g] - off[sub0])
+// the settled frames' symbols
 __global__ __launch_bounds__(kHdThreads) void k_hdb_write(const HdbFrame *__restrict__ fr, const uint32_t *__restrict__ blk_frame, const uint64_t *__restrict__ start,
                                                           const uint64_t *__restrict__ off, const uint32_t *__restrict__ done) {
-    extern __shared__ __align__(16) uint32_t hd_lds[];
     const uint32_t f = blk_frame[blockIdx.x];
     if (!done[f]) return;
     const HdbFrame &F = fr[f];
-    const HdStream &S = F.S;
-    const HdTables &T = F.T;
-    uint32_t *lut_s = hd_lds;
-    uint32_t *stage = hd_lds + (T.use1 ? (1u << kHdLut) : 0u);
-    const uint32_t lb = blockIdx.x - F.blk0;
-    const uint64_t t = (uint64_t)lb * kHdThreads + threadIdx.x, g = F.sub0 + t;
-    const uint64_t base = hd_stage_at(S, T.use1 ? T.lut1 : nullptr, lut_s, stage, lb);
-    if (t >= F.nsub) return;
-    const uint64_t hi = min((t + 1) * kHdSub, S.nbits), nsyms = F.nsyms;
-    uint64_t at = start[g], idx = off[g] - off[F.sub0], widx = idx;
-    if (at >= hi) return;
-    uint8_t *rgb = F.out;
-    HdBits<false> B;
-    B.seek(stage, (uint32_t)(at - base));
-    auto next = [&](uint32_t &key) -> bool {
-        if (at >= hi || widx >= nsyms) return false;
-        const HdSym sy = hd_lookup<true>(T, lut_s, B.window());
-        if (at + sy.len > S.nbits) { at = hi; return false; }
-        at += sy.len;
-        B.skip(sy.len);
-        widx++;
-        key = sy.key;
-        return true;
-    };
-    auto put1 = [&](uint32_t key) {
-        rgb[3 * idx] = (uint8_t)(key >> 16); rgb[3 * idx + 1] = (uint8_t)(key >> 8); rgb[3 * idx + 2] = (uint8_t)key;
-        idx++;
-    };
-    uint32_t k0, k1, k2, k3;
-    while ((idx & 3) && next(k0)) put1(k0);
-    for (;;) {
-        if (!next(k0)) break;
-        if (!next(k1)) { put1(k0); break; }
-        if (!next(k2)) { put1(k0); put1(k1); break; }
-        if (!next(k3)) { put1(k0); put1(k1); put1(k2); break; }
-        uint32_t *dst = reinterpret_cast<uint32_t *>(rgb + 3 * idx);   // (idx is a multiple of 4 and out 4-byte aligned)
-        dst[0] = ((k0 >> 16) & 255) | (((k0 >> 8) & 255) << 8) | ((k0 & 255) << 16) | (((k1 >> 16) & 255) << 24);
-        dst[1] = ((k1 >> 8) & 255) | ((k1 & 255) << 8) | (((k2 >> 16) & 255) << 16) | (((k2 >> 8) & 255) << 24);
-        dst[2] = (k2 & 255) | (((k3 >> 16) & 255) << 8) | (((k3 >> 8) & 255) << 16) | ((k3 & 255) << 24);
-        idx += 4;
-    }
+    hd_write_block<false, 1>(F.S, F.T, blockIdx.x - F.blk0, F.sub0, off[F.sub0], F.nsub, start, off, F.nsyms, F.out, nullptr, nullptr);
 }
 
 // per frame: the symbols its payload holds and whether it settled (res[2 f], res[2 f + 1])
@@ -1142,13 +1033,8 @@ int huff_decode_batch_dev(Ctx *c, std::vector<HdBatchFrame> &fv) {
         F.sub0 = nsub_all;
         F.blk0 = nblk;
         if (n == 1) continue;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(b.payload);
-        F.S.w = reinterpret_cast<const uint32_t *>(a & ~uintptr_t(3));
-        F.S.bit0 = (a & 3) * 8;
-        F.S.nbits = F.S.bit0 + b.payload_bytes * 8;
-        F.S.nwords = ceil_div(F.S.nbits, 32);
-        F.S.warm = b.payload_bytes * 8 >= b.nsyms * 12 ? 384 : 128;   // (as huff_decode_tables_dev)
-        F.T.bits2 = lt.max_len > (uint32_t)kHdLut ? std::min<uint32_t>(lt.max_len, 18u) : 0u;
+        F.S = hd_stream(b.payload, b.payload_bytes, b.nsyms);
+        F.T.bits2 = hd_lut2_bits(lt.max_len, 18u);   // (no larger second table and no third tables here)
         F.T.use1 = hd_use_first_table(b.payload_bytes * 8, b.nsyms, F.T.bits2) ? 1u : 0u;
         lut2_at[f] = lut2_bytes;
         if (F.T.bits2) { lut2_bytes += 8ull << F.T.bits2; lut2_grid = std::max(lut2_grid, (1u << F.T.bits2) / 256); }
