@@ -1,7 +1,7 @@
 """zip(dict) and hilbert-zip on the GPU against the CPU restatement of the reference's dictionary coder (tests/zip_dict_ref.py / .c):
 byte-exact streams, images back, the reference's verdict on hostile streams.  Each image is the smallest that reaches the code it
 names (the byte positions come from the restatement and are asserted as properties: which side of the hand-over, how long the longest
-entry)."""
+entry).  The edges of those code paths -- the thresholds the kernels switch on -- are tests/test_zip_dict_edges.py's."""
 import struct
 
 import numpy as np
