@@ -8,6 +8,6 @@ cniic_amd/csrc/).  This package is the thin host-side mirror of the reference's 
 HIP library is missing.
 """
 from ._lib import CniicError, Context, lib, lib_path  # noqa: F401
-from .codec import AnyCodec, Codec, HilbertRleApprox, HilbertZip  # noqa: F401
+from .codec import AnyCodec, Codec, HilbertRleApprox, HilbertZip, ZipBack  # noqa: F401
 
-__all__ = ["AnyCodec", "Codec", "Context", "CniicError", "HilbertRleApprox", "HilbertZip", "lib", "lib_path"]
+__all__ = ["AnyCodec", "Codec", "Context", "CniicError", "HilbertRleApprox", "HilbertZip", "ZipBack", "lib", "lib_path"]

@@ -37,6 +37,8 @@ SYMBOLS = [
     "cniic_hilbert_rle_approx_encode", "cniic_synth_image",
     "cniic_codec_encode_batch_var", "cniic_mse_batch_var", "cniic_codec_measure_batch", "cniic_codec_parse_f64",
     "cniic_zip_dict_encode", "cniic_zip_dict_decode", "cniic_zip_dict_dims", "cniic_hilbert_zip_encode", "cniic_hilbert_zip_decode",
+    "cniic_zip_back_encode", "cniic_zip_back_decode", "cniic_zip_back_dims", "cniic_zip_back_image_encode", "cniic_zip_back_image_decode",
+    "cniic_zip_back_image_encode_batch_var", "cniic_zip_back_image_decode_batch",
 ]
 
 
@@ -446,6 +448,107 @@ class Context:
             return rc, None
         return rc, out[:w * h].reshape(h, w, 3)
 
+    # ---- the look-back coder
+    def zip_back_encode(self, data, n=None, out=None, allow=()):
+        """cniic_zip_back_encode: data = bytes / numpy array (host), or a device tensor / address with n given.
+        -> (rc, bytes) when out is None, else (rc, length; with CAPACITY: the bytes needed)"""
+        if isinstance(data, (bytes, bytearray)):
+            data = np.frombuffer(bytes(data), np.uint8)
+        if n is None:
+            n = data.numel() if hasattr(data, "numel") else data.size
+        own = out is None
+        if own:
+            cap = n + n // 4 + 16
+            out = np.empty(cap, np.uint8)
+        else:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_zip_back_encode(self.h, _ptr(data) if n else None, C.c_uint64(n), _ptr(out), C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
+
+    def zip_back_decode(self, data, n=None, out=None, cap=None, allow=()):
+        """cniic_zip_back_decode -> (rc, bytes) when out is None (cap: the most bytes the text may have, default 64 MiB), else (rc, length;
+        with CAPACITY: the bytes needed)"""
+        if isinstance(data, (bytes, bytearray)):
+            data = np.frombuffer(bytes(data), np.uint8)
+        if n is None:
+            n = data.numel() if hasattr(data, "numel") else data.size
+        own = out is None
+        if own:
+            cap = (64 << 20) if cap is None else cap
+            out = np.empty(max(cap, 1), np.uint8)
+        elif cap is None:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_zip_back_decode(self.h, _ptr(data) if n else None, C.c_uint64(n), _ptr(out), C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
+
+    def zip_back_image_encode(self, img, w=None, h=None, out=None, allow=()):
+        """cniic_zip_back_image_encode.  img: HxWx3 uint8 numpy array, or a device tensor / address with w,h given.
+        -> (rc, bytes) when out is None, else (rc, length)"""
+        if isinstance(img, np.ndarray):
+            img = np.ascontiguousarray(img, np.uint8)
+            h, w = img.shape[:2]
+        own = out is None
+        if own:
+            cap = 14 * w * h + 32
+            out = np.empty(cap, np.uint8)
+        else:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        rc = self._check(self._L.cniic_zip_back_image_encode(self.h, _ptr(img), C.c_uint32(w), C.c_uint32(h), _ptr(out), C.c_uint64(cap), C.byref(ln)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b"")
+        return rc, ln.value
+
+    def zip_back_image_decode(self, data, allow=()):
+        """cniic_zip_back_image_decode of a host stream -> (rc, HxWx3 image or None)"""
+        raw = np.frombuffer(bytes(data), np.uint8)
+        dims = zip_back_dims(raw)
+        if dims is None:
+            return DECODE, None
+        w, h = dims
+        if w * h > (1 << 28):
+            return CAPACITY, None
+        out = np.zeros((max(w * h, 1), 3), np.uint8)
+        cw, ch = C.c_uint32(0), C.c_uint32(0)
+        rc = self._check(self._L.cniic_zip_back_image_decode(self.h, _ptr(raw), C.c_uint64(raw.size), _ptr(out), C.c_uint64(out.size), C.byref(cw),
+                                                             C.byref(ch)), allow)
+        if rc != OK:
+            return rc, None
+        return rc, out[:w * h].reshape(h, w, 3)
+
+    def zip_back_image_decode_into(self, data, nbytes, out, allow=()):
+        """cniic_zip_back_image_decode with caller-owned buffers (device tensors, numpy arrays or addresses) -> (rc, w, h)"""
+        cap = out.numel() if hasattr(out, "numel") else out.size
+        cw, ch = C.c_uint32(0), C.c_uint32(0)
+        rc = self._check(self._L.cniic_zip_back_image_decode(self.h, _ptr(data), C.c_uint64(nbytes), _ptr(out), C.c_uint64(cap), C.byref(cw), C.byref(ch)), allow)
+        return rc, cw.value, ch.value
+
+    def zip_back_encode_batch_var(self, images, offs, ws, hs, out, stride, allow=()):
+        """cniic_zip_back_image_encode_batch_var: the layout of encode_batch_var -> (rc, list of lengths, list of per-image status codes)"""
+        F = len(offs)
+        n = max(F, 1)
+        off = (C.c_uint64 * n)(*[int(x) for x in offs])
+        w = (C.c_uint32 * n)(*[int(x) for x in ws])
+        h = (C.c_uint32 * n)(*[int(x) for x in hs])
+        lens, rcs = (C.c_uint64 * n)(), (C.c_int32 * n)()
+        rc = self._check(self._L.cniic_zip_back_image_encode_batch_var(self.h, _ptr(images), off, w, h, C.c_uint32(F), _ptr(out), C.c_uint64(stride), lens, rcs), allow)
+        return rc, [int(lens[f]) for f in range(F)], [int(rcs[f]) for f in range(F)]
+
+    def zip_back_decode_batch(self, streams, stride, lens, F, out, img_stride, allow=()):
+        """cniic_zip_back_image_decode_batch: the layout of decode_batch -> (rc, list of widths, list of heights, list of per-frame status codes)"""
+        n = max(F, 1)
+        ln = (C.c_uint64 * n)(*[int(x) for x in lens])
+        ws, hs, rcs = (C.c_uint32 * n)(), (C.c_uint32 * n)(), (C.c_int32 * n)()
+        rc = self._check(self._L.cniic_zip_back_image_decode_batch(self.h, _ptr(streams), C.c_uint64(stride), ln, C.c_uint32(F), _ptr(out), C.c_uint64(img_stride),
+                                                                   ws, hs, rcs), allow)
+        return rc, [int(ws[f]) for f in range(F)], [int(hs[f]) for f in range(F)], [int(rcs[f]) for f in range(F)]
+
     def encode_batch(self, expr, frames, w, h, F, out, stride, seed=0, max_iters=0, flags=0, allow=()):
         """cniic_codec_encode_batch: F images (one contiguous [F][h][w][3] buffer), each encoded on its own (its own palette), image f's
         stream at out[f * stride:].  -> (rc, list of F lengths, list of F per-image status codes, list of F stats dicts)"""
@@ -568,6 +671,14 @@ def zip_dict_dims(data):
     raw = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
     w, h = C.c_uint32(0), C.c_uint32(0)
     rc = lib().cniic_zip_dict_dims(_ptr(raw) if raw.size else None, C.c_uint64(raw.size), C.byref(w), C.byref(h))
+    return (w.value, h.value) if rc == OK else None
+
+
+def zip_back_dims(data):
+    """cniic_zip_back_dims: (w, h) from the first symbols of a zip-back stream in host memory, or None"""
+    raw = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    rc = lib().cniic_zip_back_dims(_ptr(raw) if raw.size else None, C.c_uint64(raw.size), C.byref(w), C.byref(h))
     return (w.value, h.value) if rc == OK else None
 
 

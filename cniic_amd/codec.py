@@ -10,9 +10,12 @@
     HilbertRleApprox(4.0)                   # the same codec for a caller that holds d as a float
     AnyCodec.from_str("zip(dict)")          # the dictionary coder over the serialised image
     HilbertZip()                            # Hilbert { compress: Zip }: not an expression here, a class of its own
+    ZipBack()                               # Zip::Back, the look-back coder: likewise
 """
 import math
 from decimal import Decimal
+
+import numpy as np
 
 from . import _lib
 
@@ -211,3 +214,62 @@ class HilbertZip(Codec):
 
     def is_lossless(self):
         return True               # :92
+
+
+class ZipBack(Codec):
+    """Zip::Back (src/codec/zipc.rs:14-48): the look-back coder (src/zip/back.rs) over the dimensions and the 11-byte records of the
+    pixels, row by row.  `zip(back)` is not an expression of this library: encode and decode go through cniic_zip_back_image_encode /
+    cniic_zip_back_image_decode, batches through cniic_zip_back_image_encode_batch_var / _decode_batch (one workgroup per image).
+    encode raises CniicError(UNSUPPORTED) for an image on which the reference panics (a flat stretch of about 3000 pixels)."""
+
+    def __init__(self, ctx=None):
+        self.expr = None
+        self._ctx = ctx
+        self.last_stats = None
+
+    def encode(self, img, **kw):
+        rc, data = self.ctx.zip_back_image_encode(img, **kw)
+        return data
+
+    def decode(self, data):
+        rc, img = self.ctx.zip_back_image_decode(data, allow=(_lib.DECODE,))
+        return img if rc == _lib.OK else None
+
+    def encode_batch(self, imgs):
+        """the streams of a list of HxWx3 images of any sizes, in one call; None for an image that cannot be encoded"""
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        if not imgs:
+            return []
+        offs = np.concatenate([[0], np.cumsum([im.size for im in imgs])])[:-1]
+        blob = np.concatenate([im.reshape(-1) for im in imgs]) if sum(im.size for im in imgs) else np.zeros(1, np.uint8)
+        stride = max(14 * im.shape[0] * im.shape[1] + 32 for im in imgs)
+        out = np.empty(stride * len(imgs), np.uint8)
+        rc, lens, rcs = self.ctx.zip_back_encode_batch_var(blob, offs, [im.shape[1] for im in imgs], [im.shape[0] for im in imgs], out, stride,
+                                                           allow=(_lib.UNSUPPORTED,))
+        return [out[f * stride:f * stride + lens[f]].tobytes() if rcs[f] == _lib.OK else None for f in range(len(imgs))]
+
+    def decode_batch(self, streams):
+        """the images of a list of streams, in one call; None where a stream does not decode"""
+        streams = [bytes(s) for s in streams]
+        if not streams:
+            return []
+        dims = [_lib.zip_back_dims(s) for s in streams]
+        stride = max(max(len(s) for s in streams), 1)
+        img_stride = max([3 * d[0] * d[1] for d in dims if d is not None and d[0] * d[1] <= (1 << 28)] + [1])
+        blob = np.zeros(stride * len(streams), np.uint8)
+        for f, s in enumerate(streams):
+            blob[f * stride:f * stride + len(s)] = np.frombuffer(s, np.uint8)
+        out = np.zeros(img_stride * len(streams), np.uint8)
+        rc, ws, hs, rcs = self.ctx.zip_back_decode_batch(blob, stride, [len(s) for s in streams], len(streams), out, img_stride,
+                                                         allow=(_lib.DECODE, _lib.CAPACITY))
+        return [out[f * img_stride:f * img_stride + 3 * ws[f] * hs[f]].reshape(hs[f], ws[f], 3).copy() if rcs[f] == _lib.OK else None
+                for f in range(len(streams))]
+
+    def measure(self, imgs, **kw):
+        raise NotImplementedError("zip-back has no expression: cniic_codec_measure_batch cannot name it")
+
+    def name(self):
+        return "zip-back"         # zipc.rs:53
+
+    def is_lossless(self):
+        return True               # :57-59

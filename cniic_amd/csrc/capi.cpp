@@ -952,6 +952,67 @@ int32_t cniic_hilbert_zip_decode(cniic_ctx *c, const uint8_t *bytes, uint64_t n,
     return decode_hilbert_zip(c, bytes, n, rgb, cap, w, h);
 }
 
+// ------------------------------------------------------------------ the look-back coder (zipback.cpp, k_zipback.hip)
+int32_t cniic_zip_back_encode(cniic_ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!bytes && n) || (!out && n)) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_encode: null argument");
+    *len = 0;
+    if (!n) return CNIIC_OK;   // (no input, no symbol: back.rs:727-729)
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, bytes, n));
+    return zip_back_encode_text(c, in.d, n, out, cap, len);
+}
+
+int32_t cniic_zip_back_decode(cniic_ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!bytes && n) || (!out && cap)) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_decode: null argument");
+    *len = 0;
+    if (!n) return CNIIC_OK;
+    return zip_back_decode_bytes(c, bytes, n, out, cap, len);
+}
+
+int32_t cniic_zip_back_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint32_t *h) {
+    if ((!bytes && n) || !w || !h) return CNIIC_ERR_BAD_ARG;
+    return zip_back_dims(bytes, n, n, w, h);
+}
+
+int32_t cniic_zip_back_image_encode(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_image_encode: null argument");
+    const uint64_t off = 0;
+    return encode_zip_back_batch(c, rgb, &off, &w, &h, 1, out, cap, len, nullptr);
+}
+
+int32_t cniic_zip_back_image_decode(cniic_ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!bytes || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_image_decode: null argument");
+    return decode_zip_back_batch(c, bytes, 0, &n, 1, rgb, cap, w, h, nullptr);
+}
+
+int32_t cniic_zip_back_image_encode_batch_var(cniic_ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                              uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!frames) return CNIIC_OK;
+    if (!img_off || !w || !h || !out || !lens) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_image_encode_batch_var: null argument");
+    for (uint32_t f = 0; f < frames; f++)
+        if (!rgb && (uint64_t)w[f] * h[f]) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_image_encode_batch_var: null images");
+    return encode_zip_back_batch(c, rgb, img_off, w, h, frames, out, stride, lens, rcs);
+}
+
+int32_t cniic_zip_back_image_decode_batch(cniic_ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames, uint8_t *rgb,
+                                          uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!frames) return CNIIC_OK;
+    if (!bytes || !lens || !w || !h || (!rgb && img_stride)) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_image_decode_batch: null argument");
+    return decode_zip_back_batch(c, bytes, stride, lens, frames, rgb, img_stride, w, h, rcs);
+}
+
 int32_t cniic_codec_encode_opts(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w,
                                 uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     LOCK(c);

@@ -84,6 +84,17 @@ int decode_zip_dict(Ctx *c, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_
 int encode_hilbert_zip(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
 int decode_hilbert_zip(Ctx *c, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap, uint32_t *w, uint32_t *h);
 
+// ---- zipback.cpp: the look-back coder (src/zip/back.rs) and its codec Zip::Back, a batch at a time (k_zipback.hip: one workgroup per stream)
+int zip_back_encode_text(Ctx *c, const uint8_t *text_d, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);   // text_d: HBM; out: host or device
+int zip_back_decode_bytes(Ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);    // the whole text; bytes / out: host or device
+// host memory: the first 8 bytes of the text of a stream of `total` bytes, of which the first `avail` are at bytes (64 are always enough)
+int zip_back_dims(const uint8_t *bytes, uint64_t avail, uint64_t total, uint32_t *w, uint32_t *h);
+// the layouts of cniic_codec_encode_batch_var / cniic_codec_decode_batch; rgb, out, bytes: host or device; the other arrays on the host
+int encode_zip_back_batch(Ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride,
+                          uint64_t *lens, int32_t *rcs);
+int decode_zip_back_batch(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, uint64_t img_stride, uint32_t *w,
+                          uint32_t *h, int32_t *rcs);
+
 // cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames of a batch decoded together (stream f at bytes + f *
 // stride, lens[f] bytes; image f to rgb + f * img_stride).  taken[f] = 1: frame f was decoded here (rcs[f], msgs[f], w[f], h[f]); 0: the
 // caller decodes it on its own (codec_decode).

@@ -710,8 +710,9 @@ constexpr uint64_t kZdSat = 1ull << 62;            // where the decoder's sums o
 constexpr uint64_t kZdLenClamp = 1ull << 38;       // ... and what a single text's length is cut to in the device table (no buffer is that long)
 __host__ __device__ inline uint32_t zd_hash(uint32_t key, uint32_t bits) { return (key * 2654435761u) >> (32 - bits); }
 // text = [w, h as u32 when dims] + 11 bytes per pixel (u64 3, r, g, b); and back: *first_bad_h = the first record whose length is not 3 (npx: none)
-int zd_serialize(Ctx *c, const uint8_t *px_d, uint64_t npx, bool dims, uint32_t w, uint32_t h, uint8_t *text_d);
-int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, uint64_t *first_bad_h);
+// (stage: the stage timer's name -- zip(back) shares both kernels and times them under names of its own)
+int zd_serialize(Ctx *c, const uint8_t *px_d, uint64_t npx, bool dims, uint32_t w, uint32_t h, uint8_t *text_d, const char *stage = "zd_serialize");
+int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, uint64_t *first_bad_h, const char *stage = nullptr);
 // the greedy parse of text_d[P0, N) against the frozen trie (table_h: 2^bits edges, at most half of them used; max_entry: its longest text)
 struct ZdFrozen { uint64_t M = 0, nsyms = 0; uint32_t nchunks = 0; bool windowed = false; DevBuf sym, mark, chunk_off; };
 int zd_frozen_plan(Ctx *c, const uint8_t *text_d, uint64_t N, uint64_t P0, const ZdEdge *table_h, uint32_t bits, uint64_t max_entry, ZdFrozen *plan);  // counts the symbols (syncs)
@@ -720,6 +721,26 @@ int zd_frozen_emit(Ctx *c, const ZdFrozen *plan, uint16_t *out_d);   // nsyms sy
 struct ZdExpand { uint64_t nsym = 0, total = 0; uint32_t nchunks = 0; const uint8_t *syms_d = nullptr; DevBuf tab, chunk_off; };
 int zd_expand_plan(Ctx *c, const uint8_t *syms_d, uint64_t nsym, const uint64_t *tab_off_h, const uint64_t *tab_len_h, ZdExpand *plan);   // total (saturating; syncs)
 int zd_expand_copy(Ctx *c, const ZdExpand *plan, uint64_t base, uint8_t *out_d, uint64_t limit);
+
+// ---- k_zipback.hip: the look-back coder of zip(back) (src/zip/back.rs), one workgroup per stream; zipback.cpp has the host side ----
+// a stream of a call, in HBM: encode reads the text in[0, n) and writes symbols to out[0, cap); decode reads the symbols in[0, n) and
+// writes text to out[0, cap), whole symbols while fewer than `need` bytes are there
+struct ZbStream { const uint8_t *in; uint64_t n; uint8_t *out; uint64_t cap, need; };
+// where a stream stands between two launches.  encode: p bytes of text accepted, o bytes of stream made (counted behind cap too), e of
+// them an explicit run whose header is still open.  decode: p bytes of stream read, o bytes of text made.
+struct ZbState { uint64_t p, o; uint32_t e, status; };
+// status: over for good unless kZbRunning.  BadExplicit / BadLookback: encode -- a length of 32 768 or more, which the reference's header
+// cannot say (back.rs:45); decode -- an explicit symbol cut short (:97), a `back` behind the start of the text (:466)
+constexpr uint32_t kZbRunning = 0, kZbDone = 1, kZbBadExplicit = 2, kZbBadLookback = 3;
+// A launch takes every stream this far at most (NOTES.md L has the measurements): bytes of text accepted in encode; bytes of stream
+// read, and bytes of text made, in decode.
+constexpr uint64_t kZbEncodeSlice = 256 << 10, kZbDecodeSlice = 4 << 20;
+// the most text n bytes of stream can spell (a look-back of four bytes: 32 767), and the most stream n bytes of text can take (two
+// explicit bytes and a look-back of six: eight bytes for eight; two more for a last explicit symbol)
+inline uint64_t zb_text_bound(uint64_t n) { return n < (1ull << 48) ? (n / 4 + 1) * 32767 : ~0ull; }
+inline uint64_t zb_stream_bound(uint64_t n) { return n + n / 4 + 16; }
+int zb_encode_streams(Ctx *c, const ZbStream *streams_h, uint32_t F, ZbState *states_h);   // to the end of every stream (syncs)
+int zb_decode_streams(Ctx *c, const ZbStream *streams_h, uint32_t F, ZbState *states_h);
 
 // ---- k_hilbert.hip ----
 int hilbert_xy(Ctx *c, uint32_t w, uint32_t h, uint32_t *xy_d);

@@ -243,21 +243,22 @@ __global__ __launch_bounds__(kZdThreads) void k_zd_dec_copy(const uint8_t *__res
 }
 
 // ================================================================ host launchers
-int zd_serialize(Ctx *c, const uint8_t *px_d, uint64_t npx, bool dims, uint32_t w, uint32_t h, uint8_t *text_d) {
+int zd_serialize(Ctx *c, const uint8_t *px_d, uint64_t npx, bool dims, uint32_t w, uint32_t h, uint8_t *text_d, const char *stage) {
     const uint64_t nbytes = (dims ? 8 : 0) + 11 * npx;
     if (!nbytes) return CNIIC_OK;
     const uint64_t blocks = ceil_div(nbytes, kZdThreads);
     if (blocks > 0x7fffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "zip-dict: image too large");
-    ScopedKernelTimer timer(c, "zd_serialize");
+    ScopedKernelTimer timer(c, stage);
     hipLaunchKernelGGL(k_zd_serialize, dim3((uint32_t)blocks), dim3(kZdThreads), 0, c->stream, px_d, nbytes, dims ? 8u : 0u, w, h, text_d);
     CNIIC_HIP_TRY(c, hipGetLastError());
     timer.stop();
     return CNIIC_OK;
 }
 
-int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, uint64_t *first_bad_h) {
+int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, uint64_t *first_bad_h, const char *stage) {
     *first_bad_h = npx;
     if (!npx) return CNIIC_OK;
+    ScopedKernelTimer timer(c, stage ? stage : "", stage && c->timers);
     DevBuf bad;
     CNIIC_HIP_TRY(c, bad.alloc(8));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(bad.p, first_bad_h, 8, hipMemcpyHostToDevice, c->stream));
@@ -266,6 +267,7 @@ int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, ui
     CNIIC_HIP_TRY(c, hipGetLastError());
     CNIIC_HIP_TRY(c, hipMemcpyAsync(first_bad_h, bad.p, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    timer.stop();
     return CNIIC_OK;
 }
 

@@ -365,8 +365,8 @@ int32_t cniic_huf_size(int32_t sym_kind, const uint64_t *counts, uint64_t n, uin
  * "voronoi(2048)", "delta", "hilbert(rle)" = "hilbert(rle(0))", "hilbert(rle(4))" (src/codec.rs:41-59, FromStr impls of each
  * codec; hilbertc.rs:341-397 for the last two: rle(<f64>) takes what Rust's f64::from_str takes -- "4", "+4", "4.", ".5", "1e-3",
  * "inf", "-infinity", "nan" -- and its name() is "hilbert-rle" for d == 0, else "hilbert-rle-approx_" + d as Rust's Display prints
- * it, which can be longer than 300 characters), "zip(dict)" (zipc.rs:62-80: exactly that; name() "zip-dict", lossless; zip(back) is
- * not built, and hilbert(zip) is not an expression here: cniic_hilbert_zip_encode / _decode below).  Every entry point below that
+ * it, which can be longer than 300 characters), "zip(dict)" (zipc.rs:62-80: exactly that; name() "zip-dict", lossless; zip(back) and
+ * hilbert(zip) are built, but are not expressions here: cniic_zip_back_image_encode / cniic_hilbert_zip_encode and their kin below).  Every entry point below that
  * takes an expression takes all of them.  The dimensions of a zip(dict) stream are inside its compressed text: cniic_zip_dict_dims.
  * cniic_codec_parse describes a codec as (kind, u32 argument), which cannot carry the f64: it answers CNIIC_ERR_BAD_ARG for
  * hilbert(rle(d)) with d != 0.  cniic_codec_parse_f64 takes every expression; darg is d (0 for d == 0.0 and -0.0, for `hilbert(rle)`
@@ -439,6 +439,41 @@ int32_t cniic_zip_dict_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint3
  * before it gives up: what is malformed behind such a record is not reported here).  Host or device buffers. */
 int32_t cniic_hilbert_zip_encode(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
 int32_t cniic_hilbert_zip_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
+/* The look-back coder on plain bytes (zip::zip_back_encode / zip_back_decode, src/zip/back.rs:5-21).  The stream is what the reference
+ * writes: symbols headed by a little-endian u16 (bit 15 the kind, the low 15 bits len) -- explicit, len literal bytes behind it, or
+ * look-back, a little-endian u16 `back` behind it: min(len, back) bytes from `back` bytes before the end of the text so far.  Encode
+ * (Encoder::next_symbols, :148-212): with six bytes or more ahead, the longest common run of text[q, p) and text[p, n) over every q in
+ * [p - 65535, p - 6] whose six bytes equal those at p, the smallest q among equals; none: max(e, 2) more explicit bytes, e the explicit
+ * run so far, unprobed.  One workgroup walks a stream, its window in LDS, its lanes sharing each probe's scan of the window; a launch
+ * takes the text 256 KiB further.  Host or device buffers; CNIIC_ERR_CAPACITY with *len = bytes needed and nothing written behind cap.
+ * CNIIC_ERR_UNSUPPORTED where the reference panics: a look-back or an explicit symbol of 32 768 bytes or more, which the header cannot
+ * say (assert in compress_len, back.rs:45) -- a flat stretch of about 3000 pixels, or 32 768 bytes without any repetition at the probed
+ * places.  Decode (Decoder, :648-706): ends quietly where no whole header stands, at a look-back header without its `back`, and at a
+ * symbol that stands for no byte (explicit of length 0, look-back with len or back 0: Decoder::next then answers None, :657-664);
+ * CNIIC_ERR_DECODE where the reference panics: an explicit symbol with fewer than len bytes behind it (:97), a `back` greater than the
+ * text so far (:466).  No memory is allocated from a size a stream claims.
+ * Stage timers (cniic_last_kernel_time): "zb_encode", "zb_decode" (launches = the slices); the codec adds "zb_serialize", "zb_rebuild". */
+int32_t cniic_zip_back_encode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
+int32_t cniic_zip_back_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
+/* The dimensions of a zip-back stream: the first 8 bytes of its text, decoded from its first symbols (they lie within the first 64
+ * bytes).  HOST memory, no context.  CNIIC_ERR_DECODE when the stream is malformed before it has spelt 8 bytes, or ends there. */
+int32_t cniic_zip_back_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint32_t *h);
+/* Zip::Back (src/codec/zipc.rs:14-48; name "zip-back", lossless): the look-back coder over zip(dict)'s text -- (w, h) as two u32, then
+ * the 11-byte records (u64 3, r, g, b) of the pixels row by row.  Decode is lazy (zipc.rs:28-36): exactly 8 + 11 w h bytes of text are
+ * pulled, whole symbols as they are needed, and nothing behind the symbol that completes the last pixel is looked at; fewer bytes, or a
+ * pixel record whose length is not 3, is CNIIC_ERR_DECODE; cap < 3 w h is CNIIC_ERR_CAPACITY.  Host or device buffers. */
+int32_t cniic_zip_back_image_encode(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
+int32_t cniic_zip_back_image_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
+/* The harness's many-images loop (src/bench.rs:24-35) for Zip::Back: the layouts and the per-frame rcs of cniic_codec_encode_batch_var
+ * and cniic_codec_decode_batch (image f is w[f] x h[f] at rgb + img_off[f]; stream f at out + f * stride, its length in lens[f];
+ * decoded image f at rgb + f * img_stride; img_off, w, h, lens, rcs: HOST arrays).  Every frame is one workgroup of the same launches,
+ * whatever their number; stream, lens[f] and rcs[f] are what the single call gives for frame f, and a frame that fails (UNSUPPORTED,
+ * CAPACITY with lens[f] = bytes needed, DECODE) leaves the others as they are.  rcs may be NULL; the call returns the first failure
+ * (lowest f) with its message in cniic_last_error; frames == 0 returns CNIIC_OK. */
+int32_t cniic_zip_back_image_encode_batch_var(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h,
+                                              uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs);
+int32_t cniic_zip_back_image_decode_batch(cniic_ctx *ctx, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+                                          uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics.  zip(dict): the reader is lazy (zipc.rs:28-36) -- exactly
  * 8 + 11 w h bytes of text are pulled, whole pairs as they are needed, and nothing behind the pair that completes the last pixel is
  * looked at; fewer bytes, or a pixel record whose length is not 3, is CNIIC_ERR_DECODE. */
