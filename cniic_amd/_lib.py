@@ -17,6 +17,8 @@ SYM_RGB, SYM_SIGNED = 1, 2
 KIND_ZIP_DICT = 6   # cniic_codec_parse's kind of zip(dict)
 SYNTH_UNIFORM, SYNTH_PHOTO = 0, 1
 KM_BRUTE_FORCE, KM_PROFILE, KM_NO_SKIP = 1, 2, 4
+LIN_RECT, LIN_SMALL, LIN_LARGE = 0, 1, 2
+LIN_METHODS = {"rect": LIN_RECT, "small": LIN_SMALL, "large": LIN_LARGE}   # hilbert.rs:10-32
 OPT_SP_MIN_PIXELS, OPT_HUF_GPU_CODES_MIN, OPT_GPU_DECODE_MIN, OPT_DELTA_ROUTE, OPT_STAGE_TIMERS, OPT_FRAME_TREES_HOST, OPT_BATCH_STREAMS, OPT_KM_MAX_BLOCKS, OPT_KM_LOOP = range(1, 10)
 
 # every symbol include/cniic_hip.h declares (checked by tests/test_abi.py)
@@ -39,6 +41,7 @@ SYMBOLS = [
     "cniic_zip_dict_encode", "cniic_zip_dict_decode", "cniic_zip_dict_dims", "cniic_hilbert_zip_encode", "cniic_hilbert_zip_decode",
     "cniic_zip_back_encode", "cniic_zip_back_decode", "cniic_zip_back_dims", "cniic_zip_back_image_encode", "cniic_zip_back_image_decode",
     "cniic_zip_back_image_encode_batch_var", "cniic_zip_back_image_decode_batch",
+    "cniic_hilbert_linearize_count", "cniic_hilbert_linearize_as", "cniic_channel_diff_hist",
 ]
 
 
@@ -295,6 +298,36 @@ class Context:
         out = np.empty((h * w, 3), np.uint8)
         self._check(self._L.cniic_hilbert_linearize(self.h, _ptr(img), C.c_uint32(w), C.c_uint32(h), _ptr(out)))
         return out
+
+    def hilbert_linearize_as(self, img, method, w=None, h=None, out=None, allow=()):
+        """cniic_hilbert_linearize_as: method "rect" | "small" | "large" (or a CNIIC_LIN_* number).  img: HxWx3 uint8 numpy array, or a
+        device tensor / address with w, h given.  -> the (npx, 3) pixels when out is None, else (rc, npx) with out (numpy array, device
+        tensor) filled; with CAPACITY allowed: npx = the pixels needed"""
+        if isinstance(img, np.ndarray):
+            img = np.ascontiguousarray(img, np.uint8)
+            h, w = img.shape[:2]
+        m = LIN_METHODS[method] if isinstance(method, str) else int(method)
+        own = out is None
+        if own:
+            out = np.empty((max(linearize_count(m, w, h), 1), 3), np.uint8)
+        cap = (out.numel() if hasattr(out, "numel") else out.size) // 3
+        n = C.c_uint64(0)
+        rc = self._check(self._L.cniic_hilbert_linearize_as(self.h, C.c_int32(m), _ptr(img), C.c_uint32(w), C.c_uint32(h), _ptr(out), C.c_uint64(cap),
+                                                            C.byref(n)), allow)
+        if own:
+            return out[:n.value]
+        return rc, n.value
+
+    def channel_diff_hist(self, lin, npx=None, out=None):
+        """cniic_channel_diff_hist: lin = (n, 3) uint8 numpy array, or a device tensor / address (npx: its pixels, default all of it)
+        -> int64 [3, 511] array, or `out` (a device tensor / numpy array of 3 x 511 64-bit words) filled"""
+        if isinstance(lin, np.ndarray):
+            lin = np.ascontiguousarray(lin, np.uint8)
+        if npx is None:
+            npx = (lin.numel() if hasattr(lin, "numel") else lin.size) // 3
+        res = np.zeros((3, 511), np.int64) if out is None else out
+        self._check(self._L.cniic_channel_diff_hist(self.h, _ptr(lin) if npx else None, C.c_uint64(npx), _ptr(res)))
+        return res
 
     def hilbert_delta(self, img):
         img = np.ascontiguousarray(img, np.uint8)
@@ -664,6 +697,54 @@ class Context:
             out = np.empty((h, w, 3), np.uint8)
         self._check(self._L.cniic_synth_image(self.h, kind, C.c_uint64(seed), C.c_uint32(w), C.c_uint32(h), _ptr(out)))
         return out
+
+
+def linearize_count(method, w, h):
+    """cniic_hilbert_linearize_count: pixels `method` ("rect" | "small" | "large", or a CNIIC_LIN_* number) yields for a w x h image"""
+    m = LIN_METHODS[method] if isinstance(method, str) else int(method)
+    n = C.c_uint64(0)
+    rc = lib().cniic_hilbert_linearize_count(C.c_int32(m), C.c_uint32(w), C.c_uint32(h), C.byref(n))
+    if rc != OK:
+        raise CniicError(rc, "linearize_count(%r, %d, %d)" % (method, w, h))
+    return n.value
+
+
+def hilbert_linearize(img, method="rect", ctx=None):
+    """hilbert::linearize_rect / linearize_small / linearize_large (hilbert.rs:10-32) of an HxWx3 uint8 image: a numpy array -> the
+    (npx, 3) numpy array of its pixels in that order; a device tensor -> a device tensor.  ctx: a Context, or None for one on device 0"""
+    own = ctx is None
+    if own:
+        ctx = Context(0)
+    try:
+        if isinstance(img, np.ndarray):
+            return ctx.hilbert_linearize_as(img, method)
+        import torch
+        img = img.contiguous()
+        h, w = int(img.shape[0]), int(img.shape[1])
+        out = torch.empty((max(linearize_count(method, w, h), 1), 3), dtype=torch.uint8, device=img.device)
+        torch.cuda.synchronize(img.device)   # (the context runs on a stream of its own)
+        _, n = ctx.hilbert_linearize_as(img, method, w, h, out)
+        return out[:n]
+    finally:
+        if own:
+            ctx.close()
+
+
+def channel_diff_hist(lin, ctx=None):
+    """counts[c][v + 255] = how often channel c steps by v between neighbours of the linear RGB stream `lin` ((n, 3) uint8: numpy array or
+    device tensor) -> int64 [3, 511] numpy array (scripts/experiments/hilbert_distribution.py)"""
+    own = ctx is None
+    if own:
+        ctx = Context(0)
+    try:
+        if not isinstance(lin, np.ndarray):
+            import torch
+            lin = lin.contiguous()
+            torch.cuda.synchronize(lin.device)
+        return ctx.channel_diff_hist(lin)
+    finally:
+        if own:
+            ctx.close()
 
 
 def zip_dict_dims(data):

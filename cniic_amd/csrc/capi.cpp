@@ -786,6 +786,46 @@ int32_t cniic_hilbert_linearize(cniic_ctx *c, const uint8_t *rgb, uint32_t w, ui
     return CNIIC_OK;
 }
 
+// hilbert.rs:10-32: linearize_rect / linearize_small / linearize_large (k_linearize.hip)
+int32_t cniic_hilbert_linearize_count(int32_t method, uint32_t w, uint32_t h, uint64_t *npx) { return linearize_count(method, w, h, npx); }
+
+int32_t cniic_hilbert_linearize_as(cniic_ctx *c, int32_t method, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out_rgb, uint64_t cap_px,
+                                   uint64_t *npx) {
+    LOCK(c);
+    c->ktimes.clear();
+    uint64_t need = 0;
+    if (linearize_count(method, w, h, &need) != CNIIC_OK)
+        return c->fail(CNIIC_ERR_BAD_ARG, "hilbert_linearize_as: unknown method %d, or a %ux%u image is too large", method, w, h);
+    if (npx) *npx = need;
+    if (cap_px < need)
+        return c->fail(CNIIC_ERR_CAPACITY, "hilbert_linearize_as: %llu pixels, capacity %llu", (unsigned long long)need, (unsigned long long)cap_px);
+    if (!need) return CNIIC_OK;
+    if (!rgb || !out_rgb) return c->fail(CNIIC_ERR_BAD_ARG, "hilbert_linearize_as: null argument");
+    In<uint8_t> in;
+    Out<uint8_t> o;
+    CNIIC_TRY(in.bind(c, rgb, 3 * (uint64_t)w * h));
+    CNIIC_TRY(o.bind(c, out_rgb, 3 * need));
+    CNIIC_TRY(linearize_as(c, method, in.d, w, h, o.d));
+    CNIIC_TRY(o.finish(c));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+// scripts/experiments/hilbert_distribution.py: how often each neighbour difference occurs along a linear stream, per channel
+int32_t cniic_channel_diff_hist(cniic_ctx *c, const uint8_t *lin_rgb, uint64_t npx, uint64_t *counts) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!counts || (npx && !lin_rgb)) return c->fail(CNIIC_ERR_BAD_ARG, "channel_diff_hist: null argument");
+    In<uint8_t> in;
+    Out<uint64_t> o;
+    CNIIC_TRY(in.bind(c, lin_rgb, 3 * npx));
+    CNIIC_TRY(o.bind(c, counts, 3 * 511));
+    CNIIC_TRY(channel_diff_hist(c, in.d, npx, o.d));
+    CNIIC_TRY(o.finish(c));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
 int32_t cniic_hilbert_delta(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t *syms) {
     LOCK(c);
     c->ktimes.clear();

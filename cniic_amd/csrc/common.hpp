@@ -742,6 +742,11 @@ inline uint64_t zb_stream_bound(uint64_t n) { return n + n / 4 + 16; }
 int zb_encode_streams(Ctx *c, const ZbStream *streams_h, uint32_t F, ZbState *states_h);   // to the end of every stream (syncs)
 int zb_decode_streams(Ctx *c, const ZbStream *streams_h, uint32_t F, ZbState *states_h);
 
+// ---- k_linearize.hip: hilbert.rs:10-32 linearize_rect / _small / _large, and the per-channel difference histogram of a linear stream ----
+int linearize_count(int32_t method, uint32_t w, uint32_t h, uint64_t *npx);   // host only: pixels the method yields (CNIIC_LIN_*)
+int linearize_as(Ctx *c, int32_t method, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out_d);   // out_d: linearize_count pixels
+int channel_diff_hist(Ctx *c, const uint8_t *lin_d, uint64_t npx, uint64_t *counts_d);   // counts_d: u64[3][511]
+
 // ---- k_hilbert.hip ----
 int hilbert_xy(Ctx *c, uint32_t w, uint32_t h, uint32_t *xy_d);
 int hilbert_linearize(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out_d);

@@ -343,6 +343,29 @@ int32_t cniic_hilbert_xy(cniic_ctx *ctx, uint32_t w, uint32_t h, uint32_t *xy);
 int32_t cniic_ctx_set_scan(cniic_ctx *ctx, uint32_t w, uint32_t h, const uint32_t *xy);
 /* hilbert::linearize (src/hilbert.rs:10-12): pixels gathered in scan order. */
 int32_t cniic_hilbert_linearize(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out_rgb);
+/* The three linearisations `--special=hilbert` writes out (src/main.rs:23-55), by method:
+ *   CNIIC_LIN_RECT  (src/hilbert.rs:10-12)  out[d] = img(scan of w x h at d): w h pixels, cniic_hilbert_linearize's byte for byte
+ *   CNIIC_LIN_SMALL (src/hilbert.rs:15-22)  s = min(npot(w) >> 1, npot(h) >> 1), npot = u32::next_power_of_two: the scan of s x s over the
+ *                   top-left s x s pixels, s^2 pixels.  For w an exact power of two that is w / 2, not w (4 x 4 gives its 2 x 2 corner,
+ *                   a 1-wide image nothing: 0 pixels and CNIIC_OK) -- the reference's arithmetic, kept.
+ *   CNIIC_LIN_LARGE (src/hilbert.rs:25-32)  S = max(npot(w), npot(h)): the scan of S x S, only the positions with x < w && y < h kept, in
+ *                   their order: w h pixels.  The S^2 positions are not walked (a pixel's rank is computed from the curve's levels), unless
+ *                   the context holds an injected scan for exactly S x S, whose order is then followed position by position.
+ * "The scan of a x b" is what cniic_hilbert_xy answers on this context (an injected scan for exactly a x b included).
+ * Limits as everywhere here: w, h < 2^30 and w h < 2^32. */
+#define CNIIC_LIN_RECT  0
+#define CNIIC_LIN_SMALL 1
+#define CNIIC_LIN_LARGE 2
+/* host only, no context: pixels the method yields; CNIIC_ERR_BAD_ARG for an unknown method or dimensions beyond the limits */
+int32_t cniic_hilbert_linearize_count(int32_t method, uint32_t w, uint32_t h, uint64_t *npx);
+/* rgb, out_rgb: host or device memory; *npx = pixels written.  cap_px < needed: CNIIC_ERR_CAPACITY with *npx = needed and nothing written.
+ * Stage timers: lin_small, lin_large (launches: 1 on the computed route, 3 along an injected S x S scan). */
+int32_t cniic_hilbert_linearize_as(cniic_ctx *ctx, int32_t method, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out_rgb, uint64_t cap_px,
+                                   uint64_t *npx);
+/* scripts/experiments/hilbert_distribution.py: for a linear RGB stream of npx pixels, counts[c][v + 255] = number of i in 1 .. npx-1 with
+ * lin[i][c] - lin[i-1][c] == v, c = r, g, b; counts: u64[3][511], host or device.  npx <= 1: all zero; a channel's counts sum to npx - 1
+ * (pandas.diff drops the first element: no START zero, unlike the DiffStream below).  Stage timer: chan_diff_hist. */
+int32_t cniic_channel_diff_hist(cniic_ctx *ctx, const uint8_t *lin_rgb, uint64_t npx, uint64_t *counts);
 /* DiffStream over the Hilbert-ordered pixels (src/codec/hilbertc.rs:449-477): N packed
  * CNIIC_SYM_SIGNED keys. */
 int32_t cniic_hilbert_delta(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t *syms);

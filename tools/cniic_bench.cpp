@@ -13,6 +13,10 @@
 //   cniic_bench --codec=<expr> --one-call <image>...
 // loads all the images first (back to back in one device buffer) and hands the whole loop to ONE cniic_codec_measure_batch: the same
 // CSV, rows in argument order, the same exit status.
+//   cniic_bench --special=hilbert <image>...
+// the reference's other command (main.rs:23-55): per image the three linearisations of src/hilbert.rs:10-32 as CSV, one pixel per row, in
+// output/<file stem>.rect.hilbert.csv, .small.hilbert.csv and .large.hilbert.csv (under_output, main.rs:91-96: only the last extension
+// is replaced).  The header is "red,blue,green" as the reference writes it (main.rs:38); the rows are r,g,b.
 #include <sys/stat.h>
 #include <zlib.h>
 
@@ -178,7 +182,56 @@ static int run_one_call(const std::string &expr, const char *name, const std::ve
     return failures ? 1 : 0;
 }
 
+// --special=hilbert (main.rs:31-49)
+static int run_special_hilbert(const std::vector<std::string> &paths) {
+    cniic_ctx *ctx = nullptr;
+    if (cniic_ctx_create(0, nullptr, &ctx) != CNIIC_OK) { fprintf(stderr, "no usable MI355X\n"); return 1; }
+    mkdir("output", 0755);
+    int failures = 0;
+    static const struct { int32_t method; const char *name; } kMethods[3] = {{CNIIC_LIN_RECT, "rect"}, {CNIIC_LIN_SMALL, "small"}, {CNIIC_LIN_LARGE, "large"}};
+    for (const std::string &p : paths) {
+        Image im;
+        if (!parse_synth(p, im) && !read_png(p, im) && !read_ppm(p, im)) {
+            fprintf(stderr, "%s: cannot read image (PNG, binary PPM or synth:<P|U>:<w>x<h>[:seed])\n", p.c_str());
+            failures++;
+            continue;
+        }
+        if (im.synth) {
+            im.rgb.resize((size_t)im.w * im.h * 3);
+            if (cniic_synth_image(ctx, im.kind, im.seed, im.w, im.h, im.rgb.data()) != CNIIC_OK) { fprintf(stderr, "%s: %s\n", p.c_str(), cniic_last_error(ctx)); failures++; continue; }
+        }
+        // under_output: output/<file name>, its last extension replaced (a leading dot starts no extension)
+        std::string stem = p.substr(p.find_last_of('/') == std::string::npos ? 0 : p.find_last_of('/') + 1);
+        const size_t dot = stem.find_last_of('.');
+        if (dot != std::string::npos && dot > 0) stem.resize(dot);
+        for (const auto &m : kMethods) {
+            uint64_t npx = 0;
+            if (cniic_hilbert_linearize_count(m.method, im.w, im.h, &npx) != CNIIC_OK) { fprintf(stderr, "%s: image too large\n", p.c_str()); failures++; break; }
+            std::vector<uint8_t> lin(3 * npx + 1);
+            if (cniic_hilbert_linearize_as(ctx, m.method, im.rgb.data(), im.w, im.h, lin.data(), npx, &npx) != CNIIC_OK) {
+                fprintf(stderr, "%s: %s (%s)\n", p.c_str(), m.name, cniic_last_error(ctx));
+                failures++;
+                continue;
+            }
+            const std::string out_path = "output/" + stem + "." + m.name + ".hilbert.csv";
+            FILE *csv = fopen(out_path.c_str(), "w");
+            if (!csv) { perror(out_path.c_str()); failures++; continue; }
+            std::string text = "red,blue,green\n";
+            for (uint64_t i = 0; i < npx; i++) {
+                char row[16];
+                text.append(row, (size_t)snprintf(row, sizeof row, "%u,%u,%u\n", lin[3 * i], lin[3 * i + 1], lin[3 * i + 2]));
+                if (text.size() > (1u << 20)) { fwrite(text.data(), 1, text.size(), csv); text.clear(); }
+            }
+            fwrite(text.data(), 1, text.size(), csv);
+            fclose(csv);
+        }
+    }
+    cniic_ctx_destroy(ctx);
+    return failures ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--special=hilbert")) return run_special_hilbert(std::vector<std::string>(argv + 2, argv + argc));
     if (argc < 3 || strncmp(argv[1], "--codec=", 8) != 0) {
         fprintf(stderr, "Usage: cniic_bench --codec=<codec> [--one-call] [<img file>..]\nAvailable codecs:\n  hufman\n  cluster-colors(<ncolors>)\n  voronoi(<k>)\n  delta\n  hilbert(rle)\n");
         return 2;
