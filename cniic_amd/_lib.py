@@ -42,6 +42,7 @@ SYMBOLS = [
     "cniic_zip_back_encode", "cniic_zip_back_decode", "cniic_zip_back_dims", "cniic_zip_back_image_encode", "cniic_zip_back_image_decode",
     "cniic_zip_back_image_encode_batch_var", "cniic_zip_back_image_decode_batch",
     "cniic_hilbert_linearize_count", "cniic_hilbert_linearize_as", "cniic_channel_diff_hist",
+    "cniic_cc_finish_frames_var",
 ]
 
 
@@ -115,6 +116,9 @@ def lib():
         L.cniic_cc_unique.argtypes = [C.c_void_p]
         L.cniic_cc_label_bytes.restype = C.c_uint32
         L.cniic_cc_label_bytes.argtypes = [C.c_void_p]
+        L.cniic_cc_finish_frames_var.restype = C.c_int32
+        L.cniic_cc_finish_frames_var.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_uint64,
+                                                 C.POINTER(C.c_uint64), C.c_void_p]
         _lib = L
     return _lib
 

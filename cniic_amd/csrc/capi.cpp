@@ -709,6 +709,28 @@ int32_t cniic_cc_finish_frames(cniic_cc *cc, const uint8_t *rgb, uint32_t w, uin
     return cc_finish_frames(cc->s, in.d, w, h, frames, out, stride, lens, stats);
 }
 
+int32_t cniic_cc_finish_frames_var(cniic_cc *cc, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride,
+                                   uint64_t *lens, cniic_kmeans_stats *stats) {
+    if (!cc) return CNIIC_ERR_BAD_ARG;
+    cniic_ctx *c = static_cast<cniic_ctx *>(cc->c);
+    LOCK(c);
+    if (!cc->s->km) return c->fail(CNIIC_ERR_BAD_ARG, "the session has no K-means state yet (cniic_cc_image_create comes first)");
+    if (!rgb || !w || !h || !out || !lens || !frames) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: null argument");
+    uint64_t n = 0;
+    for (uint32_t f = 0; f < frames; f++) {
+        const uint64_t np = (uint64_t)w[f] * h[f];
+        if (!np) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: frame %u is %u x %u", f, w[f], h[f]);
+        if (__builtin_add_overflow(n, np, &n) || n > (~0ull) / 3) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: too many pixels");
+    }
+    if (stride & 3) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: the stride between streams must be a multiple of 4");   // (before the image is bound)
+    if (cc->s->sp_mode && cc->s->sp.npx != n)
+        return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: the session was opened on %llu pixels, the batch has %llu", (unsigned long long)cc->s->sp.npx,
+                       (unsigned long long)n);
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, n * 3));
+    return cc_finish_frames_var(cc->s, in.d, w, h, frames, out, stride, lens, stats);
+}
+
 void cniic_cc_destroy(cniic_cc *cc) {
     if (!cc) return;
     {

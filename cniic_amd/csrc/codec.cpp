@@ -433,6 +433,7 @@ int cc_prepare(Ctx *c, uint32_t *table_counts_d, uint32_t K, const cniic_kmeans_
     if (K == 0) return c->fail(CNIIC_ERR_BAD_ARG, "cluster-colors(0)");
     auto s = std::make_unique<CcSession>();
     s->c = c; s->K = K; s->table = table_counts_d;
+    s->counts_local = occ_d != nullptr || nshards == 1;
     CompactPlan plan;
     DevBuf cell_count;  // occupied bins per K-means colour cell, counted by the compaction on its way
     CNIIC_HIP_TRY(c, cell_count.alloc((uint64_t)kNumCells * 4));
@@ -666,31 +667,86 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     return rc_fin;
 }
 
-// A batch of F equally sized frames (contiguous in rgb_d) coded with ONE palette -- north_star config 4: the K-means ran over the
-// union of all the pixels (of all ranks); every frame is then its own Hufman stream (clusterc.rs:31-52 per frame: the reduced
-// frame's own histogram, tree and payload), written at out + f * stride.  One pass gives every pixel's label, one kernel the
-// pixels per (frame, cluster), the host builds the F small trees on a few threads and the F packs are enqueued back to back.
-int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
-                     cniic_kmeans_stats *stats) {
+// A batch of F frames (contiguous in rgb_d) coded with ONE palette -- north_star config 4: the K-means ran over the union of all the
+// pixels (of all ranks); every frame is then its own Hufman stream (clusterc.rs:31-52 per frame: the reduced frame's own histogram,
+// tree and payload), written at out + f * stride.  One pass gives every pixel's label, one kernel the pixels per (frame, cluster), the
+// trees are built by one kernel (or on a few host threads) and the F packs are enqueued back to back.
+//   wv == nullptr  F equally sized frames of w x h (cc_finish_frames): grids of (chunk, frame)
+//   wv, hv         frame f is wv[f] x hv[f] (cc_finish_frames_var): the host builds one table row per frame (FrameVar, common.hpp), uploads
+//                  it once, and every kernel runs a 1-D grid over the chunks of all frames.  Stage timers (when on): frames_var_*
+// Everything that does not depend on the frames' shapes is the same code for both.
+static int finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const uint32_t *wv, const uint32_t *hv, uint32_t F, uint8_t *out,
+                         uint64_t stride, uint64_t *lens, cniic_kmeans_stats *stats) {
     Ctx *c = s->c;
     const uint32_t K = s->K;
-    const uint64_t U = s->U, npf = (uint64_t)w * h, n = npf * F;
+    const bool var = wv != nullptr;
+    const char *who = var ? "cc_finish_frames_var" : "cc_finish_frames";
+    const uint64_t U = s->U, npf = var ? 0 : (uint64_t)w * h;
+    uint64_t n = npf * F;
     KmRgbwState *km = s->km;
     host_trace().mark("frames: enter");
-    if (!F || !npf) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames: empty batch");
-    if (stride & 3) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames: the stride between streams must be a multiple of 4");
-    if (s->sp_mode && s->sp.npx != n) return c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames: the session was opened on %llu pixels, the batch has %llu",
+    if (!F || (!var && !npf)) return c->fail(CNIIC_ERR_BAD_ARG, "%s: empty batch", who);
+    if (var) {
+        n = 0;
+        for (uint32_t f = 0; f < F; f++) {
+            const uint64_t np = (uint64_t)wv[f] * hv[f];
+            if (!np) return c->fail(CNIIC_ERR_BAD_ARG, "%s: frame %u is %u x %u", who, f, wv[f], hv[f]);
+            if (__builtin_add_overflow(n, np, &n)) return c->fail(CNIIC_ERR_BAD_ARG, "%s: too many pixels", who);
+        }
+    }
+    if (stride & 3) return c->fail(CNIIC_ERR_BAD_ARG, "%s: the stride between streams must be a multiple of 4", who);
+    if (s->sp_mode && s->sp.npx != n) return c->fail(CNIIC_ERR_BAD_ARG, "%s: the session was opened on %llu pixels, the batch has %llu", who,
                                                      (unsigned long long)s->sp.npx, (unsigned long long)n);
+    if (var && !s->sp_mode && s->counts_local) {  // a dense-table session knows its pixels as the sum of its colours' counts
+        DevBuf sum_d;
+        uint64_t opened = 0;
+        CNIIC_HIP_TRY(c, sum_d.alloc(8));
+        CNIIC_TRY(sum_u32_dev(c, s->weight_d.as<uint32_t>(), U, sum_d.as<uint64_t>()));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(&opened, sum_d.p, 8, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (opened != n) return c->fail(CNIIC_ERR_BAD_ARG, "%s: the session was opened on %llu pixels, the batch has %llu", who,
+                                        (unsigned long long)opened, (unsigned long long)n);
+    }
+    const bool wide = km_rgbw_is_wide(km);
+    const uint64_t lb = wide ? 2 : 1;
+    // ---- frames of any sizes: the frame table.  Label bases on 16-byte boundaries (16 elements, for labels of either width); when every
+    // run already starts on one where the pixel-label kernels write it, the bases are those and nothing is copied
+    std::vector<FrameVar> ft;
+    uint64_t lab_total = 0;      // elements of the aligned label buffer
+    uint32_t chunks = 0, hblocks = 0;
+    bool runs_aligned = true;
+    if (var) {
+        ft.resize(F);
+        uint64_t src = 0, ch = 0, hb = 0;
+        for (uint32_t f = 0; f < F; f++) {
+            const uint64_t np = (uint64_t)wv[f] * hv[f];
+            if ((src * lb) & 15) runs_aligned = false;
+            ft[f] = FrameVar{np, lab_total, src, (uint32_t)ch, (uint32_t)hb, wv[f], hv[f]};
+            src += np;
+            lab_total += (np + 15) & ~15ull;
+            ch += ceil_div(np, kFrameVarChunk);
+            hb += ceil_div(np, kFrameVarHistSpan);
+            if (ch > 0x7fffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "%s: too many pixels for one batch", who);
+        }
+        chunks = (uint32_t)ch;
+        hblocks = (uint32_t)hb;
+        if (runs_aligned)
+            for (uint32_t f = 0; f < F; f++) ft[f].lab_base = ft[f].src_base;
+    }
     std::vector<uint8_t> cent(3 * (size_t)K);
     std::vector<uint64_t> members(K), wsum(K);
     cniic_kmeans_stats st{};
     CNIIC_TRY(km_rgbw_result_begin(km));
-    const bool wide = km_rgbw_is_wide(km);
-    const uint64_t lb = wide ? 2 : 1;
-    DevBuf lab_d, key2label, pixlab, pixlab_al, cnt_d;
+    DevBuf lab_d, key2label, pixlab, pixlab_al, cnt_d, ft_d;
     host_trace().mark("frames: result_begin");
     CNIIC_HIP_TRY(c, pixlab.alloc(n * lb + 16));
     host_trace().mark("frames: alloc pixel labels");
+    if (var) {
+        CNIIC_HIP_TRY(c, ft_d.alloc((uint64_t)F * sizeof(FrameVar)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(ft_d.p, ft.data(), (size_t)F * sizeof(FrameVar), hipMemcpyHostToDevice, c->stream));
+    }
+    const FrameVar *fr_d = var ? ft_d.as<FrameVar>() : nullptr;
+    ScopedKernelTimer t_labels(c, "frames_var_labels", var && c->timers);
     if (s->sp_mode) {
         uint32_t *cell_start, *ckeys, *cweight;
         km_rgbw_cell_arrays(km, &cell_start, &ckeys, &cweight);
@@ -703,17 +759,32 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
         CNIIC_TRY(scatter_labels_by_key(c, s->keys_d.as<uint32_t>(), lab_d.p, wide, U, key2label.p));
         CNIIC_TRY(pixel_labels(c, rgb_d, n, key2label.p, wide, pixlab.p));
     }
+    t_labels.stop(1);
     // frames whose label run does not start on a 16-byte boundary are moved apart (the pack reads 16 labels per load)
     const void *labs = pixlab.p;
     uint64_t lab_stride = npf;
-    if ((npf * lb) & 15) {
+    if (var) {
+        if (!runs_aligned) {
+            ScopedKernelTimer t(c, "frames_var_align");
+            CNIIC_HIP_TRY(c, pixlab_al.alloc(lab_total * lb + 16));
+            CNIIC_TRY(frame_labels_align_var(c, pixlab.p, pixlab_al.p, fr_d, F, chunks, wide));
+            labs = pixlab_al.p;
+            t.stop(1);
+        }
+    } else if ((npf * lb) & 15) {
         lab_stride = (npf + 15) & ~15ull;
         CNIIC_HIP_TRY(c, pixlab_al.alloc(lab_stride * lb * F + 16));
         CNIIC_HIP_TRY(c, hipMemcpy2DAsync(pixlab_al.p, lab_stride * lb, pixlab.p, npf * lb, npf * lb, F, hipMemcpyDeviceToDevice, c->stream));
         labs = pixlab_al.p;
     }
     CNIIC_HIP_TRY(c, cnt_d.alloc((uint64_t)F * K * 4));
-    CNIIC_TRY(frame_label_hist(c, labs, npf, lab_stride, F, wide, K, cnt_d.as<uint32_t>()));
+    if (var) {
+        ScopedKernelTimer t(c, "frames_var_hist");
+        CNIIC_TRY(frame_label_hist_var(c, labs, fr_d, F, hblocks, wide, K, cnt_d.as<uint32_t>()));
+        t.stop(1);
+    } else {
+        CNIIC_TRY(frame_label_hist(c, labs, npf, lab_stride, F, wide, K, cnt_d.as<uint32_t>()));
+    }
     const bool gpu_trees = !wide && K <= 256 && c->opt(CNIIC_OPT_FRAME_TREES_HOST, "CNIIC_FRAME_TREES_HOST", 0) == 0;
     std::vector<uint32_t> cnt(gpu_trees ? 0 : (size_t)F * K);
     if (!gpu_trees) CNIIC_HIP_TRY(c, hipMemcpyAsync(cnt.data(), cnt_d.p, cnt.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -729,6 +800,15 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
     CNIIC_HIP_TRY(c, clen_d.alloc((size_t)F * K));
     CNIIC_HIP_TRY(c, ccode_d.alloc((size_t)F * K * 8));
     std::vector<uint64_t> totals(F, 0);
+    // the label pack of every frame behind its header: bit bases on the host (bb_h) or already on the device (bb_d)
+    auto pack = [&](const uint64_t *bb_h, const uint64_t *bb_d) {
+        if (!var)
+            return huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bb_h, totals.data(), bb_d);
+        ScopedKernelTimer t(c, "frames_var_pack");
+        const int rc = huff_pack_labels_frames_var(c, labs, fr_d, F, chunks, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bb_h, totals.data(), bb_d);
+        t.stop(3);
+        return rc;
+    };
     if (gpu_trees) {
         // ---- K <= 256: codes, code tables and stream headers of all frames by one kernel (k_frame_trees); the host sees the
         // lengths (it owes them to the caller and must hold them against the stride before anything is packed) and nothing else
@@ -738,7 +818,9 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
         uint64_t *bb_d = meta_d.as<uint64_t>(), *nb_d = bb_d + F, *ln_d = nb_d + F;
         uint32_t *err_d = reinterpret_cast<uint32_t *>(ln_d + F);
         CNIIC_HIP_TRY(c, hipMemsetAsync(err_d, 0, 8, c->stream));
-        CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), km_rgbw_centroids_dev(km), F, K, w, h, fo.dev, stride, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d));
+        ScopedKernelTimer t_trees(c, "frames_var_trees", var && c->timers);
+        CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), km_rgbw_centroids_dev(km), F, K, w, h, fo.dev, stride, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d, fr_d));
+        t_trees.stop(1);
         std::vector<uint64_t> meta((size_t)F * 3 + 1);
         CNIIC_HIP_TRY(c, hipMemcpyAsync(meta.data(), meta_d.p, (size_t)F * 24 + 8, hipMemcpyDeviceToHost, c->stream));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -747,7 +829,7 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
         if (err & 3u) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
         std::copy_n(meta.data() + 2 * (size_t)F, F, lens);
         CNIIC_TRY(fo.check_lens(lens, (err & 4u) != 0));
-        CNIIC_TRY(huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, nullptr, totals.data(), bb_d));
+        CNIIC_TRY(pack(nullptr, bb_d));
         host_trace().mark("frames: pack (+sync)");
         CNIIC_TRY(fo.finish(totals.data(), meta.data() + F));
         host_trace().dump();
@@ -759,7 +841,9 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
     std::vector<uint64_t> ccode((size_t)F * K), nbits(F, 0);
     std::atomic<int> bad{0};
     parallel_for(F, std::max(1u, std::min({F, 16u, std::thread::hardware_concurrency()})), [&](uint32_t f, uint32_t) {
-        if (!palette_code(cent.data(), cnt.data() + (size_t)f * K, K, w, h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K], &nbits[f])) bad = 1;
+        if (!palette_code(cent.data(), cnt.data() + (size_t)f * K, K, var ? wv[f] : w, var ? hv[f] : h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K],
+                          &nbits[f]))
+            bad = 1;
     });
     host_trace().mark("frames: trees, codes, headers (host threads)");
     if (bad) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
@@ -780,11 +864,22 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
     CNIIC_HIP_TRY(c, hipMemcpy2DAsync(fo.dev, stride, hdr_d.p, hmax, hmax, F, hipMemcpyDeviceToDevice, c->stream));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(clen_d.p, clen.data(), clen.size(), hipMemcpyHostToDevice, c->stream));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(ccode_d.p, ccode.data(), ccode.size() * 8, hipMemcpyHostToDevice, c->stream));
-    CNIIC_TRY(huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bit_base.data(), totals.data()));
+    CNIIC_TRY(pack(bit_base.data(), nullptr));
     host_trace().mark("frames: copies + pack (+sync)");
     CNIIC_TRY(fo.finish(totals.data(), nbits.data()));
     host_trace().dump();
     return CNIIC_OK;
+}
+
+int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
+                     cniic_kmeans_stats *stats) {
+    return finish_frames(s, rgb_d, w, h, nullptr, nullptr, F, out, stride, lens, stats);
+}
+
+int cc_finish_frames_var(CcSession *s, const uint8_t *rgb_d, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
+                         cniic_kmeans_stats *stats) {
+    if (!w || !h) return s->c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: null argument");
+    return finish_frames(s, rgb_d, 0, 0, w, h, F, out, stride, lens, stats);
 }
 
 // images of at least this many pixels take the super-cell partition (k_points.hip); CNIIC_SP_MIN_PIXELS overrides (tests: 0)

@@ -109,6 +109,7 @@ struct CcSession {
     uint32_t *table = nullptr;   // dense colour table: counts on entry of cc_prepare, key -> rank + 1 afterwards
     uint64_t U = 0;
     DevBuf keys_d, weight_d;
+    bool counts_local = false;   // dense table: weight_d holds THIS session's pixels per colour (one rank, or the caller's own image), not the union's
     DevBuf gbits, gprefix, gtotal;  // shared palette over several images: index of the colours that occur in ANY of them (+ their number, on the device)
     bool local_points = false;   // ... and the points of this session are this image's colours only
     SpPlan sp;                   // large images: the pixels partitioned by colour super-cell (k_points.hip) instead of the dense table
@@ -130,6 +131,9 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
 // a batch of F frames coded with the session's one palette: F Hufman streams, stream f at out + f * stride, its length in lens[f]
 int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
                      cniic_kmeans_stats *stats);
+// the same for frames of any sizes: frame f is w[f] x h[f] (host arrays), the frames back to back in rgb_d
+int cc_finish_frames_var(CcSession *s, const uint8_t *rgb_d, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
+                         cniic_kmeans_stats *stats);
 
 // header carries any prefix already serialised (image dimensions); the decoder trie is appended
 // to it and the whole stream lands in out[0..*len)  (out: host or device memory).

@@ -811,8 +811,26 @@ int scatter_labels_by_key(Ctx *c, const uint32_t *keys_d, const void *labels_d, 
 int frame_label_hist(Ctx *c, const void *pixlab_d, uint64_t npf, uint64_t lab_stride, uint32_t frames, bool wide, uint32_t K, uint32_t *out_d /* u32[frames][K] */);
 int huff_pack_labels_frames(Ctx *c, const void *pixlab_d, uint64_t npf, uint64_t lab_stride, uint32_t frames, bool wide, uint32_t K, const uint8_t *clen_d,
                             const uint64_t *ccode_d, uint8_t *out_d, uint64_t stride, const uint64_t *bit_base_h, uint64_t *totals_h, const uint64_t *bit_base_d = nullptr);
+// ---- a batch of frames of ANY sizes sharing one palette (cc_finish_frames_var).  One table row per frame, built on the host, uploaded once:
+// every kernel of the route runs a 1-D grid over the chunks (or histogram blocks) of all frames and finds its frame by a binary search in
+// chunk0 (hblock0); a block never spans two frames.
+struct FrameVar {
+    uint64_t npx;        // w h
+    uint64_t lab_base;   // first label, in elements of the label buffer the pack reads: on a 16-byte boundary
+    uint64_t src_base;   // first label where the pixel-label kernels wrote it: the pixels before this frame
+    uint32_t chunk0;     // first pack chunk: the sum of ceil(npx / 4096) over the frames before
+    uint32_t hblock0;    // first histogram block: the sum of ceil(npx / 2^16)
+    uint32_t w, h;
+};
+constexpr uint32_t kFrameVarChunk = 4096, kFrameVarHistSpan = 1u << 16;   // (= kPackChunk, kHistSpan of k_huff.hip)
 // the Huffman codes and stream headers of a batch's frames on the GPU (K <= 256; k_huff.hip k_frame_trees)
 int frame_trees(Ctx *c, const uint32_t *cnt_d, const uint32_t *cent_d, uint32_t frames, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, uint64_t stride,
-                uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d);
+                uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d,
+                const FrameVar *fr_d = nullptr /* frames of any sizes: w, h per frame from the table */);
+int frame_labels_align_var(Ctx *c, const void *src_d, void *dst_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide);
+int frame_label_hist_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t hblocks, bool wide, uint32_t K, uint32_t *out_d /* u32[frames][K] */);
+int huff_pack_labels_frames_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide, uint32_t K, const uint8_t *clen_d,
+                                const uint64_t *ccode_d, uint8_t *out_d, uint64_t stride, const uint64_t *bit_base_h, uint64_t *totals_h, const uint64_t *bit_base_d = nullptr);
+int sum_u32_dev(Ctx *c, const uint32_t *v_d, uint64_t n, uint64_t *out_d);   // *out_d = the sum of n u32
 
 }  // namespace cniic

@@ -261,19 +261,27 @@ __global__ __launch_bounds__(kPackThreads) void k_pixel_labels(const uint8_t *__
     }
 }
 
-// pass 1: code lengths of a chunk's labels, from an LDS table
+// the frame whose row of chunks (FIRST = &FrameVar::chunk0) or of histogram blocks (hblock0) holds block b: the LAST f with fr[f].*FIRST <= b
+// (every frame has at least one pixel, so the firsts rise strictly; the loads depend on the block alone)
+template <uint32_t FrameVar::*FIRST>
+__device__ __forceinline__ uint32_t frame_of_block(const FrameVar *__restrict__ fr, uint32_t frames, uint32_t b) {
+    uint32_t f = 0;
+    for (uint32_t hi = frames; hi - f > 1;) {   // fr[f].*FIRST <= b < fr[hi].*FIRST
+        const uint32_t mid = f + (hi - f) / 2;
+        if (fr[mid].*FIRST <= b) f = mid; else hi = mid;
+    }
+    return f;
+}
+
+// pass 1: code lengths of a chunk's labels, from an LDS table.  One body for one image, a batch of equal frames (grid.y = frame) and a
+// batch of frames of any sizes (a 1-D grid over all frames' chunks): the callers differ in where a block finds its labels and its row
 template <typename LabelT>
-__global__ __launch_bounds__(kPackThreads) void k_pack_count_lab(const LabelT *__restrict__ pixlab, uint64_t n, uint32_t K,
-                                                                 const uint8_t *__restrict__ clen,
-                                                                 uint32_t *__restrict__ chunk_bits, uint64_t lab_stride = 0) {
+__device__ __forceinline__ void pack_count_body(const LabelT *__restrict__ pixlab, uint64_t n, uint32_t K, const uint8_t *__restrict__ clen,
+                                                uint32_t chunk, uint32_t *__restrict__ chunk_total) {
     extern __shared__ uint8_t s_len[];  // [K]
-    // (a batch of frames: blockIdx.y = frame, its labels lab_stride elements further, its own code table and chunk row)
-    pixlab += (size_t)blockIdx.y * lab_stride;
-    clen += (size_t)blockIdx.y * K;
-    chunk_bits += (size_t)blockIdx.y * gridDim.x;
     for (uint32_t i = threadIdx.x; i < K; i += kPackThreads) s_len[i] = clen[i];
     __syncthreads();
-    const uint64_t first = (uint64_t)blockIdx.x * kPackChunk + (uint64_t)threadIdx.x * kPackPer;
+    const uint64_t first = (uint64_t)chunk * kPackChunk + (uint64_t)threadIdx.x * kPackPer;
     uint32_t bits = 0;
     if (sizeof(LabelT) == 1 && first + kPackPer <= n) {
         const uint4 v = *reinterpret_cast<const uint4 *>(pixlab + first);
@@ -285,24 +293,32 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_count_lab(const LabelT *_
             if (first + i < n) bits += s_len[pixlab[first + i]];
     }
     bits = block_reduce_sum<kPackThreads>(bits);
-    if (threadIdx.x == 0) chunk_bits[blockIdx.x] = bits;
+    if (threadIdx.x == 0) *chunk_total = bits;
 }
 
 template <typename LabelT>
-__global__ __launch_bounds__(kPackThreads) void k_pack_write_lab(const LabelT *__restrict__ pixlab, uint64_t n, uint32_t K,
+__global__ __launch_bounds__(kPackThreads) void k_pack_count_lab(const LabelT *__restrict__ pixlab, uint64_t n, uint32_t K,
                                                                  const uint8_t *__restrict__ clen,
-                                                                 const uint64_t *__restrict__ ccode,
-                                                                 const uint64_t *__restrict__ chunk_off,
-                                                                 uint32_t *__restrict__ out_words, uint64_t bit_base, uint64_t lab_stride = 0,
-                                                                 uint64_t out_stride_words = 0, const uint64_t *__restrict__ bit_base_frames = nullptr,
-                                                                 uint32_t img_cap = 0xffffffffu /* tests: a smaller image forces the direct route */) {
+                                                                 uint32_t *__restrict__ chunk_bits, uint64_t lab_stride = 0) {
+    // (a batch of frames: blockIdx.y = frame, its labels lab_stride elements further, its own code table and chunk row)
+    pack_count_body(pixlab + (size_t)blockIdx.y * lab_stride, n, K, clen + (size_t)blockIdx.y * K, blockIdx.x,
+                    chunk_bits + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+// frames of any sizes: block b is chunk b - chunk0 of its frame; the chunk totals of all frames lie in one row, frame after frame
+template <typename LabelT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_count_lab_var(const LabelT *__restrict__ labs, const FrameVar *__restrict__ fr, uint32_t frames,
+                                                                     uint32_t K, const uint8_t *__restrict__ clen, uint32_t *__restrict__ chunk_bits) {
+    const uint32_t f = frame_of_block<&FrameVar::chunk0>(fr, frames, blockIdx.x);
+    pack_count_body(labs + fr[f].lab_base, fr[f].npx, K, clen + (size_t)f * K, blockIdx.x - fr[f].chunk0, chunk_bits + blockIdx.x);
+}
+
+// pass 3: a chunk's codes into the output.  chunk_off: this chunk's bit offset behind bit_base.  One body, as for pass 1
+template <typename LabelT>
+__device__ __forceinline__ void pack_write_body(const LabelT *__restrict__ pixlab, uint64_t n, uint32_t K, const uint8_t *__restrict__ clen,
+                                                const uint64_t *__restrict__ ccode, uint32_t chunk, const uint64_t *__restrict__ chunk_off,
+                                                uint32_t *__restrict__ out_words, uint64_t bit_base, uint32_t img_cap) {
     extern __shared__ __align__(8) unsigned long long s_tab[];  // [K] codes, then [K] lens (bytes)
-    pixlab += (size_t)blockIdx.y * lab_stride;   // (a batch of frames: blockIdx.y = frame)
-    clen += (size_t)blockIdx.y * K;
-    ccode += (size_t)blockIdx.y * K;
-    chunk_off += (size_t)blockIdx.y * gridDim.x;
-    out_words += (size_t)blockIdx.y * out_stride_words;
-    if (bit_base_frames) bit_base = bit_base_frames[blockIdx.y];
     // the chunk's bit image: 16 bits per symbol on average fit (a palette's codes average 8); a chunk of rarer symbols goes to
     // memory piece by piece instead (below).  Sized for the worst case (64 bits per symbol, 32 KiB) the array held the kernel at
     // four blocks per CU.
@@ -313,7 +329,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_write_lab(const LabelT *_
     uint8_t *s_len = reinterpret_cast<uint8_t *>(s_tab + K);
     for (uint32_t i = threadIdx.x; i < K; i += kPackThreads) { s_tab[i] = ccode[i]; s_len[i] = clen[i]; }
     __syncthreads();
-    const uint64_t first = (uint64_t)blockIdx.x * kPackChunk + (uint64_t)threadIdx.x * kPackPer;
+    const uint64_t first = (uint64_t)chunk * kPackChunk + (uint64_t)threadIdx.x * kPackPer;
     uint32_t lab[kPackPer], l[kPackPer];
     uint32_t bits = 0;
     if (sizeof(LabelT) == 1 && first + kPackPer <= n) {
@@ -328,7 +344,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_write_lab(const LabelT *_
 #pragma unroll
     for (int i = 0; i < kPackPer; i++) { l[i] = lab[i] != 0xffffffffu ? s_len[lab[i]] : 0; bits += l[i]; }
     uint32_t excl = block_exclusive_scan<kPackThreads>(bits, wsum);
-    const uint64_t g0 = bit_base + chunk_off[blockIdx.x];
+    const uint64_t g0 = bit_base + *chunk_off;
     const uint32_t skew = (uint32_t)(g0 & 31);
     uint32_t pos = skew + excl;
     // the image is cleared only as far as this chunk's bits reach (the array is sized for 64 bits per symbol; a palette's codes
@@ -387,6 +403,29 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_write_lab(const LabelT *_
     }
 }
 
+template <typename LabelT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_write_lab(const LabelT *__restrict__ pixlab, uint64_t n, uint32_t K,
+                                                                 const uint8_t *__restrict__ clen,
+                                                                 const uint64_t *__restrict__ ccode,
+                                                                 const uint64_t *__restrict__ chunk_off,
+                                                                 uint32_t *__restrict__ out_words, uint64_t bit_base, uint64_t lab_stride = 0,
+                                                                 uint64_t out_stride_words = 0, const uint64_t *__restrict__ bit_base_frames = nullptr,
+                                                                 uint32_t img_cap = 0xffffffffu /* tests: a smaller image forces the direct route */) {
+    if (bit_base_frames) bit_base = bit_base_frames[blockIdx.y];   // (a batch of frames: blockIdx.y = frame)
+    pack_write_body(pixlab + (size_t)blockIdx.y * lab_stride, n, K, clen + (size_t)blockIdx.y * K, ccode + (size_t)blockIdx.y * K, blockIdx.x,
+                    chunk_off + (size_t)blockIdx.y * gridDim.x + blockIdx.x, out_words + (size_t)blockIdx.y * out_stride_words, bit_base, img_cap);
+}
+
+template <typename LabelT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_write_lab_var(const LabelT *__restrict__ labs, const FrameVar *__restrict__ fr, uint32_t frames,
+                                                                     uint32_t K, const uint8_t *__restrict__ clen, const uint64_t *__restrict__ ccode,
+                                                                     const uint64_t *__restrict__ chunk_off, uint32_t *__restrict__ out_words,
+                                                                     uint64_t out_stride_words, const uint64_t *__restrict__ bit_base_frames, uint32_t img_cap) {
+    const uint32_t f = frame_of_block<&FrameVar::chunk0>(fr, frames, blockIdx.x);
+    pack_write_body(labs + fr[f].lab_base, fr[f].npx, K, clen + (size_t)f * K, ccode + (size_t)f * K, blockIdx.x - fr[f].chunk0, chunk_off + blockIdx.x,
+                    out_words + (size_t)f * out_stride_words, bit_base_frames[f], img_cap);
+}
+
 // key2label_d: LabelT[2^24] dense colour -> cluster label; pixlab_d receives n labels (+16 bytes of slack)
 int pixel_labels(Ctx *c, const uint8_t *rgb_d, uint64_t n, const void *key2label_d, bool wide, void *pixlab_d) {
     if (n == 0) return CNIIC_OK;
@@ -438,16 +477,13 @@ int huff_pack_labels(Ctx *c, const void *pixlab_d, uint64_t n, bool wide, uint32
 
 // ---- a batch of frames coded with one palette (north_star config 4): per-frame label histograms, and the label pack
 // of every frame enqueued back to back (no host round trip per frame)
+// labels [lo, hi) of one frame (base: its first label) counted into the block's LDS bins and added to the frame's row
 template <typename LabelT>
-__global__ __launch_bounds__(256) void k_frame_label_hist(const LabelT *__restrict__ pixlab, uint64_t npf, uint64_t lab_stride, uint32_t K,
-                                                          uint32_t *__restrict__ out /* [frames][K] */) {
+__device__ __forceinline__ void frame_hist_body(const LabelT *__restrict__ base, uint64_t lo, uint64_t hi, uint32_t K, uint32_t *__restrict__ row /* [K] */) {
     extern __shared__ uint32_t s_hist[];  // [4][K]: one histogram per wave (a frame's pixels fall into few clusters: four times fewer collisions)
     for (uint32_t i = threadIdx.x; i < 4 * K; i += 256) s_hist[i] = 0;
     __syncthreads();
-    const LabelT *base = pixlab + (size_t)blockIdx.y * lab_stride;
     uint32_t *hw = s_hist + (threadIdx.x >> 6) * K;
-    const uint64_t per = ((npf + gridDim.x - 1) / gridDim.x + 15) & ~15ull;
-    const uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per < npf ? lo + per : npf;
     if (sizeof(LabelT) == 1 && (reinterpret_cast<uintptr_t>(base) & 15) == 0) {  // 16 labels per load
         for (uint64_t i = lo + (uint64_t)threadIdx.x * 16; i < hi; i += 256 * 16) {
             if (i + 16 <= hi) {
@@ -465,8 +501,89 @@ __global__ __launch_bounds__(256) void k_frame_label_hist(const LabelT *__restri
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < K; i += 256) {
         const uint32_t v = s_hist[i] + s_hist[K + i] + s_hist[2 * K + i] + s_hist[3 * K + i];
-        if (v) atomicAdd(&out[(size_t)blockIdx.y * K + i], v);
+        if (v) atomicAdd(&row[i], v);
     }
+}
+
+template <typename LabelT>
+__global__ __launch_bounds__(256) void k_frame_label_hist(const LabelT *__restrict__ pixlab, uint64_t npf, uint64_t lab_stride, uint32_t K,
+                                                          uint32_t *__restrict__ out /* [frames][K] */) {
+    const uint64_t per = ((npf + gridDim.x - 1) / gridDim.x + 15) & ~15ull;
+    const uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per < npf ? lo + per : npf;
+    frame_hist_body(pixlab + (size_t)blockIdx.y * lab_stride, lo, hi, K, out + (size_t)blockIdx.y * K);
+}
+
+// frames of any sizes: a 1-D grid, block b counts labels [kHistSpan (b - hblock0), + kHistSpan) of its frame (a frame of fewer labels is one
+// block); 2^16 labels per block as for the equal frames, so a block adds its K sums to HBM once per 2^16 labels
+constexpr uint64_t kHistSpan = kFrameVarHistSpan;
+static_assert(kPackChunk == (int)kFrameVarChunk, "the frame table's chunks are the pack's");
+template <typename LabelT>
+__global__ __launch_bounds__(256) void k_frame_label_hist_var(const LabelT *__restrict__ labs, const FrameVar *__restrict__ fr, uint32_t frames, uint32_t K,
+                                                              uint32_t *__restrict__ out /* [frames][K] */) {
+    const uint32_t f = frame_of_block<&FrameVar::hblock0>(fr, frames, blockIdx.x);
+    const uint64_t npf = fr[f].npx, lo = (uint64_t)(blockIdx.x - fr[f].hblock0) * kHistSpan, hi = lo + kHistSpan < npf ? lo + kHistSpan : npf;
+    frame_hist_body(labs + fr[f].lab_base, lo, hi, K, out + (size_t)f * K);
+}
+
+// frames of any sizes: every frame's label run copied from where the pixel-label kernels left it (runs back to back, src_base) to its
+// 16-byte aligned base (lab_base): the pack and the histogram read 16 labels per load.  One launch over the chunks of all frames; a thread
+// moves 16 labels, the store always 16-byte aligned, the load too when the run happens to start aligned
+template <typename LabelT>
+__global__ __launch_bounds__(kPackThreads) void k_labels_align_var(const LabelT *__restrict__ src, LabelT *__restrict__ dst, const FrameVar *__restrict__ fr,
+                                                                   uint32_t frames) {
+    const uint32_t f = frame_of_block<&FrameVar::chunk0>(fr, frames, blockIdx.x);
+    const uint64_t n = fr[f].npx, first = (uint64_t)(blockIdx.x - fr[f].chunk0) * kPackChunk + (uint64_t)threadIdx.x * kPackPer;
+    if (first >= n) return;
+    const LabelT *s = src + fr[f].src_base + first;
+    LabelT *d = dst + fr[f].lab_base + first;
+    constexpr int kQuads = (int)sizeof(LabelT);   // uint4 per 16 labels
+    if (first + kPackPer <= n) {
+        uint4 q[kQuads];
+        if ((reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+#pragma unroll
+            for (int j = 0; j < kQuads; j++) q[j] = reinterpret_cast<const uint4 *>(s)[j];
+        } else {
+            constexpr int kPerWord = 4 / (int)sizeof(LabelT);
+            uint32_t w[4 * kQuads];
+#pragma unroll
+            for (int j = 0; j < 4 * kQuads; j++) {
+                w[j] = 0;
+#pragma unroll
+                for (int e = 0; e < kPerWord; e++) w[j] |= (uint32_t)s[j * kPerWord + e] << (8 * (int)sizeof(LabelT) * e);
+            }
+#pragma unroll
+            for (int j = 0; j < kQuads; j++) q[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+        }
+#pragma unroll
+        for (int j = 0; j < kQuads; j++) reinterpret_cast<uint4 *>(d)[j] = q[j];
+    } else {
+        for (int i = 0; i < kPackPer; i++)
+            if (first + i < n) d[i] = s[i];
+    }
+}
+
+// (every launcher of the frames-of-any-sizes route: `chunks` / `hblocks` = the sums the frame table's firsts end in)
+int frame_labels_align_var(Ctx *c, const void *src_d, void *dst_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide) {
+    if (wide)
+        hipLaunchKernelGGL(k_labels_align_var<uint16_t>, dim3(chunks), dim3(kPackThreads), 0, c->stream, reinterpret_cast<const uint16_t *>(src_d),
+                           reinterpret_cast<uint16_t *>(dst_d), fr_d, frames);
+    else
+        hipLaunchKernelGGL(k_labels_align_var<uint8_t>, dim3(chunks), dim3(kPackThreads), 0, c->stream, reinterpret_cast<const uint8_t *>(src_d),
+                           reinterpret_cast<uint8_t *>(dst_d), fr_d, frames);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
+int frame_label_hist_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t hblocks, bool wide, uint32_t K, uint32_t *out_d) {
+    CNIIC_HIP_TRY(c, hipMemsetAsync(out_d, 0, (uint64_t)frames * K * 4, c->stream));
+    if (wide)
+        hipLaunchKernelGGL(k_frame_label_hist_var<uint16_t>, dim3(hblocks), dim3(256), (size_t)K * 16, c->stream, reinterpret_cast<const uint16_t *>(labs_d), fr_d,
+                           frames, K, out_d);
+    else
+        hipLaunchKernelGGL(k_frame_label_hist_var<uint8_t>, dim3(hblocks), dim3(256), (size_t)K * 16, c->stream, reinterpret_cast<const uint8_t *>(labs_d), fr_d,
+                           frames, K, out_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
 }
 
 int frame_label_hist(Ctx *c, const void *pixlab_d, uint64_t npf, uint64_t lab_stride, uint32_t frames, bool wide, uint32_t K, uint32_t *out_d) {
@@ -509,7 +626,8 @@ __global__ __launch_bounds__(256) void k_frame_trees(const uint32_t *__restrict_
                                                      uint32_t K, uint32_t w, uint32_t h, uint8_t *__restrict__ out, uint64_t stride,
                                                      uint8_t *__restrict__ clen /* [F][K] */, unsigned long long *__restrict__ ccode /* [F][K] */,
                                                      unsigned long long *__restrict__ bit_base /* [F] */, unsigned long long *__restrict__ nbits /* [F] */,
-                                                     unsigned long long *__restrict__ lens /* [F] */, uint32_t *__restrict__ err) {
+                                                     unsigned long long *__restrict__ lens /* [F] */, uint32_t *__restrict__ err,
+                                                     const FrameVar *__restrict__ fr = nullptr /* frames of any sizes: frame f is fr[f].w x fr[f].h */) {
     __shared__ unsigned long long s_sort[256];
     __shared__ uint32_t s_key[256], s_cnt[256], s_bfreq[256];
     __shared__ unsigned short s_symk[256], s_left[256], s_right[256], s_parent[512], s_size[512];
@@ -575,6 +693,7 @@ __global__ __launch_bounds__(256) void k_frame_trees(const uint32_t *__restrict_
     const unsigned long long hbytes = 8ull + 12ull * n + (n - 1);
     const bool fits = hbytes <= stride;  // (the caller checks the whole stream against the stride once the lengths are back; the header alone must not overrun it)
     if (!fits && tid == 0) atomicOr(err, 4u);
+    if (fr) { w = fr[f].w; h = fr[f].h; }
     if (fits && tid < 8) o[tid] = (uint8_t)((tid < 4 ? w : h) >> (8 * (tid & 3)));
     // ---- every node walks up to the root: its offset in the pre-order stream, and for a leaf its code
     for (uint32_t v = tid; v < nnodes; v += 256) {
@@ -615,11 +734,11 @@ __global__ __launch_bounds__(256) void k_frame_trees(const uint32_t *__restrict_
 }
 
 int frame_trees(Ctx *c, const uint32_t *cnt_d, const uint32_t *cent_d, uint32_t frames, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, uint64_t stride,
-                uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d) {
+                uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d, const FrameVar *fr_d) {
     if (K > 256) return c->fail(CNIIC_ERR_BAD_ARG, "frame_trees: K <= 256");
     hipLaunchKernelGGL(k_frame_trees, dim3(frames), dim3(256), 0, c->stream, cnt_d, cent_d, K, w, h, out_d, stride, clen_d,
                        reinterpret_cast<unsigned long long *>(ccode_d), reinterpret_cast<unsigned long long *>(bit_base_d),
-                       reinterpret_cast<unsigned long long *>(nbits_d), reinterpret_cast<unsigned long long *>(lens_d), err_d);
+                       reinterpret_cast<unsigned long long *>(nbits_d), reinterpret_cast<unsigned long long *>(lens_d), err_d, fr_d);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }
@@ -689,6 +808,79 @@ int huff_pack_labels_frames(Ctx *c, const void *pixlab_d, uint64_t npf, uint64_t
     CNIIC_HIP_TRY(c, hipGetLastError());
     CNIIC_HIP_TRY(c, hipMemcpyAsync(totals_h, tot.p, (size_t)frames * 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+// exclusive scan (u64) of each frame's row of chunk totals, the rows of different lengths (frame f: chunks [chunk0[f], chunk0[f + 1])): one
+// WAVE per frame, 64 chunks a step with the carry in a register -- no barrier, and a batch of tens of thousands of one-chunk frames costs a
+// quarter of a block each
+__global__ __launch_bounds__(256) void k_pack_scan_frames_var(const uint32_t *__restrict__ chunk_bits, const FrameVar *__restrict__ fr, uint32_t frames,
+                                                               uint32_t chunks, uint64_t *__restrict__ chunk_off, uint64_t *__restrict__ totals) {
+    const uint32_t f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (f >= frames) return;   // (the whole wave)
+    const uint32_t c0 = fr[f].chunk0, c1 = f + 1 < frames ? fr[f + 1].chunk0 : chunks;
+    unsigned long long carry = 0;
+    for (uint32_t base = c0; base < c1; base += 64) {   // (bounds of the wave: the scan below runs with every lane)
+        const uint32_t i = base + lane;
+        const unsigned long long v = i < c1 ? chunk_bits[i] : 0ull;
+        const unsigned long long inc = wave_inclusive_scan64<false>(v);
+        if (i < c1) chunk_off[i] = carry + inc - v;
+        carry += ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(inc >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)inc, 63);
+    }
+    if (lane == 0) totals[f] = carry;
+}
+
+// huff_pack_labels_frames for frames of any sizes (fr_d: the frame table; labs_d + lab_base[f]: frame f's labels, 16-byte aligned): the same
+// three launches, each a 1-D grid over the `chunks` chunks of all frames, and the per-frame totals back in one copy.  No cap on the frames
+int huff_pack_labels_frames_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide, uint32_t K, const uint8_t *clen_d,
+                                const uint64_t *ccode_d, uint8_t *out_d, uint64_t stride, const uint64_t *bit_base_h, uint64_t *totals_h,
+                                const uint64_t *bit_base_d) {
+    if (!frames || !chunks) return CNIIC_OK;
+    if ((reinterpret_cast<uintptr_t>(out_d) & 3) || (stride & 3)) return c->fail(CNIIC_ERR_BAD_ARG, "huff_pack: output and stride must be 4-byte aligned");
+    DevBuf cb, co, tot, bb;
+    CNIIC_HIP_TRY(c, cb.alloc((uint64_t)chunks * 4));
+    CNIIC_HIP_TRY(c, co.alloc((uint64_t)chunks * 8));
+    CNIIC_HIP_TRY(c, tot.alloc((uint64_t)frames * 8));
+    if (!bit_base_d) {
+        CNIIC_HIP_TRY(c, bb.alloc((uint64_t)frames * 8));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(bb.p, bit_base_h, (size_t)frames * 8, hipMemcpyHostToDevice, c->stream));
+        bit_base_d = bb.as<uint64_t>();
+    }
+    if (wide)
+        hipLaunchKernelGGL(k_pack_count_lab_var<uint16_t>, dim3(chunks), dim3(kPackThreads), K, c->stream, reinterpret_cast<const uint16_t *>(labs_d), fr_d, frames, K,
+                           clen_d, cb.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_pack_count_lab_var<uint8_t>, dim3(chunks), dim3(kPackThreads), K, c->stream, reinterpret_cast<const uint8_t *>(labs_d), fr_d, frames, K,
+                           clen_d, cb.as<uint32_t>());
+    hipLaunchKernelGGL(k_pack_scan_frames_var, dim3((frames + 3) / 4), dim3(256), 0, c->stream, (const uint32_t *)cb.as<uint32_t>(), fr_d, frames, chunks,
+                       co.as<uint64_t>(), tot.as<uint64_t>());
+    if (wide)
+        hipLaunchKernelGGL(k_pack_write_lab_var<uint16_t>, dim3(chunks), dim3(kPackThreads), (size_t)K * 9 + 8, c->stream, reinterpret_cast<const uint16_t *>(labs_d),
+                           fr_d, frames, K, clen_d, ccode_d, (const uint64_t *)co.as<uint64_t>(), reinterpret_cast<uint32_t *>(out_d), stride / 4, bit_base_d,
+                           pack_img_cap());
+    else
+        hipLaunchKernelGGL(k_pack_write_lab_var<uint8_t>, dim3(chunks), dim3(kPackThreads), (size_t)K * 9 + 8, c->stream, reinterpret_cast<const uint8_t *>(labs_d),
+                           fr_d, frames, K, clen_d, ccode_d, (const uint64_t *)co.as<uint64_t>(), reinterpret_cast<uint32_t *>(out_d), stride / 4, bit_base_d,
+                           pack_img_cap());
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(totals_h, tot.p, (size_t)frames * 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+// the sum of n u32 (a dense-table session's pixels: its colours' counts), added to *out_d (zero on entry)
+__global__ __launch_bounds__(256) void k_sum_u32(const uint32_t *__restrict__ v, uint64_t n, unsigned long long *__restrict__ out) {
+    unsigned long long s = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) s += v[i];
+    s = wave_reduce_sum64(s);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
+}
+
+int sum_u32_dev(Ctx *c, const uint32_t *v_d, uint64_t n, uint64_t *out_d) {
+    CNIIC_HIP_TRY(c, hipMemsetAsync(out_d, 0, 8, c->stream));
+    if (!n) return CNIIC_OK;
+    hipLaunchKernelGGL(k_sum_u32, dim3((uint32_t)std::min<uint64_t>(ceil_div(n, 256), 1024)), dim3(256), 0, c->stream, v_d, n, reinterpret_cast<unsigned long long *>(out_d));
+    CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }
 

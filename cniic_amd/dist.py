@@ -131,6 +131,21 @@ class HipBackend:
                                                       C.c_void_p(out.data_ptr()), C.c_uint64(stride), lens, C.byref(st)))
         return list(lens), st.as_dict()
 
+    def finish_frames_var(self, h, frames_flat, ws, hs, out, stride, allow=()):
+        """cniic_cc_finish_frames_var: len(ws) frames of different sizes, back to back in frames_flat (device tensor, numpy array or
+        address), frame f's stream at out[f * stride:] -> (list of lengths, stats); with a status in `allow`: (status, lengths, stats)"""
+        F = len(ws)
+        n = max(F, 1)
+        w = (C.c_uint32 * n)(*[int(x) for x in ws])
+        hh = (C.c_uint32 * n)(*[int(x) for x in hs])
+        lens = (C.c_uint64 * n)()
+        st = _lib.KmStats()
+        rc = self.ctx._check(self.L.cniic_cc_finish_frames_var(h, _lib._ptr(frames_flat), w, hh, C.c_uint32(F), _lib._ptr(out), C.c_uint64(stride), lens,
+                                                               C.byref(st)), allow)
+        if allow:
+            return rc, [int(lens[f]) for f in range(F)], st.as_dict()
+        return [int(lens[f]) for f in range(F)], st.as_dict()
+
     def destroy(self, h):
         self.L.cniic_cc_destroy(h)
 
@@ -310,6 +325,15 @@ class ShardedClusterColors:
         handle, partials = self._cluster(frames, w * h * F)
         try:
             return self.be.finish_frames(handle, frames, w, h, F, out, stride)
+        finally:
+            self.be.destroy(handle)
+
+    def encode_frames_var(self, frames_flat, ws, hs, out, stride):
+        """the same for frames of different sizes: frames_flat = the packed bytes of all of this rank's frames (frame f is ws[f] x hs[f], the
+        frames back to back), ONE palette; frame f's stream lands at out[f * stride:].  -> (list of lengths, K-means stats)"""
+        handle, partials = self._cluster(frames_flat, sum(int(a) * int(b) for a, b in zip(ws, hs)))
+        try:
+            return self.be.finish_frames_var(handle, frames_flat, ws, hs, out, stride)
         finally:
             self.be.destroy(handle)
 

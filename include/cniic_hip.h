@@ -245,6 +245,21 @@ int32_t  cniic_cc_finish(cniic_cc *cc, const uint8_t *rgb, uint32_t w, uint32_t 
  * out + f * stride (stride: a multiple of 4, at least the longest stream rounded up to 4) and its length to lens[f]. */
 int32_t  cniic_cc_finish_frames(cniic_cc *cc, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t frames,
                                 uint8_t *out, uint64_t stride, uint64_t *lens, cniic_kmeans_stats *stats);
+/* The same for frames of DIFFERENT sizes -- a folder, a sprite sheet, the tiles of a large image with ragged edge tiles -- under the
+ * session's one palette (the harness's many-images loop, bench.rs:24-35, is run on such a folder; padding the frames instead would
+ * change the histogram and so the palette).  Frame f is w[f] x h[f]; the frames lie back to back in rgb, in order: the contiguous
+ * pixels the session was opened on (cniic_cc_image_begin(rgb, sum of w[f] h[f]), or the dense-table calls).  w, h and lens are host
+ * arrays of `frames` entries; rgb and out may be host or device memory, as above.  Stream f is ClusterColors::encode
+ * (clusterc.rs:31-52) applied to frame f with the session's palette -- the frame's own dimensions, its own tree over the clusters it
+ * uses, its payload -- written at out + f * stride (stride: a multiple of 4), its length to lens[f]: the layout
+ * cniic_codec_decode_batch reads.  Any number of frames (no 65 535 cap).
+ * CNIIC_ERR_BAD_ARG: a null argument or frames == 0; any w[f] * h[f] == 0; stride & 3; the sum of w[f] h[f] different from the pixels
+ * the session was opened on (cniic_last_error names both numbers).  A dense-table session knows its pixels when the table held its own
+ * image's counts (cniic_cc_create_local, or cniic_cc_create with one shard); one made by cniic_cc_create from the all-reduced table of
+ * several shards holds the union's counts only and, like cniic_cc_finish_frames, cannot check the total.  A stream that does not fit the stride:
+ * CNIIC_ERR_CAPACITY as from cniic_cc_finish_frames, the lengths needed in lens, nothing packed. */
+int32_t  cniic_cc_finish_frames_var(cniic_cc *cc, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                    uint8_t *out, uint64_t stride, uint64_t *lens, cniic_kmeans_stats *stats);
 void     cniic_cc_destroy(cniic_cc *cc);
 
 /* The same shared palette with every rank holding ONLY ITS OWN image's colours (per-rank work and memory do not
