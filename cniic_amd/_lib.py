@@ -43,6 +43,8 @@ SYMBOLS = [
     "cniic_zip_back_image_encode_batch_var", "cniic_zip_back_image_decode_batch",
     "cniic_hilbert_linearize_count", "cniic_hilbert_linearize_as", "cniic_channel_diff_hist",
     "cniic_cc_finish_frames_var",
+    "cniic_cc_palette", "cniic_palette_create", "cniic_palette_destroy", "cniic_palette_label_bytes", "cniic_palette_labels",
+    "cniic_palette_encode_frames_var",
 ]
 
 
@@ -119,8 +121,26 @@ def lib():
         L.cniic_cc_finish_frames_var.restype = C.c_int32
         L.cniic_cc_finish_frames_var.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_uint64,
                                                  C.POINTER(C.c_uint64), C.c_void_p]
+        if hasattr(L, "cniic_cc_palette"):   # (CNIIC_LIB_FILE may name an older build of the library, for a comparison: it has no palettes)
+            _palette_prototypes(L)
         _lib = L
     return _lib
+
+
+def _palette_prototypes(L):
+    L.cniic_cc_palette.restype = C.c_int32
+    L.cniic_cc_palette.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cniic_palette_create.restype = C.c_int32
+    L.cniic_palette_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.cniic_palette_destroy.restype = None
+    L.cniic_palette_destroy.argtypes = [C.c_void_p]
+    L.cniic_palette_label_bytes.restype = C.c_uint32
+    L.cniic_palette_label_bytes.argtypes = [C.c_void_p]
+    L.cniic_palette_labels.restype = C.c_int32
+    L.cniic_palette_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.cniic_palette_encode_frames_var.restype = C.c_int32
+    L.cniic_palette_encode_frames_var.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_uint64,
+                                                  C.POINTER(C.c_uint64)]
 
 
 def _ptr(x):
@@ -701,6 +721,76 @@ class Context:
             out = np.empty((h, w, 3), np.uint8)
         self._check(self._L.cniic_synth_image(self.h, kind, C.c_uint64(seed), C.c_uint32(w), C.c_uint32(h), _ptr(out)))
         return out
+
+
+class Palette:
+    """cniic_palette: a FROZEN palette of K colours on one Context -- every pixel's label is the nearest entry in squared integer distance,
+    the lowest index among equals (include/cniic_hip.h).  Built once (the table of all 2^24 colours), used for any number of calls:
+
+        pal = Palette.create(ctx, centroids)          # (K, 3) uint8: numpy array or device tensor
+        lens = pal.encode_frames_var(flat, ws, hs, out, stride)
+        pal.close()
+    """
+
+    def __init__(self, ctx, centroids, K=None):
+        if isinstance(centroids, np.ndarray):
+            centroids = np.ascontiguousarray(centroids, np.uint8)
+        if K is None:
+            K = (centroids.numel() if hasattr(centroids, "numel") else centroids.size) // 3
+        self.ctx = ctx
+        self.K = int(K)
+        self.h = None
+        h = C.c_void_p()
+        ctx._check(ctx._L.cniic_palette_create(ctx.h, _ptr(centroids), C.c_uint32(self.K), C.byref(h)))
+        self.h = h
+        self.label_bytes = int(ctx._L.cniic_palette_label_bytes(h))
+
+    @classmethod
+    def create(cls, ctx, centroids, K=None):
+        return cls(ctx, centroids, K)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx._L.cniic_palette_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            if getattr(self.ctx, "h", None):   # (a handle dies with its context)
+                self.close()
+        except Exception:
+            pass
+
+    def labels(self, rgb, npx=None, out=None):
+        """cniic_palette_labels: the index image.  rgb: (..., 3) uint8 numpy array, or a device tensor / address with npx given; out: a
+        buffer of npx labels of label_bytes bytes each (numpy array, device tensor), default a new numpy array -> out"""
+        if isinstance(rgb, np.ndarray):
+            rgb = np.ascontiguousarray(rgb, np.uint8)
+        if npx is None:
+            npx = (rgb.numel() if hasattr(rgb, "numel") else rgb.size) // 3
+        if out is None:
+            out = np.empty(max(npx, 1), np.uint8 if self.label_bytes == 1 else np.uint16)[:npx]
+        self.ctx._check(self.ctx._L.cniic_palette_labels(self.h, _ptr(rgb) if npx else None, C.c_uint64(npx), _ptr(out)))
+        return out
+
+    def encode_frames_var(self, frames_flat, ws, hs, out, stride, allow=()):
+        """cniic_palette_encode_frames_var: len(ws) frames of different sizes, back to back in frames_flat (device tensor, numpy array or
+        address), frame f's stream at out[f * stride:] -> list of lengths; with a status in `allow`: (status, lengths)"""
+        F = len(ws)
+        n = max(F, 1)
+        w = (C.c_uint32 * n)(*[int(x) for x in ws])
+        hh = (C.c_uint32 * n)(*[int(x) for x in hs])
+        lens = (C.c_uint64 * n)()
+        rc = self.ctx._check(self.ctx._L.cniic_palette_encode_frames_var(self.h, _ptr(frames_flat), w, hh, C.c_uint32(F), _ptr(out), C.c_uint64(stride), lens), allow)
+        if allow:
+            return rc, [int(lens[f]) for f in range(F)]
+        return [int(lens[f]) for f in range(F)]
 
 
 def linearize_count(method, w, h):

@@ -743,6 +743,90 @@ void cniic_cc_destroy(cniic_cc *cc) {
     delete cc;
 }
 
+// ------------------------------------------------------------------ frozen palettes
+int32_t cniic_cc_palette(cniic_cc *cc, uint8_t *centroids, uint64_t *pixels) {
+    if (!cc) return CNIIC_ERR_BAD_ARG;
+    cniic_ctx *c = static_cast<cniic_ctx *>(cc->c);
+    LOCK(c);
+    if (!cc->s->km) return c->fail(CNIIC_ERR_BAD_ARG, "the session has no K-means state yet (cniic_cc_image_create comes first)");
+    if (!centroids) return c->fail(CNIIC_ERR_BAD_ARG, "cc_palette: null argument");
+    return cc_palette(cc->s, centroids, pixels);
+}
+
+struct cniic_palette {
+    Ctx *c = nullptr;
+    Palette *p = nullptr;
+};
+
+int32_t cniic_palette_create(cniic_ctx *c, const uint8_t *centroids, uint32_t K, cniic_palette **out) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!centroids || !out) return c->fail(CNIIC_ERR_BAD_ARG, "palette_create: null argument");
+    if (!K || K > 65536u) return c->fail(CNIIC_ERR_BAD_ARG, "palette_create: K = %u (1 .. 65536)", K);
+    std::vector<uint8_t> cent(3 * (size_t)K);
+    CNIIC_TRY(from_caller(c, cent.data(), centroids, cent.size()));
+    Palette *p = nullptr;
+    CNIIC_TRY(palette_create(c, cent.data(), K, &p));
+    *out = new cniic_palette{c, p};
+    return CNIIC_OK;
+}
+
+uint32_t cniic_palette_label_bytes(cniic_palette *pal) { return pal && pal->p && pal->p->wide ? 2 : 1; }
+
+int32_t cniic_palette_labels(cniic_palette *pal, const uint8_t *rgb, uint64_t npx, void *labels) {
+    if (!pal) return CNIIC_ERR_BAD_ARG;
+    cniic_ctx *c = static_cast<cniic_ctx *>(pal->c);
+    LOCK(c);
+    c->ktimes.clear();
+    if (!npx) return CNIIC_OK;
+    if (!rgb || !labels) return c->fail(CNIIC_ERR_BAD_ARG, "palette_labels: null argument");
+    const uint64_t lb = pal->p->wide ? 2 : 1;
+    if (npx > (~0ull) / 3) return c->fail(CNIIC_ERR_BAD_ARG, "palette_labels: too many pixels");
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, npx * 3));
+    // the gather stores 16 labels at a time: device memory on a 16-byte boundary is written in place, anything else through a copy
+    const bool dev = is_device_ptr(labels), direct = dev && (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
+    DevBuf stage;
+    if (!direct) CNIIC_HIP_TRY(c, stage.alloc(npx * lb + 16));
+    CNIIC_TRY(palette_labels(pal->p, in.d, npx, direct ? labels : stage.p));
+    if (!direct) {
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(labels, stage.p, npx * lb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return CNIIC_OK;
+}
+
+int32_t cniic_palette_encode_frames_var(cniic_palette *pal, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out,
+                                        uint64_t stride, uint64_t *lens) {
+    if (!pal) return CNIIC_ERR_BAD_ARG;
+    cniic_ctx *c = static_cast<cniic_ctx *>(pal->c);
+    LOCK(c);
+    c->ktimes.clear();
+    if (!rgb || !w || !h || !out || !lens || !frames) return c->fail(CNIIC_ERR_BAD_ARG, "palette_encode_frames_var: null argument");
+    uint64_t n = 0;
+    for (uint32_t f = 0; f < frames; f++) {
+        const uint64_t np = (uint64_t)w[f] * h[f];
+        if (!np) return c->fail(CNIIC_ERR_BAD_ARG, "palette_encode_frames_var: frame %u is %u x %u", f, w[f], h[f]);
+        if (__builtin_add_overflow(n, np, &n) || n > (~0ull) / 3) return c->fail(CNIIC_ERR_BAD_ARG, "palette_encode_frames_var: too many pixels");
+    }
+    if (stride & 3) return c->fail(CNIIC_ERR_BAD_ARG, "palette_encode_frames_var: the stride between streams must be a multiple of 4");   // (before the image is bound)
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, n * 3));
+    return palette_encode_frames_var(pal->p, in.d, w, h, frames, out, stride, lens);
+}
+
+void cniic_palette_destroy(cniic_palette *pal) {
+    if (!pal) return;
+    {
+        std::lock_guard<std::mutex> lk(pal->c->mu);
+        (void)hipSetDevice(pal->c->device);
+        (void)hipStreamSynchronize(pal->c->stream);
+        PoolScope ps(&pal->c->pool);
+        delete pal->p;
+    }
+    delete pal;
+}
+
 // ------------------------------------------------------------------ remap
 int32_t cniic_remap_rgb(cniic_ctx *c, const uint8_t *rgb, uint64_t npx, const uint32_t *keys, const uint32_t *labels, uint64_t U,
                         const uint8_t *centroids, uint32_t K, uint8_t *out_rgb) {

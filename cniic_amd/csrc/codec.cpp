@@ -15,9 +15,11 @@
 #include <cctype>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <memory>
 
 #include "huff_host.hpp"
+#include "pal_bounds.hpp"
 
 namespace cniic {
 
@@ -667,6 +669,187 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     return rc_fin;
 }
 
+// ---- the frames of a batch, as everything behind "every pixel has a label" needs them: F equally sized frames of w x h (wv == nullptr), or
+// frame f of wv[f] x hv[f] with the table the kernels of the var route read (FrameVar, common.hpp).
+struct FrameBatch {
+    uint32_t w = 0, h = 0;                       // equally sized frames
+    const uint32_t *wv = nullptr, *hv = nullptr;   // frames of any sizes (host arrays)
+    uint32_t F = 0;
+    std::vector<FrameVar> ft;
+    DevBuf ft_d;
+    uint64_t lab_total = 0;      // elements of the aligned label buffer
+    uint32_t chunks = 0, hblocks = 0;
+    bool runs_aligned = true;
+    bool var() const { return wv != nullptr; }
+    // frames of any sizes: the frame table.  Label bases on 16-byte boundaries (16 elements, for labels of either width); when every
+    // run already starts on one where the pixel-label kernels write it, the bases are those and nothing is copied
+    int build_table(Ctx *c, const char *who, uint64_t lb) {
+        ft.resize(F);
+        uint64_t src = 0, ch = 0, hb = 0;
+        for (uint32_t f = 0; f < F; f++) {
+            const uint64_t np = (uint64_t)wv[f] * hv[f];
+            if ((src * lb) & 15) runs_aligned = false;
+            ft[f] = FrameVar{np, lab_total, src, (uint32_t)ch, (uint32_t)hb, wv[f], hv[f]};
+            src += np;
+            lab_total += (np + 15) & ~15ull;
+            ch += ceil_div(np, kFrameVarChunk);
+            hb += ceil_div(np, kFrameVarHistSpan);
+            if (ch > 0x7fffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "%s: too many pixels for one batch", who);
+        }
+        chunks = (uint32_t)ch;
+        hblocks = (uint32_t)hb;
+        if (runs_aligned)
+            for (uint32_t f = 0; f < F; f++) ft[f].lab_base = ft[f].src_base;
+        return CNIIC_OK;
+    }
+    int upload_table(Ctx *c) {
+        CNIIC_HIP_TRY(c, ft_d.alloc((uint64_t)F * sizeof(FrameVar)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(ft_d.p, ft.data(), (size_t)F * sizeof(FrameVar), hipMemcpyHostToDevice, c->stream));
+        return CNIIC_OK;
+    }
+};
+
+// From the labels of every pixel of a batch (pixlab_d: the frames' labels back to back, as the pixel-label kernels write them) to the F
+// streams at out + f * stride: per-frame label histograms, the frames' trees (k_frame_trees reading cent_d, the K palette entries as
+// 0xRRGGBB words -- or palette_code on host threads reading cent_h, K x 3 bytes), the lengths held against the stride, the label pack.
+// The two callers are a K-means session's finish_frames and a frozen palette's palette_encode_frames_var.  after_hist (optional) runs
+// once the histograms are enqueued and before the host waits for them: a session collects its K-means result there -- which is when
+// cent_h is filled in; nobody reads it earlier.  headers_aside: CNIIC_ERR_CAPACITY leaves `out` untouched on the k_frame_trees route as well (a
+// session's calls write the headers in place and refuse afterwards, as they always have).
+static int frames_tail(Ctx *c, const void *pixlab_d, bool wide, uint32_t K, const uint32_t *cent_d, const uint8_t *cent_h, const FrameBatch &fb, uint8_t *out,
+                       uint64_t stride, uint64_t *lens, const std::function<int()> &after_hist, bool headers_aside = false) {
+    const bool var = fb.var();
+    const uint32_t F = fb.F, w = fb.w, h = fb.h, chunks = fb.chunks, hblocks = fb.hblocks;
+    const uint32_t *wv = fb.wv, *hv = fb.hv;
+    const uint64_t lb = wide ? 2 : 1, npf = var ? 0 : (uint64_t)w * h, lab_total = fb.lab_total;
+    const bool runs_aligned = fb.runs_aligned;
+    const FrameVar *fr_d = var ? fb.ft_d.as<FrameVar>() : nullptr;
+    DevBuf pixlab_al, cnt_d;
+    // frames whose label run does not start on a 16-byte boundary are moved apart (the pack reads 16 labels per load)
+    const void *labs = pixlab_d;
+    uint64_t lab_stride = npf;
+    if (var) {
+        if (!runs_aligned) {
+            ScopedKernelTimer t(c, "frames_var_align");
+            CNIIC_HIP_TRY(c, pixlab_al.alloc(lab_total * lb + 16));
+            CNIIC_TRY(frame_labels_align_var(c, pixlab_d, pixlab_al.p, fr_d, F, chunks, wide));
+            labs = pixlab_al.p;
+            t.stop(1);
+        }
+    } else if ((npf * lb) & 15) {
+        lab_stride = (npf + 15) & ~15ull;
+        CNIIC_HIP_TRY(c, pixlab_al.alloc(lab_stride * lb * F + 16));
+        CNIIC_HIP_TRY(c, hipMemcpy2DAsync(pixlab_al.p, lab_stride * lb, pixlab_d, npf * lb, npf * lb, F, hipMemcpyDeviceToDevice, c->stream));
+        labs = pixlab_al.p;
+    }
+    CNIIC_HIP_TRY(c, cnt_d.alloc((uint64_t)F * K * 4));
+    if (var) {
+        ScopedKernelTimer t(c, "frames_var_hist");
+        CNIIC_TRY(frame_label_hist_var(c, labs, fr_d, F, hblocks, wide, K, cnt_d.as<uint32_t>()));
+        t.stop(1);
+    } else {
+        CNIIC_TRY(frame_label_hist(c, labs, npf, lab_stride, F, wide, K, cnt_d.as<uint32_t>()));
+    }
+    const bool gpu_trees = !wide && K <= 256 && c->opt(CNIIC_OPT_FRAME_TREES_HOST, "CNIIC_FRAME_TREES_HOST", 0) == 0;
+    std::vector<uint32_t> cnt(gpu_trees ? 0 : (size_t)F * K);
+    if (!gpu_trees) CNIIC_HIP_TRY(c, hipMemcpyAsync(cnt.data(), cnt_d.p, cnt.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    host_trace().mark("frames: hist enqueued");
+    if (after_hist) CNIIC_TRY(after_hist());
+    host_trace().mark("frames: result_end (sync)");
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    host_trace().mark("frames: wait for the histograms");
+    FramesOut fo(c, out, stride, F);
+    DevBuf clen_d, ccode_d;
+    CNIIC_HIP_TRY(c, clen_d.alloc((size_t)F * K));
+    CNIIC_HIP_TRY(c, ccode_d.alloc((size_t)F * K * 8));
+    std::vector<uint64_t> totals(F, 0);
+    // the label pack of every frame behind its header: bit bases on the host (bb_h) or already on the device (bb_d)
+    auto pack = [&](const uint64_t *bb_h, const uint64_t *bb_d) {
+        if (!var)
+            return huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bb_h, totals.data(), bb_d);
+        ScopedKernelTimer t(c, "frames_var_pack");
+        const int rc = huff_pack_labels_frames_var(c, labs, fr_d, F, chunks, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bb_h, totals.data(), bb_d);
+        t.stop(3);
+        return rc;
+    };
+    if (gpu_trees) {
+        // ---- K <= 256: codes, code tables and stream headers of all frames by one kernel (k_frame_trees); the host sees the
+        // lengths (it owes them to the caller and must hold them against the stride before anything is packed) and nothing else
+        // (headers_aside: the headers are built beside the output and copied in once the lengths are known to fit, so that a refused call
+        // leaves `out` as it was; a header is at most 8 + 12 K + (K - 1) bytes, and the pack wants the bytes behind it zero)
+        DevBuf hdr_d;
+        const uint64_t hstride = (8ull + 13ull * K + 3) & ~3ull;
+        if (headers_aside) {
+            CNIIC_HIP_TRY(c, hdr_d.alloc(hstride * F));
+            CNIIC_HIP_TRY(c, hipMemsetAsync(hdr_d.p, 0, hstride * F, c->stream));
+        } else {
+            CNIIC_TRY(fo.begin());
+        }
+        DevBuf meta_d;
+        CNIIC_HIP_TRY(c, meta_d.alloc((size_t)F * 24 + 8));  // bit base, payload bits, stream length per frame; error word
+        uint64_t *bb_d = meta_d.as<uint64_t>(), *nb_d = bb_d + F, *ln_d = nb_d + F;
+        uint32_t *err_d = reinterpret_cast<uint32_t *>(ln_d + F);
+        CNIIC_HIP_TRY(c, hipMemsetAsync(err_d, 0, 8, c->stream));
+        ScopedKernelTimer t_trees(c, "frames_var_trees", var && c->timers);
+        CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), cent_d, F, K, w, h, headers_aside ? hdr_d.as<uint8_t>() : fo.dev, headers_aside ? hstride : stride,
+                              clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d, fr_d));
+        t_trees.stop(1);
+        std::vector<uint64_t> meta((size_t)F * 3 + 1);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(meta.data(), meta_d.p, (size_t)F * 24 + 8, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        host_trace().mark("frames: trees, codes, headers (GPU) + lengths back");
+        const uint32_t err = (uint32_t)meta[(size_t)F * 3];
+        if (err & 3u) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
+        std::copy_n(meta.data() + 2 * (size_t)F, F, lens);
+        CNIIC_TRY(fo.check_lens(lens, (err & 4u) != 0));
+        if (headers_aside) {
+            uint64_t hmax = 0;   // the longest header, in whole words: within hstride, and within the stride since every stream fits
+            for (uint32_t f = 0; f < F; f++) hmax = std::max<uint64_t>(hmax, (meta[f] / 8 + 3) & ~3ull);
+            CNIIC_TRY(fo.begin());
+            CNIIC_HIP_TRY(c, hipMemcpy2DAsync(fo.dev, stride, hdr_d.p, hstride, hmax, F, hipMemcpyDeviceToDevice, c->stream));
+        }
+        CNIIC_TRY(pack(nullptr, bb_d));
+        host_trace().mark("frames: pack (+sync)");
+        CNIIC_TRY(fo.finish(totals.data(), meta.data() + F));
+        host_trace().dump();
+        return CNIIC_OK;
+    }
+    // ---- per frame on the host, on a few threads: tree, stream header and per-cluster codes from the frame's pixels per cluster
+    std::vector<std::vector<uint8_t>> headers(F);
+    std::vector<uint8_t> clen((size_t)F * K);
+    std::vector<uint64_t> ccode((size_t)F * K), nbits(F, 0);
+    std::atomic<int> bad{0};
+    parallel_for(F, std::max(1u, std::min({F, 16u, std::thread::hardware_concurrency()})), [&](uint32_t f, uint32_t) {
+        if (!palette_code(cent_h, cnt.data() + (size_t)f * K, K, var ? wv[f] : w, var ? hv[f] : h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K],
+                          &nbits[f]))
+            bad = 1;
+    });
+    host_trace().mark("frames: trees, codes, headers (host threads)");
+    if (bad) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
+    uint64_t hmax = 0;
+    for (uint32_t f = 0; f < F; f++) {
+        lens[f] = headers[f].size() + (nbits[f] + 7) / 8;
+        hmax = std::max<uint64_t>(hmax, headers[f].size());
+    }
+    CNIIC_TRY(fo.check_lens(lens));
+    hmax = (hmax + 3) & ~3ull;
+    CNIIC_TRY(fo.begin());
+    DevBuf hdr_d;
+    std::vector<uint8_t> hdr_all(hmax * F, 0);
+    std::vector<uint64_t> bit_base(F);
+    for (uint32_t f = 0; f < F; f++) { memcpy(hdr_all.data() + hmax * f, headers[f].data(), headers[f].size()); bit_base[f] = headers[f].size() * 8; }
+    CNIIC_HIP_TRY(c, hdr_d.alloc(hdr_all.size()));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(hdr_d.p, hdr_all.data(), hdr_all.size(), hipMemcpyHostToDevice, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpy2DAsync(fo.dev, stride, hdr_d.p, hmax, hmax, F, hipMemcpyDeviceToDevice, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(clen_d.p, clen.data(), clen.size(), hipMemcpyHostToDevice, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(ccode_d.p, ccode.data(), ccode.size() * 8, hipMemcpyHostToDevice, c->stream));
+    CNIIC_TRY(pack(bit_base.data(), nullptr));
+    host_trace().mark("frames: copies + pack (+sync)");
+    CNIIC_TRY(fo.finish(totals.data(), nbits.data()));
+    host_trace().dump();
+    return CNIIC_OK;
+}
+
 // A batch of F frames (contiguous in rgb_d) coded with ONE palette -- north_star config 4: the K-means ran over the union of all the
 // pixels (of all ranks); every frame is then its own Hufman stream (clusterc.rs:31-52 per frame: the reduced frame's own histogram,
 // tree and payload), written at out + f * stride.  One pass gives every pixel's label, one kernel the pixels per (frame, cluster), the
@@ -709,43 +892,18 @@ static int finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_
     }
     const bool wide = km_rgbw_is_wide(km);
     const uint64_t lb = wide ? 2 : 1;
-    // ---- frames of any sizes: the frame table.  Label bases on 16-byte boundaries (16 elements, for labels of either width); when every
-    // run already starts on one where the pixel-label kernels write it, the bases are those and nothing is copied
-    std::vector<FrameVar> ft;
-    uint64_t lab_total = 0;      // elements of the aligned label buffer
-    uint32_t chunks = 0, hblocks = 0;
-    bool runs_aligned = true;
-    if (var) {
-        ft.resize(F);
-        uint64_t src = 0, ch = 0, hb = 0;
-        for (uint32_t f = 0; f < F; f++) {
-            const uint64_t np = (uint64_t)wv[f] * hv[f];
-            if ((src * lb) & 15) runs_aligned = false;
-            ft[f] = FrameVar{np, lab_total, src, (uint32_t)ch, (uint32_t)hb, wv[f], hv[f]};
-            src += np;
-            lab_total += (np + 15) & ~15ull;
-            ch += ceil_div(np, kFrameVarChunk);
-            hb += ceil_div(np, kFrameVarHistSpan);
-            if (ch > 0x7fffffffull) return c->fail(CNIIC_ERR_BAD_ARG, "%s: too many pixels for one batch", who);
-        }
-        chunks = (uint32_t)ch;
-        hblocks = (uint32_t)hb;
-        if (runs_aligned)
-            for (uint32_t f = 0; f < F; f++) ft[f].lab_base = ft[f].src_base;
-    }
+    FrameBatch fb;
+    fb.w = w; fb.h = h; fb.wv = wv; fb.hv = hv; fb.F = F;
+    if (var) CNIIC_TRY(fb.build_table(c, who, lb));
     std::vector<uint8_t> cent(3 * (size_t)K);
     std::vector<uint64_t> members(K), wsum(K);
     cniic_kmeans_stats st{};
     CNIIC_TRY(km_rgbw_result_begin(km));
-    DevBuf lab_d, key2label, pixlab, pixlab_al, cnt_d, ft_d;
+    DevBuf lab_d, key2label, pixlab;
     host_trace().mark("frames: result_begin");
     CNIIC_HIP_TRY(c, pixlab.alloc(n * lb + 16));
     host_trace().mark("frames: alloc pixel labels");
-    if (var) {
-        CNIIC_HIP_TRY(c, ft_d.alloc((uint64_t)F * sizeof(FrameVar)));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(ft_d.p, ft.data(), (size_t)F * sizeof(FrameVar), hipMemcpyHostToDevice, c->stream));
-    }
-    const FrameVar *fr_d = var ? ft_d.as<FrameVar>() : nullptr;
+    if (var) CNIIC_TRY(fb.upload_table(c));
     ScopedKernelTimer t_labels(c, "frames_var_labels", var && c->timers);
     if (s->sp_mode) {
         uint32_t *cell_start, *ckeys, *cweight;
@@ -760,115 +918,11 @@ static int finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_
         CNIIC_TRY(pixel_labels(c, rgb_d, n, key2label.p, wide, pixlab.p));
     }
     t_labels.stop(1);
-    // frames whose label run does not start on a 16-byte boundary are moved apart (the pack reads 16 labels per load)
-    const void *labs = pixlab.p;
-    uint64_t lab_stride = npf;
-    if (var) {
-        if (!runs_aligned) {
-            ScopedKernelTimer t(c, "frames_var_align");
-            CNIIC_HIP_TRY(c, pixlab_al.alloc(lab_total * lb + 16));
-            CNIIC_TRY(frame_labels_align_var(c, pixlab.p, pixlab_al.p, fr_d, F, chunks, wide));
-            labs = pixlab_al.p;
-            t.stop(1);
-        }
-    } else if ((npf * lb) & 15) {
-        lab_stride = (npf + 15) & ~15ull;
-        CNIIC_HIP_TRY(c, pixlab_al.alloc(lab_stride * lb * F + 16));
-        CNIIC_HIP_TRY(c, hipMemcpy2DAsync(pixlab_al.p, lab_stride * lb, pixlab.p, npf * lb, npf * lb, F, hipMemcpyDeviceToDevice, c->stream));
-        labs = pixlab_al.p;
-    }
-    CNIIC_HIP_TRY(c, cnt_d.alloc((uint64_t)F * K * 4));
-    if (var) {
-        ScopedKernelTimer t(c, "frames_var_hist");
-        CNIIC_TRY(frame_label_hist_var(c, labs, fr_d, F, hblocks, wide, K, cnt_d.as<uint32_t>()));
-        t.stop(1);
-    } else {
-        CNIIC_TRY(frame_label_hist(c, labs, npf, lab_stride, F, wide, K, cnt_d.as<uint32_t>()));
-    }
-    const bool gpu_trees = !wide && K <= 256 && c->opt(CNIIC_OPT_FRAME_TREES_HOST, "CNIIC_FRAME_TREES_HOST", 0) == 0;
-    std::vector<uint32_t> cnt(gpu_trees ? 0 : (size_t)F * K);
-    if (!gpu_trees) CNIIC_HIP_TRY(c, hipMemcpyAsync(cnt.data(), cnt_d.p, cnt.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    host_trace().mark("frames: hist enqueued");
-    CNIIC_TRY(km_rgbw_result_end(km, cent.data(), members.data(), wsum.data(), &st));
-    if (stats) *stats = st;
-    CNIIC_TRY(check_enough_active(c, K, U, st.active));
-    host_trace().mark("frames: result_end (sync)");
-    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    host_trace().mark("frames: wait for the histograms");
-    FramesOut fo(c, out, stride, F);
-    DevBuf clen_d, ccode_d;
-    CNIIC_HIP_TRY(c, clen_d.alloc((size_t)F * K));
-    CNIIC_HIP_TRY(c, ccode_d.alloc((size_t)F * K * 8));
-    std::vector<uint64_t> totals(F, 0);
-    // the label pack of every frame behind its header: bit bases on the host (bb_h) or already on the device (bb_d)
-    auto pack = [&](const uint64_t *bb_h, const uint64_t *bb_d) {
-        if (!var)
-            return huff_pack_labels_frames(c, labs, npf, lab_stride, F, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bb_h, totals.data(), bb_d);
-        ScopedKernelTimer t(c, "frames_var_pack");
-        const int rc = huff_pack_labels_frames_var(c, labs, fr_d, F, chunks, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), fo.dev, stride, bb_h, totals.data(), bb_d);
-        t.stop(3);
-        return rc;
-    };
-    if (gpu_trees) {
-        // ---- K <= 256: codes, code tables and stream headers of all frames by one kernel (k_frame_trees); the host sees the
-        // lengths (it owes them to the caller and must hold them against the stride before anything is packed) and nothing else
-        CNIIC_TRY(fo.begin());
-        DevBuf meta_d;
-        CNIIC_HIP_TRY(c, meta_d.alloc((size_t)F * 24 + 8));  // bit base, payload bits, stream length per frame; error word
-        uint64_t *bb_d = meta_d.as<uint64_t>(), *nb_d = bb_d + F, *ln_d = nb_d + F;
-        uint32_t *err_d = reinterpret_cast<uint32_t *>(ln_d + F);
-        CNIIC_HIP_TRY(c, hipMemsetAsync(err_d, 0, 8, c->stream));
-        ScopedKernelTimer t_trees(c, "frames_var_trees", var && c->timers);
-        CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), km_rgbw_centroids_dev(km), F, K, w, h, fo.dev, stride, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d, fr_d));
-        t_trees.stop(1);
-        std::vector<uint64_t> meta((size_t)F * 3 + 1);
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(meta.data(), meta_d.p, (size_t)F * 24 + 8, hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        host_trace().mark("frames: trees, codes, headers (GPU) + lengths back");
-        const uint32_t err = (uint32_t)meta[(size_t)F * 3];
-        if (err & 3u) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
-        std::copy_n(meta.data() + 2 * (size_t)F, F, lens);
-        CNIIC_TRY(fo.check_lens(lens, (err & 4u) != 0));
-        CNIIC_TRY(pack(nullptr, bb_d));
-        host_trace().mark("frames: pack (+sync)");
-        CNIIC_TRY(fo.finish(totals.data(), meta.data() + F));
-        host_trace().dump();
-        return CNIIC_OK;
-    }
-    // ---- per frame on the host, on a few threads: tree, stream header and per-cluster codes from the frame's pixels per cluster
-    std::vector<std::vector<uint8_t>> headers(F);
-    std::vector<uint8_t> clen((size_t)F * K);
-    std::vector<uint64_t> ccode((size_t)F * K), nbits(F, 0);
-    std::atomic<int> bad{0};
-    parallel_for(F, std::max(1u, std::min({F, 16u, std::thread::hardware_concurrency()})), [&](uint32_t f, uint32_t) {
-        if (!palette_code(cent.data(), cnt.data() + (size_t)f * K, K, var ? wv[f] : w, var ? hv[f] : h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K],
-                          &nbits[f]))
-            bad = 1;
+    return frames_tail(c, pixlab.p, wide, K, km_rgbw_centroids_dev(km), cent.data(), fb, out, stride, lens, [&]() -> int {
+        CNIIC_TRY(km_rgbw_result_end(km, cent.data(), members.data(), wsum.data(), &st));
+        if (stats) *stats = st;
+        return check_enough_active(c, K, U, st.active);
     });
-    host_trace().mark("frames: trees, codes, headers (host threads)");
-    if (bad) return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
-    uint64_t hmax = 0;
-    for (uint32_t f = 0; f < F; f++) {
-        lens[f] = headers[f].size() + (nbits[f] + 7) / 8;
-        hmax = std::max<uint64_t>(hmax, headers[f].size());
-    }
-    CNIIC_TRY(fo.check_lens(lens));
-    hmax = (hmax + 3) & ~3ull;
-    CNIIC_TRY(fo.begin());
-    DevBuf hdr_d;
-    std::vector<uint8_t> hdr_all(hmax * F, 0);
-    std::vector<uint64_t> bit_base(F);
-    for (uint32_t f = 0; f < F; f++) { memcpy(hdr_all.data() + hmax * f, headers[f].data(), headers[f].size()); bit_base[f] = headers[f].size() * 8; }
-    CNIIC_HIP_TRY(c, hdr_d.alloc(hdr_all.size()));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(hdr_d.p, hdr_all.data(), hdr_all.size(), hipMemcpyHostToDevice, c->stream));
-    CNIIC_HIP_TRY(c, hipMemcpy2DAsync(fo.dev, stride, hdr_d.p, hmax, hmax, F, hipMemcpyDeviceToDevice, c->stream));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(clen_d.p, clen.data(), clen.size(), hipMemcpyHostToDevice, c->stream));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(ccode_d.p, ccode.data(), ccode.size() * 8, hipMemcpyHostToDevice, c->stream));
-    CNIIC_TRY(pack(bit_base.data(), nullptr));
-    host_trace().mark("frames: copies + pack (+sync)");
-    CNIIC_TRY(fo.finish(totals.data(), nbits.data()));
-    host_trace().dump();
-    return CNIIC_OK;
 }
 
 int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
@@ -880,6 +934,86 @@ int cc_finish_frames_var(CcSession *s, const uint8_t *rgb_d, const uint32_t *w, 
                          cniic_kmeans_stats *stats) {
     if (!w || !h) return s->c->fail(CNIIC_ERR_BAD_ARG, "cc_finish_frames_var: null argument");
     return finish_frames(s, rgb_d, 0, 0, w, h, F, out, stride, lens, stats);
+}
+
+// ------------------------------------------------------------------ frozen palettes (cniic_palette_*, k_palette.hip)
+// The session's centroids as of its last update and the pixels per cluster it knows (its wsum), through the session's own rule for results:
+// km_rgbw_result_begin / _end, with the hand-over of a persistent launch that had given up (kKmRetry).  Nothing of the session changes.
+int cc_palette(CcSession *s, uint8_t *centroids_h, uint64_t *pixels_h) {
+    KmRgbwState *km = s->km;
+    for (int attempt = 0;; attempt++) {
+        CNIIC_TRY(km_rgbw_result_begin(km));
+        const int rc = km_rgbw_result_end(km, centroids_h, nullptr, pixels_h, nullptr);
+        if (rc == kKmRetry && attempt == 0) continue;
+        return rc;
+    }
+}
+
+// cent_h: K x 3 bytes on the host.  The colour -> label table of all 2^24 colours is built here, once; the handle keeps it, the entries as
+// the 0xRRGGBB words k_frame_trees reads, and the host copy palette_code reads.
+int palette_create(Ctx *c, const uint8_t *cent_h, uint32_t K, Palette **out) {
+    if (!K || K > 65536u) return c->fail(CNIIC_ERR_BAD_ARG, "palette_create: K = %u (1 .. 65536)", K);
+    std::unique_ptr<Palette> p(new Palette);
+    p->c = c;
+    p->K = K;
+    p->wide = K > 256;
+    p->cent_h.assign(cent_h, cent_h + 3 * (size_t)K);
+    std::vector<uint32_t> words(K);
+    for (uint32_t k = 0; k < K; k++) words[k] = ((uint32_t)cent_h[3 * k] << 16) | ((uint32_t)cent_h[3 * k + 1] << 8) | cent_h[3 * k + 2];
+    CNIIC_HIP_TRY(c, p->cent_d.alloc((uint64_t)K * 4));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(p->cent_d.p, words.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    CNIIC_HIP_TRY(c, p->table.alloc((1ull << 24) * (p->wide ? 2 : 1)));
+    uint32_t list_max = kPalListMax;   // (the testing build: a budget low enough for ordinary palettes to take the plain route)
+    if (const char *e = test_env("CNIIC_TEST_PAL_LIST_MAX")) list_max = (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), kPalListMax);
+    DevBuf plain_d;
+    if (c->timers) {
+        CNIIC_HIP_TRY(c, plain_d.alloc(4));
+        CNIIC_HIP_TRY(c, hipMemsetAsync(plain_d.p, 0, 4, c->stream));
+    }
+    {
+        ScopedKernelTimer t(c, "pal_lut");
+        CNIIC_TRY(palette_lut(c, p->cent_d.as<uint32_t>(), K, p->wide, p->table.p, list_max, c->timers ? plain_d.as<uint32_t>() : nullptr));
+        t.stop(1);
+    }
+    uint32_t plain = 0;
+    if (c->timers) CNIIC_HIP_TRY(c, hipMemcpyAsync(&plain, plain_d.p, 4, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the words above are this call's; a handle that comes back is complete)
+    if (plain) c->ktimes["pal_lut_plain"].launches += plain;   // (stage timers: how many cells took the plain route; no duration)
+    *out = p.release();
+    return CNIIC_OK;
+}
+
+// the index image: labels_d receives n labels of 1 or 2 bytes (16-byte aligned device memory)
+int palette_labels(Palette *p, const uint8_t *rgb_d, uint64_t n, void *labels_d) {
+    Ctx *c = p->c;
+    ScopedKernelTimer t(c, "pal_labels");
+    CNIIC_TRY(pixel_labels(c, rgb_d, n, p->table.p, p->wide, labels_d));
+    t.stop(1);
+    return CNIIC_OK;
+}
+
+// cc_finish_frames_var with the gather through the handle's table in the place of a session's labels: no K-means state, no pixel total
+// to hold the batch against, no active-cluster check
+int palette_encode_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *wv, const uint32_t *hv, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens) {
+    Ctx *c = p->c;
+    const char *who = "palette_encode_frames_var";
+    if (!wv || !hv || !F) return c->fail(CNIIC_ERR_BAD_ARG, "%s: empty batch", who);
+    uint64_t n = 0;
+    for (uint32_t f = 0; f < F; f++) {
+        const uint64_t np = (uint64_t)wv[f] * hv[f];
+        if (!np) return c->fail(CNIIC_ERR_BAD_ARG, "%s: frame %u is %u x %u", who, f, wv[f], hv[f]);
+        if (__builtin_add_overflow(n, np, &n)) return c->fail(CNIIC_ERR_BAD_ARG, "%s: too many pixels", who);
+    }
+    if (stride & 3) return c->fail(CNIIC_ERR_BAD_ARG, "%s: the stride between streams must be a multiple of 4", who);
+    const uint64_t lb = p->wide ? 2 : 1;
+    FrameBatch fb;
+    fb.wv = wv; fb.hv = hv; fb.F = F;
+    CNIIC_TRY(fb.build_table(c, who, lb));
+    DevBuf pixlab;
+    CNIIC_HIP_TRY(c, pixlab.alloc(n * lb + 16));
+    CNIIC_TRY(fb.upload_table(c));
+    CNIIC_TRY(palette_labels(p, rgb_d, n, pixlab.p));
+    return frames_tail(c, pixlab.p, p->wide, p->K, p->cent_d.as<uint32_t>(), p->cent_h.data(), fb, out, stride, lens, nullptr, true);
 }
 
 // images of at least this many pixels take the super-cell partition (k_points.hip); CNIIC_SP_MIN_PIXELS overrides (tests: 0)

@@ -135,6 +135,23 @@ int cc_finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h,
 int cc_finish_frames_var(CcSession *s, const uint8_t *rgb_d, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens,
                          cniic_kmeans_stats *stats);
 
+// the session's centroids (K x 3 bytes) and the pixels per cluster it knows (may be null), as of its last update
+int cc_palette(CcSession *s, uint8_t *centroids_h, uint64_t *pixels_h);
+
+// A frozen palette (cniic_palette_*): K entries and the label of every one of the 2^24 colours under "nearest entry in squared integer
+// distance, lowest index among equals" (k_palette.hip).  It belongs to its context and stream; nothing of a K-means is behind it.
+struct Palette {
+    Ctx *c = nullptr;
+    uint32_t K = 0;
+    bool wide = false;             // two-byte labels (K > 256)
+    DevBuf table;                  // u8 / u16 [2^24]: colour key -> label
+    DevBuf cent_d;                 // u32[K] 0xRRGGBB, what k_frame_trees reads
+    std::vector<uint8_t> cent_h;   // K x 3 bytes, what palette_code reads
+};
+int palette_create(Ctx *c, const uint8_t *cent_h, uint32_t K, Palette **out);
+int palette_labels(Palette *p, const uint8_t *rgb_d, uint64_t n, void *labels_d /* 16-byte aligned */);
+int palette_encode_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens);
+
 // header carries any prefix already serialised (image dimensions); the decoder trie is appended
 // to it and the whole stream lands in out[0..*len)  (out: host or device memory).
 // syms_scratch: the symbol stream is ours and may be overwritten.

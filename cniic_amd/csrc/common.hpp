@@ -832,5 +832,9 @@ int frame_label_hist_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint3
 int huff_pack_labels_frames_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide, uint32_t K, const uint8_t *clen_d,
                                 const uint64_t *ccode_d, uint8_t *out_d, uint64_t stride, const uint64_t *bit_base_h, uint64_t *totals_h, const uint64_t *bit_base_d = nullptr);
 int sum_u32_dev(Ctx *c, const uint32_t *v_d, uint64_t n, uint64_t *out_d);   // *out_d = the sum of n u32
+// ---- k_palette.hip: the colour -> label table of a frozen palette (every colour's nearest entry, lowest index among equals).  table_d: 2^24
+// labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
+// down the plain route; plain_cells_d (optional): a zeroed counter of such cells
+int palette_lut(Ctx *c, const uint32_t *cent_d, uint32_t K, bool wide, void *table_d, uint32_t list_max, uint32_t *plain_cells_d);
 
 }  // namespace cniic

@@ -146,6 +146,14 @@ class HipBackend:
             return rc, [int(lens[f]) for f in range(F)], st.as_dict()
         return [int(lens[f]) for f in range(F)], st.as_dict()
 
+    def palette(self, h, K):
+        """cniic_cc_palette: the session's centroids ((K, 3) uint8) and the pixels per cluster it knows (uint64[K]), as of its last update;
+        the session stays usable"""
+        import numpy as np
+        cent, pixels = np.zeros((K, 3), np.uint8), np.zeros(K, np.uint64)
+        self.ctx._check(self.L.cniic_cc_palette(h, _lib._ptr(cent), _lib._ptr(pixels)))
+        return cent, pixels
+
     def destroy(self, h):
         self.L.cniic_cc_destroy(h)
 
@@ -334,6 +342,15 @@ class ShardedClusterColors:
         handle, partials = self._cluster(frames_flat, sum(int(a) * int(b) for a, b in zip(ws, hs)))
         try:
             return self.be.finish_frames_var(handle, frames_flat, ws, hs, out, stride)
+        finally:
+            self.be.destroy(handle)
+
+    def palette(self, frames_flat, npx):
+        """the shared palette itself, for frames that are not there yet: cluster this rank's npx pixels (and everybody else's) and return
+        ((K, 3) uint8 centroids, uint64[K] pixels per cluster) -- what cniic_amd.Palette.create takes, here or on another rank or day"""
+        handle, partials = self._cluster(frames_flat, npx)
+        try:
+            return self.be.palette(handle, self.K)
         finally:
             self.be.destroy(handle)
 

@@ -262,6 +262,47 @@ int32_t  cniic_cc_finish_frames_var(cniic_cc *cc, const uint8_t *rgb, const uint
                                     uint8_t *out, uint64_t stride, uint64_t *lens, cniic_kmeans_stats *stats);
 void     cniic_cc_destroy(cniic_cc *cc);
 
+/* ---- Frozen palettes: code further frames with a palette that already exists -- a video whose frames keep arriving, new tiles of the
+ * same map, a folder whose palette was built on a sample, two ranks that agree on a palette by sending K x 3 bytes.
+ *
+ * THE RULE.  A pixel's label is the index k that minimises (r - R_k)^2 + (g - G_k)^2 + (b - B_k)^2 in integers; among equal minima it is
+ * the lowest k.  This is Rgb<u8>::dist (geom.rs:8-24) compared as squared integers, with first-minimum ties.  Nothing else is defined:
+ * there is no "stay" rule, because there is no previous assignment.  Two consequences:
+ *   - For the frames a converged session was run on, this is the assignment the K-means ended with, except where a colour is equidistant
+ *     from two entries: there the K-means keeps the older cluster and this rule takes the lower index.  So the streams can differ from
+ *     cniic_cc_finish_frames_var's only at such ties.
+ *   - The error can never be larger than the session's: every pixel gets a nearest entry.
+ * Equal palette entries are legal; the lowest index wins.  The stream's alphabet is colours, as in clusterc.rs:31-52: two entries of
+ * one colour are one symbol.  The streams are ordinary cluster-colors(K) streams, which cniic_codec_decode and cniic_codec_decode_batch
+ * read.
+ *
+ * cniic_cc_palette (stands in for cniic_km_result, which a cniic_cc does not have): the session's centroids as of its last update into
+ * centroids (host memory, K x 3 bytes: r, g, b) and, when pixels is not NULL, the pixels per cluster the session knows (its wsum; host
+ * array of K entries).  Before the loop has finished it returns what the session's results are at that moment.  The session stays
+ * usable for a later cniic_cc_finish*. */
+int32_t  cniic_cc_palette(cniic_cc *cc, uint8_t *centroids, uint64_t *pixels);
+/* A handle on K entries (centroids: host or device memory, K x 3 bytes; K from 1 to 65 536) and on the label of every one of the 2^24
+ * colours under the rule: u8 for K <= 256, u16 above, built once here (k_palette.hip).  It belongs to its context and stream, like a
+ * session; one handle is used from one thread at a time, for any number of calls.  CNIIC_ERR_BAD_ARG: K == 0, K > 65 536, a null
+ * pointer.  With the stage timers on: "pal_lut" = the table kernel, "pal_lut_plain" (launches only) = the cells of the colour cube whose
+ * candidate list was too long for LDS and which scanned all K entries instead. */
+typedef struct cniic_palette cniic_palette;
+int32_t  cniic_palette_create(cniic_ctx *ctx, const uint8_t *centroids, uint32_t K, cniic_palette **out);
+void     cniic_palette_destroy(cniic_palette *pal);
+uint32_t cniic_palette_label_bytes(cniic_palette *pal);   /* 1 (K <= 256) or 2: element size of the labels */
+/* The index image (what remap's lookup stands on, clusterc.rs:43-47): labels receives npx entries of cniic_palette_label_bytes(pal)
+ * bytes, host or device memory; rgb likewise.  Stage timer: "pal_labels". */
+int32_t  cniic_palette_labels(cniic_palette *pal, const uint8_t *rgb, uint64_t npx, void *labels);
+/* cniic_cc_finish_frames_var without a session: frame f is w[f] x h[f], the frames back to back in rgb, stream f (ClusterColors::encode,
+ * clusterc.rs:31-52, applied to frame f with the handle's palette under the rule above) at out + f * stride, its length in lens[f].
+ * Layout, the stride rule (a multiple of 4) and CNIIC_ERR_CAPACITY (the lengths needed in lens, nothing packed, out untouched) are those of
+ * cniic_cc_finish_frames_var; so are the CNIIC_ERR_BAD_ARG cases -- a null argument or frames == 0, any w[f] * h[f] == 0, stride & 3 --
+ * without the pixel total, which there is no session to hold against.  frames == 1 is the single image.  There is no active-cluster
+ * check: that belongs to a K-means (kmeans.rs:41-57), not to a palette.  rgb and out may be host or device memory and are staged as
+ * cniic_cc_finish_frames_var stages them.  Stage timers: "pal_labels", then the frames_var_* names of that call. */
+int32_t  cniic_palette_encode_frames_var(cniic_palette *pal, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                         uint8_t *out, uint64_t stride, uint64_t *lens);
+
 /* The same shared palette with every rank holding ONLY ITS OWN image's colours (per-rank work and memory do not
  * grow with the number of ranks, no label exchange).  The reference's point list -- the ascending list of the
  * distinct colours of all the pixels -- is then known to every rank as a bitmap:
