@@ -32,6 +32,7 @@
 // (v_mul_i32_i24 / v_mad_i32_i24); the 32-bit v_mul_lo_u32 is quarter rate on CDNA.
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "xy_bounds.hpp"   // xy_div_floor, Box5, centre_dist, Dominance: host and device, checked without a GPU by tests/xy_bounds_check.cpp
 
 namespace cniic {
 
@@ -127,58 +128,10 @@ __global__ void k_xy_super_boxes(const uint2 *__restrict__ box, uint32_t tiles_x
     sbox[s] = make_uint2(lo[0] | (hi[0] << 8) | (lo[1] << 16) | (hi[1] << 24), lo[2] | (hi[2] << 8));
 }
 
-// floor(sum / m) for a centroid's coordinate: sum < 2^42 (a coordinate below 2^14 times at most 2^28 members), m < 2^32, quotient < 2^14.
-// A SINGLE-precision estimate is within one of it (relative error 3 * 2^-24 on a value below 2^14) and is put right with one 32 x 32 -> 64
-// product; two steps either way are allowed for.  (Until round 4: a double quotient and 64 x 64 products, five per changed centroid and
-// 2048 centroids per block and launch -- the folded-in update's 2.5 us.)
-__device__ __forceinline__ uint32_t xy_div_floor(unsigned long long sum, uint32_t m, float rm) {
-    uint32_t e = (uint32_t)((float)sum * rm);
-    unsigned long long em = (unsigned long long)e * m;
-    if (em > sum) { e--; em -= m; if (em > sum) e--; }
-    else if (em + m <= sum) { e++; em += m; if (em + m <= sum) e++; }
-    return e;
-}
-
-struct Box5 { int32_t lo[5], hi[5]; };  // x, y, r, g, b extents
-
 __device__ __forceinline__ void box_colours(Box5 &b, uint2 pb) {
     b.lo[2] = pb.x & 255; b.hi[2] = (pb.x >> 8) & 255; b.lo[3] = (pb.x >> 16) & 255; b.hi[3] = pb.x >> 24;
     b.lo[4] = pb.y & 255; b.hi[4] = (pb.y >> 8) & 255;
 }
-
-// squared distance from the box centre to a centroid
-__device__ __forceinline__ uint32_t centre_dist(const Box5 &b, int4 c) {
-    int32_t d = 0;
-    const int32_t v[5] = {c.x, c.y, (c.z >> 16) & 255, (c.z >> 8) & 255, c.z & 255};
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const int32_t e = v[i] - ((b.lo[i] + b.hi[i]) >> 1);
-        d = xmad24(e, e, d);
-    }
-    return (uint32_t)d;
-}
-
-// the pivot against one box: a[2 i] = c*_i - 2 lo_i, a[2 i + 1] = c*_i - 2 hi_i
-struct Dominance {
-    int32_t p[5], a[10];
-    __device__ __forceinline__ void set(const Box5 &b, int4 pv) {
-        p[0] = pv.x; p[1] = pv.y; p[2] = (pv.z >> 16) & 255; p[3] = (pv.z >> 8) & 255; p[4] = pv.z & 255;
-#pragma unroll
-        for (int i = 0; i < 5; i++) { a[2 * i] = p[i] - 2 * b.lo[i]; a[2 * i + 1] = p[i] - 2 * b.hi[i]; }
-    }
-    // max over the box of d(p, pivot) - d(p, c): c can be nearest (or tie) somewhere in the box only if >= 0.
-    // |c* - k| < 2^14 and |c* + k - 2p| < 2^15: 24-bit products, and the five terms sum below 2^31.
-    __device__ __forceinline__ int32_t worst(int4 c) const {
-        const int32_t v[5] = {c.x, c.y, (c.z >> 16) & 255, (c.z >> 8) & 255, c.z & 255};
-        int32_t f = 0;
-#pragma unroll
-        for (int i = 0; i < 5; i++) {
-            const int32_t d = p[i] - v[i];
-            f += max(__mul24(d, v[i] + a[2 * i]), __mul24(d, v[i] + a[2 * i + 1]));
-        }
-        return f;
-    }
-};
 
 // position of the i-th set bit of m (i < popcount(m)); wave-uniform arguments: scalar code
 __device__ __forceinline__ uint32_t nth_set_bit(uint32_t m, uint32_t i) {

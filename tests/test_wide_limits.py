@@ -1,7 +1,8 @@
 """The reference takes ANY cluster count and image size (src/codec/clusterc.rs:116-141, 274-297: `\\d+` into a usize; src/kmeans.rs:67-68
-only asks for len >= K).  The tuned kernels stop at K = 2048 (cluster-colors) and at K = 2048 / sides of 16384 (voronoi); beyond that
-cniic_amd/csrc/k_kmeans_wide.hip runs the same K-means exactly and slowly.  Here: those routes against the oracle -- K = 4096 and 5000,
-a 1 x 20000 strip, a 17000-wide sliver -- through the K-means ABI and through the codecs."""
+only asks for len >= K).  The tuned kernels stop at K = 2048 (cluster-colors) and at K = 4096 / sides of 16384 (voronoi: the tiled 5-D kernel
+keeps its centroid table in LDS up to K = 2656 and reads it from memory up to 4096, tests/test_xyrgb_limits.py); beyond that
+cniic_amd/csrc/k_kmeans_wide.hip runs the same K-means exactly and slowly.  Here: those routes against the oracle -- K = 4096 and 5000 (4100 for
+voronoi), a 1 x 20000 strip, a 17000-wide sliver -- through the K-means ABI and through the codecs."""
 import numpy as np
 import pytest
 
