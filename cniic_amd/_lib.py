@@ -45,6 +45,7 @@ SYMBOLS = [
     "cniic_cc_finish_frames_var",
     "cniic_cc_palette", "cniic_palette_create", "cniic_palette_destroy", "cniic_palette_label_bytes", "cniic_palette_labels",
     "cniic_palette_encode_frames_var",
+    "cniic_kmeans_rgbw_from", "cniic_kmeans_xyrgb_from", "cniic_cc_set_centroids", "cniic_codec_encode_warm", "cniic_palette_fit_frames_var",
 ]
 
 
@@ -123,6 +124,8 @@ def lib():
                                                  C.POINTER(C.c_uint64), C.c_void_p]
         if hasattr(L, "cniic_cc_palette"):   # (CNIIC_LIB_FILE may name an older build of the library, for a comparison: it has no palettes)
             _palette_prototypes(L)
+        if hasattr(L, "cniic_cc_set_centroids"):   # (likewise: K-means from given centroids, the fit of a handle)
+            _warm_prototypes(L)
         _lib = L
     return _lib
 
@@ -141,6 +144,16 @@ def _palette_prototypes(L):
     L.cniic_palette_encode_frames_var.restype = C.c_int32
     L.cniic_palette_encode_frames_var.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_uint64,
                                                   C.POINTER(C.c_uint64)]
+
+
+def _warm_prototypes(L):
+    L.cniic_cc_set_centroids.restype = C.c_int32
+    L.cniic_cc_set_centroids.argtypes = [C.c_void_p, C.c_void_p]
+    L.cniic_palette_fit_frames_var.restype = C.c_int32
+    L.cniic_palette_fit_frames_var.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_void_p]
+    L.cniic_codec_encode_warm.restype = C.c_int32
+    L.cniic_codec_encode_warm.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
 
 
 def _ptr(x):
@@ -249,7 +262,8 @@ class Context:
     def _opts(seed=0, max_iters=0, flags=0):
         return KmOpts(seed, max_iters, flags, 0)
 
-    def kmeans_rgbw(self, keys, weight, K, seed=0, max_iters=0, flags=0, allow=()):
+    def kmeans_rgbw(self, keys, weight, K, seed=0, max_iters=0, flags=0, allow=(), init=None):
+        """init: None (init_centroids, kmeans.rs:101-108), or (K, 3) uint8 centroids to start from (cniic_kmeans_rgbw_from)"""
         keys = np.ascontiguousarray(keys, np.uint32)
         weight = np.ascontiguousarray(weight, np.uint32)
         U = keys.size
@@ -258,8 +272,14 @@ class Context:
         members = np.zeros(K, np.uint64)
         st = KmStats()
         o = self._opts(seed, max_iters, flags)
-        rc = self._check(self._L.cniic_kmeans_rgbw(self.h, _ptr(keys), _ptr(weight), C.c_uint64(U), C.c_uint32(K), C.byref(o),
-                                                   _ptr(cent), _ptr(labels), _ptr(members), C.byref(st)), allow)
+        if init is None:
+            rc = self._L.cniic_kmeans_rgbw(self.h, _ptr(keys), _ptr(weight), C.c_uint64(U), C.c_uint32(K), C.byref(o),
+                                           _ptr(cent), _ptr(labels), _ptr(members), C.byref(st))
+        else:
+            init = np.ascontiguousarray(init, np.uint8).reshape(K, 3)
+            rc = self._L.cniic_kmeans_rgbw_from(self.h, _ptr(keys), _ptr(weight), C.c_uint64(U), C.c_uint32(K), C.byref(o), _ptr(init),
+                                                _ptr(cent), _ptr(labels), _ptr(members), C.byref(st))
+        rc = self._check(rc, allow)
         return rc, dict(centroids=cent, labels=labels, members=members, stats=st.as_dict())
 
     def kmeans_step_rgbw(self, keys, weight, K, centroids, labels):
@@ -275,7 +295,8 @@ class Context:
                                                    _ptr(cent), _ptr(labels), _ptr(sums), _ptr(wsum), _ptr(members), C.byref(ch)))
         return dict(labels=labels, sums=sums, wsum=wsum, members=members, changed=ch.value)
 
-    def kmeans_xyrgb(self, img, K, seed=0, max_iters=0, flags=0, want_labels=True, allow=()):
+    def kmeans_xyrgb(self, img, K, seed=0, max_iters=0, flags=0, want_labels=True, allow=(), init=None):
+        """init: None (init_centroids, kmeans.rs:101-108), or K COLORPOS centroids inside the image to start from (cniic_kmeans_xyrgb_from)"""
         img = np.ascontiguousarray(img, np.uint8)
         h, w = img.shape[:2]
         cent = np.zeros(K, COLORPOS)
@@ -283,8 +304,14 @@ class Context:
         members = np.zeros(K, np.uint64)
         st = KmStats()
         o = self._opts(seed, max_iters, flags)
-        rc = self._check(self._L.cniic_kmeans_xyrgb(self.h, _ptr(img), C.c_uint32(w), C.c_uint32(h), C.c_uint32(K), C.byref(o),
-                                                    _ptr(cent), _ptr(labels), _ptr(members), C.byref(st)), allow)
+        if init is None:
+            rc = self._L.cniic_kmeans_xyrgb(self.h, _ptr(img), C.c_uint32(w), C.c_uint32(h), C.c_uint32(K), C.byref(o),
+                                            _ptr(cent), _ptr(labels), _ptr(members), C.byref(st))
+        else:
+            init = np.ascontiguousarray(init, COLORPOS).reshape(K)
+            rc = self._L.cniic_kmeans_xyrgb_from(self.h, _ptr(img), C.c_uint32(w), C.c_uint32(h), C.c_uint32(K), C.byref(o), _ptr(init),
+                                                 _ptr(cent), _ptr(labels), _ptr(members), C.byref(st))
+        rc = self._check(rc, allow)
         return rc, dict(centroids=cent, labels=labels, members=members, stats=st.as_dict())
 
     def kmeans_step_xyrgb(self, img, K, centroids, labels):
@@ -411,6 +438,31 @@ class Context:
         if own:
             return rc, (out[:ln.value].tobytes() if rc == OK else b""), st.as_dict()
         return rc, ln.value, st.as_dict()
+
+    def encode_warm(self, expr, img, init, w=None, h=None, out=None, seed=0, max_iters=0, flags=0, allow=()):
+        """cniic_codec_encode_warm: Codec::encode of cluster-colors(K) / voronoi(K) with the K-means started from init ((K, 3) uint8, or K
+        COLORPOS entries) -> (rc, stream or its length as encode, stats, final centroids in init's layout: the next frame's init)"""
+        if isinstance(img, np.ndarray):
+            img = np.ascontiguousarray(img, np.uint8)
+            h, w = img.shape[:2]
+        init = np.ascontiguousarray(init)
+        if init.dtype != COLORPOS:
+            init = np.ascontiguousarray(init, np.uint8).reshape(-1, 3)
+        cent = np.zeros_like(init)
+        own = out is None
+        if own:
+            cap = 64 + w * h * 16 + (1 << 16) + 19 * init.shape[0]
+            out = np.empty(cap, np.uint8)
+        else:
+            cap = out.numel() if hasattr(out, "numel") else out.size
+        ln = C.c_uint64(0)
+        st = KmStats()
+        o = self._opts(seed, max_iters, flags)
+        rc = self._check(self._L.cniic_codec_encode_warm(self.h, expr.encode(), C.byref(o), _ptr(init), _ptr(img), C.c_uint32(w), C.c_uint32(h),
+                                                         _ptr(out), C.c_uint64(cap), C.byref(ln), _ptr(cent), C.byref(st)), allow)
+        if own:
+            return rc, (out[:ln.value].tobytes() if rc == OK else b""), st.as_dict(), cent
+        return rc, ln.value, st.as_dict(), cent
 
     def hilbert_rle_approx_encode(self, d, img, w=None, h=None, out=None, allow=()):
         """cniic_hilbert_rle_approx_encode: Hilbert { compress: RLE(d) }::encode for an f64 d (d == 0.0: the `hilbert(rle)` stream).
@@ -791,6 +843,22 @@ class Palette:
         if allow:
             return rc, [int(lens[f]) for f in range(F)]
         return [int(lens[f]) for f in range(F)]
+
+
+    def fit_frames_var(self, frames_flat, ws, hs, want_pixels=True, allow=()):
+        """cniic_palette_fit_frames_var: len(ws) frames of different sizes, back to back in frames_flat (device tensor, numpy array or
+        address) -> (sse: uint64[F], the exact summed squared distance of every frame's pixels to their entries; pixels: uint64[K], the
+        pixels of all frames per entry, or None); with a status in `allow`: (status, sse, pixels)"""
+        F = len(ws)
+        n = max(F, 1)
+        w = (C.c_uint32 * n)(*[int(x) for x in ws])
+        hh = (C.c_uint32 * n)(*[int(x) for x in hs])
+        sse = np.zeros(n, np.uint64)
+        pixels = np.zeros(self.K, np.uint64) if want_pixels else None
+        rc = self.ctx._check(self.ctx._L.cniic_palette_fit_frames_var(self.h, _ptr(frames_flat), w, hh, C.c_uint32(F), _ptr(sse), _ptr(pixels)), allow)
+        if allow:
+            return rc, sse[:F], pixels
+        return sse[:F], pixels
 
 
 def linearize_count(method, w, h):

@@ -41,6 +41,14 @@ class Codec:
         self.last_stats = st
         return data
 
+    def encode_warm(self, img, init, **kw):
+        """cluster-colors(K) / voronoi(K) only: encode with the K-means started from init (the centroids of the previous frame of a video,
+        of a neighbouring tile: (K, 3) uint8, or K _lib.COLORPOS entries) -> (stream, final centroids: the next call's init).  Any other
+        codec raises CniicError(BAD_ARG)."""
+        rc, data, st, cent = self.ctx.encode_warm(self.expr, img, init, **kw)
+        self.last_stats = st
+        return data, cent
+
     def decode(self, data):
         rc, img = self.ctx.decode(self.expr, data, allow=(_lib.DECODE,))
         return img if rc == _lib.OK else None

@@ -240,10 +240,10 @@ int32_t cniic_hist_syms(cniic_ctx *c, int32_t sym_kind, const uint32_t *syms, ui
 }
 
 // ------------------------------------------------------------------ K-means
-int32_t cniic_kmeans_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *weight, uint64_t U, uint32_t K,
-                          const cniic_kmeans_opts *opts, uint8_t *centroids, uint32_t *labels, uint64_t *members,
-                          cniic_kmeans_stats *stats) {
-    LOCK(c);
+// cniic_kmeans_rgbw (init == nullptr: init_centroids, kmeans.rs:101-108) and cniic_kmeans_rgbw_from (init: K x 3 bytes, host), the mutex held
+static int32_t kmeans_rgbw_locked(cniic_ctx *c, const uint32_t *keys, const uint32_t *weight, uint64_t U, uint32_t K,
+                                  const cniic_kmeans_opts *opts, const uint8_t *init, uint8_t *centroids, uint32_t *labels, uint64_t *members,
+                                  cniic_kmeans_stats *stats) {
     c->ktimes.clear();
     if (!keys || !weight || !centroids) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: null argument");
     In<uint32_t> k, w;
@@ -252,6 +252,7 @@ int32_t cniic_kmeans_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *we
     KmRgbwState *km = nullptr;
     CNIIC_TRY(km_rgbw_create(c, k.d, w.d, U, 0, 1, K, opts, nullptr, nullptr, &km));
     std::unique_ptr<KmRgbwState, void (*)(KmRgbwState *)> guard(km, km_rgbw_destroy);
+    if (init) CNIIC_TRY(km_rgbw_set_centroids(km, init));
     CNIIC_TRY(km_rgbw_run(km));
     Out<uint32_t> lo;
     CNIIC_TRY(lo.bind(c, labels, U));
@@ -265,6 +266,21 @@ int32_t cniic_kmeans_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *we
     CNIIC_TRY(to_caller(c, members, mem.data(), mem.size() * 8));
     if (stats) *stats = st;
     return check_enough_active(c, K, U, st.active);   // (the caller has centroids, labels, members and stats of a failed run too)
+}
+
+int32_t cniic_kmeans_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *weight, uint64_t U, uint32_t K,
+                          const cniic_kmeans_opts *opts, uint8_t *centroids, uint32_t *labels, uint64_t *members,
+                          cniic_kmeans_stats *stats) {
+    LOCK(c);
+    return kmeans_rgbw_locked(c, keys, weight, U, K, opts, nullptr, centroids, labels, members, stats);
+}
+
+int32_t cniic_kmeans_rgbw_from(cniic_ctx *c, const uint32_t *keys, const uint32_t *weight, uint64_t U, uint32_t K,
+                               const cniic_kmeans_opts *opts, const uint8_t *init, uint8_t *centroids, uint32_t *labels, uint64_t *members,
+                               cniic_kmeans_stats *stats) {
+    LOCK(c);
+    if (!init || is_device_ptr(init)) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw_from: init is K x 3 bytes of host memory");
+    return kmeans_rgbw_locked(c, keys, weight, U, K, opts, init, centroids, labels, members, stats);
 }
 
 int32_t cniic_kmeans_step_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_t *weight, uint64_t U, uint32_t K,
@@ -300,9 +316,9 @@ int32_t cniic_kmeans_step_rgbw(cniic_ctx *c, const uint32_t *keys, const uint32_
     return CNIIC_OK;
 }
 
-int32_t cniic_kmeans_xyrgb(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts,
-                           cniic_colorpos *centroids, uint32_t *labels, uint64_t *members, cniic_kmeans_stats *stats) {
-    LOCK(c);
+// cniic_kmeans_xyrgb (init == nullptr) and cniic_kmeans_xyrgb_from (init: K cniic_colorpos, host), the mutex held
+static int32_t kmeans_xyrgb_locked(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts, const cniic_colorpos *init,
+                                   cniic_colorpos *centroids, uint32_t *labels, uint64_t *members, cniic_kmeans_stats *stats) {
     c->ktimes.clear();
     if (!rgb || !centroids) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_xyrgb: null argument");
     const uint64_t N = (uint64_t)w * h;
@@ -313,13 +329,26 @@ int32_t cniic_kmeans_xyrgb(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_
     std::vector<cniic_colorpos> cent(K ? K : 1);
     std::vector<uint64_t> mem(K ? K : 1);
     cniic_kmeans_stats st{};
-    CNIIC_TRY(km_xyrgb_run(c, in.d, w, h, K, opts, cent.data(), lo.d, mem.data(), &st));
+    CNIIC_TRY(km_xyrgb_run(c, in.d, w, h, K, opts, cent.data(), lo.d, mem.data(), &st, init));
     CNIIC_TRY(lo.finish(c));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
     CNIIC_TRY(to_caller(c, centroids, cent.data(), (size_t)K * sizeof(cniic_colorpos)));
     CNIIC_TRY(to_caller(c, members, mem.data(), (size_t)K * 8));
     if (stats) *stats = st;
     return check_enough_active(c, K, N, st.active);
+}
+
+int32_t cniic_kmeans_xyrgb(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts,
+                           cniic_colorpos *centroids, uint32_t *labels, uint64_t *members, cniic_kmeans_stats *stats) {
+    LOCK(c);
+    return kmeans_xyrgb_locked(c, rgb, w, h, K, opts, nullptr, centroids, labels, members, stats);
+}
+
+int32_t cniic_kmeans_xyrgb_from(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts, const cniic_colorpos *init,
+                                cniic_colorpos *centroids, uint32_t *labels, uint64_t *members, cniic_kmeans_stats *stats) {
+    LOCK(c);
+    if (!init || is_device_ptr(init)) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_xyrgb_from: init is K entries of host memory");
+    return kmeans_xyrgb_locked(c, rgb, w, h, K, opts, init, centroids, labels, members, stats);
 }
 
 int32_t cniic_kmeans_step_xyrgb(cniic_ctx *c, const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t K,
@@ -490,6 +519,15 @@ int32_t cniic_cc_assign(cniic_cc *cc) {
     LOCK(c);
     if (!cc->s->km) return c->fail(CNIIC_ERR_BAD_ARG, "the session has no K-means state yet (cniic_cc_image_create comes first)");
     return km_rgbw_assign(cc->s->km);
+}
+
+int32_t cniic_cc_set_centroids(cniic_cc *cc, const uint8_t *init) {
+    if (!cc) return CNIIC_ERR_BAD_ARG;
+    cniic_ctx *c = static_cast<cniic_ctx *>(cc->c);
+    LOCK(c);
+    if (!cc->s->km) return c->fail(CNIIC_ERR_BAD_ARG, "the session has no K-means state yet (cniic_cc_image_create comes first)");
+    if (!init || is_device_ptr(init)) return c->fail(CNIIC_ERR_BAD_ARG, "cc_set_centroids: init is K x 3 bytes of host memory");
+    return km_rgbw_set_centroids(cc->s->km, init);
 }
 
 int32_t cniic_cc_update(cniic_cc *cc, uint64_t *changed) {
@@ -813,6 +851,24 @@ int32_t cniic_palette_encode_frames_var(cniic_palette *pal, const uint8_t *rgb, 
     In<uint8_t> in;
     CNIIC_TRY(in.bind(c, rgb, n * 3));
     return palette_encode_frames_var(pal->p, in.d, w, h, frames, out, stride, lens);
+}
+
+int32_t cniic_palette_fit_frames_var(cniic_palette *pal, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames, uint64_t *sse,
+                                     uint64_t *pixels) {
+    if (!pal) return CNIIC_ERR_BAD_ARG;
+    cniic_ctx *c = static_cast<cniic_ctx *>(pal->c);
+    LOCK(c);
+    c->ktimes.clear();
+    if (!rgb || !w || !h || !sse || !frames) return c->fail(CNIIC_ERR_BAD_ARG, "palette_fit_frames_var: null argument");
+    uint64_t n = 0;
+    for (uint32_t f = 0; f < frames; f++) {
+        const uint64_t np = (uint64_t)w[f] * h[f];
+        if (!np) return c->fail(CNIIC_ERR_BAD_ARG, "palette_fit_frames_var: frame %u is %u x %u", f, w[f], h[f]);
+        if (__builtin_add_overflow(n, np, &n) || n > (~0ull) / 3) return c->fail(CNIIC_ERR_BAD_ARG, "palette_fit_frames_var: too many pixels");
+    }
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, n * 3));
+    return palette_fit_frames_var(pal->p, in.d, w, h, frames, sse, pixels);
 }
 
 void cniic_palette_destroy(cniic_palette *pal) {
@@ -1163,6 +1219,20 @@ int32_t cniic_codec_encode_opts(cniic_ctx *c, const char *expr, const cniic_kmea
                                 uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     LOCK(c);
     return encode_locked(c, expr, opts, rgb, w, h, out, cap, len, stats);
+}
+
+int32_t cniic_codec_encode_warm(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const void *init, const uint8_t *rgb, uint32_t w, uint32_t h,
+                                uint8_t *out, uint64_t cap, uint64_t *len, void *centroids_out, cniic_kmeans_stats *stats) {
+    LOCK(c);
+    c->ktimes.clear();
+    CodecDesc d;
+    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_warm: null argument");
+    if (!init || is_device_ptr(init) || (centroids_out && is_device_ptr(centroids_out)))
+        return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_warm: init and centroids_out are host memory");
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
+    return codec_encode_warm(c, d, in.d, w, h, opts, init, out, cap, len, centroids_out, stats);
 }
 
 // the first S worker contexts of a batch call (created on first use), with this context's route switches and its injected scan (a view

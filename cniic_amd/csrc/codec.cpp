@@ -1016,12 +1016,48 @@ int palette_encode_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *
     return frames_tail(c, pixlab.p, p->wide, p->K, p->cent_d.as<uint32_t>(), p->cent_h.data(), fb, out, stride, lens, nullptr, true);
 }
 
+// How well the handle's palette fits a batch of frames: sse_h[f] = the exact sum over frame f's pixels of the squared distance to the pixel's entry
+// under the rule (3 w h times the MSE of decoding that frame's palette_encode_frames_var stream), pixels_h[k] (may be null) = the pixels of all
+// frames whose entry is k.  One launch (k_palette_fit) over the frame table of the var route; no labels are stored.
+int palette_fit_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *wv, const uint32_t *hv, uint32_t F, uint64_t *sse_h, uint64_t *pixels_h) {
+    Ctx *c = p->c;
+    const char *who = "palette_fit_frames_var";
+    if (!wv || !hv || !F || !sse_h) return c->fail(CNIIC_ERR_BAD_ARG, "%s: empty batch", who);
+    uint64_t n = 0;
+    for (uint32_t f = 0; f < F; f++) {
+        const uint64_t np = (uint64_t)wv[f] * hv[f];
+        if (!np) return c->fail(CNIIC_ERR_BAD_ARG, "%s: frame %u is %u x %u", who, f, wv[f], hv[f]);
+        if (__builtin_add_overflow(n, np, &n)) return c->fail(CNIIC_ERR_BAD_ARG, "%s: too many pixels", who);
+    }
+    FrameBatch fb;
+    fb.wv = wv; fb.hv = hv; fb.F = F;
+    CNIIC_TRY(fb.build_table(c, who, p->wide ? 2 : 1));
+    CNIIC_TRY(fb.upload_table(c));
+    const uint64_t words = (uint64_t)F + (pixels_h ? p->K : 0);
+    DevBuf res;
+    CNIIC_HIP_TRY(c, res.alloc(words * 8));
+    CNIIC_HIP_TRY(c, hipMemsetAsync(res.p, 0, words * 8, c->stream));
+    {
+        ScopedKernelTimer t(c, "pal_fit");
+        CNIIC_TRY(palette_fit(c, rgb_d, fb.ft_d.as<FrameVar>(), F, fb.chunks, p->table.p, p->wide, p->cent_d.as<uint32_t>(), p->K, res.as<uint64_t>(),
+                              pixels_h ? res.as<uint64_t>() + F : nullptr));
+        t.stop(1);
+    }
+    std::vector<uint64_t> host(words);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), res.p, words * 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    memcpy(sse_h, host.data(), (size_t)F * 8);
+    if (pixels_h) memcpy(pixels_h, host.data() + F, (size_t)p->K * 8);
+    return CNIIC_OK;
+}
+
 // images of at least this many pixels take the super-cell partition (k_points.hip); CNIIC_SP_MIN_PIXELS overrides (tests: 0)
 static uint64_t sp_min_pixels(const Ctx *c) { return c->opt(CNIIC_OPT_SP_MIN_PIXELS, "CNIIC_SP_MIN_PIXELS", 1ull << 20); }
 
+// init_h (codec_encode_warm; host, K x 3 bytes): the K-means starts from these centroids; cent_out_h (host, may be null) receives the palette
 static int encode_cluster_colors(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K,
                                  const cniic_kmeans_opts *opts, uint8_t *out, uint64_t cap, uint64_t *len,
-                                 cniic_kmeans_stats *stats) {
+                                 cniic_kmeans_stats *stats, const uint8_t *init_h = nullptr, uint8_t *cent_out_h = nullptr) {
     const uint64_t n = (uint64_t)w * h;
     host_trace().mark("enter");
     if (n >= sp_min_pixels(c) && (reinterpret_cast<uintptr_t>(rgb_d) & 15) == 0 && !(opts && (opts->flags & CNIIC_KM_BRUTE_FORCE))) {
@@ -1029,9 +1065,11 @@ static int encode_cluster_colors(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint3
         CcSession *raw = nullptr;
         CNIIC_TRY(cc_prepare_image(c, rgb_d, n, K, opts, &raw));
         std::unique_ptr<CcSession> s(raw);
+        if (init_h) CNIIC_TRY(km_rgbw_set_centroids(s->km, init_h));
         CNIIC_TRY(km_rgbw_run(s->km, nullptr, /*may_defer=*/true));   // (cc_finish looks at how a persistent launch ended where it fetches the result)
         host_trace().mark("km_run");
         const int rc_all = cc_finish(s.get(), rgb_d, w, h, nullptr, out, cap, len, stats);
+        if (rc_all == CNIIC_OK && cent_out_h) CNIIC_TRY(cc_palette(s.get(), cent_out_h, nullptr));
         host_trace().dump();
         return rc_all;
     }
@@ -1047,20 +1085,24 @@ static int encode_cluster_colors(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint3
     CcSession *raw = nullptr;
     CNIIC_TRY(cc_prepare(c, table, K, opts, 0, 1, nullptr, &raw));
     std::unique_ptr<CcSession> s(raw);
+    if (init_h) CNIIC_TRY(km_rgbw_set_centroids(s->km, init_h));
     CNIIC_TRY(km_rgbw_run(s->km, nullptr, /*may_defer=*/true));
     host_trace().mark("km_run");
     const int rc_all = cc_finish(s.get(), rgb_d, w, h, nullptr, out, cap, len, stats);
+    if (rc_all == CNIIC_OK && cent_out_h) CNIIC_TRY(cc_palette(s.get(), cent_out_h, nullptr));
     host_trace().dump();
     return rc_all;
 }
 
 // ------------------------------------------------------------------ VoronoiCluster::encode (clusterc.rs:148-166)
 static int encode_voronoi(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts,
-                          uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
+                          uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats, const cniic_colorpos *init_h = nullptr,
+                          cniic_colorpos *cent_out_h = nullptr) {
     if (K == 0) return c->fail(CNIIC_ERR_BAD_ARG, "voronoi(0)");
     std::vector<cniic_colorpos> cent(K);
     cniic_kmeans_stats st{};
-    CNIIC_TRY(km_xyrgb_run(c, rgb_d, w, h, K, opts, cent.data(), nullptr, nullptr, &st));
+    CNIIC_TRY(km_xyrgb_run(c, rgb_d, w, h, K, opts, cent.data(), nullptr, nullptr, &st, init_h));
+    if (cent_out_h) memcpy(cent_out_h, cent.data(), (size_t)K * sizeof(cniic_colorpos));
     if (stats) *stats = st;
     CNIIC_TRY(check_enough_active(c, K, (uint64_t)w * h, st.active));
     std::vector<uint8_t> header;
@@ -1237,6 +1279,19 @@ int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, u
     case CODEC_ZIP_DICT: return encode_zip_dict(c, rgb_d, w, h, out, cap, len);
     }
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
+}
+
+// codec_encode for the two K-means codecs with the run started from the caller's centroids (cniic_codec_encode_warm): init_h / cent_out_h are host
+// arrays of K entries, K x 3 bytes for cluster-colors and K cniic_colorpos for voronoi; cent_out_h may be null.  Any other codec: BAD_ARG.
+int codec_encode_warm(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, uint32_t h, const cniic_kmeans_opts *opts, const void *init_h,
+                      uint8_t *out, uint64_t cap, uint64_t *len, void *cent_out_h, cniic_kmeans_stats *stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_VORONOI)
+        return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_warm: only cluster-colors(K) and voronoi(K) run a K-means");
+    if ((uint64_t)w * h >= (1ull << 32)) return c->fail(CNIIC_ERR_BAD_ARG, "image too large");
+    if (d.kind == CODEC_CLUSTER_COLORS)
+        return encode_cluster_colors(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats, static_cast<const uint8_t *>(init_h), static_cast<uint8_t *>(cent_out_h));
+    return encode_voronoi(c, rgb_d, w, h, d.arg, opts, out, cap, len, stats, static_cast<const cniic_colorpos *>(init_h), static_cast<cniic_colorpos *>(cent_out_h));
 }
 
 // ------------------------------------------------------------------ decode

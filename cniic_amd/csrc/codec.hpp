@@ -23,6 +23,10 @@ bool        codec_is_lossless(const CodecDesc &d);          // Codec::is_lossles
 // rgb_d is device memory; out / rgb_out may be host or device.
 int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, uint32_t h, const cniic_kmeans_opts *opts,
                  uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats);
+// the same for cluster-colors(K) / voronoi(K) with the K-means started from init_h (host: K x 3 bytes / K cniic_colorpos); cent_out_h (may be null)
+// receives the final centroids in the same layout
+int codec_encode_warm(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, uint32_t h, const cniic_kmeans_opts *opts, const void *init_h,
+                      uint8_t *out, uint64_t cap, uint64_t *len, void *cent_out_h, cniic_kmeans_stats *stats);
 // Hilbert { compress: RLE(d) }::encode for any d (d == 0.0: the `hilbert(rle)` stream); rgb_d is device memory, out host or device.
 int encode_hilbert_rle(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
 // bytes may be host or device memory: of a stream in HBM only the head comes to the host, the payload is decoded where it lies.
@@ -151,6 +155,7 @@ struct Palette {
 int palette_create(Ctx *c, const uint8_t *cent_h, uint32_t K, Palette **out);
 int palette_labels(Palette *p, const uint8_t *rgb_d, uint64_t n, void *labels_d /* 16-byte aligned */);
 int palette_encode_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride, uint64_t *lens);
+int palette_fit_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *w, const uint32_t *h, uint32_t F, uint64_t *sse_h, uint64_t *pixels_h /* K entries, or null */);
 
 // header carries any prefix already serialised (image dimensions); the decoder trie is appended
 // to it and the whole stream lands in out[0..*len)  (out: host or device memory).

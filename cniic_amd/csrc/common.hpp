@@ -552,6 +552,8 @@ int km_rgbw_set_points(KmRgbwState *s, uint64_t U, uint64_t Ulist = 0 /* 0: the 
 void km_rgbw_cell_arrays(KmRgbwState *s, uint32_t **cell_start_d, uint32_t **ckeys_d, uint32_t **cweight_d);
 void km_rgbw_destroy(KmRgbwState *s);
 int km_rgbw_set_state(KmRgbwState *s, const uint8_t *centroids_h, const uint32_t *labels_d_u32);
+// kmeans::cluster from K centroids of the caller's (host, K x 3 bytes) instead of init_centroids; before the first assign / run only (BAD_ARG after)
+int km_rgbw_set_centroids(KmRgbwState *s, const uint8_t *init_h);
 int km_rgbw_assign(KmRgbwState *s);                       // async: assign + partial sums -> partials
 int km_rgbw_update(KmRgbwState *s);                       // async: centroids from partials
 // ---- comm.cpp: RCCL on the context's stream (bound at run time) ----
@@ -607,11 +609,12 @@ int km_rgbw_import_labels(KmRgbwState *s, const void *src_d);
 uint64_t km_rgbw_points(KmRgbwState *s);
 
 // ---- k_kmeans_xyrgb.hip ----
+// init_h (optional; host, K entries with x < w and y < h): the run starts from these centroids instead of init_centroids (kmeans.rs:101-108)
 int km_xyrgb_run(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K,
                  const cniic_kmeans_opts *opts, cniic_colorpos *centroids_h, uint32_t *labels_d_u32,
-                 uint64_t *members_h, cniic_kmeans_stats *stats);
+                 uint64_t *members_h, cniic_kmeans_stats *stats, const cniic_colorpos *init_h = nullptr);
 int km_xyrgb_run_wide(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts, cniic_colorpos *centroids_h,
-                      uint32_t *labels_d_u32, uint64_t *members_h, cniic_kmeans_stats *stats);   // k_kmeans_wide.hip: any K, any sides
+                      uint32_t *labels_d_u32, uint64_t *members_h, cniic_kmeans_stats *stats, const cniic_colorpos *init_h = nullptr);   // k_kmeans_wide.hip: any K, any sides
 int km_xyrgb_step(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K,
                   const cniic_colorpos *centroids_h, uint32_t *labels_d_u32, uint64_t *sums_h,
                   uint64_t *wsum_h, uint64_t *members_h, uint64_t *changed_h, const cniic_kmeans_opts *opts);
@@ -823,6 +826,17 @@ struct FrameVar {
     uint32_t w, h;
 };
 constexpr uint32_t kFrameVarChunk = 4096, kFrameVarHistSpan = 1u << 16;   // (= kPackChunk, kHistSpan of k_huff.hip)
+// the frame whose row of chunks (FIRST = &FrameVar::chunk0) or of histogram blocks (hblock0) holds block b: the LAST f with fr[f].*FIRST <= b
+// (every frame has at least one pixel, so the firsts rise strictly; the loads depend on the block alone)
+template <uint32_t FrameVar::*FIRST>
+__device__ __forceinline__ uint32_t frame_of_block(const FrameVar *__restrict__ fr, uint32_t frames, uint32_t b) {
+    uint32_t f = 0;
+    for (uint32_t hi = frames; hi - f > 1;) {   // fr[f].*FIRST <= b < fr[hi].*FIRST
+        const uint32_t mid = f + (hi - f) / 2;
+        if (fr[mid].*FIRST <= b) f = mid; else hi = mid;
+    }
+    return f;
+}
 // the Huffman codes and stream headers of a batch's frames on the GPU (K <= 256; k_huff.hip k_frame_trees)
 int frame_trees(Ctx *c, const uint32_t *cnt_d, const uint32_t *cent_d, uint32_t frames, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, uint64_t stride,
                 uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d,
@@ -836,5 +850,9 @@ int sum_u32_dev(Ctx *c, const uint32_t *v_d, uint64_t n, uint64_t *out_d);   // 
 // labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
 // down the plain route; plain_cells_d (optional): a zeroed counter of such cells
 int palette_lut(Ctx *c, const uint32_t *cent_d, uint32_t K, bool wide, void *table_d, uint32_t list_max, uint32_t *plain_cells_d);
+// the fit of a batch of frames (the frame table's rows, `chunks` chunks of 4096 pixels) under that table: sse_d[f] += the frame's summed squared
+// distance to its pixels' entries, pixels_d[k] (optional) += the pixels whose entry is k; one launch
+int palette_fit(Ctx *c, const uint8_t *rgb_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, const void *table_d, bool wide, const uint32_t *cent_d, uint32_t K,
+                uint64_t *sse_d, uint64_t *pixels_d);
 
 }  // namespace cniic

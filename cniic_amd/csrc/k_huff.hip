@@ -261,18 +261,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pixel_labels(const uint8_t *__
     }
 }
 
-// the frame whose row of chunks (FIRST = &FrameVar::chunk0) or of histogram blocks (hblock0) holds block b: the LAST f with fr[f].*FIRST <= b
-// (every frame has at least one pixel, so the firsts rise strictly; the loads depend on the block alone)
-template <uint32_t FrameVar::*FIRST>
-__device__ __forceinline__ uint32_t frame_of_block(const FrameVar *__restrict__ fr, uint32_t frames, uint32_t b) {
-    uint32_t f = 0;
-    for (uint32_t hi = frames; hi - f > 1;) {   // fr[f].*FIRST <= b < fr[hi].*FIRST
-        const uint32_t mid = f + (hi - f) / 2;
-        if (fr[mid].*FIRST <= b) f = mid; else hi = mid;
-    }
-    return f;
-}
-
+// (frame_of_block, the frame a block of the var route works on: common.hpp, beside FrameVar)
 // pass 1: code lengths of a chunk's labels, from an LDS table.  One body for one image, a batch of equal frames (grid.y = frame) and a
 // batch of frames of any sizes (a 1-D grid over all frames' chunks): the callers differ in where a block finds its labels and its row
 template <typename LabelT>

@@ -66,6 +66,23 @@ __global__ void k_rgbw_init_cent(const uint32_t *__restrict__ keys, uint64_t U, 
     }
 }
 
+// The same from K centroids the caller gives (km_rgbw_set_centroids: cniic_kmeans_rgbw_from, cniic_cc_set_centroids), enqueued behind the kernel
+// above: the three places it writes -- cent, the fused loop's cent_copy, cconst with its padding -- and nothing else.  moved_list[0] = K stays as
+// create left it (every centroid counts as moved), and the labels are the chunk labels of init_assignment: kmeans::cluster with only
+// init_centroids (kmeans.rs:101-108) replaced.
+__global__ void k_rgbw_given_cent(const uint32_t *__restrict__ given /* [K] 0xRRGGBB */, uint32_t K, uint32_t Kpad, uint32_t idbits, uint2 *__restrict__ cconst,
+                                  uint32_t *__restrict__ cent, uint32_t *__restrict__ cent_copy) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < K) {
+        const uint32_t ck = given[k] & 0xffffffu;
+        cent[k] = ck;
+        if (cent_copy) cent_copy[k] = ck;
+        cconst[k] = make_cconst(ck, k, idbits);
+    } else if (k < Kpad) {
+        cconst[k] = make_uint2(0u, 0u);  // padding: key 0 never wins
+    }
+}
+
 // labels[i - lo] = init label of canonical index rank[i] (or i itself when rank == nullptr)
 template <typename LabelT>
 __global__ void k_rgbw_init_labels(const uint32_t *__restrict__ rank, uint64_t U, uint64_t lo, uint64_t hi, uint32_t K,
@@ -1452,6 +1469,21 @@ static int launch_update(KmRgbwState *s, int mode) {
     return CNIIC_OK;
 }
 
+// K centroids of the caller's (host, K x 3 bytes r, g, b) in the place of init_centroids.  Valid until the first assign of the state, on every
+// route: the launches and the persistent launch read cconst (and cent: k_rgbw_assign_big) when they start, ps_prepare keeps no copy of either.
+int km_rgbw_set_centroids(KmRgbwState *s, const uint8_t *init_h) {
+    Ctx *c = s->c;
+    if (s->started) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: the centroids can only be given before the first assign");
+    s->given_h.resize(s->K);   // (kept with the state: the copy below is asynchronous)
+    for (uint32_t k = 0; k < s->K; k++) s->given_h[k] = ((uint32_t)init_h[3 * k] << 16) | ((uint32_t)init_h[3 * k + 1] << 8) | init_h[3 * k + 2];
+    if (!s->given.p) CNIIC_HIP_TRY(c, s->given.alloc((uint64_t)s->K * 4));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(s->given.p, s->given_h.data(), (size_t)s->K * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rgbw_given_cent, dim3(ceil_div(s->Kpad, 256)), dim3(256), 0, c->stream, (const uint32_t *)s->given.as<uint32_t>(), s->K, s->Kpad, s->idbits,
+                       s->cconst.as<uint2>(), s->cent.as<uint32_t>(), s->fused ? s->fused_cent.as<uint32_t>() : (uint32_t *)nullptr);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
 // Kept for ABI stability: the first assign produces full sums, nothing to fold in beforehand.
 int km_rgbw_fold_initial(KmRgbwState *) { return CNIIC_OK; }
 
@@ -1490,6 +1522,7 @@ static void ensure_wave_ranges(KmRgbwState *s) {
 static void launch_assign(KmRgbwState *s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const FusedUpdate *fused = nullptr,
                           unsigned long long *part_fused = nullptr) {
     Ctx *c = s->c;
+    s->started = true;
     if (s->cells) ensure_wave_ranges(s);
     FusedUpdate fz{};
     if (fused) fz = *fused;
@@ -1640,6 +1673,7 @@ int km_rgbw_run(KmRgbwState *s, Comm *cm, bool may_defer) {
 
 static int km_rgbw_run_loop(KmRgbwState *s, Comm *cm, bool may_defer) {
     Ctx *c = s->c;
+    s->started = true;   // (the persistent launch as well: km_rgbw_set_centroids)
     int batch = test_env("CNIIC_KM_BATCH") ? atoi(test_env("CNIIC_KM_BATCH")) : cm ? 2 : 8;  // iterations enqueued between two looks at the state; with collectives an iteration past convergence still
                                    // pays a full all-reduce, so fewer are in flight (and each is long enough for the host to keep up)
     const bool batch_fixed = test_env("CNIIC_KM_BATCH") != nullptr || cm != nullptr;

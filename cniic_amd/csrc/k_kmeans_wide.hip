@@ -102,6 +102,17 @@ __global__ void k_xyw_init(const uint8_t *__restrict__ rgb, uint32_t w, uint64_t
     }
 }
 
+// the same from K centroids the caller gives (km_xyrgb_run has held them against w and h)
+__global__ void k_xyw_init_from(const cniic_colorpos *__restrict__ given, uint64_t N, uint32_t K, uint32_t *__restrict__ labels, WideCent *__restrict__ cent) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t i = tid; i < N; i += stride) labels[i] = init_label(i, N, K);  // kmeans.rs:61-78
+    for (uint64_t k = tid; k < K; k += stride) {
+        const cniic_colorpos g = given[k];
+        cent[k] = WideCent{(int32_t)g.x, (int32_t)g.y, ((uint32_t)g.rgb[0] << 16) | ((uint32_t)g.rgb[1] << 8) | g.rgb[2], 0u};
+    }
+}
+
 // sums layout: [5k + d] d = x, y, r, g, b; [5K + k] members; [6K] moved; [6K + 1] pair evaluations
 __global__ __launch_bounds__(256) void k_xyw_assign(const uint8_t *__restrict__ rgb, uint32_t w, uint64_t N, uint32_t K, const WideCent *__restrict__ cent,
                                                     uint32_t *__restrict__ labels, unsigned long long *__restrict__ sums) {
@@ -157,7 +168,7 @@ __global__ void k_xyw_update(unsigned long long *__restrict__ sums, const uint8_
 }
 
 int km_xyrgb_run_wide(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts, cniic_colorpos *centroids_h,
-                      uint32_t *labels_d_u32, uint64_t *members_h, cniic_kmeans_stats *stats) {
+                      uint32_t *labels_d_u32, uint64_t *members_h, cniic_kmeans_stats *stats, const cniic_colorpos *init_h) {
     const uint64_t N = (uint64_t)w * h;
     if (K == 0 || N == 0) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_xyrgb: empty problem");
     if (N / K == 0) return c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu points for %u clusters (src/kmeans.rs:68)", (unsigned long long)N, K);
@@ -173,7 +184,14 @@ int km_xyrgb_run_wide(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint
     CNIIC_HIP_TRY(c, counters.alloc(16));
     CNIIC_HIP_TRY(c, hipMemsetAsync(sums.p, 0, W * 8, c->stream));
     const uint32_t g = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ceil_div(N, 256), 1), 4096), gk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ceil_div(K, 256), 1), 4096);
-    hipLaunchKernelGGL(k_xyw_init, dim3(std::max(g, gk)), dim3(256), 0, c->stream, rgb_d, w, N, K, labels, cent.as<WideCent>());
+    DevBuf given;
+    if (init_h) {
+        CNIIC_HIP_TRY(c, given.alloc((uint64_t)K * sizeof(cniic_colorpos)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(given.p, init_h, (size_t)K * sizeof(cniic_colorpos), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_xyw_init_from, dim3(std::max(g, gk)), dim3(256), 0, c->stream, (const cniic_colorpos *)given.as<cniic_colorpos>(), N, K, labels, cent.as<WideCent>());
+    } else {
+        hipLaunchKernelGGL(k_xyw_init, dim3(std::max(g, gk)), dim3(256), 0, c->stream, rgb_d, w, N, K, labels, cent.as<WideCent>());
+    }
     uint64_t iter = 0, reseeds = 0, active = 0, changed = 0, evals = 0;
     for (;;) {   // kmeans.rs:26-32: assign, update, until an assign step moves nobody
         hipLaunchKernelGGL(k_xyw_assign, dim3(g), dim3(256), 0, c->stream, rgb_d, w, N, K, (const WideCent *)cent.as<WideCent>(), labels, sums.as<unsigned long long>());

@@ -83,6 +83,18 @@ __global__ void k_xy_init(const uint8_t *__restrict__ rgb, uint32_t w, uint64_t 
     }
 }
 
+// The same from K centroids the caller gives (cniic_kmeans_xyrgb_from): the labels as above, cent from the array through make_cent (the host has
+// held every x against w and every y against h: the 24-bit coordinate products stand on that).
+__global__ void k_xy_init_from(const cniic_colorpos *__restrict__ given, uint64_t N, uint32_t K, uint16_t *__restrict__ labels, int4 *__restrict__ cent) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t i = tid; i < N; i += stride) labels[i] = (uint16_t)init_label(i, N, K);  // kmeans.rs:61-78
+    if (tid < K) {
+        const cniic_colorpos g = given[tid];
+        cent[tid] = make_cent((int32_t)g.x, (int32_t)g.y, ((uint32_t)g.rgb[0] << 16) | ((uint32_t)g.rgb[1] << 8) | g.rgb[2]);
+    }
+}
+
 // static colour extents of every tile: x = r0 | r1<<8 | g0<<16 | g1<<24, y = b0 | b1<<8.  One wave per tile.
 __global__ __launch_bounds__(256) void k_xy_boxes(const uint8_t *__restrict__ rgb, uint32_t w, uint32_t h, uint32_t tiles_x,
                                                   uint32_t ntiles, uint2 *__restrict__ box) {
@@ -938,13 +950,24 @@ static int xy_update(KmXyState &s) {
 static uint32_t xy_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ceil_div(n, 256), 1), 4096); }
 
 int km_xyrgb_run(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t K, const cniic_kmeans_opts *opts,
-                 cniic_colorpos *centroids_h, uint32_t *labels_d_u32, uint64_t *members_h, cniic_kmeans_stats *stats) {
+                 cniic_colorpos *centroids_h, uint32_t *labels_d_u32, uint64_t *members_h, cniic_kmeans_stats *stats, const cniic_colorpos *init_h) {
+    for (uint32_t k = 0; init_h && k < K; k++)
+        if (init_h[k].x >= w || init_h[k].y >= h)
+            return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_xyrgb: given centroid %u at (%u, %u) outside the %u x %u image", k, init_h[k].x, init_h[k].y, w, h);
     // beyond what the tiled kernel is laid out for (table and sums in LDS, 24-bit coordinate products): the exact, slow route
-    if (K > kXMaxK || w > 16384 || h > 16384) return km_xyrgb_run_wide(c, rgb_d, w, h, K, opts, centroids_h, labels_d_u32, members_h, stats);
+    if (K > kXMaxK || w > 16384 || h > 16384) return km_xyrgb_run_wide(c, rgb_d, w, h, K, opts, centroids_h, labels_d_u32, members_h, stats, init_h);
     KmXyState s;
     CNIIC_TRY(xy_create(c, rgb_d, w, h, K, opts, s));
-    hipLaunchKernelGGL(k_xy_init, dim3(xy_grid(std::max<uint64_t>(s.N, K))), dim3(256), 0, c->stream, rgb_d, w, s.N, K,
-                       s.labels.as<uint16_t>(), s.cent.as<int4>());
+    DevBuf given;   // (lives to the end of the run; the copy's source is the caller's array, which outlives the call)
+    if (init_h) {
+        CNIIC_HIP_TRY(c, given.alloc((uint64_t)K * sizeof(cniic_colorpos)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(given.p, init_h, (size_t)K * sizeof(cniic_colorpos), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_xy_init_from, dim3(xy_grid(std::max<uint64_t>(s.N, K))), dim3(256), 0, c->stream, (const cniic_colorpos *)given.as<cniic_colorpos>(), s.N, K,
+                           s.labels.as<uint16_t>(), s.cent.as<int4>());
+    } else {
+        hipLaunchKernelGGL(k_xy_init, dim3(xy_grid(std::max<uint64_t>(s.N, K))), dim3(256), 0, c->stream, rgb_d, w, s.N, K,
+                           s.labels.as<uint16_t>(), s.cent.as<int4>());
+    }
     CNIIC_HIP_TRY(c, hipGetLastError());
     KmDevState hst;
     LaggedPoll poll(c, s.dstate.p);

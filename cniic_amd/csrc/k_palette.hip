@@ -14,6 +14,7 @@
 // longer runs and pay with a wider box, i.e. more candidates (NOTES.md section O).
 // A list longer than list_max (kPalListMax entries of LDS; K in the thousands, many equal entries) sends the cell down the plain route: the
 // same lanes scan all K entries from memory for their colours.  Correct, and nothing claims it is fast.
+// Below it: k_palette_fit, the summed squared error and the pixels per entry of a batch of frames under that table.
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "pal_bounds.hpp"
@@ -123,6 +124,100 @@ int palette_lut(Ctx *c, const uint32_t *cent_d, uint32_t K, bool wide, void *tab
         hipLaunchKernelGGL(k_palette_lut<true>, dim3(kPalCells), dim3(kPalThreads), 0, c->stream, cent_d, K, list_max, table_d, plain_cells_d);
     else
         hipLaunchKernelGGL(k_palette_lut<false>, dim3(kPalCells), dim3(kPalThreads), 0, c->stream, cent_d, K, list_max, table_d, plain_cells_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
+// ---------------------------------------------------------------- how well the palette fits a batch of frames (cniic_palette_fit_frames_var)
+// sse[f] = the sum over frame f's pixels of the squared distance to the pixel's entry under the rule, pixels[k] = the pixels of all frames whose
+// entry is k.  One launch whatever the number of frames: a 1-D grid over the 4096-pixel chunks of all frames (FrameVar, common.hpp); a block finds
+// its frame by the search in chunk0 and never spans two.  Frames of odd sizes start at any byte, so a chunk is cut into a head of < 16 pixels up
+// to the first 16-byte boundary, groups of 16 pixels = three 16-byte loads, a group per thread, and a tail of < 16 pixels (a pixel per lane).
+// A pixel's label is ONE read of the handle's 2^24 table, its entry's colour comes from LDS (K <= 256) or from memory.  |p - e|^2 as
+// p.p + e.e - 2 p.e, three byte dot products; a lane meets at most 17 pixels of at most 195 075 each, a wave's sum stays below 2^28.
+// The counts: K <= 256 in u32 bins of the block's LDS, larger K straight onto the u64 counts -- both through a count that lets the lanes
+// of a wave that hold the same entry add together, so a flat frame costs a wave one add per round and not 64 on one address.
+constexpr int kFitThreads = 256;
+static_assert(kFitThreads * 16 == (int)kFrameVarChunk, "a thread's group is 16 pixels, a block's chunk the frame table's");
+
+// counts[key] += 1 for every calling lane; device_utils.hpp's atomic_count for u64 counts in memory
+__device__ __forceinline__ void fit_count64(unsigned long long *counts, uint32_t key) {
+    bool todo = true;
+#pragma unroll 1
+    for (int r = 0; r < 8; r++) {
+        const unsigned long long act = __ballot(todo);
+        if (!act) return;
+        const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, __builtin_ctzll(act));
+        const bool same = todo && key == k;
+        const unsigned long long sm = __ballot(same);
+        if (same) {
+            if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (uint32_t)__builtin_ctzll(sm)) atomicAdd(&counts[k], (unsigned long long)__popcll(sm));
+            todo = false;
+        }
+    }
+    if (todo) atomicAdd(&counts[key], 1ull);
+}
+
+template <typename LabelT>
+__global__ __launch_bounds__(kFitThreads) void k_palette_fit(const uint8_t *__restrict__ rgb, const FrameVar *__restrict__ fr, uint32_t frames,
+                                                             const LabelT *__restrict__ table, const uint32_t *__restrict__ cent /* [K] 0xRRGGBB */, uint32_t K,
+                                                             unsigned long long *__restrict__ sse /* [frames] */, unsigned long long *__restrict__ pixels /* [K] or null */) {
+    constexpr bool WIDE = sizeof(LabelT) == 2;
+    __shared__ uint32_t s_cent[WIDE ? 1 : 256];
+    __shared__ uint32_t s_bins[WIDE ? 1 : 256];
+    __shared__ uint32_t s_w[kFitThreads / 64];
+    const uint32_t t = threadIdx.x;
+    if (!WIDE) {
+        s_cent[t] = t < K ? cent[t] : 0u;
+        s_bins[t] = 0u;
+        __syncthreads();
+    }
+    const uint32_t f = frame_of_block<&FrameVar::chunk0>(fr, frames, blockIdx.x);
+    const uint64_t in_frame = (uint64_t)(blockIdx.x - fr[f].chunk0) * kFrameVarChunk;   // the chunk's first pixel, counted in its frame
+    const uint32_t cnt = (uint32_t)min((uint64_t)kFrameVarChunk, fr[f].npx - in_frame);  // 1 .. 4096
+    const uint8_t *const base = rgb + 3 * (fr[f].src_base + in_frame);
+    // pixels before the first 16-byte boundary: 3 hd = -address (mod 16), and 11 is 3's inverse
+    const uint32_t hd = min(cnt, (((16u - (uint32_t)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u) * 11u) & 15u);
+    const uint32_t groups = (cnt - hd) / 16u, tail0 = hd + 16u * groups;   // groups <= 256: every thread at most one
+    uint32_t sum = 0;
+    auto one = [&](uint32_t key) {
+        const uint32_t lab = table[key];
+        const uint32_t e = WIDE ? cent[lab] : s_cent[lab];
+        sum += __builtin_amdgcn_udot4(key, key, __builtin_amdgcn_udot4(e, e, 0u, false), false) - 2u * __builtin_amdgcn_udot4(key, e, 0u, false);
+        if (pixels) {
+            if (WIDE) fit_count64(pixels, lab);
+            else atomic_count(s_bins, lab);
+        }
+    };
+    if (t < groups) {
+        uint32_t key[16];
+        load16px_keys(reinterpret_cast<const uint4 *>(base + 3 * hd) + 3 * t, key);
+#pragma unroll
+        for (int i = 0; i < 16; i++) one(key[i]);
+    }
+    // head and tail, a pixel per lane of the first wave: lanes 0 .. 15 the head, lanes 16 .. 31 the tail
+    if (t < 16 ? t < hd : (t < 32 && tail0 + (t - 16) < cnt)) one(rgb_key(base + 3 * (t < 16 ? t : tail0 + (t - 16))));
+    sum = wave_reduce_sum(sum);
+    if ((t & 63) == 0) s_w[t >> 6] = sum;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long all = 0;
+#pragma unroll
+        for (int i = 0; i < kFitThreads / 64; i++) all += s_w[i];
+        if (all) atomicAdd(&sse[f], all);
+    }
+    if (!WIDE && pixels && t < K && s_bins[t]) atomicAdd(&pixels[t], (unsigned long long)s_bins[t]);
+}
+
+// fr_d: the batch's frame table (F rows, `chunks` chunks in all); sse_d: u64[F], pixels_d: u64[K] or null, both zeroed by the caller
+int palette_fit(Ctx *c, const uint8_t *rgb_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, const void *table_d, bool wide, const uint32_t *cent_d, uint32_t K,
+                uint64_t *sse_d, uint64_t *pixels_d) {
+    if (!frames || !chunks || !K || (!wide && K > 256u)) return c->fail(CNIIC_ERR_BAD_ARG, "palette_fit: %u frames, K = %u", frames, K);
+    auto *sse = reinterpret_cast<unsigned long long *>(sse_d), *px = reinterpret_cast<unsigned long long *>(pixels_d);
+    if (wide)
+        hipLaunchKernelGGL(k_palette_fit<uint16_t>, dim3(chunks), dim3(kFitThreads), 0, c->stream, rgb_d, fr_d, frames, static_cast<const uint16_t *>(table_d), cent_d, K, sse, px);
+    else
+        hipLaunchKernelGGL(k_palette_fit<uint8_t>, dim3(chunks), dim3(kFitThreads), 0, c->stream, rgb_d, fr_d, frames, static_cast<const uint8_t *>(table_d), cent_d, K, sse, px);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }

@@ -70,6 +70,9 @@ struct KmRgbwState {
     DevBuf ps_pk;                // packed words of the points that do not fit their block's LDS
     uint64_t ps_o_part = 0, ps_o_fail = 0, ps_o_rng = 0;
     uint32_t ps_budget = 0;      // bytes of dynamic LDS the block ranges were made for
+    bool started = false;        // an assign has been enqueued (or the persistent launch): too late for km_rgbw_set_centroids
+    DevBuf given;                // km_rgbw_set_centroids: the caller's K centroids as 0xRRGGBB words, and the host copy the upload reads
+    std::vector<uint32_t> given_h;
 };
 
 // ---- k_kmeans_persist.hip: the LDS of a block and what the launch shares with its set-up

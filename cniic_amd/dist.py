@@ -85,6 +85,13 @@ class HipBackend:
         o = _lib.KmOpts(seed, max_iters, flags, 0)
         self.ctx._check(self.L.cniic_cc_image_create(h, C.c_void_p(occ.data_ptr()), C.c_uint32(K), C.byref(o), C.c_void_p(partials.data_ptr())))
 
+    def set_centroids(self, h, init, allow=()):
+        """cniic_cc_set_centroids: the session's K-means starts from init ((K, 3) uint8, host) instead of the chunk heads; before the
+        first assign / run only (BAD_ARG afterwards, the session unchanged) -> status"""
+        import numpy as np
+        init = np.ascontiguousarray(init, np.uint8)
+        return self.ctx._check(self.L.cniic_cc_set_centroids(h, _lib._ptr(init)), allow)
+
     def assign(self, h):
         self.ctx._check(self.L.cniic_cc_assign(h))
 

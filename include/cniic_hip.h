@@ -159,6 +159,30 @@ int32_t cniic_kmeans_xyrgb(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint3
                            cniic_colorpos *centroids, uint32_t *labels, uint64_t *members,
                            cniic_kmeans_stats *stats);
 
+/* ---- K-means from given centroids -- an extension, as shared and frozen palettes are: the reference always starts from init_centroids.
+ *
+ * THE DEFINITION.  It is kmeans::cluster (kmeans.rs:21-39) with only init_centroids (kmeans.rs:101-108) replaced by the caller's K
+ * centroids.  Everything else is unchanged: init_assignment by position in the point list (kmeans.rs:61-78), so the first assign starts
+ * from the chunk labels; a point stays unless another centroid is STRICTLY nearer; the lowest index among equal minima; the integer
+ * means; the seeded empty-cluster reseed with its iteration number; max_iters, CNIIC_ERR_TOO_FEW_POINTS, CNIIC_ERR_FEW_ACTIVE.  Two
+ * consequences:
+ *   - A run started from its own reference init centroids (the first element of chunk k) is the ordinary run, bit for bit.
+ *   - A run started from a converged palette need not stop after one iteration: the initial labels are the chunk labels, not the
+ *     assignment the palette converged with, so colours equidistant from two centroids resolve differently (they stay with their chunk's
+ *     cluster where they can), the means move, and a few more iterations follow.
+ * init is always HOST memory: K x 3 bytes r, g, b for colours, K cniic_colorpos for voronoi (pad ignored).  Equal entries are legal.
+ * cniic_kmeans_xyrgb_from: init[k].x >= w or init[k].y >= h returns CNIIC_ERR_BAD_ARG (the tiled kernel's 24-bit coordinate products stand
+ * on coordinates inside the image); it takes the tiled route and the exact slow route (K > 4096, a side above 16384) as cniic_kmeans_xyrgb
+ * does.  Everything else as the calls above. */
+int32_t cniic_kmeans_rgbw_from(cniic_ctx *ctx, const uint32_t *keys, const uint32_t *weight, uint64_t U,
+                               uint32_t K, const cniic_kmeans_opts *opts, const uint8_t *init,
+                               uint8_t *centroids, uint32_t *labels, uint64_t *members,
+                               cniic_kmeans_stats *stats);
+int32_t cniic_kmeans_xyrgb_from(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h,
+                                uint32_t K, const cniic_kmeans_opts *opts, const cniic_colorpos *init,
+                                cniic_colorpos *centroids, uint32_t *labels, uint64_t *members,
+                                cniic_kmeans_stats *stats);
+
 /* One assign step from given centroids and labels (src/kmeans.rs:330-416 + the sums consumed by
  * Point::mean): labels updated in place; sums[K x D] (D = 3 / 5), wsum[K] (sum of weights, or
  * member count), members[K], *changed.  Centroids are not updated.  For parity tests and for
@@ -223,6 +247,11 @@ int32_t  cniic_cc_create(cniic_ctx *ctx, uint32_t *table_dev, uint32_t K, const 
 uint64_t cniic_cc_unique(cniic_cc *cc);        /* distinct colours U */
 uint32_t cniic_cc_label_bytes(cniic_cc *cc);   /* 1 (K <= 256) or 2: element size of the label buffers */
 int32_t  cniic_cc_partials(cniic_cc *cc, void **dev_ptr);
+/* The session's K-means started from the caller's centroids ("K-means from given centroids" above; init: host, K x 3 bytes).  Valid on any
+ * session that has its K-means state, however it was made (cniic_cc_create, cniic_cc_create_local, cniic_cc_image_create; any shard count:
+ * every rank must pass the same bytes), and only before the session's first cniic_cc_assign / cniic_cc_run: afterwards it returns
+ * CNIIC_ERR_BAD_ARG and the session stays as it was.  The loop, cniic_cc_finish* and cniic_cc_palette follow unchanged. */
+int32_t  cniic_cc_set_centroids(cniic_cc *cc, const uint8_t *init);
 int32_t  cniic_cc_assign(cniic_cc *cc);                        /* async on the ctx stream */
 int32_t  cniic_cc_update(cniic_cc *cc, uint64_t *changed);     /* syncs; changed == NULL: asynchronous */
 /* iterations completed so far and whether an iteration has moved nothing (syncs).  Iterations issued
@@ -302,6 +331,15 @@ int32_t  cniic_palette_labels(cniic_palette *pal, const uint8_t *rgb, uint64_t n
  * cniic_cc_finish_frames_var stages them.  Stage timers: "pal_labels", then the frames_var_* names of that call. */
 int32_t  cniic_palette_encode_frames_var(cniic_palette *pal, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames,
                                          uint8_t *out, uint64_t stride, uint64_t *lens);
+
+/* How well the handle's palette fits a batch of frames, without coding them: frames back to back in rgb (host or device memory) as for
+ * cniic_palette_encode_frames_var.  sse[f] (host, u64[frames]) = the exact integer sum over frame f's pixels of the squared distance to the
+ * pixel's entry under THE RULE: 3 w[f] h[f] times the MSE of decoding that frame's cniic_palette_encode_frames_var stream.  pixels (host,
+ * u64[K], may be NULL) = the pixels of all frames per entry; an entry shadowed by an equal one of lower index gets 0.  One kernel launch
+ * whatever the number of frames, no label buffer.  CNIIC_ERR_BAD_ARG: a null argument or frames == 0, any w[f] * h[f] == 0.
+ * Stage timer: "pal_fit". */
+int32_t  cniic_palette_fit_frames_var(cniic_palette *pal, const uint8_t *rgb, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                      uint64_t *sse, uint64_t *pixels);
 
 /* The same shared palette with every rank holding ONLY ITS OWN image's colours (per-rank work and memory do not
  * grow with the number of ranks, no label exchange).  The reference's point list -- the ascending list of the
@@ -460,6 +498,13 @@ int32_t cniic_codec_encode(cniic_ctx *ctx, const char *expr, const uint8_t *rgb,
 /* same, with explicit K-means options (seed, iteration cap) */
 int32_t cniic_codec_encode_opts(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb,
                                 uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len,
+                                cniic_kmeans_stats *stats);
+/* cniic_codec_encode_opts for cluster-colors(K) and voronoi(K) with the K-means started from init ("K-means from given centroids" above:
+ * host memory, K x 3 bytes for cluster-colors, K cniic_colorpos for voronoi).  centroids_out (host, may be NULL) receives the final K
+ * centroids in init's layout after a successful encode: what the caller passes as init for the next frame of a video.  The streams are
+ * ordinary streams of those codecs; CNIIC_ERR_CAPACITY with *len = bytes needed as the cold call.  Any other expression: CNIIC_ERR_BAD_ARG. */
+int32_t cniic_codec_encode_warm(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const void *init, const uint8_t *rgb,
+                                uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len, void *centroids_out,
                                 cniic_kmeans_stats *stats);
 /* The harness's many-images loop (src/bench.rs:24-35: `paths.into_par_iter()`, one Codec::encode per rayon worker) as ONE call, for
  * EQUALLY SIZED images (cniic_codec_encode_batch_var below takes a folder of any sizes):
