@@ -7,8 +7,8 @@ cniic_amd/csrc/).  This package is the thin host-side mirror of the reference's 
 (src/codec.rs:14-19) over that ABI via ctypes; it holds no compute of its own and raises if the
 HIP library is missing.
 """
-from ._lib import CniicError, Context, Palette, channel_diff_hist, hilbert_linearize, lib, lib_path  # noqa: F401
+from ._lib import CniicError, Context, Palette, Surface, channel_diff_hist, hilbert_linearize, lib, lib_path, surface_span  # noqa: F401
 from .codec import AnyCodec, Codec, HilbertRleApprox, HilbertZip, ZipBack  # noqa: F401
 
-__all__ = ["AnyCodec", "Codec", "Context", "CniicError", "HilbertRleApprox", "HilbertZip", "ZipBack", "channel_diff_hist", "hilbert_linearize", "lib",
-           "lib_path"]
+__all__ = ["AnyCodec", "Codec", "Context", "CniicError", "HilbertRleApprox", "HilbertZip", "Surface", "ZipBack", "channel_diff_hist", "hilbert_linearize", "lib",
+           "lib_path", "surface_span"]

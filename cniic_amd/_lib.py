@@ -19,6 +19,9 @@ SYNTH_UNIFORM, SYNTH_PHOTO = 0, 1
 KM_BRUTE_FORCE, KM_PROFILE, KM_NO_SKIP = 1, 2, 4
 LIN_RECT, LIN_SMALL, LIN_LARGE = 0, 1, 2
 LIN_METHODS = {"rect": LIN_RECT, "small": LIN_SMALL, "large": LIN_LARGE}   # hilbert.rs:10-32
+PX_L8, PX_LA8, PX_RGB8, PX_RGBA8, PX_BGR8, PX_BGRA8, PX_NV12 = range(1, 8)
+PX_BYTES = {PX_L8: 1, PX_LA8: 2, PX_RGB8: 3, PX_RGBA8: 4, PX_BGR8: 3, PX_BGRA8: 4, PX_NV12: 1}   # per pixel (NV12: of the Y plane)
+YUV_601_LIMITED, YUV_601_FULL, YUV_709_LIMITED, YUV_709_FULL = range(1, 5)
 OPT_SP_MIN_PIXELS, OPT_HUF_GPU_CODES_MIN, OPT_GPU_DECODE_MIN, OPT_DELTA_ROUTE, OPT_STAGE_TIMERS, OPT_FRAME_TREES_HOST, OPT_BATCH_STREAMS, OPT_KM_MAX_BLOCKS, OPT_KM_LOOP = range(1, 10)
 
 # every symbol include/cniic_hip.h declares (checked by tests/test_abi.py)
@@ -46,6 +49,7 @@ SYMBOLS = [
     "cniic_cc_palette", "cniic_palette_create", "cniic_palette_destroy", "cniic_palette_label_bytes", "cniic_palette_labels",
     "cniic_palette_encode_frames_var",
     "cniic_kmeans_rgbw_from", "cniic_kmeans_xyrgb_from", "cniic_cc_set_centroids", "cniic_codec_encode_warm", "cniic_palette_fit_frames_var",
+    "cniic_surface_span", "cniic_frames_from_surfaces", "cniic_frames_to_surfaces",
 ]
 
 
@@ -74,6 +78,12 @@ class MeasureRow(C.Structure):
     def as_dict(self):
         return dict(compressed_size=int(self.compressed_size), compression_ratio=float(self.compression_ratio), error=float(self.error),
                     rc=int(self.rc), lossless_mismatch=int(self.lossless_mismatch), kmeans=self.kmeans.as_dict())
+
+
+class Surface(C.Structure):
+    """cniic_surface: one pitched surface inside a larger buffer (offsets in bytes from the buffer's first byte)"""
+    _fields_ = [("off", C.c_uint64), ("pitch", C.c_uint64), ("off_uv", C.c_uint64), ("pitch_uv", C.c_uint64), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("format", C.c_int32), ("matrix", C.c_int32)]
 
 
 COLORPOS = np.dtype([("x", "<u4"), ("y", "<u4"), ("rgb", "u1", (3,)), ("pad", "u1")])
@@ -126,6 +136,8 @@ def lib():
             _palette_prototypes(L)
         if hasattr(L, "cniic_cc_set_centroids"):   # (likewise: K-means from given centroids, the fit of a handle)
             _warm_prototypes(L)
+        if hasattr(L, "cniic_surface_span"):   # (likewise: surfaces)
+            _surface_prototypes(L)
         _lib = L
     return _lib
 
@@ -154,6 +166,15 @@ def _warm_prototypes(L):
     L.cniic_codec_encode_warm.restype = C.c_int32
     L.cniic_codec_encode_warm.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                           C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+
+
+def _surface_prototypes(L):
+    L.cniic_surface_span.restype = C.c_int32
+    L.cniic_surface_span.argtypes = [C.POINTER(Surface), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.cniic_frames_from_surfaces.restype = C.c_int32
+    L.cniic_frames_from_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Surface), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.cniic_frames_to_surfaces.restype = C.c_int32
+    L.cniic_frames_to_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(Surface), C.c_uint32, C.c_void_p, C.c_uint32]
 
 
 def _ptr(x):
@@ -696,6 +717,23 @@ class Context:
         self._check(self._L.cniic_mse_batch_var(self.h, _ptr(a), ao, _ptr(b), bo, px, C.c_uint32(F), v))
         return [float(v[f]) for f in range(F)]
 
+    def frames_from_surfaces(self, src, surfaces, rgb, img_offs, allow=()):
+        """cniic_frames_from_surfaces: surface f of src (a list of Surface) -> packed RGB24 at rgb[img_offs[f]:], all frames in one launch.
+        src / rgb: device tensors, numpy arrays or addresses.  With device memory on both sides the call is asynchronous on the
+        context's stream (sync() waits).  -> rc"""
+        F = len(surfaces)
+        n = max(F, 1)
+        return self._check(self._L.cniic_frames_from_surfaces(self.h, _ptr(src), (Surface * n)(*surfaces), C.c_uint32(F), _ptr(rgb),
+                                                              (C.c_uint64 * n)(*[int(x) for x in img_offs])), allow)
+
+    def frames_to_surfaces(self, rgb, img_offs, surfaces, dst, alpha=255, allow=()):
+        """cniic_frames_to_surfaces: packed RGB24 at rgb[img_offs[f]:] -> surface f of dst (RGB8 / BGR8 / RGBA8 / BGRA8; the alpha byte
+        written is `alpha`), the pitch's padding untouched.  -> rc"""
+        F = len(surfaces)
+        n = max(F, 1)
+        return self._check(self._L.cniic_frames_to_surfaces(self.h, _ptr(rgb), (C.c_uint64 * n)(*[int(x) for x in img_offs]), (Surface * n)(*surfaces),
+                                                            C.c_uint32(F), _ptr(dst), C.c_uint32(alpha)), allow)
+
     def measure_batch(self, expr, images, offs, ws, hs, out=None, stride=0, seed=0, max_iters=0, flags=0, allow=()):
         """cniic_codec_measure_batch: encode, size, ratio, decode, MSE and the lossless check of every image in one call (the body of
         bench::measure_all's loop).  out (optional): stream f is copied to out[f * stride:].
@@ -859,6 +897,14 @@ class Palette:
         if allow:
             return rc, sse[:F], pixels
         return sse[:F], pixels
+
+
+def surface_span(s):
+    """cniic_surface_span (host only, no context): (one past the last byte of the buffer the surface spans, 3 w h), or None for a
+    descriptor the calls refuse"""
+    end, nb = C.c_uint64(0), C.c_uint64(0)
+    rc = lib().cniic_surface_span(C.byref(s), C.byref(end), C.byref(nb))
+    return (end.value, nb.value) if rc == OK else None
 
 
 def linearize_count(method, w, h):

@@ -13,6 +13,7 @@
 
 #include "common.hpp"
 #include "huff_host.hpp"
+#include "surf_index.hpp"
 
 using namespace cniic;
 
@@ -106,6 +107,7 @@ void cniic_ctx_destroy(cniic_ctx *c) {
     if (c->pinned_u) (void)hipHostFree(c->pinned_u);
     if (c->u_ev) (void)hipEventDestroy(c->u_ev);
     if (c->huf_ev) (void)hipEventDestroy(c->huf_ev);
+    if (c->surf_ev) (void)hipEventDestroy(c->surf_ev);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1511,6 +1513,100 @@ int32_t cniic_mse_batch_var(cniic_ctx *c, const uint8_t *a, const uint64_t *a_of
     if (!frames) return CNIIC_OK;
     if (!mse || !a_off || !b_off || !npx) return c->fail(CNIIC_ERR_BAD_ARG, "mse_batch_var: null argument");
     return mse_batch_var_locked(c, a, a_off, b, b_off, npx, frames, mse);
+}
+
+// ---- pitched surfaces <-> packed RGB24 frames (cniic_surface_span, cniic_frames_from_surfaces, cniic_frames_to_surfaces)
+// one descriptor: nullptr if it is in order (then *first / *end = the bytes of the surface side it spans, *rgb_bytes = 3 w h), else what is wrong
+static const char *surface_check(const cniic_surface &s, uint64_t *first, uint64_t *end, uint64_t *rgb_bytes) {
+    const uint32_t bpp = surf_bpp(s.format);
+    if (!bpp) return "unknown format";
+    const uint64_t npx = (uint64_t)s.w * s.h;
+    if (!npx || npx >> 32) return "w * h must be in [1, 2^32)";
+    const uint64_t row = (uint64_t)s.w * bpp;
+    if (s.pitch < row) return "pitch below the row's bytes";
+    typedef unsigned __int128 u128;
+    u128 e = (u128)s.off + (u128)(s.h - 1) * s.pitch + row;
+    uint64_t lo = s.off;
+    if (s.format == CNIIC_PX_NV12) {
+        if (s.matrix < CNIIC_YUV_601_LIMITED || s.matrix > CNIIC_YUV_709_FULL) return "NV12 needs a CNIIC_YUV_* matrix";
+        const uint64_t row_uv = 2 * (((uint64_t)s.w + 1) / 2);
+        if (s.pitch_uv < row_uv) return "pitch_uv below the UV row's bytes";
+        e = std::max(e, (u128)s.off_uv + (u128)(((uint64_t)s.h + 1) / 2 - 1) * s.pitch_uv + row_uv);
+        lo = std::min(lo, s.off_uv);
+    }
+    if (e >> 64) return "the surface's end does not fit 64 bits";
+    *first = lo; *end = (uint64_t)e; *rgb_bytes = npx * 3;
+    return nullptr;
+}
+
+int32_t cniic_surface_span(const cniic_surface *s, uint64_t *src_end, uint64_t *rgb_bytes) {
+    uint64_t first;
+    if (!s || !src_end || !rgb_bytes || surface_check(*s, &first, src_end, rgb_bytes)) return CNIIC_ERR_BAD_ARG;
+    return CNIIC_OK;
+}
+
+// both directions, the context's mutex held: surf = the surface side (read by the import, written by the export), rgb = the packed side
+static int32_t surfaces_locked(cniic_ctx *c, const char *who, bool to_surfaces, uint8_t *surf, const cniic_surface *s, uint32_t frames, uint8_t *rgb,
+                               const uint64_t *img_off, uint32_t alpha) {
+    if (!frames) return CNIIC_OK;
+    if (!surf || !s || !rgb || !img_off) return c->fail(CNIIC_ERR_BAD_ARG, "%s: null argument", who);
+    if (to_surfaces && alpha > 255) return c->fail(CNIIC_ERR_BAD_ARG, "%s: alpha is a byte", who);
+    std::vector<SurfFrame> fr(frames);
+    uint64_t lo[2] = {~0ull, ~0ull}, hi[2] = {0, 0};   // [0]: the surface side, [1]: the packed side
+    for (uint32_t f = 0; f < frames; f++) {
+        uint64_t first, end, bytes;
+        if (const char *why = surface_check(s[f], &first, &end, &bytes)) return c->fail(CNIIC_ERR_BAD_ARG, "%s: surface %u: %s", who, f, why);
+        if (to_surfaces && (s[f].format == CNIIC_PX_L8 || s[f].format == CNIIC_PX_LA8 || s[f].format == CNIIC_PX_NV12))
+            return c->fail(CNIIC_ERR_BAD_ARG, "%s: surface %u: only RGB8, BGR8, RGBA8 and BGRA8 can be written", who, f);
+        if (img_off[f] + bytes < bytes) return c->fail(CNIIC_ERR_BAD_ARG, "%s: frame %u ends behind 2^64", who, f);
+        fr[f] = {s[f].off, s[f].pitch, s[f].off_uv, s[f].pitch_uv, img_off[f], s[f].w, s[f].h, s[f].format, s[f].matrix};
+        lo[0] = std::min(lo[0], first); hi[0] = std::max(hi[0], end);
+        lo[1] = std::min(lo[1], img_off[f]); hi[1] = std::max(hi[1], img_off[f] + bytes);
+    }
+    // a host side lives in scratch from its first used byte to its last: its offsets move down by lo
+    const bool surf_host = !is_device_ptr(surf), rgb_host = !is_device_ptr(rgb);
+    DevBuf stage[2];
+    uint8_t *base[2] = {surf, rgb};
+    for (int side = 0; side < 2; side++) {
+        if (!(side ? rgb_host : surf_host)) continue;
+        CNIIC_HIP_TRY(c, stage[side].alloc(hi[side] - lo[side]));
+        if ((side == 1) == to_surfaces)   // the side that is read
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(stage[side].p, base[side] + lo[side], hi[side] - lo[side], hipMemcpyHostToDevice, c->stream));
+        base[side] = stage[side].as<uint8_t>();
+        for (uint32_t f = 0; f < frames; f++) {
+            if (side) fr[f].rgb_off -= lo[1];
+            else { fr[f].off -= lo[0]; if (fr[f].format == CNIIC_PX_NV12) fr[f].off_uv -= lo[0]; }
+        }
+    }
+    if (to_surfaces) CNIIC_TRY(surf_convert(c, true, base[1], base[0], fr.data(), frames, alpha));
+    else CNIIC_TRY(surf_convert(c, false, base[0], base[1], fr.data(), frames, 0));
+    // the written side back to a host caller: exactly the bytes the kernel wrote, frame by frame (row by row for a surface)
+    if (!to_surfaces && rgb_host)
+        for (uint32_t f = 0; f < frames; f++)
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(rgb + img_off[f], base[1] + fr[f].rgb_off, 3ull * fr[f].w * fr[f].h, hipMemcpyDeviceToHost, c->stream));
+    if (to_surfaces && surf_host)
+        for (uint32_t f = 0; f < frames; f++) {
+            const uint64_t row = (uint64_t)s[f].w * surf_bpp(s[f].format);
+            if (s[f].pitch == row || s[f].h == 1)
+                CNIIC_HIP_TRY(c, hipMemcpyAsync(surf + s[f].off, base[0] + fr[f].off, (s[f].h - 1) * s[f].pitch + row, hipMemcpyDeviceToHost, c->stream));
+            else
+                CNIIC_HIP_TRY(c, hipMemcpy2DAsync(surf + s[f].off, s[f].pitch, base[0] + fr[f].off, s[f].pitch, row, s[f].h, hipMemcpyDeviceToHost, c->stream));
+        }
+    if (surf_host || rgb_host) CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+int32_t cniic_frames_from_surfaces(cniic_ctx *c, const uint8_t *src, const cniic_surface *s, uint32_t frames, uint8_t *rgb, const uint64_t *img_off) {
+    LOCK(c);
+    c->ktimes.clear();
+    return surfaces_locked(c, "frames_from_surfaces", false, const_cast<uint8_t *>(src), s, frames, rgb, img_off, 0);
+}
+
+int32_t cniic_frames_to_surfaces(cniic_ctx *c, const uint8_t *rgb, const uint64_t *img_off, const cniic_surface *s, uint32_t frames, uint8_t *dst,
+                                 uint32_t alpha) {
+    LOCK(c);
+    c->ktimes.clear();
+    return surfaces_locked(c, "frames_to_surfaces", true, dst, s, frames, const_cast<uint8_t *>(rgb), img_off, alpha);
 }
 
 // ---- bench::measure_all's loop body for a whole folder (cniic_codec_measure_batch)

@@ -161,6 +161,7 @@ struct Ctx {
     void  *pinned_huf = nullptr;  // pinned host memory, grown on demand: the Huffman code stage's counts, tree and codes (HuffCodeStage, codec.cpp); a decode's stream heads
     uint64_t pinned_huf_bytes = 0;
     hipEvent_t huf_ev = nullptr;   // behind the D2H copies of the compacted histogram (huf_encode_all_dev)
+    hipEvent_t surf_ev = nullptr;  // behind the upload of a surface call's frame and chunk tables: the call returns while its kernel runs, not before that copy has read the host's vectors (k_surface.hip)
     std::shared_ptr<void> scan_leaves;  // the built-in scan of large rectangles: per image size, the recursion's leaves and class tables (k_hilbert.hip)
     DevBuf scan_xy;         // cniic_ctx_set_scan: an injected scan of scan_w x scan_h images, (x, y) per position (uint2[w h])
     uint32_t scan_w = 0, scan_h = 0;
@@ -637,6 +638,12 @@ int mse_rgb_batch(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, uint64_t npx, 
 int mse_rgb_batch_var(Ctx *c, const uint8_t *a_d, const uint8_t *b_d, const uint64_t *a_off, const uint64_t *b_off, const uint64_t *npx,
                       uint32_t frames, double *mse_h);
 int synth_image(Ctx *c, int kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *out_d);
+
+// ---- k_surface.hip: pitched surfaces <-> packed RGB24 frames (cniic_frames_from_surfaces / cniic_frames_to_surfaces) ----
+// a validated cniic_surface (offsets from the surface side's device pointer) + where its packed frame starts (from the packed side's)
+struct SurfFrame { uint64_t off, pitch, off_uv, pitch_uv, rgb_off; uint32_t w, h; int32_t format, matrix; };
+// one launch for all frames; to_surfaces: in_d = the packed frames, out_d = the surfaces (alpha: the fourth byte of RGBA8 / BGRA8)
+int surf_convert(Ctx *c, bool to_surfaces, const uint8_t *in_d, uint8_t *out_d, const SurfFrame *fr_h, uint32_t frames, uint32_t alpha);
 int rgb_to_keys(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t *keys_d);
 
 // ---- colour-space cells of the cluster-colors K-means (numbering: cell_of in device_utils.hpp) ----

@@ -646,6 +646,66 @@ int32_t cniic_codec_measure_batch(cniic_ctx *ctx, const char *expr, const cniic_
                                   const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows,
                                   uint8_t *out, uint64_t stride, uint64_t *lens);
 
+/* ------------------------------------------------------------------ surfaces: what a decoder or a crop hands over <-> packed RGB24 */
+/* Every call above takes packed RGB24, rows back to back; the reference takes an image::DynamicImage and begins with px.to_rgb() per
+ * pixel (clusterc.rs:19,151, hilbertc.rs:29,410, zipc.rs:19, bench.rs:97).  These two calls are that step for frames that already lie
+ * in HBM the way a video pipeline delivers them: with a row pitch, as grey, RGBA, BGRA or NV12, or as a window of a larger image.
+ * One kernel launch per call whatever the number of frames, written exactly where the *_batch_var, cniic_cc_*_var and
+ * cniic_palette_*_var calls read (rgb + img_off[f], any alignment). */
+#define CNIIC_PX_L8    1   /* 1 B/px: (l, l, l)              Luma<u8>::to_rgb()                 */
+#define CNIIC_PX_LA8   2   /* 2 B/px: l, a -> (l, l, l)      alpha dropped                      */
+#define CNIIC_PX_RGB8  3   /* 3 B/px: copy (a pitched image, a crop)                            */
+#define CNIIC_PX_RGBA8 4   /* 4 B/px: alpha dropped          Rgba<u8>::to_rgb()                 */
+#define CNIIC_PX_BGR8  5   /* 3 B/px: the ends swapped                                          */
+#define CNIIC_PX_BGRA8 6   /* 4 B/px: the ends swapped, alpha dropped                           */
+#define CNIIC_PX_NV12  7   /* Y plane + interleaved U,V plane at half resolution both ways      */
+/* NV12: pixel (x, y) takes Y from the Y plane and (U, V) from pair x >> 1 of UV row y >> 1 (the nearest chroma sample, no
+ * interpolation; the UV plane has ceil(h / 2) rows of ceil(w / 2) pairs).  With D = U - 128, E = V - 128, floor() a floor and every
+ * result clipped to 0 ... 255, in 32-bit integers (the largest magnitude is below 2^18) and without any floating point:
+ *   matrix         C        R                                  G                                          B
+ *   601 limited    Y - 16   floor((298 C + 409 E + 128) / 256)  floor((298 C - 100 D - 208 E + 128) / 256)  floor((298 C + 516 D + 128) / 256)
+ *   709 limited    Y - 16   floor((298 C + 459 E + 128) / 256)  floor((298 C -  55 D - 136 E + 128) / 256)  floor((298 C + 541 D + 128) / 256)
+ *   601 full       Y        floor((256 C + 359 E + 128) / 256)  floor((256 C -  88 D - 183 E + 128) / 256)  floor((256 C + 454 D + 128) / 256)
+ *   709 full       Y        floor((256 C + 403 E + 128) / 256)  floor((256 C -  48 D - 120 E + 128) / 256)  floor((256 C + 475 D + 128) / 256)
+ * This table is the definition. */
+#define CNIIC_YUV_601_LIMITED 1
+#define CNIIC_YUV_601_FULL    2
+#define CNIIC_YUV_709_LIMITED 3
+#define CNIIC_YUV_709_FULL    4
+typedef struct {
+    uint64_t off;       /* first byte of row 0 (NV12: of the Y plane), from the base pointer  */
+    uint64_t pitch;     /* bytes from one row to the next, >= w * bytes per pixel             */
+    uint64_t off_uv;    /* NV12: first byte of the UV plane; otherwise ignored                */
+    uint64_t pitch_uv;  /* NV12: >= 2 * ceil(w / 2); otherwise ignored                        */
+    uint32_t w, h;
+    int32_t  format;    /* CNIIC_PX_*  */
+    int32_t  matrix;    /* NV12: CNIIC_YUV_*; otherwise ignored */
+} cniic_surface;
+
+/* HOST only, no context: validates one descriptor.  *src_end = one past the last byte the import may read (from the base pointer),
+ * *rgb_bytes = 3 w h.  CNIIC_ERR_BAD_ARG for what the calls below refuse in a descriptor: a null argument, an unknown format, NV12
+ * without a known matrix, w h == 0 or w h >= 2^32, a pitch below the row's bytes (pitch_uv below 2 ceil(w / 2)), a surface whose end
+ * does not fit 64 bits. */
+int32_t cniic_surface_span(const cniic_surface *s, uint64_t *src_end, uint64_t *rgb_bytes);
+/* Frame f: surface s[f] of src -> packed RGB24 at rgb + img_off[f].  L8 / LA8 give r = g = b = l, RGB8 is a copy, RGBA8 drops a, BGR8 /
+ * BGRA8 swap the ends, NV12 as above; bytes of a source row behind w * bytes per pixel (the pitch's padding) are never read.
+ * s and img_off are HOST arrays of `frames` entries; src and rgb are host or device memory (host memory is staged through the context's
+ * scratch: the source as ONE range from the first byte any surface reads to the last, a host rgb frame by frame, so that nothing
+ * between the frames is written).  Any offsets, pitches and alignments are legal, and several surfaces may read the same bytes (32
+ * windows of one image are 32 descriptors on it).  Source and destination may not overlap; this is not checked.  With device memory
+ * on both sides the call returns once the launch is enqueued on the context's stream (cniic_sync waits for it; a later call on this
+ * context is ordered behind it).  frames == 0 returns CNIIC_OK.  CNIIC_ERR_BAD_ARG with NOTHING written: a null argument, a descriptor
+ * that cniic_surface_span refuses, a frame whose end (img_off[f] + 3 w h) does not fit 64 bits.  Stage timer: "surf_import", launches = 1. */
+int32_t cniic_frames_from_surfaces(cniic_ctx *ctx, const uint8_t *src, const cniic_surface *s, uint32_t frames,
+                                   uint8_t *rgb, const uint64_t *img_off);
+/* The way back, for display: packed RGB24 at rgb + img_off[f] -> surface s[f] of dst; RGB8 / BGR8 / RGBA8 / BGRA8 only, and the alpha
+ * byte written is `alpha`.  Bytes of a destination row behind w * bytes per pixel are not written.  Memory and arguments as above (a
+ * host dst is filled row by row, so its padding stays as it was); a 4-byte format whose rows do not start on a multiple of 4 is
+ * legal and written in byte stores.  CNIIC_ERR_BAD_ARG with nothing written: as above, and L8, LA8 or NV12, and alpha > 255.
+ * Stage timer: "surf_export", launches = 1. */
+int32_t cniic_frames_to_surfaces(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const cniic_surface *s,
+                                 uint32_t frames, uint8_t *dst, uint32_t alpha);
+
 /* ------------------------------------------------------------------ synthetic inputs (bench/tests) */
 #define CNIIC_SYNTH_UNIFORM 0  /* "U": splitmix64 byte stream                               */
 #define CNIIC_SYNTH_PHOTO   1  /* "P": bilinear 64-px lattice + noise, photo-like statistics */
