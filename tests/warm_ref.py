@@ -14,9 +14,10 @@ import oracle_lib as O
 DIM = {O.PT_RGBW: 3, O.PT_XYRGB: 5}
 
 
-def lloyd_from(kind, pts, weight, K, init, seed=O.DEFAULT_SEED, max_iters=0):
+def lloyd_from(kind, pts, weight, K, init, seed=O.DEFAULT_SEED, max_iters=0, trace=None):
     """-> (rc, dict(rc, centroids int32 (K, D), labels, members, iterations, empty_reseeds, moved_last, active)); rc is OK or FEW_ACTIVE (the
-    results are there in both cases, as from the library), or TOO_FEW_POINTS with no results"""
+    results are there in both cases, as from the library), or TOO_FEW_POINTS with no results.
+    trace: a list that receives, per assign step, (the centroid table the step used, the labels it started from)"""
     D = DIM[kind]
     pts = np.ascontiguousarray(pts, np.int32).reshape(-1, D)
     n = pts.shape[0]
@@ -28,6 +29,8 @@ def lloyd_from(kind, pts, weight, K, init, seed=O.DEFAULT_SEED, max_iters=0):
     members = np.zeros(K, np.uint64)
     changed = 1
     while changed:                                          # kmeans.c:292
+        if trace is not None:
+            trace.append((cent.copy(), labels.copy()))
         r = O.kmeans_step(kind, pts, weight, K, cent, labels)                                        # :298
         labels, members, changed = r["labels"], r["members"], r["changed"]
         cent, res = O.kmeans_finalize(kind, pts, K, seed, iterations, r["sums"], r["wsum"], members)   # :302, the count before the increment
