@@ -17,15 +17,6 @@
 
 using namespace cniic;
 
-struct cniic_ctx : public Ctx {};
-
-// routes every DevBuf allocated during the call through the context's caching pool
-struct PoolScope {
-    DevPool *prev;
-    explicit PoolScope(DevPool *p) : prev(current_pool()) { current_pool() = p; }
-    ~PoolScope() { current_pool() = prev; }
-};
-
 struct cniic_km {
     Ctx *c = nullptr;
     KmRgbwState *st = nullptr;
@@ -38,7 +29,7 @@ struct cniic_km {
     if (!(ctx)) return CNIIC_ERR_BAD_ARG;  \
     std::lock_guard<std::mutex> _lk((ctx)->mu); \
     (ctx)->err.clear();                    \
-    PoolScope _ps(&(ctx)->pool);           \
+    PoolScope _ps(&(ctx)->pool);           /* every DevBuf allocated during the call comes from the context's caching pool */ \
     do { hipError_t _e = hipSetDevice((ctx)->device); if (_e != hipSuccess) return (ctx)->fail(CNIIC_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(_e)); } while (0)
 
 // results computed into host vectors -> caller buffer (host or device)
@@ -73,43 +64,20 @@ int32_t cniic_ctx_create(int32_t device, void *stream, cniic_ctx **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return CNIIC_ERR_HIP;
     if (hipSetDevice(device) != hipSuccess) return CNIIC_ERR_HIP;
-    auto *c = new cniic_ctx();
+    std::unique_ptr<cniic_ctx> c(new cniic_ctx());   // (a failure below gives back what has been created: ~Ctx and its members)
     c->device = device;
-    if (stream) { c->stream = reinterpret_cast<hipStream_t>(stream); c->own_stream = false; }
+    if (stream) c->stream = reinterpret_cast<hipStream_t>(stream);
     else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return CNIIC_ERR_HIP; }
-        c->own_stream = true;
+        if (hipStreamCreateWithFlags(&c->own_stream.s, hipStreamNonBlocking) != hipSuccess) return CNIIC_ERR_HIP;
+        c->stream = c->own_stream.s;
     }
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) { delete c; return CNIIC_ERR_HIP; }
-    *out = c;
+    if (c->ev0.ensure(hipEventDefault) != hipSuccess || c->ev1.ensure(hipEventDefault) != hipSuccess) return CNIIC_ERR_HIP;
+    *out = c.release();
     return CNIIC_OK;
 }
 
 void cniic_ctx_destroy(cniic_ctx *c) {
-    if (!c) return;
-    for (void *w : c->batch_workers) cniic_ctx_destroy(static_cast<cniic_ctx *>(w));
-    c->batch_workers.clear();
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    c->dense.release();
-    c->batch_stage.release();
-    c->scan_xy.release();
-    c->scan_leaves.reset();   // (device tables of the scan of large rectangles)
-    c->pool.trim();
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (auto e : c->poll_ev) if (e) (void)hipEventDestroy(e);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->pinned_ps) (void)hipHostFree(c->pinned_ps);
-    if (c->pinned_res) (void)hipHostFree(c->pinned_res);
-    if (c->pinned_huf) (void)hipHostFree(c->pinned_huf);
-    if (c->res_ev) (void)hipEventDestroy(c->res_ev);
-    if (c->pinned_u) (void)hipHostFree(c->pinned_u);
-    if (c->u_ev) (void)hipEventDestroy(c->u_ev);
-    if (c->huf_ev) (void)hipEventDestroy(c->huf_ev);
-    if (c->surf_ev) (void)hipEventDestroy(c->surf_ev);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c) delete c;   // ~Ctx (common.hpp)
 }
 
 const char *cniic_last_error(const cniic_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -1237,30 +1205,42 @@ int32_t cniic_codec_encode_warm(cniic_ctx *c, const char *expr, const cniic_kmea
     return codec_encode_warm(c, d, in.d, w, h, opts, init, out, cap, len, centroids_out, stats);
 }
 
-// the first S worker contexts of a batch call (created on first use), with this context's route switches and its injected scan (a view
-// of this context's table)
-static int32_t batch_workers_ready(cniic_ctx *c, uint32_t S, const char *who) {
+// The worker contexts of a batch call of n > 0 frames: S = min(n, CNIIC_OPT_BATCH_STREAMS, 8 unless set) of them, created on first use,
+// with this context's route switches and its injected scan (a view of this context's table).  Returns S, or 0 when a worker could not be
+// created: the message is set and the call's status is CNIIC_ERR_HIP (all that creating a context on this context's device can answer).
+static uint32_t batch_workers_ready(cniic_ctx *c, uint32_t n, const char *who) {
+    const uint32_t S = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
     while (c->batch_workers.size() < S) {
         cniic_ctx *wk = nullptr;
         const int32_t rc = cniic_ctx_create(c->device, nullptr, &wk);
-        if (rc != CNIIC_OK) return c->fail(rc, "%s: cannot create worker context %zu", who, c->batch_workers.size());
-        c->batch_workers.push_back(wk);
+        if (rc != CNIIC_OK) { c->fail(rc, "%s: cannot create worker context %zu", who, c->batch_workers.size()); return 0; }
+        c->batch_workers.emplace_back(wk);
     }
     for (uint32_t i = 0; i < S; i++) {
-        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        cniic_ctx *wk = c->batch_workers[i].get();
         memcpy(wk->opt_val, c->opt_val, sizeof c->opt_val);
         wk->opt_set = c->opt_set;
         wk->scan_xy.release();
         wk->scan_w = wk->scan_h = 0;
         if (c->scan_xy.p) { wk->scan_xy.view(c->scan_xy.p, c->scan_xy.bytes); wk->scan_w = c->scan_w; wk->scan_h = c->scan_h; }
     }
-    return CNIIC_OK;
+    return S;
+}
+
+// What a batch call answers from its n frames' codes and messages: the first frame that failed decides the call's status and its
+// message; rcs_out (optional) takes every frame's code.
+static int32_t fold_status(Ctx *c, const int32_t *rcs_in, const std::string *msgs, uint32_t n, int32_t *rcs_out) {
+    if (rcs_out) std::copy(rcs_in, rcs_in + n, rcs_out);
+    const int32_t *bad = std::find_if(rcs_in, rcs_in + n, [](int32_t rc) { return rc != CNIIC_OK; });
+    if (bad == rcs_in + n) return CNIIC_OK;
+    c->err = msgs[bad - rcs_in];
+    return *bad;
 }
 
 // S workers encode side by side: what each gives up so that the others fit
 static void batch_workers_share(cniic_ctx *c, uint32_t S) {
     for (uint32_t i = 0; i < S; i++) {
-        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        cniic_ctx *wk = c->batch_workers[i].get();
         // several images in flight: half-size K-means grids, so that two images' launches are resident together (measured on 64 frames
         // 1920 x 1080 with 8 workers: 768 blocks 0.885 ms per frame, 384: 0.729, 192: 0.80, 96: 1.17)
         if (S > 1 && !((c->opt_set >> CNIIC_OPT_KM_MAX_BLOCKS) & 1u) && !getenv("CNIIC_KM_MAX_BLOCKS")) { wk->opt_val[CNIIC_OPT_KM_MAX_BLOCKS] = 384; wk->opt_set |= 1u << CNIIC_OPT_KM_MAX_BLOCKS; }
@@ -1277,29 +1257,20 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
     if (!frames) return CNIIC_OK;
     if (!rgb || !out || !lens) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_batch: null argument");
     const uint64_t img_bytes = (uint64_t)w * h * 3;
-    const uint32_t S = (uint32_t)std::min<uint64_t>(frames, std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
-    CNIIC_TRY(batch_workers_ready(c, S, "codec_encode_batch"));
+    const uint32_t S = batch_workers_ready(c, frames, "codec_encode_batch");
+    if (!S) return CNIIC_ERR_HIP;
     batch_workers_share(c, S);
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
     std::vector<int32_t> status(frames, CNIIC_OK);
+    std::vector<std::string> msg(frames);
     parallel_for(frames, S, [&](uint32_t f, uint32_t i) {
-        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        cniic_ctx *wk = c->batch_workers[i].get();
         cniic_kmeans_stats st{};
         status[f] = cniic_codec_encode_opts(wk, expr, opts, rgb + (uint64_t)f * img_bytes, w, h, out + (uint64_t)f * stride, stride, &lens[f], &st);
+        if (status[f] != CNIIC_OK) msg[f] = wk->err;   // (the worker's next frame clears it)
         if (stats) stats[f] = st;
     });
-    int32_t first = CNIIC_OK;
-    for (uint32_t f = 0; f < frames; f++) {
-        if (rcs) rcs[f] = status[f];
-        if (status[f] != CNIIC_OK && first == CNIIC_OK) first = status[f];
-    }
-    if (first != CNIIC_OK) {
-        for (uint32_t i = 0; i < S; i++) {
-            cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
-            if (!wk->err.empty()) { c->err = wk->err; break; }
-        }
-    }
-    return first;
+    return fold_status(c, status.data(), msg.data(), frames, rcs);
 }
 
 // ---- images of different sizes (cniic_codec_encode_batch_var, cniic_codec_measure_batch)
@@ -1326,11 +1297,8 @@ static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kme
     const bool stage = src_dev && npx && (reinterpret_cast<uintptr_t>(src) & 15);
     if (stage) {
         if (wk->batch_stage.bytes < npx * 3) {   // (the largest frames come first: grown once or twice in a batch)
-            DevPool *saved = current_pool();
-            current_pool() = nullptr;            // lives as long as the worker
-            const hipError_t e = wk->batch_stage.alloc(npx * 3);
-            current_pool() = saved;
-            CNIIC_HIP_TRY(wk, e);
+            PoolScope keep(nullptr);             // lives as long as the worker
+            CNIIC_HIP_TRY(wk, wk->batch_stage.alloc(npx * 3));
         }
         CNIIC_HIP_TRY(wk, hipMemcpyAsync(wk->batch_stage.p, src, npx * 3, hipMemcpyDeviceToDevice, wk->stream));
         src = wk->batch_stage.as<uint8_t>();
@@ -1348,8 +1316,8 @@ static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kme
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
     const uint32_t n = (uint32_t)fr.size();
     if (!n) return CNIIC_OK;
-    const uint32_t S = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
-    CNIIC_TRY(batch_workers_ready(c, S, who));
+    const uint32_t S = batch_workers_ready(c, n, who);
+    if (!S) return CNIIC_ERR_HIP;
     batch_workers_share(c, S);
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; i++) order[i] = i;
@@ -1361,14 +1329,14 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
     });
     std::vector<uint8_t> saved_timers(S);
     for (uint32_t i = 0; i < S; i++) {
-        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        cniic_ctx *wk = c->batch_workers[i].get();
         saved_timers[i] = wk->timers;
         wk->timers = wk->timers || c->timers;
     }
     std::mutex kt_mu;
     std::map<std::string, KernelTime> kt;
     parallel_for(n, S, [&](uint32_t j, uint32_t i) {
-        cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+        cniic_ctx *wk = c->batch_workers[i].get();
         VarFrame &f = fr[order[j]];
         f.rc = encode_var_frame(wk, expr, opts, src_dev, f);
         if (f.rc != CNIIC_OK) f.msg = wk->err;
@@ -1377,7 +1345,7 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
             for (const auto &e : wk->ktimes) { kt[e.first].ms += e.second.ms; kt[e.first].launches += e.second.launches; }
         }
     });
-    for (uint32_t i = 0; i < S; i++) static_cast<cniic_ctx *>(c->batch_workers[i])->timers = saved_timers[i] != 0;
+    for (uint32_t i = 0; i < S; i++) c->batch_workers[i]->timers = saved_timers[i] != 0;
     if (c->timers) c->ktimes.swap(kt);
     return CNIIC_OK;
 }
@@ -1398,14 +1366,15 @@ int32_t cniic_codec_encode_batch_var(cniic_ctx *c, const char *expr, const cniic
         fr[f].out = out + (uint64_t)f * stride; fr[f].cap = stride;
     }
     CNIIC_TRY(encode_frames(c, expr, opts, fr, is_device_ptr(rgb), "codec_encode_batch_var"));
-    int32_t first = CNIIC_OK;
+    std::vector<int32_t> status(frames);
+    std::vector<std::string> msg(frames);
     for (uint32_t f = 0; f < frames; f++) {
         lens[f] = fr[f].len;
-        if (rcs) rcs[f] = fr[f].rc;
         if (stats) stats[f] = fr[f].st;
-        if (fr[f].rc != CNIIC_OK && first == CNIIC_OK) { first = fr[f].rc; c->err = fr[f].msg; }
+        status[f] = fr[f].rc;
+        msg[f].swap(fr[f].msg);
     }
-    return first;
+    return fold_status(c, status.data(), msg.data(), frames, rcs);
 }
 
 int32_t cniic_codec_decode(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w,
@@ -1441,20 +1410,16 @@ static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t
     std::vector<uint32_t> rest;
     for (uint32_t f = 0; f < frames; f++) if (!taken[f]) rest.push_back(f);
     if (!rest.empty()) {
-        const uint32_t S = (uint32_t)std::min<uint64_t>(rest.size(), std::max<uint64_t>(1, c->opt(CNIIC_OPT_BATCH_STREAMS, nullptr, 8)));
-        CNIIC_TRY(batch_workers_ready(c, S, "codec_decode_batch"));
+        const uint32_t S = batch_workers_ready(c, (uint32_t)rest.size(), "codec_decode_batch");
+        if (!S) return CNIIC_ERR_HIP;
         parallel_for((uint32_t)rest.size(), S, [&](uint32_t j, uint32_t i) {
-            cniic_ctx *wk = static_cast<cniic_ctx *>(c->batch_workers[i]);
+            cniic_ctx *wk = c->batch_workers[i].get();
             const uint32_t f = rest[j];
             status[f] = cniic_codec_decode(wk, expr, bytes + (uint64_t)f * stride, lens[f], rgb + (uint64_t)f * img_stride, img_stride, &w[f], &h[f]);
             if (status[f] != CNIIC_OK) msg[f] = wk->err;
         });
     }
-    int32_t first = CNIIC_OK;
-    for (uint32_t f = 0; f < frames; f++) {
-        if (rcs) rcs[f] = status[f];
-        if (status[f] != CNIIC_OK && first == CNIIC_OK) { first = status[f]; c->err = msg[f]; }
-    }
+    const int32_t first = fold_status(c, status.data(), msg.data(), frames, rcs);
     if (msgs_out) msgs_out->swap(msg);
     return first;
 }
@@ -1751,9 +1716,9 @@ int32_t cniic_codec_measure_batch(cniic_ctx *c, const char *expr, const cniic_km
         CNIIC_TRY(job.chunk(part, room, nullptr));
         i += n;
     }
-    for (uint32_t f = 0; f < frames; f++)
-        if (rows[f].rc != CNIIC_OK) { c->err = job.msg[f]; return rows[f].rc; }
-    return CNIIC_OK;
+    std::vector<int32_t> status(frames);
+    for (uint32_t f = 0; f < frames; f++) status[f] = rows[f].rc;
+    return fold_status(c, status.data(), job.msg.data(), frames, nullptr);
 }
 
 int32_t cniic_synth_image(cniic_ctx *c, int32_t kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *rgb) {

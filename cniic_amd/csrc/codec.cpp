@@ -239,8 +239,9 @@ struct HuffCodeStage {
         // each of the U - 1 branches u32].  Small: [counts u64 | code u64 | len u8]; the keys and the decoder in ordinary memory (the
         // host reads the keys at random and writes the decoder byte by byte: 0.20 ms in pinned memory, 0.12 there).
         gpu_codes = U >= c->opt(CNIIC_OPT_HUF_GPU_CODES_MIN, "CNIIC_HUF_GPU_CODES_MIN", 32768) && U >= 2 && U < (1ull << 30) && n < (1ull << 32);
-        CNIIC_HIP_TRY(c, ctx_pinned_huf(c, gpu_codes ? U * 8 + 3 * (U - 1) * 4 + 64 : U * 8 + U * 8 + U));
-        counts_h = static_cast<uint64_t *>(c->pinned_huf);
+        const uint64_t need = gpu_codes ? U * 8 + 3 * (U - 1) * 4 + 64 : U * 8 + U * 8 + U;
+        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(need, pinned_huf_want(need)));
+        counts_h = c->pinned_huf.as<uint64_t>();
         left_h = reinterpret_cast<uint32_t *>(counts_h + U);
         right_h = left_h + (U - 1);
         nleaves_h = right_h + (U - 1);
@@ -283,8 +284,8 @@ struct HuffCodeStage {
         const uint32_t *left_d = tree_d.as<uint32_t>(), *right_d = left_d + (U - 1), *nleaves_d = right_d + (U - 1);
         CNIIC_TRY(huff_tree_codes(c, left_d, right_d, nleaves_d, counts_d.as<uint64_t>(), (uint32_t)U, root, sym_kind, len_d.as<uint8_t>(),
                                   code_d.as<uint64_t>(), off_d.as<uint64_t>(), totals_d));
-        CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuHufTotals.at, totals_d, 16, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuHufTotals.at, totals_d, 16, hipMemcpyDeviceToHost, c->stream));
         totals_pending = true;
         return CNIIC_OK;
     }
@@ -292,8 +293,8 @@ struct HuffCodeStage {
     int bits(uint64_t *payload_bits) {
         if (totals_pending) {
             totals_pending = false;
-            if (c->pinned_u[kPuHufTotals.at + 1]) return cannot_build();
-            nbits = c->pinned_u[kPuHufTotals.at];
+            if (c->pinned_u.as<uint64_t>()[kPuHufTotals.at + 1]) return cannot_build();
+            nbits = c->pinned_u.as<uint64_t>()[kPuHufTotals.at];
             host_trace().mark("huf: codes (GPU)");
         }
         *payload_bits = nbits;
@@ -350,7 +351,7 @@ int huf_encode_all_dev(Ctx *c, int sym_kind, const uint8_t *rgb_d, uint32_t *sym
     HuffCodeStage st(c, sym_kind);
     CNIIC_TRY(st.begin(table_d, &plan, n));
     const uint64_t U = st.U;
-    if (!c->huf_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->huf_ev, hipEventDisableTiming));
+    CNIIC_HIP_TRY(c, c->huf_ev.ensure(hipEventDisableTiming));
     CNIIC_HIP_TRY(c, hipEventRecord(c->huf_ev, c->stream));
     // `delta` symbols on a buffer of ours: nothing to do while the host builds the tree -- the pack looks (length, code) up
     // in an LDS table of the cube of small differences (huff_pack_code32_hot).  Otherwise the GPU meanwhile turns every
@@ -507,8 +508,8 @@ int cc_image_create(CcSession *s, const uint32_t *occ_d, uint32_t K, const cniic
     // The reference's point list is the colours of ALL images: the summed occupancy as a bitmap + prefix.  Its length (and
     // this image's own colour count) stay on the device while the state is set up -- sized for the most there can be, the
     // set-up kernels read the counts where they are -- and the host fetches both once everything is enqueued.
-    CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    uint64_t *Ug_h = c->pinned_u + kPuPointCount.at;
+    CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+    uint64_t *Ug_h = c->pinned_u.as<uint64_t>() + kPuPointCount.at;
     CNIIC_TRY(gidx_build(c, occ_d, s->gbits, s->gprefix, Ug_h, &s->gtotal));
     const uint64_t Umax = std::min<uint64_t>(s->sp.npx, 1ull << 24);
     const uint64_t *Ug_dev = s->gtotal.as<uint64_t>();
@@ -520,10 +521,10 @@ int cc_image_create(CcSession *s, const uint32_t *occ_d, uint32_t K, const cniic
                       s->gprefix.as<uint32_t>(), 0, Ug_dev));
     // this image's own colour count, fetched again here: the word sp_build copied it to (kPuSpCount) may have been
     // rewritten since by another session of the same context (a second cniic_cc_image_begin, a plain encode)
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuImageCount.at, s->sp.total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuImageCount.at, s->sp.total.p, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the all-reduced occupancy had to arrive anyway)
     const uint64_t Ug = *Ug_h;
-    s->sp.U = c->pinned_u[kPuImageCount.at];
+    s->sp.U = c->pinned_u.as<uint64_t>()[kPuImageCount.at];
     s->U = s->sp.U;
     if (Ug / K == 0 || s->U == 0)
         return c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu distinct colours for %u clusters (src/kmeans.rs:68)", (unsigned long long)Ug, K);
@@ -594,12 +595,12 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
         if (s->local_points && K <= kPuPaletteWeights.words) {
             // shared palette: THIS image's pixels per cluster (below) -- asked for first, so that the answer travels while
             // the pixel labels are computed instead of stalling the stream after them
-            CNIIC_HIP_TRY(c, ctx_pinned_u(c));
+            CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
             CNIIC_HIP_TRY(c, lw.alloc((uint64_t)K * 8));
             CNIIC_HIP_TRY(c, hipMemsetAsync(lw.p, 0, (uint64_t)K * 8, c->stream));
             CNIIC_TRY(local_cluster_weights(c, ckeys, km_rgbw_labels_internal(km, nullptr), wide, U, nullptr, K, lw.as<uint64_t>(), cweight));
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuPaletteWeights.at, lw.p, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
-            if (!c->u_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->u_ev, hipEventDisableTiming));
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuPaletteWeights.at, lw.p, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+            CNIIC_HIP_TRY(c, c->u_ev.ensure(hipEventDisableTiming));
             CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
             lw_early = true;
         }
@@ -623,7 +624,7 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     // wsum: the pixels per cluster of the image Hufman.encode sees (clusterc.rs:52).  One image: the member weights' sums, as they came.
     if (lw_early) {
         CNIIC_HIP_TRY(c, hipEventSynchronize(c->u_ev));
-        for (uint32_t k = 0; k < K; k++) wsum[k] = c->pinned_u[kPuPaletteWeights.at + k];
+        for (uint32_t k = 0; k < K; k++) wsum[k] = c->pinned_u.as<uint64_t>()[kPuPaletteWeights.at + k];
     } else if (local_counts_d || s->local_points) {
         // shared palette over several images: THIS image's pixels per cluster, from its own colour counts
         CNIIC_HIP_TRY(c, lw.alloc((uint64_t)K * 8));
@@ -1159,8 +1160,8 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
     uint64_t *const packed_d = small.as<uint64_t>() + 2;
     CNIIC_TRY(delta_gather_hist(c, rgb_d, w, h, hot16.as<uint16_t>(), table, pages, coldkeys.as<uint32_t>(), chunk_cold.as<uint8_t>(),
                                 small.as<uint32_t>()));
-    CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuDeltaOverflow.at, small.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuDeltaOverflow.at, small.p, 8, hipMemcpyDeviceToHost, c->stream));
     host_trace().mark("delta: gather + hist enqueued");
     // (stage timers, bench.py --config c5: everything between the histogram and the pack -- compaction, the leaves' sort, the host's merge with
     // the GPU idle, the codes -- as ONE stage, so that the stages account for the whole call)
@@ -1168,7 +1169,7 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
     CompactPlan plan;
     CNIIC_TRY(hist_compact_count(c, table, 27, &plan, nullptr, pages));  // (waits for the stream)
     host_trace().mark("delta: ... + count of the distinct (wait)");
-    const bool overflow = c->pinned_u[kPuDeltaOverflow.at] != 0;
+    const bool overflow = c->pinned_u.as<uint64_t>()[kPuDeltaOverflow.at] != 0;
     if (host_trace().on) fprintf(stderr, "[host] delta: %llu symbols, %llu distinct%s\n", (unsigned long long)n, (unsigned long long)plan.n_unique,
                                  overflow ? " (a chunk with more than 64 symbols outside the cube: the 32-bit route)" : "");
     if (plan.n_unique >= (1ull << 26) || overflow) {
@@ -1190,7 +1191,7 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
     if (st.totals_pending) {
         // (round 4) the payload's size is on its way to the host: the first half of the pack, which wants the codes and nothing else, is
         // enqueued behind it, and the host waits for the size while the GPU counts
-        if (!c->res_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->res_ev, hipEventDisableTiming));
+        CNIIC_HIP_TRY(c, c->res_ev.ensure(hipEventDisableTiming));
         CNIIC_HIP_TRY(c, hipEventRecord(c->res_ev, c->stream));
         if (!c->timers) {   // (with the stage timers on the whole pack is timed as one stage below)
             CNIIC_HIP_TRY(c, hipMemsetAsync(packed_d, 0, 8, c->stream));
@@ -1216,7 +1217,7 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
         timer.stop(1);
     }
     ScopedKernelTimer timer_fin(c, "delta_finish");   // (the table's sweep, the header, the decoder, the last wait)
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuDeltaPacked.at, packed_d, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuDeltaPacked.at, packed_d, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_TRY(delta_table_clean(c));
     host_trace().mark("delta: pack enqueued");
     // the decoder goes in AFTER the pack, whose first word comes out with zeros where the decoder's last bytes are
@@ -1229,7 +1230,7 @@ static int encode_delta(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, ui
     host_trace().mark("delta: pack + finish");
     host_trace().dump();
     if (rc_fin != CNIIC_OK) return rc_fin;
-    const uint64_t packed_bits = c->pinned_u[kPuDeltaPacked.at];
+    const uint64_t packed_bits = c->pinned_u.as<uint64_t>()[kPuDeltaPacked.at];
     if (packed_bits != nbits)
         return c->fail(CNIIC_ERR_HIP, "huffman: packed %llu bits, histogram predicts %llu", (unsigned long long)packed_bits, (unsigned long long)nbits);
     return CNIIC_OK;
@@ -1323,10 +1324,10 @@ static int stream_head(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t nb
     // there has hundreds of thousands of leaves and is parsed faster on the GPU than by this core)
     if (!bytes_dev) { h->p = bytes; h->n = std::max(h->n, want); return CNIIC_OK; }
     if (h->n >= want) return CNIIC_OK;
-    CNIIC_HIP_TRY(c, ctx_pinned_huf(c, want));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_huf, bytes, want, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, c->pinned_huf.reserve(want, pinned_huf_want(want)));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_huf.p, bytes, want, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    h->p = static_cast<const uint8_t *>(c->pinned_huf);
+    h->p = c->pinned_huf.as<const uint8_t>();
     h->n = want;
     return CNIIC_OK;
 }
@@ -1651,8 +1652,8 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     std::vector<const uint8_t *> head_p(F);
     std::vector<uint64_t> head_n(F);
     auto fetch = [&](uint64_t W, uint32_t f0, uint32_t f1) -> int {   // the first W bytes of frames [f0, f1] into the pinned block, row f at (f - f0) W
-        CNIIC_HIP_TRY(c, ctx_pinned_huf(c, W * (f1 - f0 + 1)));
-        uint8_t *ph = static_cast<uint8_t *>(c->pinned_huf);
+        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(W * (f1 - f0 + 1), pinned_huf_want(W * (f1 - f0 + 1))));
+        uint8_t *ph = c->pinned_huf.as<uint8_t>();
         const uint32_t last = F >= 2 ? std::min(f1, F - 2) : 0;   // (the batch's last frame may end before W bytes: a copy of its own)
         if (F >= 2 && f0 <= last)
             CNIIC_HIP_TRY(c, hipMemcpy2DAsync(ph, W, bytes + (uint64_t)f0 * stride, stride, W, last - f0 + 1, hipMemcpyDeviceToHost, c->stream));

@@ -36,6 +36,10 @@ struct DevPool {
     struct Block { void *p; uint64_t cap; };
     std::vector<Block> free_blocks;
     uint64_t cached_bytes = 0;
+    DevPool() = default;
+    DevPool(const DevPool &) = delete;
+    DevPool &operator=(const DevPool &) = delete;
+    ~DevPool() { trim(); }   // (every DevBuf that took a block from this pool has given it back: Ctx's member order)
     hipError_t get(uint64_t bytes, void **p, uint64_t *cap) {
         // best fit among cached blocks that are not more than 2x too large
         size_t best = SIZE_MAX;
@@ -76,6 +80,16 @@ inline DevPool *&current_pool() {
     return p;
 }
 
+// DevBufs allocated while this lives come from pool p (an ABI call: its context's pool) -- or, PoolScope keep(nullptr), straight from
+// hipMalloc: buffers that live as long as the context and are not recycled
+struct PoolScope {
+    DevPool *prev;
+    explicit PoolScope(DevPool *p) : prev(current_pool()) { current_pool() = p; }
+    PoolScope(const PoolScope &) = delete;
+    PoolScope &operator=(const PoolScope &) = delete;
+    ~PoolScope() { current_pool() = prev; }
+};
+
 // RAII device allocation on the context's device (recycled through the context's pool).
 struct DevBuf {
     void    *p = nullptr;
@@ -111,6 +125,46 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// A block of pinned host memory that a context owns.
+struct PinnedBuf {
+    void    *p = nullptr;
+    uint64_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    // at least `need` bytes: a block that is too small is freed and one of `want` (>= need) bytes takes its place, contents lost
+    hipError_t reserve(uint64_t need, uint64_t want) {
+        if (bytes >= need) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; bytes = 0;
+        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) bytes = want; else p = nullptr;
+        return e;
+    }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+// An event that a context owns, created at its first use.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t ensure(unsigned flags) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// The stream a context made for itself (none when the host gave it one).
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream &) = delete;
+    OwnedStream &operator=(const OwnedStream &) = delete;
+    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+};
+
 // Knobs of the test-suite and the probes under tools/ (CNIIC_TEST_* hooks, route forcing, the persistent launch's timeout) are
 // read from the environment ONLY by the testing build (-DCNIIC_TESTING: libcniic_hip_testing.so, which tests/conftest.py and tools/ ask
 // for with CNIIC_USE_TESTING_LIB=1).  In the release library test_env() is a constant nullptr: no getenv, and the names are not even in
@@ -122,14 +176,17 @@ inline const char *test_env(const char *name) { return getenv(name); }
 inline const char *test_env(const char *) { return nullptr; }
 #endif
 
+// Every resource below is owned by its member's type and released by that type's destructor, in reverse order of declaration: the order
+// of the members IS the order of the teardown.  What it must keep: the workers go first (they hold views of scan_xy), every DevBuf that
+// may hold a block of `pool` goes before `pool` (whose destructor frees what it caches), the stream the context made goes last.
 struct Ctx {
     int         device = 0;
-    hipStream_t stream = nullptr;
-    bool        own_stream = false;
+    OwnedStream own_stream;        // declared before everything that may have work on it
+    hipStream_t stream = nullptr;  // the stream the calls run on: own_stream.s, or the host's
     std::mutex  mu;
     std::string err;
     std::map<std::string, KernelTime> ktimes;  // per-call dominant-kernel timings (HIP events)
-    hipEvent_t  ev0 = nullptr, ev1 = nullptr;
+    Event   ev0, ev1;       // the stage timers' pair (default flags: they read elapsed time), created with the context
     bool    timers = getenv("CNIIC_KERNEL_TIMERS") != nullptr;  // per-stage HIP-event timers (they synchronise)
     // cniic_ctx_set_opt: values a host set for this context (bit i of opt_set); unset options read their environment variable per call
     uint64_t opt_val[CNIIC_OPT_COUNT] = {};
@@ -145,29 +202,29 @@ struct Ctx {
     DevBuf dense27, dense27_pages;  // `delta`: u32[2^27] SignedColor counts + a flag per 4096-entry page, all zero between calls (k_delta.hip)
     bool   dense27_clean = false;
     DevBuf hilbert_lut;     // state-machine tables of the 2^n Hilbert scan (k_hilbert.hip)
-    void  *pinned = nullptr; // 4 KiB of pinned host memory: two KmDevState slots for lagged convergence polling
-    void  *pinned_ps = nullptr;  // pinned: how the persistent K-means launch ended (PsExit, k_kmeans_persist.hip)
+    PinnedBuf pinned;       // 4 KiB of pinned host memory: two KmDevState slots for lagged convergence polling
+    PinnedBuf pinned_ps;    // 1 KiB: how the persistent K-means launch ended (PsExit, k_kmeans_persist.hip)
     uint32_t ps_div = 1;         // the persistent K-means launch takes 1 / ps_div of the CUs (worker contexts of a batch encode)
     uint32_t ps_backoff = 0, ps_backoff_left = 0;   // after a persistent launch whose grid was not resident together in time (somebody else's kernels on the CUs: a 2 s
                                                     // wait before the launches take over) the next 4, 8, ... 256 K-means runs of this context do not try one
-    hipEvent_t poll_ev[2] = {nullptr, nullptr};
-    void  *pinned_res = nullptr;  // pinned landing area of K-means result blocks (grown on demand)
-    uint64_t pinned_res_bytes = 0;
-    hipEvent_t res_ev = nullptr;
-    uint64_t *pinned_u = nullptr;  // 64 KiB of pinned host memory for small answers from the GPU: who owns which words is the PuSlot table below
-    hipEvent_t u_ev = nullptr;     // behind a copy into pinned_u that the host waits for later (kPuSpCount, kPuPaletteWeights)
+    Event poll_ev[2];
+    PinnedBuf pinned_res;   // pinned landing area of K-means result blocks (grown on demand)
+    Event res_ev;
+    PinnedBuf pinned_u;     // 64 KiB of pinned host memory (u64 words) for small answers from the GPU: who owns which words is the PuSlot table below
+    Event u_ev;             // behind a copy into pinned_u that the host waits for later (kPuSpCount, kPuPaletteWeights)
     std::shared_ptr<void> trie_scratch; // the decoder's parsed leaf table (LeafTable, codec.cpp), kept between calls: 90 MB of fresh pages cost 25 ms
     std::shared_ptr<void> huf_scratch;  // host arrays of the Huffman tree build, kept between calls (HuffScratch, codec.cpp)
-    void  *pinned_huf = nullptr;  // pinned host memory, grown on demand: the Huffman code stage's counts, tree and codes (HuffCodeStage, codec.cpp); a decode's stream heads
-    uint64_t pinned_huf_bytes = 0;
-    hipEvent_t huf_ev = nullptr;   // behind the D2H copies of the compacted histogram (huf_encode_all_dev)
-    hipEvent_t surf_ev = nullptr;  // behind the upload of a surface call's frame and chunk tables: the call returns while its kernel runs, not before that copy has read the host's vectors (k_surface.hip)
+    PinnedBuf pinned_huf;   // pinned host memory, grown on demand (pinned_huf_want): the Huffman code stage's counts, tree and codes (HuffCodeStage, codec.cpp); a decode's stream heads
+    Event huf_ev;           // behind the D2H copies of the compacted histogram (huf_encode_all_dev)
+    Event surf_ev;          // behind the upload of a surface call's frame and chunk tables: the call returns while its kernel runs, not before that copy has read the host's vectors (k_surface.hip)
     std::shared_ptr<void> scan_leaves;  // the built-in scan of large rectangles: per image size, the recursion's leaves and class tables (k_hilbert.hip)
     DevBuf scan_xy;         // cniic_ctx_set_scan: an injected scan of scan_w x scan_h images, (x, y) per position (uint2[w h])
     uint32_t scan_w = 0, scan_h = 0;
-    std::vector<void *> batch_workers;  // cniic_codec_encode_batch: worker contexts (cniic_ctx *), created on first use
     DevBuf batch_stage;     // a worker of cniic_codec_encode_batch_var: the 16-byte aligned copy of a frame that lies at another address
     const void *poll_owner = nullptr;  // the K-means state whose lagged polls own `pinned` / poll_ev (one loop at a time per context)
+    std::vector<std::unique_ptr<cniic_ctx>> batch_workers;  // the batch calls' worker contexts, created on first use; the last member: destroyed first
+
+    ~Ctx();   // (below cniic_ctx)
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -179,6 +236,16 @@ struct Ctx {
         return code;
     }
 };
+
+}  // namespace cniic
+struct cniic_ctx : cniic::Ctx {};   // the ABI's handle
+namespace cniic {
+
+// waits for the context's work; the members' destructors release everything after it
+inline Ctx::~Ctx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+}
 
 #define CNIIC_HIP_TRY(ctx, expr)                                                          \
     do {                                                                                  \
@@ -196,20 +263,12 @@ inline hipError_t ctx_spin_sync(Ctx *c) {
     return e;
 }
 
-inline hipError_t ctx_pinned_huf(Ctx *c, uint64_t bytes) {  // at least `bytes` of pinned memory at c->pinned_huf (contents lost when it grows)
-    if (c->pinned_huf_bytes >= bytes) return hipSuccess;
-    if (c->pinned_huf) (void)hipHostFree(c->pinned_huf);
-    c->pinned_huf = nullptr; c->pinned_huf_bytes = 0;
-    const uint64_t want = bytes + bytes / 4 + 65536;
-    const hipError_t e = hipHostMalloc(&c->pinned_huf, want, hipHostMallocDefault);
-    if (e == hipSuccess) c->pinned_huf_bytes = want;
-    return e;
-}
+constexpr uint64_t pinned_huf_want(uint64_t bytes) { return bytes + bytes / 4 + 65536; }   // what Ctx::pinned_huf grows to when `bytes` are asked of it
 
 // Ctx::pinned_u in u64 words.  Every user has words of its own: a copy into one may still be on its way for one session of a context
 // (cc_image_begin ... cc_finish) when another call on that context starts, so no two meanings share a word.
 struct PuSlot { uint32_t at, words; };
-constexpr uint32_t kPinnedUWords = 64 * 1024 / 8;
+constexpr uint32_t kPinnedUWords = 64 * 1024 / 8, kPinnedUBytes = kPinnedUWords * 8;
 constexpr PuSlot kPuSpCount{0, 1};            // sp_build: distinct colours of the image (k_points.hip)
 constexpr PuSlot kPuPointCount{1, 1};         // cc_image_create: length of the point list, the colours of all images
 constexpr PuSlot kPuImageCount{2, 1};         // cc_image_create: this image's own distinct colours, fetched again
@@ -232,11 +291,6 @@ constexpr bool pu_slots_disjoint() {
 }
 static_assert(pu_slots_disjoint(), "Ctx::pinned_u: two slots overlap, or the last one ends behind the 64 KiB block");
 static_assert(kPuPaletteWeights.words >= 4096, "Ctx::pinned_u: the shared-palette weights need room for K = 4096");
-
-inline hipError_t ctx_pinned_u(Ctx *c) {
-    if (c->pinned_u) return hipSuccess;
-    return hipHostMalloc(reinterpret_cast<void **>(&c->pinned_u), kPinnedUWords * 8, hipHostMallocDefault);
-}
 
 #define CNIIC_TRY(expr)              \
     do {                             \
@@ -358,7 +412,7 @@ struct LaggedPoll {
     static constexpr size_t ring_offset() { return (3 * sizeof(KmDevState) + 63) & ~size_t(63); }
     int ring_slot(PollRec **dev_ptr) {
         static_assert(ring_offset() + kPollRing * sizeof(PollRec) <= 4096, "the poll ring must fit the pinned page");
-        PollRec *r = reinterpret_cast<PollRec *>(static_cast<uint8_t *>(c->pinned) + ring_offset());
+        PollRec *r = reinterpret_cast<PollRec *>(c->pinned.as<uint8_t>() + ring_offset());
         memset(r, 0xff, kPollRing * sizeof(PollRec));  // no slot carries a valid launch number yet
         void *d = nullptr;
         CNIIC_HIP_TRY(c, hipHostGetDevicePointer(&d, r, 0));
@@ -368,7 +422,7 @@ struct LaggedPoll {
     }
     // device address of the slot the kernels write in mapped mode (zeroed here)
     int mapped_slot(KmDevState **dev_ptr) {
-        KmDevState *slots = static_cast<KmDevState *>(c->pinned);
+        KmDevState *slots = c->pinned.as<KmDevState>();
         memset(&slots[2], 0, sizeof(KmDevState));
         void *d = nullptr;
         CNIIC_HIP_TRY(c, hipHostGetDevicePointer(&d, &slots[2], 0));
@@ -385,15 +439,14 @@ struct LaggedPoll {
                                               "destroy it, or give the second session its own context)");
         c->poll_owner = dstate;
         owner = true;
-        if (!c->pinned) CNIIC_HIP_TRY(c, hipHostMalloc(&c->pinned, 4096, hipHostMallocDefault));
-        for (int i = 0; i < 2; i++)
-            if (!c->poll_ev[i]) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->poll_ev[i], hipEventDisableTiming));
+        CNIIC_HIP_TRY(c, c->pinned.reserve(4096, 4096));
+        for (Event &e : c->poll_ev) CNIIC_HIP_TRY(c, e.ensure(hipEventDisableTiming));
         return CNIIC_OK;
     }
     // call after enqueuing a batch; returns the state as of the batch BEFORE it in *h (valid when *have).
     // last_launch: number of the batch's last launch (ring mode)
     int after_batch(KmDevState *h, bool *have, uint32_t last_launch = 0) {
-        KmDevState *slots = static_cast<KmDevState *>(c->pinned);
+        KmDevState *slots = c->pinned.as<KmDevState>();
         if (!mapped && !ring) CNIIC_HIP_TRY(c, hipMemcpyAsync(&slots[slot], dstate, sizeof(KmDevState), hipMemcpyDeviceToHost, c->stream));
         CNIIC_HIP_TRY(c, hipEventRecord(c->poll_ev[slot], c->stream));
         *have = pending > 0;
@@ -418,7 +471,7 @@ struct LaggedPoll {
             }
             CNIIC_HIP_TRY(c, hipEventSynchronize(c->poll_ev[slot ^ 1]));
             if (ring) {  // the record the previous batch's last launch wrote: complete before its event, untouched for kPollRing launches
-                const volatile PollRec *r = reinterpret_cast<const volatile PollRec *>(static_cast<uint8_t *>(c->pinned) + ring_offset()) + last_prev % kPollRing;
+                const volatile PollRec *r = reinterpret_cast<const volatile PollRec *>(c->pinned.as<uint8_t>() + ring_offset()) + last_prev % kPollRing;
                 if (r->seq != last_prev) return c->fail(CNIIC_ERR_HIP, "kmeans: launch %u left no state record (found %u)", last_prev, r->seq);
                 KmDevState t{};
                 t.done = r->done; t.iter = r->iter; t.moved_last = r->moved_last; t.reseeds = r->reseeds; t.active = r->active; t.pair_evals = r->pair_evals;
@@ -441,7 +494,7 @@ struct LaggedPoll {
     }
     // state after everything enqueued so far
     int drain(KmDevState *h) {
-        KmDevState *slots = static_cast<KmDevState *>(c->pinned);
+        KmDevState *slots = c->pinned.as<KmDevState>();
         CNIIC_HIP_TRY(c, hipEventSynchronize(c->poll_ev[slot ^ 1]));
         *h = slots[slot ^ 1];
         return CNIIC_OK;

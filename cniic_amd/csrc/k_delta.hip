@@ -553,11 +553,9 @@ __global__ __launch_bounds__(256) void k_delta_edges(const uint2 *__restrict__ e
 int delta_table(Ctx *c, uint32_t **table_d, uint8_t **pages_d) {
     const uint64_t bytes = (1ull << 27) * 4, npages = (1ull << 27) >> kPageShift;
     if (!c->dense27.p) {
-        DevPool *saved = current_pool();
-        current_pool() = nullptr;  // live as long as the context
+        PoolScope keep(nullptr);  // live as long as the context
         hipError_t e = c->dense27.alloc(bytes);
         if (e == hipSuccess) e = c->dense27_pages.alloc(npages);
-        current_pool() = saved;
         if (e != hipSuccess) { c->dense27.release(); c->dense27_pages.release(); return c->fail(CNIIC_ERR_HIP, "delta: hipMalloc of the symbol table failed"); }
         c->dense27_clean = false;
     }

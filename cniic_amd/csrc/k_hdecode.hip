@@ -790,8 +790,8 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     CNIIC_HIP_TRY(c, tot.alloc(8));
     CNIIC_HIP_TRY(c, changed.alloc(32));   // [0] an end moved in this check; [5] pass 0's blocks that gave the stream up
     CNIIC_HIP_TRY(c, hipMemsetAsync(changed.p, 0, 32, c->stream));
-    CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + kPuHdecode.at;   // [0] total symbols, [1] did the last pass move an end?, [2] pass 0's blocks that gave the stream up
+    CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+    volatile uint64_t *pin = c->pinned_u.as<volatile uint64_t>() + kPuHdecode.at;   // [0] total symbols, [1] did the last pass move an end?, [2] pass 0's blocks that gave the stream up
     const uint32_t grid = (uint32_t)ceil_div(nsub, kHdThreads);
     const size_t lds = use1 ? kHdLds : (size_t)kHdStageAlloc * 4;
     const bool wide = lt.max_len > 32;
@@ -925,12 +925,12 @@ int huff_decode_dev(Ctx *c, const LeafTable &lt, const uint8_t *payload, bool pa
     const uint64_t off_key = n * 8, off_len = off_key + n * 4, tab_bytes = off_len + n;
     DevBuf tab_d;
     CNIIC_HIP_TRY(c, tab_d.alloc(tab_bytes));
-    CNIIC_HIP_TRY(c, ctx_pinned_huf(c, tab_bytes));   // (the stream's head, if it was fetched there, has been parsed: lt owns what it said)
-    uint8_t *ph = static_cast<uint8_t *>(c->pinned_huf);
+    CNIIC_HIP_TRY(c, c->pinned_huf.reserve(tab_bytes, pinned_huf_want(tab_bytes)));   // (the stream's head, if it was fetched there, has been parsed: lt owns what it said)
+    uint8_t *ph = c->pinned_huf.as<uint8_t>();
     memcpy(ph, lt.code.data(), n * 8);
     memcpy(ph + off_key, lt.key.data(), n * 4);
     memcpy(ph + off_len, lt.len.data(), n);
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(tab_d.p, c->pinned_huf, tab_bytes, hipMemcpyHostToDevice, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(tab_d.p, c->pinned_huf.p, tab_bytes, hipMemcpyHostToDevice, c->stream));
     return huff_decode_tables_dev(c, tab_d.as<uint8_t>(), n, off_key, off_len, lt.max_len, lt.key[0], payload, payload_dev, payload_bytes, nsyms, mode, out_d, status, sums);
 }
 
@@ -1051,8 +1051,8 @@ int huff_decode_batch_dev(Ctx *c, std::vector<HdBatchFrame> &fv) {
     CNIIC_HIP_TRY(c, up_d.alloc(up_bytes));
     CNIIC_HIP_TRY(c, lut1_d.alloc((uint64_t)nf << (kHdLut + 2)));
     CNIIC_HIP_TRY(c, lut2_d.alloc(std::max<uint64_t>(lut2_bytes, 16)));
-    CNIIC_HIP_TRY(c, ctx_pinned_huf(c, res_at + 16ull * nf));
-    uint8_t *ph = static_cast<uint8_t *>(c->pinned_huf);
+    CNIIC_HIP_TRY(c, c->pinned_huf.reserve(res_at + 16ull * nf, pinned_huf_want(res_at + 16ull * nf)));
+    uint8_t *ph = c->pinned_huf.as<uint8_t>();
     uint8_t *ud = up_d.as<uint8_t>();
     for (uint32_t f = 0; f < nf; f++) {
         const LeafTable &lt = *fv[f].lt;

@@ -528,10 +528,8 @@ int hilbert_lut(Ctx *c, const HilbertLut **lut_d) {
         static std::once_flag once;
         std::call_once(once, [] { ok = build_hilbert_lut(host_lut); });
         if (!ok) return c->fail(CNIIC_ERR_HIP, "hilbert: look-up tables failed their self-check");
-        DevPool *saved = current_pool();
-        current_pool() = nullptr;  // lives as long as the context, not recycled
+        PoolScope keep(nullptr);  // lives as long as the context, not recycled
         hipError_t e = c->hilbert_lut.alloc(sizeof(HilbertLut));
-        current_pool() = saved;
         if (e != hipSuccess) return c->fail(CNIIC_ERR_HIP, "hilbert: hipMalloc failed");
         CNIIC_HIP_TRY(c, hipMemcpyAsync(c->hilbert_lut.p, &host_lut, sizeof(HilbertLut), hipMemcpyHostToDevice, c->stream));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -668,14 +666,12 @@ static int scan_leaves_get(Ctx *c, uint32_t w, uint32_t h, const ScanLeavesDev *
     en->w = w; en->h = h; en->stamp = ++cache->clock;
     DevBuf cls_d, bad_d;
     {
-        DevPool *saved = current_pool();
-        current_pool() = nullptr;   // live as long as the context keeps the entry, not recycled
+        PoolScope keep(nullptr);   // live as long as the context keeps the entry, not recycled
         hipError_t e = en->idx.alloc(idx.size() * 4);
         if (e == hipSuccess) e = en->d0.alloc(d0.size() * 4);
         if (e == hipSuccess) e = en->rec.alloc((uint64_t)nleaf * sizeof(int4));
         if (e == hipSuccess) e = en->lut.alloc(std::max<uint64_t>(total, 1) * 4);
         if (e == hipSuccess) e = en->hdr.alloc(sizeof(ScanLeavesDev));
-        current_pool() = saved;
         if (e != hipSuccess) return c->fail(CNIIC_ERR_NOMEM, "hilbert: no memory for the leaves of a %ux%u image", w, h);
     }
     CNIIC_HIP_TRY(c, cls_d.alloc(cls.size() * sizeof(LeafClass)));

@@ -1379,8 +1379,8 @@ int huff_tree_from_runs(Ctx *c, const uint64_t *sorted_d, const uint64_t *counts
     unsigned long long *totals = reinterpret_cast<unsigned long long *>(small.as<uint8_t>() + 16);   // [0] bits, [1] too long, [2] longest
     const uint32_t g = std::min<uint32_t>(ceil_div(n, 256u), 2048u);
     hipLaunchKernelGGL(k_leaf_run_count, dim3(g), dim3(256), 0, c->stream, sorted_d, n, nruns_d);
-    CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    volatile uint64_t *pin = reinterpret_cast<volatile uint64_t *>(c->pinned_u) + kPuLeafRuns.at;
+    CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+    volatile uint64_t *pin = c->pinned_u.as<volatile uint64_t>() + kPuLeafRuns.at;
     CNIIC_HIP_TRY(c, hipMemcpyAsync(const_cast<uint64_t *>(pin), nruns_d, 4, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
     const uint32_t R = (uint32_t)pin[0];
@@ -1389,19 +1389,19 @@ int huff_tree_from_runs(Ctx *c, const uint64_t *sorted_d, const uint64_t *counts
     hipLaunchKernelGGL(k_leaf_run_list, dim3(g), dim3(256), 0, c->stream, sorted_d, n, runs_d.as<uint2>(), cursor_d);
     // (pinned_huf is the caller's: used as it is when large enough, never grown here -- the caller holds pointers into it)
     std::vector<uint2> runs(R);
-    const bool pinned_runs = c->pinned_huf && c->pinned_huf_bytes >= (uint64_t)R * 8;
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(pinned_runs ? c->pinned_huf : (void *)runs.data(), runs_d.p, (uint64_t)R * 8, hipMemcpyDeviceToHost, c->stream));
+    const bool pinned_runs = c->pinned_huf.p && c->pinned_huf.bytes >= (uint64_t)R * 8;
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(pinned_runs ? c->pinned_huf.p : (void *)runs.data(), runs_d.p, (uint64_t)R * 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (pinned_runs) memcpy(runs.data(), c->pinned_huf, (uint64_t)R * 8);
+    if (pinned_runs) memcpy(runs.data(), c->pinned_huf.p, (uint64_t)R * 8);
     std::sort(runs.begin(), runs.end(), [](const uint2 &x, const uint2 &y) { return x.x < y.x; });
     std::vector<TreeDesc> desc;
     if (!merge_runs(runs.data(), R, n, desc)) return CNIIC_OK;
     host_trace().mark("huf: tree by runs (host)");
     const uint64_t dbytes = desc.size() * sizeof(TreeDesc);
     CNIIC_HIP_TRY(c, desc_d.alloc(dbytes));
-    const bool pinned_desc = c->pinned_huf && c->pinned_huf_bytes >= dbytes;
-    if (pinned_desc) memcpy(c->pinned_huf, desc.data(), dbytes);
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(desc_d.p, pinned_desc ? c->pinned_huf : (const void *)desc.data(), dbytes, hipMemcpyHostToDevice, c->stream));
+    const bool pinned_desc = c->pinned_huf.p && c->pinned_huf.bytes >= dbytes;
+    if (pinned_desc) memcpy(c->pinned_huf.p, desc.data(), dbytes);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(desc_d.p, pinned_desc ? c->pinned_huf.p : (const void *)desc.data(), dbytes, hipMemcpyHostToDevice, c->stream));
     CNIIC_HIP_TRY(c, tree_d.alloc(2ull * (n - 1) * 4));
     CNIIC_HIP_TRY(c, par.alloc(2ull * n * 4));
     uint32_t *left_d = tree_d.as<uint32_t>(), *right_d = left_d + (n - 1);

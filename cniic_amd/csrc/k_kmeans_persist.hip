@@ -1051,9 +1051,9 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     const int dev = c->device >= 0 && c->device < 16 ? c->device : 0, G = (int)s->ps_blocks;
     if (g_ps_cus_in_use[dev].fetch_add(G) + G > ps_cu_count(c->device)) { g_ps_cus_in_use[dev].fetch_sub(G); return CNIIC_OK; }
     std::shared_ptr<void> release(nullptr, [dev, G](void *) { g_ps_cus_in_use[dev].fetch_sub(G); });   // (given back when this goes -- or, deferred, when the state's copy does)
-    if (!c->pinned_ps) CNIIC_HIP_TRY(c, hipHostMalloc(&c->pinned_ps, 1024, hipHostMallocDefault));
+    CNIIC_HIP_TRY(c, c->pinned_ps.reserve(1024, 1024));
     static_assert(sizeof(PsCold) <= 1024, "the pinned block holds a PsCold");
-    PsCold *cold = static_cast<PsCold *>(c->pinned_ps);
+    PsCold *cold = c->pinned_ps.as<PsCold>();
     memset(cold, 0, sizeof *cold);
     PsExit *xh = &cold->exit;
     uint8_t *ar = s->ps_arena.as<uint8_t>();
@@ -1120,7 +1120,7 @@ int km_rgbw_persistent_verdict(KmRgbwState *s, bool *retry) {
     *retry = false;
     s->ps_pending = false;
     s->ps_hold.reset();
-    const PsExit *xh = &static_cast<const PsCold *>(c->pinned_ps)->exit;
+    const PsExit *xh = &c->pinned_ps.as<const PsCold>()->exit;
     ps_learn(c, xh->status, test_env("CNIIC_TEST_PS_ABORT_AT") != nullptr);
     if (xh->status == kPsStatusDone) {
         s->run_stats.iterations = xh->iter; s->run_stats.moved_last = xh->moved_last; s->run_stats.empty_reseeds = xh->reseeds;

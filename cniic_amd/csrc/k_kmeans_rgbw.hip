@@ -1942,14 +1942,9 @@ int km_rgbw_result(KmRgbwState *s, uint8_t *centroids_h, uint32_t *labels_d_u32,
 // state, centroids, members, weight sums are one block: one copy into pinned memory, one event
 int km_rgbw_result_begin(KmRgbwState *s) {
     Ctx *c = s->c;
-    if (c->pinned_res_bytes < s->res_bytes) {
-        if (c->pinned_res) CNIIC_HIP_TRY(c, hipHostFree(c->pinned_res));
-        c->pinned_res = nullptr; c->pinned_res_bytes = 0;
-        CNIIC_HIP_TRY(c, hipHostMalloc(&c->pinned_res, s->res_bytes, hipHostMallocDefault));
-        c->pinned_res_bytes = s->res_bytes;
-    }
-    if (!c->res_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->res_ev, hipEventDisableTiming));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_res, s->resblk.p, s->res_bytes, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, c->pinned_res.reserve(s->res_bytes, s->res_bytes));
+    CNIIC_HIP_TRY(c, c->res_ev.ensure(hipEventDisableTiming));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_res.p, s->resblk.p, s->res_bytes, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipEventRecord(c->res_ev, c->stream));
     return CNIIC_OK;
 }
@@ -1962,7 +1957,7 @@ int km_rgbw_result_end(KmRgbwState *s, uint8_t *centroids_h, uint64_t *members_h
         CNIIC_TRY(km_rgbw_persistent_verdict(s, &retry));
         if (retry) return kKmRetry;
     }
-    const uint8_t *blk = static_cast<const uint8_t *>(c->pinned_res);
+    const uint8_t *blk = c->pinned_res.as<const uint8_t>();
     KmDevState h;
     memcpy(&h, blk, sizeof h);
     const uint32_t *ck = reinterpret_cast<const uint32_t *>(blk + s->res_cent);

@@ -481,8 +481,8 @@ int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan) {
     CNIIC_HIP_TRY(c, total.alloc((uint64_t)kSpBuckets * 4));
     CNIIC_HIP_TRY(c, blocktot.alloc(256 * 4));
     CNIIC_HIP_TRY(c, plan->total.alloc(8));
-    CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    if (!c->u_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->u_ev, hipEventDisableTiming));
+    CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+    CNIIC_HIP_TRY(c, c->u_ev.ensure(hipEventDisableTiming));
     hipLaunchKernelGGL(k_sp_count, dim3(plan->nchunks), dim3(kSpThreads), 0, c->stream, rgb_d, npx, plan->cnt.as<uint32_t>());
     hipLaunchKernelGGL(k_sp_colscan, dim3(kSpBuckets), dim3(256), 0, c->stream, plan->cnt.as<uint32_t>(), plan->nchunks,
                        plan->pre.as<uint32_t>(), total.as<uint32_t>());
@@ -498,14 +498,14 @@ int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan) {
                        blocktot.as<uint32_t>());
     CNIIC_TRY(gidx_finish(c, plan->wprefix.as<uint32_t>(), blocktot.as<uint32_t>(), plan->total.as<uint64_t>()));
     CNIIC_HIP_TRY(c, hipGetLastError());
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
     return CNIIC_OK;
 }
 
 int sp_wait_count(Ctx *c, SpPlan *plan) {
     CNIIC_HIP_TRY(c, hipEventSynchronize(c->u_ev));
-    plan->U = c->pinned_u[kPuSpCount.at];
+    plan->U = c->pinned_u.as<uint64_t>()[kPuSpCount.at];
     return CNIIC_OK;
 }
 

@@ -250,7 +250,7 @@ int surf_convert(Ctx *c, bool to_surfaces, const uint8_t *in_d, uint8_t *out_d, 
     uint8_t *p = buf.as<uint8_t>();
     CNIIC_HIP_TRY(c, hipMemcpyAsync(p, fr_h, off_first, hipMemcpyHostToDevice, c->stream));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(p + off_first, first.data(), 4ull * (frames + 1), hipMemcpyHostToDevice, c->stream));
-    if (!c->surf_ev) CNIIC_HIP_TRY(c, hipEventCreateWithFlags(&c->surf_ev, hipEventDisableTiming));
+    CNIIC_HIP_TRY(c, c->surf_ev.ensure(hipEventDisableTiming));
     CNIIC_HIP_TRY(c, hipEventRecord(c->surf_ev, c->stream));
     const SurfFrame *fr_d = reinterpret_cast<const SurfFrame *>(p);
     const uint32_t *first_d = reinterpret_cast<const uint32_t *>(p + off_first);

@@ -344,8 +344,8 @@ int huff_parse_leaves_dev(Ctx *c, int sym_kind, const uint8_t *stream_d, uint64_
     CNIIC_HIP_TRY(c, pbase.alloc((uint64_t)nchunks * 4));
     CNIIC_HIP_TRY(c, picked.alloc((uint64_t)nchunks * sizeof(TpInfo)));
     CNIIC_HIP_TRY(c, tot_d.alloc(sizeof(TpTotals)));
-    CNIIC_HIP_TRY(c, ctx_pinned_u(c));
-    TpTotals *th = reinterpret_cast<TpTotals *>(c->pinned_u + kPuTrieTotals.at);
+    CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+    TpTotals *th = reinterpret_cast<TpTotals *>(c->pinned_u.as<uint64_t>() + kPuTrieTotals.at);
     TpTotals init{};
     init.end_chunk = 0xffffffffu; init.min_len = 0xffffffffu;
     *th = init;
