@@ -25,26 +25,15 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "delta_sym.hpp"
 #include "device_utils.hpp"
 #include "hilbert_scan.hpp"
 
 namespace cniic {
 
-constexpr uint32_t kHot = 32 * 32 * 32;
-constexpr uint32_t kCold16 = 0x8000u, kPad16 = 0x8040u;  // kCold16 + r, r < 64
+// (the symbol's three forms -- key, cube index, field word -- and the ways between them: delta_sym.hpp, checked on the host by
+// tests/delta_sym_check.cpp)
 constexpr int kChunk16 = 512;  // symbols per wave and step of the count and the pack: one 16-byte read per lane
-
-// DiffStream::next (hilbertc.rs:458-476) on two r | g << 8 | b << 16 pixels: the packed SignedColor key and the cube index
-__device__ __forceinline__ uint32_t delta_key(uint32_t px, uint32_t prev, uint32_t &hot) {
-    const int32_t dr = (int32_t)(px & 255) - (int32_t)(prev & 255), dg = (int32_t)((px >> 8) & 255) - (int32_t)((prev >> 8) & 255),
-                  db = (int32_t)((px >> 16) & 255) - (int32_t)((prev >> 16) & 255);
-    const uint32_t hr = (uint32_t)(dr + 16), hg = (uint32_t)(dg + 16), hb = (uint32_t)(db + 16);
-    hot = (hr | hg | hb) < 32u ? (hr << 10) | (hg << 5) | hb : kCold16;
-    return ((uint32_t)(dr + 255) << 18) | ((uint32_t)(dg + 255) << 9) | (uint32_t)(db + 255);
-}
-__device__ __forceinline__ uint32_t hot_to_key(uint32_t i) {
-    return (((i >> 10) + 255 - 16) << 18) | ((((i >> 5) & 31) + 255 - 16) << 9) | ((i & 31) + 255 - 16);
-}
 constexpr uint32_t kColdPerChunk = 64;
 __device__ __forceinline__ uint32_t lanes_before(uint64_t mask) {  // set bits of mask below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -60,11 +49,6 @@ __device__ __forceinline__ uint32_t lanes_before(uint64_t mask) {  // set bits o
 // the block's base (wave-uniform, scalar) plus the lane's place in the block for the orientation the curve has there --
 // four possibilities, six bits each, packed in one register per lane for the whole kernel.  The predecessor of a lane's
 // pixel is the lane before; the wave's last pixel is carried to its next step.
-constexpr uint32_t kField = 528;                                      // c - p + 528 in [273, 783]: ten bits, never negative
-constexpr uint32_t kFields = 1u | (1u << 10) | (1u << 20);
-__device__ __forceinline__ uint32_t px_fields(uint32_t px) {         // r | g << 8 | b << 16 (bits 24..31: anything)
-    return ((px >> 16) & 255u) + (((px >> 8) & 255u) << 10) + ((px & 255u) << 20) + kField * kFields;
-}
 __global__ __launch_bounds__(256) void k_delta_gather_p2(const uint8_t *__restrict__ rgb, uint32_t order, const HilbertLut *__restrict__ lut,
                                                          uint16_t *__restrict__ hot16, uint32_t *__restrict__ table, uint8_t *__restrict__ pages,
                                                          uint32_t *__restrict__ coldkeys, uint8_t *__restrict__ chunk_cold,
@@ -94,7 +78,6 @@ __global__ __launch_bounds__(256) void k_delta_gather_p2(const uint8_t *__restri
     // a block's word base and the XOR of its rows, from x:3 | y:3 << 3
     auto blk_base = [](uint32_t e) { return (e & 63u) << 6; };
     auto blk_xor = [](uint32_t e) { return (((e >> 1) & 3u) | (((e >> 3) & 1u) << 2)) << 3; };
-    constexpr uint32_t kC = kField * kFields, kMask = 0x3e0u * kFields, kHotBits = 0x200u * kFields;
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         // where the tile lies and in which orientation the curve enters it: the levels above the tile
         uint32_t st = 0, tx = 0, ty = 0, rem = order - 6;
@@ -147,10 +130,10 @@ __global__ __launch_bounds__(256) void k_delta_gather_p2(const uint8_t *__restri
             const uint32_t e = (es[j >> 2] >> (8 * (j & 3))) & 255u;
             const uint32_t place = (places >> (6 * (e >> 6))) & 63u;
             const uint32_t t = s_tile[blk_base(e) + (place ^ blk_xor(e))];
-            const uint32_t d = t - wave_prev_lane(t, carried) + kC;  // fields c - p + 528
+            const uint32_t d = fields_diff(t, wave_prev_lane(t, carried));  // fields c - p + 528
             carried = (uint32_t)__builtin_amdgcn_readlane((int)t, 63);
-            const bool cold = (d & kMask) != kHotBits;              // some field outside [512, 543]
-            uint32_t hot = ((d >> 10) & 0x7c00u) | ((d >> 5) & 0x3e0u) | (d & 31u);
+            const bool cold = fields_cold(d);                       // some field outside [512, 543]
+            uint32_t hot = fields_hot(d);
             const uint64_t cm = __builtin_amdgcn_ballot_w64(cold);
             if (cm) {  // (one step in two: one lane in 90 is cold) the lane's differences go to the wave's list in LDS
                 if (cold) {
@@ -167,8 +150,7 @@ __global__ __launch_bounds__(256) void k_delta_gather_p2(const uint8_t *__restri
                 __builtin_amdgcn_wave_barrier();
                 if (lane < min(crank, kColdPerChunk)) {
                     const uint32_t dd = s_cold[wave * kColdPerChunk + lane];
-                    const uint32_t key = ((((dd >> 20) & 1023u) - (kField - 255)) << 18) | ((((dd >> 10) & 1023u) - (kField - 255)) << 9) |
-                                         ((dd & 1023u) - (kField - 255));
+                    const uint32_t key = fields_key(dd);
                     // (a photograph's chunk holds five such symbols of five kinds: one atomic each.  A chunk with sixteen or more is not a
                     // photograph's -- a pattern of few colours, whose keys repeat: those add together, atomic_count.  crank is wave-uniform.)
                     if (crank >= 16) atomic_count(table, key);
@@ -314,9 +296,8 @@ __global__ void k_delta_fill_codes(const uint32_t *__restrict__ keys, const uint
         const uint32_t v = len[i] <= inline_max ? ((uint32_t)len[i] << 26) | (uint32_t)code[i] : (kEscape << 26) | (uint32_t)i;
         const uint32_t k = keys[i];
         dense[k] = v;
-        const uint32_t hr = (k >> 18) - (255 - 16), hg = ((k >> 9) & 511) - (255 - 16), hb = (k & 511) - (255 - 16);
-        if ((hr | hg | hb) < 32u) {
-            const uint32_t hx = (hr << 10) | (hg << 5) | hb;
+        uint32_t hx;
+        if (key_to_hot(k, hx)) {
             hot[hx] = v;
             hotlen[hx] = len[i];
         }
