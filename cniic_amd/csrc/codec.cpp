@@ -262,6 +262,7 @@ struct HuffCodeStage {
         CNIIC_TRY(huff_tree_from_runs(c, sorted_d, counts_d.as<uint64_t>(), (uint32_t)U, sym_kind, len_d.as<uint8_t>(), code_d.as<uint64_t>(),
                                       off_d.as<uint64_t>(), &nbits, &tree_built));
         if (!tree_built) CNIIC_HIP_TRY(c, hipMemcpyAsync(counts_h, sorted_d, U * 8, hipMemcpyDeviceToHost, c->stream));
+        if (c->timers && tree_built) c->ktimes["huf_tree_runs"].launches++;   // (stage timers: which route the tree took; no duration)
         return CNIIC_OK;
     }
 
@@ -284,6 +285,7 @@ struct HuffCodeStage {
         const uint32_t *left_d = tree_d.as<uint32_t>(), *right_d = left_d + (U - 1), *nleaves_d = right_d + (U - 1);
         CNIIC_TRY(huff_tree_codes(c, left_d, right_d, nleaves_d, counts_d.as<uint64_t>(), (uint32_t)U, root, sym_kind, len_d.as<uint8_t>(),
                                   code_d.as<uint64_t>(), off_d.as<uint64_t>(), totals_d));
+        if (c->timers) c->ktimes["huf_tree_host"].launches++;   // (stage timers: the tree came from the host's merge; no duration)
         CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
         CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuHufTotals.at, totals_d, 16, hipMemcpyDeviceToHost, c->stream));
         totals_pending = true;

@@ -1112,7 +1112,8 @@ int huff_sort_leaves_dev(Ctx *c, const uint64_t *counts_d, uint32_t n, uint64_t 
     CNIIC_HIP_TRY(c, tot.alloc(8));
     hipLaunchKernelGGL(k_leaf_init, dim3(ceil_div(n, 256u)), dim3(256), 0, c->stream, counts_d, n, buf_a);
     uint64_t *src = buf_a, *dst = buf_b;
-    for (uint32_t shift = 32; shift < 64 && (max_count >> (shift - 32)) != 0; shift += 8) {
+    uint32_t passes = 0;
+    for (uint32_t shift = 32; shift < 64 && (max_count >> (shift - 32)) != 0; shift += 8, passes++) {
         hipLaunchKernelGGL(k_sort_hist, dim3(nblocks), dim3(kSortThreads), 0, c->stream, (const uint64_t *)src, n, shift, nblocks, hist.as<uint32_t>());
         CNIIC_TRY(pack_scan_counts(c, hist.as<uint32_t>(), 256 * nblocks, off.as<uint64_t>(), tot.as<uint64_t>()));
         hipLaunchKernelGGL(k_sort_scatter, dim3(nblocks), dim3(kSortThreads), 0, c->stream, (const uint64_t *)src, n, shift, nblocks,
@@ -1120,6 +1121,7 @@ int huff_sort_leaves_dev(Ctx *c, const uint64_t *counts_d, uint32_t n, uint64_t 
         std::swap(src, dst);
     }
     CNIIC_HIP_TRY(c, hipGetLastError());
+    if (c->timers) c->ktimes["huf_sort_passes"].launches += passes;   // (stage timers: how many radix passes the counts needed; no duration)
     *out_d = src;
     return CNIIC_OK;
 }

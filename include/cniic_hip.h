@@ -99,7 +99,11 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * Names: "kmeans_rgbw_persist" (the colour K-means as one persistent launch; "kmeans_rgbw_persist_iters": the same duration, launches =
  * its iterations), "kmeans_rgbw_assign" (... as one launch per iteration), "kmeans_xyrgb_iter", "hist_rgb", "remap_rgb", "huff_pack", "hilbert_delta", "undiff_scatter", "hd_pass0" /
  * "hd_check" / "hd_write", and the five consecutive stages of a `delta` encode, which together are the whole call: "delta_gather",
- * "delta_hist", "delta_tree" (compaction, the leaves' sort, the host's merge, the codes), "huff_pack", "delta_finish". */
+ * "delta_hist", "delta_tree" (compaction, the leaves' sort, the host's merge, the codes), "huff_pack", "delta_finish".
+ * With CNIIC_OPT_STAGE_TIMERS on, the Huffman code stage of a large alphabet adds three marks (launches only, no duration): "huf_tree_runs" =
+ * 1 when the tree was built on the GPU from runs of equally frequent leaves, "huf_tree_host" = 1 when it came from the host's merge with
+ * codes and decoder from the GPU, "huf_sort_passes" = the 8-bit radix passes of the leaves' sort by count.  None of them for a small
+ * alphabet, whose tree and codes are the host's. */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */

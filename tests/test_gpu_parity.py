@@ -3,6 +3,7 @@ Bit-exact for every integer / byte / index result."""
 import numpy as np
 import pytest
 
+import huff_limits_ref as H
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -307,14 +308,10 @@ def test_huf_encode_all_rgb(ctx, n):
 
 
 def test_huf_encode_all_long_codes(ctx):
-    """Fibonacci-like counts give code lengths > 32 bits: exercises the 3-word straddle path."""
-    fib = [1, 1]
-    while len(fib) < 40:
-        fib.append(fib[-1] + fib[-2])
-    fib = [min(f, 3000) if i > 20 else f for i, f in enumerate(fib)]
-    syms = np.concatenate([np.full(f, i * 7 + 1, np.uint32) for i, f in enumerate(fib)])
-    np.random.default_rng(0).shuffle(syms)
-    assert ctx.huf_encode_all(2, syms) == O.huf_encode_all(O.SYM_SIGNED, syms)
+    """Fibonacci counts F(1) .. F(34) give a longest code of exactly 33 bits (tests/test_huff_limits_cpu.py holds the stream to that): codes
+    above 26 bits escape from the inline (length, code) word, and a 33-bit code spans two or three output words."""
+    syms = H.stream("fib33")
+    assert ctx.huf_encode_all(2, syms) == H.expected("fib33")
 
 
 @pytest.mark.parametrize("runs", [False, True])
@@ -348,18 +345,13 @@ def test_huf_codes_and_decoder_on_the_gpu(ctx, monkeypatch, kind, n, runs):
 
 @pytest.mark.parametrize("runs", [False, True])
 def test_huf_long_codes_on_the_gpu(ctx, monkeypatch, runs):
-    """Fibonacci-like counts: codes of up to 39 bits through the GPU's walk (`runs`: the tree from runs gives way to the host's
+    """Fibonacci counts F(1) .. F(34): codes of up to 33 bits through the GPU's walk (`runs`: the tree from runs gives way to the host's
     merge when a code outgrows the 32 bits its sort by code keys on)"""
     monkeypatch.setenv("CNIIC_HUF_GPU_CODES_MIN", "0")
     if runs:
         monkeypatch.setenv("CNIIC_HUF_RUNS_MIN", "0")
-    fib = [1, 1]
-    while len(fib) < 40:
-        fib.append(fib[-1] + fib[-2])
-    fib = [min(f, 3000) if i > 20 else f for i, f in enumerate(fib)]
-    syms = np.concatenate([np.full(f, i * 7 + 1, np.uint32) for i, f in enumerate(fib)])
-    np.random.default_rng(0).shuffle(syms)
-    assert ctx.huf_encode_all(2, syms) == O.huf_encode_all(O.SYM_SIGNED, syms)
+    syms = H.stream("fib33")
+    assert ctx.huf_encode_all(2, syms) == H.expected("fib33")
 
 
 # ------------------------------------------------------------------ codecs end to end
