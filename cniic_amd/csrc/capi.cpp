@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "huff_host.hpp"
 #include "surf_index.hpp"
+#include "cc_small.hpp"
 
 using namespace cniic;
 
@@ -1274,16 +1275,7 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
 }
 
 // ---- images of different sizes (cniic_codec_encode_batch_var, cniic_codec_measure_batch)
-struct VarFrame {
-    const uint8_t *src = nullptr;   // the image (host or device memory, any alignment)
-    uint32_t w = 0, h = 0;
-    uint8_t *out = nullptr;         // where its stream goes, cap bytes at most
-    uint64_t cap = 0;
-    uint64_t len = 0;               // results: what cniic_codec_encode_opts answers for this image alone
-    int32_t rc = CNIIC_OK;
-    cniic_kmeans_stats st{};
-    std::string msg;
-};
+// (VarFrame, a frame's arguments and results: codec.hpp)
 
 // One frame on a worker context.  A DEVICE image that does not start on a 16-byte boundary would leave the pixel partition of
 // cluster-colors and the 16-byte tile reads of `delta` (same bytes, slower routes): it is copied into the worker's aligned scratch
@@ -1308,17 +1300,23 @@ static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kme
     return rc;
 }
 
-// Every frame of the list encoded exactly as cniic_codec_encode_opts would, on the worker contexts of cniic_codec_encode_batch.  The
-// frames are handed out from one queue, LARGEST FIRST: with sizes that differ the last worker to finish then holds a small frame, and
-// frames of one size follow one another, which keeps the few scan tables a context caches (`delta`, `hilbert(rle)`) in use.  Which
-// worker takes which frame shows in no output.  With the stage timers on, the workers' timers are on too and the context's kernel
-// times are the sums over all frames.
+// Every frame of the list encoded exactly as cniic_codec_encode_opts would.  SMALL cluster-colors(K <= 256) frames in device memory
+// (1 .. kCcSmallMaxPx pixels, no K-means flags) are coded together in one set of launches on this context (cc_small_encode, codec.cpp: a
+// workgroup per frame); which route a frame took shows in no output byte.  The testing library can switch the route off
+// (CNIIC_TEST_CC_SMALL_OFF=1) or lower its pixel bound (CNIIC_TEST_CC_SMALL_MAX_PX).  Every other frame goes to the worker contexts of
+// cniic_codec_encode_batch, handed out from one queue, LARGEST FIRST: with sizes that differ the last worker to finish then holds a small
+// frame, and frames of one size follow one another, which keeps the few scan tables a context caches (`delta`, `hilbert(rle)`) in use.
+// Which worker takes which frame shows in no output.  With the stage timers on, the workers' timers are on too and the context's kernel
+// times are the sums over all frames ("cc_small_batch": k_cc_small, launches = the frames that took the small-frame route).
+static uint64_t cc_small_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_CC_SMALL_OFF")) if (atoi(e) != 0) return 0;
+    if (const char *e = test_env("CNIIC_TEST_CC_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kCcSmallMaxPx);
+    return kCcSmallMaxPx;
+}
+
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
     const uint32_t n = (uint32_t)fr.size();
     if (!n) return CNIIC_OK;
-    const uint32_t S = batch_workers_ready(c, n, who);
-    if (!S) return CNIIC_ERR_HIP;
-    batch_workers_share(c, S);
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; i++) order[i] = i;
     std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
@@ -1327,6 +1325,35 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
         if (fr[x].w != fr[y].w) return fr[x].w > fr[y].w;
         return x < y;
     });
+    std::map<std::string, KernelTime> kt;
+    // ---- the small cluster-colors frames, together
+    CodecDesc d;
+    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_CLUSTER_COLORS && d.arg >= 1 && d.arg <= kCcSmallMaxK && (!opts || opts->flags == 0)) {
+        const uint64_t max_px = cc_small_max_px();
+        std::vector<VarFrame *> small;
+        std::vector<uint32_t> rest;
+        for (uint32_t j = 0; j < n; j++) {
+            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
+            if (px >= 1 && px <= max_px) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
+        }
+        if (!small.empty()) {
+            std::map<std::string, KernelTime> mine;
+            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
+            const int32_t rc = cc_small_encode(c, d.arg, opts, small.data(), (uint32_t)small.size());
+            mine.swap(c->ktimes);
+            CNIIC_TRY(rc);
+            if (c->timers) kt.swap(mine);
+            order.swap(rest);
+        }
+    }
+    const uint32_t nw = (uint32_t)order.size();
+    if (!nw) {
+        if (c->timers) c->ktimes.swap(kt);
+        return CNIIC_OK;
+    }
+    const uint32_t S = batch_workers_ready(c, nw, who);
+    if (!S) return CNIIC_ERR_HIP;
+    batch_workers_share(c, S);
     std::vector<uint8_t> saved_timers(S);
     for (uint32_t i = 0; i < S; i++) {
         cniic_ctx *wk = c->batch_workers[i].get();
@@ -1334,8 +1361,7 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
         wk->timers = wk->timers || c->timers;
     }
     std::mutex kt_mu;
-    std::map<std::string, KernelTime> kt;
-    parallel_for(n, S, [&](uint32_t j, uint32_t i) {
+    parallel_for(nw, S, [&](uint32_t j, uint32_t i) {
         cniic_ctx *wk = c->batch_workers[i].get();
         VarFrame &f = fr[order[j]];
         f.rc = encode_var_frame(wk, expr, opts, src_dev, f);
@@ -1620,12 +1646,15 @@ struct MeasureJob {
             fr[j].out = sbuf.as<uint8_t>() + room * j; fr[j].cap = room;
         }
         CNIIC_TRY(encode_frames(c, expr, opts, fr, true, "codec_measure_batch"));
+        std::map<std::string, KernelTime> enc_kt;   // (the decode below starts its stage times afresh: the encode's are added back)
+        if (c->timers) enc_kt = c->ktimes;
         for (uint32_t j = 0; j < n; j++) slen[j] = fr[j].rc == CNIIC_OK ? fr[j].len : 0;
         std::vector<uint32_t> w2(n), h2(n);
         std::vector<int32_t> drc(n, CNIIC_OK);
         std::vector<std::string> dmsg;
         (void)decode_batch_locked(c, expr, sbuf.as<uint8_t>(), room, slen.data(), n, ibuf.as<uint8_t>(), img_stride, w2.data(), h2.data(), drc.data(), &dmsg);
         if (dmsg.size() != n) return CNIIC_ERR_HIP;   // (the batch as a whole failed: the message is the context's)
+        for (const auto &e : enc_kt) { c->ktimes[e.first].ms += e.second.ms; c->ktimes[e.first].launches += e.second.launches; }
         for (uint32_t j = 0; j < n; j++) {
             b_off[j] = img_stride * j;
             npx[j] = fr[j].rc == CNIIC_OK && drc[j] == CNIIC_OK ? (uint64_t)fr[j].w * fr[j].h : 0;

@@ -10,6 +10,7 @@
 //                                             the running average (k_rle_approx.hip): `hilbert(rle)` and `hilbert(rle(<f64>))`
 //   Zip::Dict       src/codec/zipc.rs         `zip(dict)`: the dictionary coder over the serialised image (zipdict.cpp, k_zipdict.hip)
 #include "codec.hpp"
+#include "cc_small.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -718,9 +719,10 @@ struct FrameBatch {
 // The two callers are a K-means session's finish_frames and a frozen palette's palette_encode_frames_var.  after_hist (optional) runs
 // once the histograms are enqueued and before the host waits for them: a session collects its K-means result there -- which is when
 // cent_h is filled in; nobody reads it earlier.  headers_aside: CNIIC_ERR_CAPACITY leaves `out` untouched on the k_frame_trees route as well (a
-// session's calls write the headers in place and refuse afterwards, as they always have).
+// session's calls write the headers in place and refuse afterwards, as they always have).  pal_stride: 0 = the one palette at cent_d / cent_h
+// for every frame; K = a palette per frame, frame f's entries at cent_d + f K (cent_h + 3 f K): the small-frame route of cc_small_encode.
 static int frames_tail(Ctx *c, const void *pixlab_d, bool wide, uint32_t K, const uint32_t *cent_d, const uint8_t *cent_h, const FrameBatch &fb, uint8_t *out,
-                       uint64_t stride, uint64_t *lens, const std::function<int()> &after_hist, bool headers_aside = false) {
+                       uint64_t stride, uint64_t *lens, const std::function<int()> &after_hist, bool headers_aside = false, uint32_t pal_stride = 0) {
     const bool var = fb.var();
     const uint32_t F = fb.F, w = fb.w, h = fb.h, chunks = fb.chunks, hblocks = fb.hblocks;
     const uint32_t *wv = fb.wv, *hv = fb.hv;
@@ -795,7 +797,7 @@ static int frames_tail(Ctx *c, const void *pixlab_d, bool wide, uint32_t K, cons
         CNIIC_HIP_TRY(c, hipMemsetAsync(err_d, 0, 8, c->stream));
         ScopedKernelTimer t_trees(c, "frames_var_trees", var && c->timers);
         CNIIC_TRY(frame_trees(c, cnt_d.as<uint32_t>(), cent_d, F, K, w, h, headers_aside ? hdr_d.as<uint8_t>() : fo.dev, headers_aside ? hstride : stride,
-                              clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d, fr_d));
+                              clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), bb_d, nb_d, ln_d, err_d, fr_d, pal_stride));
         t_trees.stop(1);
         std::vector<uint64_t> meta((size_t)F * 3 + 1);
         CNIIC_HIP_TRY(c, hipMemcpyAsync(meta.data(), meta_d.p, (size_t)F * 24 + 8, hipMemcpyDeviceToHost, c->stream));
@@ -823,7 +825,7 @@ static int frames_tail(Ctx *c, const void *pixlab_d, bool wide, uint32_t K, cons
     std::vector<uint64_t> ccode((size_t)F * K), nbits(F, 0);
     std::atomic<int> bad{0};
     parallel_for(F, std::max(1u, std::min({F, 16u, std::thread::hardware_concurrency()})), [&](uint32_t f, uint32_t) {
-        if (!palette_code(cent_h, cnt.data() + (size_t)f * K, K, var ? wv[f] : w, var ? hv[f] : h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K],
+        if (!palette_code(cent_h + 3 * (size_t)f * pal_stride, cnt.data() + (size_t)f * K, K, var ? wv[f] : w, var ? hv[f] : h, headers[f], &clen[(size_t)f * K], &ccode[(size_t)f * K],
                           &nbits[f]))
             bad = 1;
     });
@@ -1017,6 +1019,139 @@ int palette_encode_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *
     CNIIC_TRY(fb.upload_table(c));
     CNIIC_TRY(palette_labels(p, rgb_d, n, pixlab.p));
     return frames_tail(c, pixlab.p, p->wide, p->K, p->cent_d.as<uint32_t>(), p->cent_h.data(), fb, out, stride, lens, nullptr, true);
+}
+
+// ---- small cluster-colors frames of a batch call, all at once (codec.hpp; k_cc_small.hip)
+// The stride of the tail's scratch is one no stream of a frame of npx pixels can exceed: the header is at most 8 + 13 K bytes (the tail's
+// own hstride), the payload fewer than (log2 256 + 1) npx = 9 npx bits (Huffman's redundancy bound over at most 256 symbols).
+static uint64_t cc_small_stream_bound(uint64_t npx, uint32_t K) { return (8ull + 13ull * K + (9 * npx + 7) / 8 + 15) & ~15ull; }
+
+static int cc_small_chunk(Ctx *c, uint32_t K, uint64_t seed, uint64_t max_iters, VarFrame *const *fr, uint32_t n) {
+    // ---- k_cc_small: rows, labels, palettes, results
+    std::vector<CcSmallRow> rows(n);
+    uint64_t lab_total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        rows[i] = CcSmallRow{fr[i]->src, lab_total, fr[i]->w, fr[i]->h};
+        lab_total += ((uint64_t)fr[i]->w * fr[i]->h + 15) & ~15ull;
+    }
+    DevBuf rows_d, labels_d, cent_d, res_d;
+    CNIIC_HIP_TRY(c, rows_d.alloc((uint64_t)n * sizeof(CcSmallRow)));
+    CNIIC_HIP_TRY(c, labels_d.alloc(lab_total + 16));
+    CNIIC_HIP_TRY(c, cent_d.alloc((uint64_t)n * K * 4));
+    CNIIC_HIP_TRY(c, res_d.alloc((uint64_t)n * sizeof(CcSmallResult)));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(CcSmallRow), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedKernelTimer t(c, "cc_small_batch");
+        CNIIC_TRY(cc_small_run(c, rows_d.as<CcSmallRow>(), n, fr[0]->w * fr[0]->h, K, seed, max_iters, labels_d.as<uint8_t>(), cent_d.as<uint32_t>(),
+                               res_d.as<CcSmallResult>()));
+        t.stop(n);
+    }
+    std::vector<CcSmallResult> res(n);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, (size_t)n * sizeof(CcSmallResult), hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // ---- every frame's K-means outcome, as the single call reports it; the frames that go on
+    std::vector<uint32_t> ok;
+    for (uint32_t i = 0; i < n; i++) {
+        VarFrame &f = *fr[i];
+        const CcSmallResult &r = res[i];
+        if (r.status) {
+            f.rc = c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu distinct colours for %u clusters (src/kmeans.rs:68)", (unsigned long long)r.U, K);
+            f.msg = c->err;
+            continue;
+        }
+        f.st.iterations = r.iterations; f.st.moved_last = r.moved_last; f.st.empty_reseeds = r.reseeds; f.st.active = r.active;
+        f.st.pair_evals = (uint64_t)r.iterations * r.U * K;
+        f.rc = check_enough_active(c, K, r.U, r.active);
+        if (f.rc != CNIIC_OK) { f.msg = c->err; continue; }
+        ok.push_back(i);
+    }
+    const uint32_t F = (uint32_t)ok.size();
+    if (!F) return CNIIC_OK;
+    // ---- the tail over those frames, a palette each, into scratch
+    std::vector<uint32_t> wv(F), hv(F);
+    FrameBatch fb;
+    fb.F = F;
+    fb.ft.resize(F);
+    uint64_t ch = 0, hb = 0;
+    for (uint32_t j = 0; j < F; j++) {
+        const VarFrame &f = *fr[ok[j]];
+        const uint64_t np = (uint64_t)f.w * f.h;
+        wv[j] = f.w; hv[j] = f.h;
+        fb.ft[j] = FrameVar{np, rows[ok[j]].lab_base, rows[ok[j]].lab_base, (uint32_t)ch, (uint32_t)hb, f.w, f.h};
+        ch += ceil_div(np, kFrameVarChunk);
+        hb += ceil_div(np, kFrameVarHistSpan);
+    }
+    fb.wv = wv.data(); fb.hv = hv.data();
+    fb.lab_total = lab_total; fb.chunks = (uint32_t)ch; fb.hblocks = (uint32_t)hb;
+    CNIIC_TRY(fb.upload_table(c));
+    // the palettes of the frames that go on, in the tail's frame order (all of them: where they are)
+    DevBuf cent_ok;
+    const uint32_t *cent_tail = cent_d.as<uint32_t>();
+    if (F != n) {
+        CNIIC_HIP_TRY(c, cent_ok.alloc((uint64_t)F * K * 4));
+        for (uint32_t j = 0; j < F;) {   // (runs of neighbours move together)
+            uint32_t e = j + 1;
+            while (e < F && ok[e] == ok[e - 1] + 1) e++;
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(cent_ok.as<uint32_t>() + (size_t)j * K, cent_d.as<uint32_t>() + (size_t)ok[j] * K, (size_t)(e - j) * K * 4,
+                                            hipMemcpyDeviceToDevice, c->stream));
+            j = e;
+        }
+        cent_tail = cent_ok.as<uint32_t>();
+    }
+    std::vector<uint8_t> cent_h;
+    if (c->opt(CNIIC_OPT_FRAME_TREES_HOST, "CNIIC_FRAME_TREES_HOST", 0) != 0) {   // the trees on host threads: they read K x 3 bytes per frame
+        std::vector<uint32_t> words((size_t)F * K);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(words.data(), cent_tail, words.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        cent_h.resize(words.size() * 3);
+        for (size_t k = 0; k < words.size(); k++) { cent_h[3 * k] = (uint8_t)(words[k] >> 16); cent_h[3 * k + 1] = (uint8_t)(words[k] >> 8); cent_h[3 * k + 2] = (uint8_t)words[k]; }
+    }
+    const uint64_t sstride = cc_small_stream_bound((uint64_t)fr[ok[0]]->w * fr[ok[0]]->h, K);   // (largest first)
+    DevBuf scratch;
+    CNIIC_HIP_TRY(c, scratch.alloc(sstride * F + 16));
+    std::vector<uint64_t> lens(F);
+    CNIIC_TRY(frames_tail(c, labels_d.p, false, K, cent_tail, cent_h.data(), fb, scratch.as<uint8_t>(), sstride, lens.data(), nullptr, false, K));
+    // ---- every stream to its own place, unless it is longer than the caller's room
+    const bool out_dev = is_device_ptr(fr[ok[0]]->out);
+    std::vector<CcSmallPlace> pl;
+    for (uint32_t j = 0; j < F; j++) {
+        VarFrame &f = *fr[ok[j]];
+        f.len = lens[j];
+        if (f.len > f.cap) {
+            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
+            f.msg = c->err;
+            continue;
+        }
+        pl.push_back(CcSmallPlace{sstride * j, f.out, f.len});
+    }
+    if (pl.empty()) return CNIIC_OK;
+    if (out_dev) {
+        DevBuf pl_d;
+        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
+        ScopedKernelTimer t(c, "cc_small_place");
+        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
+        t.stop(1);
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<uint8_t> host(sstride * F);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
+    }
+    return CNIIC_OK;
+}
+
+int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n) {
+    const uint64_t seed = (opts && opts->seed) ? opts->seed : kDefaultSeed, max_iters = opts ? opts->max_iters : 0;
+    // the tail's scratch stays below 2 GiB: the frames in chunks, each under the stride of its first (largest) frame
+    for (uint32_t at = 0; at < n;) {
+        const uint64_t room = (2ull << 30) / cc_small_stream_bound((uint64_t)fr[at]->w * fr[at]->h, K);
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
+        CNIIC_TRY(cc_small_chunk(c, K, seed, max_iters, fr + at, cnt));
+        at += cnt;
+    }
+    return CNIIC_OK;
 }
 
 // How well the handle's palette fits a batch of frames: sse_h[f] = the exact sum over frame f's pixels of the squared distance to the pixel's entry

@@ -33,6 +33,23 @@ int encode_hilbert_rle(Ctx *c, double d, const uint8_t *rgb_d, uint32_t w, uint3
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h);
 
+// ---- a frame of cniic_codec_encode_batch_var / cniic_codec_measure_batch (capi.cpp encode_frames)
+struct VarFrame {
+    const uint8_t *src = nullptr;   // the image (host or device memory, any alignment)
+    uint32_t w = 0, h = 0;
+    uint8_t *out = nullptr;         // where its stream goes, cap bytes at most
+    uint64_t cap = 0;
+    uint64_t len = 0;               // results: what cniic_codec_encode_opts answers for this image alone
+    int32_t rc = CNIIC_OK;
+    cniic_kmeans_stats st{};
+    std::string msg;
+};
+// cluster-colors(K), 1 <= K <= 256, of n > 0 small frames (1 .. kCcSmallMaxPx pixels each, DEVICE images, largest first; all destinations
+// host or all device memory) in one set of launches whatever n: k_cc_small, one workgroup per frame with a palette of its own, then
+// frames_tail with a palette per frame into scratch, then every stream to its own destination.  Fills in rc, len, st and msg of every
+// frame as cniic_codec_encode_opts would for that frame alone; what it returns is the status of the machinery, not of a frame.
+int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
+
 // ---- output assembly
 // The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in
 // the caller's buffer when that is 4-byte aligned device memory, otherwise in a staging buffer

@@ -900,12 +900,22 @@ __device__ __forceinline__ uint32_t frame_of_block(const FrameVar *__restrict__ 
 // the Huffman codes and stream headers of a batch's frames on the GPU (K <= 256; k_huff.hip k_frame_trees)
 int frame_trees(Ctx *c, const uint32_t *cnt_d, const uint32_t *cent_d, uint32_t frames, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, uint64_t stride,
                 uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d,
-                const FrameVar *fr_d = nullptr /* frames of any sizes: w, h per frame from the table */);
+                const FrameVar *fr_d = nullptr /* frames of any sizes: w, h per frame from the table */,
+                uint32_t pal_stride = 0 /* 0: the K entries at cent_d for every frame; K: frame f's own at cent_d + f K */);
 int frame_labels_align_var(Ctx *c, const void *src_d, void *dst_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide);
 int frame_label_hist_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t hblocks, bool wide, uint32_t K, uint32_t *out_d /* u32[frames][K] */);
 int huff_pack_labels_frames_var(Ctx *c, const void *labs_d, const FrameVar *fr_d, uint32_t frames, uint32_t chunks, bool wide, uint32_t K, const uint8_t *clen_d,
                                 const uint64_t *ccode_d, uint8_t *out_d, uint64_t stride, const uint64_t *bit_base_h, uint64_t *totals_h, const uint64_t *bit_base_d = nullptr);
 int sum_u32_dev(Ctx *c, const uint32_t *v_d, uint64_t n, uint64_t *out_d);   // *out_d = the sum of n u32
+// ---- k_cc_small.hip: cluster-colors(K <= 256) of small frames, one workgroup per frame (cc_small.hpp has the arithmetic and the limits).
+// A row per frame: its pixels (device memory, any alignment) and where its u8 labels go in labels_d (a multiple of 16; room for the
+// pixel count rounded up to 16).  The frame's K centroids land at cent_d + row * K as 0xRRGGBB words.
+struct CcSmallRow { const uint8_t *src; uint64_t lab_base; uint32_t w, h; };
+struct CcSmallResult { uint32_t U, iterations, moved_last, reseeds, active, status; };   // status 1: U / K == 0, nothing else was computed
+struct CcSmallPlace { uint64_t src_off; uint8_t *dst; uint64_t len; };                   // a stream in the tail's scratch, and where it belongs
+int cc_small_run(Ctx *c, const CcSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t K, uint64_t seed, uint64_t max_iters,
+                 uint8_t *labels_d, uint32_t *cent_d, CcSmallResult *res_d);
+int cc_small_place(Ctx *c, const CcSmallPlace *pl_d, uint32_t n, const uint8_t *scratch_d /* 16-byte aligned offsets, 16 spare bytes behind */);
 // ---- k_palette.hip: the colour -> label table of a frozen palette (every colour's nearest entry, lowest index among equals).  table_d: 2^24
 // labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
 // down the plain route; plain_cells_d (optional): a zeroed counter of such cells

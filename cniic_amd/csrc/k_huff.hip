@@ -616,7 +616,8 @@ __global__ __launch_bounds__(256) void k_frame_trees(const uint32_t *__restrict_
                                                      uint8_t *__restrict__ clen /* [F][K] */, unsigned long long *__restrict__ ccode /* [F][K] */,
                                                      unsigned long long *__restrict__ bit_base /* [F] */, unsigned long long *__restrict__ nbits /* [F] */,
                                                      unsigned long long *__restrict__ lens /* [F] */, uint32_t *__restrict__ err,
-                                                     const FrameVar *__restrict__ fr = nullptr /* frames of any sizes: frame f is fr[f].w x fr[f].h */) {
+                                                     const FrameVar *__restrict__ fr = nullptr /* frames of any sizes: frame f is fr[f].w x fr[f].h */,
+                                                     uint32_t pal_stride = 0 /* 0: one palette; K: frame f's entries at cent + f K */) {
     __shared__ unsigned long long s_sort[256];
     __shared__ uint32_t s_key[256], s_cnt[256], s_bfreq[256];
     __shared__ unsigned short s_symk[256], s_left[256], s_right[256], s_parent[512], s_size[512];
@@ -626,6 +627,7 @@ __global__ __launch_bounds__(256) void k_frame_trees(const uint32_t *__restrict_
     const uint32_t tid = threadIdx.x, f = blockIdx.x;
     const uint32_t *fc = cnt + (size_t)f * K;
     const uint32_t myc = tid < K ? fc[tid] : 0u;
+    cent += (size_t)f * pal_stride;
     // ---- symbols: (colour, cluster) sorted; heads of runs of one colour are the symbols
     s_sort[tid] = myc ? (((unsigned long long)(cent[tid] & 0xffffffu) << 32) | tid) : ~0ull;
     s_cnt[tid] = 0;
@@ -723,11 +725,11 @@ __global__ __launch_bounds__(256) void k_frame_trees(const uint32_t *__restrict_
 }
 
 int frame_trees(Ctx *c, const uint32_t *cnt_d, const uint32_t *cent_d, uint32_t frames, uint32_t K, uint32_t w, uint32_t h, uint8_t *out_d, uint64_t stride,
-                uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d, const FrameVar *fr_d) {
+                uint8_t *clen_d, uint64_t *ccode_d, uint64_t *bit_base_d, uint64_t *nbits_d, uint64_t *lens_d, uint32_t *err_d, const FrameVar *fr_d, uint32_t pal_stride) {
     if (K > 256) return c->fail(CNIIC_ERR_BAD_ARG, "frame_trees: K <= 256");
     hipLaunchKernelGGL(k_frame_trees, dim3(frames), dim3(256), 0, c->stream, cnt_d, cent_d, K, w, h, out_d, stride, clen_d,
                        reinterpret_cast<unsigned long long *>(ccode_d), reinterpret_cast<unsigned long long *>(bit_base_d),
-                       reinterpret_cast<unsigned long long *>(nbits_d), reinterpret_cast<unsigned long long *>(lens_d), err_d, fr_d);
+                       reinterpret_cast<unsigned long long *>(nbits_d), reinterpret_cast<unsigned long long *>(lens_d), err_d, fr_d, pal_stride);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }

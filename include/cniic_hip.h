@@ -532,7 +532,18 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
  * (the pixel partition of cluster-colors, the tile reads of `delta`).  With CNIIC_OPT_STAGE_TIMERS on, cniic_last_kernel_time answers
  * with the SUMS over all frames, and knows two more names (launches only, no duration): "cc_pixel_partition" = cluster-colors encodes
  * that took the pixel partition, "batch_stage" = frames that were copied to aligned scratch.  rcs / stats may be NULL; the call returns
- * the first failure (lowest f) with that frame's message in cniic_last_error; frames == 0 returns CNIIC_OK. */
+ * the first failure (lowest f) with that frame's message in cniic_last_error; frames == 0 returns CNIIC_OK.
+ *
+ * SMALL cluster-colors frames take a route of their own, here and in cniic_codec_measure_batch: with the expression cluster-colors(K),
+ * 1 <= K <= 256, DEVICE images and opts NULL or opts->flags == 0 (seed and max_iters are honoured), every frame of 1 .. 16384 pixels is
+ * coded on ONE workgroup (its distinct colours, their counts and labels and the K centroids in the CU's LDS: sort, exact brute-force
+ * Lloyd, every pixel's label), all such frames of the call in one set of launches whatever their number, each with its own palette as
+ * the reference has it.  Larger frames, host images, any CNIIC_KM_* flag, K = 0 or K > 256 and every other codec go to the worker
+ * contexts as above; cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took shows in no output
+ * byte, status or message.  Stage timers: "cc_small_batch" = the duration of that kernel, with launches = the frames that took the route;
+ * "cc_small_place" = the copy of the finished streams to out + f * stride; the tail between them keeps the names "frames_var_hist",
+ * "frames_var_trees" and "frames_var_pack".  stats[f].pair_evals counts what the route that ran evaluated -- on this route
+ * iterations x distinct colours x K, on the workers what their pruned search evaluated; the other four fields do not depend on the route. */
 int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
                                      const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
                                      int32_t *rcs, cniic_kmeans_stats *stats);
