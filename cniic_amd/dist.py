@@ -46,7 +46,7 @@ class HipBackend:
 
     def hist_dense(self, img, npx):
         t = self.torch.empty(1 << 24, dtype=self.torch.int32, device=self.dev)
-        self.ctx._check(self.L.cniic_hist_rgb24_dense(self.ctx.h, C.c_void_p(img.data_ptr()), C.c_uint64(npx), C.c_void_p(t.data_ptr())))
+        self.ctx._check(self.L.cniic_hist_rgb24_dense(self.ctx.h, img.data_ptr(), npx, t.data_ptr()))
         return t
 
     def new_partials(self, K):
@@ -56,15 +56,15 @@ class HipBackend:
     def occupancy(self, table):
         """one nibble per colour, 1 where this image has it (u32[2^21]); summed over the ranks by an all-reduce"""
         occ = self.torch.empty(1 << 21, dtype=self.torch.int32, device=self.dev)
-        self.ctx._check(self.L.cniic_occupancy_pack(self.ctx.h, C.c_void_p(table.data_ptr()), C.c_void_p(occ.data_ptr())))
+        self.ctx._check(self.L.cniic_occupancy_pack(self.ctx.h, table.data_ptr(), occ.data_ptr()))
         return occ
 
     def cc_create_local(self, table, occ, K, partials, max_iters=0, seed=0, flags=0):
         """K-means state over this rank's colours (table: its counts, overwritten), placed in the list of all occupied colours"""
         h = C.c_void_p()
         o = _lib.KmOpts(seed, max_iters, flags, 0)
-        self.ctx._check(self.L.cniic_cc_create_local(self.ctx.h, C.c_void_p(table.data_ptr()), C.c_void_p(occ.data_ptr()), C.c_uint32(K),
-                                                     C.byref(o), C.c_void_p(partials.data_ptr()), C.byref(h)))
+        self.ctx._check(self.L.cniic_cc_create_local(self.ctx.h, table.data_ptr(), occ.data_ptr(), K,
+                                                     C.byref(o), partials.data_ptr(), C.byref(h)))
         return h
 
     # ---- large images: the pixel partition instead of the dense table (same session handle afterwards)
@@ -73,17 +73,17 @@ class HipBackend:
         if npx < int(os.environ.get("CNIIC_SP_MIN_PIXELS", 1 << 20)) or img.data_ptr() % 16:  # (the library's own threshold and knob)
             return None
         h = C.c_void_p()
-        self.ctx._check(self.L.cniic_cc_image_begin(self.ctx.h, C.c_void_p(img.data_ptr()), C.c_uint64(npx), C.byref(h)))
+        self.ctx._check(self.L.cniic_cc_image_begin(self.ctx.h, img.data_ptr(), npx, C.byref(h)))
         return h
 
     def image_occupancy(self, h):
         occ = self.torch.empty(1 << 21, dtype=self.torch.int32, device=self.dev)
-        self.ctx._check(self.L.cniic_cc_image_occupancy(h, C.c_void_p(occ.data_ptr())))
+        self.ctx._check(self.L.cniic_cc_image_occupancy(h, occ.data_ptr()))
         return occ
 
     def image_create(self, h, occ, K, partials, max_iters=0, seed=0, flags=0):
         o = _lib.KmOpts(seed, max_iters, flags, 0)
-        self.ctx._check(self.L.cniic_cc_image_create(h, C.c_void_p(occ.data_ptr()), C.c_uint32(K), C.byref(o), C.c_void_p(partials.data_ptr())))
+        self.ctx._check(self.L.cniic_cc_image_create(h, occ.data_ptr(), K, C.byref(o), partials.data_ptr()))
 
     def set_centroids(self, h, init, allow=()):
         """cniic_cc_set_centroids: the session's K-means starts from init ((K, 3) uint8, host) instead of the chunk heads; before the
@@ -115,40 +115,37 @@ class HipBackend:
         U = int(self.L.cniic_cc_unique(h))
         dt = self.torch.uint8 if self.L.cniic_cc_label_bytes(h) == 1 else self.torch.int16
         t = self.torch.empty(U, dtype=dt, device=self.dev)
-        self.ctx._check(self.L.cniic_cc_export_labels(h, C.c_void_p(t.data_ptr())))
+        self.ctx._check(self.L.cniic_cc_export_labels(h, t.data_ptr()))
         return t
 
     def import_labels(self, h, t):
-        self.ctx._check(self.L.cniic_cc_import_labels(h, C.c_void_p(t.data_ptr())))
+        self.ctx._check(self.L.cniic_cc_import_labels(h, t.data_ptr()))
 
     def finish(self, h, img, w, hh, local_table, out):
         ln = C.c_uint64(0)
         st = _lib.KmStats()
         cap = out.numel()
-        lt = C.c_void_p(local_table.data_ptr()) if local_table is not None else None
-        self.ctx._check(self.L.cniic_cc_finish(h, C.c_void_p(img.data_ptr()), C.c_uint32(w), C.c_uint32(hh), lt,
-                                               C.c_void_p(out.data_ptr()), C.c_uint64(cap), C.byref(ln), C.byref(st)))
+        lt = local_table.data_ptr() if local_table is not None else None
+        self.ctx._check(self.L.cniic_cc_finish(h, img.data_ptr(), w, hh, lt,
+                                               out.data_ptr(), cap, C.byref(ln), C.byref(st)))
         return ln.value, st.as_dict()
 
     def finish_frames(self, h, frames, w, hh, F, out, stride):
         """F streams, frame f's at out[f * stride:], lengths as a list"""
         lens = (C.c_uint64 * F)()
         st = _lib.KmStats()
-        self.ctx._check(self.L.cniic_cc_finish_frames(h, C.c_void_p(frames.data_ptr()), C.c_uint32(w), C.c_uint32(hh), C.c_uint32(F),
-                                                      C.c_void_p(out.data_ptr()), C.c_uint64(stride), lens, C.byref(st)))
+        self.ctx._check(self.L.cniic_cc_finish_frames(h, frames.data_ptr(), w, hh, F,
+                                                      out.data_ptr(), stride, lens, C.byref(st)))
         return list(lens), st.as_dict()
 
     def finish_frames_var(self, h, frames_flat, ws, hs, out, stride, allow=()):
         """cniic_cc_finish_frames_var: len(ws) frames of different sizes, back to back in frames_flat (device tensor, numpy array or
         address), frame f's stream at out[f * stride:] -> (list of lengths, stats); with a status in `allow`: (status, lengths, stats)"""
         F = len(ws)
-        n = max(F, 1)
-        w = (C.c_uint32 * n)(*[int(x) for x in ws])
-        hh = (C.c_uint32 * n)(*[int(x) for x in hs])
-        lens = (C.c_uint64 * n)()
+        lens = (C.c_uint64 * max(F, 1))()
         st = _lib.KmStats()
-        rc = self.ctx._check(self.L.cniic_cc_finish_frames_var(h, _lib._ptr(frames_flat), w, hh, C.c_uint32(F), _lib._ptr(out), C.c_uint64(stride), lens,
-                                                               C.byref(st)), allow)
+        rc = self.ctx._check(self.L.cniic_cc_finish_frames_var(h, _lib._ptr(frames_flat), _lib._array(C.c_uint32, ws, F), _lib._array(C.c_uint32, hs, F),
+                                                               F, _lib._ptr(out), stride, lens, C.byref(st)), allow)
         if allow:
             return rc, [int(lens[f]) for f in range(F)], st.as_dict()
         return [int(lens[f]) for f in range(F)], st.as_dict()
@@ -185,7 +182,7 @@ class HipBackend:
             return None
         idb = (C.c_uint8 * 128)(*raw[1:])
         h = C.c_void_p()
-        rc = self.L.cniic_comm_create(self.ctx.h, idb, C.c_uint32(rank), C.c_uint32(world), C.byref(h))
+        rc = self.L.cniic_comm_create(self.ctx.h, idb, rank, world, C.byref(h))
         def agreed(mine):  # all ranks or none
             if dist is None or world == 1:
                 return mine
@@ -201,7 +198,7 @@ class HipBackend:
         # known-answer all-reduce before the K-means loop depends on it: rank r gives r + 1 in every word
         probe = torch.full((5 * 256 + 2,), rank + 1, dtype=torch.int64, device=self.dev)
         torch.cuda.synchronize(self.dev)  # (filled on torch's stream, reduced on the context's)
-        rc = self.L.cniic_comm_all_reduce(h, C.c_void_p(probe.data_ptr()), C.c_uint64(probe.numel()), C.c_int32(8))
+        rc = self.L.cniic_comm_all_reduce(h, probe.data_ptr(), probe.numel(), 8)
         torch.cuda.synchronize(self.dev)
         good = 1 if rc == _lib.OK and bool((probe == world * (world + 1) // 2).all()) else 0
         if not agreed(good):
@@ -225,7 +222,7 @@ class HipBackend:
 
         hb = (C.c_uint8 * 64)()
         h = C.c_void_p()
-        rc = self.L.cniic_comm_create_mailbox(self.ctx.h, C.c_uint32(rank), C.c_uint32(world), C.c_uint64(max_bytes), hb, C.byref(h))
+        rc = self.L.cniic_comm_create_mailbox(self.ctx.h, rank, world, max_bytes, hb, C.byref(h))
         mine = 1 if rc == _lib.OK else 0
         if not agreed(mine):
             if mine:
@@ -245,7 +242,7 @@ class HipBackend:
             return None
         probe = torch.full((5 * 256 + 2,), rank + 1, dtype=torch.int64, device=self.dev)
         torch.cuda.synchronize(self.dev)
-        rc = self.L.cniic_comm_all_reduce(h, C.c_void_p(probe.data_ptr()), C.c_uint64(probe.numel()), C.c_int32(8))
+        rc = self.L.cniic_comm_all_reduce(h, probe.data_ptr(), probe.numel(), 8)
         torch.cuda.synchronize(self.dev)
         good = 1 if rc == _lib.OK and bool((probe == world * (world + 1) // 2).all()) else 0
         if not agreed(good):
@@ -280,7 +277,7 @@ class HipBackend:
 
         self._host_sum_cb = _lib.HOST_SUM_FN(host_sum)   # kept alive as long as the backend
         h = C.c_void_p()
-        self.ctx._check(self.L.cniic_comm_create_host(self.ctx.h, C.c_uint32(rank), C.c_uint32(world), self._host_sum_cb, None, C.byref(h)))
+        self.ctx._check(self.L.cniic_comm_create_host(self.ctx.h, rank, world, self._host_sum_cb, None, C.byref(h)))
         return h
 
     def comm_destroy(self, comm):
@@ -288,7 +285,7 @@ class HipBackend:
             self.L.cniic_comm_destroy(comm)
 
     def comm_all_reduce(self, comm, t):
-        self.ctx._check(self.L.cniic_comm_all_reduce(comm, C.c_void_p(t.data_ptr()), C.c_uint64(t.numel()), C.c_int32(t.element_size())))
+        self.ctx._check(self.L.cniic_comm_all_reduce(comm, t.data_ptr(), t.numel(), t.element_size()))
 
     def run(self, h, comm):
         st = _lib.KmStats()

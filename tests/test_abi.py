@@ -26,6 +26,83 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SYMBOLS) == decl
 
 
+def declared_prototypes():
+    """include/cniic_hip.h -> {name: (restype, [argtypes])} by the fixed mapping that cniic_amd/_lib.py states above its PROTOTYPES"""
+    import ctypes as C
+
+    from cniic_amd import _lib
+    text = open(os.path.join(ROOT, "include", "cniic_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = "\n".join(line for line in text.split("\n") if not line.lstrip().startswith("#"))
+    scalar = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "double": C.c_double}
+    ret = dict(scalar, void=None)
+
+    def param(p):
+        if p.startswith("cniic_host_sum_fn "):
+            return _lib.HOST_SUM_FN
+        if re.match(r"const char ?\*", p):
+            return C.c_char_p
+        if "*" in p or "[" in p:
+            return C.c_void_p
+        return scalar[p.split(" ")[0]]   # (KeyError: a parameter kind the mapping does not know)
+
+    protos = {}
+    for m in re.finditer(r"\b(void|int32_t|uint32_t|uint64_t|double|const\s+char\s*\*)\s*(cniic_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        r, name, params = m.groups()
+        params = [re.sub(r"\s+", " ", p).strip() for p in params.split(",")]
+        protos[name] = (C.c_char_p if "char" in r else ret[r], [] if params == ["void"] else [param(p) for p in params])
+    return protos
+
+
+def test_prototype_table_matches_header():
+    """every declaration of the header has exactly its restype and argtypes in _lib.PROTOTYPES, and the table names nothing else"""
+    from cniic_amd import _lib
+    decl = declared_prototypes()
+    assert sorted(decl) == declared_symbols()       # the parser found every function the name check knows
+    assert len(decl) >= 111
+    for name, (restype, argtypes) in decl.items():
+        assert name in _lib.PROTOTYPES, name
+        assert _lib.PROTOTYPES[name][0] is restype, name
+        assert list(_lib.PROTOTYPES[name][1]) == argtypes, name
+    assert not set(_lib.PROTOTYPES) - set(decl)
+    assert _lib.SYMBOLS == list(_lib.PROTOTYPES)
+
+
+def test_loaded_library_is_fully_declared():
+    from cniic_amd import _lib
+    L = _lib.lib()
+    decl = declared_prototypes()
+    for name in _lib.SYMBOLS:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, name
+        assert len(fn.argtypes) == len(decl[name][1]), name
+        assert fn.restype is _lib.PROTOTYPES[name][0], name
+
+
+def test_bare_int_arrives_in_full_width():
+    """a uint64_t given as a bare Python int: without a prototype ctypes passes 32 bits of it, and this capacity would arrive as 0"""
+    import ctypes as C
+
+    from cniic_amd import _lib
+    buf = C.create_string_buffer(64)
+    assert _lib.lib().cniic_codec_name(b"hufman", buf, 1 << 32) == _lib.OK      # (host only; writes 7 bytes)
+    assert buf.value == b"Hufman"
+
+
+def test_ptr_of_bytearray_is_its_own_buffer():
+    import ctypes as C
+
+    from cniic_amd import _lib
+    ba = bytearray(b"0123456789abcdef")
+    assert _lib._ptr(ba).value == C.addressof((C.c_char * len(ba)).from_buffer(ba))
+    C.memmove(_lib._ptr(ba).value, b"X", 1)
+    assert ba[0] == ord("X") and bytes(ba[1:]) == b"123456789abcdef"
+    assert isinstance(_lib._ptr(bytearray()), C.c_void_p)    # empty: still a pointer (which may be null), no exception
+    b = b"0123456789abcdef"
+    assert C.string_at(_lib._ptr(b).value, len(b)) == b      # bytes: the caller's own object, as before
+
+
 def test_release_library_has_no_test_hooks():
     """CNIIC_TEST_* / CNIIC_DBG_* and the other route-forcing knobs are compiled into the testing build only.
     The release library exports the same symbols, says it is the release build, and none of those names is in its binary."""
