@@ -15,6 +15,7 @@
 #include "huff_host.hpp"
 #include "surf_index.hpp"
 #include "cc_small.hpp"
+#include "delta_small.hpp"
 
 using namespace cniic;
 
@@ -1313,6 +1314,14 @@ static uint64_t cc_small_max_px() {
     if (const char *e = test_env("CNIIC_TEST_CC_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kCcSmallMaxPx);
     return kCcSmallMaxPx;
 }
+// Small `delta` frames in device memory (1 .. kDeltaSmallMaxPx pixels) likewise: delta_small_encode (codec.cpp), a workgroup per frame from
+// the pixels to the finished stream ("delta_small_batch": k_delta_small, launches = the frames that took the route; "delta_small_place").
+// The testing library can switch it off (CNIIC_TEST_DELTA_SMALL_OFF=1) or lower its bound (CNIIC_TEST_DELTA_SMALL_MAX_PX).
+static uint64_t delta_small_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_OFF")) if (atoi(e) != 0) return 0;
+    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallMaxPx);
+    return kDeltaSmallMaxPx;
+}
 
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
     const uint32_t n = (uint32_t)fr.size();
@@ -1340,6 +1349,27 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
             std::map<std::string, KernelTime> mine;
             mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
             const int32_t rc = cc_small_encode(c, d.arg, opts, small.data(), (uint32_t)small.size());
+            mine.swap(c->ktimes);
+            CNIIC_TRY(rc);
+            if (c->timers) kt.swap(mine);
+            order.swap(rest);
+        }
+    }
+    // ---- the small `delta` frames, together: not with the big encoder's route forced, and not a frame whose size has an injected scan
+    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_DELTA && c->opt(CNIIC_OPT_DELTA_ROUTE, "CNIIC_DELTA_ROUTE", 0) != 32) {
+        const uint64_t max_px = delta_small_max_px();
+        std::vector<VarFrame *> small;
+        std::vector<uint32_t> rest;
+        for (uint32_t j = 0; j < n; j++) {
+            const VarFrame &f = fr[order[j]];
+            const uint64_t px = (uint64_t)f.w * f.h;
+            const bool own_scan = c->scan_xy.p && c->scan_w == f.w && c->scan_h == f.h;
+            if (px >= 1 && px <= max_px && !own_scan) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
+        }
+        if (!small.empty()) {
+            std::map<std::string, KernelTime> mine;
+            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
+            const int32_t rc = delta_small_encode(c, small.data(), (uint32_t)small.size());
             mine.swap(c->ktimes);
             CNIIC_TRY(rc);
             if (c->timers) kt.swap(mine);

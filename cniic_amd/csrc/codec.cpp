@@ -11,6 +11,7 @@
 //   Zip::Dict       src/codec/zipc.rs         `zip(dict)`: the dictionary coder over the serialised image (zipdict.cpp, k_zipdict.hip)
 #include "codec.hpp"
 #include "cc_small.hpp"
+#include "delta_small.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -1149,6 +1150,73 @@ int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame 
         const uint64_t room = (2ull << 30) / cc_small_stream_bound((uint64_t)fr[at]->w * fr[at]->h, K);
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
         CNIIC_TRY(cc_small_chunk(c, K, seed, max_iters, fr + at, cnt));
+        at += cnt;
+    }
+    return CNIIC_OK;
+}
+
+// ---- small `delta` frames of a batch call, all at once (codec.hpp; k_delta_small.hip)
+// what a frame of the chunk whose largest frame has npx pixels takes in HBM: its stream's slot and the kernel's three arrays of a word per pixel
+static uint64_t delta_small_tmp_px(uint64_t npx) { return (npx + 3) & ~3ull; }
+static uint64_t delta_small_frame_bytes(uint64_t npx) { return ds_stride(npx) + 12 * delta_small_tmp_px(npx); }
+
+static int delta_small_chunk(Ctx *c, VarFrame *const *fr, uint32_t n) {
+    const uint64_t max_px = (uint64_t)fr[0]->w * fr[0]->h;   // (largest first)
+    const uint64_t sstride = ds_stride(max_px), tmp_px = delta_small_tmp_px(max_px);
+    std::vector<DeltaSmallRow> rows(n);
+    for (uint32_t i = 0; i < n; i++) rows[i] = DeltaSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
+    DevBuf rows_d, res_d, scratch, tmp;
+    CNIIC_HIP_TRY(c, rows_d.alloc((uint64_t)n * sizeof(DeltaSmallRow)));
+    CNIIC_HIP_TRY(c, res_d.alloc((uint64_t)n * sizeof(DeltaSmallResult)));
+    CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
+    CNIIC_HIP_TRY(c, tmp.alloc(12 * tmp_px * n));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(DeltaSmallRow), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedKernelTimer t(c, "delta_small_batch");
+        CNIIC_TRY(delta_small_run(c, rows_d.as<DeltaSmallRow>(), n, (uint32_t)max_px, scratch.as<uint8_t>(), sstride, tmp.as<uint32_t>(), tmp_px, res_d.as<DeltaSmallResult>()));
+        t.stop(n);
+    }
+    std::vector<DeltaSmallResult> res(n);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, (size_t)n * sizeof(DeltaSmallResult), hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // ---- every stream to its own place, unless it is longer than the caller's room
+    const bool out_dev = is_device_ptr(fr[0]->out);
+    std::vector<CcSmallPlace> pl;
+    for (uint32_t i = 0; i < n; i++) {
+        VarFrame &f = *fr[i];
+        f.len = res[i].len;
+        if (f.len < 15 || f.len > sstride) return c->fail(CNIIC_ERR_HIP, "delta_small: a stream of %llu bytes in a slot of %llu", (unsigned long long)f.len, (unsigned long long)sstride);
+        if (f.len > f.cap) {
+            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
+            f.msg = c->err;
+            continue;
+        }
+        pl.push_back(CcSmallPlace{sstride * i, f.out, f.len});
+    }
+    if (pl.empty()) return CNIIC_OK;
+    if (out_dev) {
+        DevBuf pl_d;
+        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
+        ScopedKernelTimer t(c, "delta_small_place");
+        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
+        t.stop(1);
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<uint8_t> host(sstride * n);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
+    }
+    return CNIIC_OK;
+}
+
+int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
+    // the scratch stays below 2 GiB: the frames in chunks, each under the slot of its first (largest) frame
+    for (uint32_t at = 0; at < n;) {
+        const uint64_t room = (2ull << 30) / delta_small_frame_bytes((uint64_t)fr[at]->w * fr[at]->h);
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
+        CNIIC_TRY(delta_small_chunk(c, fr + at, cnt));
         at += cnt;
     }
     return CNIIC_OK;

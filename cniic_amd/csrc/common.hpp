@@ -916,6 +916,13 @@ struct CcSmallPlace { uint64_t src_off; uint8_t *dst; uint64_t len; };          
 int cc_small_run(Ctx *c, const CcSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t K, uint64_t seed, uint64_t max_iters,
                  uint8_t *labels_d, uint32_t *cent_d, CcSmallResult *res_d);
 int cc_small_place(Ctx *c, const CcSmallPlace *pl_d, uint32_t n, const uint8_t *scratch_d /* 16-byte aligned offsets, 16 spare bytes behind */);
+// ---- k_delta_small.hip: `delta` of small frames, one workgroup per frame (delta_small.hpp has the arithmetic and the limits).  A row per
+// frame: its pixels (device memory, any alignment).  Frame f's finished stream lands at scratch_d + f * sstride (sstride >= ds_stride of
+// the largest frame, a multiple of 16), its length in res_d[f]; tmp_d holds 3 * tmp_px words per frame (tmp_px >= the largest frame's pixels).
+struct DeltaSmallRow { const uint8_t *src; uint32_t w, h; };
+struct DeltaSmallResult { uint32_t U, len; };   // distinct symbols, bytes of the stream
+int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint8_t *scratch_d, uint64_t sstride,
+                    uint32_t *tmp_d, uint64_t tmp_px, DeltaSmallResult *res_d);
 // ---- k_palette.hip: the colour -> label table of a frozen palette (every colour's nearest entry, lowest index among equals).  table_d: 2^24
 // labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
 // down the plain route; plain_cells_d (optional): a zeroed counter of such cells

@@ -543,7 +543,16 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
  * byte, status or message.  Stage timers: "cc_small_batch" = the duration of that kernel, with launches = the frames that took the route;
  * "cc_small_place" = the copy of the finished streams to out + f * stride; the tail between them keeps the names "frames_var_hist",
  * "frames_var_trees" and "frames_var_pack".  stats[f].pair_evals counts what the route that ran evaluated -- on this route
- * iterations x distinct colours x K, on the workers what their pruned search evaluated; the other four fields do not depend on the route. */
+ * iterations x distinct colours x K, on the workers what their pruned search evaluated; the other four fields do not depend on the route.
+ *
+ * SMALL `delta` frames likewise, here and in cniic_codec_measure_batch: with the expression `delta`, DEVICE images and CNIIC_OPT_DELTA_ROUTE
+ * not 32, every frame of 1 .. 16384 pixels whose size has no injected scan (cniic_ctx_set_scan) is coded on ONE workgroup from its pixels
+ * to its finished stream (symbols along the scan, sort, the Huffman tree, header and payload; no host round trip), all such frames of the
+ * call in one launch whatever their number.  Larger frames, host images, a frame of exactly the injected scan's size and a forced 32-bit
+ * route go to the worker contexts as above; cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took
+ * shows in no output byte, status or message; stats[f] stays zero as the single call leaves it.  Stage timers: "delta_small_batch" = the
+ * duration of that kernel, with launches = the frames that took the route; "delta_small_place" = the copy of the finished streams to
+ * out + f * stride. */
 int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
                                      const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
                                      int32_t *rcs, cniic_kmeans_stats *stats);
