@@ -4,6 +4,12 @@
 // key / order of making), codes by recursion from the root, the trie written in pre-order by recursion.  Tree shape, code lengths, codes,
 // header bytes and total length must agree.
 // Build: c++ -O2 -std=c++17 -I cniic_amd/csrc tests/delta_small_check.cpp.  Prints "ok <part>: ..." per part; exit status 1 on a mismatch.
+//
+// Second mode: delta_small_check --keys FILE W H [OUT] reads W * H little-endian u32 keys by scan position from FILE, runs the scalar
+// encoder above on them (not the restatement) and prints the stream's length and CRC-32 (OUT, if given, receives the stream), then what
+// the merge did -- per queue the runs of pairs that were full (64), cut by the weight test, or ended by the queue; a leaf run of one pair
+// before any branch exists is "single" -- the general steps by the order of their two picks, the longest code, and how many of the
+// kernel's 1024 threads write payload bits that end exactly on a 32-bit word.  tests/test_delta_small_edges_cpu.py reads these lines.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +40,15 @@ struct Encoded {
     bool operator==(const Encoded &o) const { return left == o.left && right == o.right && len == o.len && code == o.code && bytes == o.bytes; }
 };
 
+// what the merge and the payload phase did on one frame (the second mode prints it)
+struct MergeStats {
+    uint32_t leaf_full = 0, leaf_cut = 0, leaf_queue = 0, leaf_single = 0;   // runs of leaf pairs by what ended them
+    uint32_t branch_full = 0, branch_cut = 0, branch_queue = 0;
+    uint32_t general[2][2] = {{0, 0}, {0, 0}};                               // [first pick][second pick], 0 = leaf, 1 = branch
+    uint32_t longest_leaf_run = 0, longest_branch_run = 0;
+    uint32_t threads_with_bits = 0, word_ends = 0, most_thread_bits = 0;
+};
+
 static void put_bits(std::vector<uint8_t> &o, uint64_t &bitpos, uint32_t code, uint32_t len) {   // MSB first
     for (uint32_t i = 0; i < len; i++, bitpos++) {
         if ((bitpos >> 3) >= o.size()) o.push_back(0);
@@ -42,7 +57,7 @@ static void put_bits(std::vector<uint8_t> &o, uint64_t &bitpos, uint32_t code, u
 }
 
 // ---- the kernel's way, scalar, from the headers' functions.  syms: the keys by position
-static Encoded encode_headers(uint32_t w, uint32_t h, const std::vector<uint32_t> &syms) {
+static Encoded encode_headers(uint32_t w, uint32_t h, const std::vector<uint32_t> &syms, MergeStats *ms = nullptr) {
     Encoded e;
     const uint32_t n = (uint32_t)syms.size();
     std::vector<uint32_t> keys(syms);
@@ -83,6 +98,14 @@ static Encoded encode_headers(uint32_t w, uint32_t h, const std::vector<uint32_t
                 if (!((hb || lane == 0) && i1 < U && ds_leaf_pair(lq[i1], hb, bw))) break;
                 c++;
             }
+            if (c && ms) {
+                const uint32_t i1 = li + 2 * c + 1;   // the pair that ended the run
+                if (c == 64) ms->leaf_full++;
+                else if (!hb) ms->leaf_single++;
+                else if (i1 >= U) ms->leaf_queue++;
+                else ms->leaf_cut++;
+                ms->longest_leaf_run = std::max(ms->longest_leaf_run, c);
+            }
             if (c) {
                 std::vector<uint32_t> a(c), b(c);
                 for (uint32_t lane = 0; lane < c; lane++) { a[lane] = lq[li + 2 * lane]; b[lane] = lq[li + 2 * lane + 1]; }
@@ -105,6 +128,12 @@ static Encoded encode_headers(uint32_t w, uint32_t h, const std::vector<uint32_t
                 if (!(i1 < made && ds_branch_pair(bq[i1], hl, lw))) break;
                 c++;
             }
+            if (c && ms) {
+                if (c == 64) ms->branch_full++;
+                else if (bi + 2 * c + 1 >= made) ms->branch_queue++;
+                else ms->branch_cut++;
+                ms->longest_branch_run = std::max(ms->longest_branch_run, c);
+            }
             if (c) {
                 std::vector<uint32_t> a(c), b(c), na(c), nb(c);
                 for (uint32_t lane = 0; lane < c; lane++) { a[lane] = bq[bi + 2 * lane]; b[lane] = bq[bi + 2 * lane + 1]; na[lane] = nl[bi + 2 * lane]; nb[lane] = nl[bi + 2 * lane + 1]; }
@@ -118,15 +147,16 @@ static Encoded encode_headers(uint32_t w, uint32_t h, const std::vector<uint32_t
                 continue;
             }
         }
-        uint32_t wsum = 0, leaves = 0;
+        uint32_t wsum = 0, leaves = 0, picks[2];
         for (uint32_t k = 0; k < 2; k++) {
             const bool hl = li < U, hb = bi < made;
             const uint32_t lw = hl ? lq[li] : 0u, bw = hb ? bq[bi] : 0u;
             uint32_t node;
-            if (ds_pick_leaf(hl, lw, hb, bw)) { wsum += lw; leaves += 1; lq[li] = (uint16_t)ds_link(made, k); node = li++; }
-            else { wsum += bw; leaves += nl[bi]; bq[bi] = (uint16_t)ds_link(made, k); node = U + bi++; }
+            if (ds_pick_leaf(hl, lw, hb, bw)) { wsum += lw; leaves += 1; lq[li] = (uint16_t)ds_link(made, k); node = li++; picks[k] = 0; }
+            else { wsum += bw; leaves += nl[bi]; bq[bi] = (uint16_t)ds_link(made, k); node = U + bi++; picks[k] = 1; }
             (k ? e.right : e.left)[made] = node;
         }
+        if (ms) ms->general[picks[0]][picks[1]]++;
         bq[made] = (uint16_t)wsum; nl[made] = (uint16_t)leaves;
         made++;
     }
@@ -153,10 +183,18 @@ static Encoded encode_headers(uint32_t w, uint32_t h, const std::vector<uint32_t
     }
     for (uint32_t j = 0; j < nbr; j++) e.bytes[8 + (j == root ? 0u : walk(bq[j], nl[j]).off)] = 1;
     uint64_t bitpos = (uint64_t)e.bytes.size() * 8, bits = 0;
+    const uint32_t per = (n + 1023) / 1024;   // consecutive positions per thread of the kernel's payload phase
+    uint32_t mine = 0;                        // bits of the thread that d belongs to
     for (uint32_t d = 0; d < n; d++) {
         const uint32_t r = (uint32_t)(std::upper_bound(keys.begin(), keys.end(), syms[d]) - keys.begin()) - 1;
         put_bits(e.bytes, bitpos, ds_codeword_code(cw[r]), ds_codeword_len(cw[r]));
         bits += ds_codeword_len(cw[r]);
+        mine += ds_codeword_len(cw[r]);
+        if (ms && ((d + 1) % per == 0 || d + 1 == n)) {
+            if (mine) { ms->threads_with_bits++; ms->word_ends += (bitpos & 31) == 0; }
+            ms->most_thread_bits = std::max(ms->most_thread_bits, mine);
+            mine = 0;
+        }
     }
     if (e.bytes.size() != ds_stream_bytes(U, bits) || e.bytes.size() > ds_stride(n)) { printf("FAIL: %zu bytes, ds_stream_bytes %llu, ds_stride %llu\n", e.bytes.size(), (unsigned long long)ds_stream_bytes(U, bits), (unsigned long long)ds_stride(n)); g_fail = 1; }
     return e;
@@ -244,7 +282,47 @@ static uint32_t check(const char *what, const std::vector<uint32_t> &syms, uint3
     return a.longest;
 }
 
-int main() {
+static uint32_t crc32_of(const std::vector<uint8_t> &v) {   // the CRC-32 of zlib
+    uint32_t c = 0xffffffffu;
+    for (uint8_t b : v) {
+        c ^= b;
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
+    }
+    return ~c;
+}
+
+// the second mode: one frame's keys from a file
+static int keys_mode(int argc, char **argv) {
+    if (argc < 5) { fprintf(stderr, "usage: %s --keys FILE W H [OUT]\n", argv[0]); return 2; }
+    const uint32_t w = (uint32_t)strtoul(argv[3], nullptr, 10), h = (uint32_t)strtoul(argv[4], nullptr, 10);
+    const uint64_t n = (uint64_t)w * h;
+    if (!n || n > kDeltaSmallMaxPx) { fprintf(stderr, "%u x %u is outside the route\n", w, h); return 2; }
+    std::vector<uint8_t> raw(4 * n);
+    FILE *f = fopen(argv[2], "rb");
+    if (!f || fread(raw.data(), 1, raw.size(), f) != raw.size() || fgetc(f) != EOF) { fprintf(stderr, "%s does not hold %llu keys\n", argv[2], (unsigned long long)n); return 2; }
+    fclose(f);
+    std::vector<uint32_t> syms(n);
+    for (uint64_t i = 0; i < n; i++) {
+        syms[i] = (uint32_t)raw[4 * i] | ((uint32_t)raw[4 * i + 1] << 8) | ((uint32_t)raw[4 * i + 2] << 16) | ((uint32_t)raw[4 * i + 3] << 24);
+        if (syms[i] >> 27) { fprintf(stderr, "key %llu is no three 9-bit fields\n", (unsigned long long)i); return 2; }
+    }
+    MergeStats ms;
+    const Encoded e = encode_headers(w, h, syms, &ms);
+    if (argc > 5) {
+        FILE *o = fopen(argv[5], "wb");
+        if (!o || fwrite(e.bytes.data(), 1, e.bytes.size(), o) != e.bytes.size() || fclose(o) != 0) { fprintf(stderr, "cannot write %s\n", argv[5]); return 2; }
+    }
+    printf("stream %zu %08x\n", e.bytes.size(), crc32_of(e.bytes));
+    printf("tree leaves %zu longest %u\n", e.len.size(), e.longest);
+    printf("leaf_runs full %u cut %u queue %u single %u longest %u\n", ms.leaf_full, ms.leaf_cut, ms.leaf_queue, ms.leaf_single, ms.longest_leaf_run);
+    printf("branch_runs full %u cut %u queue %u longest %u\n", ms.branch_full, ms.branch_cut, ms.branch_queue, ms.longest_branch_run);
+    printf("general leaf_leaf %u leaf_branch %u branch_leaf %u branch_branch %u\n", ms.general[0][0], ms.general[0][1], ms.general[1][0], ms.general[1][1]);
+    printf("payload threads %u word_ends %u most_bits %u\n", ms.threads_with_bits, ms.word_ends, ms.most_thread_bits);
+    return g_fail;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "--keys")) return keys_mode(argc, argv);
     {   // random symbol lists: a few to many distinct symbols, skewed and flat
         for (int rep = 0; rep < 60; rep++) {
             const uint32_t n = rep < 4 ? 1 + rnd(8) : 1 + rnd(kDeltaSmallMaxPx), spread = 1 + rnd(rep % 3 ? 40 : 511);

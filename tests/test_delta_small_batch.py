@@ -94,26 +94,43 @@ def singles(key, expr, imgs, scan=None):
     return _SINGLES[key]
 
 
-def batch(ctx, expr, imgs, stride, host_out=False, host_src=False, poison=0):
-    """one cniic_codec_encode_batch_var call with the stage timers on -> (rc, lens, rcs, stats, streams, raw output, routed frames, message)"""
+def output_buffer(nbytes, out_off, host_out, poison):
+    """(buffer, at): a poisoned allocation of 16 + out_off + nbytes + 16 bytes and the index `at` in it whose address is out_off modulo 16
+    (at = out_off where the allocation is 16-byte aligned): the output pointer of a call is buffer[at:]"""
+    import torch
+    total = 16 + out_off + nbytes + 16
+    buf = np.full(total, poison, np.uint8) if host_out else torch.full((total,), poison, dtype=torch.uint8, device=torch.device("cuda", 0))
+    base = buf.ctypes.data if host_out else buf.data_ptr()
+    return buf, (-base) % 16 + out_off
+
+
+def batch(ctx, expr, imgs, stride, host_out=False, host_src=False, poison=0, out_off=None, timer=TIMER):
+    """one cniic_codec_encode_batch_var call with the stage timers on -> (rc, lens, rcs, stats, streams, raw output, routed frames, message).
+    With out_off (0 .. 15) the output pointer is out_off modulo 16 inside a larger poisoned allocation, and the raw output is then
+    (the whole allocation, the index of the output pointer in it)"""
     import torch
     from cniic_amd import _lib
     dev = torch.device("cuda", 0)
     buf, offs, ws, hs = _pack(imgs)
     F = len(imgs)
     src = buf if host_src else torch.from_numpy(buf).to(dev)
-    out = np.full(stride * F, poison, np.uint8) if host_out else torch.full((stride * F,), poison, dtype=torch.uint8, device=dev)
+    if out_off is None:
+        whole, at = (np.full(stride * F, poison, np.uint8) if host_out else torch.full((stride * F,), poison, dtype=torch.uint8, device=dev)), 0
+    else:
+        whole, at = output_buffer(stride * F, out_off, host_out, poison)
+    out = whole[at:]
     torch.cuda.synchronize()
     ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
     try:
         rc, lens, rcs, sts = ctx.encode_batch_var(expr, src, offs, ws, hs, out, stride, allow=FAILURES)
         msg = _last_error(ctx) if rc != 0 else ""
-        launches = ctx.kernel_time(TIMER)[1]
+        launches = ctx.kernel_time(timer)[1]
     finally:
         ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
-    host = out if host_out else out.cpu().numpy()
+    whole = whole if host_out else whole.cpu().numpy()
+    host = whole[at:]
     streams = [host[f * stride:f * stride + lens[f]].tobytes() if rcs[f] == 0 else None for f in range(F)]
-    return rc, lens, rcs, sts, streams, host, launches, msg
+    return rc, lens, rcs, sts, streams, host if out_off is None else (whole, at), launches, msg
 
 
 def check_against_singles(res, want, what):
