@@ -12,6 +12,7 @@
 #include "codec.hpp"
 #include "cc_small.hpp"
 #include "delta_small.hpp"
+#include "delta_small_dec.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -1829,10 +1830,113 @@ static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, 
     return CNIIC_OK;
 }
 
+// ------------------------------------------------------------------ small `delta` frames of a batch (k_delta_small_dec.hip)
+// codec_decode_batch_route has parsed the decoders; what it hands over are the frames of 1 .. kDeltaSmallDecMaxPx pixels whose size has no
+// injected scan and whose decoder has no code longer than kDeltaSmallMaxCodeLen (delta_small.hpp proves that no encoder of so few symbols
+// makes one; a hostile stream that has one is the single decode's).  They are worked through in chunks whose scratch -- the tables of
+// leaves, the rows, the status words, and for a host destination the staged images -- stays below kDeltaSmallDecScratch: per chunk one
+// copy up for the tables and rows (and one for host streams, from the chunk's first frame to its last), ONE launch with a workgroup per
+// frame, one copy down for the status words (and one for a host destination's images, which a memcpy per frame then puts in place), one
+// wait.  A frame the kernel hands back (not settled within its rounds) is left to the caller like everything else not taken.
+// The testing library can switch the route off (CNIIC_TEST_DELTA_SMALL_DEC_OFF=1), lower its bound (CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX) and its
+// settle rounds (CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS), and make the chunks small (CNIIC_TEST_MEASURE_BUDGET, bytes).
+constexpr uint64_t kDeltaSmallDecScratch = 2ull << 30;
+static uint64_t delta_small_dec_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_OFF")) if (atoi(e) != 0) return 0;
+    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecMaxPx);
+    return kDeltaSmallDecMaxPx;
+}
+static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
+                              const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route, const std::vector<std::vector<uint32_t>> &tabs,
+                              const std::vector<uint64_t> &pay, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs, std::vector<std::string> &msgs) {
+    uint32_t max_rounds = kDsdMaxRounds;
+    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS")) max_rounds = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kDsdMaxRounds);
+    uint64_t budget = kDeltaSmallDecScratch;
+    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) budget = std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecScratch);
+    auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
+    auto scratch_of = [&](uint32_t f) { return tabs[f].size() * 4 + sizeof(DeltaSmallDecRow) + 4 + (dst_dev ? 0 : img_room(f)); };
+    for (size_t i0 = 0; i0 < route.size();) {
+        size_t i1 = i0;
+        uint64_t need = 0;
+        while (i1 < route.size() && (i1 == i0 || need + scratch_of(route[i1]) <= budget)) need += scratch_of(route[i1++]);
+        const size_t S = i1 - i0;
+        // ---- the streams in HBM (a host batch: from the chunk's first frame to its last, in one copy)
+        DevBuf up_d, tab_d, img_d;
+        const uint8_t *base = bytes;
+        if (!bytes_dev) {
+            const uint64_t lo = (uint64_t)route[i0] * stride, hi = (uint64_t)route[i1 - 1] * stride + lens[route[i1 - 1]];
+            CNIIC_HIP_TRY(c, up_d.alloc(hi - lo + 16));
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+            base = up_d.as<uint8_t>() - lo;
+        }
+        // ---- one block for the rows, the status words and every frame's leaves; the staged images of a host destination
+        uint64_t words = 0, img_bytes = 0;
+        uint32_t max_px = 0;
+        for (size_t i = 0; i < S; i++) { words += tabs[route[i0 + i]].size(); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }
+        const uint64_t rows_at = 0, status_at = (S * sizeof(DeltaSmallDecRow) + 15) & ~15ull, tab_at = (status_at + S * 4 + 15) & ~15ull;
+        // (assembled in the context's pinned block, which held the streams' heads until the decoders were parsed: nothing reads those any more)
+        const uint64_t up_bytes = tab_at + words * 4;
+        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(up_bytes, pinned_huf_want(up_bytes)));
+        uint8_t *up = c->pinned_huf.as<uint8_t>();
+        CNIIC_HIP_TRY(c, tab_d.alloc(up_bytes));
+        if (img_bytes) CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
+        DeltaSmallDecRow *rows = reinterpret_cast<DeltaSmallDecRow *>(up + rows_at);
+        std::vector<uint64_t> img_at(S, 0), tab_word(S, 0);
+        std::vector<uint32_t> longest(S, 0);
+        uint64_t wat = 0, iat = 0;
+        for (size_t i = 0; i < S; i++) { tab_word[i] = wat; wat += tabs[route[i0 + i]].size(); }
+        parallel_for((uint32_t)S, (uint32_t)std::min<size_t>(16, std::max<uint64_t>(1, words >> 16)), [&](uint32_t i, uint32_t) {
+            const std::vector<uint32_t> &t = tabs[route[i0 + i]];
+            memcpy(up + tab_at + tab_word[i] * 4, t.data(), t.size() * 4);
+            for (size_t k = t.size() / 2; k < t.size(); k++) longest[i] = std::max(longest[i], dsd_keylen_len(t[k]));
+        });
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            const uint32_t n = w[f] * h[f], L = (uint32_t)(tabs[f].size() / 2);
+            DeltaSmallDecRow r;
+            r.payload = base + (uint64_t)f * stride + pay[f];
+            r.payload_bytes = dsd_stage_bytes(n, lens[f] - pay[f]);
+            r.code = reinterpret_cast<const uint32_t *>(tab_d.as<uint8_t>() + tab_at) + tab_word[i];
+            r.keylen = r.code + L;
+            r.leaves = L; r.w = w[f]; r.h = h[f]; r.max_len = longest[i];
+            r.dst = dst_dev ? rgb + (uint64_t)f * img_stride : img_d.as<uint8_t>() + iat;
+            rows[i] = r;
+            img_at[i] = iat;
+            if (!dst_dev) iat += img_room(f);
+            max_px = std::max(max_px, n);
+        }
+        memset(up + status_at, 0xff, S * 4);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(tab_d.p, up, up_bytes, hipMemcpyHostToDevice, c->stream));
+        {
+            ScopedKernelTimer t(c, "delta_small_dec_batch");
+            CNIIC_TRY(delta_small_dec_run(c, reinterpret_cast<const DeltaSmallDecRow *>(tab_d.as<uint8_t>() + rows_at), (uint32_t)S, max_px, max_rounds,
+                                          reinterpret_cast<uint32_t *>(tab_d.as<uint8_t>() + status_at)));
+            t.stop(S);
+        }
+        std::vector<uint32_t> st(S);
+        std::vector<uint8_t> imgs_h(img_bytes);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(st.data(), tab_d.as<uint8_t>() + status_at, S * 4, hipMemcpyDeviceToHost, c->stream));
+        if (img_bytes) CNIIC_HIP_TRY(c, hipMemcpyAsync(imgs_h.data(), img_d.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            if (st[i] == kDsdUnsettled) continue;   // the caller's
+            if (st[i] > kDsdRange) return c->fail(CNIIC_ERR_HIP, "delta_small_dec: frame %u reported no status", f);
+            taken[f] = 1;
+            if (st[i] == kDsdShort) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "delta: cannot decode the difference stream"; }
+            else if (st[i] == kDsdRange) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "delta: colour out of range (hilbertc.rs:505)"; }
+            else if (!dst_dev) memcpy(rgb + (uint64_t)f * img_stride, imgs_h.data() + img_at[i], (uint64_t)w[f] * h[f] * 3);
+        }
+        i0 = i1;
+    }
+    return CNIIC_OK;
+}
+
 // ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
 // The heads of all frames come to the host together (one strided copy for streams in HBM), every decoder is parsed there (up to 16
 // threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev); `hilbert(rle)` frames have
-// no decoder to parse and go to rle_decode_batch_route with their dimensions.  Whatever this route does
+// no decoder to parse and go to rle_decode_batch_route with their dimensions; `delta` frames of at most kDeltaSmallDecMaxPx pixels go to
+// delta_small_decode with their tables of leaves, a workgroup per frame (larger `delta` frames are the caller's).  Whatever this route does
 // not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more than 32
 // bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
 constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
@@ -1842,7 +1946,10 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     taken.assign(F, 0);
     rcs.assign(F, CNIIC_OK);
     msgs.assign(F, std::string());
-    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE)) return CNIIC_OK;
+    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE && d.kind != CODEC_DELTA)) return CNIIC_OK;
+    const bool delta = d.kind == CODEC_DELTA;
+    const uint64_t delta_max_px = delta ? delta_small_dec_max_px() : 0;
+    if (delta && !delta_max_px) return CNIIC_OK;
     const bool bytes_dev = is_device_ptr(bytes), dst_dev = is_device_ptr(rgb);
     std::vector<uint8_t> off_route(F, 0);   // tests (CNIIC_TEST_DECODE_BATCH_OFF=i,j,..): these frames through the single-stream decode
     if (const char *e = test_env("CNIIC_TEST_DECODE_BATCH_OFF"))
@@ -1882,6 +1989,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     if (bytes_dev) {
         uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
         for (uint32_t f = 0; f < F; f++) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
+        if (delta) W = std::min<uint64_t>(W, 8192);   // (what a single decode first looks at of a stream of a frame this route takes; a larger frame only shows its header)
         // (never wider than the stride, which is the source pitch of the strided copy: a stride below a header's 8 bytes reads fewer,
         // and every frame goes to the single decode)
         W = std::min<uint64_t>(std::max<uint64_t>(8, std::min(W, kBatchHeadsMax / F)), stride);
@@ -1891,10 +1999,11 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
     }
     // ---- the decoders, parsed on the host
-    std::vector<LeafTable> lts(F);
+    std::vector<LeafTable> lts(delta ? 16 : F);   // (`delta`: one per parsing thread; a frame keeps its leaves in two words each, delta_tabs)
+    std::vector<std::vector<uint32_t>> delta_tabs(delta ? F : 0);
     std::vector<uint64_t> pay(F);      // where the payload starts
     std::vector<uint8_t> cand(F, 0);   // 1: on the route; 2: the decoder runs past the head (a second look)
-    auto classify = [&](uint32_t f) {
+    auto classify = [&](uint32_t f, uint32_t thread) {
         cand[f] = 0;
         if (off_route[f]) return;
         uint64_t pos = 0;
@@ -1902,15 +2011,22 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         if (!get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) return;
         const uint64_t n = (uint64_t)fw * fh;
         if (!n || n >= (1ull << 32) || n * 3 > img_stride) return;
-        LeafTable &lt = lts[f];
-        if (!huff_parse_leaves(CNIIC_SYM_RGB, head_p[f], head_n[f], pos, lt)) { if (head_n[f] < lens[f]) cand[f] = 2; return; }
-        if (lt.too_deep || lt.max_len > 32 || lt.n() >= (1u << 20) || (lt.n() > 1 && pos >= lens[f])) return;
+        if (delta && (n > delta_max_px || (c->scan_xy.p && c->scan_w == fw && c->scan_h == fh))) return;   // (a size with an injected scan: the single decode follows it)
+        LeafTable &lt = lts[delta ? thread : f];
+        if (!huff_parse_leaves(delta ? CNIIC_SYM_SIGNED : CNIIC_SYM_RGB, head_p[f], head_n[f], pos, lt)) { if (head_n[f] < lens[f]) cand[f] = 2; return; }
+        if (lt.too_deep || lt.max_len > (delta ? kDeltaSmallMaxCodeLen : 32u) || lt.n() >= (1u << 20) || (lt.n() > 1 && pos >= lens[f])) return;
+        if (delta) {   // codes left-aligned in 32 bits, then key | length << 27 (delta_small_dec.hpp)
+            const uint32_t L = (uint32_t)lt.n();
+            std::vector<uint32_t> &tab = delta_tabs[f];
+            tab.resize(2 * (size_t)L);
+            for (uint32_t i = 0; i < L; i++) { tab[i] = (uint32_t)(lt.code[i] >> 32); tab[L + i] = dsd_keylen(lt.key[i], lt.len[i]); }
+        }
         w[f] = fw; h[f] = fh;
         pay[f] = pos;
         cand[f] = 1;
     };
     auto parse_all = [&](const std::vector<uint32_t> &which) {
-        parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t) { classify(which[i]); });
+        parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t thread) { classify(which[i], thread); });
     };
     {
         std::vector<uint32_t> all(F);
@@ -1920,7 +2036,23 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     std::vector<uint32_t> again;
     uint64_t W2 = 0;
     for (uint32_t f = 0; f < F; f++) if (cand[f] == 2) { again.push_back(f); W2 = std::max(W2, std::min<uint64_t>(lens[f], 4ull << 20)); }
-    if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
+    if (!again.empty() && delta) {
+        // `delta`: a small frame's decoder is most of its stream (a leaf's 7 bytes against a code of a dozen bits), so the second look is
+        // the rule, and 4096 frames of 128 x 128 would share kBatchHeadsMax at 64 KiB each, less than their decoders.  The frames are looked
+        // at again in groups of as many rows as the pinned block holds at the full width (the tables parsed from a group are the frames' own)
+        W2 = std::min(W2, stride);
+        const uint64_t rows = std::max<uint64_t>(1, kBatchHeadsMax / std::max<uint64_t>(W2, 1));
+        for (size_t g0 = 0; g0 < again.size();) {
+            size_t g1 = g0 + 1;
+            while (g1 < again.size() && (uint64_t)again[g1] - again[g0] + 1 <= rows) g1++;
+            const uint32_t f0 = again[g0], f1 = again[g1 - 1];
+            if (W2 > head_n[f0] || W2 > head_n[f1]) {
+                CNIIC_TRY(fetch(W2, f0, f1));
+                parse_all(std::vector<uint32_t>(again.begin() + g0, again.begin() + g1));
+            }
+            g0 = g1;
+        }
+    } else if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
         const uint32_t f0 = again.front(), f1 = again.back();
         W2 = std::min({W2, stride, kBatchHeadsMax / (f1 - f0 + 1)});
         if (W2 > head_n[f0] || W2 > head_n[f1]) {
@@ -1931,6 +2063,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     std::vector<uint32_t> route;
     for (uint32_t f = 0; f < F; f++) if (cand[f] == 1) route.push_back(f);
     if (route.empty()) return CNIIC_OK;
+    if (delta) return delta_small_decode(c, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, route, delta_tabs, pay, taken, rcs, msgs);
     // ---- payloads in HBM, outputs in HBM (4-byte aligned)
     DevBuf up_d, img_d;
     const uint8_t *base = bytes;

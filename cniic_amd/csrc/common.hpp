@@ -923,6 +923,13 @@ struct DeltaSmallRow { const uint8_t *src; uint32_t w, h; };
 struct DeltaSmallResult { uint32_t U, len; };   // distinct symbols, bytes of the stream
 int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint8_t *scratch_d, uint64_t sstride,
                     uint32_t *tmp_d, uint64_t tmp_px, DeltaSmallResult *res_d);
+// ---- k_delta_small_dec.hip: the decode of small `delta` frames, one workgroup per frame (delta_small_dec.hpp has the arithmetic and the
+// limits).  A row per frame: its payload (device memory, any alignment; payload_bytes to the stream's end), where its w x h x 3 image goes
+// (device memory, any alignment) and its decoder as `leaves` words of left-aligned codes, ascending, and as many key | length << 27 words
+// (no code longer than kDeltaSmallMaxCodeLen).  status_d[f]: kDsdOk (the image is written), kDsdShort / kDsdRange (it is not: the single
+// decode's two failures), kDsdUnsettled (not written: the caller decodes the frame on its own).  max_rounds >= 1: settle rounds per frame.
+struct DeltaSmallDecRow { const uint8_t *payload; uint8_t *dst; const uint32_t *code, *keylen; uint32_t payload_bytes, leaves, w, h, max_len /* the longest code */; };
+int delta_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t max_rounds, uint32_t *status_d);
 // ---- k_palette.hip: the colour -> label table of a frozen palette (every colour's nearest entry, lowest index among equals).  table_d: 2^24
 // labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
 // down the plain route; plain_cells_d (optional): a zeroed counter of such cells

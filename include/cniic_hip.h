@@ -635,7 +635,19 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
  * its own w * h * 3 bytes); other codecs, and the frames that route does not take, are decoded one by one on the worker contexts of
  * cniic_codec_encode_batch (CNIIC_OPT_BATCH_STREAMS at a time).  rcs (may be NULL): per-frame status, identical to what
  * cniic_codec_decode returns for that stream alone.  The call returns the first failure; cniic_last_error carries that frame's
- * message.  frames == 0 returns CNIIC_OK. */
+ * message.  frames == 0 returns CNIIC_OK.
+ *
+ * SMALL `delta` frames of a decode, here and in cniic_codec_measure_batch, mirror the encode's: with the expression `delta`, every frame
+ * of 1 .. 16 384 pixels whose image fits img_stride, whose size has no injected scan (cniic_ctx_set_scan) and whose decoder -- parsed on
+ * the host with the others' -- has no code longer than 19 bits (no encoder of so few symbols makes one) is decoded on ONE workgroup from
+ * its payload to its pixels in place (the payload's bits in 1024 subsequences that settle among themselves, FromDiff as a scan, the walk
+ * along the scan, the image stored whole), all such frames of the call in one launch whatever their number.  Host or device memory on
+ * either side, at any alignment.  Larger frames, a frame of exactly the injected scan's size, a decoder that does not parse or has a
+ * longer code, and a frame whose subsequences have not settled within the kernel's rounds go to the worker contexts as above.  Which
+ * route a frame took shows in no output byte, status or message, with one difference in a frame's favour: a frame that fails on this
+ * route ("delta: cannot decode the difference stream", "delta: colour out of range (hilbertc.rs:505)") leaves its w * h * 3 bytes
+ * untouched.  Stage timer: "delta_small_dec_batch" = the duration of that kernel, with launches = the frames it was given;
+ * cniic_codec_measure_batch leaves it readable beside the encode's "delta_small_batch". */
 int32_t cniic_codec_decode_batch(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens,
                                  uint32_t frames, uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* bench::compute_error (src/bench.rs:95-104): MSE between two RGB8 images. */
