@@ -13,6 +13,7 @@
 #include "cc_small.hpp"
 #include "delta_small.hpp"
 #include "delta_small_dec.hpp"
+#include "small_trie.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -1838,6 +1839,7 @@ static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, 
 // copy up for the tables and rows (and one for host streams, from the chunk's first frame to its last), ONE launch with a workgroup per
 // frame, one copy down for the status words (and one for a host destination's images, which a memcpy per frame then puts in place), one
 // wait.  A frame the kernel hands back (not settled within its rounds) is left to the caller like everything else not taken.
+// Frames whose decoders k_small_trieparse has parsed (delta_small_parse_dev below) come with their tables in HBM: nothing of those goes up.
 // The testing library can switch the route off (CNIIC_TEST_DELTA_SMALL_DEC_OFF=1), lower its bound (CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX) and its
 // settle rounds (CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS), and make the chunks small (CNIIC_TEST_MEASURE_BUDGET, bytes).
 constexpr uint64_t kDeltaSmallDecScratch = 2ull << 30;
@@ -1846,15 +1848,23 @@ static uint64_t delta_small_dec_max_px() {
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecMaxPx);
     return kDeltaSmallDecMaxPx;
 }
+// A decoder that k_small_trieparse has left in HBM (delta_small_parse_dev below): its codes, then as many key | length words
+struct DeltaSmallDevTab { const uint32_t *code; uint32_t leaves, max_len; };
+static uint64_t delta_small_dec_budget() {
+    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecScratch);
+    return kDeltaSmallDecScratch;
+}
+// dev != nullptr: the routed frames' tables lie in HBM already ((*dev)[f]), and `tabs` is not looked at
 static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
                               const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route, const std::vector<std::vector<uint32_t>> &tabs,
-                              const std::vector<uint64_t> &pay, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs, std::vector<std::string> &msgs) {
+                              const std::vector<DeltaSmallDevTab> *dev, const std::vector<uint64_t> &pay, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
+                              std::vector<std::string> &msgs) {
     uint32_t max_rounds = kDsdMaxRounds;
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS")) max_rounds = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kDsdMaxRounds);
-    uint64_t budget = kDeltaSmallDecScratch;
-    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) budget = std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecScratch);
+    const uint64_t budget = delta_small_dec_budget();
     auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
-    auto scratch_of = [&](uint32_t f) { return tabs[f].size() * 4 + sizeof(DeltaSmallDecRow) + 4 + (dst_dev ? 0 : img_room(f)); };
+    auto tab_words = [&](uint32_t f) -> uint64_t { return dev ? 0 : tabs[f].size(); };
+    auto scratch_of = [&](uint32_t f) { return tab_words(f) * 4 + sizeof(DeltaSmallDecRow) + 4 + (dst_dev ? 0 : img_room(f)); };
     for (size_t i0 = 0; i0 < route.size();) {
         size_t i1 = i0;
         uint64_t need = 0;
@@ -1872,7 +1882,7 @@ static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint
         // ---- one block for the rows, the status words and every frame's leaves; the staged images of a host destination
         uint64_t words = 0, img_bytes = 0;
         uint32_t max_px = 0;
-        for (size_t i = 0; i < S; i++) { words += tabs[route[i0 + i]].size(); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }
+        for (size_t i = 0; i < S; i++) { words += tab_words(route[i0 + i]); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }
         const uint64_t rows_at = 0, status_at = (S * sizeof(DeltaSmallDecRow) + 15) & ~15ull, tab_at = (status_at + S * 4 + 15) & ~15ull;
         // (assembled in the context's pinned block, which held the streams' heads until the decoders were parsed: nothing reads those any more)
         const uint64_t up_bytes = tab_at + words * 4;
@@ -1884,21 +1894,22 @@ static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint
         std::vector<uint64_t> img_at(S, 0), tab_word(S, 0);
         std::vector<uint32_t> longest(S, 0);
         uint64_t wat = 0, iat = 0;
-        for (size_t i = 0; i < S; i++) { tab_word[i] = wat; wat += tabs[route[i0 + i]].size(); }
-        parallel_for((uint32_t)S, (uint32_t)std::min<size_t>(16, std::max<uint64_t>(1, words >> 16)), [&](uint32_t i, uint32_t) {
-            const std::vector<uint32_t> &t = tabs[route[i0 + i]];
-            memcpy(up + tab_at + tab_word[i] * 4, t.data(), t.size() * 4);
-            for (size_t k = t.size() / 2; k < t.size(); k++) longest[i] = std::max(longest[i], dsd_keylen_len(t[k]));
-        });
+        for (size_t i = 0; i < S; i++) { tab_word[i] = wat; wat += tab_words(route[i0 + i]); }
+        if (!dev)
+            parallel_for((uint32_t)S, (uint32_t)std::min<size_t>(16, std::max<uint64_t>(1, words >> 16)), [&](uint32_t i, uint32_t) {
+                const std::vector<uint32_t> &t = tabs[route[i0 + i]];
+                memcpy(up + tab_at + tab_word[i] * 4, t.data(), t.size() * 4);
+                for (size_t k = t.size() / 2; k < t.size(); k++) longest[i] = std::max(longest[i], dsd_keylen_len(t[k]));
+            });
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
-            const uint32_t n = w[f] * h[f], L = (uint32_t)(tabs[f].size() / 2);
+            const uint32_t n = w[f] * h[f], L = dev ? (*dev)[f].leaves : (uint32_t)(tabs[f].size() / 2);
             DeltaSmallDecRow r;
             r.payload = base + (uint64_t)f * stride + pay[f];
             r.payload_bytes = dsd_stage_bytes(n, lens[f] - pay[f]);
-            r.code = reinterpret_cast<const uint32_t *>(tab_d.as<uint8_t>() + tab_at) + tab_word[i];
+            r.code = dev ? (*dev)[f].code : reinterpret_cast<const uint32_t *>(tab_d.as<uint8_t>() + tab_at) + tab_word[i];
             r.keylen = r.code + L;
-            r.leaves = L; r.w = w[f]; r.h = h[f]; r.max_len = longest[i];
+            r.leaves = L; r.w = w[f]; r.h = h[f]; r.max_len = dev ? (*dev)[f].max_len : longest[i];
             r.dst = dst_dev ? rgb + (uint64_t)f * img_stride : img_d.as<uint8_t>() + iat;
             rows[i] = r;
             img_at[i] = iat;
@@ -1932,6 +1943,93 @@ static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint
     return CNIIC_OK;
 }
 
+// ------------------------------------------------------------------ the decoders of small `delta` frames, parsed where the streams lie
+// Streams in device memory (k_small_trie.hip): no head of a stream comes to the host.  Every frame with a header (lens[f] >= 8, not named
+// by CNIIC_TEST_DECODE_BATCH_OFF) is a candidate; what the kernel may read of frame f is what the host's looks below get to see of it,
+// min(lens[f], stride) bytes.  The candidates are worked through in chunks whose scratch -- 8 bytes per leaf a stream has room for, at most
+// kSmallTrieMaxLeaves, and the rows -- stays below the budget: per chunk one copy up of the rows, ONE launch with a workgroup per frame,
+// one copy down of the result rows, one wait; then delta_small_decode for the chunk's parsed frames, whose rows point at the tables where
+// the kernel left them.  A parsed frame is routed under the host parse's conditions (no code longer than kDeltaSmallMaxCodeLen -- the
+// kernel finishes no other --, more leaves than one only with a payload).  Every other candidate whose header the kernel did not turn
+// away -- not a decoder, not ours -- is handed back in `host`: the caller runs the host's looks and parse for those frames alone, which
+// keeps the routed frames, every status and every message what they are without this parse.
+// Stage timers: "delta_small_dec_parse" (the launches' time; launches = frames parsed) and "delta_small_dec_parse_host" (no time;
+// launches = frames handed back).  The testing library keeps the host's parse for everything with CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF=1.
+static bool delta_small_parse_off() {
+    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF")) return atoi(e) != 0;
+    return false;
+}
+static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
+                                 uint32_t *w, uint32_t *h, const std::vector<uint8_t> &off_route, uint64_t max_px, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
+                                 std::vector<std::string> &msgs, std::vector<uint32_t> &host) {
+    host.clear();
+    std::vector<uint32_t> cands;
+    auto view = [&](uint32_t f) { return std::min(lens[f], stride); };
+    for (uint32_t f = 0; f < F; f++) if (!off_route[f] && lens[f] >= 8 && view(f) >= 8) cands.push_back(f);
+    if (c->timers) { (void)c->ktimes["delta_small_dec_parse"]; (void)c->ktimes["delta_small_dec_parse_host"]; }
+    if (cands.empty()) return CNIIC_OK;
+    const uint64_t budget = delta_small_dec_budget();
+    auto scratch_of = [&](uint32_t f) { return (uint64_t)st_leaves_room<6>(view(f)) * 8 + sizeof(SmallTrieRow) + sizeof(SmallTrieResult); };
+    const bool scan = c->scan_xy.p != nullptr;
+    std::vector<DeltaSmallDevTab> dev(F);
+    std::vector<uint64_t> pay(F, 0);
+    const std::vector<std::vector<uint32_t>> no_tabs;
+    uint64_t parsed = 0;
+    for (size_t i0 = 0; i0 < cands.size();) {
+        size_t i1 = i0;
+        uint64_t need = 0, longest = 0;
+        while (i1 < cands.size() && (i1 == i0 || need + scratch_of(cands[i1]) <= budget)) need += scratch_of(cands[i1++]);
+        const size_t S = i1 - i0;
+        // ---- one block: the rows, the result rows, every frame's table
+        const uint64_t res_at = (S * sizeof(SmallTrieRow) + 15) & ~15ull, tab_at = (res_at + S * sizeof(SmallTrieResult) + 15) & ~15ull;
+        uint64_t words = 0;
+        for (size_t i = 0; i < S; i++) words += 2ull * st_leaves_room<6>(view(cands[i0 + i]));
+        DevBuf blk_d;
+        CNIIC_HIP_TRY(c, blk_d.alloc(tab_at + words * 4 + 16));
+        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(res_at, pinned_huf_want(res_at)));
+        SmallTrieRow *rows = c->pinned_huf.as<SmallTrieRow>();
+        uint32_t *tab0 = reinterpret_cast<uint32_t *>(blk_d.as<uint8_t>() + tab_at);
+        uint64_t wat = 0;
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = cands[i0 + i];
+            rows[i].stream = bytes + (uint64_t)f * stride;
+            rows[i].table = tab0 + wat;
+            rows[i].bytes = view(f);
+            wat += 2ull * st_leaves_room<6>(view(f));
+            longest = std::max(longest, view(f));
+        }
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(blk_d.p, rows, S * sizeof(SmallTrieRow), hipMemcpyHostToDevice, c->stream));
+        {
+            ScopedKernelTimer t(c, "delta_small_dec_parse");
+            CNIIC_TRY(small_trie_run(c, blk_d.as<SmallTrieRow>(), (uint32_t)S, longest, (uint32_t)max_px, img_stride, scan ? c->scan_w : 0, scan ? c->scan_h : 0,
+                                     reinterpret_cast<SmallTrieResult *>(blk_d.as<uint8_t>() + res_at)));
+            t.stop(0);
+        }
+        std::vector<SmallTrieResult> res(S);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), blk_d.as<uint8_t>() + res_at, S * sizeof(SmallTrieResult), hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<uint32_t> route;
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = cands[i0 + i];
+            const SmallTrieResult &r = res[i];
+            if (r.verdict == kStSkipped) continue;   // (its size or an injected scan: the host's parse would not look at it either)
+            if (r.verdict != kStParsed) { host.push_back(f); continue; }
+            parsed++;
+            if (r.leaves == 0 || r.leaves > st_leaves_room<6>(view(f)) || r.max_len > kDeltaSmallMaxCodeLen || r.payload_at > view(f))
+                return c->fail(CNIIC_ERR_HIP, "small_trieparse: frame %u reported a decoder outside its stream", f);
+            if (r.leaves > 1 && r.payload_at >= lens[f]) continue;   // (symbols, and no payload: the single decode answers)
+            w[f] = r.w; h[f] = r.h;
+            pay[f] = r.payload_at;
+            dev[f] = DeltaSmallDevTab{rows[i].table, r.leaves, r.max_len};
+            route.push_back(f);
+        }
+        if (!route.empty()) CNIIC_TRY(delta_small_decode(c, bytes, true, stride, lens, rgb, dst_dev, img_stride, w, h, route, no_tabs, &dev, pay, taken, rcs, msgs));
+        i0 = i1;
+    }
+    if (c->timers) { c->ktimes["delta_small_dec_parse"].launches += parsed; c->ktimes["delta_small_dec_parse_host"].launches += host.size(); }
+    return CNIIC_OK;
+}
+
 // ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
 // The heads of all frames come to the host together (one strided copy for streams in HBM), every decoder is parsed there (up to 16
 // threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev); `hilbert(rle)` frames have
@@ -1939,6 +2037,8 @@ static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint
 // delta_small_decode with their tables of leaves, a workgroup per frame (larger `delta` frames are the caller's).  Whatever this route does
 // not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more than 32
 // bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
+// `delta` streams that lie in device memory are parsed there first (delta_small_parse_dev); the heads and the host's parse below are then
+// for the frames that parse hands back, and for those alone.  Streams in host memory keep the host's parse: the bytes are where the parser is.
 constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
                              uint64_t img_stride, uint32_t *w, uint32_t *h, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
@@ -1986,15 +2086,25 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         }
         return rle_decode_batch_route(c, bytes, bytes_dev, stride, lens, F, rgb, dst_dev, img_stride, w, h, head_p, head_n, off_route, taken, rcs, msgs);
     }
+    // `delta` streams in device memory: the decoders are parsed there, and the host looks only at the frames that parse hands back
+    std::vector<uint32_t> all;
+    if (delta && bytes_dev && !delta_small_parse_off()) {
+        CNIIC_TRY(delta_small_parse_dev(c, bytes, stride, lens, F, rgb, dst_dev, img_stride, w, h, off_route, delta_max_px, taken, rcs, msgs, all));
+        if (all.empty()) return CNIIC_OK;
+    } else {
+        all.resize(F);
+        for (uint32_t f = 0; f < F; f++) all[f] = f;
+    }
+    const uint32_t fa = all.front(), fb = all.back();   // (ascending)
     if (bytes_dev) {
         uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
-        for (uint32_t f = 0; f < F; f++) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
+        for (uint32_t f : all) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
         if (delta) W = std::min<uint64_t>(W, 8192);   // (what a single decode first looks at of a stream of a frame this route takes; a larger frame only shows its header)
         // (never wider than the stride, which is the source pitch of the strided copy: a stride below a header's 8 bytes reads fewer,
         // and every frame goes to the single decode)
-        W = std::min<uint64_t>(std::max<uint64_t>(8, std::min(W, kBatchHeadsMax / F)), stride);
-        if (W) CNIIC_TRY(fetch(W, 0, F - 1));
-        else for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes; head_n[f] = 0; }
+        W = std::min<uint64_t>(std::max<uint64_t>(8, std::min(W, kBatchHeadsMax / (fb - fa + 1))), stride);
+        if (W) CNIIC_TRY(fetch(W, fa, fb));
+        else for (uint32_t f = fa; f <= fb; f++) { head_p[f] = bytes; head_n[f] = 0; }
     } else {
         for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
     }
@@ -2028,11 +2138,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     auto parse_all = [&](const std::vector<uint32_t> &which) {
         parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t thread) { classify(which[i], thread); });
     };
-    {
-        std::vector<uint32_t> all(F);
-        for (uint32_t f = 0; f < F; f++) all[f] = f;
-        parse_all(all);
-    }
+    parse_all(all);
     std::vector<uint32_t> again;
     uint64_t W2 = 0;
     for (uint32_t f = 0; f < F; f++) if (cand[f] == 2) { again.push_back(f); W2 = std::max(W2, std::min<uint64_t>(lens[f], 4ull << 20)); }
@@ -2063,7 +2169,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     std::vector<uint32_t> route;
     for (uint32_t f = 0; f < F; f++) if (cand[f] == 1) route.push_back(f);
     if (route.empty()) return CNIIC_OK;
-    if (delta) return delta_small_decode(c, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, route, delta_tabs, pay, taken, rcs, msgs);
+    if (delta) return delta_small_decode(c, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, route, delta_tabs, nullptr, pay, taken, rcs, msgs);
     // ---- payloads in HBM, outputs in HBM (4-byte aligned)
     DevBuf up_d, img_d;
     const uint8_t *base = bytes;

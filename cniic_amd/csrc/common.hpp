@@ -930,6 +930,16 @@ int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32
 // decode's two failures), kDsdUnsettled (not written: the caller decodes the frame on its own).  max_rounds >= 1: settle rounds per frame.
 struct DeltaSmallDecRow { const uint8_t *payload; uint8_t *dst; const uint32_t *code, *keylen; uint32_t payload_bytes, leaves, w, h, max_len /* the longest code */; };
 int delta_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t max_rounds, uint32_t *status_d);
+// ---- k_small_trie.hip: the parse of small `delta` frames' decoders, one workgroup per frame (small_trie.hpp has the arithmetic and the
+// limits).  A row per frame: its stream (device memory, any alignment; `bytes` of it may be read) and where its table goes -- room for
+// st_leaves_room<6>(bytes) leaves of two words, 4-byte aligned: the left-aligned codes, then as many key | length << 27 words, which is what
+// DeltaSmallDecRow points at.  res_d[f]: the header's w and h (when there are 8 bytes), the verdict (small_trie.hpp), and of a parsed
+// decoder the leaves, the longest code and the payload's offset in the stream.  A frame of 0 or more than max_px pixels, of more than
+// img_stride bytes or of the size scan_w x scan_h (0 x 0: none) is skipped (kStSkipped).
+struct SmallTrieRow { const uint8_t *stream; uint32_t *table; uint64_t bytes; };
+struct SmallTrieResult { uint32_t w, h, verdict, leaves, max_len, payload_at; };
+int small_trie_run(Ctx *c, const SmallTrieRow *rows_d, uint32_t frames, uint64_t max_bytes /* of the longest stream */, uint32_t max_px, uint64_t img_stride,
+                   uint32_t scan_w, uint32_t scan_h, SmallTrieResult *res_d);
 // ---- k_palette.hip: the colour -> label table of a frozen palette (every colour's nearest entry, lowest index among equals).  table_d: 2^24
 // labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
 // down the plain route; plain_cells_d (optional): a zeroed counter of such cells

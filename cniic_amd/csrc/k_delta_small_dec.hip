@@ -1,6 +1,7 @@
 // k_delta_small_dec.hip -- the decode of SMALL `delta` frames (at most kDeltaSmallDecMaxPx pixels), one workgroup per frame, any number of
-// frames in one launch (cniic_codec_decode_batch / cniic_codec_measure_batch; codec.cpp delta_small_decode).  The host has parsed every
-// frame's decoder into its table of leaves (huff_parse_leaves), which lies in HBM; the block goes from the payload to the pixels in place:
+// frames in one launch (cniic_codec_decode_batch / cniic_codec_measure_batch; codec.cpp delta_small_decode).  Every frame's decoder has
+// been parsed into its table of leaves, which lies in HBM -- by k_small_trieparse (k_small_trie.hip) for streams in device memory, by the
+// host (huff_parse_leaves) otherwise; the block goes from the payload to the pixels in place:
 //   a. stage: the first ceil(19 n / 8) bytes of the payload from any byte alignment into LDS, as big-endian words
 //   b. symbols, self-synchronising: the payload's bits in one subsequence per lane; every lane decodes from where it assumes a code starts
 //      until it crosses into the next subsequence, lanes whose predecessor ended elsewhere decode again from there, until a block-wide

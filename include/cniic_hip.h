@@ -647,7 +647,14 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
  * route a frame took shows in no output byte, status or message, with one difference in a frame's favour: a frame that fails on this
  * route ("delta: cannot decode the difference stream", "delta: colour out of range (hilbertc.rs:505)") leaves its w * h * 3 bytes
  * untouched.  Stage timer: "delta_small_dec_batch" = the duration of that kernel, with launches = the frames it was given;
- * cniic_codec_measure_batch leaves it readable beside the encode's "delta_small_batch". */
+ * cniic_codec_measure_batch leaves it readable beside the encode's "delta_small_batch".
+ * When the streams lie in device memory their decoders are parsed there as well, a workgroup per frame and all frames in one launch: the
+ * block reads the header and the pre-order trie where the stream lies and leaves the leaves' codes and symbols for the decode kernel, so
+ * that no byte of such a stream comes to the host.  A decoder that kernel does not finish -- more than 16 384 leaves, a code longer than
+ * 19 bits, bytes that are no decoder -- is parsed on the host as before, and so is every decoder of a batch in host memory: the routed
+ * frames, every status and every message are the same either way.  Stage timers, only when that parse ran: "delta_small_dec_parse" = the
+ * duration of its launches, with launches = the frames it parsed; "delta_small_dec_parse_host" = no time, launches = the frames handed
+ * back to the host's parse. */
 int32_t cniic_codec_decode_batch(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens,
                                  uint32_t frames, uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* bench::compute_error (src/bench.rs:95-104): MSE between two RGB8 images. */

@@ -1,16 +1,18 @@
 """Batches of SMALL `delta` frames through cniic_codec_decode_batch and cniic_codec_measure_batch: this build (the small-frame decode
-route, k_delta_small_dec.hip) against another build of the library and against this build with the route switched off, device buffers
-throughout.
+route, k_delta_small_dec.hip, its decoders parsed on the GPU by k_small_trie.hip) against another build of the library, against this
+build with the host's parse of the decoders and against this build with the route switched off, device buffers throughout.
     python tools/small_delta_decode_probe.py --against libcniic_hip_parent.so [--out profiles/small_delta_decode_probe.json] [--reps 5] [--rounds 1]
 Batches of 256 and 4096 synthetic frames of 32 x 32, 64 x 64, 128 x 96 and 128 x 128, photo-like and uniform noise (noise: nearly every
 symbol a leaf and codes of nearly one length, which settle slowest).  Every variant is timed in a child process of its own, the variants
-in alternation (this, route off, other, this, ...), --rounds times --reps runs each after --warmup untimed ones; the medians are compared
+in alternation (this, parse off, route off, other, this, ...), --rounds times --reps runs each after --warmup untimed ones; the medians are compared
 with min - max beside them, and the digests of the decoded images (and of the measure rows) must agree.
   this        libcniic_hip_testing.so of this tree
+  parse_off   the same library under CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF=1: the decoders parsed on the host
   route_off   the same library under CNIIC_TEST_DELTA_SMALL_DEC_OFF=1: every frame's decode on a worker context
   other       --against FILE: another build in cniic_amd/ (CNIIC_LIB_FILE), e.g. the parent commit's library
-A fourth child runs `this` with the stage timers on and records the duration of k_delta_small_dec ("delta_small_dec_batch") of both calls.
---sizes / --frames / --kinds / --calls narrow the sweep."""
+A further child runs `this` with the stage timers on and records the duration of k_delta_small_dec ("delta_small_dec_batch") and of
+k_small_trieparse ("delta_small_dec_parse", with the frames it parsed and, under "delta_small_dec_parse_host", those it handed back) of
+both calls.  --sizes / --frames / --kinds / --calls narrow the sweep, --variants the builds."""
 import argparse
 import hashlib
 import json
@@ -28,7 +30,9 @@ FRAMES = (256, 4096)
 KINDS = ("photo", "uniform")
 CALLS = ("decode_batch", "measure_batch")
 STAGE = "delta_small_dec_batch"
+PARSE_STAGE, PARSE_HOST_STAGE = "delta_small_dec_parse", "delta_small_dec_parse_host"
 OFF = "CNIIC_TEST_DELTA_SMALL_DEC_OFF"
+PARSE_OFF = "CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF"
 
 
 def cases(a):
@@ -74,7 +78,8 @@ def child(a):
                 call()
                 ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
                 call()
-                out[name] = dict(ms=round(ctx.kernel_time(STAGE)[0], 3), launches=ctx.kernel_time(STAGE)[1])
+                out[name] = dict(ms=round(ctx.kernel_time(STAGE)[0], 3), launches=ctx.kernel_time(STAGE)[1], parse_ms=round(ctx.kernel_time(PARSE_STAGE)[0], 3),
+                                 parsed=ctx.kernel_time(PARSE_STAGE)[1], handed_back=ctx.kernel_time(PARSE_HOST_STAGE)[1])
                 ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
                 continue
             img.zero_()
@@ -116,21 +121,25 @@ def main():
     ap.add_argument("--frames")
     ap.add_argument("--kinds")
     ap.add_argument("--calls")
+    ap.add_argument("--variants", help="of this,parse_off,route_off,other (this is always run)")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--stages", action="store_true")
     a = ap.parse_args()
     if a.child:
         return child(a)
-    variants = [("this", {"CNIIC_USE_TESTING_LIB": "1"}), ("route_off", {"CNIIC_USE_TESTING_LIB": "1", OFF: "1"})]
+    variants = [("this", {"CNIIC_USE_TESTING_LIB": "1"}), ("parse_off", {"CNIIC_USE_TESTING_LIB": "1", PARSE_OFF: "1"}),
+                ("route_off", {"CNIIC_USE_TESTING_LIB": "1", OFF: "1"})]
     if a.against:
         variants.append(("other", {"CNIIC_LIB_FILE": a.against}))
+    if a.variants:
+        variants = [v for v in variants if v[0] == "this" or v[0] in a.variants.split(",")]
     base = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup)]
     for k in ("sizes", "frames", "kinds", "calls"):
         if getattr(a, k):
             base += ["--" + k, getattr(a, k)]
 
     def run(env_add, extra=()):
-        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", OFF)}
+        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", OFF, PARSE_OFF)}
         env.update(env_add)
         r = subprocess.run(base + list(extra), capture_output=True, text=True, timeout=1100, env=env)
         if r.returncode != 0:
@@ -151,7 +160,7 @@ def main():
     rows = []
     for k, v in got["this"].items():
         row = dict(case=k, failed_frames=v["failed"], this=stats(v["ms"]), kernel=stages.get(k))
-        for who in ("route_off", "other"):
+        for who in ("parse_off", "route_off", "other"):
             if who not in got:
                 continue
             o = got[who][k]
