@@ -26,8 +26,10 @@ namespace cniic {
 
 constexpr int kPsThreads = 1024, kPsWaves = kPsThreads / 64;
 constexpr uint32_t kPsAccWords = 5 * 256;              // u64 accumulators (K <= 256)
-// dynamic LDS: [acc u64 5 x 256 | tab uint2 256 | ids u8 kPsSlotsMax x kPsScap | per block (ps_cell_bytes): first points, records, cell ids, work list, list slots | points u32[...]]
+// dynamic LDS, kPsBudget bytes (or the tests' fewer) and then u64 running sums 5 x 256: [acc u64 5 x 256 | tab uint2 256 | ids u8 kPsSlotsMax x kPsScap | per block (ps_cell_bytes): first points, records, cell ids, work list, list slots | points u32[...]]
 constexpr uint32_t kPsOffTab = kPsAccWords * 8, kPsOffS = kPsOffTab + 256 * 8;
+constexpr uint32_t kPsStaticMax = 3072;                // the kernel's static LDS variables stay below this (asserted where they are declared)
+static_assert(kPsDynBytes + kPsStaticMax <= 160 * 1024, "static + dynamic LDS of k_rgbw_persist: a CU has 160 KiB");
 static_assert(kPsOffCell == kPsOffS + kPsSlotsMax * kPsScap * 4, "ps_cell_bytes / kPsOffCell (kmeans_rgbw.hpp) describe this layout");
 
 __device__ __forceinline__ uint32_t ps_xcc_id() {
@@ -86,8 +88,11 @@ __device__ __forceinline__ bool ps_barrier_xcd(PsBar *b, uint32_t x, uint32_t nx
 // instead of landing on one or two (profiles/r05_persist_v1_block_phases.txt: with one contiguous range per block the slowest block of a
 // skip iteration did 25 us of work while the mean was 2).  cb[i] = first cell of chunk i, cb[G kPsChunks] = M.
 // fail: a block would own more cells than its LDS can describe (then no block starts and the classic loop runs).
+// It also leaves the launch its set-up's pointers (PsDev, kmeans_rgbw.hpp): in device memory, so that no block reads them over the bus.
 __global__ __launch_bounds__(1024) void k_ps_ranges(const uint32_t *__restrict__ ne_cost, const uint32_t *__restrict__ ne_count, uint32_t G, uint32_t dyn_bytes,
-                                                    uint32_t *__restrict__ cb, uint32_t *__restrict__ fail) {
+                                                    uint32_t *__restrict__ cb, PsDev *__restrict__ dev, PsDevPtrs ptrs) {
+    uint32_t *fail = &dev->fail;
+    if (threadIdx.x == 0) dev->p = ptrs;
     const uint32_t M = *ne_count, NC = G * kPsChunks;
     const uint64_t total = ne_cost[M];
     // (a thread's boundaries searched TOGETHER, eight at a time: one after the other the 4097 bisections of the headline image were 60
@@ -519,16 +524,12 @@ struct PsCold {
     GIdx gx;                              // ... or the index of all occupied colours
     uint64_t seed, U;
 };
+// ... and what only the set-up and the write-out need sits in the launch's arena in DEVICE memory (every block reads it on entry), written by
+// k_ps_ranges; the arena's parts lie at fixed offsets from its head, the barrier words: one pointer instead of four.
 struct PsArgs {
-    const uint32_t *ckeys, *cweight;      // cell-major colours and pixel counts
-    uint8_t *labels;                      // cell-major labels: the initial assignment on entry, the result on a regular exit
-    const uint32_t *ne_cell, *ne_start;   // compacted non-empty cells: id, first position
-    const uint32_t *cb;                   // chunk boundaries (k_ps_ranges)
-    const uint32_t *ranges_fail;
+    const uint32_t *cweight;              // cell-major pixel counts (a mover whose count does not fit its packed word)
     uint32_t *pk;                         // packed words of the points that do not fit their block's LDS, by cell-major position
-    const uint2 *cconst0;                 // the initial centroids (k_rgbw_init_cent)
-    unsigned long long *partials;         // 3 x kPsPartWords, zero on entry
-    PsBar *bar;                           // zero on entry
+    PsBar *bar;                           // the arena (kmeans_rgbw.hpp): barrier words and sums zero on entry, PsDev and the chunk boundaries from k_ps_ranges
     KmDevState *st_rw;
     PsCold *cold;                         // pinned
     uint64_t max_iters;
@@ -537,32 +538,45 @@ struct PsArgs {
     unsigned long long timeout_ticks;
 };
 
+__device__ __forceinline__ unsigned long long *ps_partials(PsBar *bar) {   // 3 x kPsPartWords sums, zero on entry
+    return reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(bar) + kPsArenaPart);
+}
+
 __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     extern __shared__ __align__(16) unsigned long long lds[];
     __shared__ uint32_t s_moved, s_nmoved, s_reseed, s_active, s_ok, s_nx, s_nxcd, s_qn, s_qhead, s_Cres, s_nslots;
     __shared__ uint32_t s_mlist[kMaxMovedSkip];
-    __shared__ unsigned long long s_mm[4], s_evals, s_changed, s_pev;
+    __shared__ unsigned long long s_mm[4], s_evals, s_changed, s_pev, s_rtot, s_etot;   // (s_rtot, s_etot: the run's reseeds and pair evaluations, thread 0's)
     __shared__ uint32_t s_nS[kPsSlotsMax], s_lpiv[kPsSlotsMax], s_mcol[kMaxMovedSkip];
     __shared__ uint16_t s_ssup[kPsSlotsMax];
     __shared__ uint32_t s_cbase[kPsChunks + 1], s_cm0[kPsChunks], s_scan[kPsThreads / 64];
+    // (the static variables above, with room for their alignment: static + dynamic LDS stay inside a CU's 160 KiB.  The sum is written
+    // out by hand: whoever adds a __shared__ variable adds it here too -- tools/kernel_regs.sh prints what the compiler counted)
+    static_assert(4 * (11 + 2 * kMaxMovedSkip + 2 * kPsSlotsMax + 2 * kPsChunks + 1 + kPsThreads / 64) + 8 * (4 + 5) + 2 * kPsSlotsMax + 64 <= kPsStaticMax, "the static LDS of k_rgbw_persist");
     const uint32_t tid = threadIdx.x, K = a.K, G = gridDim.x;
     const int lane = tid & 63, wid = tid >> 6;
     unsigned long long *acc = lds;
+    // the running sums of the clusters (kmeans.rs: the members of every cluster, as sums), the same in every block: row i of cluster k at
+    // 256 i + k, at the top of the dynamic LDS behind the budget (as registers of the threads k < K they were ten vector registers alive
+    // across the whole loop)
+    unsigned long long *runs = lds + kPsBudget / 8;
     uint2 *tab = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(lds) + kPsOffTab);
     uint32_t *Sent = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(lds) + kPsOffS);
-    if (*a.ranges_fail) {   // (the same word for every block: nobody starts, nobody waits)
+    const PsDev *dev = reinterpret_cast<const PsDev *>(reinterpret_cast<const uint8_t *>(a.bar) + kPsArenaFail);
+    if (dev->fail) {   // (the same word for every block: nobody starts, nobody waits)
         if (blockIdx.x == 0 && tid == 0) { a.cold->exit.status = kPsStatusRanges; __threadfence_system(); }
         return;
     }
     // ---- the block's cells: chunks b, G + b, 2 G + b, ... of the compacted list, in that order
     if (tid < kPsChunks) {
-        const uint32_t m0 = a.cb[tid * G + blockIdx.x], m1 = a.cb[tid * G + blockIdx.x + 1];
+        const uint32_t *cb = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(a.bar) + kPsArenaRng);
+        const uint32_t m0 = cb[tid * G + blockIdx.x], m1 = cb[tid * G + blockIdx.x + 1];
         s_cm0[tid] = m0;
         s_cbase[tid + 1] = m1 - m0;
     }
     if (tid == 0) {
         s_cbase[0] = 0;
-        s_moved = 0; s_evals = 0; s_nmoved = 0; s_reseed = 0; s_active = 0; s_mm[0] = s_mm[1] = s_mm[2] = s_mm[3] = 0ull; s_qn = 0; s_qhead = 0; s_Cres = 0; s_nslots = 0;
+        s_moved = 0; s_evals = 0; s_nmoved = 0; s_reseed = 0; s_active = 0; s_mm[0] = s_mm[1] = s_mm[2] = s_mm[3] = 0ull; s_qn = 0; s_qhead = 0; s_Cres = 0; s_nslots = 0; s_rtot = 0ull; s_etot = 0ull;
     }
     __syncthreads();
     if (tid == 0)
@@ -579,6 +593,7 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     uint32_t *pts = reinterpret_cast<uint32_t *>(cslot + Cr);                    // the resident points' words
     const uint32_t cap = (a.lds_budget - kPsOffCell - ps_cell_bytes(C)) / 4u;    // (k_ps_ranges made sure the budget covers the descriptors)
     {   // two cells per thread: 2 tid and 2 tid + 1 (a block owns at most kPsMaxCells = 2 x kPsThreads)
+        const uint32_t *ne_cell = dev->p.ne_cell, *ne_start = dev->p.ne_start;
         uint32_t np[2] = {0, 0}, cid[2] = {0, 0}, rr[2] = {0, 0};
         bool mine[2];
 #pragma unroll
@@ -590,9 +605,9 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                 while (i >= s_cbase[r + 1]) r++;
                 rr[q] = r;
                 const uint32_t m = s_cm0[r] + (i - s_cbase[r]);
-                cid[q] = a.ne_cell[m];
-                const uint32_t gs = a.ne_start[m];
-                np[q] = a.ne_start[m + 1] - gs;
+                cid[q] = ne_cell[m];
+                const uint32_t gs = ne_start[m];
+                np[q] = ne_start[m + 1] - gs;
                 ccell[i] = (uint16_t)cid[q];
                 gstart[i] = gs;
                 uint32_t *rec = recs + (size_t)kPsRecWords * i;
@@ -627,12 +642,18 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         }
     }
     for (uint32_t i = tid; i < 5 * K; i += kPsThreads) acc[i] = 0ull;
-    for (uint32_t i = tid; i < K; i += kPsThreads) tab[i] = a.cconst0[i];
+    for (uint32_t i = tid; i < kPsRunWords; i += kPsThreads) runs[i] = 0ull;
+    {
+        const uint2 *cconst0 = dev->p.cconst0;
+        for (uint32_t i = tid; i < K; i += kPsThreads) tab[i] = cconst0[i];
+    }
     __syncthreads();
     // ---- the block's points: colour, pixel count and the initial label (init_assignment, kmeans.rs:61-78) of every point of its cells,
     // as one packed word each, into LDS (the cells that fit) or the packed array in memory; a wave per cell, four loads in flight per array
     {
         const uint32_t Cres0 = s_Cres;
+        const uint32_t *ckeys = dev->p.ckeys, *cweight = dev->p.cweight;
+        const uint8_t *labels0 = dev->p.labels;
         for (uint32_t i = wid; i < C; i += kPsWaves) {
             const uint32_t s = cstart[i], n = cstart[i + 1] - s, gs = gstart[i];
             const uint32_t cbk = cell_base_key(ccell[i]);
@@ -643,9 +664,9 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                 for (int u = 0; u < 4; u++) {
                     const uint32_t t = t0 + u * 64 + lane;
                     const bool in = t < n;
-                    kk[u] = in ? a.ckeys[gs + t] : 0u;
-                    ww[u] = in ? a.cweight[gs + t] : 0u;
-                    ll[u] = in ? (uint32_t)a.labels[gs + t] : 0u;
+                    kk[u] = in ? ckeys[gs + t] : 0u;
+                    ww[u] = in ? cweight[gs + t] : 0u;
+                    ll[u] = in ? (uint32_t)labels0[gs + t] : 0u;
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
@@ -675,21 +696,24 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         return;
     }
     const uint32_t Cres = s_Cres, nslots = s_nslots;
-    const uint32_t row = (uint32_t)lane >> 4, l16 = (uint32_t)lane & 15u;
-    // running sums of cluster k = tid (kmeans.rs: the members of every cluster, as sums): registers, the same in every block
-    unsigned long long run[5] = {0, 0, 0, 0, 0};
     uint32_t moved = 0;
-    unsigned long long evals = 0;
+    unsigned long long evals = 0;   // (the same in every lane of a wave: scalar registers)
     uint32_t j = 0;              // the iteration whose assign step runs
     uint32_t nS = K;             // centroids the last update moved
-    unsigned long long reseeds_total = 0, evals_total = 0;
     for (;;) {
+        // The thread's coordinates anew in every iteration, from a value the compiler cannot see through: what it derives from them (lane
+        // masks, addresses, dozens of them) would otherwise be computed once in front of the loop and kept in registers across all of
+        // it -- which is what spilled.  Inside an iteration they are still computed once.
+        uint32_t tid_i = threadIdx.x;   // (_i: the iteration's own; tid, lane and wid of the set-up are used again by the write-out)
+        asm volatile("" : "+v"(tid_i));
+        const int lane_i = (int)(tid_i & 63u), wid_i = (int)(tid_i >> 6);
+        const uint32_t row = (uint32_t)lane_i >> 4, l16 = (uint32_t)lane_i & 15u;
         const bool first = j == 0;
         const bool skip_mode = !first && a.max_skip && nS <= a.max_skip;
         if (!skip_mode) {
             // ============================================================= FULL schedule: every cell's candidates anew
-            ps_build_lists(tab, K, nslots, s_ssup, s_nS, s_lpiv, Sent, wid, lane);
-            for (uint32_t i0 = (uint32_t)wid * 4; i0 < C; i0 += kPsWaves * 4) {   // a row of 16 lanes per cell
+            ps_build_lists(tab, K, nslots, s_ssup, s_nS, s_lpiv, Sent, wid_i, lane_i);
+            for (uint32_t i0 = (uint32_t)wid_i * 4; i0 < C; i0 += kPsWaves * 4) {   // a row of 16 lanes per cell
                 const uint32_t i = i0 + row;
                 if (i < C) {
                     const uint32_t c = ccell[i], slot = cslot[i];
@@ -719,14 +743,7 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             // ============================================================= SKIP schedule (at most max_skip centroids moved)
             // A cell none of whose candidates moved and whose pivot still dominates every moved centroid repeats all its decisions.  The
             // test, a row of 16 lanes per cell; what fails it goes on the list and is worked on by a whole wave below.
-            uint32_t mk[4], mc[4];   // the lane's share of the moved centroids: ids and colours
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const uint32_t jj = l16 + 16u * t;
-                mk[t] = jj < nS ? s_mlist[jj] : 0xffffffffu;
-                mc[t] = jj < nS ? s_mcol[jj] : 0u;
-            }
-            for (uint32_t i0 = (uint32_t)wid * 4; i0 < C; i0 += kPsWaves * 4) {
+            for (uint32_t i0 = (uint32_t)wid_i * 4; i0 < C; i0 += kPsWaves * 4) {
                 const uint32_t i = i0 + row;
                 const bool ok = i < C;
                 const uint32_t *rec = recs + (size_t)kPsRecWords * (ok ? i : 0u);
@@ -735,10 +752,12 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                 dm.set(cell_box(c), (1 << kCellShift) - 1, rec[0]);
                 bool dv = !(r1 & kPsComplete) && ((s_mm[lp >> 6] >> (lp & 63)) & 1ull) != 0ull;   // the list the mask came from lost its pivot
 #pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    if (mk[t] != 0xffffffffu) {
-                        const bool in = ((rec[2 + (mk[t] >> 5)] >> (mk[t] & 31)) & 1u) != 0;
-                        dv = dv | in | (dm.worst(mc[t]) >= 0);   // a moved centroid matters if it was a candidate or is no longer dominated by the pivot
+                for (int t = 0; t < 4; t++) {   // the lane's share of the moved centroids: ids and colours
+                    const uint32_t jj = l16 + 16u * t;
+                    if (jj < nS) {
+                        const uint32_t mk = s_mlist[jj], mc = s_mcol[jj];
+                        const bool in = ((rec[2 + (mk >> 5)] >> (mk & 31)) & 1u) != 0;
+                        dv = dv | in | (dm.worst(mc) >= 0);   // a moved centroid matters if it was a candidate or is no longer dominated by the pivot
                     }
                 }
                 const unsigned long long bm = __ballot(dv && ok);
@@ -752,12 +771,12 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             const bool agg = !first && j <= a.agg_iters;
             for (;;) {   // the waves draw cells from the list (what a cell costs depends on how many of its points move)
                 uint32_t qi = 0;
-                if (lane == 0) qi = atomicAdd(&s_qhead, 1u);
+                if (lane_i == 0) qi = atomicAdd(&s_qhead, 1u);
                 qi = (uint32_t)__builtin_amdgcn_readfirstlane((int)qi);
                 if (qi >= qn) break;
                 const uint32_t i = queue[qi];
                 const uint32_t s = cstart[i], e = cstart[i + 1], gs = gstart[i], c = ccell[i];
-                uint32_t rw = lane < (int)kPsRecWords ? recs[(size_t)kPsRecWords * i + lane] : 0u;
+                uint32_t rw = lane_i < (int)kPsRecWords ? recs[(size_t)kPsRecWords * i + lane_i] : 0u;
                 if (skip_mode) {
                     // ---- a dirty cell of the skip schedule: its mask brought up to date by the whole wave.  A mask whose pivot (and, unless
                     // complete, whose list's pivot) has not moved keeps every verdict on the centroids that have not moved: the moved ones
@@ -772,8 +791,8 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                     if (keep) {
                         Dominance dm;
                         dm.set(bx, ext, npv);
-                        const uint32_t k1 = (uint32_t)lane < nS ? s_mlist[lane] : 0xffffffffu;
-                        const uint32_t ck1 = (uint32_t)lane < nS ? s_mcol[lane] : 0u;
+                        const uint32_t k1 = (uint32_t)lane_i < nS ? s_mlist[lane_i] : 0xffffffffu;
+                        const uint32_t ck1 = (uint32_t)lane_i < nS ? s_mcol[lane_i] : 0u;
                         unsigned long long f1 = __ballot(k1 != 0xffffffffu && dm.worst(ck1) >= 0);
 #pragma unroll
                         for (int w = 0; w < 4; w++)
@@ -787,13 +806,13 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                             um[0] |= w == 0 ? bit : 0ull; um[1] |= w == 1 ? bit : 0ull; um[2] |= w == 2 ? bit : 0ull; um[3] |= w == 3 ? bit : 0ull;
                         }
                     } else {
-                        npid = nearest_to_centre(tab, K, bx, ext, lane);
+                        npid = nearest_to_centre(tab, K, bx, ext, lane_i);
                         npv = (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[npid].x);
                         Dominance dm;
                         dm.set(bx, ext, npv);
 #pragma unroll
                         for (int w = 0; w < 4; w++) {
-                            const uint32_t k = 64 * w + lane;
+                            const uint32_t k = 64 * w + lane_i;
                             um[w] = __ballot(k < K && dm.worst(tab[k < K ? k : 0].x) >= 0);
                         }
                         complete = true;
@@ -812,22 +831,22 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                     uint32_t nw = rw;
 #pragma unroll
                     for (int t = 0; t < 8; t++)
-                        if (lane == 2 + t) nw = (uint32_t)(um[t >> 1] >> (32 * (t & 1)));
-                    if (lane == 0) nw = npv;
-                    if (lane == 1) nw = r1n;
-                    if (lane == 10) nw = c4;
+                        if (lane_i == 2 + t) nw = (uint32_t)(um[t >> 1] >> (32 * (t & 1)));
+                    if (lane_i == 0) nw = npv;
+                    if (lane_i == 1) nw = r1n;
+                    if (lane_i == 10) nw = c4;
                     rw = nw;
-                    if (lane < (int)kPsRecWords) recs[(size_t)kPsRecWords * i + lane] = rw;
+                    if (lane_i < (int)kPsRecWords) recs[(size_t)kPsRecWords * i + lane_i] = rw;
                     const uint32_t ncd = (uint32_t)(__popcll(um[0]) + __popcll(um[1]) + __popcll(um[2]) + __popcll(um[3]));
                     if (ncd == 1 && (r1o & kPsUlMask) == (c4 & 255u)) continue;   // one candidate, and every point carries it: nothing can move
                 }
                 uint32_t wd[kSweep];
                 if (i < Cres) {
 #pragma unroll
-                    for (int u = 0; u < kSweep; u++) { const uint32_t idx = s + u * 64 + lane; wd[u] = idx < e ? pts[idx] : 0u; }
+                    for (int u = 0; u < kSweep; u++) { const uint32_t idx = s + u * 64 + lane_i; wd[u] = idx < e ? pts[idx] : 0u; }
                 } else {
 #pragma unroll
-                    for (int u = 0; u < kSweep; u++) { const uint32_t idx = s + u * 64 + lane; wd[u] = idx < e ? a.pk[gs + (idx - s)] : 0u; }
+                    for (int u = 0; u < kSweep; u++) { const uint32_t idx = s + u * 64 + lane_i; wd[u] = idx < e ? a.pk[gs + (idx - s)] : 0u; }
                 }
                 unsigned long long nm[4];
 #pragma unroll
@@ -846,49 +865,49 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                     if (base + 64 * kSweep < e) {   // (a cell of more than 256 points: its next sweep's words now)
                         if (res) {
 #pragma unroll
-                            for (int u = 0; u < kSweep; u++) { const uint32_t idx = base + 64 * kSweep + u * 64 + lane; w2[u] = idx < e ? pts[idx] : 0u; }
+                            for (int u = 0; u < kSweep; u++) { const uint32_t idx = base + 64 * kSweep + u * 64 + lane_i; w2[u] = idx < e ? pts[idx] : 0u; }
                         } else {
 #pragma unroll
-                            for (int u = 0; u < kSweep; u++) { const uint32_t idx = base + 64 * kSweep + u * 64 + lane; w2[u] = idx < e ? pkc[idx - s] : 0u; }
+                            for (int u = 0; u < kSweep; u++) { const uint32_t idx = base + 64 * kSweep + u * 64 + lane_i; w2[u] = idx < e ? pkc[idx - s] : 0u; }
                         }
                     }
                     if (res) {
                         auto st = [&](uint32_t idx, uint32_t l) { reinterpret_cast<uint8_t *>(pts)[4 * idx + 3] = (uint8_t)l; };
-                        if (first) ps_sweep_first(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, st);
-                        else uniform = ps_sweep(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st) && uniform;
+                        if (first) ps_sweep_first(wd, base, e, s, lane_i, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, st);
+                        else uniform = ps_sweep(wd, base, e, s, lane_i, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st) && uniform;
                     } else {
                         auto st = [&](uint32_t idx, uint32_t l) { reinterpret_cast<uint8_t *>(pkc)[4 * (size_t)(idx - s) + 3] = (uint8_t)l; };
-                        if (first) ps_sweep_first(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, st);
-                        else uniform = ps_sweep(wd, base, e, s, lane, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st) && uniform;
+                        if (first) ps_sweep_first(wd, base, e, s, lane_i, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, st);
+                        else uniform = ps_sweep(wd, base, e, s, lane_i, nm, ncand, cand4, tab, K, cbk, cwc, acc, moved, agg, st) && uniform;
                     }
 #pragma unroll
                     for (int u = 0; u < kSweep; u++) wd[u] = w2[u];
                 }
-                if (lane == 0) rec[1] = (r1 & ~kPsUlMask) | (uniform && ncand == 1 ? cand4 & 255u : kPsUlMask);
-                evals += (unsigned long long)(e - s) * (ncand + 1);
+                if (lane_i == 0) rec[1] = (r1 & ~kPsUlMask) | (uniform && ncand == 1 ? cand4 & 255u : kPsUlMask);
+                evals += (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(e - s)) * (ncand + 1);
             }
         }
         // ------------------------------------------------------------- this iteration's deltas leave the block
         moved = wave_reduce_sum(moved);
-        if (lane == 0) {
+        if (lane_i == 0) {
             if (moved) atomicAdd(&s_moved, moved);
             if (evals) atomicAdd(&s_evals, evals);
         }
         moved = 0; evals = 0;
         __syncthreads();
-        unsigned long long *Pcur = a.partials + (size_t)(j % 3) * kPsPartWords;
-        for (uint32_t i = tid; i < 5 * K; i += kPsThreads) {
+        unsigned long long *Pcur = ps_partials(a.bar) + (size_t)(j % 3) * kPsPartWords;
+        for (uint32_t i = tid_i; i < 5 * K; i += kPsThreads) {
             const unsigned long long v = acc[i];
             if (v) { __hip_atomic_fetch_add(&Pcur[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); acc[i] = 0ull; }
         }
-        if (tid == 0) {
+        if (tid_i == 0) {
             if (s_moved) __hip_atomic_fetch_add(&Pcur[5 * (size_t)K], (unsigned long long)s_moved, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (s_evals) __hip_atomic_fetch_add(&Pcur[5 * (size_t)K + 1], s_evals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s_moved = 0; s_evals = 0; s_qn = 0; s_qhead = 0; s_nmoved = 0; s_reseed = 0; s_active = 0; s_mm[0] = s_mm[1] = s_mm[2] = s_mm[3] = 0ull;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's atomics have been performed before its block arrives
         __syncthreads();
-        if (tid == 0) {
+        if (tid_i == 0) {
             bool ok = ps_barrier_xcd(a.bar, ps_xcc_id(), s_nx, s_nxcd, a.timeout_ticks);
 #ifdef CNIIC_TESTING
             if (a.test_abort_at && j + 1 == a.test_abort_at) { ps_st(&a.bar->abort_.v, 1u); ok = false; }   // (fault injection: CNIIC_TEST_PS_ABORT_AT)
@@ -897,24 +916,25 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         }
         __syncthreads();
         if (!s_ok) {
-            if (tid == 0) { a.cold->exit.status = kPsStatusAborted; __threadfence_system(); }
+            if (tid_i == 0) { a.cold->exit.status = kPsStatusAborted; __threadfence_system(); }
             return;
         }
         j++;
         // ------------------------------------------------------------- finish iteration j - 1: Point::mean for ColorCount (clusterc.rs:83-113)
         // + empty-cluster reseed (kmeans.rs:110-137), redundantly in every block: the sums are the same everywhere
         if (blockIdx.x == 0) {   // the buffer iteration j + 1 adds into (every block has read it: they all came through the barrier)
-            unsigned long long *Pclr = a.partials + (size_t)((j + 1) % 3) * kPsPartWords;
-            for (uint32_t i = tid; i < 5 * K + 2; i += kPsThreads) __hip_atomic_store(&Pclr[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned long long *Pclr = ps_partials(a.bar) + (size_t)((j + 1) % 3) * kPsPartWords;
+            for (uint32_t i = tid_i; i < 5 * K + 2; i += kPsThreads) __hip_atomic_store(&Pclr[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (tid < K) {
-            const uint32_t k = tid;
+        if (tid_i < K) {
+            const uint32_t k = tid_i;
             const size_t at[5] = {3 * (size_t)k, 3 * (size_t)k + 1, 3 * (size_t)k + 2, 3 * (size_t)K + k, 4 * (size_t)K + k};
             unsigned long long d[5];
 #pragma unroll
             for (int i = 0; i < 5; i++) d[i] = ps_aread(&Pcur[at[i]]);
+            unsigned long long run[5];   // the running sums of cluster k, the same in every block (they live in LDS between the updates)
 #pragma unroll
-            for (int i = 0; i < 5; i++) run[i] += d[i];
+            for (int i = 0; i < 5; i++) { run[i] = runs[256 * i + k] + d[i]; runs[256 * i + k] = run[i]; }
             uint32_t ck;
             if (run[4] == 0) {
                 const PsCold *cd = a.cold;
@@ -934,18 +954,18 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                 if (pos < kMaxMovedSkip) { s_mlist[pos] = k; s_mcol[pos] = ck; }
                 atomicOr(&s_mm[(k >> 6) & 3], 1ull << (k & 63));
             }
-        } else if (tid == kPsThreads - 1) {
+        } else if (tid_i == kPsThreads - 1) {
             s_changed = ps_aread(&Pcur[5 * (size_t)K]);
             s_pev = ps_aread(&Pcur[5 * (size_t)K + 1]);
         }
         __syncthreads();
         const unsigned long long changed = s_changed;
         nS = s_nmoved;
-        reseeds_total += s_reseed;
-        evals_total += s_pev;
         const bool fin = changed == 0 || (a.max_iters && j >= a.max_iters);
-        if (blockIdx.x == 0 && tid == 0) {
+        if (blockIdx.x == 0 && tid_i == 0) {
             KmDevState *sw = a.st_rw;
+            const unsigned long long reseeds_total = s_rtot + s_reseed, evals_total = s_etot + s_pev;
+            s_rtot = reseeds_total; s_etot = evals_total;
             sw->changed_ring[(j - 1) % kHistRing] = changed;
             sw->nmoved_ring[(j - 1) % kHistRing] = nS;
             if (fin) {
@@ -962,13 +982,14 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         const uint2 cc = tab[tid];
         cd->cent_g[tid] = cc.x;
         cd->cconst_g[tid] = cc;
-        cd->members_out[tid] = run[4];
-        cd->wsum_out[tid] = run[3];
+        cd->members_out[tid] = runs[256 * 4 + tid];
+        cd->wsum_out[tid] = runs[256 * 3 + tid];
     }
+    uint8_t *labels = dev->p.labels;
     for (uint32_t i = wid; i < C; i += kPsWaves) {   // the labels of the block's points, a wave per cell
         const uint32_t s = cstart[i], n = cstart[i + 1] - s, gs = gstart[i];
-        if (i < Cres) { for (uint32_t t = lane; t < n; t += 64) a.labels[gs + t] = (uint8_t)(255u - (pts[s + t] >> 24)); }
-        else { for (uint32_t t = lane; t < n; t += 64) a.labels[gs + t] = (uint8_t)(255u - (a.pk[gs + t] >> 24)); }
+        if (i < Cres) { for (uint32_t t = lane; t < n; t += 64) labels[gs + t] = (uint8_t)(255u - (pts[s + t] >> 24)); }
+        else { for (uint32_t t = lane; t < n; t += 64) labels[gs + t] = (uint8_t)(255u - (a.pk[gs + t] >> 24)); }
     }
     if (blockIdx.x == 0) {
         __syncthreads();
@@ -1021,20 +1042,21 @@ int ps_prepare(KmRgbwState *s) {
         CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_rgbw_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPsDynBytes));
         attr_set[c->device] = true;
     }
-    const uint64_t o_bar = 0, o_part = (sizeof(PsBar) + 255) & ~255ull, o_fail = o_part + ((3 * (uint64_t)kPsPartWords * 8 + 255) & ~255ull);
-    const uint64_t o_rng = o_fail + 256, total = o_rng + ((uint64_t)G * kPsChunks + 1) * 4;
+    const uint64_t o_part = kPsArenaPart, o_fail = kPsArenaFail, o_rng = kPsArenaRng, total = o_rng + ((uint64_t)G * kPsChunks + 1) * 4;
     CNIIC_HIP_TRY(c, s->ps_arena.alloc(total));
     CNIIC_HIP_TRY(c, hipMemsetAsync(s->ps_arena.p, 0, o_rng, c->stream));
     CNIIC_HIP_TRY(c, s->ps_pk.alloc(std::max<uint64_t>(s->U, 1) * 4));
     s->ps_blocks = G;
     s->ps_o_part = o_part; s->ps_o_fail = o_fail; s->ps_o_rng = o_rng;
-    (void)o_bar;
     uint8_t *a = s->ps_arena.as<uint8_t>();
-    uint32_t budget = kPsDynBytes;   // (the tests shrink it: CNIIC_TEST_PS_LDS_BYTES leaves most cells' points in memory)
-    if (const char *e = test_env("CNIIC_TEST_PS_LDS_BYTES")) budget = std::min<uint32_t>(kPsDynBytes, (uint32_t)atoi(e));
+    uint32_t budget = kPsBudget;   // (the tests shrink it: CNIIC_TEST_PS_LDS_BYTES leaves most cells' points in memory)
+    if (const char *e = test_env("CNIIC_TEST_PS_LDS_BYTES")) budget = std::min<uint32_t>(kPsBudget, (uint32_t)atoi(e));
     s->ps_budget = budget;
+    PsDevPtrs ptrs{};
+    ptrs.ckeys = s->ckeys.as<uint32_t>(); ptrs.cweight = s->cweight.as<uint32_t>(); ptrs.labels = s->labels.as<uint8_t>();
+    ptrs.ne_cell = s->ne_cell.as<uint32_t>(); ptrs.ne_start = s->ne_start.as<uint32_t>(); ptrs.cconst0 = s->cconst.as<uint2>();
     hipLaunchKernelGGL(k_ps_ranges, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)s->ne_cost.as<uint32_t>(), (const uint32_t *)s->ne_count.as<uint32_t>(), G, budget,
-                       reinterpret_cast<uint32_t *>(a + o_rng), reinterpret_cast<uint32_t *>(a + o_fail));
+                       reinterpret_cast<uint32_t *>(a + o_rng), reinterpret_cast<PsDev *>(a + o_fail), ptrs);
     CNIIC_HIP_TRY(c, hipGetLastError());
     s->ps = true;
     return CNIIC_OK;
@@ -1058,12 +1080,10 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     PsExit *xh = &cold->exit;
     uint8_t *ar = s->ps_arena.as<uint8_t>();
     PsArgs a{};
-    a.ckeys = s->ckeys.as<uint32_t>(); a.cweight = s->cweight.as<uint32_t>(); a.labels = s->labels.as<uint8_t>();
-    a.ne_cell = s->ne_cell.as<uint32_t>(); a.ne_start = s->ne_start.as<uint32_t>();
-    a.cb = reinterpret_cast<const uint32_t *>(ar + s->ps_o_rng); a.ranges_fail = reinterpret_cast<const uint32_t *>(ar + s->ps_o_fail);
+    a.cweight = s->cweight.as<uint32_t>();
     a.lds_budget = s->ps_budget;
-    a.pk = s->ps_pk.as<uint32_t>(); a.cconst0 = s->cconst.as<uint2>();
-    a.partials = reinterpret_cast<unsigned long long *>(ar + s->ps_o_part); a.bar = reinterpret_cast<PsBar *>(ar);
+    a.pk = s->ps_pk.as<uint32_t>();
+    a.bar = reinterpret_cast<PsBar *>(ar);   // (the sums, PsDev and the chunk boundaries behind it: ps_prepare)
     cold->cconst_g = s->cconst.as<uint2>(); cold->cent_g = s->cent.as<uint32_t>(); cold->members_out = s->members_last.as<uint64_t>(); cold->wsum_out = s->wsum_last.as<uint64_t>();
     cold->keys = s->keys; cold->gx = s->gidx; cold->seed = s->seed; cold->U = s->gidx.bits ? s->gidx.U : s->U;
     a.st_rw = s->dstate.as<KmDevState>(); a.cold = cold; a.max_iters = s->max_iters;

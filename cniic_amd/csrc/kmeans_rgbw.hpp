@@ -66,7 +66,7 @@ struct KmRgbwState {
     bool ps_pending = false;     // the persistent launch is in the stream and nobody has looked at how it ended yet (km_rgbw_run with may_defer): km_rgbw_result_end does
     std::shared_ptr<void> ps_hold;   // the CUs promised to that launch, given back when the verdict is in (or the state goes)
     uint32_t ps_blocks = 0;
-    DevBuf ps_arena;             // [PsBar | 3 x kPsPartWords sums | fail word | PsRange[ps_blocks]]
+    DevBuf ps_arena;             // [PsBar | 3 x kPsPartWords sums | PsDev | chunk boundaries] (kPsArena*, below)
     DevBuf ps_pk;                // packed words of the points that do not fit their block's LDS
     uint64_t ps_o_part = 0, ps_o_fail = 0, ps_o_rng = 0;
     uint32_t ps_budget = 0;      // bytes of dynamic LDS the block ranges were made for
@@ -85,11 +85,25 @@ constexpr uint32_t kPsRecWords = 11;                    // a cell's record: pivo
 constexpr uint32_t kPsMaxCells = 2048;                  // cells a block may own (two per thread of its set-up)
 constexpr uint32_t kPsOffCell = 5 * 256 * 8 + 256 * 8 + kPsSlotsMax * kPsScap * 4;   // accumulators, table, the shared lists (id << 24 | colour)
 constexpr uint32_t kPsDynBytes = 160 * 1024 - 3072;     // the launch's dynamic LDS (the kernel's static variables take the rest)
+constexpr uint32_t kPsRunWords = 5 * 256;               // u64 running sums of the clusters (K <= 256): the top of the dynamic LDS, behind ...
+constexpr uint32_t kPsBudget = kPsDynBytes - kPsRunWords * 8;   // ... what the block ranges are made for and a block's cells and points may take (the tests shrink it)
 constexpr uint32_t kPsPartWords = 5 * 256 + 8;          // u64 words of one buffer of sums (5K + 2, padded)
 // per cell (C rounded up to a multiple of 4): first point u32 (own numbering; + 4 words), first point u32 (cell-major), record, id u16, work list u16, list slot u8
 __host__ __device__ constexpr uint32_t ps_cell_bytes(uint32_t C) { return 16u + ((C + 3u) & ~3u) * (4u + 4u + kPsRecWords * 4u + 2u + 2u + 1u); }
+static_assert(kPsOffCell + ps_cell_bytes(kPsMaxCells) <= kPsBudget, "a full block's descriptors fit the budget");
 struct alignas(128) PsLine { uint32_t v; uint32_t pad[31]; };
 struct PsBar { PsLine xcount[8], xgen[8], xblocks[8], top, topgen, count, gen, abort_; };   // every counter on a line of its own
+// the launch's arena (KmRgbwState::ps_arena): [PsBar | 3 x kPsPartWords sums | PsDev | chunk boundaries u32[ps_blocks x kPsChunks + 1]]; everything in front of
+// the boundaries is zero when k_ps_ranges starts
+struct PsDevPtrs {                        // what only the launch's set-up and write-out read (k_ps_ranges leaves it in device memory)
+    const uint32_t *ckeys, *cweight;      // cell-major colours and pixel counts
+    uint8_t *labels;                      // cell-major labels: the initial assignment on entry, the result on a regular exit
+    const uint32_t *ne_cell, *ne_start;   // compacted non-empty cells: id, first position
+    const uint2 *cconst0;                 // the initial centroids (k_rgbw_init_cent)
+};
+struct PsDev { uint32_t fail, pad; PsDevPtrs p; };   // fail: some block's cells do not fit its LDS (k_ps_ranges): no block starts
+constexpr uint32_t kPsArenaPart = (sizeof(PsBar) + 255u) & ~255u, kPsArenaFail = kPsArenaPart + ((3u * kPsPartWords * 8u + 255u) & ~255u), kPsArenaRng = kPsArenaFail + 256u;
+static_assert(sizeof(PsDev) <= 256, "PsDev has 256 bytes of the arena");
 constexpr uint32_t kPsStatusDone = 1, kPsStatusAborted = 2, kPsStatusRanges = 3;
 struct PsExit { uint32_t status, pad; uint64_t iter, moved_last, reseeds, active, pair_evals; };   // pinned: how the launch ended
 void launch_rgbw_assign_big(Ctx *c, const uint32_t *ckeys, const uint32_t *cweight, uint64_t U, uint32_t K, const uint32_t *cent, uint16_t *labels,
