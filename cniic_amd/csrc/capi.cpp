@@ -15,6 +15,7 @@
 #include "huff_host.hpp"
 #include "surf_index.hpp"
 #include "cc_small.hpp"
+#include "vor_small.hpp"
 #include "delta_small.hpp"
 
 using namespace cniic;
@@ -1322,6 +1323,36 @@ static uint64_t delta_small_max_px() {
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallMaxPx);
     return kDeltaSmallMaxPx;
 }
+// Small voronoi(K <= 256) frames in device memory (1 .. kVorSmallMaxPx pixels, no K-means flags) likewise: vor_small_encode (codec.cpp), a
+// workgroup per frame from the pixels through the whole K-means to the finished stream ("vor_small_batch": k_vor_small, launches = the
+// frames that took the route; "vor_small_place").  The testing library can switch it off (CNIIC_TEST_VOR_SMALL_OFF=1), lower its bound
+// (CNIIC_TEST_VOR_SMALL_MAX_PX) and run it without the stay test (CNIIC_TEST_VOR_SMALL_NO_STAY=1, read in vor_small_encode).  Few heavy
+// frames stay with the workers: vor_small_max_work below.
+static uint64_t vor_small_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_OFF")) if (atoi(e) != 0) return 0;
+    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kVorSmallMaxPx);
+    return kVorSmallMaxPx;
+}
+// The floor of that route.  One workgroup on one CU is slower for ONE heavy frame than the workers' whole chip; what the route costs is set by
+// its heaviest frame (every frame has a CU of its own up to 256 frames), what the workers cost grows with the number of frames.  Measured
+// against the parent commit's library (tools/small_voronoi_probe.py, profiles/small_voronoi_probe.json; NOTES AD), in pixels x K of a frame,
+// parent's time / this route's:
+//   1 frame:    won at 16 384 .. 65 536 (1.8x .. 2.9x), mixed at 196 608 .. 262 144 (0.65x .. 1.9x), lost from 786 432 on (0.75x .. 0.05x)
+//   8 frames:   won up to 786 432 (1.3x .. 7.4x); at 1 048 576 four shapes won (1.05x .. 1.9x) and 16384 x 1 noise lost (0.55x); lost at
+//               3 .. 4 M (0.14x .. 0.82x; one shape 1.07x)
+//   64 frames:  at 4 194 304 three shapes won (2.4x .. 3.8x) and 16384 x 1 noise lost (0.55x: 31 ms against 0.27 ms a frame on the workers,
+//               which breaks even at 117 frames)
+//   256 frames and more: every shape won (2.0x .. 126x)
+// So a frame takes the route when its pixels x K are at most 131 072 (between the last product that always won and the first that lost) in a
+// call with fewer than 8 candidate frames, at most 786 432 (the last that always won) with 8 .. 127, and whatever its product with 128 or
+// more.  The other candidates go to the workers like every larger frame.  The testing library takes the floor away with
+// CNIIC_TEST_VOR_SMALL_FLOOR_OFF=1.
+constexpr uint32_t kVorSmallFloorFew = 8, kVorSmallFloorMany = 128;
+constexpr uint64_t kVorSmallFloorWorkFew = 131072, kVorSmallFloorWorkSome = 786432;
+static uint64_t vor_small_max_work(uint64_t candidates) {
+    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
+    return candidates >= kVorSmallFloorMany ? ~0ull : candidates >= kVorSmallFloorFew ? kVorSmallFloorWorkSome : kVorSmallFloorWorkFew;
+}
 
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
     const uint32_t n = (uint32_t)fr.size();
@@ -1349,6 +1380,31 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
             std::map<std::string, KernelTime> mine;
             mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
             const int32_t rc = cc_small_encode(c, d.arg, opts, small.data(), (uint32_t)small.size());
+            mine.swap(c->ktimes);
+            CNIIC_TRY(rc);
+            if (c->timers) kt.swap(mine);
+            order.swap(rest);
+        }
+    }
+    // ---- the small voronoi frames, together
+    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_VORONOI && d.arg >= 1 && d.arg <= kVorSmallMaxK && (!opts || opts->flags == 0)) {
+        const uint64_t max_px = vor_small_max_px();
+        std::vector<VarFrame *> small;
+        std::vector<uint32_t> rest;
+        uint64_t candidates = 0;
+        for (uint32_t j = 0; j < n; j++) {
+            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
+            candidates += px >= 1 && px <= max_px;
+        }
+        const uint64_t max_work = vor_small_max_work(candidates);   // (the floor: few frames, large pixels x K -- the workers are faster)
+        for (uint32_t j = 0; j < n; j++) {
+            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
+            if (px >= 1 && px <= max_px && px * d.arg <= max_work) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
+        }
+        if (!small.empty()) {
+            std::map<std::string, KernelTime> mine;
+            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
+            const int32_t rc = vor_small_encode(c, d.arg, opts, small.data(), (uint32_t)small.size());
             mine.swap(c->ktimes);
             CNIIC_TRY(rc);
             if (c->timers) kt.swap(mine);

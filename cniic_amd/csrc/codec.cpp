@@ -11,6 +11,7 @@
 //   Zip::Dict       src/codec/zipc.rs         `zip(dict)`: the dictionary coder over the serialised image (zipdict.cpp, k_zipdict.hip)
 #include "codec.hpp"
 #include "cc_small.hpp"
+#include "vor_small.hpp"
 #include "delta_small.hpp"
 #include "delta_small_dec.hpp"
 #include "small_trie.hpp"
@@ -1224,6 +1225,89 @@ int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
     return CNIIC_OK;
 }
 
+// ---- small voronoi(K) frames of a batch call, all at once (codec.hpp; k_vor_small.hip)
+// A chunk's scratch is a slot per frame for the stream (16 + 19 K bytes, rounded up to 16), its row and its result row; the chunks stay
+// below 2 GiB (the testing library: below CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least).
+constexpr uint64_t kVorSmallScratch = 2ull << 30;
+static uint64_t vor_small_budget() {
+    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kVorSmallScratch);
+    return kVorSmallScratch;
+}
+static uint64_t vor_small_slot(uint32_t K) { return ((uint64_t)vs_stream_len(K) + 15) & ~15ull; }
+
+static int vor_small_chunk(Ctx *c, uint32_t K, uint64_t seed, uint64_t max_iters, bool stay_test, VarFrame *const *fr, uint32_t n) {
+    const uint64_t sstride = vor_small_slot(K), len = vs_stream_len(K);
+    std::vector<VorSmallRow> rows(n);
+    for (uint32_t i = 0; i < n; i++) rows[i] = VorSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
+    DevBuf rows_d, res_d, scratch;
+    CNIIC_HIP_TRY(c, rows_d.alloc((uint64_t)n * sizeof(VorSmallRow)));
+    CNIIC_HIP_TRY(c, res_d.alloc((uint64_t)n * sizeof(VorSmallResult)));
+    CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(VorSmallRow), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedKernelTimer t(c, "vor_small_batch");
+        CNIIC_TRY(vor_small_run(c, rows_d.as<VorSmallRow>(), n, fr[0]->w * fr[0]->h, K, seed, max_iters, stay_test, scratch.as<uint8_t>(), sstride,
+                                res_d.as<VorSmallResult>()));   // (largest first)
+        t.stop(n);
+    }
+    std::vector<VorSmallResult> res(n);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, (size_t)n * sizeof(VorSmallResult), hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // ---- every frame's outcome, as the single call reports it; every good stream to its own place
+    const bool out_dev = is_device_ptr(fr[0]->out);
+    std::vector<CcSmallPlace> pl;
+    for (uint32_t i = 0; i < n; i++) {
+        VarFrame &f = *fr[i];
+        const VorSmallResult &r = res[i];
+        if (r.status > 1 || r.n != (uint64_t)f.w * f.h) return c->fail(CNIIC_ERR_HIP, "vor_small: frame %u of the chunk reported no result", i);
+        if (r.status) {
+            f.rc = c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu points for %u clusters (src/kmeans.rs:68)", (unsigned long long)r.n, K);
+            f.msg = c->err;
+            continue;
+        }
+        f.st.iterations = r.iterations; f.st.moved_last = r.moved_last; f.st.empty_reseeds = r.reseeds; f.st.active = r.active;
+        f.st.pair_evals = r.evals;
+        f.rc = check_enough_active(c, K, r.n, r.active);
+        if (f.rc != CNIIC_OK) { f.msg = c->err; continue; }
+        f.len = len;
+        if (f.len > f.cap) {
+            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
+            f.msg = c->err;
+            continue;
+        }
+        pl.push_back(CcSmallPlace{sstride * i, f.out, f.len});
+    }
+    if (pl.empty()) return CNIIC_OK;
+    if (out_dev) {
+        DevBuf pl_d;
+        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
+        ScopedKernelTimer t(c, "vor_small_place");
+        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
+        t.stop(1);
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<uint8_t> host(sstride * n);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
+    }
+    return CNIIC_OK;
+}
+
+int vor_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n) {
+    const uint64_t seed = (opts && opts->seed) ? opts->seed : kDefaultSeed, max_iters = opts ? opts->max_iters : 0;
+    bool stay_test = true;
+    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_NO_STAY")) stay_test = atoi(e) == 0;
+    const uint64_t room = std::max<uint64_t>(1, vor_small_budget() / (vor_small_slot(K) + sizeof(VorSmallRow) + sizeof(VorSmallResult)));
+    for (uint32_t at = 0; at < n;) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
+        CNIIC_TRY(vor_small_chunk(c, K, seed, max_iters, stay_test, fr + at, cnt));
+        at += cnt;
+    }
+    return CNIIC_OK;
+}
+
 // How well the handle's palette fits a batch of frames: sse_h[f] = the exact sum over frame f's pixels of the squared distance to the pixel's entry
 // under the rule (3 w h times the MSE of decoding that frame's palette_encode_frames_var stream), pixels_h[k] (may be null) = the pixels of all
 // frames whose entry is k.  One launch (k_palette_fit) over the frame table of the var route; no labels are stored.
@@ -2030,6 +2114,68 @@ static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, 
     return CNIIC_OK;
 }
 
+// ------------------------------------------------------------------ small `voronoi` frames of a batch (k_vor_small.hip k_vor_small_dec)
+// codec_decode_batch_route has parsed the heads exactly as codec_decode does; what it hands over are the frames whose header and whole
+// centroid list are there and well formed, with 1 <= K <= kVorSmallMaxK, 1 <= w h <= kVorSmallMaxPx and an image that fits img_stride:
+// cent[f] = where frame f's centroids start in `table` (three words each: x, y, 0xRRGGBB), Ks[f] = how many.  They are worked through in
+// chunks whose scratch -- the centroids, the rows, and for a host destination the staged images -- stays below the budget: per chunk one
+// copy up, ONE launch with a workgroup per slice of kVorSmallDecSlice pixels of a frame, for a host destination one copy down (a memcpy per frame then puts the images in place),
+// one wait.  Every routed frame decodes: there is no status to fetch.
+static uint64_t vor_small_dec_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_DEC_OFF")) if (atoi(e) != 0) return 0;
+    return kVorSmallMaxPx;
+}
+static int vor_small_decode(Ctx *c, uint8_t *rgb, bool dst_dev, uint64_t img_stride, const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route,
+                            const std::vector<uint32_t> &table, const std::vector<uint64_t> &cent, const std::vector<uint32_t> &Ks, std::vector<uint8_t> &taken) {
+    const uint64_t budget = vor_small_budget();
+    auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
+    auto slices_of = [&](uint32_t f) { return (w[f] * h[f] + kVorSmallDecSlice - 1) / kVorSmallDecSlice; };   // (a workgroup's share of a frame: k_vor_small.hip)
+    auto scratch_of = [&](uint32_t f) { return (uint64_t)Ks[f] * 12 + slices_of(f) * sizeof(VorSmallDecRow) + (dst_dev ? 0 : img_room(f)); };
+    for (size_t i0 = 0; i0 < route.size();) {
+        size_t i1 = i0;
+        uint64_t need = 0;
+        while (i1 < route.size() && (i1 == i0 || need + scratch_of(route[i1]) <= budget)) need += scratch_of(route[i1++]);
+        const size_t S = i1 - i0;
+        uint64_t cents = 0, img_bytes = 0, slices = 0;
+        for (size_t i = 0; i < S; i++) { cents += Ks[route[i0 + i]]; slices += slices_of(route[i0 + i]); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }
+        const uint64_t tab_at = (slices * sizeof(VorSmallDecRow) + 15) & ~15ull, up_bytes = tab_at + cents * 12;
+        std::vector<uint8_t> up(up_bytes);
+        DevBuf up_d, img_d;
+        CNIIC_HIP_TRY(c, up_d.alloc(up_bytes));
+        if (img_bytes) CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
+        VorSmallDecRow *rows = reinterpret_cast<VorSmallDecRow *>(up.data());
+        std::vector<uint64_t> img_at(S, 0);
+        uint64_t cat = 0, iat = 0, rat = 0;
+        uint32_t max_px = 0;
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            memcpy(up.data() + tab_at + cat * 12, table.data() + 3 * cent[f], (size_t)Ks[f] * 12);
+            for (uint32_t px0 = 0; px0 < w[f] * h[f]; px0 += kVorSmallDecSlice)
+                rows[rat++] = VorSmallDecRow{dst_dev ? rgb + (uint64_t)f * img_stride : img_d.as<uint8_t>() + iat, (uint32_t)cat, Ks[f], w[f], h[f], px0, 0u};
+            cat += Ks[f];
+            img_at[i] = iat;
+            if (!dst_dev) iat += img_room(f);
+            max_px = std::max(max_px, w[f] * h[f]);
+        }
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, up.data(), up_bytes, hipMemcpyHostToDevice, c->stream));
+        {
+            ScopedKernelTimer t(c, "vor_small_dec_batch");
+            CNIIC_TRY(vor_small_dec_run(c, up_d.as<VorSmallDecRow>(), (uint32_t)slices, max_px, reinterpret_cast<const uint32_t *>(up_d.as<uint8_t>() + tab_at)));
+            t.stop(S);
+        }
+        std::vector<uint8_t> imgs_h(img_bytes);
+        if (img_bytes) CNIIC_HIP_TRY(c, hipMemcpyAsync(imgs_h.data(), img_d.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i];
+            taken[f] = 1;
+            if (!dst_dev) memcpy(rgb + (uint64_t)f * img_stride, imgs_h.data() + img_at[i], (uint64_t)w[f] * h[f] * 3);
+        }
+        i0 = i1;
+    }
+    return CNIIC_OK;
+}
+
 // ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
 // The heads of all frames come to the host together (one strided copy for streams in HBM), every decoder is parsed there (up to 16
 // threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev); `hilbert(rle)` frames have
@@ -2046,7 +2192,9 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     taken.assign(F, 0);
     rcs.assign(F, CNIIC_OK);
     msgs.assign(F, std::string());
-    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE && d.kind != CODEC_DELTA)) return CNIIC_OK;
+    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE && d.kind != CODEC_DELTA && d.kind != CODEC_VORONOI))
+        return CNIIC_OK;
+    if (d.kind == CODEC_VORONOI && !vor_small_dec_max_px()) return CNIIC_OK;
     const bool delta = d.kind == CODEC_DELTA;
     const uint64_t delta_max_px = delta ? delta_small_dec_max_px() : 0;
     if (delta && !delta_max_px) return CNIIC_OK;
@@ -2085,6 +2233,53 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
             for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
         }
         return rle_decode_batch_route(c, bytes, bytes_dev, stride, lens, F, rgb, dst_dev, img_stride, w, h, head_p, head_n, off_route, taken, rcs, msgs);
+    }
+    if (d.kind == CODEC_VORONOI) {
+        // `voronoi`: a stream is its header and at most 16 + 19 K bytes of centroids.  The heads of streams in HBM come down in groups of as many
+        // rows as the pinned block holds (never wider than the stride, the source pitch of the strided copy); a group is parsed before the
+        // next one takes its place.  A frame is the route's when the single decode's parse (codec_decode) goes through on what was looked
+        // at and the frame is small; every other frame is the caller's, with that decode's status and message.
+        std::vector<uint32_t> route, table, Ks(F, 0);
+        std::vector<uint64_t> cent(F, 0);
+        const uint64_t max_px = vor_small_dec_max_px();
+        auto classify = [&](uint32_t f) {
+            if (off_route[f]) return;
+            const uint8_t *hb = head_p[f];
+            const uint64_t nb = head_n[f];
+            uint64_t pos = 0, K;
+            uint32_t fw, fh;
+            if (!get_u32(hb, nb, pos, fw) || !get_u32(hb, nb, pos, fh) || !get_u64(hb, nb, pos, K)) return;
+            const uint64_t n = (uint64_t)fw * fh;
+            if (!n || n > max_px || n * 3 > img_stride || !K || K > kVorSmallMaxK || K > (nb - pos) / 19) return;
+            const size_t at = table.size();
+            for (uint64_t k = 0; k < K; k++) {
+                uint32_t x, y;
+                uint64_t l;
+                if (!get_u32(hb, nb, pos, x) || !get_u32(hb, nb, pos, y) || !get_u64(hb, nb, pos, l) || l != 3 || pos + 3 > nb) { table.resize(at); return; }
+                table.push_back(x); table.push_back(y);
+                table.push_back((uint32_t)hb[pos] << 16 | (uint32_t)hb[pos + 1] << 8 | hb[pos + 2]);
+                pos += 3;
+            }
+            w[f] = fw; h[f] = fh;
+            cent[f] = at / 3; Ks[f] = (uint32_t)K;
+            route.push_back(f);
+        };
+        if (bytes_dev) {
+            const uint64_t W = std::min<uint64_t>(vs_stream_len(kVorSmallMaxK), stride);
+            if (!W && F > 1) return CNIIC_OK;   // (streams on top of one another: every frame to the single decode)
+            const uint64_t Wf = W ? W : vs_stream_len(kVorSmallMaxK);   // (one frame: its stride does not matter)
+            const uint32_t group = (uint32_t)std::max<uint64_t>(1, kBatchHeadsMax / Wf);
+            for (uint32_t f0 = 0; f0 < F;) {
+                const uint32_t f1 = (uint32_t)std::min<uint64_t>((uint64_t)f0 + group, F) - 1;
+                CNIIC_TRY(fetch(Wf, f0, f1));
+                for (uint32_t f = f0; f <= f1; f++) classify(f);
+                f0 = f1 + 1;
+            }
+        } else {
+            for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; classify(f); }
+        }
+        if (route.empty()) return CNIIC_OK;
+        return vor_small_decode(c, rgb, dst_dev, img_stride, w, h, route, table, cent, Ks, taken);
     }
     // `delta` streams in device memory: the decoders are parsed there, and the host looks only at the frames that parse hands back
     std::vector<uint32_t> all;

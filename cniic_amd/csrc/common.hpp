@@ -940,6 +940,20 @@ struct SmallTrieRow { const uint8_t *stream; uint32_t *table; uint64_t bytes; };
 struct SmallTrieResult { uint32_t w, h, verdict, leaves, max_len, payload_at; };
 int small_trie_run(Ctx *c, const SmallTrieRow *rows_d, uint32_t frames, uint64_t max_bytes /* of the longest stream */, uint32_t max_px, uint64_t img_stride,
                    uint32_t scan_w, uint32_t scan_h, SmallTrieResult *res_d);
+// ---- k_vor_small.hip: voronoi(K <= 256) of small frames, one workgroup per frame (vor_small.hpp has the arithmetic, the limits and the
+// stream's layout).  A row per frame: its pixels (device memory, any alignment).  Frame f's finished stream (16 + 19 K bytes) lands at
+// scratch_d + f * sstride, its K-means outcome in res_d[f].  stay_test: points well inside their cell skip the search (vs_stays; the
+// outcome is the same without it, res_d[f].evals is not).
+struct VorSmallRow { const uint8_t *src; uint32_t w, h; };
+struct VorSmallResult { uint32_t status /* 1: n / K == 0, nothing else was computed */, n, iterations, moved_last, reseeds, active; uint64_t evals; };
+int vor_small_run(Ctx *c, const VorSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t K, uint64_t seed, uint64_t max_iters,
+                  bool stay_test, uint8_t *scratch_d, uint64_t sstride, VorSmallResult *res_d);
+// The repaint of such frames' streams.  A row per frame: where its w x h x 3 image goes (device memory, any alignment) and its K centroids
+// (1 .. 256) in table_d from centroid cent0 on, three words each: x, y (any u32: the squares wrap as the reference's do) and 0xRRGGBB.
+// A row is a slice of a frame, a workgroup's share: the pixels from px0 (a multiple of kVorSmallDecSlice) on, at most kVorSmallDecSlice of them.
+constexpr uint32_t kVorSmallDecSlice = 2048;
+struct VorSmallDecRow { uint8_t *dst /* the frame's */; uint32_t cent0, K, w, h, px0, pad; };
+int vor_small_dec_run(Ctx *c, const VorSmallDecRow *rows_d, uint32_t slices, uint32_t max_px /* of the largest frame */, const uint32_t *table_d);
 // ---- k_palette.hip: the colour -> label table of a frozen palette (every colour's nearest entry, lowest index among equals).  table_d: 2^24
 // labels of 1 (K <= 256) or 2 bytes; list_max: candidates of a cell kept in LDS (<= kPalListMax, pal_bounds.hpp), a longer list sends the cell
 // down the plain route; plain_cells_d (optional): a zeroed counter of such cells

@@ -954,6 +954,20 @@ int km_xyrgb_run(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint32_t h, uint32_t 
     for (uint32_t k = 0; init_h && k < K; k++)
         if (init_h[k].x >= w || init_h[k].y >= h)
             return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_xyrgb: given centroid %u at (%u, %u) outside the %u x %u image", k, init_h[k].x, init_h[k].y, w, h);
+    // An image of ONE pixel: k_xy_assign reads an image's last pixel through the dword that ENDS with it, and three bytes hold no such dword
+    // (the load fell outside the buffer and the centroid came out black).  kmeans::cluster of one point in one cluster is that point, after one
+    // iteration in which nothing moves, whatever centroid it started from.
+    if ((uint64_t)w * h == 1 && K == 1) {
+        uint8_t px[3];
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(px, rgb_d, 3, hipMemcpyDeviceToHost, c->stream));
+        if (labels_d_u32) CNIIC_HIP_TRY(c, hipMemsetAsync(labels_d_u32, 0, 4, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        centroids_h[0].x = 0; centroids_h[0].y = 0; centroids_h[0].pad = 0;
+        memcpy(centroids_h[0].rgb, px, 3);
+        if (members_h) members_h[0] = 1;
+        if (stats) { stats->iterations = 1; stats->moved_last = 0; stats->empty_reseeds = 0; stats->active = 1; stats->pair_evals = 1; }
+        return CNIIC_OK;
+    }
     // beyond what the tiled kernel is laid out for (table and sums in LDS, 24-bit coordinate products): the exact, slow route
     if (K > kXMaxK || w > 16384 || h > 16384) return km_xyrgb_run_wide(c, rgb_d, w, h, K, opts, centroids_h, labels_d_u32, members_h, stats, init_h);
     KmXyState s;

@@ -552,7 +552,23 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
  * route go to the worker contexts as above; cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took
  * shows in no output byte, status or message; stats[f] stays zero as the single call leaves it.  Stage timers: "delta_small_batch" = the
  * duration of that kernel, with launches = the frames that took the route; "delta_small_place" = the copy of the finished streams to
- * out + f * stride. */
+ * out + f * stride.
+ *
+ * SMALL `voronoi` frames likewise, here and in cniic_codec_measure_batch: with the expression voronoi(K), 1 <= K <= 256, DEVICE images and
+ * opts NULL or opts->flags == 0 (seed and max_iters are honoured), every frame of 1 .. 16384 pixels is coded on ONE workgroup from its
+ * pixels to its finished stream of 16 + 19 K bytes: the pixels, their labels, the K centroids and the clusters' sums stay in the CU's LDS
+ * for the whole K-means (exact Lloyd over x, y, r, g, b in integers; a point whose squared distance to its own centroid, times four, does
+ * not exceed that centroid's squared distance to its nearest neighbour stays without a search, which the triangle inequality makes
+ * exact), with no launch boundary and no host round trip between iterations; all such frames of the call in one launch whatever their
+ * number.  Larger frames, host images, any CNIIC_KM_* flag, K = 0 or K > 256 go to the worker contexts as above, and so do FEW HEAVY
+ * frames, which the workers' whole chip codes faster than one CU each (measured): with n = the call's frames of 1 .. 16384 pixels, a frame
+ * takes the route when its pixels x K are at most 131072 for n < 8, at most 786432 for 8 <= n < 128, and always for n >= 128.
+ * cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took shows in no output byte, status or message
+ * (CNIIC_ERR_TOO_FEW_POINTS before CNIIC_ERR_FEW_ACTIVE before CNIIC_ERR_CAPACITY with lens[f] = bytes needed, as the single call).
+ * Stage timers: "vor_small_batch" = the duration of that kernel, with launches = the frames that took the route; "vor_small_place" = the
+ * copy of the finished streams to out + f * stride.  stats[f].pair_evals counts what the route that ran evaluated -- on this route one
+ * evaluation per point and iteration against its own centroid and K more for every point that was searched, on the workers what their
+ * pruned search evaluated; the other four fields do not depend on the route. */
 int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
                                      const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
                                      int32_t *rcs, cniic_kmeans_stats *stats);
@@ -654,7 +670,19 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
  * 19 bits, bytes that are no decoder -- is parsed on the host as before, and so is every decoder of a batch in host memory: the routed
  * frames, every status and every message are the same either way.  Stage timers, only when that parse ran: "delta_small_dec_parse" = the
  * duration of its launches, with launches = the frames it parsed; "delta_small_dec_parse_host" = no time, launches = the frames handed
- * back to the host's parse. */
+ * back to the host's parse.
+ *
+ * SMALL `voronoi` frames of a decode, here and in cniic_codec_measure_batch: with the expression voronoi(K) (the stream carries its own
+ * K), every frame whose header and whole centroid list are there and well formed, with 1 <= K <= 256 centroids, 1 .. 16384 pixels and an
+ * image that fits img_stride, is repainted on ONE workgroup (its centroids in the CU's LDS; every pixel the colour of the FIRST centroid
+ * with the smallest (c.x - x)^2 + (c.y - y)^2 in u32 arithmetic that wraps, as the single decode; the image stored whole, with 16-byte
+ * stores where the address allows and not a byte outside its 3 w h), all such frames of the call in one launch whatever their number.
+ * The heads come to the host as the other codecs' do (at most 16 + 19 * 256 = 4880 bytes of a stream in device memory, never more than
+ * stride) and are parsed there.  Host or device memory on either side, at any alignment.  Every other frame -- larger, K = 0 or K > 256,
+ * a truncated or malformed centroid, w h = 0, an image that does not fit, a head cut by a stride below the stream's length -- goes to
+ * the worker contexts as above, with the single decode's status and message.  Which route a frame took shows in no output byte, status
+ * or message.  Stage timer: "vor_small_dec_batch" = the duration of that kernel, with launches = the frames it was given;
+ * cniic_codec_measure_batch leaves it readable beside the encode's "vor_small_batch".  (A decode evaluates no K-means: no pair_evals.) */
 int32_t cniic_codec_decode_batch(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens,
                                  uint32_t frames, uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* bench::compute_error (src/bench.rs:95-104): MSE between two RGB8 images. */
