@@ -1711,6 +1711,8 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
                                                      delta ? 0 : 1, delta ? keys_d.p : (void *)dst, &status, delta ? &ud_sums : nullptr));
                     done_dev = status != 2;
                 }
+                // which parse answered (tests): the GPU's table, or the host's walk after the GPU parse was tried
+                if (c->timers) c->ktimes[done_dev ? "trie_parse" : "trie_parse_host"].launches += 1;
             }
             if (!done_dev) {  // the host's way: the whole stream there
                 if (bytes_dev) head.n = 0;

@@ -103,7 +103,11 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * With CNIIC_OPT_STAGE_TIMERS on, the Huffman code stage of a large alphabet adds three marks (launches only, no duration): "huf_tree_runs" =
  * 1 when the tree was built on the GPU from runs of equally frequent leaves, "huf_tree_host" = 1 when it came from the host's merge with
  * codes and decoder from the GPU, "huf_sort_passes" = the 8-bit radix passes of the leaves' sort by count.  None of them for a small
- * alphabet, whose tree and codes are the host's. */
+ * alphabet, whose tree and codes are the host's.
+ * A single decode whose serialised decoder outgrew the host's looks at the stream, so that the GPU parse (k_trieparse.hip) was tried, adds
+ * one of two marks (launches only, no duration): "trie_parse" = 1 when that parse's table decoded the payload, "trie_parse_host" = 1 when
+ * the stream was handed to the host's node walk instead (a leaf deeper than 56, a stack deeper than 120, or a payload the table's decoder
+ * gave up).  Neither when the host parsed the decoder in its first or second look. */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */

@@ -155,13 +155,17 @@ def test_decoder_parsed_on_the_gpu_equals_oracle(env, monkeypatch, expr, shape, 
     assert rco == 0
     monkeypatch.setenv("CNIIC_TEST_TRIE_GPU", "1")
     ctx.set_opt(_lib.OPT_GPU_DECODE_MIN, 0)
+    ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
     try:
         rc, back = ctx.decode(expr, data)
         assert rc == 0 and np.array_equal(back, exp)
+        # the GPU's table answered, not the host's walk behind it (the stage marks of include/cniic_hip.h)
+        assert (ctx.kernel_time("trie_parse")[1], ctx.kernel_time("trie_parse_host")[1]) == (1, 0)
         full = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
         out = torch.zeros(h * w * 3, dtype=torch.uint8, device=dev)
         rc, _, _ = ctx.decode_into(expr, full, len(data), out)
         assert rc == 0 and np.array_equal(out.cpu().numpy().reshape(h, w, 3), exp)
+        assert (ctx.kernel_time("trie_parse")[1], ctx.kernel_time("trie_parse_host")[1]) == (1, 0)
         rng = np.random.default_rng(h * w)
         cuts = [1, 2, 9, len(data) // 3, len(data) - 9, len(data) - 12] + rng.integers(1, max(2, len(data) - 8), 6).tolist()
         for cut in cuts:
@@ -181,6 +185,7 @@ def test_decoder_parsed_on_the_gpu_equals_oracle(env, monkeypatch, expr, shape, 
                 assert np.array_equal(b2, e2)
     finally:
         ctx.set_opt(_lib.OPT_GPU_DECODE_MIN, None)
+        ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
 
 
 @pytest.mark.parametrize("phases", ["1", "0", None, "verdict-off", "verdict-eager"])
