@@ -17,6 +17,7 @@
 #include "cc_small.hpp"
 #include "vor_small.hpp"
 #include "delta_small.hpp"
+#include "huf_small.hpp"
 
 using namespace cniic;
 
@@ -1323,6 +1324,29 @@ static uint64_t delta_small_max_px() {
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallMaxPx);
     return kDeltaSmallMaxPx;
 }
+// Small `hufman` frames in device memory (1 .. kHufSmallMaxPx pixels) likewise: huf_small_encode (codec.cpp), the `delta` route's kernel body
+// over the pixels' own colours ("huf_small_batch": k_huf_small, launches = the frames that took the route; "huf_small_place").  The testing
+// library can switch it off (CNIIC_TEST_HUF_SMALL_OFF=1) or lower its bound (CNIIC_TEST_HUF_SMALL_MAX_PX).
+static uint64_t huf_small_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_OFF")) if (atoi(e) != 0) return 0;
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kHufSmallMaxPx);
+    return kHufSmallMaxPx;
+}
+// The floor of that route.  The kernel's time is set by its largest frame (every frame has a CU of its own up to 256 frames: 0.05 ms at 32 x 32,
+// 0.11 at 64 x 64, 0.38 - 0.40 from 128 x 96 on), what the workers cost grows with the number of frames.  Measured against the parent
+// commit's library (tools/small_hufman_probe.py, profiles/small_hufman_probe.json; NOTES AF), whole call, parent's time / this route's:
+//   1 frame:   32 x 32 and 64 x 64 won (1.5x .. 1.9x); 128 x 96, 128 x 128 and 16384 x 1 lost (0.68x .. 0.75x, beyond the spreads)
+//   2 frames:  up to 64 x 64 won (2.2x .. 4.3x); the three larger sizes 0.87x .. 1.11x, within the spreads
+//   4 frames:  every size won (1.27x .. 4.3x); 8 and more: 2.0x .. 68x
+// So in a call with fewer than 4 candidate frames only the frames of at most 4096 pixels take the route (the largest size that won alone;
+// the next one measured, 12 288 pixels, lost); with 4 or more every candidate does.  The testing library takes the floor away with
+// CNIIC_TEST_HUF_SMALL_FLOOR_OFF=1.
+constexpr uint32_t kHufSmallFloorFew = 4;
+constexpr uint64_t kHufSmallFloorPxFew = 4096;
+static uint64_t huf_small_floor_px(uint64_t candidates) {
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
+    return candidates >= kHufSmallFloorFew ? ~0ull : kHufSmallFloorPxFew;
+}
 // Small voronoi(K <= 256) frames in device memory (1 .. kVorSmallMaxPx pixels, no K-means flags) likewise: vor_small_encode (codec.cpp), a
 // workgroup per frame from the pixels through the whole K-means to the finished stream ("vor_small_batch": k_vor_small, launches = the
 // frames that took the route; "vor_small_place").  The testing library can switch it off (CNIIC_TEST_VOR_SMALL_OFF=1), lower its bound
@@ -1426,6 +1450,31 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
             std::map<std::string, KernelTime> mine;
             mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
             const int32_t rc = delta_small_encode(c, small.data(), (uint32_t)small.size());
+            mine.swap(c->ktimes);
+            CNIIC_TRY(rc);
+            if (c->timers) kt.swap(mine);
+            order.swap(rest);
+        }
+    }
+    // ---- the small `hufman` frames, together
+    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_HUFMAN && (!opts || opts->flags == 0)) {
+        const uint64_t max_px = huf_small_max_px();
+        std::vector<VarFrame *> small;
+        std::vector<uint32_t> rest;
+        uint64_t candidates = 0;
+        for (uint32_t j = 0; j < n; j++) {
+            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
+            candidates += px >= 1 && px <= max_px;
+        }
+        const uint64_t floor_px = huf_small_floor_px(candidates);   // (the floor: few frames, many pixels -- the workers are faster)
+        for (uint32_t j = 0; j < n; j++) {
+            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
+            if (px >= 1 && px <= max_px && px <= floor_px) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
+        }
+        if (!small.empty()) {
+            std::map<std::string, KernelTime> mine;
+            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
+            const int32_t rc = huf_small_encode(c, small.data(), (uint32_t)small.size());
             mine.swap(c->ktimes);
             CNIIC_TRY(rc);
             if (c->timers) kt.swap(mine);

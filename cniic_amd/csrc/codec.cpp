@@ -14,6 +14,7 @@
 #include "vor_small.hpp"
 #include "delta_small.hpp"
 #include "delta_small_dec.hpp"
+#include "huf_small.hpp"
 #include "small_trie.hpp"
 
 #include <algorithm>
@@ -1163,9 +1164,19 @@ int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame 
 static uint64_t delta_small_tmp_px(uint64_t npx) { return (npx + 3) & ~3ull; }
 static uint64_t delta_small_frame_bytes(uint64_t npx) { return ds_stride(npx) + 12 * delta_small_tmp_px(npx); }
 
-static int delta_small_chunk(Ctx *c, VarFrame *const *fr, uint32_t n) {
+// The two codecs of the route (k_delta_small.hip: one body, two symbol kinds) differ on the host by the slot, the launch and the names
+struct SmallHuffKind {
+    const char *name, *t_batch, *t_place;
+    uint64_t (*stride)(uint64_t npx);
+    int (*run)(Ctx *, const DeltaSmallRow *, uint32_t, uint32_t, uint8_t *, uint64_t, uint32_t *, uint64_t, DeltaSmallResult *);
+    uint64_t min_len;   // one leaf and no payload
+};
+static const SmallHuffKind kSmallDelta = {"delta_small", "delta_small_batch", "delta_small_place", ds_stride, delta_small_run, 15};
+static const SmallHuffKind kSmallHuf = {"huf_small", "huf_small_batch", "huf_small_place", hs_stride, huf_small_run, 20};
+
+static int delta_small_chunk(Ctx *c, const SmallHuffKind &kind, VarFrame *const *fr, uint32_t n) {
     const uint64_t max_px = (uint64_t)fr[0]->w * fr[0]->h;   // (largest first)
-    const uint64_t sstride = ds_stride(max_px), tmp_px = delta_small_tmp_px(max_px);
+    const uint64_t sstride = kind.stride(max_px), tmp_px = delta_small_tmp_px(max_px);
     std::vector<DeltaSmallRow> rows(n);
     for (uint32_t i = 0; i < n; i++) rows[i] = DeltaSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
     DevBuf rows_d, res_d, scratch, tmp;
@@ -1175,8 +1186,8 @@ static int delta_small_chunk(Ctx *c, VarFrame *const *fr, uint32_t n) {
     CNIIC_HIP_TRY(c, tmp.alloc(12 * tmp_px * n));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(DeltaSmallRow), hipMemcpyHostToDevice, c->stream));
     {
-        ScopedKernelTimer t(c, "delta_small_batch");
-        CNIIC_TRY(delta_small_run(c, rows_d.as<DeltaSmallRow>(), n, (uint32_t)max_px, scratch.as<uint8_t>(), sstride, tmp.as<uint32_t>(), tmp_px, res_d.as<DeltaSmallResult>()));
+        ScopedKernelTimer t(c, kind.t_batch);
+        CNIIC_TRY(kind.run(c, rows_d.as<DeltaSmallRow>(), n, (uint32_t)max_px, scratch.as<uint8_t>(), sstride, tmp.as<uint32_t>(), tmp_px, res_d.as<DeltaSmallResult>()));
         t.stop(n);
     }
     std::vector<DeltaSmallResult> res(n);
@@ -1188,7 +1199,7 @@ static int delta_small_chunk(Ctx *c, VarFrame *const *fr, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) {
         VarFrame &f = *fr[i];
         f.len = res[i].len;
-        if (f.len < 15 || f.len > sstride) return c->fail(CNIIC_ERR_HIP, "delta_small: a stream of %llu bytes in a slot of %llu", (unsigned long long)f.len, (unsigned long long)sstride);
+        if (f.len < kind.min_len || f.len > sstride) return c->fail(CNIIC_ERR_HIP, "%s: a stream of %llu bytes in a slot of %llu", kind.name, (unsigned long long)f.len, (unsigned long long)sstride);
         if (f.len > f.cap) {
             f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
             f.msg = c->err;
@@ -1201,7 +1212,7 @@ static int delta_small_chunk(Ctx *c, VarFrame *const *fr, uint32_t n) {
         DevBuf pl_d;
         CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
         CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
-        ScopedKernelTimer t(c, "delta_small_place");
+        ScopedKernelTimer t(c, kind.t_place);
         CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
         t.stop(1);
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1219,7 +1230,28 @@ int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
     for (uint32_t at = 0; at < n;) {
         const uint64_t room = (2ull << 30) / delta_small_frame_bytes((uint64_t)fr[at]->w * fr[at]->h);
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
-        CNIIC_TRY(delta_small_chunk(c, fr + at, cnt));
+        CNIIC_TRY(delta_small_chunk(c, kSmallDelta, fr + at, cnt));
+        at += cnt;
+    }
+    return CNIIC_OK;
+}
+
+// ---- small `hufman` frames of a batch call, all at once (codec.hpp; k_huf_small in k_delta_small.hip): the chunk above under the other kind.
+// A frame of the chunk whose largest frame has npx pixels takes its slot (hs_stride), the kernel's three words per pixel, its row and its
+// result row; the chunks stay below 2 GiB (the testing library: below CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least).
+constexpr uint64_t kHufSmallScratch = 2ull << 30;
+static uint64_t huf_small_budget() {
+    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kHufSmallScratch);
+    return kHufSmallScratch;
+}
+static uint64_t huf_small_frame_bytes(uint64_t npx) { return hs_stride(npx) + 12 * delta_small_tmp_px(npx) + sizeof(DeltaSmallRow) + sizeof(DeltaSmallResult); }
+
+int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
+    const uint64_t budget = huf_small_budget();
+    for (uint32_t at = 0; at < n;) {
+        const uint64_t room = std::max<uint64_t>(1, budget / huf_small_frame_bytes((uint64_t)fr[at]->w * fr[at]->h));
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
+        CNIIC_TRY(delta_small_chunk(c, kSmallHuf, fr + at, cnt));
         at += cnt;
     }
     return CNIIC_OK;
@@ -1940,8 +1972,39 @@ static uint64_t delta_small_dec_budget() {
     if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecScratch);
     return kDeltaSmallDecScratch;
 }
+// Small `hufman` and `cluster-colors` frames take the same route under the other symbol kind (k_huf_small_dec: RGB keys, no FromDiff, no
+// scan): frames of 1 .. kHufSmallMaxPx pixels whose decoder the host has parsed and has no code longer than kDeltaSmallMaxCodeLen; larger
+// frames, longer codes and everything unparsed keep huff_decode_batch_dev.  Stage timer "huf_small_dec_batch"; the testing library can
+// switch it off (CNIIC_TEST_HUF_SMALL_DEC_OFF=1) and lower its bound (CNIIC_TEST_HUF_SMALL_DEC_MAX_PX); the rounds' knob above caps both.
+static uint64_t huf_small_dec_max_px() {
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_DEC_OFF")) if (atoi(e) != 0) return 0;
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_DEC_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kHufSmallMaxPx);
+    return kHufSmallMaxPx;
+}
+// The floor of that route.  Most of the call is the host's parse of the decoders either way; what the kernel adds for few frames is its settle
+// rounds (0.35 ms for one 32 x 32 frame, whatever the number of frames up to the CUs) against launches that the batched route shares among
+// its frames.  Measured against the parent commit's library (tools/small_hufman_probe.py, profiles/small_hufman_probe.json; NOTES AF), whole
+// call, parent's time / this route's, `hufman` streams:
+//   1 .. 4 frames:   32 x 32, 64 x 64 and one 128 x 96 frame lost (0.63x .. 0.78x, most beyond the spreads); 128 x 128 and 16384 x 1 won or tied (0.99x .. 2.3x)
+//   16, 64 frames:   0.93x .. 2.35x, and photo-like 128 x 96 lost beyond the spreads (0.76x, 0.86x)
+//   256, 4096:       every class won: 1.01x .. 4.08x
+// and cluster-colors(256) streams: 0.80x .. 1.82x up to 64 frames (two classes of 16 frames lost beyond the spreads), 0.88x .. 1.38x from 256 on with
+// no class beyond the spreads.  So the frames take this route in a call with at least 256 small frames (the first count at which every class won) and
+// keep the batched route otherwise.  The testing library takes the floor away with CNIIC_TEST_HUF_SMALL_FLOOR_OFF=1.
+constexpr uint32_t kHufSmallDecFloorFrames = 256;
+static uint32_t huf_small_dec_floor() {
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return 0;
+    return kHufSmallDecFloorFrames;
+}
+struct SmallDecKind {
+    const char *name, *timer, *short_msg;
+    int (*run)(Ctx *, const DeltaSmallDecRow *, uint32_t, uint32_t, uint32_t, uint32_t *);
+    uint32_t last_status;
+};
+static const SmallDecKind kSmallDecDelta = {"delta_small_dec", "delta_small_dec_batch", "delta: cannot decode the difference stream", delta_small_dec_run, kDsdRange};
+static const SmallDecKind kSmallDecRgb = {"huf_small_dec", "huf_small_dec_batch", "Failed to decode symbol", huf_small_dec_run, kDsdUnsettled};
 // dev != nullptr: the routed frames' tables lie in HBM already ((*dev)[f]), and `tabs` is not looked at
-static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
+static int delta_small_decode(Ctx *c, const SmallDecKind &kind, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
                               const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route, const std::vector<std::vector<uint32_t>> &tabs,
                               const std::vector<DeltaSmallDevTab> *dev, const std::vector<uint64_t> &pay, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
                               std::vector<std::string> &msgs) {
@@ -2005,8 +2068,8 @@ static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint
         memset(up + status_at, 0xff, S * 4);
         CNIIC_HIP_TRY(c, hipMemcpyAsync(tab_d.p, up, up_bytes, hipMemcpyHostToDevice, c->stream));
         {
-            ScopedKernelTimer t(c, "delta_small_dec_batch");
-            CNIIC_TRY(delta_small_dec_run(c, reinterpret_cast<const DeltaSmallDecRow *>(tab_d.as<uint8_t>() + rows_at), (uint32_t)S, max_px, max_rounds,
+            ScopedKernelTimer t(c, kind.timer);
+            CNIIC_TRY(kind.run(c, reinterpret_cast<const DeltaSmallDecRow *>(tab_d.as<uint8_t>() + rows_at), (uint32_t)S, max_px, max_rounds,
                                           reinterpret_cast<uint32_t *>(tab_d.as<uint8_t>() + status_at)));
             t.stop(S);
         }
@@ -2018,9 +2081,9 @@ static int delta_small_decode(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
             if (st[i] == kDsdUnsettled) continue;   // the caller's
-            if (st[i] > kDsdRange) return c->fail(CNIIC_ERR_HIP, "delta_small_dec: frame %u reported no status", f);
+            if (st[i] > kind.last_status) return c->fail(CNIIC_ERR_HIP, "%s: frame %u reported no status", kind.name, f);
             taken[f] = 1;
-            if (st[i] == kDsdShort) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "delta: cannot decode the difference stream"; }
+            if (st[i] == kDsdShort) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = kind.short_msg; }
             else if (st[i] == kDsdRange) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "delta: colour out of range (hilbertc.rs:505)"; }
             else if (!dst_dev) memcpy(rgb + (uint64_t)f * img_stride, imgs_h.data() + img_at[i], (uint64_t)w[f] * h[f] * 3);
         }
@@ -2109,7 +2172,7 @@ static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, 
             dev[f] = DeltaSmallDevTab{rows[i].table, r.leaves, r.max_len};
             route.push_back(f);
         }
-        if (!route.empty()) CNIIC_TRY(delta_small_decode(c, bytes, true, stride, lens, rgb, dst_dev, img_stride, w, h, route, no_tabs, &dev, pay, taken, rcs, msgs));
+        if (!route.empty()) CNIIC_TRY(delta_small_decode(c, kSmallDecDelta, bytes, true, stride, lens, rgb, dst_dev, img_stride, w, h, route, no_tabs, &dev, pay, taken, rcs, msgs));
         i0 = i1;
     }
     if (c->timers) { c->ktimes["delta_small_dec_parse"].launches += parsed; c->ktimes["delta_small_dec_parse_host"].launches += host.size(); }
@@ -2200,6 +2263,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     const bool delta = d.kind == CODEC_DELTA;
     const uint64_t delta_max_px = delta ? delta_small_dec_max_px() : 0;
     if (delta && !delta_max_px) return CNIIC_OK;
+    uint64_t rgb_max_px = delta ? 0 : huf_small_dec_max_px();   // small `hufman` / `cluster-colors` frames: a workgroup per frame (delta_small_decode)
     const bool bytes_dev = is_device_ptr(bytes), dst_dev = is_device_ptr(rgb);
     std::vector<uint8_t> off_route(F, 0);   // tests (CNIIC_TEST_DECODE_BATCH_OFF=i,j,..): these frames through the single-stream decode
     if (const char *e = test_env("CNIIC_TEST_DECODE_BATCH_OFF"))
@@ -2305,11 +2369,22 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     } else {
         for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
     }
+    if (rgb_max_px) {   // (the floor: a call with few small frames keeps the batched route for them)
+        uint32_t candidates = 0;
+        for (uint32_t f : all) {
+            uint64_t pos = 0;
+            uint32_t fw, fh;
+            if (off_route[f] || !get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) continue;
+            candidates += (uint64_t)fw * fh >= 1 && (uint64_t)fw * fh <= rgb_max_px;
+        }
+        if (candidates < huf_small_dec_floor()) rgb_max_px = 0;
+    }
     // ---- the decoders, parsed on the host
     std::vector<LeafTable> lts(delta ? 16 : F);   // (`delta`: one per parsing thread; a frame keeps its leaves in two words each, delta_tabs)
-    std::vector<std::vector<uint32_t>> delta_tabs(delta ? F : 0);
+    std::vector<std::vector<uint32_t>> delta_tabs(delta || rgb_max_px ? F : 0);   // (and of the small RGB frames)
     std::vector<uint64_t> pay(F);      // where the payload starts
-    std::vector<uint8_t> cand(F, 0);   // 1: on the route; 2: the decoder runs past the head (a second look)
+    std::vector<uint64_t> npx(F, 0);   // the header's pixels, of a frame whose header was read
+    std::vector<uint8_t> cand(F, 0);   // 1: on the route; 2: the decoder runs past the head (a second look); 3: a small RGB frame, on the workgroup-per-frame route
     auto classify = [&](uint32_t f, uint32_t thread) {
         cand[f] = 0;
         if (off_route[f]) return;
@@ -2319,54 +2394,66 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         const uint64_t n = (uint64_t)fw * fh;
         if (!n || n >= (1ull << 32) || n * 3 > img_stride) return;
         if (delta && (n > delta_max_px || (c->scan_xy.p && c->scan_w == fw && c->scan_h == fh))) return;   // (a size with an injected scan: the single decode follows it)
+        npx[f] = n;
         LeafTable &lt = lts[delta ? thread : f];
         if (!huff_parse_leaves(delta ? CNIIC_SYM_SIGNED : CNIIC_SYM_RGB, head_p[f], head_n[f], pos, lt)) { if (head_n[f] < lens[f]) cand[f] = 2; return; }
         if (lt.too_deep || lt.max_len > (delta ? kDeltaSmallMaxCodeLen : 32u) || lt.n() >= (1u << 20) || (lt.n() > 1 && pos >= lens[f])) return;
-        if (delta) {   // codes left-aligned in 32 bits, then key | length << 27 (delta_small_dec.hpp)
+        const bool small_rgb = !delta && n <= rgb_max_px && lt.max_len <= kDeltaSmallMaxCodeLen;
+        if (delta || small_rgb) {   // codes left-aligned in 32 bits, then key | length << 27 (delta_small_dec.hpp; an RGB key has 24 bits)
             const uint32_t L = (uint32_t)lt.n();
             std::vector<uint32_t> &tab = delta_tabs[f];
             tab.resize(2 * (size_t)L);
             for (uint32_t i = 0; i < L; i++) { tab[i] = (uint32_t)(lt.code[i] >> 32); tab[L + i] = dsd_keylen(lt.key[i], lt.len[i]); }
+            if (small_rgb) lt = LeafTable();   // (the two words per leaf are all the route needs)
         }
         w[f] = fw; h[f] = fh;
         pay[f] = pos;
-        cand[f] = 1;
+        cand[f] = small_rgb ? 3 : 1;
     };
     auto parse_all = [&](const std::vector<uint32_t> &which) {
         parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t thread) { classify(which[i], thread); });
     };
     parse_all(all);
-    std::vector<uint32_t> again;
-    uint64_t W2 = 0;
-    for (uint32_t f = 0; f < F; f++) if (cand[f] == 2) { again.push_back(f); W2 = std::max(W2, std::min<uint64_t>(lens[f], 4ull << 20)); }
-    if (!again.empty() && delta) {
-        // `delta`: a small frame's decoder is most of its stream (a leaf's 7 bytes against a code of a dozen bits), so the second look is
-        // the rule, and 4096 frames of 128 x 128 would share kBatchHeadsMax at 64 KiB each, less than their decoders.  The frames are looked
-        // at again in groups of as many rows as the pinned block holds at the full width (the tables parsed from a group are the frames' own)
-        W2 = std::min(W2, stride);
-        const uint64_t rows = std::max<uint64_t>(1, kBatchHeadsMax / std::max<uint64_t>(W2, 1));
-        for (size_t g0 = 0; g0 < again.size();) {
+    // (the frames of the workgroup-per-frame routes -- `delta`, and the RGB kinds' frames that are small by their headers -- apart from the others)
+    std::vector<uint32_t> again, again_small;
+    uint64_t W2 = 0, W2s = 0;
+    for (uint32_t f = 0; f < F; f++)
+        if (cand[f] == 2) {
+            const bool small = delta || (npx[f] && npx[f] <= rgb_max_px);
+            (small ? again_small : again).push_back(f);
+            (small ? W2s : W2) = std::max(small ? W2s : W2, std::min<uint64_t>(lens[f], 4ull << 20));
+        }
+    if (!again_small.empty()) {
+        // A small frame's decoder is most of its stream (`delta`: a leaf's 7 bytes against a code of a dozen bits; `hufman`: 12 bytes), so
+        // the second look is the rule, and 4096 frames of 128 x 128 would share kBatchHeadsMax at 64 KiB each, less than their decoders.  The
+        // frames are looked at again in groups of as many rows as the pinned block holds at the full width (the tables parsed from a group
+        // are the frames' own)
+        W2s = std::min(W2s, stride);
+        const uint64_t rows = std::max<uint64_t>(1, kBatchHeadsMax / std::max<uint64_t>(W2s, 1));
+        for (size_t g0 = 0; g0 < again_small.size();) {
             size_t g1 = g0 + 1;
-            while (g1 < again.size() && (uint64_t)again[g1] - again[g0] + 1 <= rows) g1++;
-            const uint32_t f0 = again[g0], f1 = again[g1 - 1];
-            if (W2 > head_n[f0] || W2 > head_n[f1]) {
-                CNIIC_TRY(fetch(W2, f0, f1));
-                parse_all(std::vector<uint32_t>(again.begin() + g0, again.begin() + g1));
+            while (g1 < again_small.size() && (uint64_t)again_small[g1] - again_small[g0] + 1 <= rows) g1++;
+            const uint32_t f0 = again_small[g0], f1 = again_small[g1 - 1];
+            if (W2s > head_n[f0] || W2s > head_n[f1]) {
+                CNIIC_TRY(fetch(W2s, f0, f1));
+                parse_all(std::vector<uint32_t>(again_small.begin() + g0, again_small.begin() + g1));
             }
             g0 = g1;
         }
-    } else if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
+    }
+    if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
         const uint32_t f0 = again.front(), f1 = again.back();
         W2 = std::min({W2, stride, kBatchHeadsMax / (f1 - f0 + 1)});
-        if (W2 > head_n[f0] || W2 > head_n[f1]) {
+        if (!again_small.empty() || W2 > head_n[f0] || W2 > head_n[f1]) {   // (the small frames' look has taken the pinned block since the first one)
             CNIIC_TRY(fetch(W2, f0, f1));
             parse_all(again);
         }
     }
-    std::vector<uint32_t> route;
-    for (uint32_t f = 0; f < F; f++) if (cand[f] == 1) route.push_back(f);
+    std::vector<uint32_t> route, small_route;
+    for (uint32_t f = 0; f < F; f++) if (cand[f] == 1) route.push_back(f); else if (cand[f] == 3) small_route.push_back(f);
+    if (!small_route.empty()) CNIIC_TRY(delta_small_decode(c, kSmallDecRgb, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, small_route, delta_tabs, nullptr, pay, taken, rcs, msgs));
     if (route.empty()) return CNIIC_OK;
-    if (delta) return delta_small_decode(c, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, route, delta_tabs, nullptr, pay, taken, rcs, msgs);
+    if (delta) return delta_small_decode(c, kSmallDecDelta, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, route, delta_tabs, nullptr, pay, taken, rcs, msgs);
     // ---- payloads in HBM, outputs in HBM (4-byte aligned)
     DevBuf up_d, img_d;
     const uint8_t *base = bytes;

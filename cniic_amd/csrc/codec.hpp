@@ -54,6 +54,11 @@ int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame 
 // stream to its own destination.  Fills in rc, len and msg of every frame as cniic_codec_encode_opts would for that frame alone (st stays
 // zero, as there); what it returns is the status of the machinery, not of a frame.
 int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
+// `hufman` of n > 0 small frames (1 .. kHufSmallMaxPx pixels each, DEVICE images, largest first; all destinations host or all device
+// memory) likewise: k_huf_small, the same kernel body over the pixels' own colours (huf_small.hpp), a workgroup per frame in one launch per
+// chunk of scratch, then every stream to its own destination.  Fills in rc, len and msg of every frame as cniic_codec_encode_opts would for
+// that frame alone (st stays zero, as there).
+int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
 // voronoi(K), 1 <= K <= 256, of n > 0 small frames (1 .. kVorSmallMaxPx pixels each, DEVICE images, largest first; all destinations host or
 // all device memory) in one launch per chunk of scratch: k_vor_small, one workgroup per frame from the pixels to the finished stream, then
 // every stream to its own destination.  Fills in rc, len, st and msg of every frame as cniic_codec_encode_opts would for that frame alone

@@ -923,6 +923,9 @@ struct DeltaSmallRow { const uint8_t *src; uint32_t w, h; };
 struct DeltaSmallResult { uint32_t U, len; };   // distinct symbols, bytes of the stream
 int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint8_t *scratch_d, uint64_t sstride,
                     uint32_t *tmp_d, uint64_t tmp_px, DeltaSmallResult *res_d);
+// the same for `hufman` (k_huf_small, the same body over the pixels' colours; huf_small.hpp): sstride >= hs_stride(max_px)
+int huf_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint8_t *scratch_d, uint64_t sstride,
+                  uint32_t *tmp_d, uint64_t tmp_px, DeltaSmallResult *res_d);
 // ---- k_delta_small_dec.hip: the decode of small `delta` frames, one workgroup per frame (delta_small_dec.hpp has the arithmetic and the
 // limits).  A row per frame: its payload (device memory, any alignment; payload_bytes to the stream's end), where its w x h x 3 image goes
 // (device memory, any alignment) and its decoder as `leaves` words of left-aligned codes, ascending, and as many key | length << 27 words
@@ -930,6 +933,9 @@ int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32
 // decode's two failures), kDsdUnsettled (not written: the caller decodes the frame on its own).  max_rounds >= 1: settle rounds per frame.
 struct DeltaSmallDecRow { const uint8_t *payload; uint8_t *dst; const uint32_t *code, *keylen; uint32_t payload_bytes, leaves, w, h, max_len /* the longest code */; };
 int delta_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t max_rounds, uint32_t *status_d);
+// the same for RGB symbols (k_huf_small_dec: small `hufman` and `cluster-colors` frames; key = r << 16 | g << 8 | b, position d is pixel d,
+// no FromDiff): status_d[f] is kDsdOk, kDsdShort or kDsdUnsettled
+int huf_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t max_rounds, uint32_t *status_d);
 // ---- k_small_trie.hip: the parse of small `delta` frames' decoders, one workgroup per frame (small_trie.hpp has the arithmetic and the
 // limits).  A row per frame: its stream (device memory, any alignment; `bytes` of it may be read) and where its table goes -- room for
 // st_leaves_room<6>(bytes) leaves of two words, 4-byte aligned: the left-aligned codes, then as many key | length << 27 words, which is what

@@ -14,10 +14,16 @@
 // and a per-frame HBM slice of 12 bytes per pixel holds what LDS cannot beside the tree: the position-ordered symbols (read once more in e),
 // the ascending keys (read by d for the header, reloaded by e) and the code words by rank (written by d, loaded by e).  No block waits for
 // another.
+//
+// `hufman` of small frames (k_huf_small; codec.cpp huf_small_encode) is the same body, phases b-e untouched, under another SYMBOL KIND
+// (DsKindRgb below): the symbols are the pixels' colours in row-major order, so phase a needs no scan and no tables, a leaf's record is
+// 12 bytes against 7 and a subtree 13 * leaves - 1 bytes against 8 * leaves - 1 (huf_small.hpp).  The longest code is a matter of counts
+// (delta_small.hpp) and holds for both.
 #include "common.hpp"
 #include "hilbert_scan.hpp"
 #include "delta_sym.hpp"
 #include "delta_small.hpp"
+#include "huf_small.hpp"
 
 namespace cniic {
 
@@ -97,13 +103,41 @@ __device__ __forceinline__ uint32_t ds_leading(bool ok) {   // how many lanes fr
     return m == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
 }
 
-__global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow *__restrict__ rows, uint32_t cap_px, const HilbertLut *__restrict__ lut,
-                                                            uint8_t *__restrict__ scratch, uint64_t sstride, uint32_t *__restrict__ tmp, uint64_t tpx,
-                                                            DeltaSmallResult *__restrict__ res) {
+// ---- a, for `hufman`: the symbols are the pixels themselves in row-major order, r << 16 | g << 8 | b: no scan, no tables.  Ends with a barrier.
+__device__ __forceinline__ void hs_symbols(const uint8_t *__restrict__ src, uint32_t n, uint32_t *s_sym, uint32_t *__restrict__ syms_g) {
+    for (uint32_t d = threadIdx.x; d < n; d += kDsThreads) {
+        const uint8_t *p = src + 3ull * d;
+        const uint32_t key = hs_key(p[0], p[1], p[2]);
+        s_sym[d] = key; syms_g[d] = key;
+    }
+    __syncthreads();
+}
+
+// ---- THE SYMBOL KIND: what the phases below ask of a codec -- whether the symbols come along a scan (a), a leaf's record and the
+// subtree's size (d), the stream's sizes (b, e).  Everything else (sort, leaf order, merge, walks, search, pack) knows counts and keys only.
+struct DsKindDelta {   // `delta`: differences along the Hilbert scan, a leaf is tag + three i16 (delta_small.hpp)
+    static constexpr bool kScan = true;
+    static constexpr uint32_t kLeaf = 7;
+    static __device__ __forceinline__ void leaf_bytes(uint32_t key, uint8_t *o) { ds_leaf_bytes(key, o); }
+    static __device__ __forceinline__ void walk_step(DsWalk &wk, uint32_t link, uint32_t leaves, uint32_t pl) { ds_walk_step(wk, link, leaves, pl); }
+    static __device__ __forceinline__ uint32_t header_bytes(uint32_t U) { return (uint32_t)ds_header_bytes(U); }
+    static __device__ __forceinline__ uint32_t stream_bytes(uint32_t U, uint32_t bits) { return (uint32_t)ds_stream_bytes(U, bits); }
+};
+struct DsKindRgb {     // `hufman`: the pixels in row-major order, a leaf is tag + u64 3 + r, g, b (huf_small.hpp)
+    static constexpr bool kScan = false;
+    static constexpr uint32_t kLeaf = 1 + kHufSmallLeafSym;
+    static __device__ __forceinline__ void leaf_bytes(uint32_t key, uint8_t *o) { hs_leaf_bytes(key, o); }
+    static __device__ __forceinline__ void walk_step(DsWalk &wk, uint32_t link, uint32_t leaves, uint32_t pl) { hs_walk_step(wk, link, leaves, pl); }
+    static __device__ __forceinline__ uint32_t header_bytes(uint32_t U) { return (uint32_t)hs_header_bytes(U); }
+    static __device__ __forceinline__ uint32_t stream_bytes(uint32_t U, uint32_t bits) { return (uint32_t)hs_stream_bytes(U, bits); }
+};
+
+// one frame, from the pixels to the finished stream (k_delta_small and k_huf_small below are this body under the two kinds)
+template <class Kind>
+__device__ __forceinline__ void ds_frame(const DeltaSmallRow *__restrict__ rows, uint32_t cap_px, const HilbertLut *__restrict__ lut, uint8_t *__restrict__ scratch,
+                                         uint64_t sstride, uint32_t *__restrict__ tmp, uint64_t tpx, DeltaSmallResult *__restrict__ res) {
     extern __shared__ __align__(16) uint8_t ds_lds[];
     __shared__ uint32_t s_scan[kDsThreads / 64 + 1];
-    __shared__ uint16_t s_l4[1024];
-    __shared__ uint8_t s_l1[16];
     __shared__ uint32_t s_bad;   // a walk did not end at the root within the longest code: the frame is reported, not written
     if (threadIdx.x == 0) s_bad = 0;
     const uint32_t cap = max(cap_px, kDsMinCap);
@@ -116,9 +150,15 @@ __global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow 
     uint32_t *__restrict__ syms_g = tmp + (uint64_t)f * 3 * tpx, *__restrict__ keys_g = syms_g + tpx, *__restrict__ cw_g = keys_g + tpx;
 
     // ---- a. symbols
-    const uint32_t order = (w == h && w >= 2 && !(w & (w - 1))) ? (uint32_t)__builtin_ctz(w) : 0u;   // (pow2_order, k_hilbert.hip)
-    const Scan sc = load_scan(w, h, order, order ? lut : nullptr, s_l4, s_l1);
-    ds_symbols(sc, row.src, w, n, s_a, syms_g);
+    if constexpr (Kind::kScan) {
+        __shared__ uint16_t s_l4[1024];
+        __shared__ uint8_t s_l1[16];
+        const uint32_t order = (w == h && w >= 2 && !(w & (w - 1))) ? (uint32_t)__builtin_ctz(w) : 0u;   // (pow2_order, k_hilbert.hip)
+        const Scan sc = load_scan(w, h, order, order ? lut : nullptr, s_l4, s_l1);
+        ds_symbols(sc, row.src, w, n, s_a, syms_g);
+    } else {
+        hs_symbols(row.src, n, s_a, syms_g);
+    }
 
     // ---- b. sort, unique
     uint32_t P = 1;
@@ -148,12 +188,12 @@ __global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow 
     for (uint32_t q = 0; q < kDsPer; q++)
         if ((heads >> q) & 1u) { s_a[rank] = kv[q]; s_hd[rank] = (uint16_t)(first + q); rank++; }
     __syncthreads();
-    const uint32_t hdr = (uint32_t)ds_header_bytes(U);
+    const uint32_t hdr = Kind::header_bytes(U);
     if (U == 1) {   // one symbol: the zero-length code and no payload (huf.rs:140-142)
         if (tid == 0) {
             for (int i = 0; i < 4; i++) { slot[i] = (uint8_t)(w >> (8 * i)); slot[4 + i] = (uint8_t)(h >> (8 * i)); }
             slot[8] = 0;
-            ds_leaf_bytes(s_a[0], slot + 9);
+            Kind::leaf_bytes(s_a[0], slot + 9);
             res[f] = DeltaSmallResult{1u, hdr};
         }
         return;
@@ -266,17 +306,17 @@ __global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow 
         uint32_t link = s_lq[q], leaves = 1;
         for (uint32_t s = 0; s < kDeltaSmallMaxCodeLen; s++) {
             const uint32_t p = ds_link_parent(link), pl = s_nl[p];
-            ds_walk_step(wk, link, leaves, pl);
+            Kind::walk_step(wk, link, leaves, pl);
             if (p == root) { link = kDsAtRoot; break; }
             leaves = pl;
             link = s_bq[p];
         }
-        if (link != kDsAtRoot || wk.off + 7 > hdr - 8) { s_bad = 1; continue; }   // (cannot happen: delta_small.hpp's bound; nothing is written out of place)
+        if (link != kDsAtRoot || wk.off + Kind::kLeaf > hdr - 8) { s_bad = 1; continue; }   // (cannot happen: delta_small.hpp's bound; nothing is written out of place)
         const uint32_t r = s_qrank[q];
         cw_g[r] = ds_codeword(wk.code, wk.depth);
         uint8_t *o = slot + 8 + wk.off;
         o[0] = 0;
-        ds_leaf_bytes(keys_g[r], o + 1);
+        Kind::leaf_bytes(keys_g[r], o + 1);
     }
     for (uint32_t j = tid; j < nbr; j += kDsThreads) {
         DsWalk wk;
@@ -284,7 +324,7 @@ __global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow 
             uint32_t link = s_bq[j], leaves = s_nl[j];
             for (uint32_t s = 0; s < kDeltaSmallMaxCodeLen; s++) {
                 const uint32_t p = ds_link_parent(link), pl = s_nl[p];
-                ds_walk_step(wk, link, leaves, pl);
+                Kind::walk_step(wk, link, leaves, pl);
                 if (p == root) { link = kDsAtRoot; break; }
                 leaves = pl;
                 link = s_bq[p];
@@ -341,7 +381,19 @@ __global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow 
         }
         if (nb) atomicOr(&words[wi], __builtin_bswap32((uint32_t)(acc >> 32)));
     }
-    if (tid == 0) res[f] = DeltaSmallResult{U, s_bad ? 0u : (uint32_t)ds_stream_bytes(U, total)};
+    if (tid == 0) res[f] = DeltaSmallResult{U, s_bad ? 0u : Kind::stream_bytes(U, total)};
+}
+
+__global__ __launch_bounds__(kDsThreads) void k_delta_small(const DeltaSmallRow *__restrict__ rows, uint32_t cap_px, const HilbertLut *__restrict__ lut,
+                                                            uint8_t *__restrict__ scratch, uint64_t sstride, uint32_t *__restrict__ tmp, uint64_t tpx,
+                                                            DeltaSmallResult *__restrict__ res) {
+    ds_frame<DsKindDelta>(rows, cap_px, lut, scratch, sstride, tmp, tpx, res);
+}
+
+// `hufman` of small frames: the same body over the pixels' own colours (no scan: neither load_scan nor its tables in LDS)
+__global__ __launch_bounds__(kDsThreads) void k_huf_small(const DeltaSmallRow *__restrict__ rows, uint32_t cap_px, uint8_t *__restrict__ scratch, uint64_t sstride,
+                                                          uint32_t *__restrict__ tmp, uint64_t tpx, DeltaSmallResult *__restrict__ res) {
+    ds_frame<DsKindRgb>(rows, cap_px, nullptr, scratch, sstride, tmp, tpx, res);
 }
 
 int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px, uint8_t *scratch_d, uint64_t sstride, uint32_t *tmp_d, uint64_t tmp_px,
@@ -355,6 +407,19 @@ int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32
     while (cap_px < max_px) cap_px <<= 1;
     CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_delta_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ds_lds_bytes(kDeltaSmallMaxPx)));
     hipLaunchKernelGGL(k_delta_small, dim3(frames), dim3(kDsThreads), ds_lds_bytes(cap_px), c->stream, rows_d, cap_px, lut, scratch_d, sstride, tmp_d, tmp_px, res_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
+int huf_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px, uint8_t *scratch_d, uint64_t sstride, uint32_t *tmp_d, uint64_t tmp_px,
+                  DeltaSmallResult *res_d) {
+    if (!frames) return CNIIC_OK;
+    if (max_px == 0 || max_px > kHufSmallMaxPx || tmp_px < max_px || sstride < hs_stride(max_px) || (sstride & 15))
+        return c->fail(CNIIC_ERR_BAD_ARG, "huf_small: frame size or scratch outside the route");
+    uint32_t cap_px = 1;
+    while (cap_px < max_px) cap_px <<= 1;
+    CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_huf_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ds_lds_bytes(kHufSmallMaxPx)));
+    hipLaunchKernelGGL(k_huf_small, dim3(frames), dim3(kDsThreads), ds_lds_bytes(cap_px), c->stream, rows_d, cap_px, scratch_d, sstride, tmp_d, tmp_px, res_d);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }

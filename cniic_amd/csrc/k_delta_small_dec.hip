@@ -18,9 +18,14 @@
 //                   one lane per round, and a round must not wait for HBM)        b-e  one word per symbol: its key, from d on its colour
 // The full table of leaves (a code word and a key | length word per leaf, up to 2^19 leaves of a hostile stream) stays in HBM.  No block
 // waits for another, and no loop is without a bound: a pass advances by a code of at least one bit per step.
+//
+// Small `hufman` and `cluster-colors` frames (k_huf_small_dec; codec.cpp delta_small_decode under the other kind) are the same body with
+// RGB symbols: phases a-c as they are -- a key's 27 bits hold a 24-bit colour r << 16 | g << 8 | b --, no FromDiff (d is skipped, so there
+// is no range status) and no scan: position d is pixel d.  Nothing is stored before the image is complete there either.
 #include "common.hpp"
 #include "hilbert_scan.hpp"
 #include "delta_small_dec.hpp"
+#include "huf_small.hpp"
 
 namespace cniic {
 
@@ -62,13 +67,14 @@ __device__ __forceinline__ void dsd_block_scan3(int32_t v[3], int32_t s_w[3][kDs
     for (int ch = 0; ch < 3; ch++) v[ch] = s_w[ch][wv] + inc[ch] - v[ch];
 }
 
-__global__ __launch_bounds__(kDsdLanes) void k_delta_small_dec(const DeltaSmallDecRow *__restrict__ rows, uint32_t cap_px, uint32_t max_rounds,
-                                                               const HilbertLut *__restrict__ lut, uint32_t *__restrict__ status) {
+// one frame, from the payload to the pixels in place.  kDiff: the symbols are differences along the scan (`delta`); otherwise they are the
+// pixels' colours in row-major order (`hufman`, `cluster-colors`)
+template <bool kDiff>
+__device__ __forceinline__ void dsd_frame(const DeltaSmallDecRow *__restrict__ rows, uint32_t cap_px, uint32_t max_rounds, const HilbertLut *__restrict__ lut,
+                                          uint32_t *__restrict__ status) {
     extern __shared__ __align__(16) uint8_t dsd_lds[];
     __shared__ uint32_t s_end[kDsdLanes];
     __shared__ int32_t s_scan[3][kDsdLanes / 64 + 1];
-    __shared__ uint16_t s_l4[1024];
-    __shared__ uint8_t s_l1[16];
     const uint32_t tid = threadIdx.x, f = blockIdx.x;
     const DeltaSmallDecRow row = rows[f];
     const uint32_t w = row.w, h = row.h, n = w * h, L = row.leaves;   // 1 <= n <= cap_px, 1 <= L
@@ -80,8 +86,13 @@ __global__ __launch_bounds__(kDsdLanes) void k_delta_small_dec(const DeltaSmallD
     uint32_t *s_sym = reinterpret_cast<uint32_t *>(dsd_lds + (((dec > img ? dec : img) + 15) & ~15u));   // [cap_px]
     const uint32_t *__restrict__ code = row.code, *__restrict__ keylen = row.keylen;
 
-    const uint32_t order = (w == h && w >= 2 && !(w & (w - 1))) ? (uint32_t)__builtin_ctz(w) : 0u;   // (pow2_order, k_hilbert.hip)
-    const Scan sc = load_scan(w, h, order, order ? lut : nullptr, s_l4, s_l1);
+    Scan sc{};
+    if constexpr (kDiff) {
+        __shared__ uint16_t s_l4[1024];
+        __shared__ uint8_t s_l1[16];
+        const uint32_t order = (w == h && w >= 2 && !(w & (w - 1))) ? (uint32_t)__builtin_ctz(w) : 0u;   // (pow2_order, k_hilbert.hip)
+        sc = load_scan(w, h, order, order ? lut : nullptr, s_l4, s_l1);
+    }
 
     if (L == 1) {   // one symbol: zero-length codes and no payload (huf.rs:140-142): the frame is filled, not decoded
         const uint32_t key0 = dsd_keylen_key(keylen[0]);
@@ -144,6 +155,7 @@ __global__ __launch_bounds__(kDsdLanes) void k_delta_small_dec(const DeltaSmallD
     }
     __syncthreads();
 
+    if constexpr (kDiff) {
     // ---- d. FromDiff: consecutive positions per lane
     const uint32_t per = (n + kDsdLanes - 1) / kDsdLanes, d0 = tid * per;   // per <= 16
     int32_t run[3] = {0, 0, 0};
@@ -171,17 +183,22 @@ __global__ __launch_bounds__(kDsdLanes) void k_delta_small_dec(const DeltaSmallD
         if (tid == 0) status[f] = kDsdRange;
         return;
     }
+    }   // (RGB symbols: the barrier behind the symbols has made region A dead)
 
     // ---- e. the image in LDS, at the destination's offset within 16 bytes, then out
     uint8_t *__restrict__ dst = row.dst;
     const uint32_t a16 = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15);
     uint8_t *s_img = dsd_lds + a16;
     for (uint32_t d = tid; d < n; d += kDsdLanes) {
-        uint32_t x, y;
-        sc.xy(d, x, y);
         const uint32_t v = s_sym[d];
-        uint8_t *o = s_img + 3 * (y * w + x);
-        o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16);
+        if constexpr (kDiff) {
+            uint32_t x, y;
+            sc.xy(d, x, y);
+            uint8_t *o = s_img + 3 * (y * w + x);
+            o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16);
+        } else {   // position d is pixel d, the key r << 16 | g << 8 | b
+            hs_pixel_bytes(v, s_img + 3 * d);
+        }
     }
     __syncthreads();
     const uint32_t len = 3 * n, to16 = (16 - a16) & 15, head = len < to16 ? len : to16, body = (len - head) / 16;
@@ -192,6 +209,15 @@ __global__ __launch_bounds__(kDsdLanes) void k_delta_small_dec(const DeltaSmallD
     if (tid == 0) status[f] = kDsdOk;
 }
 
+__global__ __launch_bounds__(kDsdLanes) void k_delta_small_dec(const DeltaSmallDecRow *__restrict__ rows, uint32_t cap_px, uint32_t max_rounds,
+                                                               const HilbertLut *__restrict__ lut, uint32_t *__restrict__ status) {
+    dsd_frame<true>(rows, cap_px, max_rounds, lut, status);
+}
+
+__global__ __launch_bounds__(kDsdLanes) void k_huf_small_dec(const DeltaSmallDecRow *__restrict__ rows, uint32_t cap_px, uint32_t max_rounds, uint32_t *__restrict__ status) {
+    dsd_frame<false>(rows, cap_px, max_rounds, nullptr, status);
+}
+
 int delta_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px, uint32_t max_rounds, uint32_t *status_d) {
     if (!frames) return CNIIC_OK;
     if (max_px == 0 || max_px > kDeltaSmallDecMaxPx || max_rounds == 0) return c->fail(CNIIC_ERR_BAD_ARG, "delta_small_dec: frame size or rounds outside the route");
@@ -200,6 +226,16 @@ int delta_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames,
     const uint32_t cap_px = dsd_cap_px(max_px);
     CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_delta_small_dec), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsd_lds_bytes(kDeltaSmallDecMaxPx)));
     hipLaunchKernelGGL(k_delta_small_dec, dim3(frames), dim3(kDsdLanes), dsd_lds_bytes(cap_px), c->stream, rows_d, cap_px, max_rounds, lut, status_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
+int huf_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px, uint32_t max_rounds, uint32_t *status_d) {
+    if (!frames) return CNIIC_OK;
+    if (max_px == 0 || max_px > kDeltaSmallDecMaxPx || max_rounds == 0) return c->fail(CNIIC_ERR_BAD_ARG, "huf_small_dec: frame size or rounds outside the route");
+    const uint32_t cap_px = dsd_cap_px(max_px);
+    CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_huf_small_dec), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsd_lds_bytes(kDeltaSmallDecMaxPx)));
+    hipLaunchKernelGGL(k_huf_small_dec, dim3(frames), dim3(kDsdLanes), dsd_lds_bytes(cap_px), c->stream, rows_d, cap_px, max_rounds, status_d);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }

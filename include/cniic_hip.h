@@ -558,6 +558,17 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
  * duration of that kernel, with launches = the frames that took the route; "delta_small_place" = the copy of the finished streams to
  * out + f * stride.
  *
+ * SMALL `hufman` frames likewise, here and in cniic_codec_measure_batch: with the expression `hufman`, DEVICE images and opts NULL or
+ * opts->flags == 0, every frame of 1 .. 16384 pixels is coded on ONE workgroup from its pixels to its finished stream by the `delta`
+ * route's kernel body over the pixels' own colours (row-major order, key r << 16 | g << 8 | b: no scan; sort, the Huffman tree, the
+ * header of 12-byte leaves and the payload; no dense table and no host round trip), all such frames of the call in one launch per
+ * 2 GiB of scratch whatever their number.  Larger frames and host images go to the worker contexts as above, and so does a LARGE frame
+ * in a call of FEW (measured: one CU is slower for it than the workers' whole chip): with fewer than 4 frames of 1 .. 16384 pixels in the
+ * call, only those of at most 4096 pixels take the route.  cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took shows in no output byte, status or message (CNIIC_ERR_CAPACITY with
+ * lens[f] = bytes needed and the frame's room untouched, as the single call); stats[f] stays zero.  Stage timers: "huf_small_batch" = the
+ * duration of that kernel, with launches = the frames that took the route; "huf_small_place" = the copy of the finished streams to
+ * out + f * stride; cniic_codec_measure_batch leaves both readable after its decode.
+ *
  * SMALL `voronoi` frames likewise, here and in cniic_codec_measure_batch: with the expression voronoi(K), 1 <= K <= 256, DEVICE images and
  * opts NULL or opts->flags == 0 (seed and max_iters are honoured), every frame of 1 .. 16384 pixels is coded on ONE workgroup from its
  * pixels to its finished stream of 16 + 19 K bytes: the pixels, their labels, the K centroids and the clusters' sums stay in the CU's LDS
@@ -675,6 +686,18 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
  * frames, every status and every message are the same either way.  Stage timers, only when that parse ran: "delta_small_dec_parse" = the
  * duration of its launches, with launches = the frames it parsed; "delta_small_dec_parse_host" = no time, launches = the frames handed
  * back to the host's parse.
+ *
+ * SMALL `hufman` and `cluster-colors` frames of a decode likewise, here and in cniic_codec_measure_batch (a cluster-colors stream is a
+ * Hufman stream of palette colours): every frame of 1 .. 16384 pixels whose image fits img_stride and whose decoder -- parsed on the
+ * host, up to 16 threads -- has no code longer than 19 bits is decoded on ONE workgroup by the `delta` decode's kernel body over RGB
+ * symbols (no FromDiff and no scan: position d is pixel d; the image stored whole, and a frame whose payload ends early, "Failed to
+ * decode symbol", leaves its bytes untouched), all such frames of the call in one launch per chunk of scratch.  Host or device memory
+ * on either side, at any alignment.  The decoders of such streams in device memory are most of the stream (12 bytes a leaf), so the
+ * heads are looked at a second time in groups of as many frames as the pinned block holds at their full width, not cut to fit.  Larger
+ * frames, a longer code, a decoder that does not parse and a frame that has not settled within the kernel's rounds keep the routes
+ * above, and so do the small frames of a call that has fewer than 256 of them (measured: below that the batched route is as fast or faster).  Which route a frame took shows in no output byte, status or message.  Stage timer: "huf_small_dec_batch" = the duration of
+ * that kernel, with launches = the frames it was given; cniic_codec_measure_batch leaves it readable beside the encode's
+ * "huf_small_batch" (or, for cluster-colors, "cc_small_batch").
  *
  * SMALL `voronoi` frames of a decode, here and in cniic_codec_measure_batch: with the expression voronoi(K) (the stream carries its own
  * K), every frame whose header and whole centroid list are there and well formed, with 1 <= K <= 256 centroids, 1 .. 16384 pixels and an
