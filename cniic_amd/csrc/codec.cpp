@@ -589,8 +589,12 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     // colour -> label table and the label of every pixel (the one random read per pixel) - so that the GPU
     // is busy while the host waits for the block and builds the tree.
     const bool wide = km_rgbw_is_wide(km);
-    DevBuf lab_d, key2label, pixlab;
-    CNIIC_HIP_TRY(c, pixlab.alloc(n * (wide ? 2 : 1) + 16));
+    // Narrow labels from the partition: the pixels' labels are never written out -- the kernel that picks them packs them
+    // (k_sp_pixpack, k_points.hip), so only the labels in partition order need no code table and run under the host's wait.
+    bool fused = s->sp_mode && !wide;
+    if (const char *e = test_env("CNIIC_TEST_CC_TAIL")) fused = fused && strcmp(e, "split") != 0;
+    DevBuf lab_d, key2label, pixlab, partlab, look;
+    if (!fused) CNIIC_HIP_TRY(c, pixlab.alloc(n * (wide ? 2 : 1) + 16));
     DevBuf lw;
     bool lw_early = false;
     // (twice only if a persistent K-means launch that nobody had waited for turns out to have given up: km_rgbw_result_end has run the
@@ -612,7 +616,8 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
             CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
             lw_early = true;
         }
-        CNIIC_TRY(sp_pixel_labels(c, &s->sp, rgb_d, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, pixlab.p));
+        if (fused) CNIIC_TRY(sp_part_labels(c, &s->sp, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, partlab, &look));
+        else CNIIC_TRY(sp_pixel_labels(c, &s->sp, rgb_d, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, pixlab.p));
     } else {
         CNIIC_HIP_TRY(c, lab_d.alloc(U * (wide ? 2 : 1)));
         CNIIC_TRY(km_rgbw_labels_canonical(km, lab_d.p));
@@ -655,6 +660,45 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
         return c->fail(CNIIC_ERR_BAD_ARG, "huffman: cannot build code");
     host_trace().mark("tree+codes (host)");
     StreamOut so(c, out, cap, len);
+    uint64_t packed_bits = 0;
+    if (fused && header.size() <= kCcUpBytes - kCcUpHdr) {
+        static_assert(kPuCcUpload.words * 8 == kCcUpBytes && kCcUpHdr >= kCcUpHdrBytes + 4 && kCcUpHdrBytes >= kCcUpLen + 256 && kCcUpLen >= kCcUpCode + 256 * 8, "the upload block's layout");
+        CNIIC_TRY(so.begin_sized(header.size(), (nbits + 7) / 8));   // (the capacity check; the stream's bytes cleared)
+        host_trace().mark("so.begin");
+        // codes, lengths and header in one pinned block that the kernel reads where it lies (three pageable uploads before); its chunk 0
+        // puts the header in front of the payload
+        CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
+        uint8_t *up = reinterpret_cast<uint8_t *>(c->pinned_u.as<uint64_t>() + kPuCcUpload.at);
+        const uint32_t hb = (uint32_t)header.size();
+        const size_t up_bytes = (kCcUpHdr + (size_t)hb + 3) & ~(size_t)3;
+        memset(up, 0, up_bytes);
+        memcpy(up + kCcUpCode, ccode.data(), (size_t)K * 8);
+        memcpy(up + kCcUpLen, clen.data(), K);
+        memcpy(up + kCcUpHdrBytes, &hb, 4);
+        memcpy(up + kCcUpHdr, header.data(), hb);
+        uint64_t *done = c->pinned_u.as<uint64_t>() + kPuCcPacked.at;
+        {
+            ScopedKernelTimer t(c, "huff_pack");
+            CNIIC_TRY(sp_pixpack(c, &s->sp, partlab.p, look, up, hb, so.dev, done));
+            host_trace().mark("pixpack enq");
+            CNIIC_HIP_TRY(c, ctx_spin_sync(c));
+            t.stop(1);
+        }
+        host_trace().mark("pack (+sync)");
+        // a block that gave the look-back up (its wait ran out): the stream is incomplete -- the split kernels below, from the same partlab
+        if (done[0]) fused = false;
+        else packed_bits = done[1];
+    } else {
+        fused = false;
+    }
+    if (!fused) {
+    // (tests: CNIIC_TEST_CC_TAIL=require makes the silent hand-over an error, as CNIIC_KM_PS_REQUIRE does for the persistent K-means)
+    if (const char *e = test_env("CNIIC_TEST_CC_TAIL"))
+        if (!strcmp(e, "require")) return c->fail(CNIIC_ERR_HIP, "cluster-colors: the fused pick-and-pack did not produce the stream (CNIIC_TEST_CC_TAIL=require)");
+    if (partlab.p) {   // (the labels in partition order are there, the pixels' are not)
+        CNIIC_HIP_TRY(c, pixlab.alloc(n + 16));
+        CNIIC_TRY(sp_pixlab(c, &s->sp, rgb_d, partlab.p, wide, pixlab.p));
+    }
     CNIIC_TRY(so.begin(header, (nbits + 7) / 8));
     host_trace().mark("so.begin");
     DevBuf clen_d, ccode_d;
@@ -662,7 +706,6 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     CNIIC_HIP_TRY(c, ccode_d.alloc((uint64_t)K * 8));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(clen_d.p, clen.data(), K, hipMemcpyHostToDevice, c->stream));
     CNIIC_HIP_TRY(c, hipMemcpyAsync(ccode_d.p, ccode.data(), (size_t)K * 8, hipMemcpyHostToDevice, c->stream));
-    uint64_t packed_bits = 0;
     {
         ScopedKernelTimer t(c, "huff_pack");
         CNIIC_TRY(huff_pack_labels(c, pixlab.p, n, wide, K, clen_d.as<uint8_t>(), ccode_d.as<uint64_t>(), so.dev,
@@ -670,6 +713,7 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
         t.stop(1);
     }
     host_trace().mark("pack (+sync)");
+    }
     if (packed_bits != nbits)
         return c->fail(CNIIC_ERR_HIP, "cluster-colors: packed %llu bits, histogram predicts %llu",
                        (unsigned long long)packed_bits, (unsigned long long)nbits);

@@ -279,8 +279,10 @@ constexpr PuSlot kPuPaletteWeights{8, 4096};  // cc_finish: this image's pixels 
 constexpr PuSlot kPuHdecode{4104, 3};         // huff_decode_dev: total symbols, "an end moved", blocks that gave the stream up (k_hdecode.hip)
 constexpr PuSlot kPuTrieTotals{4108, 6};      // huff_parse_leaves_dev: TpTotals (k_trieparse.hip)
 constexpr PuSlot kPuLeafRuns{4114, 3};        // huff_tree_from_runs: number of runs, then bits / too long / longest (k_huff.hip)
+constexpr PuSlot kPuCcUpload{4120, 1024};     // cc_finish: codes, lengths and header for k_sp_pixpack, which reads them here (kCcUp*)
+constexpr PuSlot kPuCcPacked{5144, 2};        // cc_finish: "a block of k_sp_pixpack gave up", the bits it wrote
 constexpr PuSlot kPuSlots[] = {kPuSpCount, kPuPointCount, kPuImageCount, kPuHufTotals, kPuDeltaOverflow, kPuDeltaPacked,
-                               kPuPaletteWeights, kPuHdecode, kPuTrieTotals, kPuLeafRuns};   // in ascending order
+                               kPuPaletteWeights, kPuHdecode, kPuTrieTotals, kPuLeafRuns, kPuCcUpload, kPuCcPacked};   // in ascending order
 constexpr bool pu_slots_disjoint() {
     uint32_t end = 0;
     for (const PuSlot &s : kPuSlots) {
@@ -582,6 +584,13 @@ int sp_occupancy(Ctx *c, const SpPlan *plan, uint32_t *occ_d);  // this image's 
 // final cell-major labels -> label of every pixel, image order
 int sp_pixel_labels(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const uint32_t *cell_start_d, const uint32_t *ckeys_d,
                     const void *labels_d, bool wide, void *pixlab_d);
+// ... in its two steps (partition order, then image order), and the second step fused with the Huffman pack for narrow labels (k_sp_pixpack)
+int sp_part_labels(Ctx *c, const SpPlan *plan, const uint32_t *cell_start_d, const uint32_t *ckeys_d, const void *labels_d, bool wide, DevBuf &partlab,
+                   DevBuf *look /* optional: sp_pixpack's ticket and look-back words, zeroed by the kernel */);
+int sp_pixlab(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const void *partlab_d, bool wide, void *pixlab_d);
+int sp_pixpack(Ctx *c, const SpPlan *plan, const void *partlab_d, DevBuf &look, const uint8_t *upl_h, uint32_t hdr_bytes, uint8_t *out_d, uint64_t *done_h);
+// the block cc_finish fills for sp_pixpack (pinned: kPuCcUpload; the kernel reads it there): the K <= 256 clusters' codes and lengths, the stream's header
+constexpr uint32_t kCcUpCode = 0, kCcUpLen = 2048, kCcUpHdrBytes = 2304 /* u32 */, kCcUpHdr = 2312 /* zero-padded to whole words */, kCcUpBytes = 8192;
 // cell_count_d (optional, 24-bit tables): zeroed u32[32768] receiving the occupied bins per K-means colour cell
 int hist_compact_count(Ctx *c, const uint32_t *table_d, uint32_t bits, CompactPlan *plan, uint32_t *cell_count_d = nullptr,
                        const uint8_t *pages_d = nullptr);

@@ -183,6 +183,68 @@ template <int THREADS> __device__ __forceinline__ uint32_t block_exclusive_scan(
     return off + inc - v;
 }
 
+// ---- the codes of a block's symbols into the output (k_huff.hip: pack_write_body; k_points.hip: k_sp_pixpack).  Thread t holds PER
+// consecutive symbols: lab[i] = row of s_tab (the codes, in LDS), l[i] = code length (0: no symbol, or a zero-length code); excl = bits of
+// the threads before it, total = bits of the whole block (the same value in every thread), g0 = bit of the output the block's first bit is.
+// The bits are put together in `img` (LDS, img_words words: the image starts on the output's word grid) and leave as whole big-endian
+// words, atomicOr only on the two words shared with the neighbours; a block of more bits than the image holds goes to memory piece by
+// piece.  The output is pre-zeroed.  Every thread of the block calls; a caller that comes back with the same img puts a barrier in between.
+template <int THREADS, int PER>
+__device__ __forceinline__ void pack_emit(const uint32_t (&lab)[PER], const uint32_t (&l)[PER], uint32_t excl, uint32_t total, uint64_t g0,
+                                          const unsigned long long *s_tab, uint32_t *img, uint32_t img_words, uint32_t *__restrict__ out_words) {
+    const uint32_t skew = (uint32_t)(g0 & 31);
+    uint32_t pos = skew + excl;
+    const uint32_t nw_all = (skew + total + 31) >> 5;
+    if (nw_all + 2 > img_words) {  // too many bits for the image: straight to memory (words are big-endian bit order)
+        const uint64_t w0 = g0 >> 5;
+#pragma unroll 1
+        for (int i = 0; i < PER; i++) {
+            const uint32_t L = l[i];
+            if (L == 0) continue;
+            const uint64_t cd = s_tab[lab[i]];
+            const uint32_t w = pos >> 5, b = pos & 31, room = 32 - b;
+            if (L <= room) {
+                atomicOr(&out_words[w0 + w], __builtin_bswap32((uint32_t)(cd << (room - L))));
+            } else {
+                const uint32_t rem = L - room;
+                atomicOr(&out_words[w0 + w], __builtin_bswap32((uint32_t)(cd >> rem)));
+                if (rem <= 32) atomicOr(&out_words[w0 + w + 1], __builtin_bswap32((uint32_t)(cd << (32 - rem))));
+                else { atomicOr(&out_words[w0 + w + 1], __builtin_bswap32((uint32_t)(cd >> (rem - 32)))); atomicOr(&out_words[w0 + w + 2], __builtin_bswap32((uint32_t)(cd << (64 - rem)))); }
+            }
+            pos += L;
+        }
+        return;
+    }
+    // the image is cleared only as far as this block's bits reach (a palette's codes average 8 bits)
+    for (uint32_t i = threadIdx.x; i < nw_all + 2; i += THREADS) img[i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PER; i++) {
+        const uint32_t L = l[i];
+        if (L == 0) continue;
+        const uint64_t cd = s_tab[lab[i]];
+        const uint32_t w = pos >> 5, b = pos & 31, room = 32 - b;
+        if (L <= room) {
+            atomicOr(&img[w], (uint32_t)(cd << (room - L)));
+        } else {
+            const uint32_t rem = L - room;
+            atomicOr(&img[w], (uint32_t)(cd >> rem));
+            if (rem <= 32) atomicOr(&img[w + 1], (uint32_t)(cd << (32 - rem)));
+            else { atomicOr(&img[w + 1], (uint32_t)(cd >> (rem - 32))); atomicOr(&img[w + 2], (uint32_t)(cd << (64 - rem))); }
+        }
+        pos += L;
+    }
+    __syncthreads();
+    if (total == 0) return;
+    const uint64_t w0 = g0 >> 5;
+    for (uint32_t i = threadIdx.x; i < nw_all; i += THREADS) {
+        const uint32_t v = __builtin_bswap32(img[i]);
+        if (v == 0) continue;
+        if (i == 0 || i == nw_all - 1) atomicOr(&out_words[w0 + i], v);
+        else out_words[w0 + i] = v;
+    }
+}
+
 // ---- colour-space cells of the cluster-colors K-means (k_kmeans_rgbw.hip); the compaction counts them on its way
 // (kCellShift, kCellsPerDim, kNumCells: common.hpp)
 // Cell id = super-cell (4x4x4 cells = a 32^3 cube of colours; 9 bits, r-major) << 6 | cell within it (6 bits,

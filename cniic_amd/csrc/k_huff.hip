@@ -332,64 +332,10 @@ __device__ __forceinline__ void pack_write_body(const LabelT *__restrict__ pixla
     }
 #pragma unroll
     for (int i = 0; i < kPackPer; i++) { l[i] = lab[i] != 0xffffffffu ? s_len[lab[i]] : 0; bits += l[i]; }
-    uint32_t excl = block_exclusive_scan<kPackThreads>(bits, wsum);
-    const uint64_t g0 = bit_base + *chunk_off;
-    const uint32_t skew = (uint32_t)(g0 & 31);
-    uint32_t pos = skew + excl;
-    // the image is cleared only as far as this chunk's bits reach (the array is sized for 64 bits per symbol; a palette's codes
-    // average 8: clearing all of it was 8 LDS bytes per symbol)
+    const uint32_t excl = block_exclusive_scan<kPackThreads>(bits, wsum);
     if (threadIdx.x == kPackThreads - 1) s_total = excl + bits;
     __syncthreads();
-    const uint32_t nw_all = (skew + s_total + 31) >> 5;
-    if (nw_all + 2 > min(kImgWords, img_cap)) {  // too many bits for the image: straight to memory (the output is pre-zeroed; words are big-endian bit order)
-        const uint64_t w0 = g0 >> 5;
-#pragma unroll 1
-        for (int i = 0; i < kPackPer; i++) {
-            const uint32_t L = l[i];
-            if (L == 0) continue;
-            const uint64_t cd = s_tab[lab[i]];
-            const uint32_t w = pos >> 5, b = pos & 31, room = 32 - b;
-            if (L <= room) {
-                atomicOr(&out_words[w0 + w], __builtin_bswap32((uint32_t)(cd << (room - L))));
-            } else {
-                const uint32_t rem = L - room;
-                atomicOr(&out_words[w0 + w], __builtin_bswap32((uint32_t)(cd >> rem)));
-                if (rem <= 32) atomicOr(&out_words[w0 + w + 1], __builtin_bswap32((uint32_t)(cd << (32 - rem))));
-                else { atomicOr(&out_words[w0 + w + 1], __builtin_bswap32((uint32_t)(cd >> (rem - 32)))); atomicOr(&out_words[w0 + w + 2], __builtin_bswap32((uint32_t)(cd << (64 - rem)))); }
-            }
-            pos += L;
-        }
-        return;
-    }
-    for (uint32_t i = threadIdx.x; i < nw_all + 2; i += kPackThreads) img[i] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kPackPer; i++) {
-        const uint32_t L = l[i];
-        if (L == 0) continue;
-        const uint64_t cd = s_tab[lab[i]];
-        const uint32_t w = pos >> 5, b = pos & 31, room = 32 - b;
-        if (L <= room) {
-            atomicOr(&img[w], (uint32_t)(cd << (room - L)));
-        } else {
-            const uint32_t rem = L - room;
-            atomicOr(&img[w], (uint32_t)(cd >> rem));
-            if (rem <= 32) atomicOr(&img[w + 1], (uint32_t)(cd << (32 - rem)));
-            else { atomicOr(&img[w + 1], (uint32_t)(cd >> (rem - 32))); atomicOr(&img[w + 2], (uint32_t)(cd << (64 - rem))); }
-        }
-        pos += L;
-    }
-    __syncthreads();
-    const uint32_t total = s_total;
-    if (total == 0) return;
-    const uint32_t nwords = (skew + total + 31) >> 5;
-    const uint64_t w0 = g0 >> 5;
-    for (uint32_t i = threadIdx.x; i < nwords; i += kPackThreads) {
-        const uint32_t v = __builtin_bswap32(img[i]);
-        if (v == 0) continue;
-        if (i == 0 || i == nwords - 1) atomicOr(&out_words[w0 + i], v);
-        else out_words[w0 + i] = v;
-    }
+    pack_emit<kPackThreads, kPackPer>(lab, l, excl, s_total, bit_base + *chunk_off, s_tab, img, min(kImgWords, img_cap), out_words);
 }
 
 template <typename LabelT>

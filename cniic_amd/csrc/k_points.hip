@@ -20,7 +20,12 @@
 //   k_sp_emit      the staged colours, counts and their initial labels to their places in the K-means arrays
 //   ... K-means ...
 //   k_sp_partlab   per bucket: label of every partitioned pixel from an LDS table of the bucket's colours
-//   k_sp_pixlab    per chunk: its 512 label runs into LDS, each pixel picks stage[prank]  -> label stream   read 1 + 2, write 1 B/px
+//   (the host waits for the K-means result block here, builds the Huffman tree and leaves codes, lengths and header in a pinned block)
+//   k_sp_pixpack   narrow labels (K <= 256): per chunk, its 512 label runs into LDS, each pixel picks stage[prank] into a REGISTER,
+//                  and the chunk's codes go straight into the stream -- the chunk's first bit from a ticketed look-back over the
+//                  chunks' bit counts, the emit the label pack's own (pack_emit, device_utils.hpp)          read 1 + 2 B/px, write the stream
+//   k_sp_pixlab    wide labels, the frame batches, the frozen palettes, and when k_sp_pixpack gives its look-back up: the same pick
+//                  written out as a label stream for the pack's three passes (k_huff.hip)                   read 1 + 2, write 1 B/px
 //
 // No atomics on global memory, no table of 2^24 entries, and every pixel's label is found without a random
 // read.  Results are identical to the dense-table path (k_hist.hip + k_cells_write_tbl + k_pixel_labels): the
@@ -352,9 +357,13 @@ __global__ __launch_bounds__(256) void k_bits_prefix(const unsigned long long *_
 template <typename LabelT>
 __global__ __launch_bounds__(kSpThreads) void k_sp_partlab(const uint16_t *__restrict__ part, const uint32_t *__restrict__ bstart,
                                                            const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ ckeys,
-                                                           const LabelT *__restrict__ labels, LabelT *__restrict__ partlab) {
+                                                           const LabelT *__restrict__ labels, LabelT *__restrict__ partlab,
+                                                           unsigned long long *__restrict__ look = nullptr, uint32_t look_words = 0) {
     extern __shared__ __align__(16) uint8_t sp_lds[];
     LabelT *lut = reinterpret_cast<LabelT *>(sp_lds);
+    // (the ticket, the give-up word and the look-back words of the k_sp_pixpack behind this kernel start at zero: no dispatch of their own)
+    if (look && blockIdx.x == 0 && blockIdx.y == 0)
+        for (uint32_t i = threadIdx.x; i < look_words; i += kSpThreads) look[i] = 0ull;
     const uint32_t bucket = blockIdx.x;
     uint64_t s = bstart[bucket], e = bstart[bucket + 1];
     if (s == e) return;
@@ -383,19 +392,13 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_partlab(const uint16_t *__res
     });
 }
 
-// One block per chunk: its 512 label runs into LDS (the chunk's pixels in bucket-sorted order), then every pixel picks stage[prank].
-// LDS (dynamic): stage LabelT[kSpChunk] | off u32[kSpBuckets + 1] | gsrc u32[kSpBuckets]
+// A chunk's 512 label runs into LDS: stage[j] = label of the pixel at place j of the chunk's bucket-sorted order.  The whole block calls;
+// a barrier stands behind the last store.  off u32[kSpBuckets + 1], gsrc u32[kSpBuckets], wsum u32[kSpWaves]: LDS
 template <typename LabelT>
-__global__ __launch_bounds__(kSpThreads) void k_sp_pixlab(const uint8_t *__restrict__ rgb, uint64_t npx, const uint32_t *__restrict__ cnt,
-                                                          const uint32_t *__restrict__ pre, const uint32_t *__restrict__ bstart,
-                                                          const LabelT *__restrict__ partlab, const uint16_t *__restrict__ prank,
-                                                          LabelT *__restrict__ pixlab) {
-    extern __shared__ __align__(16) uint8_t sp_lds[];
-    LabelT *stage = reinterpret_cast<LabelT *>(sp_lds);
-    uint32_t *off = reinterpret_cast<uint32_t *>(sp_lds + (size_t)kSpChunk * sizeof(LabelT));  // [kSpBuckets + 1]
-    uint32_t *gsrc = off + kSpBuckets + 1;
-    __shared__ uint32_t wsum[kSpWaves];
-    const uint32_t *mycnt = cnt + (size_t)blockIdx.x * kSpBuckets, *mypre = pre + (size_t)blockIdx.x * kSpBuckets;
+__device__ __forceinline__ void sp_stage_labels(uint32_t chunk, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ pre,
+                                                const uint32_t *__restrict__ bstart, const LabelT *__restrict__ partlab, LabelT *stage,
+                                                uint32_t *off, uint32_t *gsrc, uint32_t *wsum) {
+    const uint32_t *mycnt = cnt + (size_t)chunk * kSpBuckets, *mypre = pre + (size_t)chunk * kSpBuckets;
     const uint32_t n_b = threadIdx.x < kSpBuckets ? mycnt[threadIdx.x] : 0u;
     const uint32_t ex = scan512(n_b, wsum);
     if (threadIdx.x < kSpBuckets) off[threadIdx.x] = ex;
@@ -413,6 +416,21 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_pixlab(const uint8_t *__restr
             if (jb[t] != 0xffffffffu) stage[j + 64 * t] = got[t];
     });
     __syncthreads();
+}
+
+// One block per chunk: its 512 label runs into LDS (the chunk's pixels in bucket-sorted order), then every pixel picks stage[prank].
+// LDS (dynamic): stage LabelT[kSpChunk] | off u32[kSpBuckets + 1] | gsrc u32[kSpBuckets]
+template <typename LabelT>
+__global__ __launch_bounds__(kSpThreads) void k_sp_pixlab(const uint8_t *__restrict__ rgb, uint64_t npx, const uint32_t *__restrict__ cnt,
+                                                          const uint32_t *__restrict__ pre, const uint32_t *__restrict__ bstart,
+                                                          const LabelT *__restrict__ partlab, const uint16_t *__restrict__ prank,
+                                                          LabelT *__restrict__ pixlab) {
+    extern __shared__ __align__(16) uint8_t sp_lds[];
+    LabelT *stage = reinterpret_cast<LabelT *>(sp_lds);
+    uint32_t *off = reinterpret_cast<uint32_t *>(sp_lds + (size_t)kSpChunk * sizeof(LabelT));  // [kSpBuckets + 1]
+    uint32_t *gsrc = off + kSpBuckets + 1;
+    __shared__ uint32_t wsum[kSpWaves];
+    sp_stage_labels(blockIdx.x, cnt, pre, bstart, partlab, stage, off, gsrc, wsum);
     // every pixel picks stage[its place in the sorted order] (prank, written by k_sp_scatter): 2 + 1 bytes per pixel, the
     // image itself is not read again
     const uint64_t p0 = (uint64_t)blockIdx.x * kSpChunk, p1 = min(npx, p0 + kSpChunk);
@@ -442,6 +460,190 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_pixlab(const uint8_t *__restr
     }
 }
 
+// ---- the pixel labels of a chunk straight into the Huffman stream (narrow labels): k_sp_pixlab's pick and the label pack's count, scan
+// and write (k_huff.hip) in one kernel, so the label image -- written once and read twice -- never exists.
+// Phase 1: the block stages the chunk's label runs and every thread picks its 64 labels (the 16-pixel groups tid + 1024 r of the chunk,
+// r = 0..3, k_sp_pixlab's mapping) into registers, four to a word, and sums their code lengths round by round; ONE block scan of the four
+// sums gives every thread its bit offset in every round, the rounds' bits and the chunk's.
+// The chunk's first bit, a decoupled look-back: a block takes its chunk from a ticket counter, so the chunks before it belong to blocks
+// that have started and wait for nobody before they publish.  Chunk i's word = state << 62 | bits: kLookAgg with the chunk's own bits as
+// soon as phase 1 has them, kLookInc with the bits of chunks 0..i once its first bit is known (chunk 0 at once).  The word is the whole
+// message, so it is stored and polled with relaxed agent-scope atomics and no fence (Guideline 16's 8-byte granule: nothing else is
+// handed over).  Wave 0 looks at 256 words at a time, four a lane, and adds everything down to the nearest inclusive one.  Every spin
+// watches the clock and the give-up word (as ps_spin, k_kmeans_persist.hip); who gives up sets that word, every block that sees it
+// leaves, and the host packs from partlab with the split kernels, which clear the stream first.
+// Phase 2: round by round pack_emit (device_utils.hpp), the pack's own emit.
+// look: [0] ticket, [1] give-up, [2] the stream's payload bits (the last chunk's inclusive word without its state), [3 + i] chunk i's
+// word -- zeroed by block (0, 0) of the k_sp_partlab in front; the host fetches [1] and [2] with one copy.
+constexpr uint32_t kSpPackRounds = kSpChunk / (kSpThreads * 16);
+constexpr uint32_t kSpPackImgWords = kSpThreads * 16 / 2 + 2;   // 16 bits per symbol of a round fit (a palette's codes average 8)
+constexpr unsigned long long kLookAgg = 1ull << 62, kLookInc = 2ull << 62, kLookMask = (1ull << 62) - 1;
+constexpr uint32_t kLookHead = 3, kLookPer = 4;   // words in front of the chunks'; words a lane of wave 0 looks at per window
+constexpr size_t kSpPackDyn = (size_t)kSpChunk + kSpBuckets * 8 + 16;
+struct SpPackArgs {
+    const uint32_t *cnt, *pre, *bstart;
+    const uint8_t *partlab;
+    const uint16_t *prank;
+    uint64_t npx;
+    uint32_t nchunks, img_cap;
+    const uint8_t *upl;             // the host's pinned block (kCcUp*, common.hpp): codes, lengths, the stream's header -- read where it lies
+    uint32_t hdr_bytes;
+    uint32_t *out_words;            // pre-zeroed
+    uint64_t bit_base;
+    unsigned long long *look;
+    unsigned long long timeout_ticks;
+    uint32_t test_giveup;           // tests: give up at the first poll
+};
+__device__ __forceinline__ unsigned long long look_ld(unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void look_st(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(kSpThreads) void k_sp_pixpack(SpPackArgs a) {
+    extern __shared__ __align__(16) uint8_t sp_lds[];
+    uint8_t *stage = sp_lds;
+    uint32_t *off = reinterpret_cast<uint32_t *>(sp_lds + (size_t)kSpChunk);  // [kSpBuckets + 1]
+    uint32_t *gsrc = off + kSpBuckets + 1;
+    __shared__ unsigned long long s_tab[256], s_excl;
+    __shared__ uint32_t img[kSpPackImgWords];
+    __shared__ uint32_t wsum[kSpWaves], s_rsum[kSpPackRounds][kSpWaves], s_chunk, s_ok;
+    __shared__ uint8_t s_len[256];
+    // stage 64 KiB + offsets 4 KiB + codes 2.3 KiB + bit image 32 KiB: one block per CU
+    static_assert(kSpPackDyn + 8 * 257 + 4 * kSpPackImgWords + 4 * ((1 + kSpPackRounds) * kSpWaves + 2) + 256 + 64 <= 160 * 1024, "the LDS of k_sp_pixpack");
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) { s_chunk = atomicAdd(reinterpret_cast<uint32_t *>(a.look), 1u); s_excl = 0ull; s_ok = 1u; }
+    // the codes and the header come straight from the host's pinned block (no copy dispatch in front of this kernel): asked for now,
+    // used behind the staging, which hides the trip
+    unsigned long long tcode = 0;
+    uint32_t tlen = 0;
+    if (tid < 256) { tcode = reinterpret_cast<const unsigned long long *>(a.upl + kCcUpCode)[tid]; tlen = a.upl[kCcUpLen + tid]; }
+    __syncthreads();
+    const uint32_t chunk = s_chunk;
+    if (chunk >= a.nchunks) return;   // (cannot be: the grid is nchunks blocks and the ticket starts at zero)
+    constexpr uint32_t kHdrPer = (kCcUpBytes - kCcUpHdr) / 4 / kSpThreads + 1;
+    uint32_t hv[kHdrPer];
+    const uint32_t hw = chunk == 0 ? (a.hdr_bytes + 3u) / 4u : 0u;
+#pragma unroll
+    for (uint32_t q = 0; q < kHdrPer; q++) { const uint32_t i = tid + kSpThreads * q; hv[q] = i < hw ? reinterpret_cast<const uint32_t *>(a.upl + kCcUpHdr)[i] : 0u; }
+    // the thread's 64 ranks are asked for now: they need nothing of the stage and arrive while it is filled (a ragged last group reads
+    // its 16 ranks all the same: prank has 16 entries of slack, and any rank is a place of the stage)
+    const uint64_t p0 = (uint64_t)chunk * kSpChunk, p1 = min(a.npx, p0 + kSpChunk);
+    uint4 pr[kSpPackRounds][2];
+#pragma unroll
+    for (uint32_t r = 0; r < kSpPackRounds; r++) {
+        const uint64_t first = p0 + ((uint64_t)tid + kSpThreads * r) * 16;
+        const uint4 *rp = reinterpret_cast<const uint4 *>(a.prank + first);
+        pr[r][0] = first < p1 ? rp[0] : make_uint4(0, 0, 0, 0);
+        pr[r][1] = first < p1 ? rp[1] : make_uint4(0, 0, 0, 0);
+    }
+    sp_stage_labels<uint8_t>(chunk, a.cnt, a.pre, a.bstart, a.partlab, stage, off, gsrc, wsum);
+    if (tid < 256) { s_tab[tid] = tcode; s_len[tid] = (uint8_t)tlen; }
+    // the header, as words OR-ed in like everything else: its last word may hold the payload's first bits
+#pragma unroll
+    for (uint32_t q = 0; q < kHdrPer; q++) { const uint32_t i = tid + kSpThreads * q; if (i < hw && hv[q]) atomicOr(&a.out_words[i], hv[q]); }
+    __syncthreads();
+    // ---- phase 1
+    const uint32_t lane = tid & 63u, wid = tid >> 6;
+    uint32_t lw[kSpPackRounds][4], wexcl[kSpPackRounds];   // the packed labels; the bits of the wave's lanes before this one, per round
+#pragma unroll
+    for (uint32_t r = 0; r < kSpPackRounds; r++) {
+        const uint64_t first = p0 + ((uint64_t)tid + kSpThreads * r) * 16;
+        const uint32_t m = first < p1 ? (uint32_t)min<uint64_t>(16, p1 - first) : 0u;
+        uint32_t lab[16], bits = 0;
+        const uint32_t rw[8] = {pr[r][0].x, pr[r][0].y, pr[r][0].z, pr[r][0].w, pr[r][1].x, pr[r][1].y, pr[r][1].z, pr[r][1].w};
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) lab[i] = stage[(rw[i >> 1] >> (16 * (i & 1))) & 0xffffu];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) bits += i < m ? (uint32_t)s_len[lab[i]] : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; j++) lw[r][j] = lab[4 * j] | (lab[4 * j + 1] << 8) | (lab[4 * j + 2] << 16) | (lab[4 * j + 3] << 24);
+        // (a word the compiler cannot see through: it kept the 64 labels it had packed in a register each, for phase 2 to come, and
+        // spilled -- tests/test_kernel_resources_cpu.py holds the kernel to a scratch size of zero)
+#pragma unroll
+        for (int j = 0; j < 4; j++) asm volatile("" : "+v"(lw[r][j]));
+        const uint32_t inc = wave_inclusive_scan(bits);
+        wexcl[r] = inc - bits;
+        if (lane == 63) s_rsum[r][wid] = inc;
+    }
+    __syncthreads();
+    uint32_t total = 0;   // (a chunk has at most 2^16 x 64 bits)
+#pragma unroll
+    for (uint32_t r = 0; r < kSpPackRounds; r++)
+#pragma unroll
+        for (uint32_t i = 0; i < kSpWaves; i++) total += s_rsum[r][i];
+    // ---- the chunk's first bit
+    if (tid < 64) {
+        unsigned long long *W = a.look + kLookHead;
+        uint32_t *giveup = reinterpret_cast<uint32_t *>(a.look + 1);
+        bool ok = true;
+        unsigned long long mine = 0;   // what this lane adds to the bits in front of the chunk
+        if (chunk == 0) {
+            if (tid == 0) look_st(&W[0], kLookInc | total);
+        } else {
+            if (tid == 0) look_st(&W[chunk], kLookAgg | total);
+            const unsigned long long t0 = wall_clock64();
+            long long hi = (long long)chunk - 1;
+            for (bool found = false; !found; hi -= 64 * kLookPer) {
+                unsigned long long v[kLookPer];
+                for (uint32_t spins = 0;;) {
+                    bool ready = true;
+#pragma unroll
+                    for (uint32_t k = 0; k < kLookPer; k++) {
+                        const long long j = hi - (long long)(tid + 64 * k);
+                        v[k] = j >= 0 ? look_ld(&W[j]) : kLookInc;
+                        ready = ready && (v[k] >> 62) != 0;
+                    }
+                    if (a.test_giveup) { ok = false; break; }
+                    if (__all(ready)) break;
+                    __builtin_amdgcn_s_sleep(1);
+                    // (the wave leaves together: one lane's clock past the limit takes all of them)
+                    if ((++spins & 63u) == 0 && __any(__hip_atomic_load(giveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || wall_clock64() - t0 > a.timeout_ticks)) { ok = false; break; }
+                }
+                if (!ok) break;
+#pragma unroll
+                for (uint32_t k = 0; k < kLookPer; k++) {   // nearest first: words chunk - 1 - (64 k + lane)
+                    const bool there = hi - (long long)(tid + 64 * k) >= 0;
+                    const unsigned long long inc = __ballot(there && (v[k] >> 62) == 2);
+                    const uint32_t nearest = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;
+                    if (!found && there && tid <= nearest) mine += v[k] & kLookMask;
+                    found = found || inc != 0;   // (chunk 0's word is inclusive from the start: a window without one has 256 words and more in front of it)
+                }
+            }
+        }
+        const unsigned long long sum = wave_inclusive_scan64<false>(mine);   // lane 63: the bits in front of the chunk
+        if (tid == 63) {
+            if (!ok) {
+                __hip_atomic_store(giveup, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s_ok = 0u;
+            } else {
+                s_excl = sum;
+                if (chunk) look_st(&W[chunk], kLookInc | (sum + total));
+                if (chunk == a.nchunks - 1) look_st(a.look + 2, sum + total);
+            }
+        }
+    }
+    __syncthreads();
+    if (!s_ok) return;
+    const uint64_t g0 = a.bit_base + s_excl;
+    // ---- phase 2
+    uint32_t run = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kSpPackRounds; r++) {
+        const uint64_t first = p0 + ((uint64_t)tid + kSpThreads * r) * 16;
+        const uint32_t m = first < p1 ? (uint32_t)min<uint64_t>(16, p1 - first) : 0u;
+        uint32_t lab[16], l[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) {
+            lab[i] = (lw[r][i >> 2] >> (8 * (i & 3))) & 255u;
+            l[i] = i < m ? (uint32_t)s_len[lab[i]] : 0u;
+        }
+        uint32_t before = 0, rtot = 0;   // the waves' sums of the round stay where phase 1 left them
+#pragma unroll
+        for (uint32_t i = 0; i < kSpWaves; i++) { const uint32_t v = s_rsum[r][i]; rtot += v; if (i < wid) before += v; }
+        pack_emit<kSpThreads, 16>(lab, l, before + wexcl[r], rtot, g0 + run, s_tab, img, min(kSpPackImgWords, a.img_cap), a.out_words);
+        run += rtot;
+        __syncthreads();   // (img is the next round's)
+    }
+}
+
 // =========================================================================== host
 static int sp_set_lds(Ctx *c) {
     static bool done = false;  // (function attributes are per process)
@@ -453,6 +655,7 @@ static int sp_set_lds(Ctx *c) {
     CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_sp_partlab<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, big));
     CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_sp_pixlab<uint8_t>), hipFuncAttributeMaxDynamicSharedMemorySize, big));
     CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_sp_pixlab<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    CNIIC_HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_sp_pixpack), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSpPackDyn));   // (beside 35 KiB of static LDS)
     done = true;
     return CNIIC_OK;
 }
@@ -535,26 +738,67 @@ int sp_occupancy(Ctx *c, const SpPlan *plan, uint32_t *occ_d) {
     return CNIIC_OK;
 }
 
+// labels_d: the K-means' final cell-major labels -> partlab: label of every pixel in partition order.  look (optional, narrow labels): the
+// ticket and look-back words of sp_pixpack, allocated here and zeroed by the kernel
+int sp_part_labels(Ctx *c, const SpPlan *plan, const uint32_t *cell_start_d, const uint32_t *ckeys_d, const void *labels_d, bool wide, DevBuf &partlab,
+                   DevBuf *look) {
+    const uint64_t lb = wide ? 2 : 1;
+    CNIIC_HIP_TRY(c, partlab.alloc(plan->npx * lb + 16));
+    const uint32_t look_words = look ? plan->nchunks + kLookHead : 0;
+    if (look) CNIIC_HIP_TRY(c, look->alloc((uint64_t)look_words * 8));
+    const dim3 grid(kSpBuckets, plan->npx >= 2 * (uint64_t)kSpSliceMin ? kSpSlices : 1);
+    if (wide)
+        hipLaunchKernelGGL(k_sp_partlab<uint16_t>, grid, dim3(kSpThreads), (size_t)kSpBins * 2, c->stream, plan->part.as<uint16_t>(),
+                           plan->bstart.as<uint32_t>(), cell_start_d, ckeys_d, static_cast<const uint16_t *>(labels_d), partlab.as<uint16_t>(),
+                           (unsigned long long *)nullptr, 0u);
+    else
+        hipLaunchKernelGGL(k_sp_partlab<uint8_t>, grid, dim3(kSpThreads), (size_t)kSpBins, c->stream, plan->part.as<uint16_t>(),
+                           plan->bstart.as<uint32_t>(), cell_start_d, ckeys_d, static_cast<const uint8_t *>(labels_d), partlab.as<uint8_t>(),
+                           look ? look->as<unsigned long long>() : nullptr, look_words);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
+// partlab -> pixlab_d: label of every pixel in image order
+int sp_pixlab(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const void *partlab_d, bool wide, void *pixlab_d) {
+    if (wide)
+        hipLaunchKernelGGL(k_sp_pixlab<uint16_t>, dim3(plan->nchunks), dim3(kSpThreads), (size_t)kSpChunk * 2 + kSpBuckets * 8 + 16, c->stream, rgb_d,
+                           plan->npx, plan->cnt.as<uint32_t>(), plan->pre.as<uint32_t>(), plan->bstart.as<uint32_t>(), static_cast<const uint16_t *>(partlab_d),
+                           plan->prank.as<uint16_t>(), static_cast<uint16_t *>(pixlab_d));
+    else
+        hipLaunchKernelGGL(k_sp_pixlab<uint8_t>, dim3(plan->nchunks), dim3(kSpThreads), (size_t)kSpChunk + kSpBuckets * 8 + 16, c->stream, rgb_d,
+                           plan->npx, plan->cnt.as<uint32_t>(), plan->pre.as<uint32_t>(), plan->bstart.as<uint32_t>(), static_cast<const uint8_t *>(partlab_d),
+                           plan->prank.as<uint16_t>(), static_cast<uint8_t *>(pixlab_d));
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
 // labels_d: the K-means' final cell-major labels -> pixlab_d: label of every pixel in image order
 int sp_pixel_labels(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const uint32_t *cell_start_d, const uint32_t *ckeys_d,
                     const void *labels_d, bool wide, void *pixlab_d) {
     DevBuf partlab;
-    const uint64_t lb = wide ? 2 : 1;
-    CNIIC_HIP_TRY(c, partlab.alloc(plan->npx * lb + 16));
-    if (wide) {
-        hipLaunchKernelGGL(k_sp_partlab<uint16_t>, dim3(kSpBuckets, plan->npx >= 2 * (uint64_t)kSpSliceMin ? kSpSlices : 1), dim3(kSpThreads), (size_t)kSpBins * 2, c->stream, plan->part.as<uint16_t>(),
-                           plan->bstart.as<uint32_t>(), cell_start_d, ckeys_d, static_cast<const uint16_t *>(labels_d), partlab.as<uint16_t>());
-        hipLaunchKernelGGL(k_sp_pixlab<uint16_t>, dim3(plan->nchunks), dim3(kSpThreads), (size_t)kSpChunk * 2 + kSpBuckets * 8 + 16, c->stream, rgb_d,
-                           plan->npx, plan->cnt.as<uint32_t>(), plan->pre.as<uint32_t>(), plan->bstart.as<uint32_t>(), partlab.as<uint16_t>(),
-                           plan->prank.as<uint16_t>(), static_cast<uint16_t *>(pixlab_d));
-    } else {
-        hipLaunchKernelGGL(k_sp_partlab<uint8_t>, dim3(kSpBuckets, plan->npx >= 2 * (uint64_t)kSpSliceMin ? kSpSlices : 1), dim3(kSpThreads), (size_t)kSpBins, c->stream, plan->part.as<uint16_t>(),
-                           plan->bstart.as<uint32_t>(), cell_start_d, ckeys_d, static_cast<const uint8_t *>(labels_d), partlab.as<uint8_t>());
-        hipLaunchKernelGGL(k_sp_pixlab<uint8_t>, dim3(plan->nchunks), dim3(kSpThreads), (size_t)kSpChunk + kSpBuckets * 8 + 16, c->stream, rgb_d,
-                           plan->npx, plan->cnt.as<uint32_t>(), plan->pre.as<uint32_t>(), plan->bstart.as<uint32_t>(), partlab.as<uint8_t>(),
-                           plan->prank.as<uint16_t>(), static_cast<uint8_t *>(pixlab_d));
-    }
+    CNIIC_TRY(sp_part_labels(c, plan, cell_start_d, ckeys_d, labels_d, wide, partlab, nullptr));
+    return sp_pixlab(c, plan, rgb_d, partlab.p, wide, pixlab_d);
+}
+
+// partlab (narrow labels) -> the Huffman payload behind hdr_bytes of out_d (4-byte aligned, pre-zeroed) and the header in front of it, from the
+// host's pinned block upl_h (kCcUp*, common.hpp), which the kernel reads where it lies.  look: from sp_part_labels.  done_h: two pinned
+// words that one copy behind the kernel fills -- [0] != 0: a block gave the look-back up and the stream is not complete (the caller packs
+// with sp_pixlab + huff_pack_labels), [1] the payload's bits.  Asynchronous: the words are there when the stream has been waited for.
+int sp_pixpack(Ctx *c, const SpPlan *plan, const void *partlab_d, DevBuf &look, const uint8_t *upl_h, uint32_t hdr_bytes, uint8_t *out_d, uint64_t *done_h) {
+    if (reinterpret_cast<uintptr_t>(out_d) & 3) return c->fail(CNIIC_ERR_BAD_ARG, "sp_pixpack: output must be 4-byte aligned");
+    CNIIC_TRY(sp_set_lds(c));
+    SpPackArgs a{};
+    a.cnt = plan->cnt.as<uint32_t>(); a.pre = plan->pre.as<uint32_t>(); a.bstart = plan->bstart.as<uint32_t>();
+    a.partlab = static_cast<const uint8_t *>(partlab_d); a.prank = plan->prank.as<uint16_t>();
+    a.npx = plan->npx; a.nchunks = plan->nchunks; a.img_cap = pack_img_cap();
+    a.upl = upl_h; a.hdr_bytes = hdr_bytes; a.out_words = reinterpret_cast<uint32_t *>(out_d); a.bit_base = (uint64_t)hdr_bytes * 8;
+    a.look = look.as<unsigned long long>();
+    a.timeout_ticks = 2000ull * 100000ull;   // 2 s at 100 MHz, as the persistent K-means
+    a.test_giveup = test_env("CNIIC_TEST_CC_TAIL_GIVEUP") ? 1u : 0u;
+    hipLaunchKernelGGL(k_sp_pixpack, dim3(plan->nchunks), dim3(kSpThreads), kSpPackDyn, c->stream, a);
     CNIIC_HIP_TRY(c, hipGetLastError());
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(done_h, look.as<unsigned long long>() + 1, 16, hipMemcpyDeviceToHost, c->stream));
     return CNIIC_OK;
 }
 
