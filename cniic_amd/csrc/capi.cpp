@@ -1303,36 +1303,15 @@ static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kme
     return rc;
 }
 
-// Every frame of the list encoded exactly as cniic_codec_encode_opts would.  SMALL cluster-colors(K <= 256) frames in device memory
-// (1 .. kCcSmallMaxPx pixels, no K-means flags) are coded together in one set of launches on this context (cc_small_encode, codec.cpp: a
-// workgroup per frame); which route a frame took shows in no output byte.  The testing library can switch the route off
-// (CNIIC_TEST_CC_SMALL_OFF=1) or lower its pixel bound (CNIIC_TEST_CC_SMALL_MAX_PX).  Every other frame goes to the worker contexts of
-// cniic_codec_encode_batch, handed out from one queue, LARGEST FIRST: with sizes that differ the last worker to finish then holds a small
-// frame, and frames of one size follow one another, which keeps the few scan tables a context caches (`delta`, `hilbert(rle)`) in use.
-// Which worker takes which frame shows in no output.  With the stage timers on, the workers' timers are on too and the context's kernel
-// times are the sums over all frames ("cc_small_batch": k_cc_small, launches = the frames that took the small-frame route).
-static uint64_t cc_small_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_CC_SMALL_OFF")) if (atoi(e) != 0) return 0;
-    if (const char *e = test_env("CNIIC_TEST_CC_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kCcSmallMaxPx);
-    return kCcSmallMaxPx;
-}
-// Small `delta` frames in device memory (1 .. kDeltaSmallMaxPx pixels) likewise: delta_small_encode (codec.cpp), a workgroup per frame from
-// the pixels to the finished stream ("delta_small_batch": k_delta_small, launches = the frames that took the route; "delta_small_place").
-// The testing library can switch it off (CNIIC_TEST_DELTA_SMALL_OFF=1) or lower its bound (CNIIC_TEST_DELTA_SMALL_MAX_PX).
-static uint64_t delta_small_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_OFF")) if (atoi(e) != 0) return 0;
-    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallMaxPx);
-    return kDeltaSmallMaxPx;
-}
-// Small `hufman` frames in device memory (1 .. kHufSmallMaxPx pixels) likewise: huf_small_encode (codec.cpp), the `delta` route's kernel body
-// over the pixels' own colours ("huf_small_batch": k_huf_small, launches = the frames that took the route; "huf_small_place").  The testing
-// library can switch it off (CNIIC_TEST_HUF_SMALL_OFF=1) or lower its bound (CNIIC_TEST_HUF_SMALL_MAX_PX).
-static uint64_t huf_small_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_OFF")) if (atoi(e) != 0) return 0;
-    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kHufSmallMaxPx);
-    return kHufSmallMaxPx;
-}
-// The floor of that route.  The kernel's time is set by its largest frame (every frame has a CU of its own up to 256 frames: 0.05 ms at 32 x 32,
+// Every frame of the list encoded exactly as cniic_codec_encode_opts would.  SMALL frames in device memory of the codecs that have a
+// small-frame route (kSmallRoutes below; codec.hpp has the routes' contract) are coded together on this context, a workgroup per frame;
+// which route a frame took shows in no output byte.  Every other frame goes to the worker contexts of cniic_codec_encode_batch, handed out
+// from one queue, LARGEST FIRST: with sizes that differ the last worker to finish then holds a small frame, and frames of one size follow
+// one another, which keeps the few scan tables a context caches (`delta`, `hilbert(rle)`) in use.  Which worker takes which frame shows in
+// no output.  With the stage timers on, the workers' timers are on too and the context's kernel times are the sums over all frames (a
+// route's "<route>_batch": launches = the frames that took it).
+//
+// The floor of the `hufman` route.  The kernel's time is set by its largest frame (every frame has a CU of its own up to 256 frames: 0.05 ms at 32 x 32,
 // 0.11 at 64 x 64, 0.38 - 0.40 from 128 x 96 on), what the workers cost grows with the number of frames.  Measured against the parent
 // commit's library (tools/small_hufman_probe.py, profiles/small_hufman_probe.json; NOTES AF), whole call, parent's time / this route's:
 //   1 frame:   32 x 32 and 64 x 64 won (1.5x .. 1.9x); 128 x 96, 128 x 128 and 16384 x 1 lost (0.68x .. 0.75x, beyond the spreads)
@@ -1343,21 +1322,11 @@ static uint64_t huf_small_max_px() {
 // CNIIC_TEST_HUF_SMALL_FLOOR_OFF=1.
 constexpr uint32_t kHufSmallFloorFew = 4;
 constexpr uint64_t kHufSmallFloorPxFew = 4096;
-static uint64_t huf_small_floor_px(uint64_t candidates) {
+static uint64_t huf_small_floor_px(uint64_t candidates, uint32_t) {
     if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
     return candidates >= kHufSmallFloorFew ? ~0ull : kHufSmallFloorPxFew;
 }
-// Small voronoi(K <= 256) frames in device memory (1 .. kVorSmallMaxPx pixels, no K-means flags) likewise: vor_small_encode (codec.cpp), a
-// workgroup per frame from the pixels through the whole K-means to the finished stream ("vor_small_batch": k_vor_small, launches = the
-// frames that took the route; "vor_small_place").  The testing library can switch it off (CNIIC_TEST_VOR_SMALL_OFF=1), lower its bound
-// (CNIIC_TEST_VOR_SMALL_MAX_PX) and run it without the stay test (CNIIC_TEST_VOR_SMALL_NO_STAY=1, read in vor_small_encode).  Few heavy
-// frames stay with the workers: vor_small_max_work below.
-static uint64_t vor_small_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_OFF")) if (atoi(e) != 0) return 0;
-    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kVorSmallMaxPx);
-    return kVorSmallMaxPx;
-}
-// The floor of that route.  One workgroup on one CU is slower for ONE heavy frame than the workers' whole chip; what the route costs is set by
+// The floor of the voronoi route.  One workgroup on one CU is slower for ONE heavy frame than the workers' whole chip; what the route costs is set by
 // its heaviest frame (every frame has a CU of its own up to 256 frames), what the workers cost grows with the number of frames.  Measured
 // against the parent commit's library (tools/small_voronoi_probe.py, profiles/small_voronoi_probe.json; NOTES AD), in pixels x K of a frame,
 // parent's time / this route's:
@@ -1377,6 +1346,35 @@ static uint64_t vor_small_max_work(uint64_t candidates) {
     if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
     return candidates >= kVorSmallFloorMany ? ~0ull : candidates >= kVorSmallFloorFew ? kVorSmallFloorWorkSome : kVorSmallFloorWorkFew;
 }
+static uint64_t vor_small_floor_px(uint64_t candidates, uint32_t K) { return vor_small_max_work(candidates) / K; }   // (pixels x K <= the work)
+
+// A small-frame route of encode_frames.  A frame is a CANDIDATE when the route applies to the call and the frame has 1 .. max_px() pixels;
+// a candidate takes the route unless the floor or `takes` keeps it with the workers.  (max_px is a function, not its knobs' names: those
+// must not be in the release library, and small_route_max_px folds them away only as arguments of a call.)
+struct SmallRoute {
+    bool (*applies)(const cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts);   // the codec, its argument, the call's options
+    uint64_t (*max_px)();                                                                     // the route's bound under its _OFF and _MAX_PX knobs
+    uint64_t (*floor)(uint64_t candidates, uint32_t K);                                       // null, or: the most pixels of a frame in a call with so many candidates
+    bool (*takes)(const cniic_ctx *c, const VarFrame &f);                                     // null, or: a veto on one frame
+    int (*run)(cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
+};
+static bool no_flags(const cniic_kmeans_opts *opts) { return !opts || opts->flags == 0; }
+static const SmallRoute kSmallRoutes[] = {
+    {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *opts) { return d.kind == CODEC_CLUSTER_COLORS && d.arg >= 1 && d.arg <= kCcSmallMaxK && no_flags(opts); },
+     [] { return small_route_max_px("CNIIC_TEST_CC_SMALL_OFF", "CNIIC_TEST_CC_SMALL_MAX_PX", kCcSmallMaxPx); }, nullptr, nullptr,
+     [](cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n) { return cc_small_encode(c, d.arg, opts, fr, n); }},
+    {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *opts) { return d.kind == CODEC_VORONOI && d.arg >= 1 && d.arg <= kVorSmallMaxK && no_flags(opts); },
+     [] { return small_route_max_px("CNIIC_TEST_VOR_SMALL_OFF", "CNIIC_TEST_VOR_SMALL_MAX_PX", kVorSmallMaxPx); }, vor_small_floor_px, nullptr,
+     [](cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n) { return vor_small_encode(c, d.arg, opts, fr, n); }},
+    // `delta`: not with the big encoder's route forced, and not a frame whose size has an injected scan
+    {[](const cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *) { return d.kind == CODEC_DELTA && c->opt(CNIIC_OPT_DELTA_ROUTE, "CNIIC_DELTA_ROUTE", 0) != 32; },
+     [] { return small_route_max_px("CNIIC_TEST_DELTA_SMALL_OFF", "CNIIC_TEST_DELTA_SMALL_MAX_PX", kDeltaSmallMaxPx); }, nullptr,
+     [](const cniic_ctx *c, const VarFrame &f) { return !(c->scan_xy.p && c->scan_w == f.w && c->scan_h == f.h); },
+     [](cniic_ctx *c, const CodecDesc &, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return delta_small_encode(c, fr, n); }},
+    {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *opts) { return d.kind == CODEC_HUFMAN && no_flags(opts); },
+     [] { return small_route_max_px("CNIIC_TEST_HUF_SMALL_OFF", "CNIIC_TEST_HUF_SMALL_MAX_PX", kHufSmallMaxPx); }, huf_small_floor_px, nullptr,
+     [](cniic_ctx *c, const CodecDesc &, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return huf_small_encode(c, fr, n); }},
+};
 
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
     const uint32_t n = (uint32_t)fr.size();
@@ -1390,96 +1388,30 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
         return x < y;
     });
     std::map<std::string, KernelTime> kt;
-    // ---- the small cluster-colors frames, together
+    // ---- the small frames of a codec that has a route for them, together
     CodecDesc d;
-    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_CLUSTER_COLORS && d.arg >= 1 && d.arg <= kCcSmallMaxK && (!opts || opts->flags == 0)) {
-        const uint64_t max_px = cc_small_max_px();
-        std::vector<VarFrame *> small;
-        std::vector<uint32_t> rest;
-        for (uint32_t j = 0; j < n; j++) {
-            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
-            if (px >= 1 && px <= max_px) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
-        }
-        if (!small.empty()) {
-            std::map<std::string, KernelTime> mine;
-            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
-            const int32_t rc = cc_small_encode(c, d.arg, opts, small.data(), (uint32_t)small.size());
-            mine.swap(c->ktimes);
-            CNIIC_TRY(rc);
-            if (c->timers) kt.swap(mine);
-            order.swap(rest);
-        }
-    }
-    // ---- the small voronoi frames, together
-    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_VORONOI && d.arg >= 1 && d.arg <= kVorSmallMaxK && (!opts || opts->flags == 0)) {
-        const uint64_t max_px = vor_small_max_px();
-        std::vector<VarFrame *> small;
-        std::vector<uint32_t> rest;
+    const bool routable = src_dev && parse_codec(expr, &d);
+    for (const SmallRoute &r : kSmallRoutes) {
+        if (!routable || !r.applies(c, d, opts)) continue;
+        const uint64_t max_px = r.max_px();
+        auto candidate = [&](const VarFrame &f) { const uint64_t px = (uint64_t)f.w * f.h; return px >= 1 && px <= max_px; };
         uint64_t candidates = 0;
-        for (uint32_t j = 0; j < n; j++) {
-            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
-            candidates += px >= 1 && px <= max_px;
-        }
-        const uint64_t max_work = vor_small_max_work(candidates);   // (the floor: few frames, large pixels x K -- the workers are faster)
-        for (uint32_t j = 0; j < n; j++) {
-            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
-            if (px >= 1 && px <= max_px && px * d.arg <= max_work) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
-        }
-        if (!small.empty()) {
-            std::map<std::string, KernelTime> mine;
-            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
-            const int32_t rc = vor_small_encode(c, d.arg, opts, small.data(), (uint32_t)small.size());
-            mine.swap(c->ktimes);
-            CNIIC_TRY(rc);
-            if (c->timers) kt.swap(mine);
-            order.swap(rest);
-        }
-    }
-    // ---- the small `delta` frames, together: not with the big encoder's route forced, and not a frame whose size has an injected scan
-    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_DELTA && c->opt(CNIIC_OPT_DELTA_ROUTE, "CNIIC_DELTA_ROUTE", 0) != 32) {
-        const uint64_t max_px = delta_small_max_px();
+        for (uint32_t j : order) candidates += candidate(fr[j]);
+        const uint64_t floor_px = r.floor ? r.floor(candidates, d.arg) : ~0ull;   // (the floor: few heavy frames -- the workers are faster)
         std::vector<VarFrame *> small;
         std::vector<uint32_t> rest;
-        for (uint32_t j = 0; j < n; j++) {
-            const VarFrame &f = fr[order[j]];
-            const uint64_t px = (uint64_t)f.w * f.h;
-            const bool own_scan = c->scan_xy.p && c->scan_w == f.w && c->scan_h == f.h;
-            if (px >= 1 && px <= max_px && !own_scan) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
+        for (uint32_t j : order) {
+            VarFrame &f = fr[j];
+            if (candidate(f) && (uint64_t)f.w * f.h <= floor_px && (!r.takes || r.takes(c, f))) small.push_back(&f); else rest.push_back(j);
         }
-        if (!small.empty()) {
-            std::map<std::string, KernelTime> mine;
-            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
-            const int32_t rc = delta_small_encode(c, small.data(), (uint32_t)small.size());
-            mine.swap(c->ktimes);
-            CNIIC_TRY(rc);
-            if (c->timers) kt.swap(mine);
-            order.swap(rest);
-        }
-    }
-    // ---- the small `hufman` frames, together
-    if (src_dev && parse_codec(expr, &d) && d.kind == CODEC_HUFMAN && (!opts || opts->flags == 0)) {
-        const uint64_t max_px = huf_small_max_px();
-        std::vector<VarFrame *> small;
-        std::vector<uint32_t> rest;
-        uint64_t candidates = 0;
-        for (uint32_t j = 0; j < n; j++) {
-            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
-            candidates += px >= 1 && px <= max_px;
-        }
-        const uint64_t floor_px = huf_small_floor_px(candidates);   // (the floor: few frames, many pixels -- the workers are faster)
-        for (uint32_t j = 0; j < n; j++) {
-            const uint64_t px = (uint64_t)fr[order[j]].w * fr[order[j]].h;
-            if (px >= 1 && px <= max_px && px <= floor_px) small.push_back(&fr[order[j]]); else rest.push_back(order[j]);
-        }
-        if (!small.empty()) {
-            std::map<std::string, KernelTime> mine;
-            mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
-            const int32_t rc = huf_small_encode(c, small.data(), (uint32_t)small.size());
-            mine.swap(c->ktimes);
-            CNIIC_TRY(rc);
-            if (c->timers) kt.swap(mine);
-            order.swap(rest);
-        }
+        if (small.empty()) continue;
+        std::map<std::string, KernelTime> mine;
+        mine.swap(c->ktimes);   // (the route's stage times alone, added to the workers' below)
+        const int32_t rc = r.run(c, d, opts, small.data(), (uint32_t)small.size());
+        mine.swap(c->ktimes);
+        CNIIC_TRY(rc);
+        if (c->timers) for (const auto &e : mine) { kt[e.first].ms += e.second.ms; kt[e.first].launches += e.second.launches; }
+        order.swap(rest);
     }
     const uint32_t nw = (uint32_t)order.size();
     if (!nw) {

@@ -1070,7 +1070,101 @@ int palette_encode_frames_var(Palette *p, const uint8_t *rgb_d, const uint32_t *
     return frames_tail(c, pixlab.p, p->wide, p->K, p->cent_d.as<uint32_t>(), p->cent_h.data(), fb, out, stride, lens, nullptr, true);
 }
 
-// ---- small cluster-colors frames of a batch call, all at once (codec.hpp; k_cc_small.hip)
+// ---- small frames of a batch call, a workgroup per frame: what the encode routes share (codec.hpp)
+static uint64_t frame_px(const VarFrame &f) { return (uint64_t)f.w * f.h; }
+
+// The frames (largest first) in chunks: a chunk takes as many as frames_that_fit(its first, largest frame) says -- one at least --, and
+// body(the chunk's frames, how many) encodes it.
+template <class Fit, class Body>
+static int for_chunks(VarFrame *const *fr, uint32_t n, Fit frames_that_fit, Body body) {
+    for (uint32_t at = 0; at < n;) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, std::max<uint64_t>(1, frames_that_fit(*fr[at])));
+        CNIIC_TRY(body(fr + at, cnt));
+        at += cnt;
+    }
+    return CNIIC_OK;
+}
+
+// The decode routes' chunks, whose items cost what they cost each: the end i1 of the chunk that starts at item i0 of n and takes items
+// while their cost(i) together stay within budget; the first always fits.
+template <class Cost>
+static size_t take_chunk(size_t i0, size_t n, uint64_t budget, Cost cost) {
+    size_t i1 = i0;
+    uint64_t need = 0;
+    while (i1 < n && (i1 == i0 || need + cost(i1) <= budget)) need += cost(i1++);
+    return i1;
+}
+
+// A chunk's rows go up, launch(rows, result rows) runs under the stage timer `timer` (launches = the rows), the result rows come down: one wait
+template <class Row, class Result, class Launch>
+static int run_rows(Ctx *c, const char *timer, const std::vector<Row> &rows, std::vector<Result> &res, Launch launch) {
+    const size_t n = rows.size();
+    DevBuf rows_d, res_d;
+    CNIIC_HIP_TRY(c, rows_d.alloc(n * sizeof(Row)));
+    CNIIC_HIP_TRY(c, res_d.alloc(n * sizeof(Result)));
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), n * sizeof(Row), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedKernelTimer t(c, timer);
+        CNIIC_TRY(launch(rows_d.as<Row>(), res_d.as<Result>()));
+        t.stop(n);
+    }
+    res.resize(n);
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, n * sizeof(Result), hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+// A frame's K-means outcome as the single call reports it: too few points (`what` they are called there), else the stats and the check
+// of the active clusters.  Returns whether the frame goes on.
+static bool report_kmeans_outcome(Ctx *c, uint32_t K, VarFrame &f, uint32_t status, uint64_t points, uint64_t iterations, uint64_t moved_last, uint64_t reseeds,
+                                  uint64_t active, uint64_t pair_evals, const char *what) {
+    if (status) {
+        f.rc = c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu %s for %u clusters (src/kmeans.rs:68)", (unsigned long long)points, what, K);
+        f.msg = c->err;
+        return false;
+    }
+    f.st.iterations = iterations; f.st.moved_last = moved_last; f.st.empty_reseeds = reseeds; f.st.active = active;
+    f.st.pair_evals = pair_evals;
+    f.rc = check_enough_active(c, K, points, active);
+    if (f.rc != CNIIC_OK) f.msg = c->err;
+    return f.rc == CNIIC_OK;
+}
+
+// Every finished stream of a chunk to its frame's own place, unless it is longer than the caller's room.  The streams lie in `scratch`, a
+// slot of sstride bytes each, `slots` of them; a SmallStream says which slot holds whose stream and how long it is.  Device destinations:
+// one launch of cc_small_place under the stage timer t_place; host destinations: the whole scratch comes down once.
+struct SmallStream { uint32_t slot; VarFrame *f; uint64_t len; };
+static int place_streams(Ctx *c, const DevBuf &scratch, uint64_t sstride, uint32_t slots, const std::vector<SmallStream> &streams, const char *t_place) {
+    std::vector<CcSmallPlace> pl;
+    for (const SmallStream &s : streams) {
+        VarFrame &f = *s.f;
+        f.len = s.len;
+        if (f.len > f.cap) {
+            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
+            f.msg = c->err;
+            continue;
+        }
+        pl.push_back(CcSmallPlace{sstride * s.slot, f.out, f.len});
+    }
+    if (pl.empty()) return CNIIC_OK;
+    if (is_device_ptr(pl[0].dst)) {   // (all destinations host or all device memory)
+        DevBuf pl_d;
+        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
+        ScopedKernelTimer t(c, t_place);
+        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
+        t.stop(1);
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        std::vector<uint8_t> host(sstride * slots);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
+    }
+    return CNIIC_OK;
+}
+
+// ---- small cluster-colors frames of a batch call, all at once (k_cc_small.hip)
 // The stride of the tail's scratch is one no stream of a frame of npx pixels can exceed: the header is at most 8 + 13 K bytes (the tail's
 // own hstride), the payload fewer than (log2 256 + 1) npx = 9 npx bits (Huffman's redundancy bound over at most 256 symbols).
 static uint64_t cc_small_stream_bound(uint64_t npx, uint32_t K) { return (8ull + 13ull * K + (9 * npx + 7) / 8 + 15) & ~15ull; }
@@ -1083,36 +1177,19 @@ static int cc_small_chunk(Ctx *c, uint32_t K, uint64_t seed, uint64_t max_iters,
         rows[i] = CcSmallRow{fr[i]->src, lab_total, fr[i]->w, fr[i]->h};
         lab_total += ((uint64_t)fr[i]->w * fr[i]->h + 15) & ~15ull;
     }
-    DevBuf rows_d, labels_d, cent_d, res_d;
-    CNIIC_HIP_TRY(c, rows_d.alloc((uint64_t)n * sizeof(CcSmallRow)));
+    DevBuf labels_d, cent_d;
     CNIIC_HIP_TRY(c, labels_d.alloc(lab_total + 16));
     CNIIC_HIP_TRY(c, cent_d.alloc((uint64_t)n * K * 4));
-    CNIIC_HIP_TRY(c, res_d.alloc((uint64_t)n * sizeof(CcSmallResult)));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(CcSmallRow), hipMemcpyHostToDevice, c->stream));
-    {
-        ScopedKernelTimer t(c, "cc_small_batch");
-        CNIIC_TRY(cc_small_run(c, rows_d.as<CcSmallRow>(), n, fr[0]->w * fr[0]->h, K, seed, max_iters, labels_d.as<uint8_t>(), cent_d.as<uint32_t>(),
-                               res_d.as<CcSmallResult>()));
-        t.stop(n);
-    }
-    std::vector<CcSmallResult> res(n);
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, (size_t)n * sizeof(CcSmallResult), hipMemcpyDeviceToHost, c->stream));
-    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<CcSmallResult> res;
+    CNIIC_TRY(run_rows(c, "cc_small_batch", rows, res, [&](const CcSmallRow *rows_d, CcSmallResult *res_d) {
+        return cc_small_run(c, rows_d, n, fr[0]->w * fr[0]->h, K, seed, max_iters, labels_d.as<uint8_t>(), cent_d.as<uint32_t>(), res_d);   // (largest first)
+    }));
     // ---- every frame's K-means outcome, as the single call reports it; the frames that go on
     std::vector<uint32_t> ok;
     for (uint32_t i = 0; i < n; i++) {
-        VarFrame &f = *fr[i];
         const CcSmallResult &r = res[i];
-        if (r.status) {
-            f.rc = c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu distinct colours for %u clusters (src/kmeans.rs:68)", (unsigned long long)r.U, K);
-            f.msg = c->err;
-            continue;
-        }
-        f.st.iterations = r.iterations; f.st.moved_last = r.moved_last; f.st.empty_reseeds = r.reseeds; f.st.active = r.active;
-        f.st.pair_evals = (uint64_t)r.iterations * r.U * K;
-        f.rc = check_enough_active(c, K, r.U, r.active);
-        if (f.rc != CNIIC_OK) { f.msg = c->err; continue; }
-        ok.push_back(i);
+        if (report_kmeans_outcome(c, K, *fr[i], r.status, r.U, r.iterations, r.moved_last, r.reseeds, r.active, (uint64_t)r.iterations * r.U * K, "distinct colours"))
+            ok.push_back(i);
     }
     const uint32_t F = (uint32_t)ok.size();
     if (!F) return CNIIC_OK;
@@ -1160,47 +1237,16 @@ static int cc_small_chunk(Ctx *c, uint32_t K, uint64_t seed, uint64_t max_iters,
     CNIIC_HIP_TRY(c, scratch.alloc(sstride * F + 16));
     std::vector<uint64_t> lens(F);
     CNIIC_TRY(frames_tail(c, labels_d.p, false, K, cent_tail, cent_h.data(), fb, scratch.as<uint8_t>(), sstride, lens.data(), nullptr, false, K));
-    // ---- every stream to its own place, unless it is longer than the caller's room
-    const bool out_dev = is_device_ptr(fr[ok[0]]->out);
-    std::vector<CcSmallPlace> pl;
-    for (uint32_t j = 0; j < F; j++) {
-        VarFrame &f = *fr[ok[j]];
-        f.len = lens[j];
-        if (f.len > f.cap) {
-            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
-            f.msg = c->err;
-            continue;
-        }
-        pl.push_back(CcSmallPlace{sstride * j, f.out, f.len});
-    }
-    if (pl.empty()) return CNIIC_OK;
-    if (out_dev) {
-        DevBuf pl_d;
-        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
-        ScopedKernelTimer t(c, "cc_small_place");
-        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
-        t.stop(1);
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-        std::vector<uint8_t> host(sstride * F);
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
-    }
-    return CNIIC_OK;
+    std::vector<SmallStream> streams(F);
+    for (uint32_t j = 0; j < F; j++) streams[j] = SmallStream{j, fr[ok[j]], lens[j]};
+    return place_streams(c, scratch, sstride, F, streams, "cc_small_place");
 }
 
 int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n) {
     const uint64_t seed = (opts && opts->seed) ? opts->seed : kDefaultSeed, max_iters = opts ? opts->max_iters : 0;
-    // the tail's scratch stays below 2 GiB: the frames in chunks, each under the stride of its first (largest) frame
-    for (uint32_t at = 0; at < n;) {
-        const uint64_t room = (2ull << 30) / cc_small_stream_bound((uint64_t)fr[at]->w * fr[at]->h, K);
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
-        CNIIC_TRY(cc_small_chunk(c, K, seed, max_iters, fr + at, cnt));
-        at += cnt;
-    }
-    return CNIIC_OK;
+    // the tail's scratch stays below 2 GiB
+    return for_chunks(fr, n, [&](const VarFrame &first) { return (2ull << 30) / cc_small_stream_bound(frame_px(first), K); },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return cc_small_chunk(c, K, seed, max_iters, chunk, cnt); });
 }
 
 // ---- small `delta` frames of a batch call, all at once (codec.hpp; k_delta_small.hip)
@@ -1219,169 +1265,78 @@ static const SmallHuffKind kSmallDelta = {"delta_small", "delta_small_batch", "d
 static const SmallHuffKind kSmallHuf = {"huf_small", "huf_small_batch", "huf_small_place", hs_stride, huf_small_run, 20};
 
 static int delta_small_chunk(Ctx *c, const SmallHuffKind &kind, VarFrame *const *fr, uint32_t n) {
-    const uint64_t max_px = (uint64_t)fr[0]->w * fr[0]->h;   // (largest first)
+    const uint64_t max_px = frame_px(*fr[0]);   // (largest first)
     const uint64_t sstride = kind.stride(max_px), tmp_px = delta_small_tmp_px(max_px);
     std::vector<DeltaSmallRow> rows(n);
     for (uint32_t i = 0; i < n; i++) rows[i] = DeltaSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
-    DevBuf rows_d, res_d, scratch, tmp;
-    CNIIC_HIP_TRY(c, rows_d.alloc((uint64_t)n * sizeof(DeltaSmallRow)));
-    CNIIC_HIP_TRY(c, res_d.alloc((uint64_t)n * sizeof(DeltaSmallResult)));
+    DevBuf scratch, tmp;
     CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
     CNIIC_HIP_TRY(c, tmp.alloc(12 * tmp_px * n));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(DeltaSmallRow), hipMemcpyHostToDevice, c->stream));
-    {
-        ScopedKernelTimer t(c, kind.t_batch);
-        CNIIC_TRY(kind.run(c, rows_d.as<DeltaSmallRow>(), n, (uint32_t)max_px, scratch.as<uint8_t>(), sstride, tmp.as<uint32_t>(), tmp_px, res_d.as<DeltaSmallResult>()));
-        t.stop(n);
-    }
-    std::vector<DeltaSmallResult> res(n);
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, (size_t)n * sizeof(DeltaSmallResult), hipMemcpyDeviceToHost, c->stream));
-    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // ---- every stream to its own place, unless it is longer than the caller's room
-    const bool out_dev = is_device_ptr(fr[0]->out);
-    std::vector<CcSmallPlace> pl;
+    std::vector<DeltaSmallResult> res;
+    CNIIC_TRY(run_rows(c, kind.t_batch, rows, res, [&](const DeltaSmallRow *rows_d, DeltaSmallResult *res_d) {
+        return kind.run(c, rows_d, n, (uint32_t)max_px, scratch.as<uint8_t>(), sstride, tmp.as<uint32_t>(), tmp_px, res_d);
+    }));
+    std::vector<SmallStream> streams(n);
     for (uint32_t i = 0; i < n; i++) {
-        VarFrame &f = *fr[i];
-        f.len = res[i].len;
-        if (f.len < kind.min_len || f.len > sstride) return c->fail(CNIIC_ERR_HIP, "%s: a stream of %llu bytes in a slot of %llu", kind.name, (unsigned long long)f.len, (unsigned long long)sstride);
-        if (f.len > f.cap) {
-            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
-            f.msg = c->err;
-            continue;
-        }
-        pl.push_back(CcSmallPlace{sstride * i, f.out, f.len});
+        const uint64_t len = res[i].len;
+        if (len < kind.min_len || len > sstride) return c->fail(CNIIC_ERR_HIP, "%s: a stream of %llu bytes in a slot of %llu", kind.name, (unsigned long long)len, (unsigned long long)sstride);
+        streams[i] = SmallStream{i, fr[i], len};
     }
-    if (pl.empty()) return CNIIC_OK;
-    if (out_dev) {
-        DevBuf pl_d;
-        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
-        ScopedKernelTimer t(c, kind.t_place);
-        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
-        t.stop(1);
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-        std::vector<uint8_t> host(sstride * n);
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
-    }
-    return CNIIC_OK;
+    return place_streams(c, scratch, sstride, n, streams, kind.t_place);
 }
 
 int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
-    // the scratch stays below 2 GiB: the frames in chunks, each under the slot of its first (largest) frame
-    for (uint32_t at = 0; at < n;) {
-        const uint64_t room = (2ull << 30) / delta_small_frame_bytes((uint64_t)fr[at]->w * fr[at]->h);
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
-        CNIIC_TRY(delta_small_chunk(c, kSmallDelta, fr + at, cnt));
-        at += cnt;
-    }
-    return CNIIC_OK;
+    // the scratch stays below 2 GiB
+    return for_chunks(fr, n, [](const VarFrame &first) { return (2ull << 30) / delta_small_frame_bytes(frame_px(first)); },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return delta_small_chunk(c, kSmallDelta, chunk, cnt); });
 }
 
-// ---- small `hufman` frames of a batch call, all at once (codec.hpp; k_huf_small in k_delta_small.hip): the chunk above under the other kind.
+// ---- small `hufman` frames of a batch call, all at once (k_huf_small in k_delta_small.hip): the chunk above under the other kind.
 // A frame of the chunk whose largest frame has npx pixels takes its slot (hs_stride), the kernel's three words per pixel, its row and its
 // result row; the chunks stay below 2 GiB (the testing library: below CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least).
 constexpr uint64_t kHufSmallScratch = 2ull << 30;
-static uint64_t huf_small_budget() {
-    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kHufSmallScratch);
-    return kHufSmallScratch;
-}
 static uint64_t huf_small_frame_bytes(uint64_t npx) { return hs_stride(npx) + 12 * delta_small_tmp_px(npx) + sizeof(DeltaSmallRow) + sizeof(DeltaSmallResult); }
 
 int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
-    const uint64_t budget = huf_small_budget();
-    for (uint32_t at = 0; at < n;) {
-        const uint64_t room = std::max<uint64_t>(1, budget / huf_small_frame_bytes((uint64_t)fr[at]->w * fr[at]->h));
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
-        CNIIC_TRY(delta_small_chunk(c, kSmallHuf, fr + at, cnt));
-        at += cnt;
-    }
-    return CNIIC_OK;
+    const uint64_t budget = test_budget(kHufSmallScratch);
+    return for_chunks(fr, n, [&](const VarFrame &first) { return budget / huf_small_frame_bytes(frame_px(first)); },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return delta_small_chunk(c, kSmallHuf, chunk, cnt); });
 }
 
-// ---- small voronoi(K) frames of a batch call, all at once (codec.hpp; k_vor_small.hip)
+// ---- small voronoi(K) frames of a batch call, all at once (k_vor_small.hip)
 // A chunk's scratch is a slot per frame for the stream (16 + 19 K bytes, rounded up to 16), its row and its result row; the chunks stay
 // below 2 GiB (the testing library: below CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least).
 constexpr uint64_t kVorSmallScratch = 2ull << 30;
-static uint64_t vor_small_budget() {
-    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kVorSmallScratch);
-    return kVorSmallScratch;
-}
 static uint64_t vor_small_slot(uint32_t K) { return ((uint64_t)vs_stream_len(K) + 15) & ~15ull; }
 
 static int vor_small_chunk(Ctx *c, uint32_t K, uint64_t seed, uint64_t max_iters, bool stay_test, VarFrame *const *fr, uint32_t n) {
-    const uint64_t sstride = vor_small_slot(K), len = vs_stream_len(K);
+    const uint64_t sstride = vor_small_slot(K);
     std::vector<VorSmallRow> rows(n);
     for (uint32_t i = 0; i < n; i++) rows[i] = VorSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
-    DevBuf rows_d, res_d, scratch;
-    CNIIC_HIP_TRY(c, rows_d.alloc((uint64_t)n * sizeof(VorSmallRow)));
-    CNIIC_HIP_TRY(c, res_d.alloc((uint64_t)n * sizeof(VorSmallResult)));
+    DevBuf scratch;
     CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), (size_t)n * sizeof(VorSmallRow), hipMemcpyHostToDevice, c->stream));
-    {
-        ScopedKernelTimer t(c, "vor_small_batch");
-        CNIIC_TRY(vor_small_run(c, rows_d.as<VorSmallRow>(), n, fr[0]->w * fr[0]->h, K, seed, max_iters, stay_test, scratch.as<uint8_t>(), sstride,
-                                res_d.as<VorSmallResult>()));   // (largest first)
-        t.stop(n);
-    }
-    std::vector<VorSmallResult> res(n);
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, (size_t)n * sizeof(VorSmallResult), hipMemcpyDeviceToHost, c->stream));
-    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // ---- every frame's outcome, as the single call reports it; every good stream to its own place
-    const bool out_dev = is_device_ptr(fr[0]->out);
-    std::vector<CcSmallPlace> pl;
+    std::vector<VorSmallResult> res;
+    CNIIC_TRY(run_rows(c, "vor_small_batch", rows, res, [&](const VorSmallRow *rows_d, VorSmallResult *res_d) {
+        return vor_small_run(c, rows_d, n, fr[0]->w * fr[0]->h, K, seed, max_iters, stay_test, scratch.as<uint8_t>(), sstride, res_d);   // (largest first)
+    }));
+    // ---- every frame's K-means outcome, as the single call reports it; the frames whose streams stand
+    std::vector<SmallStream> streams;
     for (uint32_t i = 0; i < n; i++) {
-        VarFrame &f = *fr[i];
         const VorSmallResult &r = res[i];
-        if (r.status > 1 || r.n != (uint64_t)f.w * f.h) return c->fail(CNIIC_ERR_HIP, "vor_small: frame %u of the chunk reported no result", i);
-        if (r.status) {
-            f.rc = c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu points for %u clusters (src/kmeans.rs:68)", (unsigned long long)r.n, K);
-            f.msg = c->err;
-            continue;
-        }
-        f.st.iterations = r.iterations; f.st.moved_last = r.moved_last; f.st.empty_reseeds = r.reseeds; f.st.active = r.active;
-        f.st.pair_evals = r.evals;
-        f.rc = check_enough_active(c, K, r.n, r.active);
-        if (f.rc != CNIIC_OK) { f.msg = c->err; continue; }
-        f.len = len;
-        if (f.len > f.cap) {
-            f.rc = c->fail(CNIIC_ERR_CAPACITY, "encode: stream is %llu bytes, capacity %llu", (unsigned long long)f.len, (unsigned long long)f.cap);
-            f.msg = c->err;
-            continue;
-        }
-        pl.push_back(CcSmallPlace{sstride * i, f.out, f.len});
+        if (r.status > 1 || r.n != frame_px(*fr[i])) return c->fail(CNIIC_ERR_HIP, "vor_small: frame %u of the chunk reported no result", i);
+        if (report_kmeans_outcome(c, K, *fr[i], r.status, r.n, r.iterations, r.moved_last, r.reseeds, r.active, r.evals, "points"))
+            streams.push_back(SmallStream{i, fr[i], vs_stream_len(K)});
     }
-    if (pl.empty()) return CNIIC_OK;
-    if (out_dev) {
-        DevBuf pl_d;
-        CNIIC_HIP_TRY(c, pl_d.alloc(pl.size() * sizeof(CcSmallPlace)));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(pl_d.p, pl.data(), pl.size() * sizeof(CcSmallPlace), hipMemcpyHostToDevice, c->stream));
-        ScopedKernelTimer t(c, "vor_small_place");
-        CNIIC_TRY(cc_small_place(c, pl_d.as<CcSmallPlace>(), (uint32_t)pl.size(), scratch.as<uint8_t>()));
-        t.stop(1);
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else {
-        std::vector<uint8_t> host(sstride * n);
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(host.data(), scratch.p, host.size(), hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (const CcSmallPlace &p : pl) memcpy(p.dst, host.data() + p.src_off, p.len);
-    }
-    return CNIIC_OK;
+    return place_streams(c, scratch, sstride, n, streams, "vor_small_place");
 }
 
 int vor_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n) {
     const uint64_t seed = (opts && opts->seed) ? opts->seed : kDefaultSeed, max_iters = opts ? opts->max_iters : 0;
     bool stay_test = true;
     if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_NO_STAY")) stay_test = atoi(e) == 0;
-    const uint64_t room = std::max<uint64_t>(1, vor_small_budget() / (vor_small_slot(K) + sizeof(VorSmallRow) + sizeof(VorSmallResult)));
-    for (uint32_t at = 0; at < n;) {
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, room);
-        CNIIC_TRY(vor_small_chunk(c, K, seed, max_iters, stay_test, fr + at, cnt));
-        at += cnt;
-    }
-    return CNIIC_OK;
+    const uint64_t room = test_budget(kVorSmallScratch) / (vor_small_slot(K) + sizeof(VorSmallRow) + sizeof(VorSmallResult));   // (whatever the frames' sizes)
+    return for_chunks(fr, n, [&](const VarFrame &) { return room; },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return vor_small_chunk(c, K, seed, max_iters, stay_test, chunk, cnt); });
 }
 
 // How well the handle's palette fits a batch of frames: sse_h[f] = the exact sum over frame f's pixels of the squared distance to the pixel's entry
@@ -1939,9 +1894,7 @@ static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, 
         return (lens[f] - 8) / 12 * 4 + 2 * ((n * 3 + 15) & ~15ull) + (bytes_dev ? 0 : lens[f]);
     };
     for (size_t i0 = 0; i0 < route.size();) {
-        size_t i1 = i0;
-        uint64_t need = 0;
-        while (i1 < route.size() && i1 - i0 < kBatchRouteFrames && (i1 == i0 || need + scratch_of(route[i1]) <= kRleSetScratch)) need += scratch_of(route[i1++]);
+        const size_t i1 = take_chunk(i0, std::min(route.size(), i0 + kBatchRouteFrames), kRleSetScratch, [&](size_t i) { return scratch_of(route[i]); });
         const size_t S = i1 - i0;
         // ---- the streams in HBM (a host batch: from the set's first frame to its last, in one copy), the colours and staged images
         DevBuf up_d, lin_d, img_d;
@@ -2005,26 +1958,14 @@ static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, 
 // The testing library can switch the route off (CNIIC_TEST_DELTA_SMALL_DEC_OFF=1), lower its bound (CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX) and its
 // settle rounds (CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS), and make the chunks small (CNIIC_TEST_MEASURE_BUDGET, bytes).
 constexpr uint64_t kDeltaSmallDecScratch = 2ull << 30;
-static uint64_t delta_small_dec_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_OFF")) if (atoi(e) != 0) return 0;
-    if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecMaxPx);
-    return kDeltaSmallDecMaxPx;
-}
+static uint64_t delta_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_DELTA_SMALL_DEC_OFF", "CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX", kDeltaSmallDecMaxPx); }
 // A decoder that k_small_trieparse has left in HBM (delta_small_parse_dev below): its codes, then as many key | length words
 struct DeltaSmallDevTab { const uint32_t *code; uint32_t leaves, max_len; };
-static uint64_t delta_small_dec_budget() {
-    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kDeltaSmallDecScratch);
-    return kDeltaSmallDecScratch;
-}
 // Small `hufman` and `cluster-colors` frames take the same route under the other symbol kind (k_huf_small_dec: RGB keys, no FromDiff, no
 // scan): frames of 1 .. kHufSmallMaxPx pixels whose decoder the host has parsed and has no code longer than kDeltaSmallMaxCodeLen; larger
 // frames, longer codes and everything unparsed keep huff_decode_batch_dev.  Stage timer "huf_small_dec_batch"; the testing library can
 // switch it off (CNIIC_TEST_HUF_SMALL_DEC_OFF=1) and lower its bound (CNIIC_TEST_HUF_SMALL_DEC_MAX_PX); the rounds' knob above caps both.
-static uint64_t huf_small_dec_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_DEC_OFF")) if (atoi(e) != 0) return 0;
-    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_DEC_MAX_PX")) return std::min<uint64_t>(strtoull(e, nullptr, 10), kHufSmallMaxPx);
-    return kHufSmallMaxPx;
-}
+static uint64_t huf_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_HUF_SMALL_DEC_OFF", "CNIIC_TEST_HUF_SMALL_DEC_MAX_PX", kHufSmallMaxPx); }
 // The floor of that route.  Most of the call is the host's parse of the decoders either way; what the kernel adds for few frames is its settle
 // rounds (0.35 ms for one 32 x 32 frame, whatever the number of frames up to the CUs) against launches that the batched route shares among
 // its frames.  Measured against the parent commit's library (tools/small_hufman_probe.py, profiles/small_hufman_probe.json; NOTES AF), whole
@@ -2054,14 +1995,12 @@ static int delta_small_decode(Ctx *c, const SmallDecKind &kind, const uint8_t *b
                               std::vector<std::string> &msgs) {
     uint32_t max_rounds = kDsdMaxRounds;
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS")) max_rounds = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kDsdMaxRounds);
-    const uint64_t budget = delta_small_dec_budget();
+    const uint64_t budget = test_budget(kDeltaSmallDecScratch);
     auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
     auto tab_words = [&](uint32_t f) -> uint64_t { return dev ? 0 : tabs[f].size(); };
     auto scratch_of = [&](uint32_t f) { return tab_words(f) * 4 + sizeof(DeltaSmallDecRow) + 4 + (dst_dev ? 0 : img_room(f)); };
     for (size_t i0 = 0; i0 < route.size();) {
-        size_t i1 = i0;
-        uint64_t need = 0;
-        while (i1 < route.size() && (i1 == i0 || need + scratch_of(route[i1]) <= budget)) need += scratch_of(route[i1++]);
+        const size_t i1 = take_chunk(i0, route.size(), budget, [&](size_t i) { return scratch_of(route[i]); });
         const size_t S = i1 - i0;
         // ---- the streams in HBM (a host batch: from the chunk's first frame to its last, in one copy)
         DevBuf up_d, tab_d, img_d;
@@ -2161,7 +2100,7 @@ static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, 
     for (uint32_t f = 0; f < F; f++) if (!off_route[f] && lens[f] >= 8 && view(f) >= 8) cands.push_back(f);
     if (c->timers) { (void)c->ktimes["delta_small_dec_parse"]; (void)c->ktimes["delta_small_dec_parse_host"]; }
     if (cands.empty()) return CNIIC_OK;
-    const uint64_t budget = delta_small_dec_budget();
+    const uint64_t budget = test_budget(kDeltaSmallDecScratch);
     auto scratch_of = [&](uint32_t f) { return (uint64_t)st_leaves_room<6>(view(f)) * 8 + sizeof(SmallTrieRow) + sizeof(SmallTrieResult); };
     const bool scan = c->scan_xy.p != nullptr;
     std::vector<DeltaSmallDevTab> dev(F);
@@ -2169,9 +2108,8 @@ static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, 
     const std::vector<std::vector<uint32_t>> no_tabs;
     uint64_t parsed = 0;
     for (size_t i0 = 0; i0 < cands.size();) {
-        size_t i1 = i0;
-        uint64_t need = 0, longest = 0;
-        while (i1 < cands.size() && (i1 == i0 || need + scratch_of(cands[i1]) <= budget)) need += scratch_of(cands[i1++]);
+        const size_t i1 = take_chunk(i0, cands.size(), budget, [&](size_t i) { return scratch_of(cands[i]); });
+        uint64_t longest = 0;
         const size_t S = i1 - i0;
         // ---- one block: the rows, the result rows, every frame's table
         const uint64_t res_at = (S * sizeof(SmallTrieRow) + 15) & ~15ull, tab_at = (res_at + S * sizeof(SmallTrieResult) + 15) & ~15ull;
@@ -2230,20 +2168,15 @@ static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, 
 // chunks whose scratch -- the centroids, the rows, and for a host destination the staged images -- stays below the budget: per chunk one
 // copy up, ONE launch with a workgroup per slice of kVorSmallDecSlice pixels of a frame, for a host destination one copy down (a memcpy per frame then puts the images in place),
 // one wait.  Every routed frame decodes: there is no status to fetch.
-static uint64_t vor_small_dec_max_px() {
-    if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_DEC_OFF")) if (atoi(e) != 0) return 0;
-    return kVorSmallMaxPx;
-}
+static uint64_t vor_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_VOR_SMALL_DEC_OFF", nullptr, kVorSmallMaxPx); }
 static int vor_small_decode(Ctx *c, uint8_t *rgb, bool dst_dev, uint64_t img_stride, const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route,
                             const std::vector<uint32_t> &table, const std::vector<uint64_t> &cent, const std::vector<uint32_t> &Ks, std::vector<uint8_t> &taken) {
-    const uint64_t budget = vor_small_budget();
+    const uint64_t budget = test_budget(kVorSmallScratch);
     auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
     auto slices_of = [&](uint32_t f) { return (w[f] * h[f] + kVorSmallDecSlice - 1) / kVorSmallDecSlice; };   // (a workgroup's share of a frame: k_vor_small.hip)
     auto scratch_of = [&](uint32_t f) { return (uint64_t)Ks[f] * 12 + slices_of(f) * sizeof(VorSmallDecRow) + (dst_dev ? 0 : img_room(f)); };
     for (size_t i0 = 0; i0 < route.size();) {
-        size_t i1 = i0;
-        uint64_t need = 0;
-        while (i1 < route.size() && (i1 == i0 || need + scratch_of(route[i1]) <= budget)) need += scratch_of(route[i1++]);
+        const size_t i1 = take_chunk(i0, route.size(), budget, [&](size_t i) { return scratch_of(route[i]); });
         const size_t S = i1 - i0;
         uint64_t cents = 0, img_bytes = 0, slices = 0;
         for (size_t i = 0; i < S; i++) { cents += Ks[route[i0 + i]]; slices += slices_of(route[i0 + i]); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }

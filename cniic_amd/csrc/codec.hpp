@@ -44,25 +44,23 @@ struct VarFrame {
     cniic_kmeans_stats st{};
     std::string msg;
 };
-// cluster-colors(K), 1 <= K <= 256, of n > 0 small frames (1 .. kCcSmallMaxPx pixels each, DEVICE images, largest first; all destinations
-// host or all device memory) in one set of launches whatever n: k_cc_small, one workgroup per frame with a palette of its own, then
-// frames_tail with a palette per frame into scratch, then every stream to its own destination.  Fills in rc, len, st and msg of every
-// frame as cniic_codec_encode_opts would for that frame alone; what it returns is the status of the machinery, not of a frame.
+// ---- the small-frame encode routes (codec.cpp; capi.cpp kSmallRoutes picks the frames)
+// Each codes n > 0 small frames (DEVICE images of 1 .. the route's bound pixels, largest first; all destinations host or all device memory)
+// together, one workgroup per frame.  The frames go in chunks whose scratch stays below 2 GiB (for_chunks); a chunk is one upload of its
+// rows, ONE launch of the route's kernel under the stage timer "<route>_batch" (launches = the chunk's frames), one copy down of its
+// result rows (run_rows), then every stream from its slot of the scratch to its own destination unless it is longer than the frame's cap
+// (place_streams: k_cc_small_place under "<route>_place" for device destinations, one copy down of the scratch for host destinations).
+// Every frame's rc, len, st and msg are filled in as cniic_codec_encode_opts would for that frame alone; what a route returns is the
+// status of the machinery, not of a frame.  The testing library can switch a route off (CNIIC_TEST_<ROUTE>_OFF=1) and lower its pixel
+// bound (CNIIC_TEST_<ROUTE>_MAX_PX).  What differs:
+//   cc_small     cluster-colors(K <= 256), kCcSmallMaxPx: k_cc_small runs the K-means with a palette per frame, frames_tail codes the frames that go on into the scratch
+//   delta_small  `delta`, kDeltaSmallMaxPx: k_delta_small, from the pixels to the finished stream; st stays zero, as in the single call
+//   huf_small    `hufman`, kHufSmallMaxPx: k_huf_small, the same kernel body over the pixels' own colours (huf_small.hpp); st stays zero; chunks: CNIIC_TEST_MEASURE_BUDGET
+//   vor_small    voronoi(K <= 256), kVorSmallMaxPx: k_vor_small, from the pixels through the whole K-means to the finished stream (st.pair_evals: what
+//                this route evaluated); chunks: CNIIC_TEST_MEASURE_BUDGET; without the stay test: CNIIC_TEST_VOR_SMALL_NO_STAY=1
 int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
-// `delta` of n > 0 small frames (1 .. kDeltaSmallMaxPx pixels each, DEVICE images, largest first; all destinations host or all device
-// memory) in one launch per 2 GiB of scratch: k_delta_small, one workgroup per frame from the pixels to the finished stream, then every
-// stream to its own destination.  Fills in rc, len and msg of every frame as cniic_codec_encode_opts would for that frame alone (st stays
-// zero, as there); what it returns is the status of the machinery, not of a frame.
 int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
-// `hufman` of n > 0 small frames (1 .. kHufSmallMaxPx pixels each, DEVICE images, largest first; all destinations host or all device
-// memory) likewise: k_huf_small, the same kernel body over the pixels' own colours (huf_small.hpp), a workgroup per frame in one launch per
-// chunk of scratch, then every stream to its own destination.  Fills in rc, len and msg of every frame as cniic_codec_encode_opts would for
-// that frame alone (st stays zero, as there).
 int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
-// voronoi(K), 1 <= K <= 256, of n > 0 small frames (1 .. kVorSmallMaxPx pixels each, DEVICE images, largest first; all destinations host or
-// all device memory) in one launch per chunk of scratch: k_vor_small, one workgroup per frame from the pixels to the finished stream, then
-// every stream to its own destination.  Fills in rc, len, st and msg of every frame as cniic_codec_encode_opts would for that frame alone
-// (st.pair_evals: what this route evaluated); what it returns is the status of the machinery, not of a frame.
 int vor_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
 
 // ---- output assembly

@@ -175,6 +175,20 @@ inline const char *test_env(const char *name) { return getenv(name); }
 #else
 inline const char *test_env(const char *) { return nullptr; }
 #endif
+// Two shapes that most knobs of the small-frame routes have.  Both are inline so that the release library folds them to their last
+// argument and keeps none of the names.
+// A scratch budget of `cap` bytes that the tests make small (CNIIC_TEST_MEASURE_BUDGET, bytes; never above cap)
+inline uint64_t test_budget(uint64_t cap) {
+    if (const char *e = test_env("CNIIC_TEST_MEASURE_BUDGET")) return std::min<uint64_t>(strtoull(e, nullptr, 10), cap);
+    return cap;
+}
+// The most pixels of a frame that takes a route whose own bound is `bound`: 0 with off_env=1 (the route is off), max_px_env (may be null:
+// no such knob) lowers it
+inline uint64_t small_route_max_px(const char *off_env, const char *max_px_env, uint64_t bound) {
+    if (const char *e = test_env(off_env)) if (atoi(e) != 0) return 0;
+    if (const char *e = max_px_env ? test_env(max_px_env) : nullptr) return std::min<uint64_t>(strtoull(e, nullptr, 10), bound);
+    return bound;
+}
 
 // Every resource below is owned by its member's type and released by that type's destructor, in reverse order of declaration: the order
 // of the members IS the order of the teardown.  What it must keep: the workers go first (they hold views of scan_xy), every DevBuf that

@@ -253,6 +253,52 @@ def test_capacity_is_one_frame_s(host_out):
             assert rcs[f] == 0 and streams[f] == want[f][1], f
 
 
+def tiny_images():
+    """at most 16 x 16: three frames of at least 16 distinct colours, three of fewer"""
+    from cniic_amd import synth
+    yy, xx = np.mgrid[0:5, 0:6]
+    checker = np.where(((xx + yy) & 1)[..., None] == 1, np.array([200, 30, 40], np.uint8), np.array([10, 220, 90], np.uint8)).astype(np.uint8)
+    rich = [synth.uniform(16, 16, synth.SEED0 + 7400), synth.uniform(12, 9, synth.SEED0 + 7401), synth.uniform(7, 9, synth.SEED0 + 7402)]
+    poor = [np.full((8, 8, 3), 9, np.uint8), checker, synth.photo(3, 1, synth.SEED0 + 7403)]
+    return rich, poor
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_chunk_whose_frames_all_fail_the_kmeans_check(host_out):
+    """no frame goes on to the tail: nothing is placed, no place timer is recorded, no byte is written"""
+    import cniic_amd
+    expr = "cluster-colors(16)"
+    imgs = tiny_images()[1]
+    want = singles("all fail", expr, imgs)
+    assert [s[0] for s in want] == [TOO_FEW_POINTS] * len(imgs)
+    with cniic_amd.Context(0) as ctx:
+        res = batch(ctx, expr, imgs, 64, host_out=host_out, poison=0xA5)
+        assert ctx.kernel_time("cc_small_place")[1] == 0
+    assert res[6] == len(imgs) and res[1] == [0] * len(imgs)
+    check_against_singles(res, want, "all fail")
+    assert bool((res[5] == 0xA5).all())
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_chunk_whose_frames_all_exceed_their_capacity(host_out):
+    """every frame has a stream and none has the room: nothing is placed, no place timer is recorded, no byte is written"""
+    import cniic_amd
+    expr = "cluster-colors(16)"
+    imgs = tiny_images()[0]
+    want = singles("all short", expr, imgs)
+    assert all(s[0] == 0 and len(s[1]) > 8 for s in want)
+    with cniic_amd.Context(0) as ctx:
+        rc, lens, rcs, sts, streams, host, launches, msg = batch(ctx, expr, imgs, 8, host_out=host_out, poison=0xA5)
+        assert ctx.kernel_time("cc_small_place")[1] == 0
+    assert launches == len(imgs) and rc == CAPACITY and rcs == [CAPACITY] * len(imgs)
+    assert lens == [len(s[1]) for s in want]
+    assert msg == "encode: stream is %d bytes, capacity 8" % len(want[0][1])
+    for f, s in enumerate(want):
+        for k in ("iterations", "moved_last", "empty_reseeds", "active"):
+            assert sts[f][k] == s[2][k], (f, k)
+    assert bool((host == 0xA5).all())
+
+
 def test_many_frames_in_one_launch():
     import cniic_amd
     rng = np.random.default_rng(41)

@@ -234,6 +234,23 @@ def test_capacity_is_one_frame_s(host_out):
             assert bool((host[f * stride + lens[f]:(f + 1) * stride] == 0xA5).all()), f     # nothing behind a stream's end
 
 
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_chunk_whose_frames_all_exceed_their_capacity(host_out):
+    """every frame has a stream and none has the room: nothing is placed, no place timer is recorded, no byte is written"""
+    import cniic_amd
+    from cniic_amd import synth
+    imgs = [synth.uniform(16, 16, synth.SEED0 + 7550), synth.photo(12, 9, synth.SEED0 + 7551), synth.uniform(7, 9, synth.SEED0 + 7552), np.full((4, 5, 3), 77, np.uint8)]
+    want = singles("tiny", "delta", imgs)
+    assert all(s[0] == 0 and len(s[1]) > 8 for s in want)
+    with cniic_amd.Context(0) as ctx:
+        rc, lens, rcs, sts, streams, host, launches, msg = batch(ctx, "delta", imgs, 8, host_out=host_out, poison=0xA5)
+        assert ctx.kernel_time("delta_small_place")[1] == 0
+    assert launches == len(imgs) and rc == CAPACITY and rcs == [CAPACITY] * len(imgs)
+    assert lens == [len(s[1]) for s in want]
+    assert msg == "encode: stream is %d bytes, capacity 8" % len(want[0][1])
+    assert bool((host == 0xA5).all())
+
+
 def test_many_frames_in_one_launch():
     import cniic_amd
     rng = np.random.default_rng(43)

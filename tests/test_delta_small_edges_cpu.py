@@ -113,7 +113,9 @@ def test_the_chunk_size_comes_from_the_library_s_constants(programs):
     src = open(os.path.join(CSRC, "codec.cpp")).read()
     assert "static uint64_t delta_small_tmp_px(uint64_t npx) { return (npx + 3) & ~3ull; }" in src
     assert "static uint64_t delta_small_frame_bytes(uint64_t npx) { return ds_stride(npx) + 12 * delta_small_tmp_px(npx); }" in src
-    assert "const uint64_t room = (2ull << 30) / delta_small_frame_bytes((uint64_t)fr[at]->w * fr[at]->h);" in src
+    assert "static uint64_t frame_px(const VarFrame &f) { return (uint64_t)f.w * f.h; }" in src
+    assert "[](const VarFrame &first) { return (2ull << 30) / delta_small_frame_bytes(frame_px(first)); }" in src
+    assert "const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - at, std::max<uint64_t>(1, frames_that_fit(*fr[at])));" in src
     kern = open(os.path.join(CSRC, "k_delta_small.hip")).read()
     assert re.search(r"constexpr int kDsThreads = %d;" % E.THREADS, kern) and re.search(r"constexpr uint32_t kDsMinCap = %d;" % E.MIN_CAP, kern)
     assert E.ds_stride(E.MAX_PX) == 170000 and E.frame_bytes(E.MAX_PX) == 366608 and E.chunk_frames(E.MAX_PX) == 5857

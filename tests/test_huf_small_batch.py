@@ -219,6 +219,46 @@ def test_capacity_is_one_frame_s(host_out):
             assert bool((host[f * stride + lens[f]:(f + 1) * stride] == POISON).all()), f
 
 
+def tiny_images():
+    """at most 16 x 16"""
+    from cniic_amd import synth
+    return [synth.uniform(16, 16, synth.SEED0 + 7950), synth.photo(12, 9, synth.SEED0 + 7951), synth.uniform(7, 9, synth.SEED0 + 7952), np.full((4, 5, 3), 77, np.uint8)]
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_chunk_whose_frames_all_exceed_their_capacity(host_out):
+    """every frame has a stream and none has the room: nothing is placed, no place timer is recorded, no byte is written"""
+    import cniic_amd
+    imgs = tiny_images()
+    want = singles("tiny", imgs)
+    assert all(s[0] == 0 and len(s[1]) > 8 for s in want)
+    with cniic_amd.Context(0) as ctx:
+        rc, lens, rcs, sts, streams, host, launches, msg = batch(ctx, imgs, 8, host_out=host_out, poison=POISON)
+        assert ctx.kernel_time("huf_small_place")[1] == 0
+    assert launches == len(imgs) and rc == CAPACITY and rcs == [CAPACITY] * len(imgs)
+    assert lens == [len(s[1]) for s in want]
+    assert msg == "encode: stream is %d bytes, capacity 8" % len(want[0][1])
+    assert bool((host == POISON).all())
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_frame_a_chunk(host_out, monkeypatch):
+    """CNIIC_TEST_MEASURE_BUDGET=1: every frame is a chunk of its own, placed (device memory) or copied down (host memory) once per chunk"""
+    import cniic_amd
+    imgs = tiny_images()
+    want = singles("tiny", imgs)
+    stride = _stride(want)
+    monkeypatch.setenv("CNIIC_TEST_MEASURE_BUDGET", "1")
+    with cniic_amd.Context(0) as ctx:
+        res = batch(ctx, imgs, stride, host_out=host_out, poison=POISON)
+        assert ctx.kernel_time("huf_small_place")[1] == (0 if host_out else len(imgs))
+    monkeypatch.delenv("CNIIC_TEST_MEASURE_BUDGET")
+    assert res[6] == len(imgs)
+    check_against_singles(res, want, "a frame a chunk")
+    for f in range(len(imgs)):
+        assert bool((res[5][f * stride + res[1][f]:(f + 1) * stride] == POISON).all()), f
+
+
 def test_the_floor(monkeypatch):
     """in a call with fewer than FLOOR_FRAMES candidate frames only those of at most FLOOR_PX pixels take the route: one CU is slower for
     one large frame than the workers' whole chip (NOTES AF)"""

@@ -336,6 +336,67 @@ def test_a_stride_one_byte_short(host_out):
             assert src == CAPACITY and res[0] == CAPACITY and res[7] == _last_error(ref) == "encode: stream is %d bytes, capacity %d" % (stream_len(K), stride)
 
 
+def tiny_images():
+    """at most 16 x 16, 20 pixels at least"""
+    from cniic_amd import synth
+    return [synth.uniform(16, 16, synth.SEED0 + 9400), synth.photo(15, 15, synth.SEED0 + 9401), synth.uniform(7, 9, synth.SEED0 + 9402), synth.photo(5, 4, synth.SEED0 + 9403)]
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_chunk_whose_frames_all_fail_the_kmeans_check(host_out):
+    """no frame has a stream: nothing is placed, no place timer is recorded, no byte is written"""
+    import cniic_amd
+    expr = "voronoi(256)"
+    imgs = tiny_images()[1:]          # fewer than 256 pixels each
+    want = singles("all fail", expr, imgs)
+    assert [s[0] for s in want] == [TOO_FEW_POINTS] * len(imgs)
+    with cniic_amd.Context(0) as ctx:
+        res = batch(ctx, expr, imgs, stream_len(256) + 1, host_out=host_out, poison=0xA5)
+        assert ctx.kernel_time("vor_small_place")[1] == 0
+    assert res[6] == len(imgs) and res[1] == [0] * len(imgs)
+    check_against_singles(res, want, "all fail")
+    assert bool((res[5] == 0xA5).all())
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_chunk_whose_frames_all_exceed_their_capacity(host_out):
+    """every frame has a stream and none has the room: nothing is placed, no place timer is recorded, no byte is written"""
+    import cniic_amd
+    K = 16
+    expr = "voronoi(%d)" % K
+    imgs = tiny_images()
+    want = singles("all short", expr, imgs)
+    assert all(s[0] == 0 for s in want)
+    stride = stream_len(K) - 1
+    with cniic_amd.Context(0) as ctx:
+        rc, lens, rcs, sts, streams, host, launches, msg = batch(ctx, expr, imgs, stride, host_out=host_out, poison=0xA5)
+        assert ctx.kernel_time("vor_small_place")[1] == 0
+    assert launches == len(imgs) and rc == CAPACITY and rcs == [CAPACITY] * len(imgs) and lens == [stream_len(K)] * len(imgs)
+    assert msg == "encode: stream is %d bytes, capacity %d" % (stream_len(K), stride)
+    for f, s in enumerate(want):
+        assert {k: sts[f][k] for k in STATS} == {k: s[2][k] for k in STATS}, f
+    assert bool((host == 0xA5).all())
+
+
+@pytest.mark.parametrize("host_out", (False, True))
+def test_a_frame_a_chunk(host_out, monkeypatch):
+    """CNIIC_TEST_MEASURE_BUDGET=1: every frame is a chunk of its own, placed (device memory) or copied down (host memory) once per chunk"""
+    import cniic_amd
+    K = 16
+    expr = "voronoi(%d)" % K
+    imgs = tiny_images()
+    want = singles("all short", expr, imgs)
+    stride = stream_len(K) + 5
+    monkeypatch.setenv("CNIIC_TEST_MEASURE_BUDGET", "1")
+    with cniic_amd.Context(0) as ctx:
+        res = batch(ctx, expr, imgs, stride, host_out=host_out, poison=0xC3)
+        assert ctx.kernel_time("vor_small_place")[1] == (0 if host_out else len(imgs))
+    monkeypatch.delenv("CNIIC_TEST_MEASURE_BUDGET")
+    assert res[6] == len(imgs)
+    check_against_singles(res, want, "a frame a chunk")
+    check_poison(res, stride, 0xC3, "a frame a chunk", routed(imgs))
+
+
 def test_many_frames_in_one_launch():
     import cniic_amd
     rng = np.random.default_rng(43)
