@@ -1767,6 +1767,7 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
             }
         }
         if (status == 2) {  // the node walk on the host: needs the whole stream there
+            if (c->timers) c->ktimes["hd_host_walk"].launches++;   // (stage timers: the host's walk decoded the payload; no duration)
             ud_sums.filled = false;
             if (bytes_dev) head.n = 0;  // (the pinned block the head was fetched into has served other purposes since: fetch again)
             CNIIC_TRY(stream_head(c, bytes, bytes_dev, nbytes, nbytes, &head));

@@ -819,11 +819,13 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
         if (wide) hipLaunchKernelGGL(k_hd_pass<true>, dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, prev, cur, start_d.as<uint64_t>(), count.as<uint32_t>(), changed.as<uint32_t>(), kHdMaxRounds, 0u, 0u, keep_p);
         else hipLaunchKernelGGL(k_hd_pass<false>, dim3(grid), dim3(kHdThreads), lds, c->stream, S, T, nsub, prev, cur, start_d.as<uint64_t>(), count.as<uint32_t>(), changed.as<uint32_t>(), pass_rounds, hopeless_min, hopeless_pct, keep_p);
     };
+    bool copied = false;   // did the last write copy kept rows?  (the stage mark "hd_compact")
     auto write = [&](bool guarded, bool kept) -> int {   // guarded: nothing to write if pass 0 has given the stream up; kept: the passes' symbols stand in keep_d
         CNIIC_TRY(pack_scan(c, count.as<uint32_t>(), (uint32_t)nsub, off.as<uint64_t>(), tot.as<uint64_t>()));
         const uint64_t *st = start_d.as<uint64_t>(), *of = off.as<uint64_t>();
         const uint32_t *hp = guarded && hopeless_min ? changed.as<uint32_t>() + 5 : nullptr;
         if (sums) sums->filled = false;
+        copied = kept && keep_p;
         // (a wide code has no verdict: phases_ok is false, so hopeless_min is 0 and hp null)
         auto decode = [&](const uint32_t *only_long, int32_t *chunk_sum) {
             auto kern = wide ? (mode == 0 ? k_hd_write<true, 0> : k_hd_write<true, 1>) : (mode == 0 ? k_hd_write<false, 0> : k_hd_write<false, 1>);
@@ -878,6 +880,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
     CNIIC_TRY(look());
     auto phases = [&]() -> int {   // every phase of every subsequence (see k_hd_phase_maps) -> start_d, count
         DevBuf maps_d, cnts_d;
+        if (c->timers) c->ktimes["hd_phases"].launches++;   // (stage timers: which route the decode took; no duration)
         // (96 bytes a subsequence: 400 MB for a 256 MiB payload.  Without the memory the caller decodes on the host -- slow, not an error)
         if (maps_d.alloc(nsub * 32) != hipSuccess || cnts_d.alloc(nsub * 64) != hipSuccess) { (void)hipGetLastError(); *status = 2; return CNIIC_OK; }
         const uint32_t nph = std::min(32u, std::max(16u, lt.max_len)), spb = kHpThreads / nph;   // (the other entries of a map are never asked for)
@@ -902,6 +905,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
             CNIIC_HIP_TRY(c, hipMemsetAsync(changed.p, 0, 4, c->stream));
             pass(cur, nxt);
             std::swap(cur, nxt);
+            if (c->timers) c->ktimes["hd_recheck"].launches++;   // (stage timers: a looked check past the blind ones; no duration)
             CNIIC_TRY(look());
             if (!(uint32_t)pin[1]) { settled = true; break; }
         }
@@ -909,6 +913,7 @@ int huff_decode_tables_dev(Ctx *c, const uint8_t *tab_d, uint64_t n, uint64_t of
         if (!settled) { CNIIC_TRY(phases()); if (*status == 2) return CNIIC_OK; }   // (a long stream that kHdMaxPasses checks have not settled)
         else { CNIIC_TRY(write(false, true)); CNIIC_TRY(look()); }
     }
+    if (c->timers) c->ktimes["hd_compact"].launches += copied ? 1 : 0;   // (stage timers: the final write copied kept rows; no duration)
     if (pin[0] < nsyms) { *status = 1; return CNIIC_OK; }
     return CNIIC_OK;
 }

@@ -107,7 +107,12 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * A single decode whose serialised decoder outgrew the host's looks at the stream, so that the GPU parse (k_trieparse.hip) was tried, adds
  * one of two marks (launches only, no duration): "trie_parse" = 1 when that parse's table decoded the payload, "trie_parse_host" = 1 when
  * the stream was handed to the host's node walk instead (a leaf deeper than 56, a stack deeper than 120, or a payload the table's decoder
- * gave up).  Neither when the host parsed the decoder in its first or second look. */
+ * gave up).  Neither when the host parsed the decoder in its first or second look.
+ * The parallel payload decoder (k_hdecode.hip) adds the route it took (launches only, no duration): "hd_phases" = the times the phase maps
+ * ran (a stream that does not fall into step), "hd_recheck" = the checks with a look at their result past the two blind ones, "hd_compact" =
+ * 1 when the final write copied the kept symbols (k_hd_compact) and 0 when it decoded everything again; and the single decode
+ * "hd_host_walk" = 1 when the host's node walk decoded the payload (an image below the GPU's minimum, a leaf deeper than 56, or a payload
+ * the parallel decoder gave up with status 2). */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
