@@ -1955,12 +1955,12 @@ static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, 
 // copy up for the tables and rows (and one for host streams, from the chunk's first frame to its last), ONE launch with a workgroup per
 // frame, one copy down for the status words (and one for a host destination's images, which a memcpy per frame then puts in place), one
 // wait.  A frame the kernel hands back (not settled within its rounds) is left to the caller like everything else not taken.
-// Frames whose decoders k_small_trieparse has parsed (delta_small_parse_dev below) come with their tables in HBM: nothing of those goes up.
+// Frames whose decoders k_small_trieparse / k_small_trieparse_rgb have parsed (small_parse_dev below) come with their tables in HBM: nothing of those goes up.
 // The testing library can switch the route off (CNIIC_TEST_DELTA_SMALL_DEC_OFF=1), lower its bound (CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX) and its
 // settle rounds (CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS), and make the chunks small (CNIIC_TEST_MEASURE_BUDGET, bytes).
 constexpr uint64_t kDeltaSmallDecScratch = 2ull << 30;
 static uint64_t delta_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_DELTA_SMALL_DEC_OFF", "CNIIC_TEST_DELTA_SMALL_DEC_MAX_PX", kDeltaSmallDecMaxPx); }
-// A decoder that k_small_trieparse has left in HBM (delta_small_parse_dev below): its codes, then as many key | length words
+// A decoder that the parse kernel has left in HBM (small_parse_dev below): its codes, then as many key | length words
 struct DeltaSmallDevTab { const uint32_t *code; uint32_t leaves, max_len; };
 // Small `hufman` and `cluster-colors` frames take the same route under the other symbol kind (k_huf_small_dec: RGB keys, no FromDiff, no
 // scan): frames of 1 .. kHufSmallMaxPx pixels whose decoder the host has parsed and has no code longer than kDeltaSmallMaxCodeLen; larger
@@ -2076,89 +2076,132 @@ static int delta_small_decode(Ctx *c, const SmallDecKind &kind, const uint8_t *b
     return CNIIC_OK;
 }
 
-// ------------------------------------------------------------------ the decoders of small `delta` frames, parsed where the streams lie
-// Streams in device memory (k_small_trie.hip): no head of a stream comes to the host.  Every frame with a header (lens[f] >= 8, not named
-// by CNIIC_TEST_DECODE_BATCH_OFF) is a candidate; what the kernel may read of frame f is what the host's looks below get to see of it,
-// min(lens[f], stride) bytes.  The candidates are worked through in chunks whose scratch -- 8 bytes per leaf a stream has room for, at most
-// kSmallTrieMaxLeaves, and the rows -- stays below the budget: per chunk one copy up of the rows, ONE launch with a workgroup per frame,
-// one copy down of the result rows, one wait; then delta_small_decode for the chunk's parsed frames, whose rows point at the tables where
-// the kernel left them.  A parsed frame is routed under the host parse's conditions (no code longer than kDeltaSmallMaxCodeLen -- the
-// kernel finishes no other --, more leaves than one only with a payload).  Every other candidate whose header the kernel did not turn
-// away -- not a decoder, not ours -- is handed back in `host`: the caller runs the host's looks and parse for those frames alone, which
-// keeps the routed frames, every status and every message what they are without this parse.
-// Stage timers: "delta_small_dec_parse" (the launches' time; launches = frames parsed) and "delta_small_dec_parse_host" (no time;
-// launches = frames handed back).  The testing library keeps the host's parse for everything with CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF=1.
+// ------------------------------------------------------------------ the decoders of small frames, parsed where the streams lie
+// Streams in device memory (k_small_trie.hip): no head of a stream comes to the host.  Two kinds: `delta` (SignedColor leaves, S = 6 symbol
+// bytes, k_small_trieparse) and the RGB kinds `hufman` / `cluster-colors` (Rgb leaves, S = 11, k_small_trieparse_rgb).  What the kernel
+// may read of frame f is what the host's looks below get to see of it, min(lens[f], stride) bytes.  The candidates are worked through in
+// chunks whose scratch -- 8 bytes per leaf a stream has room for, at most kSmallTrieMaxLeaves, and the rows -- stays below the budget: per
+// chunk one copy up of the rows, ONE launch with a workgroup per frame, one copy down of the result rows, one wait; then
+// delta_small_decode for the chunk's parsed frames, whose rows point at the tables where the kernel left them.  A parsed frame is routed
+// under the host parse's conditions (no code longer than kDeltaSmallMaxCodeLen -- the kernel finishes no other --, more leaves than one
+// only with a payload).  `host` gets the frames the caller runs the host's looks and parse for, and those alone, which keeps the routed
+// frames, every status and every message what they are without this parse.
+//   `delta`: every frame with a header (lens[f] >= 8, not named by CNIIC_TEST_DECODE_BATCH_OFF) is a candidate.  A frame the kernel
+//     skips on its header (its size, an injected scan) is dropped: the host's parse would not look at it either.  Handed back: not a
+//     decoder, not ours.
+//   RGB kinds: a candidate is also no longer than the longest stream of a small frame (huf_small.hpp), and the parse runs only in a call
+//     with at least `floor` candidates (kHufSmallDecFloorFrames; a pure host test).  A skipped frame is too large for the small route,
+//     and the batched route takes such frames: it is handed back with everything else that was not routed.  The floor is then held on
+//     the result rows: frames are routed once `floor` frames with a verdict other than skipped have been seen.  A chunk that ends before
+//     that keeps its tables for nothing, so its parsed frames (fewer than `floor`) are parsed once more behind the last chunk; with
+//     fewer such frames in the whole call nothing is routed and every frame takes the host's path.
+// Stage timers, per kind (they exist only when the parse ran): "delta_small_dec_parse" / "huf_small_dec_parse" (the launches' time;
+// launches = frames parsed) and "delta_small_dec_parse_host" / "huf_small_dec_parse_host" (no time; launches = candidates handed back).
+// The testing library keeps the host's parse for everything with CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF=1 / CNIIC_TEST_HUF_SMALL_DEC_PARSE_OFF=1.
 static bool delta_small_parse_off() {
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_PARSE_OFF")) return atoi(e) != 0;
     return false;
 }
-static int delta_small_parse_dev(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
-                                 uint32_t *w, uint32_t *h, const std::vector<uint8_t> &off_route, uint64_t max_px, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
-                                 std::vector<std::string> &msgs, std::vector<uint32_t> &host) {
+static bool huf_small_parse_off() {
+    if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_DEC_PARSE_OFF")) return atoi(e) != 0;
+    return false;
+}
+struct SmallParseKind {
+    uint32_t sym_bytes;   // S of small_trie.hpp
+    const SmallDecKind *dec;
+    const char *timer, *timer_host;
+    bool rgb;             // skipped frames and everything else not routed go back to the host's path; the length gate and the floor
+};
+static const SmallParseKind kSmallParseDelta = {6, &kSmallDecDelta, "delta_small_dec_parse", "delta_small_dec_parse_host", false};
+static const SmallParseKind kSmallParseRgb = {11, &kSmallDecRgb, "huf_small_dec_parse", "huf_small_dec_parse_host", true};
+static int small_parse_dev(Ctx *c, const SmallParseKind &kind, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, bool dst_dev,
+                           uint64_t img_stride, uint32_t *w, uint32_t *h, const std::vector<uint8_t> &off_route, uint64_t max_px, uint32_t floor, std::vector<uint8_t> &taken,
+                           std::vector<int32_t> &rcs, std::vector<std::string> &msgs, std::vector<uint32_t> &host) {
     host.clear();
     std::vector<uint32_t> cands;
     auto view = [&](uint32_t f) { return std::min(lens[f], stride); };
-    for (uint32_t f = 0; f < F; f++) if (!off_route[f] && lens[f] >= 8 && view(f) >= 8) cands.push_back(f);
-    if (c->timers) { (void)c->ktimes["delta_small_dec_parse"]; (void)c->ktimes["delta_small_dec_parse_host"]; }
+    auto room_of = [&](uint32_t f) { return kind.sym_bytes == 6 ? st_leaves_room<6>(view(f)) : st_leaves_room<11>(view(f)); };
+    auto everything = [&]() { host.resize(F); for (uint32_t f = 0; f < F; f++) host[f] = f; };
+    const uint64_t longest_small = kind.rgb ? hs_stream_bytes(max_px, (uint64_t)kDeltaSmallMaxCodeLen * max_px) : ~0ull;
+    for (uint32_t f = 0; f < F; f++) if (!off_route[f] && lens[f] >= 8 && lens[f] <= longest_small && view(f) >= 8) cands.push_back(f);
+    if (kind.rgb && (cands.empty() || cands.size() < floor)) { everything(); return CNIIC_OK; }   // (the parse does not run: no stage of its)
+    if (c->timers) { (void)c->ktimes[kind.timer]; (void)c->ktimes[kind.timer_host]; }
     if (cands.empty()) return CNIIC_OK;
     const uint64_t budget = test_budget(kDeltaSmallDecScratch);
-    auto scratch_of = [&](uint32_t f) { return (uint64_t)st_leaves_room<6>(view(f)) * 8 + sizeof(SmallTrieRow) + sizeof(SmallTrieResult); };
+    auto scratch_of = [&](uint32_t f) { return (uint64_t)room_of(f) * 8 + sizeof(SmallTrieRow) + sizeof(SmallTrieResult); };
     const bool scan = c->scan_xy.p != nullptr;
     std::vector<DeltaSmallDevTab> dev(F);
     std::vector<uint64_t> pay(F, 0);
+    std::vector<uint8_t> back(F, kind.rgb ? 1 : 0);   // the frames of `host`
+    std::vector<uint32_t> late;                        // parsed in a chunk that ended below the floor
     const std::vector<std::vector<uint32_t>> no_tabs;
-    uint64_t parsed = 0;
-    for (size_t i0 = 0; i0 < cands.size();) {
-        const size_t i1 = take_chunk(i0, cands.size(), budget, [&](size_t i) { return scratch_of(cands[i]); });
-        uint64_t longest = 0;
-        const size_t S = i1 - i0;
-        // ---- one block: the rows, the result rows, every frame's table
-        const uint64_t res_at = (S * sizeof(SmallTrieRow) + 15) & ~15ull, tab_at = (res_at + S * sizeof(SmallTrieResult) + 15) & ~15ull;
-        uint64_t words = 0;
-        for (size_t i = 0; i < S; i++) words += 2ull * st_leaves_room<6>(view(cands[i0 + i]));
-        DevBuf blk_d;
-        CNIIC_HIP_TRY(c, blk_d.alloc(tab_at + words * 4 + 16));
-        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(res_at, pinned_huf_want(res_at)));
-        SmallTrieRow *rows = c->pinned_huf.as<SmallTrieRow>();
-        uint32_t *tab0 = reinterpret_cast<uint32_t *>(blk_d.as<uint8_t>() + tab_at);
-        uint64_t wat = 0;
-        for (size_t i = 0; i < S; i++) {
-            const uint32_t f = cands[i0 + i];
-            rows[i].stream = bytes + (uint64_t)f * stride;
-            rows[i].table = tab0 + wat;
-            rows[i].bytes = view(f);
-            wat += 2ull * st_leaves_room<6>(view(f));
-            longest = std::max(longest, view(f));
+    uint64_t parsed = 0, handed = 0, seen = 0;
+    auto run_list = [&](const std::vector<uint32_t> &list, bool first) -> int {
+        for (size_t i0 = 0; i0 < list.size();) {
+            const size_t i1 = take_chunk(i0, list.size(), budget, [&](size_t i) { return scratch_of(list[i]); });
+            uint64_t longest = 0;
+            const size_t S = i1 - i0;
+            // ---- one block: the rows, the result rows, every frame's table
+            const uint64_t res_at = (S * sizeof(SmallTrieRow) + 15) & ~15ull, tab_at = (res_at + S * sizeof(SmallTrieResult) + 15) & ~15ull;
+            uint64_t words = 0;
+            for (size_t i = 0; i < S; i++) words += 2ull * room_of(list[i0 + i]);
+            DevBuf blk_d;
+            CNIIC_HIP_TRY(c, blk_d.alloc(tab_at + words * 4 + 16));
+            CNIIC_HIP_TRY(c, c->pinned_huf.reserve(res_at, pinned_huf_want(res_at)));
+            SmallTrieRow *rows = c->pinned_huf.as<SmallTrieRow>();
+            uint32_t *tab0 = reinterpret_cast<uint32_t *>(blk_d.as<uint8_t>() + tab_at);
+            uint64_t wat = 0;
+            for (size_t i = 0; i < S; i++) {
+                const uint32_t f = list[i0 + i];
+                rows[i].stream = bytes + (uint64_t)f * stride;
+                rows[i].table = tab0 + wat;
+                rows[i].bytes = view(f);
+                wat += 2ull * room_of(f);
+                longest = std::max(longest, view(f));
+            }
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(blk_d.p, rows, S * sizeof(SmallTrieRow), hipMemcpyHostToDevice, c->stream));
+            {
+                ScopedKernelTimer t(c, kind.timer);
+                CNIIC_TRY(small_trie_run(c, kind.sym_bytes, blk_d.as<SmallTrieRow>(), (uint32_t)S, longest, (uint32_t)max_px, img_stride, scan ? c->scan_w : 0,
+                                         scan ? c->scan_h : 0, reinterpret_cast<SmallTrieResult *>(blk_d.as<uint8_t>() + res_at)));
+                t.stop(0);
+            }
+            std::vector<SmallTrieResult> res(S);
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), blk_d.as<uint8_t>() + res_at, S * sizeof(SmallTrieResult), hipMemcpyDeviceToHost, c->stream));
+            CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (first) for (size_t i = 0; i < S; i++) seen += res[i].verdict != kStSkipped;
+            const bool met = seen >= floor;
+            std::vector<uint32_t> route;
+            for (size_t i = 0; i < S; i++) {
+                const uint32_t f = list[i0 + i];
+                const SmallTrieResult &r = res[i];
+                if (r.verdict == kStSkipped) { handed += first && kind.rgb; continue; }   // (`delta`: the host's parse would not look at it either)
+                if (r.verdict != kStParsed) { back[f] = 1; handed += first; continue; }
+                parsed += first;
+                if (r.leaves == 0 || r.leaves > room_of(f) || r.max_len > kDeltaSmallMaxCodeLen || r.payload_at > view(f))
+                    return c->fail(CNIIC_ERR_HIP, "small_trieparse: frame %u reported a decoder outside its stream", f);
+                if (r.leaves > 1 && r.payload_at >= lens[f]) continue;   // (symbols, and no payload: the single decode answers)
+                if (!met) { late.push_back(f); continue; }
+                w[f] = r.w; h[f] = r.h;
+                pay[f] = r.payload_at;
+                dev[f] = DeltaSmallDevTab{rows[i].table, r.leaves, r.max_len};
+                back[f] = 0;
+                route.push_back(f);
+            }
+            if (!route.empty()) CNIIC_TRY(delta_small_decode(c, *kind.dec, bytes, true, stride, lens, rgb, dst_dev, img_stride, w, h, route, no_tabs, &dev, pay, taken, rcs, msgs));
+            i0 = i1;
         }
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(blk_d.p, rows, S * sizeof(SmallTrieRow), hipMemcpyHostToDevice, c->stream));
-        {
-            ScopedKernelTimer t(c, "delta_small_dec_parse");
-            CNIIC_TRY(small_trie_run(c, blk_d.as<SmallTrieRow>(), (uint32_t)S, longest, (uint32_t)max_px, img_stride, scan ? c->scan_w : 0, scan ? c->scan_h : 0,
-                                     reinterpret_cast<SmallTrieResult *>(blk_d.as<uint8_t>() + res_at)));
-            t.stop(0);
-        }
-        std::vector<SmallTrieResult> res(S);
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), blk_d.as<uint8_t>() + res_at, S * sizeof(SmallTrieResult), hipMemcpyDeviceToHost, c->stream));
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::vector<uint32_t> route;
-        for (size_t i = 0; i < S; i++) {
-            const uint32_t f = cands[i0 + i];
-            const SmallTrieResult &r = res[i];
-            if (r.verdict == kStSkipped) continue;   // (its size or an injected scan: the host's parse would not look at it either)
-            if (r.verdict != kStParsed) { host.push_back(f); continue; }
-            parsed++;
-            if (r.leaves == 0 || r.leaves > st_leaves_room<6>(view(f)) || r.max_len > kDeltaSmallMaxCodeLen || r.payload_at > view(f))
-                return c->fail(CNIIC_ERR_HIP, "small_trieparse: frame %u reported a decoder outside its stream", f);
-            if (r.leaves > 1 && r.payload_at >= lens[f]) continue;   // (symbols, and no payload: the single decode answers)
-            w[f] = r.w; h[f] = r.h;
-            pay[f] = r.payload_at;
-            dev[f] = DeltaSmallDevTab{rows[i].table, r.leaves, r.max_len};
-            route.push_back(f);
-        }
-        if (!route.empty()) CNIIC_TRY(delta_small_decode(c, kSmallDecDelta, bytes, true, stride, lens, rgb, dst_dev, img_stride, w, h, route, no_tabs, &dev, pay, taken, rcs, msgs));
-        i0 = i1;
+        return CNIIC_OK;
+    };
+    CNIIC_TRY(run_list(cands, true));
+    if (seen < floor) {   // (fewer small frames than the floor: nothing is routed from here)
+        everything();
+        handed = cands.size();
+    } else {
+        if (!late.empty()) { const std::vector<uint32_t> again(late); CNIIC_TRY(run_list(again, false)); }
+        for (uint32_t f = 0; f < F; f++) if (back[f]) host.push_back(f);
     }
-    if (c->timers) { c->ktimes["delta_small_dec_parse"].launches += parsed; c->ktimes["delta_small_dec_parse_host"].launches += host.size(); }
+    if (c->timers) { c->ktimes[kind.timer].launches += parsed; c->ktimes[kind.timer_host].launches += handed; }
     return CNIIC_OK;
 }
 
@@ -2226,8 +2269,9 @@ static int vor_small_decode(Ctx *c, uint8_t *rgb, bool dst_dev, uint64_t img_str
 // delta_small_decode with their tables of leaves, a workgroup per frame (larger `delta` frames are the caller's).  Whatever this route does
 // not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more than 32
 // bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
-// `delta` streams that lie in device memory are parsed there first (delta_small_parse_dev); the heads and the host's parse below are then
-// for the frames that parse hands back, and for those alone.  Streams in host memory keep the host's parse: the bytes are where the parser is.
+// `delta` streams that lie in device memory are parsed there first (small_parse_dev), and so are `hufman` and `cluster-colors` streams in
+// a call with at least kHufSmallDecFloorFrames frames short enough to be small; the heads and the host's parse below are then for the
+// frames that parse hands back, and for those alone.  Streams in host memory keep the host's parse: the bytes are where the parser is.
 constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
                              uint64_t img_stride, uint32_t *w, uint32_t *h, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
@@ -2325,10 +2369,12 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         if (route.empty()) return CNIIC_OK;
         return vor_small_decode(c, rgb, dst_dev, img_stride, w, h, route, table, cent, Ks, taken);
     }
-    // `delta` streams in device memory: the decoders are parsed there, and the host looks only at the frames that parse hands back
+    // streams in device memory: the decoders of small frames are parsed there, and the host looks only at the frames that parse hands back
     std::vector<uint32_t> all;
-    if (delta && bytes_dev && !delta_small_parse_off()) {
-        CNIIC_TRY(delta_small_parse_dev(c, bytes, stride, lens, F, rgb, dst_dev, img_stride, w, h, off_route, delta_max_px, taken, rcs, msgs, all));
+    const SmallParseKind *parse = !bytes_dev ? nullptr : delta ? (delta_small_parse_off() ? nullptr : &kSmallParseDelta) : (rgb_max_px && !huf_small_parse_off() ? &kSmallParseRgb : nullptr);
+    if (parse) {
+        CNIIC_TRY(small_parse_dev(c, *parse, bytes, stride, lens, F, rgb, dst_dev, img_stride, w, h, off_route, delta ? delta_max_px : rgb_max_px, delta ? 0 : huf_small_dec_floor(), taken,
+                                  rcs, msgs, all));
         if (all.empty()) return CNIIC_OK;
     } else {
         all.resize(F);

@@ -959,15 +959,16 @@ int delta_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames,
 // the same for RGB symbols (k_huf_small_dec: small `hufman` and `cluster-colors` frames; key = r << 16 | g << 8 | b, position d is pixel d,
 // no FromDiff): status_d[f] is kDsdOk, kDsdShort or kDsdUnsettled
 int huf_small_dec_run(Ctx *c, const DeltaSmallDecRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t max_rounds, uint32_t *status_d);
-// ---- k_small_trie.hip: the parse of small `delta` frames' decoders, one workgroup per frame (small_trie.hpp has the arithmetic and the
-// limits).  A row per frame: its stream (device memory, any alignment; `bytes` of it may be read) and where its table goes -- room for
-// st_leaves_room<6>(bytes) leaves of two words, 4-byte aligned: the left-aligned codes, then as many key | length << 27 words, which is what
+// ---- k_small_trie.hip: the parse of small frames' decoders, one workgroup per frame (small_trie.hpp has the arithmetic and the
+// limits).  sym_bytes = S: 6 for the SignedColor leaves of `delta` streams, 11 for the Rgb leaves of `hufman` and `cluster-colors` streams
+// (no scan test: scan_w and scan_h are not looked at).  A row per frame: its stream (device memory, any alignment; `bytes` of it may be
+// read) and where its table goes -- room for st_leaves_room<S>(bytes) leaves of two words, 4-byte aligned: the left-aligned codes, then as many key | length << 27 words, which is what
 // DeltaSmallDecRow points at.  res_d[f]: the header's w and h (when there are 8 bytes), the verdict (small_trie.hpp), and of a parsed
 // decoder the leaves, the longest code and the payload's offset in the stream.  A frame of 0 or more than max_px pixels, of more than
 // img_stride bytes or of the size scan_w x scan_h (0 x 0: none) is skipped (kStSkipped).
 struct SmallTrieRow { const uint8_t *stream; uint32_t *table; uint64_t bytes; };
 struct SmallTrieResult { uint32_t w, h, verdict, leaves, max_len, payload_at; };
-int small_trie_run(Ctx *c, const SmallTrieRow *rows_d, uint32_t frames, uint64_t max_bytes /* of the longest stream */, uint32_t max_px, uint64_t img_stride,
+int small_trie_run(Ctx *c, uint32_t sym_bytes, const SmallTrieRow *rows_d, uint32_t frames, uint64_t max_bytes /* of the longest stream */, uint32_t max_px, uint64_t img_stride,
                    uint32_t scan_w, uint32_t scan_h, SmallTrieResult *res_d);
 // ---- k_vor_small.hip: voronoi(K <= 256) of small frames, one workgroup per frame (vor_small.hpp has the arithmetic, the limits and the
 // stream's layout).  A row per frame: its pixels (device memory, any alignment).  Frame f's finished stream (16 + 19 K bytes) lands at

@@ -3,16 +3,18 @@
 // delta_small_dec.hpp, for the table's words) alone, so it includes nothing else of the library.
 //
 // The statement to match is huff_parse_leaves (huff_host.cpp; Dec::deserialize, huf.rs:323-348): the trie in pre-order, a record per
-// node -- tag 1: a branch, 1 byte; tag 0: a leaf, 1 + S bytes, S = 6 for SignedColor (three little-endian i16 in -255..255, get_symbol).
-// S is a template parameter throughout; the route serves S = 6 only (S = 11, Rgb<u8>, needs a 64-bit map word: 12 nibbles).
+// node -- tag 1: a branch, 1 byte; tag 0: a leaf, 1 + S bytes.  S = 6 is a SignedColor (three little-endian i16 in -255..255, get_symbol):
+// the leaf of a `delta` stream.  S = 11 is an Rgb<u8> (a little-endian u64 that must be 3, then r, g, b): the leaf of a `hufman` stream and of
+// a `cluster-colors` stream.  S is a template parameter throughout, and what follows from it -- the map's word, a lane's chunks, the symbol
+// check -- is stated per S below (StMap<S>, st_max_k<S>, StLeafKey<S>); tests/small_trie_rgb_check.cpp is small_trie_check.cpp's S = 11 twin.
 //
 // Names.  The trie's bytes (the stream behind its 8-byte header) are looked at as far as the WINDOW reaches: M = min(stream bytes,
 // st_max_bytes) -- a decoder of at most kSmallTrieMaxLeaves leaves has that many bytes at the most, and a record is read only when it
 // lies in the window whole.  The window is cut into CHUNKS of kStChunk = 32 bytes, so that a chunk's tags are two 32-bit masks (which
-// bytes are a 1, which are a 0) and a walk through it runs in registers; a LANE owns K = 1 .. 4 consecutive chunks (K the least that gives
-// 1024 lanes the window).  A walk that enters a chunk at offset o in 0 .. S (the first record starts o bytes in) leaves it at an offset of
+// bytes are a 1, which are a 0) and a walk through it runs in registers; a LANE owns K = 1 .. 4 consecutive chunks (1 .. 7 for S = 11; K the
+// least that gives 1024 lanes the window).  A walk that enters a chunk at offset o in 0 .. S (the first record starts o bytes in) leaves it at an offset of
 // the next one, or STOPS at a byte that starts no record (a tag other than 0 / 1, the window's end): the R = S + 1 exits are a MAP in one
-// word, R fields of 3 bits, the value R meaning stopped.  Composing maps is associative, so a scan gives every lane its true entry.
+// word, R fields of 3 bits (S = 11: 12 fields of 4 bits in a 64-bit word), the value R meaning stopped.  Composing maps is associative, so a scan gives every lane its true entry.
 // P of a node = the subtrees still open in front of it = branches - leaves among the earlier nodes; the trie ends behind the first leaf
 // met with P = 0 (node E).  Node k + 1 is the left child of branch k; the node behind a leaf is the right child of the last earlier node
 // with its own P.  A RUN is a leaf and the branches straight in front of it (a left spine: every node the left child of the one before),
@@ -34,7 +36,9 @@ namespace cniic {
 constexpr uint32_t kSmallTrieMaxLeaves = 16384;   // leaves of a decoder the kernel finishes: no encoder makes more leaves than pixels
 constexpr uint32_t kStLanes = 1024;               // lanes of the workgroup
 constexpr uint32_t kStChunk = 32;                 // bytes of a chunk: its tags are two 32-bit masks
-constexpr uint32_t kStMaxK = 4;                   // chunks of a lane at the bound
+constexpr uint32_t kStMaxK = 4;                   // chunks of a lane at the bound (S = 6)
+constexpr uint32_t kStMaxKRgb = 7;                // and for S = 11: 7 * 1024 * 32 = 229 376 >= 212 991
+template <uint32_t S> constexpr uint32_t st_max_k() { return S == 6 ? kStMaxK : kStMaxKRgb; }
 constexpr uint32_t kStMaxP = kDeltaSmallMaxCodeLen;   // P of a node is at most its depth: rows 0 .. kStMaxP of the table of last nodes
 constexpr uint32_t kStJumpRounds = 5;             // 2^5 > kDeltaSmallMaxCodeLen links of a chain of runs
 static_assert(kSmallTrieMaxLeaves == kDeltaSmallDecMaxPx, "a decoder of a routed frame has no more leaves than the frame has pixels");
@@ -45,6 +49,7 @@ constexpr uint32_t kStParsed = 0, kStNotDecoder = 1, kStNotOurs = 2, kStSkipped 
 
 template <uint32_t S> constexpr uint32_t st_max_bytes() { return (S + 2) * kSmallTrieMaxLeaves - 1; }   // L leaves, L - 1 branches
 static_assert((st_max_bytes<6>() + kStChunk - 1) / kStChunk <= kStMaxK * kStLanes, "1024 lanes of 4 chunks hold the largest window");
+static_assert(st_max_bytes<11>() == 212991 && (st_max_bytes<11>() + kStChunk - 1) / kStChunk <= kStMaxKRgb * kStLanes, "1024 lanes of 7 chunks hold the largest window of Rgb leaves");
 CNIIC_ST_HD uint32_t st_window(uint64_t trie_bytes, uint32_t max_bytes) { return (uint32_t)(trie_bytes < max_bytes ? trie_bytes : max_bytes); }
 CNIIC_ST_HD uint32_t st_chunks(uint32_t window) { return (window + kStChunk - 1) / kStChunk; }
 CNIIC_ST_HD uint32_t st_lane_chunks(uint32_t window) { const uint32_t k = (st_chunks(window) + kStLanes - 1) / kStLanes; return k ? k : 1; }
@@ -73,36 +78,47 @@ template <uint32_t S> CNIIC_ST_HD void st_masks(const uint32_t w[8], uint32_t at
     lf &= st_low_bits(window >= at + S + 1 ? window - S - at : 0);
 }
 
-// ---- maps: field o (3 bits) = the exit of a walk that enters at o; the value R = S + 1 is "stopped", and stopped stays stopped
-constexpr uint32_t kStMapBits = 3;
-template <uint32_t S> CNIIC_ST_HD uint32_t st_map_get(uint32_t m, uint32_t o) { return o > S ? S + 1 : (m >> (kStMapBits * o)) & ((1u << kStMapBits) - 1u); }
-template <uint32_t S> CNIIC_ST_HD uint32_t st_map_identity() {
-    static_assert(S + 1 < (1u << kStMapBits) && (S + 1) * kStMapBits <= 32, "R exits and the stopped value fit the fields, the fields one word");
-    uint32_t m = 0;
-    for (uint32_t o = 0; o <= S; o++) m |= o << (kStMapBits * o);
+// ---- maps: field o = the exit of a walk that enters at o; the value R = S + 1 is "stopped", and stopped stays stopped.  The fields' width and
+// the word follow from S: 7 fields of 3 bits in 32 bits for S = 6, 12 fields of 4 bits (48 bits) in 64 for S = 11
+constexpr uint32_t kStMapBits = 3;   // S = 6
+template <uint32_t S> struct StMap;
+template <> struct StMap<6> { typedef uint32_t word; static constexpr uint32_t bits = kStMapBits; };
+template <> struct StMap<11> { typedef uint64_t word; static constexpr uint32_t bits = 4; };
+template <uint32_t S> CNIIC_ST_HD uint32_t st_map_get(typename StMap<S>::word m, uint32_t o) {
+    return o > S ? S + 1 : (uint32_t)(m >> (StMap<S>::bits * o)) & ((1u << StMap<S>::bits) - 1u);
+}
+template <uint32_t S> CNIIC_ST_HD typename StMap<S>::word st_map_identity() {
+    typedef typename StMap<S>::word W;
+    static_assert(S + 1 < (1u << StMap<S>::bits) && (S + 1) * StMap<S>::bits <= 8 * sizeof(W), "R exits and the stopped value fit the fields, the fields one word");
+    W m = 0;
+    for (uint32_t o = 0; o <= S; o++) m |= (W)o << (StMap<S>::bits * o);
     return m;
 }
 // first a, then b
-template <uint32_t S> CNIIC_ST_HD uint32_t st_map_compose(uint32_t a, uint32_t b) {
-    uint32_t m = 0;
+template <uint32_t S> CNIIC_ST_HD typename StMap<S>::word st_map_compose(typename StMap<S>::word a, typename StMap<S>::word b) {
+    typedef typename StMap<S>::word W;
+    W m = 0;
 #pragma unroll
-    for (uint32_t o = 0; o <= S; o++) m |= st_map_get<S>(b, st_map_get<S>(a, o)) << (kStMapBits * o);
+    for (uint32_t o = 0; o <= S; o++) m |= (W)st_map_get<S>(b, st_map_get<S>(a, o)) << (StMap<S>::bits * o);
     return m;
 }
 
 // ---- a lane: its chunks' masks, its first byte, and (after the scans) where the true walk enters it, the nodes and leaves in front of it
-struct StLane {
-    uint32_t br[kStMaxK], lf[kStMaxK];
+template <uint32_t MAXK> struct StLaneK {
+    static constexpr uint32_t kMaxK = MAXK;
+    uint32_t br[MAXK], lf[MAXK];
     uint32_t K, at, entry, nodes_before, leaves_before;
 };
+typedef StLaneK<kStMaxK> StLane;         // S = 6
+typedef StLaneK<kStMaxKRgb> StLaneRgb;   // S = 11
 constexpr uint32_t kStNoStop = 0xffffffffu;
 // The walk through a lane's chunks from its entry: visit(byte offset of the record, is it a leaf) for every node, until visit says false,
 // the chunks end or the walk stops.  -> the byte at which it stopped (kStNoStop: it did not); *exit = the offset into the next lane's
 // first chunk (S + 1: stopped, or visit ended it).  Every step advances by a record of at least one byte.
-template <uint32_t S, class F> CNIIC_ST_HD uint32_t st_lane_walk(const StLane &ln, uint32_t entry, uint32_t *exit, F &&visit) {
+template <uint32_t S, class LN, class F> CNIIC_ST_HD uint32_t st_lane_walk(const LN &ln, uint32_t entry, uint32_t *exit, F &&visit) {
     uint32_t o = entry, stopped = kStNoStop;
 #pragma unroll
-    for (uint32_t k = 0; k < kStMaxK; k++) {
+    for (uint32_t k = 0; k < LN::kMaxK; k++) {
         if (k < ln.K && o <= S) {
             const uint32_t br = ln.br[k], lf = ln.lf[k];
             uint32_t pos = o;
@@ -120,18 +136,18 @@ template <uint32_t S, class F> CNIIC_ST_HD uint32_t st_lane_walk(const StLane &l
     return stopped;
 }
 // phase 1: the lane's map
-template <uint32_t S> CNIIC_ST_HD uint32_t st_lane_map(const StLane &ln) {
-    uint32_t m = 0;
+template <uint32_t S, class LN> CNIIC_ST_HD typename StMap<S>::word st_lane_map(const LN &ln) {
+    typename StMap<S>::word m = 0;
 #pragma unroll
     for (uint32_t o = 0; o <= S; o++) {
         uint32_t e;
         (void)st_lane_walk<S>(ln, o, &e, [](uint32_t, bool) { return true; });
-        m |= e << (kStMapBits * o);
+        m |= (typename StMap<S>::word)e << (StMap<S>::bits * o);
     }
     return m;
 }
 // phase 2: the true walk's nodes and leaves in the lane, whether its last node is a leaf, and where it stopped
-template <uint32_t S> CNIIC_ST_HD uint32_t st_lane_count(const StLane &ln, uint32_t &nodes, uint32_t &leaves, uint32_t &last_leaf) {
+template <uint32_t S, class LN> CNIIC_ST_HD uint32_t st_lane_count(const LN &ln, uint32_t &nodes, uint32_t &leaves, uint32_t &last_leaf) {
     uint32_t n = 0, l = 0, last = 0;
     const uint32_t stop = st_lane_walk<S>(ln, ln.entry, nullptr, [&](uint32_t, bool leaf) { n++; l += leaf; last = leaf; return true; });
     nodes = n; leaves = l; last_leaf = last;
@@ -140,20 +156,28 @@ template <uint32_t S> CNIIC_ST_HD uint32_t st_lane_count(const StLane &ln, uint3
 
 // ---- the table of last nodes: word = (node + 1) << 15 | the node's run (= leaves in front of it); 0 = none.  Later nodes have larger words,
 // so "the last earlier node with this P" over lanes is a prefix maximum per row.  tab[p * pitch + lane]
+// The word has 17 bits for node + 1, which a window of S = 6 never exceeds (the first assert below).  A window of S = 11 can hold 212 991 nodes
+// -- branches only, or payload bytes behind the trie's end that read as tags --, so st_lane_open writes NO word for a node above
+// kStLastNodeMax = 2 kSmallTrieMaxLeaves - 2, for either S.  Nothing that is read misses such a word: a frame that goes on past phase 3 has
+// L = E / 2 + 1 <= room <= kSmallTrieMaxLeaves leaves, so E <= kStLastNodeMax; phase 4 reads a slot only for the parent of a head <= E, which
+// is a node < E, and the exclusive prefix maximum carries a word only to lanes behind its own, so the words of nodes above E reach lanes that
+// hold nothing but nodes above E, where st_lane_runs reads nothing.  The words that are written have node + 1 < 2^15 and run <= node < 2^15
 CNIIC_ST_HD uint32_t st_last_word(uint32_t node, uint32_t run) { return ((node + 1) << 15) | run; }
 CNIIC_ST_HD uint32_t st_last_node1(uint32_t w) { return w >> 15; }   // node + 1
 CNIIC_ST_HD uint32_t st_last_run(uint32_t w) { return w & 0x7fffu; }
 static_assert(st_max_bytes<6>() + 1 <= (1u << 17) && st_max_bytes<6>() / 7 < (1u << 15), "a window's nodes and leaves fit the word");
+constexpr uint32_t kStLastNodeMax = 2 * kSmallTrieMaxLeaves - 2;   // the last node (leaf E) of the largest trie the kernel finishes
+static_assert(kStLastNodeMax + 1 < (1u << 15) && ((uint64_t)(kStLastNodeMax + 1) << 15 | kStLastNodeMax) < (1ull << 32), "the words st_lane_open writes fit 32 bits for every S");
 constexpr uint32_t kStNone = 0xffffffffu;
 // phase 3: P of the lane's nodes; the last node of every P <= kStMaxP into the lane's column; -> *end = the lane's first leaf with P = 0 (a
 // node index, kStNone: none), *deep = its first node with P above kStMaxP.  Nothing behind the lane's first such leaf is the trie's.
-template <uint32_t S> CNIIC_ST_HD void st_lane_open(const StLane &ln, uint32_t *tab, uint32_t pitch, uint32_t lane, uint32_t *end, uint32_t *deep) {
+template <uint32_t S, class LN> CNIIC_ST_HD void st_lane_open(const LN &ln, uint32_t *tab, uint32_t pitch, uint32_t lane, uint32_t *end, uint32_t *deep) {
     uint32_t node = ln.nodes_before, run = ln.leaves_before, e = kStNone, d = kStNone;
     int32_t P = (int32_t)ln.nodes_before - 2 * (int32_t)ln.leaves_before;
     (void)st_lane_walk<S>(ln, ln.entry, nullptr, [&](uint32_t, bool leaf) {
         if (P < 0) return false;
         if (P > (int32_t)kStMaxP) { if (d == kStNone) d = node; }
-        else tab[(uint32_t)P * pitch + lane] = st_last_word(node, run);
+        else if (node <= kStLastNodeMax) tab[(uint32_t)P * pitch + lane] = st_last_word(node, run);
         if (leaf && P == 0) { e = node; return false; }
         if (leaf) { run++; P--; } else P++;
         node++;
@@ -163,7 +187,8 @@ template <uint32_t S> CNIIC_ST_HD void st_lane_open(const StLane &ln, uint32_t *
 }
 
 // ---- runs: word = the run jumped to (14 bits) | a signed sum << 14 (18 bits).  Every word states a fact -- "A[i] = A[jump] + sum" -- so a
-// jump that reads a target another lane has already moved on is still right
+// jump that reads a target another lane has already moved on is still right.  Only runs of nodes <= E <= kStLastNodeMax get a word: the
+// fields depend on node counts alone, not on S
 CNIIC_ST_HD uint32_t st_run_word(uint32_t jump, int32_t sum) { return jump | ((uint32_t)sum << 14); }
 CNIIC_ST_HD uint32_t st_run_jump(uint32_t w) { return w & 0x3fffu; }
 CNIIC_ST_HD int32_t st_run_sum(uint32_t w) { return (int32_t)w >> 14; }
@@ -172,7 +197,7 @@ static_assert(kSmallTrieMaxLeaves <= (1u << 14) && 4 * kSmallTrieMaxLeaves < (1u
 // phase 4 (the table now holds, per lane, the last node of every P in front of the lane): the lane's runs that start at nodes <= E.
 // head: is the lane's first node behind a leaf (or the root).  -> *pay = the byte behind leaf E when the lane holds it; false: a head without
 // a parent (cannot be in a trie that ended at E with P <= kStMaxP throughout; the caller gives the frame up)
-template <uint32_t S> CNIIC_ST_HD bool st_lane_runs(const StLane &ln, bool head, uint32_t E, uint32_t *tab, uint32_t pitch, uint32_t lane, uint32_t *runs, uint32_t *pay) {
+template <uint32_t S, class LN> CNIIC_ST_HD bool st_lane_runs(const LN &ln, bool head, uint32_t E, uint32_t *tab, uint32_t pitch, uint32_t lane, uint32_t *runs, uint32_t *pay) {
     uint32_t node = ln.nodes_before, run = ln.leaves_before;
     int32_t P = (int32_t)ln.nodes_before - 2 * (int32_t)ln.leaves_before;
     bool ok = true;
@@ -202,7 +227,7 @@ template <uint32_t S> CNIIC_ST_HD bool st_lane_runs(const StLane &ln, bool head,
 // sum over all leaves is exactly 2^32, and a single leaf of length 0 adds 2^32 as well)
 CNIIC_ST_HD uint32_t st_code_step(uint32_t len) { return len ? 1u << (32 - len) : 0u; }
 // phase 5: the lengths of the lane's leaves up to E (A[i] + node) -> their steps' sum and the longest; false: one lies deeper than kDeltaSmallMaxCodeLen
-template <uint32_t S> CNIIC_ST_HD bool st_lane_lens(const StLane &ln, uint32_t E, const uint32_t *runs, uint32_t *sum, uint32_t *longest) {
+template <uint32_t S, class LN> CNIIC_ST_HD bool st_lane_lens(const LN &ln, uint32_t E, const uint32_t *runs, uint32_t *sum, uint32_t *longest) {
     uint32_t node = ln.nodes_before, run = ln.leaves_before, s = 0, m = 0;
     bool ok = true;
     (void)st_lane_walk<S>(ln, ln.entry, nullptr, [&](uint32_t, bool leaf) {
@@ -233,10 +258,21 @@ CNIIC_ST_HD bool st_symbol6(uint64_t six, uint32_t *key) {
     *key = k;
     return ok;
 }
+// get_symbol for S = 11 (CNIIC_SYM_RGB): the u64 in front must be 3; rgb = the three bytes behind it as a little-endian number -> hs_key
+CNIIC_ST_HD bool st_symbol11(uint64_t len, uint32_t rgb, uint32_t *key) {
+    *key = ((rgb & 0xffu) << 16) | (rgb & 0xff00u) | ((rgb >> 16) & 0xffu);
+    return len == 3;
+}
+struct StRgbLeaf { uint64_t len; uint32_t rgb; };   // what a reader of S = 11 returns: bytes 0 .. 7 and 8 .. 10 of the symbol, little-endian
+template <uint32_t S> struct StLeafKey;
+template <> struct StLeafKey<6> { template <class R> static CNIIC_ST_HD bool get(R &&rd, uint32_t pos, uint32_t *key) { return st_symbol6(rd(pos), key); } };
+template <> struct StLeafKey<11> {
+    template <class R> static CNIIC_ST_HD bool get(R &&rd, uint32_t pos, uint32_t *key) { const StRgbLeaf l = rd(pos); return st_symbol11(l.len, l.rgb, key); }
+};
 // phase 6: the table's words of the lane's leaves up to E -- code[i] at table[i], dsd_keylen(key, len) at table[L + i] -- from the code of the
-// lane's first leaf.  six(pos): the six bytes at trie offset pos as a little-endian number.  false: a symbol outside -255 .. 255
-template <uint32_t S, class R> CNIIC_ST_HD bool st_lane_table(const StLane &ln, uint32_t E, const uint32_t *runs, uint32_t code, uint32_t L, uint32_t *table, R &&six) {
-    static_assert(S == 6, "SignedColor: the only symbol the table's key | length word is defined for");
+// lane's first leaf.  rd(pos): the symbol's bytes at trie offset pos -- S = 6: the six bytes as a little-endian number; S = 11: an StRgbLeaf.
+// false: a symbol that get_symbol refuses (outside -255 .. 255; a length other than 3)
+template <uint32_t S, class LN, class R> CNIIC_ST_HD bool st_lane_table(const LN &ln, uint32_t E, const uint32_t *runs, uint32_t code, uint32_t L, uint32_t *table, R &&rd) {
     uint32_t node = ln.nodes_before, run = ln.leaves_before;
     bool ok = true;
     (void)st_lane_walk<S>(ln, ln.entry, nullptr, [&](uint32_t pos, bool leaf) {
@@ -244,7 +280,7 @@ template <uint32_t S, class R> CNIIC_ST_HD bool st_lane_table(const StLane &ln, 
         if (leaf) {
             const uint32_t len = (uint32_t)(st_run_sum(runs[run]) + (int32_t)node);
             uint32_t key;
-            ok = st_symbol6(six(pos + 1), &key) && ok;
+            ok = StLeafKey<S>::get(rd, pos + 1, &key) && ok;
             table[run] = code;
             table[L + run] = dsd_keylen(key, len);
             code += st_code_step(len);

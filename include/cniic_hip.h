@@ -703,6 +703,14 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
  * above, and so do the small frames of a call that has fewer than 256 of them (measured: below that the batched route is as fast or faster).  Which route a frame took shows in no output byte, status or message.  Stage timer: "huf_small_dec_batch" = the duration of
  * that kernel, with launches = the frames it was given; cniic_codec_measure_batch leaves it readable beside the encode's
  * "huf_small_batch" (or, for cluster-colors, "cc_small_batch").
+ * When the streams lie in device memory and the call has at least 256 of them that are short enough to be a small frame's (8 .. 251 911
+ * bytes), their decoders are parsed there first, as the `delta` streams' are: a workgroup per frame reads the header and the pre-order
+ * trie of Rgb leaves where the stream lies and leaves the table the decode kernel reads.  A frame that kernel does not finish -- too many
+ * pixels for this route, more than 16 384 leaves, a code longer than 19 bits, bytes that are no decoder -- goes back to the host's parse
+ * and the routes it had, and so does every frame when fewer than 256 turn out to be small; streams in host memory keep the host's parse.
+ * The routed frames, every status and every message are the same either way.  Stage timers, only when that parse ran:
+ * "huf_small_dec_parse" = the duration of its launches, with launches = the frames it parsed; "huf_small_dec_parse_host" = no time,
+ * launches = the candidates handed back to the host's parse.
  *
  * SMALL `voronoi` frames of a decode, here and in cniic_codec_measure_batch: with the expression voronoi(K) (the stream carries its own
  * K), every frame whose header and whole centroid list are there and well formed, with 1 <= K <= 256 centroids, 1 .. 16384 pixels and an

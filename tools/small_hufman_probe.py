@@ -2,17 +2,21 @@
 cluster-colors(256) streams, which are Hufman streams of palette colours) and cniic_codec_measure_batch: this build (the small-frame
 routes, k_huf_small in k_delta_small.hip and k_huf_small_dec in k_delta_small_dec.hip) against another build of the library and against
 this build with the routes switched off, device buffers throughout.
-    python tools/small_hufman_probe.py --against libcniic_hip_parent.so [--out profiles/small_hufman_probe.json] [--reps 5] [--rounds 1]
+    python tools/small_hufman_probe.py --against libcniic_hip_parent.so [--out profiles/small_hufman_parse_probe.json] [--reps 5] [--rounds 1]
 Batches of 1, 8, 256 and 4096 synthetic frames of 32 x 32, 64 x 64, 128 x 96, 128 x 128 and 16384 x 1, photo-like and uniform noise.
 Every variant is timed in a child process of its own, the variants in alternation (this, routes off, other, this, ...), --rounds times
 --reps runs each after --warmup untimed ones; the medians are compared with min - max beside them, and the digests of the streams and of
-the decoded images must agree.
+the decoded images must agree.  --variants narrows the variants, --calls the timed calls (the encodes still run once: the decodes need
+their streams).
   this        libcniic_hip_testing.so of this tree
   route_off   the same library under CNIIC_TEST_HUF_SMALL_OFF=1 and CNIIC_TEST_HUF_SMALL_DEC_OFF=1
+  parse_off   the same library under CNIIC_TEST_HUF_SMALL_DEC_PARSE_OFF=1: the decoders of device streams parsed on the host, as before
+              k_small_trieparse_rgb
   other       --against FILE: another build in cniic_amd/ (CNIIC_LIB_FILE), e.g. the parent commit's library -- the yardstick
 A fourth child runs `this` with the stage timers on and records the durations of k_huf_small ("huf_small_batch"), the placing copy
-("huf_small_place") and k_huf_small_dec ("huf_small_dec_batch", of the `hufman` streams and of the cluster-colors ones).  --sizes /
---frames / --kinds narrow the sweep."""
+("huf_small_place"), k_huf_small_dec ("huf_small_dec_batch", of the `hufman` streams and of the cluster-colors ones) and, beside it,
+k_small_trieparse_rgb ("huf_small_dec_parse": the launches' time and the frames parsed; "huf_small_dec_parse_host": the candidates handed
+back).  --sizes / --frames / --kinds narrow the sweep."""
 import argparse
 import hashlib
 import json
@@ -28,8 +32,9 @@ sys.path.insert(0, ROOT)
 SIZES = ((32, 32), (64, 64), (128, 96), (128, 128), (16384, 1))
 FRAMES = (1, 8, 256, 4096)
 KINDS = ("photo", "uniform")
-STAGES = ("huf_small_batch", "huf_small_place", "huf_small_dec_batch")
+STAGES = ("huf_small_batch", "huf_small_place", "huf_small_dec_batch", "huf_small_dec_parse", "huf_small_dec_parse_host")
 OFF = ("CNIIC_TEST_HUF_SMALL_OFF", "CNIIC_TEST_HUF_SMALL_DEC_OFF")
+PARSE_OFF = "CNIIC_TEST_HUF_SMALL_DEC_PARSE_OFF"
 CALLS = ("encode", "decode", "decode_cc", "measure")
 CC = "cluster-colors(256)"
 
@@ -86,13 +91,19 @@ def child(a):
                     calls[which]()
                     for s in STAGES:
                         ms, cnt = ctx.kernel_time(s)
-                        if cnt:
+                        if cnt or ms:
                             got[s + ("_cc" if which == "decode_cc" else "")] = dict(ms=round(ms, 3), launches=cnt)
                     ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
                 out[name] = got
                 continue
             row = {}
+            timed = a.calls.split(",") if a.calls else CALLS
             for which in CALLS:
+                if which not in timed:
+                    if which == "encode":
+                        encode()
+                    row[which] = []
+                    continue
                 for _ in range(a.warmup):
                     calls[which]()
                 ts = []
@@ -107,12 +118,13 @@ def child(a):
             host, img, cc_img = enc.cpu().numpy(), back.cpu().numpy(), cc_back.cpu().numpy()
             dg = hashlib.sha256()
             for f in range(F):
-                dg.update(bytes([rcs[f] & 255, res["d"][3][f] & 255, res["dc"][3][f] & 255]))
+                dg.update(bytes([rcs[f] & 255] + [res[c][3][f] & 255 for c in ("d", "dc") if c in res]))
                 dg.update(host[f * stride:f * stride + (lens[f] if rcs[f] == 0 else 0)].tobytes())
                 dg.update(img[f * nb:(f + 1) * nb].tobytes())
                 if cc_lens[f]:
                     dg.update(cc_img[f * nb:(f + 1) * nb].tobytes())
-                dg.update(repr((res["m"][1][f]["compressed_size"], res["m"][1][f]["error"])).encode())
+                if "m" in res:
+                    dg.update(repr((res["m"][1][f]["compressed_size"], res["m"][1][f]["error"])).encode())
             out[name] = dict(ms=row, digest=dg.hexdigest()[:16], failed=sum(r != 0 for r in rcs), cc_streams=sum(1 for l in cc_lens if l))
             print("[probe child] %s" % name, file=sys.stderr, flush=True)
             del src, enc, back, cc_enc, cc_back
@@ -129,22 +141,27 @@ def main():
     ap.add_argument("--sizes")
     ap.add_argument("--frames")
     ap.add_argument("--kinds")
+    ap.add_argument("--calls", help="the calls to time, of encode,decode,decode_cc,measure")
+    ap.add_argument("--variants", help="of this,route_off,parse_off,other (this is always run)")
     ap.add_argument("--timeout", type=int, default=1100)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--stages", action="store_true")
     a = ap.parse_args()
     if a.child:
         return child(a)
-    variants = [("this", {"CNIIC_USE_TESTING_LIB": "1"}), ("route_off", dict({"CNIIC_USE_TESTING_LIB": "1"}, **{k: "1" for k in OFF}))]
+    variants = [("this", {"CNIIC_USE_TESTING_LIB": "1"}), ("route_off", dict({"CNIIC_USE_TESTING_LIB": "1"}, **{k: "1" for k in OFF})),
+                ("parse_off", {"CNIIC_USE_TESTING_LIB": "1", PARSE_OFF: "1"})]
     if a.against:
         variants.append(("other", {"CNIIC_LIB_FILE": a.against}))
+    if a.variants:
+        variants = [v for v in variants if v[0] == "this" or v[0] in a.variants.split(",")]
     base = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup)]
-    for k in ("sizes", "frames", "kinds"):
+    for k in ("sizes", "frames", "kinds", "calls"):
         if getattr(a, k):
             base += ["--" + k, getattr(a, k)]
 
     def run(env_add, extra=()):
-        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB") + OFF}
+        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", PARSE_OFF) + OFF}
         env.update(env_add)
         r = subprocess.run(base + list(extra), stdout=subprocess.PIPE, text=True, timeout=a.timeout, env=env)   # (a child's progress lines go to stderr as they come)
         if r.returncode != 0:
@@ -162,23 +179,27 @@ def main():
                 assert e["digest"] == v["digest"], (who, k)
     stages = run(variants[0][1], ("--stages",))
 
-    # a row per case, on one line: per call the [median, min, max] ms of this build and of `other`, the median of route_off, x = the
-    # other's median over this build's, slower = this build's median exceeds the other's by more than the two min - max spreads together
+    # a row per case, on one line: per call the [median, min, max] ms of this build and of `other`, the medians of route_off and parse_off,
+    # x = the other's median over this build's, slower / faster = this build's median exceeds / beats the other's by more than the two
+    # min - max spreads together
     def tri(ts):
-        return [round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)]
+        return [round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)] if ts else None
     rows = []
     for k, v in got["this"].items():
         row = dict(case=k, failed_frames=v["failed"], cc_streams=v["cc_streams"], stages={s: [t["ms"], t["launches"]] for s, t in (stages.get(k) or {}).items()})
         for c in CALLS:
+            if not v["ms"][c]:
+                continue
             cell = dict(this=tri(v["ms"][c]))
-            if "route_off" in got:
-                cell["route_off"] = tri(got["route_off"][k]["ms"][c])[0]
+            for who in ("route_off", "parse_off"):
+                if who in got:
+                    cell[who] = tri(got[who][k]["ms"][c])[0]
             if "other" in got:
                 o = tri(got["other"][k]["ms"][c])
                 sp = (cell["this"][2] - cell["this"][1]) + (o[2] - o[1])
-                cell.update(other=o, x=round(o[0] / cell["this"][0], 3), slower=bool(o[0] + sp < cell["this"][0]))
+                cell.update(other=o, x=round(o[0] / cell["this"][0], 3), slower=bool(o[0] + sp < cell["this"][0]), faster=bool(cell["this"][0] + sp < o[0]))
             row[c] = cell
-        row["same"] = all(got[who][k]["digest"] == v["digest"] for who in ("route_off", "other") if who in got)
+        row["same"] = all(got[who][k]["digest"] == v["digest"] for who in ("route_off", "parse_off", "other") if who in got)
         print(json.dumps(row), flush=True)
         rows.append(row)
     if a.out:
