@@ -25,6 +25,7 @@
 #include <memory>
 
 #include "huff_host.hpp"
+#include "kmeans_rgbw.hpp"
 #include "pal_bounds.hpp"
 
 namespace cniic {
@@ -478,18 +479,24 @@ int cc_prepare_image(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t K, con
     if (K == 0) return c->fail(CNIIC_ERR_BAD_ARG, "cluster-colors(0)");
     auto s = std::make_unique<CcSession>();
     s->c = c; s->K = K; s->sp_mode = true;
-    CNIIC_TRY(sp_build(c, rgb_d, npx, &s->sp));   // count_freqs (clusterc.rs:21): distinct colours per cell, occupancy bitmap
+    CNIIC_TRY(sp_build(c, rgb_d, npx, &s->sp, true));   // count_freqs (clusterc.rs:21): distinct colours per cell, occupancy bitmap (its prefix: below)
     // kmeans::cluster (clusterc.rs:28): the point list is known as the bitmap and its cell-major copy is written below.
     // The number of distinct colours is still on the device: the state is sized for the most there can be, its
     // set-up kernels read the count there, and the host only waits for it after all of them are enqueued.
+    // The state enqueues nothing itself: what it would, the rest of sp_build and the emit into its arrays are three launches (sp_front).
     const uint64_t Umax = std::min<uint64_t>(npx, 1ull << 24);
     const uint64_t *U_dev = s->sp.total.as<uint64_t>();
-    CNIIC_TRY(km_rgbw_create(c, nullptr, nullptr, Umax, 0, 1, K, opts, nullptr, nullptr, &s->km, s->sp.cell_count.as<uint32_t>(), s->sp.bits.p,
-                             s->sp.wprefix.as<uint32_t>(), Umax, true, U_dev));
+    KmFront front;
+    CNIIC_TRY(km_rgbw_create_deferred(c, Umax, K, opts, &s->km, s->sp.cell_count.as<uint32_t>(), s->sp.bits.p, s->sp.wprefix.as<uint32_t>(), Umax, U_dev, &front));
     uint32_t *cell_start, *ckeys, *cweight;
     km_rgbw_cell_arrays(s->km, &cell_start, &ckeys, &cweight);
-    CNIIC_TRY(sp_emit(c, &s->sp, cell_start, ckeys, cweight, km_rgbw_labels_internal(s->km, nullptr), km_rgbw_is_wide(s->km), K, s->sp.bits.p,
-                      s->sp.wprefix.as<uint32_t>(), 0, U_dev));
+    // (tests: CNIIC_TEST_CC_FRONT=split enqueues the dispatches one by one; =require makes a silent fall-back to them an error)
+    bool fused = sp_front_fits(front);
+    if (const char *e = test_env("CNIIC_TEST_CC_FRONT")) {
+        if (!fused && !strcmp(e, "require")) return c->fail(CNIIC_ERR_HIP, "cluster-colors: the fused set-up launches cannot clear the K-means arenas (CNIIC_TEST_CC_FRONT=require)");
+        fused = fused && strcmp(e, "split") != 0;
+    }
+    CNIIC_TRY(sp_front(c, &s->sp, front, ckeys, cweight, km_rgbw_labels_internal(s->km, nullptr), km_rgbw_is_wide(s->km), fused));
     CNIIC_TRY(sp_wait_count(c, &s->sp));
     s->U = s->sp.U;
     if (s->U / K == 0)

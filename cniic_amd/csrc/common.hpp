@@ -589,7 +589,11 @@ struct SpPlan {
     DevBuf bits, wprefix;        // occupancy bitmap of the 2^24 colours + popcount prefix (GIdx)
     DevBuf total;                // u64 on the device: distinct colours (the kernels of the set-up read it there)
 };
-int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan);  // asynchronous: the count arrives with sp_wait_count
+int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan, bool hist_only = false);  // asynchronous: the count arrives with sp_wait_count
+struct KmFront;  // kmeans_rgbw.hpp: the K-means' set-up dispatches, left to the caller
+// behind sp_build(hist_only): the rest of it, the K-means' set-up and the emit, in three launches (fused) or as ever
+int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide, bool fused);
+bool sp_front_fits(const KmFront &f);
 int sp_wait_count(Ctx *c, SpPlan *plan);                                  // plan->U on the host (waits for its copy only)
 // distinct colours, counts, initial labels -> the K-means state's cell-major arrays; (gbits, gprefix, Ug): index of the point list
 int sp_emit(Ctx *c, const SpPlan *plan, const uint32_t *cell_start_d, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide,

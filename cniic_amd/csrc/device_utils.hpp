@@ -277,6 +277,31 @@ __device__ __forceinline__ uint32_t gidx_select(const GIdx &g, uint64_t idx) {
     for (uint32_t r = (uint32_t)(idx - g.wprefix[a]); r; r--) word &= word - 1;
     return (a << 6) | (uint32_t)(__ffsll((long long)word) - 1);
 }
+// The prefix in its two steps, each the work of block `blk` of 256 blocks of 256 threads (k_bits_prefix: k_points.hip, k_gidx_finish:
+// k_hist.hip, and as roles of k_cc_front_a / k_cc_front_b: k_points.hip).  wsum u32[4], boff u32[256]: LDS
+// bits (u64[2^18]) -> wprefix inside blocks of 1024 words + blocktot
+__device__ __forceinline__ void bits_prefix_body(uint32_t blk, const unsigned long long *__restrict__ bits, uint32_t *__restrict__ wprefix,
+                                                 uint32_t *__restrict__ blocktot, uint32_t *wsum) {
+    const uint32_t w0 = (blk * 256 + threadIdx.x) * 4;
+    uint32_t cnt[4], mine = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) { cnt[q] = (uint32_t)__popcll(bits[w0 + q]); mine += cnt[q]; }
+    uint32_t run = block_exclusive_scan<256>(mine, wsum);
+#pragma unroll
+    for (int q = 0; q < 4; q++) { wprefix[w0 + q] = run; run += cnt[q]; }
+    if (threadIdx.x == 255) blocktot[blk] = run;
+}
+// every block's words get the occupied keys of the blocks before; *total = all of them
+__device__ __forceinline__ void gidx_finish_body(uint32_t blk, uint32_t *__restrict__ wprefix, const uint32_t *__restrict__ blocktot,
+                                                 uint64_t *__restrict__ total, uint32_t *wsum, uint32_t *boff) {
+    const uint32_t t = blocktot[threadIdx.x];
+    const uint32_t ex = block_exclusive_scan<256>(t, wsum);
+    boff[threadIdx.x] = ex;
+    if (blk == 0 && threadIdx.x == 255) *total = (uint64_t)ex + t;
+    __syncthreads();
+    const uint32_t add = boff[blk];
+    for (uint32_t i = threadIdx.x; i < 1024; i += 256) wprefix[blk * 1024 + i] += add;
+}
 
 __host__ __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;

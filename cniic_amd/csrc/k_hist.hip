@@ -411,13 +411,7 @@ __global__ __launch_bounds__(256) void k_gidx_finish(uint32_t *__restrict__ wpre
                                                      uint64_t *__restrict__ total) {
     __shared__ uint32_t wsum[256 / 64];
     __shared__ uint32_t boff[256];
-    const uint32_t t = blocktot[threadIdx.x];
-    const uint32_t ex = block_exclusive_scan<256>(t, wsum);
-    boff[threadIdx.x] = ex;
-    if (blockIdx.x == 0 && threadIdx.x == 255) *total = (uint64_t)ex + t;
-    __syncthreads();
-    const uint32_t add = boff[blockIdx.x];
-    for (uint32_t i = threadIdx.x; i < 1024; i += 256) wprefix[blockIdx.x * 1024 + i] += add;
+    gidx_finish_body(blockIdx.x, wprefix, blocktot, total, wsum, boff);   // (device_utils.hpp)
 }
 
 int gidx_finish(Ctx *c, uint32_t *wprefix_d, const uint32_t *blocktot_d, uint64_t *total_d) {

@@ -91,43 +91,7 @@ __device__ __forceinline__ bool ps_barrier_xcd(PsBar *b, uint32_t x, uint32_t nx
 // It also leaves the launch its set-up's pointers (PsDev, kmeans_rgbw.hpp): in device memory, so that no block reads them over the bus.
 __global__ __launch_bounds__(1024) void k_ps_ranges(const uint32_t *__restrict__ ne_cost, const uint32_t *__restrict__ ne_count, uint32_t G, uint32_t dyn_bytes,
                                                     uint32_t *__restrict__ cb, PsDev *__restrict__ dev, PsDevPtrs ptrs) {
-    uint32_t *fail = &dev->fail;
-    if (threadIdx.x == 0) dev->p = ptrs;
-    const uint32_t M = *ne_count, NC = G * kPsChunks;
-    const uint64_t total = ne_cost[M];
-    // (a thread's boundaries searched TOGETHER, eight at a time: one after the other the 4097 bisections of the headline image were 60
-    // dependent reads a thread, 21 us in front of the launch)
-    for (uint32_t g0 = threadIdx.x; g0 <= NC; g0 += 8 * blockDim.x) {
-        uint32_t a[8], b[8];
-        uint64_t c_lo[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint32_t g = g0 + r * blockDim.x;
-            c_lo[r] = total * min(g, NC) / NC;
-            a[r] = 0; b[r] = g <= NC ? M : 0u;   // first cell whose cost prefix is >= c_lo
-        }
-        bool more = true;
-        while (more) {
-            more = false;
-            uint32_t mid[8], v[8];
-#pragma unroll
-            for (int r = 0; r < 8; r++) { mid[r] = (a[r] + b[r]) >> 1; v[r] = a[r] < b[r] ? ne_cost[mid[r]] : 0u; }
-#pragma unroll
-            for (int r = 0; r < 8; r++)
-                if (a[r] < b[r]) { if (v[r] < c_lo[r]) a[r] = mid[r] + 1; else b[r] = mid[r]; more = more || a[r] < b[r]; }
-        }
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint32_t g = g0 + r * blockDim.x;
-            if (g <= NC) cb[g] = g == NC ? M : a[r];
-        }
-    }
-    __syncthreads();   // (one block: its own stores are visible to it behind the barrier)
-    for (uint32_t g = threadIdx.x; g < G; g += blockDim.x) {
-        uint32_t C = 0;
-        for (uint32_t r = 0; r < kPsChunks; r++) C += cb[r * G + g + 1] - cb[r * G + g];
-        if (C > kPsMaxCells || kPsOffCell + ps_cell_bytes(C) > dyn_bytes) atomicAdd(fail, 1u);
-    }
+    ps_ranges_body(ne_cost, ne_count, G, dyn_bytes, cb, dev, ptrs);   // (kmeans_rgbw.hpp)
 }
 
 // ---- reductions inside a ROW of 16 lanes (a DPP row: rotations stay inside it), the result in every lane of the row
@@ -1023,7 +987,7 @@ uint32_t ps_grid_for(Ctx *c, uint64_t Umax) {
     return std::min<uint32_t>(G, 1024u);
 }
 
-// the set-up the persistent launch needs beyond the classic loop's (km_rgbw_create calls this once the cell list is enqueued)
+// the set-up the persistent launch needs beyond the classic loop's (km_rgbw_create: ps_decide, and ps_enqueue once the cell list is enqueued)
 // a launch that ended: what the context learns from it (a grid that could not get the CUs in time costs seconds: do not try again at once)
 static void ps_learn(Ctx *c, uint32_t status, bool injected) {
     if (status == kPsStatusDone) { c->ps_backoff = 0; c->ps_backoff_left = 0; return; }
@@ -1032,8 +996,11 @@ static void ps_learn(Ctx *c, uint32_t status, bool injected) {
     c->ps_backoff_left = c->ps_backoff;
 }
 
-int ps_prepare(KmRgbwState *s) {
+// in two steps: ps_decide says whether there is a persistent launch and allocates what it needs; ps_enqueue is the fill of the arena's head
+// and k_ps_ranges (the large cluster-colors encode enqueues both as roles of its own set-up launches instead: KmFront, k_points.hip)
+int ps_decide(KmRgbwState *s, PsSetup *out) {
     Ctx *c = s->c;
+    *out = PsSetup{};
     if (c->ps_backoff_left && !test_env("CNIIC_KM_PS_REQUIRE")) { c->ps_backoff_left--; return CNIIC_OK; }   // (see ps_learn: the launches meanwhile; the tests' REQUIRE always tries)
     const uint32_t G = ps_grid_for(c, s->U);
     if (!G) return CNIIC_OK;   // (no device properties: the classic loop)
@@ -1044,7 +1011,6 @@ int ps_prepare(KmRgbwState *s) {
     }
     const uint64_t o_part = kPsArenaPart, o_fail = kPsArenaFail, o_rng = kPsArenaRng, total = o_rng + ((uint64_t)G * kPsChunks + 1) * 4;
     CNIIC_HIP_TRY(c, s->ps_arena.alloc(total));
-    CNIIC_HIP_TRY(c, hipMemsetAsync(s->ps_arena.p, 0, o_rng, c->stream));
     CNIIC_HIP_TRY(c, s->ps_pk.alloc(std::max<uint64_t>(s->U, 1) * 4));
     s->ps_blocks = G;
     s->ps_o_part = o_part; s->ps_o_fail = o_fail; s->ps_o_rng = o_rng;
@@ -1055,10 +1021,20 @@ int ps_prepare(KmRgbwState *s) {
     PsDevPtrs ptrs{};
     ptrs.ckeys = s->ckeys.as<uint32_t>(); ptrs.cweight = s->cweight.as<uint32_t>(); ptrs.labels = s->labels.as<uint8_t>();
     ptrs.ne_cell = s->ne_cell.as<uint32_t>(); ptrs.ne_start = s->ne_start.as<uint32_t>(); ptrs.cconst0 = s->cconst.as<uint2>();
-    hipLaunchKernelGGL(k_ps_ranges, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)s->ne_cost.as<uint32_t>(), (const uint32_t *)s->ne_count.as<uint32_t>(), G, budget,
-                       reinterpret_cast<uint32_t *>(a + o_rng), reinterpret_cast<PsDev *>(a + o_fail), ptrs);
-    CNIIC_HIP_TRY(c, hipGetLastError());
+    out->on = true; out->G = G; out->budget = budget; out->ptrs = ptrs;
+    out->cb = reinterpret_cast<uint32_t *>(a + o_rng); out->dev = reinterpret_cast<PsDev *>(a + o_fail);
+    out->zero_p = a; out->zero_bytes = o_rng;
     s->ps = true;
+    return CNIIC_OK;
+}
+void ps_launch_ranges(Ctx *c, const uint32_t *ne_cost, const uint32_t *ne_count, uint32_t G, uint32_t budget, uint32_t *cb, PsDev *dev, const PsDevPtrs &ptrs) {
+    hipLaunchKernelGGL(k_ps_ranges, dim3(1), dim3(1024), 0, c->stream, ne_cost, ne_count, G, budget, cb, dev, ptrs);
+}
+int ps_enqueue(KmRgbwState *s, const PsSetup &p) {
+    Ctx *c = s->c;
+    CNIIC_HIP_TRY(c, hipMemsetAsync(p.zero_p, 0, p.zero_bytes, c->stream));
+    ps_launch_ranges(c, s->ne_cost.as<uint32_t>(), s->ne_count.as<uint32_t>(), p.G, p.budget, p.cb, p.dev, p.ptrs);
+    CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }
 
@@ -1083,7 +1059,7 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     a.cweight = s->cweight.as<uint32_t>();
     a.lds_budget = s->ps_budget;
     a.pk = s->ps_pk.as<uint32_t>();
-    a.bar = reinterpret_cast<PsBar *>(ar);   // (the sums, PsDev and the chunk boundaries behind it: ps_prepare)
+    a.bar = reinterpret_cast<PsBar *>(ar);   // (the sums, PsDev and the chunk boundaries behind it: ps_decide)
     cold->cconst_g = s->cconst.as<uint2>(); cold->cent_g = s->cent.as<uint32_t>(); cold->members_out = s->members_last.as<uint64_t>(); cold->wsum_out = s->wsum_last.as<uint64_t>();
     cold->keys = s->keys; cold->gx = s->gidx; cold->seed = s->seed; cold->U = s->gidx.bits ? s->gidx.U : s->U;
     a.st_rw = s->dstate.as<KmDevState>(); a.cold = cold; a.max_iters = s->max_iters;

@@ -50,20 +50,7 @@ namespace cniic {
 __global__ void k_rgbw_init_cent(const uint32_t *__restrict__ keys, uint64_t U, uint32_t K, uint32_t Kpad, uint32_t idbits,
                                  uint2 *__restrict__ cconst, uint32_t *__restrict__ cent, GIdx gx, uint32_t *__restrict__ cent_copy,
                                  uint32_t *__restrict__ moved_list, const uint64_t *__restrict__ U_dev) {
-    uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (U_dev) U = max(*U_dev, (uint64_t)K);  // the count is still on its way to the host (fewer points than clusters: refused there)
-    if (k == 0 && moved_list) moved_list[0] = K;  // before the first update every centroid counts as moved
-    if (k < K) {
-        // init_centroids (kmeans.rs:101-108): first element of chunk k
-        uint64_t ppc = U / K;
-        uint64_t first = (k < K - 1) ? U - ((uint64_t)k + 1) * ppc : 0;
-        uint32_t ck = gx.bits ? gidx_select(gx, first) : keys[first];
-        cent[k] = ck;
-        if (cent_copy) cent_copy[k] = ck;
-        cconst[k] = make_cconst(ck, k, idbits);
-    } else if (k < Kpad) {
-        cconst[k] = make_uint2(0u, 0u);  // padding: key 0 never wins
-    }
+    rgbw_init_cent_body(blockIdx.x * blockDim.x + threadIdx.x, keys, U, K, Kpad, idbits, cconst, cent, gx, cent_copy, moved_list, U_dev);   // (kmeans_rgbw.hpp)
 }
 
 // The same from K centroids the caller gives (km_rgbw_set_centroids: cniic_kmeans_rgbw_from, cniic_cc_set_centroids), enqueued behind the kernel
@@ -214,40 +201,16 @@ __global__ __launch_bounds__(256) void k_cell_count(const uint32_t *__restrict__
 // ne_start[M] = U, *ne_count = M.  Blocks walk the compacted list, never the empty cells.
 // Two launches of kNumCells / 64 one-wave blocks (a single 1024-thread block took 57 us: ~10^5 scattered store
 // requests from one CU): per 64 cells (points, non-empty cells), then every wave adds up the groups before its own.
-constexpr uint32_t kCellGroups = kNumCells / 64;
-// (tot[kCellGroups + g]: the group's sweeps, ceil(points / 256) per cell -- the full schedule's cost model counts them)
+// (the bodies: kmeans_rgbw.hpp)
 __global__ __launch_bounds__(64) void k_cell_totals(const uint32_t *__restrict__ cell_count, uint2 *__restrict__ tot) {
-    const uint32_t v = cell_count[blockIdx.x * 64 + threadIdx.x];
-    const uint32_t sum = wave_reduce_sum(v), sweeps = wave_reduce_sum((v + 64 * kSweep - 1) / (64 * kSweep));
-    const uint32_t ne = (uint32_t)__popcll(__ballot(v != 0));
-    if (threadIdx.x == 0) { tot[blockIdx.x] = make_uint2(sum, ne); tot[kCellGroups + blockIdx.x] = make_uint2(sweeps, 0u); }
+    cell_totals_body(blockIdx.x, threadIdx.x, cell_count, tot);
 }
 __global__ __launch_bounds__(64) void k_cell_scan(const uint32_t *__restrict__ cell_count, const uint2 *__restrict__ tot,
                                                   uint32_t *__restrict__ cell_start, uint32_t *__restrict__ cursor,
                                                   uint32_t *__restrict__ ne_cell, uint32_t *__restrict__ ne_start,
                                                   uint32_t *__restrict__ ne_cost, uint32_t *__restrict__ ne_count, uint32_t fixed_cost,
                                                   uint32_t sweep_cost) {
-    // cost of a cell in the full schedule's split: fixed_cost + points if sweep_cost == 0, else fixed_cost + sweep_cost * sweeps
-    const uint32_t lane = threadIdx.x, grp = blockIdx.x;
-    uint32_t ps = 0, pn = 0, pw = 0;
-    for (uint32_t g = lane; g < grp; g += 64) { const uint2 t = tot[g]; ps += t.x; pn += t.y; pw += tot[kCellGroups + g].x; }
-    const uint32_t base = wave_reduce_sum(ps), nbase = wave_reduce_sum(pn), wbase = wave_reduce_sum(pw);
-    const uint32_t cell = grp * 64 + lane, v = cell_count[cell], sw = (v + 64 * kSweep - 1) / (64 * kSweep);
-    const uint32_t start = base + wave_inclusive_scan(v) - v, swb = wbase + wave_inclusive_scan(sw) - sw;
-    cell_start[cell] = start;
-    if (cursor) cursor[cell] = start;
-    const unsigned long long nzm = __ballot(v != 0);
-    if (v) {
-        const uint32_t m = nbase + (uint32_t)__popcll(nzm & ((1ull << lane) - 1ull));
-        ne_cell[m] = cell; ne_start[m] = start; ne_cost[m] = (sweep_cost ? swb * sweep_cost : start) + m * fixed_cost;
-    }
-    if (grp == kCellGroups - 1 && lane == 63) {
-        const uint32_t U = start + v, M = nbase + (uint32_t)__popcll(nzm);
-        cell_start[kNumCells] = U;
-        ne_start[M] = U;
-        ne_cost[M] = (sweep_cost ? (swb + sw) * sweep_cost : U) + M * fixed_cost;
-        *ne_count = M;
-    }
+    cell_scan_body(blockIdx.x, threadIdx.x, cell_count, tot, CellScanOut{cell_start, cursor, ne_cell, ne_start, ne_cost, ne_count}, fixed_cost, sweep_cost);
 }
 
 // ---- cell-major order straight from the dense colour table (codec path).  After the canonical
@@ -1279,11 +1242,13 @@ static inline uint32_t grid_1d(uint64_t n, uint32_t cap = 2048) {
                                                         (unsigned long long)(bytes), hipGetErrorString(_e)); } \
     } while (0)
 
-int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uint64_t U, uint32_t shard,
-                   uint32_t nshards, uint32_t K, const cniic_kmeans_opts *opts, void *partials_dev,
-                   const uint32_t *rank_table_d, KmRgbwState **out, const uint32_t *cell_count_d, const void *gbits_d,
-                   const uint32_t *gprefix_d, uint64_t Ug, bool points_follow, const uint64_t *points_dev) {
+// front (points_follow only): the set-up dispatches are not enqueued but described there (KmFront, kmeans_rgbw.hpp)
+static int km_create_impl(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uint64_t U, uint32_t shard,
+                          uint32_t nshards, uint32_t K, const cniic_kmeans_opts *opts, void *partials_dev,
+                          const uint32_t *rank_table_d, KmRgbwState **out, const uint32_t *cell_count_d, const void *gbits_d,
+                          const uint32_t *gprefix_d, uint64_t Ug, bool points_follow, const uint64_t *points_dev, KmFront *front) {
     if (K == 0 || U == 0 || nshards == 0 || shard >= nshards) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: bad sizes");
+    if (front && (!points_follow || partials_dev)) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: only the set-up of points written by the caller can be left to it");
     if (points_follow && (!gbits_d || !cell_count_d || nshards != 1 || (opts && (opts->flags & CNIIC_KM_BRUTE_FORCE))))
         return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: points written by the caller need the cell counts and the colour index");
     if (!points_follow && gbits_d && (!rank_table_d || nshards != 1 || (opts && (opts->flags & CNIIC_KM_BRUTE_FORCE))))
@@ -1331,7 +1296,8 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
         const uint64_t o_fr = o_fp + up(s->fused ? 3 * W * 8 : 0), o_fc = o_fr + up(s->fused ? 2 * W * 8 : 0);
         const uint64_t o_mv = o_fc + up(s->fused ? 2 * (uint64_t)K * 4 : 0), total = o_mv + up(s->cells ? ((uint64_t)K + 1) * 4 : 0);
         KM_ALLOC(s->arena, total);
-        (void)hipMemsetAsync(s->arena.p, 0, total, c->stream);
+        if (front) { front->arena = s->arena.p; front->arena_bytes = total; }
+        else (void)hipMemsetAsync(s->arena.p, 0, total, c->stream);
         uint8_t *a = s->arena.as<uint8_t>();
         s->resblk.view(a, s->res_bytes);
         if (partials_dev) {
@@ -1355,9 +1321,16 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
     s->cent.view(static_cast<uint8_t *>(s->resblk.p) + s->res_cent, (uint64_t)K * 4);
     s->members_last.view(static_cast<uint8_t *>(s->resblk.p) + s->res_members, (uint64_t)K * 8);
     s->wsum_last.view(static_cast<uint8_t *>(s->resblk.p) + s->res_wsum, (uint64_t)K * 8);
-    hipLaunchKernelGGL(k_rgbw_init_cent, dim3(ceil_div(s->Kpad, 256)), dim3(256), 0, c->stream, keys_d, Ulist, K, s->Kpad, s->idbits,
-                       s->cconst.as<uint2>(), s->cent.as<uint32_t>(), s->gidx, s->fused ? s->fused_cent.as<uint32_t>() : (uint32_t *)nullptr,
-                       s->cells ? s->moved_list.as<uint32_t>() : (uint32_t *)nullptr, points_dev);
+    if (front) {
+        front->Ulist = Ulist; front->K = K; front->Kpad = s->Kpad; front->idbits = s->idbits;
+        front->cconst = s->cconst.as<uint2>(); front->cent = s->cent.as<uint32_t>(); front->gx = s->gidx;
+        front->cent_copy = s->fused ? s->fused_cent.as<uint32_t>() : nullptr;
+        front->moved_list = s->moved_list.as<uint32_t>(); front->U_dev = points_dev;
+    } else {
+        hipLaunchKernelGGL(k_rgbw_init_cent, dim3(ceil_div(s->Kpad, 256)), dim3(256), 0, c->stream, keys_d, Ulist, K, s->Kpad, s->idbits,
+                           s->cconst.as<uint2>(), s->cent.as<uint32_t>(), s->gidx, s->fused ? s->fused_cent.as<uint32_t>() : (uint32_t *)nullptr,
+                           s->cells ? s->moved_list.as<uint32_t>() : (uint32_t *)nullptr, points_dev);
+    }
     if (s->cells) {
         // cell-major copy of the whole point list (every rank keeps all U points and works on [lo,hi))
         s->nblocks = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ceil_div(U / nshards, s->wide ? 1024 : 64), 1), s->wide ? 4096u : kCellBlocks);  // same on every shard
@@ -1383,7 +1356,12 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
         DevBuf count, cursor, cell_tot;
         KM_ALLOC(count, (uint64_t)kNumCells * 4);
         KM_ALLOC(cell_tot, (uint64_t)kCellGroups * 8 * 2);
-        if (points_follow) {
+        if (front) {
+            front->cell_count = cell_count_d;
+            front->cell_tot = std::move(cell_tot);   // (stays the caller's until its dispatches are enqueued: the pool hands memory out again in stream order)
+            front->scan = CellScanOut{s->cell_start.as<uint32_t>(), nullptr, s->ne_cell.as<uint32_t>(), s->ne_start.as<uint32_t>(), s->ne_cost.as<uint32_t>(),
+                                      s->ne_count.as<uint32_t>()};
+        } else if (points_follow) {
             // the caller's partition (k_points.hip) writes ckeys / cweight / labels itself, from cell_start
             hipLaunchKernelGGL(k_cell_totals, dim3(kCellGroups), dim3(64), 0, c->stream, cell_count_d, cell_tot.as<uint2>());
             hipLaunchKernelGGL(k_cell_scan, dim3(kCellGroups), dim3(64), 0, c->stream, cell_count_d, (const uint2 *)cell_tot.as<uint2>(), s->cell_start.as<uint32_t>(),
@@ -1433,7 +1411,16 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
         // (not for the worker contexts of a batch encode: eight persistent launches side by side each hold an eighth of the CUs for a
         // whole run while the other stages of their neighbours' encodes wait for a CU -- 2.6 ms a frame against 0.67 with launches)
         if (s->fused && nshards == 1 && c->ps_div <= 1 && c->opt(CNIIC_OPT_KM_LOOP, "CNIIC_KM_LOOP", 0) == 0) {
-            const int rc_ps = ps_prepare(s);
+            PsSetup ps;
+            int rc_ps = ps_decide(s, &ps);
+            if (rc_ps == CNIIC_OK && ps.on) {
+                if (front) {
+                    front->ranges = true; front->G = ps.G; front->budget = ps.budget; front->cb = ps.cb; front->dev = ps.dev; front->ptrs = ps.ptrs;
+                    front->ps_arena = ps.zero_p; front->ps_zero_bytes = ps.zero_bytes;
+                } else {
+                    rc_ps = ps_enqueue(s, ps);
+                }
+            }
             if (rc_ps != CNIIC_OK) { delete s; return rc_ps; }
         }
         // (count / cursor go back to the context's pool here; it hands them out again in stream order)
@@ -1456,6 +1443,37 @@ int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uin
     return CNIIC_OK;
 }
 
+int km_rgbw_create(Ctx *c, const uint32_t *keys_d, const uint32_t *weight_d, uint64_t U, uint32_t shard,
+                   uint32_t nshards, uint32_t K, const cniic_kmeans_opts *opts, void *partials_dev,
+                   const uint32_t *rank_table_d, KmRgbwState **out, const uint32_t *cell_count_d, const void *gbits_d,
+                   const uint32_t *gprefix_d, uint64_t Ug, bool points_follow, const uint64_t *points_dev) {
+    return km_create_impl(c, keys_d, weight_d, U, shard, nshards, K, opts, partials_dev, rank_table_d, out, cell_count_d, gbits_d, gprefix_d, Ug,
+                          points_follow, points_dev, nullptr);
+}
+
+// The points_follow route with its set-up dispatches left to the caller (KmFront, kmeans_rgbw.hpp): the state is allocated and filled
+// in as by km_rgbw_create, nothing is enqueued
+int km_rgbw_create_deferred(Ctx *c, uint64_t Umax, uint32_t K, const cniic_kmeans_opts *opts, KmRgbwState **out, const uint32_t *cell_count_d,
+                            const void *gbits_d, const uint32_t *gprefix_d, uint64_t Ug, const uint64_t *points_dev, KmFront *front) {
+    return km_create_impl(c, nullptr, nullptr, Umax, 0, 1, K, opts, nullptr, nullptr, out, cell_count_d, gbits_d, gprefix_d, Ug, true, points_dev, front);
+}
+
+// ... enqueued as km_rgbw_create enqueues them: the same fills and kernels in the same order
+int km_front_enqueue_split(Ctx *c, const KmFront &f) {
+    CNIIC_HIP_TRY(c, hipMemsetAsync(f.arena, 0, f.arena_bytes, c->stream));
+    hipLaunchKernelGGL(k_rgbw_init_cent, dim3(ceil_div(f.Kpad, 256)), dim3(256), 0, c->stream, (const uint32_t *)nullptr, f.Ulist, f.K, f.Kpad, f.idbits,
+                       f.cconst, f.cent, f.gx, f.cent_copy, f.moved_list, f.U_dev);
+    hipLaunchKernelGGL(k_cell_totals, dim3(kCellGroups), dim3(64), 0, c->stream, f.cell_count, f.cell_tot.as<uint2>());
+    hipLaunchKernelGGL(k_cell_scan, dim3(kCellGroups), dim3(64), 0, c->stream, f.cell_count, (const uint2 *)f.cell_tot.as<uint2>(), f.scan.cell_start,
+                       (uint32_t *)nullptr, f.scan.ne_cell, f.scan.ne_start, f.scan.ne_cost, f.scan.ne_count, kCellFixedCost, kCellSweepCost);
+    if (f.ranges) {
+        CNIIC_HIP_TRY(c, hipMemsetAsync(f.ps_arena, 0, f.ps_zero_bytes, c->stream));
+        ps_launch_ranges(c, f.scan.ne_cost, f.scan.ne_count, f.G, f.budget, f.cb, f.dev, f.ptrs);
+    }
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+
 void km_rgbw_destroy(KmRgbwState *s) { delete s; }
 
 static int launch_update(KmRgbwState *s, int mode) {
@@ -1470,7 +1488,7 @@ static int launch_update(KmRgbwState *s, int mode) {
 }
 
 // K centroids of the caller's (host, K x 3 bytes r, g, b) in the place of init_centroids.  Valid until the first assign of the state, on every
-// route: the launches and the persistent launch read cconst (and cent: k_rgbw_assign_big) when they start, ps_prepare keeps no copy of either.
+// route: the launches and the persistent launch read cconst (and cent: k_rgbw_assign_big) when they start, ps_decide keeps no copy of either.
 int km_rgbw_set_centroids(KmRgbwState *s, const uint8_t *init_h) {
     Ctx *c = s->c;
     if (s->started) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: the centroids can only be given before the first assign");

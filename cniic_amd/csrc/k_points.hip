@@ -10,13 +10,21 @@
 // (512 buckets), staged through LDS so that every global access is a run of consecutive addresses:
 //
 //   k_sp_count     per 64 Ki-pixel chunk: pixels per bucket (LDS histogram)                     read 3 B/px
-//   k_sp_colscan / k_sp_bstart   where each (chunk, bucket) run starts
+//   k_sp_colscan   where each (chunk, bucket) run starts inside its bucket, and the buckets' totals
 //   k_sp_scatter   per chunk: 15-bit colour-in-bucket of every pixel, sorted by bucket in LDS and written as
 //                  512 runs; the pixel's place in the chunk's sorted order goes to prank[pixel]  read 3, write 2 + 2 B/px
+//                  (every block scans the 512 totals for the buckets' first entries; block 0 leaves them as bstart / sstart)
 //   k_sp_hist      per bucket: LDS histogram of its 2^15 colours -> occupied colours per cell, occupancy bitmap,
 //                  and the bucket's distinct colours with their counts, staged in cell-major order
-//   (bitmap -> popcount prefix = GIdx: rank of a colour in the ascending list of all colours = the
-//    reference's point order, used for init_assignment / init_centroids / the reseed index)
+//   Then, a single image (cc_prepare_image: sp_front), three launches whose blocks take a role from blockIdx:
+//   k_cc_front_a   k_bits_prefix | k_cell_totals | the K-means arenas zeroed
+//   k_cc_front_b   k_gidx_finish | k_cell_scan                 (the colour count's 8-byte copy to the host follows)
+//   k_cc_front_c   k_ps_ranges | k_rgbw_init_cent | k_sp_emit
+//   -- the roles being the bodies of these kernels, which every other caller (sp_build without hist_only, the shared palette's
+//   cc_image_create, CNIIC_TEST_CC_FRONT=split) launches one by one:
+//   k_bits_prefix / k_gidx_finish   bitmap -> popcount prefix = GIdx: rank of a colour in the ascending list of all colours = the
+//                  reference's point order, used for init_assignment / init_centroids / the reseed index
+//   (km_rgbw_create: arena fill, k_rgbw_init_cent, k_cell_totals, k_cell_scan, arena fill, k_ps_ranges)
 //   k_sp_emit      the staged colours, counts and their initial labels to their places in the K-means arrays
 //   ... K-means ...
 //   k_sp_partlab   per bucket: label of every partitioned pixel from an LDS table of the bucket's colours
@@ -32,6 +40,7 @@
 // point set, weights, initial labels and cell order are the same.
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "kmeans_rgbw.hpp"
 
 namespace cniic {
 
@@ -107,18 +116,6 @@ __global__ __launch_bounds__(256) void k_sp_colscan(const uint32_t *__restrict__
     if (threadIdx.x == 255) total[b] = run;  // (the last thread's range ends the column, or is empty and holds the sum)
 }
 
-// bstart: first entry of every bucket in the partition; sstart: first slot of its staged distinct colours (a bucket
-// of n pixels has at most min(n, 2^15) of them)
-__global__ __launch_bounds__(kSpBuckets) void k_sp_bstart(const uint32_t *__restrict__ total, uint32_t *__restrict__ bstart,
-                                                          uint32_t *__restrict__ sstart) {
-    __shared__ uint32_t wsum[kSpBuckets / 64];
-    const uint32_t t = total[threadIdx.x];
-    const uint32_t ex = block_exclusive_scan<kSpBuckets>(t, wsum);
-    bstart[threadIdx.x] = ex;
-    if (threadIdx.x == kSpBuckets - 1) bstart[kSpBuckets] = ex + t;
-    sstart[threadIdx.x] = block_exclusive_scan<kSpBuckets>(min(t, kSpBins), wsum);
-}
-
 // The chunk's pixels sorted by bucket occupy positions [0, n) of the LDS stage; off[b] .. off[b + 1] is bucket b's run
 // (off[kSpBuckets] = n).  Wave w walks the positions [w per, (w + 1) per) 64 at a time, lane <-> position, each lane
 // keeping the bucket of its position (runs are short: the bucket advances about every other step).  STEPS positions
@@ -153,15 +150,28 @@ template <int STEPS, typename F> __device__ __forceinline__ void sp_walk_sorted(
 
 // LDS (dynamic): stage u16[kSpChunk] | off u32[kSpBuckets + 1] | cur u32[kSpBuckets]
 __global__ __launch_bounds__(kSpThreads) void k_sp_scatter(const uint8_t *__restrict__ rgb, uint64_t npx, const uint32_t *__restrict__ cnt,
-                                                           const uint32_t *__restrict__ pre, const uint32_t *__restrict__ bstart,
+                                                           const uint32_t *__restrict__ pre, const uint32_t *__restrict__ total,
+                                                           uint32_t *__restrict__ bstart, uint32_t *__restrict__ sstart,
                                                            uint16_t *__restrict__ part, uint16_t *__restrict__ prank) {
     extern __shared__ __align__(16) uint8_t sp_lds[];
     uint16_t *stage = reinterpret_cast<uint16_t *>(sp_lds);
     uint32_t *off = reinterpret_cast<uint32_t *>(sp_lds + (size_t)kSpChunk * 2);  // [kSpBuckets + 1]
     uint32_t *cur = off + kSpBuckets + 1;
     __shared__ uint32_t wsum[kSpWaves];
+    __shared__ uint32_t bfirst[kSpBuckets];
     const uint32_t *mycnt = cnt + (size_t)blockIdx.x * kSpBuckets;
     const uint32_t n_b = threadIdx.x < kSpBuckets ? mycnt[threadIdx.x] : 0u;
+    // bstart: first entry of every bucket in the partition.  Every block scans the 512 totals itself (a one-block kernel between
+    // k_sp_colscan and this one cost a dispatch, 4-5 us, for it); block 0 leaves the result to the kernels behind, with sstart:
+    // first slot of a bucket's staged distinct colours (a bucket of n pixels has at most min(n, 2^15) of them)
+    const uint32_t tot_b = threadIdx.x < kSpBuckets ? total[threadIdx.x] : 0u;
+    const uint32_t first_b = scan512(tot_b, wsum);
+    if (threadIdx.x < kSpBuckets) bfirst[threadIdx.x] = first_b;
+    if (blockIdx.x == 0) {
+        const uint32_t sfirst = scan512(min(tot_b, kSpBins), wsum);
+        if (threadIdx.x < kSpBuckets) { bstart[threadIdx.x] = first_b; sstart[threadIdx.x] = sfirst; }
+        if (threadIdx.x == kSpBuckets - 1) bstart[kSpBuckets] = first_b + tot_b;
+    }
     const uint32_t ex = scan512(n_b, wsum);
     if (threadIdx.x < kSpBuckets) { off[threadIdx.x] = ex; cur[threadIdx.x] = 0; }
     if (threadIdx.x == kSpBuckets - 1) off[kSpBuckets] = ex + n_b;
@@ -193,7 +203,7 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_scatter(const uint8_t *__rest
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t *mypre = pre + (size_t)blockIdx.x * kSpBuckets;
     const uint32_t mb = wv + kSpWaves * (lane & 31);
-    const uint32_t m_n = mycnt[mb], m_dst = bstart[mb] + mypre[mb], m_off = off[mb];
+    const uint32_t m_n = mycnt[mb], m_dst = bfirst[mb] + mypre[mb], m_off = off[mb];
     for (uint32_t k = 0; k < kSpBuckets / kSpWaves; k++) {
         const uint32_t n = __shfl(m_n, k, 64), d0 = __shfl(m_dst, k, 64), o = __shfl(m_off, k, 64);
         for (uint32_t i = lane; i < n; i += 64) part[(size_t)d0 + i] = stage[o + i];
@@ -305,17 +315,18 @@ struct SpEmit {             // where the distinct colours go: the K-means state'
 
 // the staged colours of every bucket -> keys, counts and initial labels at their cell-major positions: a copy, the bucket's
 // place being cell_start of its first cell.  kSpEmitSplit blocks per bucket.
+// Entry i of the bucket is the work of thread i % 1024 of 1024 (`first`: this thread's number among them), four entries a step --
+// whether the 1024 are kSpEmitSplit blocks of 256 (k_sp_emit) or one block (the emit role of k_cc_front_c).
 constexpr uint32_t kSpEmitSplit = 4;
-__global__ __launch_bounds__(256) void k_sp_emit(const uint32_t *__restrict__ sstart, const uint16_t *__restrict__ sbin,
-                                                 const uint32_t *__restrict__ scnt, SpEmit em) {
-    const uint32_t bucket = blockIdx.x / kSpEmitSplit, part_no = blockIdx.x % kSpEmitSplit;
+__device__ __forceinline__ void sp_emit_body(uint32_t bucket, uint32_t first, const uint32_t *__restrict__ sstart, const uint16_t *__restrict__ sbin,
+                                             const uint32_t *__restrict__ scnt, const SpEmit &em) {
     const uint32_t q0 = em.cell_start[bucket * 64], n = em.cell_start[bucket * 64 + 64] - q0, s0 = sstart[bucket];
     const uint32_t U = em.U_dev ? (uint32_t)*em.U_dev : (uint32_t)em.gx.U, ppc = max(U / em.K, 1u);  // (fewer colours than clusters: the host refuses later)
     const float rcp = 1.0f / (float)ppc;
     // four entries per thread and step, each a chain of two loads (the staged colour, then its two index words): the
     // chains travel together
     constexpr uint32_t kStride = 256 * kSpEmitSplit;
-    for (uint32_t i0 = part_no * 256 + threadIdx.x; i0 < n; i0 += 4 * kStride) {
+    for (uint32_t i0 = first; i0 < n; i0 += 4 * kStride) {
         uint32_t key[4], cnt[4], rank[4];
 #pragma unroll
         for (int t = 0; t < 4; t++) {
@@ -337,19 +348,76 @@ __global__ __launch_bounds__(256) void k_sp_emit(const uint32_t *__restrict__ ss
         }
     }
 }
+__global__ __launch_bounds__(256) void k_sp_emit(const uint32_t *__restrict__ sstart, const uint16_t *__restrict__ sbin,
+                                                 const uint32_t *__restrict__ scnt, SpEmit em) {
+    sp_emit_body(blockIdx.x / kSpEmitSplit, (blockIdx.x % kSpEmitSplit) * 256 + threadIdx.x, sstart, sbin, scnt, em);
+}
 
 // bits (u64[2^18]) -> wprefix inside blocks of 1024 words + blocktot; k_gidx_finish (k_hist.hip) completes it
 __global__ __launch_bounds__(256) void k_bits_prefix(const unsigned long long *__restrict__ bits, uint32_t *__restrict__ wprefix,
                                                      uint32_t *__restrict__ blocktot) {
     __shared__ uint32_t wsum[256 / 64];
-    const uint32_t w0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-    uint32_t cnt[4], mine = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) { cnt[q] = (uint32_t)__popcll(bits[w0 + q]); mine += cnt[q]; }
-    uint32_t run = block_exclusive_scan<256>(mine, wsum);
-#pragma unroll
-    for (int q = 0; q < 4; q++) { wprefix[w0 + q] = run; run += cnt[q]; }
-    if (threadIdx.x == 255) blocktot[blockIdx.x] = run;
+    bits_prefix_body(blockIdx.x, bits, wprefix, blocktot, wsum);   // (device_utils.hpp)
+}
+
+// ---- The set-up between k_sp_hist and the K-means in three launches.  Eleven small dispatches stand there otherwise -- the prefix of the
+// bitmap in two steps, the scan of the cells in two, two fills, the initial centroids, the persistent launch's chunk boundaries, the emit,
+// and the copy of the colour count -- and all but the emit sit at the few microseconds any dispatch costs; k_ps_ranges is one block's latency.
+// Few of them depend on each other, so a block takes its ROLE from blockIdx, and every role is the body of the kernel it replaces:
+//   A  k_bits_prefix | k_cell_totals | the zeroing of the K-means arena and of the head of the persistent launch's arena
+//   B  k_gidx_finish | k_cell_scan                                   (the colour count is copied to the host behind B)
+//   C  k_ps_ranges (block 0: dispatched first, ONE block as ever) | k_rgbw_init_cent | k_sp_emit, a 1024-thread block per bucket
+// No role reads what another role of its own launch writes, and no block waits for another: the order is the stream's.
+constexpr uint32_t kFrontPrefixBlocks = 256;                    // blocks of 256 threads: k_bits_prefix's / k_gidx_finish's grid
+constexpr uint32_t kFrontCellBlocks = kCellGroups / 4;          // ... and four groups of 64 cells to a block, a wave each
+constexpr uint32_t kFrontZeroBlocks = 32;
+static_assert(kCellGroups % 4 == 0, "four waves of a block each take a group of cells");
+struct FrontA {
+    const unsigned long long *bits; uint32_t *wprefix, *blocktot;
+    const uint32_t *cell_count; uint2 *cell_tot;
+    uint4 *zero0, *zero1; uint32_t n0, n1;                      // two ranges of n0 and n1 16-byte words to clear
+};
+__global__ __launch_bounds__(256) void k_cc_front_a(FrontA a) {
+    __shared__ uint32_t wsum[256 / 64];
+    const uint32_t b = blockIdx.x;
+    if (b < kFrontPrefixBlocks) {
+        bits_prefix_body(b, a.bits, a.wprefix, a.blocktot, wsum);
+    } else if (b < kFrontPrefixBlocks + kFrontCellBlocks) {
+        cell_totals_body((b - kFrontPrefixBlocks) * 4 + (threadIdx.x >> 6), threadIdx.x & 63u, a.cell_count, a.cell_tot);
+    } else {
+        const uint32_t t = (b - kFrontPrefixBlocks - kFrontCellBlocks) * 256 + threadIdx.x;
+        for (uint32_t i = t; i < a.n0; i += kFrontZeroBlocks * 256) a.zero0[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (uint32_t i = t; i < a.n1; i += kFrontZeroBlocks * 256) a.zero1[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+struct FrontB {
+    uint32_t *wprefix; const uint32_t *blocktot; uint64_t *total;
+    const uint32_t *cell_count; const uint2 *cell_tot; CellScanOut scan;
+};
+__global__ __launch_bounds__(256) void k_cc_front_b(FrontB a) {
+    __shared__ uint32_t wsum[256 / 64];
+    __shared__ uint32_t boff[256];
+    const uint32_t b = blockIdx.x;
+    if (b < kFrontPrefixBlocks) gidx_finish_body(b, a.wprefix, a.blocktot, a.total, wsum, boff);
+    else cell_scan_body((b - kFrontPrefixBlocks) * 4 + (threadIdx.x >> 6), threadIdx.x & 63u, a.cell_count, a.cell_tot, a.scan, kCellFixedCost, kCellSweepCost);
+}
+struct FrontC {
+    uint32_t ranges, cent_blocks;                               // blocks of the first two roles (ranges: 0 or 1); the buckets' follow
+    const uint32_t *ne_cost, *ne_count; uint32_t G, budget; uint32_t *cb; PsDev *dev; PsDevPtrs ptrs;
+    uint64_t Ulist; uint32_t K, Kpad, idbits; uint2 *cconst; uint32_t *cent, *cent_copy, *moved_list; const uint64_t *U_dev; GIdx cgx;
+    const uint32_t *sstart; const uint16_t *sbin; const uint32_t *scnt; SpEmit em;
+};
+__global__ __launch_bounds__(kSpThreads) void k_cc_front_c(FrontC a) {
+    const uint32_t b = blockIdx.x;
+    if (b < a.ranges) {
+        ps_ranges_body(a.ne_cost, a.ne_count, a.G, a.budget, a.cb, a.dev, a.ptrs);
+    } else if (b < a.ranges + a.cent_blocks) {
+        rgbw_init_cent_body((b - a.ranges) * kSpThreads + threadIdx.x, nullptr, a.Ulist, a.K, a.Kpad, a.idbits, a.cconst, a.cent, a.cgx, a.cent_copy,
+                            a.moved_list, a.U_dev);
+    } else {
+        static_assert(kSpThreads == 256 * kSpEmitSplit, "one block is the emit's 1024 threads of a bucket");
+        sp_emit_body(b - a.ranges - a.cent_blocks, threadIdx.x, a.sstart, a.sbin, a.scnt, a.em);
+    }
 }
 
 // ---- back end.  One block per bucket: LDS table bin -> final label from the bucket's points, then the label of
@@ -662,7 +730,9 @@ static int sp_set_lds(Ctx *c) {
 
 // pixels -> partition + occupied colours per cell + occupancy bitmap with its prefix.  Nothing waits: the number of
 // distinct colours stays on the device (plan->total) for the set-up kernels that follow, and sp_wait_count fetches it
-int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan) {
+// hist_only: ends behind k_sp_hist -- the prefix of the bitmap and the copy of the count are then the caller's to enqueue, with the K-means'
+// set-up (sp_front)
+int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan, bool hist_only) {
     if (npx == 0 || (reinterpret_cast<uintptr_t>(rgb_d) & 15)) return c->fail(CNIIC_ERR_BAD_ARG, "sp_build: empty or unaligned image");
     CNIIC_TRY(sp_set_lds(c));
     plan->npx = npx;
@@ -682,21 +752,20 @@ int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan) {
     CNIIC_HIP_TRY(c, plan->wprefix.alloc((1ull << 18) * 4));
     DevBuf total, blocktot;
     CNIIC_HIP_TRY(c, total.alloc((uint64_t)kSpBuckets * 4));
-    CNIIC_HIP_TRY(c, blocktot.alloc(256 * 4));
+    if (!hist_only) CNIIC_HIP_TRY(c, blocktot.alloc(256 * 4));
     CNIIC_HIP_TRY(c, plan->total.alloc(8));
     CNIIC_HIP_TRY(c, c->pinned_u.reserve(kPinnedUBytes, kPinnedUBytes));
     CNIIC_HIP_TRY(c, c->u_ev.ensure(hipEventDisableTiming));
     hipLaunchKernelGGL(k_sp_count, dim3(plan->nchunks), dim3(kSpThreads), 0, c->stream, rgb_d, npx, plan->cnt.as<uint32_t>());
     hipLaunchKernelGGL(k_sp_colscan, dim3(kSpBuckets), dim3(256), 0, c->stream, plan->cnt.as<uint32_t>(), plan->nchunks,
                        plan->pre.as<uint32_t>(), total.as<uint32_t>());
-    hipLaunchKernelGGL(k_sp_bstart, dim3(1), dim3(kSpBuckets), 0, c->stream, total.as<uint32_t>(), plan->bstart.as<uint32_t>(),
-                       plan->sstart.as<uint32_t>());
     hipLaunchKernelGGL(k_sp_scatter, dim3(plan->nchunks), dim3(kSpThreads), (size_t)kSpChunk * 2 + kSpBuckets * 8 + 16, c->stream, rgb_d, npx,
-                       plan->cnt.as<uint32_t>(), plan->pre.as<uint32_t>(), plan->bstart.as<uint32_t>(), plan->part.as<uint16_t>(),
-                       plan->prank.as<uint16_t>());
+                       plan->cnt.as<uint32_t>(), plan->pre.as<uint32_t>(), (const uint32_t *)total.as<uint32_t>(), plan->bstart.as<uint32_t>(),
+                       plan->sstart.as<uint32_t>(), plan->part.as<uint16_t>(), plan->prank.as<uint16_t>());
     hipLaunchKernelGGL(k_sp_hist, dim3(kSpBuckets), dim3(kSpThreads), (size_t)kSpBins * 4, c->stream, plan->part.as<uint16_t>(),
                        plan->bstart.as<uint32_t>(), plan->sstart.as<uint32_t>(), plan->cell_count.as<uint32_t>(), plan->bits.as<uint32_t>(),
                        plan->sbin.as<uint16_t>(), plan->scnt.as<uint32_t>());
+    if (hist_only) { CNIIC_HIP_TRY(c, hipGetLastError()); return CNIIC_OK; }
     hipLaunchKernelGGL(k_bits_prefix, dim3(256), dim3(256), 0, c->stream, plan->bits.as<unsigned long long>(), plan->wprefix.as<uint32_t>(),
                        blocktot.as<uint32_t>());
     CNIIC_TRY(gidx_finish(c, plan->wprefix.as<uint32_t>(), blocktot.as<uint32_t>(), plan->total.as<uint64_t>()));
@@ -704,6 +773,57 @@ int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan) {
     CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
     CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
     return CNIIC_OK;
+}
+
+// Behind sp_build(hist_only): everything between k_sp_hist and the K-means of state f describes (km_rgbw_create_deferred) -- the prefix of
+// the bitmap, the copy of the colour count with its event, the state's set-up dispatches and the emit into its arrays (the point list is
+// the image's own: plan's bitmap).  fused: the three launches k_cc_front_a / b / c; else the kernels and fills one by one, as sp_build,
+// km_rgbw_create and sp_emit enqueue them.
+int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide, bool fused) {
+    DevBuf blocktot;   // (lives until everything here is enqueued: the pool hands memory out again in stream order)
+    CNIIC_HIP_TRY(c, blocktot.alloc(256 * 4));
+    const uint64_t *U_dev = plan->total.as<uint64_t>();
+    const GIdx gx{plan->bits.as<unsigned long long>(), plan->wprefix.as<uint32_t>(), 0};
+    const SpEmit em{f.scan.cell_start, ckeys_d, cweight_d, labels_d, f.K, wide ? 1u : 0u, gx, U_dev};
+    if (!fused) {
+        hipLaunchKernelGGL(k_bits_prefix, dim3(256), dim3(256), 0, c->stream, plan->bits.as<unsigned long long>(), plan->wprefix.as<uint32_t>(),
+                           blocktot.as<uint32_t>());
+        CNIIC_TRY(gidx_finish(c, plan->wprefix.as<uint32_t>(), blocktot.as<uint32_t>(), plan->total.as<uint64_t>()));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
+        CNIIC_TRY(km_front_enqueue_split(c, f));
+        hipLaunchKernelGGL(k_sp_emit, dim3(kSpBuckets * kSpEmitSplit), dim3(256), 0, c->stream, plan->sstart.as<uint32_t>(), plan->sbin.as<uint16_t>(),
+                           plan->scnt.as<uint32_t>(), em);
+        CNIIC_HIP_TRY(c, hipGetLastError());
+        return CNIIC_OK;
+    }
+    FrontA a{};
+    a.bits = plan->bits.as<unsigned long long>(); a.wprefix = plan->wprefix.as<uint32_t>(); a.blocktot = blocktot.as<uint32_t>();
+    a.cell_count = f.cell_count; a.cell_tot = f.cell_tot.as<uint2>();
+    a.zero0 = static_cast<uint4 *>(f.arena); a.n0 = (uint32_t)(f.arena_bytes / 16);
+    a.zero1 = static_cast<uint4 *>(f.ps_arena); a.n1 = f.ranges ? (uint32_t)(f.ps_zero_bytes / 16) : 0u;
+    hipLaunchKernelGGL(k_cc_front_a, dim3(kFrontPrefixBlocks + kFrontCellBlocks + kFrontZeroBlocks), dim3(256), 0, c->stream, a);
+    FrontB b{};
+    b.wprefix = a.wprefix; b.blocktot = a.blocktot; b.total = plan->total.as<uint64_t>();
+    b.cell_count = f.cell_count; b.cell_tot = a.cell_tot; b.scan = f.scan;
+    hipLaunchKernelGGL(k_cc_front_b, dim3(kFrontPrefixBlocks + kFrontCellBlocks), dim3(256), 0, c->stream, b);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
+    FrontC k{};
+    k.ranges = f.ranges ? 1u : 0u; k.cent_blocks = (uint32_t)ceil_div(f.Kpad, kSpThreads);
+    k.ne_cost = f.scan.ne_cost; k.ne_count = f.scan.ne_count; k.G = f.G; k.budget = f.budget; k.cb = f.cb; k.dev = f.dev; k.ptrs = f.ptrs;
+    k.Ulist = f.Ulist; k.K = f.K; k.Kpad = f.Kpad; k.idbits = f.idbits; k.cconst = f.cconst; k.cent = f.cent; k.cent_copy = f.cent_copy;
+    k.moved_list = f.moved_list; k.U_dev = f.U_dev; k.cgx = f.gx;
+    k.sstart = plan->sstart.as<uint32_t>(); k.sbin = plan->sbin.as<uint16_t>(); k.scnt = plan->scnt.as<uint32_t>(); k.em = em;
+    hipLaunchKernelGGL(k_cc_front_c, dim3(k.ranges + k.cent_blocks + kSpBuckets), dim3(kSpThreads), 0, c->stream, k);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    return CNIIC_OK;
+}
+// whether sp_front's launches can clear what f asks to be cleared (whole 16-byte words at 16-byte addresses)
+bool sp_front_fits(const KmFront &f) {
+    auto ok = [](const void *p, uint64_t n) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && n % 16 == 0 && n / 16 < (1ull << 32); };
+    return ok(f.arena, f.arena_bytes) && (!f.ranges || ok(f.ps_arena, f.ps_zero_bytes));
 }
 
 int sp_wait_count(Ctx *c, SpPlan *plan) {

@@ -108,7 +108,15 @@ constexpr uint32_t kPsStatusDone = 1, kPsStatusAborted = 2, kPsStatusRanges = 3;
 struct PsExit { uint32_t status, pad; uint64_t iter, moved_last, reseeds, active, pair_evals; };   // pinned: how the launch ended
 void launch_rgbw_assign_big(Ctx *c, const uint32_t *ckeys, const uint32_t *cweight, uint64_t U, uint32_t K, const uint32_t *cent, uint16_t *labels,
                             unsigned long long *partials, const KmDevState *st);
-int ps_prepare(KmRgbwState *s);
+struct PsSetup {                          // ps_decide's answer.  on: there is a persistent launch; then [zero_p, + zero_bytes) of its arena must be zeroed and
+    bool on = false;                      // k_ps_ranges run with (G, budget, cb, dev, ptrs) before it
+    uint32_t G = 0, budget = 0;
+    uint32_t *cb = nullptr; PsDev *dev = nullptr; PsDevPtrs ptrs{};
+    void *zero_p = nullptr; uint64_t zero_bytes = 0;
+};
+int ps_decide(KmRgbwState *s, PsSetup *out);
+int ps_enqueue(KmRgbwState *s, const PsSetup &p);
+void ps_launch_ranges(Ctx *c, const uint32_t *ne_cost, const uint32_t *ne_count, uint32_t G, uint32_t budget, uint32_t *cb, PsDev *dev, const PsDevPtrs &ptrs);
 int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer);
 int km_rgbw_persistent_verdict(KmRgbwState *s, bool *retry);   // for km_rgbw_result_end: how a deferred launch ended
 constexpr uint32_t kAggMin = 16;  // points that must share the first mover's (old, new) pair for a round of aggregated booking to be worth it
@@ -124,6 +132,124 @@ __device__ __forceinline__ uint2 make_cconst(uint32_t ckey, uint32_t k, uint32_t
     uint32_t idmask = (1u << idbits) - 1;
     return make_uint2(ckey, ((kBias - h) << idbits) | (idmask - k));
 }
+
+// ---- the set-up kernels' bodies.  Each is launched on its own (k_rgbw_init_cent, k_cell_totals, k_cell_scan: k_kmeans_rgbw.hip;
+// k_ps_ranges: k_kmeans_persist.hip) and as a role of the large cluster-colors encode's set-up launches (k_cc_front_*: k_points.hip).
+// init (kmeans.rs:61-108), thread k of Kpad
+__device__ __forceinline__ void rgbw_init_cent_body(uint32_t k, const uint32_t *__restrict__ keys, uint64_t U, uint32_t K, uint32_t Kpad, uint32_t idbits,
+                                                    uint2 *__restrict__ cconst, uint32_t *__restrict__ cent, const GIdx &gx, uint32_t *__restrict__ cent_copy,
+                                                    uint32_t *__restrict__ moved_list, const uint64_t *__restrict__ U_dev) {
+    if (U_dev) U = max(*U_dev, (uint64_t)K);  // the count is still on its way to the host (fewer points than clusters: refused there)
+    if (k == 0 && moved_list) moved_list[0] = K;  // before the first update every centroid counts as moved
+    if (k < K) {
+        // init_centroids (kmeans.rs:101-108): first element of chunk k
+        uint64_t ppc = U / K;
+        uint64_t first = (k < K - 1) ? U - ((uint64_t)k + 1) * ppc : 0;
+        uint32_t ck = gx.bits ? gidx_select(gx, first) : keys[first];
+        cent[k] = ck;
+        if (cent_copy) cent_copy[k] = ck;
+        cconst[k] = make_cconst(ck, k, idbits);
+    } else if (k < Kpad) {
+        cconst[k] = make_uint2(0u, 0u);  // padding: key 0 never wins
+    }
+}
+
+// Exclusive scan of the cell counts in two steps of kNumCells / 64 waves: per 64 cells (points, non-empty cells), then every wave
+// adds up the groups before its own (k_kmeans_rgbw.hip has the whole story).  A wave per group `grp`, lane <-> cell.
+constexpr uint32_t kCellGroups = kNumCells / 64;
+// (tot[kCellGroups + g]: the group's sweeps, ceil(points / 256) per cell -- the full schedule's cost model counts them)
+__device__ __forceinline__ void cell_totals_body(uint32_t grp, uint32_t lane, const uint32_t *__restrict__ cell_count, uint2 *__restrict__ tot) {
+    const uint32_t v = cell_count[grp * 64 + lane];
+    const uint32_t sum = wave_reduce_sum(v), sweeps = wave_reduce_sum((v + 64 * kSweep - 1) / (64 * kSweep));
+    const uint32_t ne = (uint32_t)__popcll(__ballot(v != 0));
+    if (lane == 0) { tot[grp] = make_uint2(sum, ne); tot[kCellGroups + grp] = make_uint2(sweeps, 0u); }
+}
+struct CellScanOut { uint32_t *cell_start, *cursor, *ne_cell, *ne_start, *ne_cost, *ne_count; };
+__device__ __forceinline__ void cell_scan_body(uint32_t grp, uint32_t lane, const uint32_t *__restrict__ cell_count, const uint2 *__restrict__ tot,
+                                               const CellScanOut &o, uint32_t fixed_cost, uint32_t sweep_cost) {
+    // cost of a cell in the full schedule's split: fixed_cost + points if sweep_cost == 0, else fixed_cost + sweep_cost * sweeps
+    uint32_t ps = 0, pn = 0, pw = 0;
+    for (uint32_t g = lane; g < grp; g += 64) { const uint2 t = tot[g]; ps += t.x; pn += t.y; pw += tot[kCellGroups + g].x; }
+    const uint32_t base = wave_reduce_sum(ps), nbase = wave_reduce_sum(pn), wbase = wave_reduce_sum(pw);
+    const uint32_t cell = grp * 64 + lane, v = cell_count[cell], sw = (v + 64 * kSweep - 1) / (64 * kSweep);
+    const uint32_t start = base + wave_inclusive_scan(v) - v, swb = wbase + wave_inclusive_scan(sw) - sw;
+    o.cell_start[cell] = start;
+    if (o.cursor) o.cursor[cell] = start;
+    const unsigned long long nzm = __ballot(v != 0);
+    if (v) {
+        const uint32_t m = nbase + (uint32_t)__popcll(nzm & ((1ull << lane) - 1ull));
+        o.ne_cell[m] = cell; o.ne_start[m] = start; o.ne_cost[m] = (sweep_cost ? swb * sweep_cost : start) + m * fixed_cost;
+    }
+    if (grp == kCellGroups - 1 && lane == 63) {
+        const uint32_t U = start + v, M = nbase + (uint32_t)__popcll(nzm);
+        o.cell_start[kNumCells] = U;
+        o.ne_start[M] = U;
+        o.ne_cost[M] = (sweep_cost ? (swb + sw) * sweep_cost : U) + M * fixed_cost;
+        *o.ne_count = M;
+    }
+}
+
+// the chunk boundaries of the persistent launch (k_kmeans_persist.hip: "who owns what"): ONE block of 1024 threads -- the barrier and the
+// fit check behind it see this block's own stores
+__device__ __forceinline__ void ps_ranges_body(const uint32_t *__restrict__ ne_cost, const uint32_t *__restrict__ ne_count, uint32_t G, uint32_t dyn_bytes,
+                                               uint32_t *__restrict__ cb, PsDev *__restrict__ dev, const PsDevPtrs &ptrs) {
+    uint32_t *fail = &dev->fail;
+    if (threadIdx.x == 0) dev->p = ptrs;
+    const uint32_t M = *ne_count, NC = G * kPsChunks;
+    const uint64_t total = ne_cost[M];
+    // (a thread's boundaries searched TOGETHER, eight at a time: one after the other the 4097 bisections of the headline image were 60
+    // dependent reads a thread, 21 us in front of the launch)
+    for (uint32_t g0 = threadIdx.x; g0 <= NC; g0 += 8 * blockDim.x) {
+        uint32_t a[8], b[8];
+        uint64_t c_lo[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const uint32_t g = g0 + r * blockDim.x;
+            c_lo[r] = total * min(g, NC) / NC;
+            a[r] = 0; b[r] = g <= NC ? M : 0u;   // first cell whose cost prefix is >= c_lo
+        }
+        bool more = true;
+        while (more) {
+            more = false;
+            uint32_t mid[8], v[8];
+#pragma unroll
+            for (int r = 0; r < 8; r++) { mid[r] = (a[r] + b[r]) >> 1; v[r] = a[r] < b[r] ? ne_cost[mid[r]] : 0u; }
+#pragma unroll
+            for (int r = 0; r < 8; r++)
+                if (a[r] < b[r]) { if (v[r] < c_lo[r]) a[r] = mid[r] + 1; else b[r] = mid[r]; more = more || a[r] < b[r]; }
+        }
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const uint32_t g = g0 + r * blockDim.x;
+            if (g <= NC) cb[g] = g == NC ? M : a[r];
+        }
+    }
+    __syncthreads();   // (one block: its own stores are visible to it behind the barrier)
+    for (uint32_t g = threadIdx.x; g < G; g += blockDim.x) {
+        uint32_t C = 0;
+        for (uint32_t r = 0; r < kPsChunks; r++) C += cb[r * G + g + 1] - cb[r * G + g];
+        if (C > kPsMaxCells || kPsOffCell + ps_cell_bytes(C) > dyn_bytes) atomicAdd(fail, 1u);
+    }
+}
+
+// What km_rgbw_create leaves to its caller when asked to (points_follow only): the set-up dispatches it would enqueue, described
+// instead.  The caller enqueues them -- as the roles of k_cc_front_* or, km_front_enqueue_split, as the kernels create itself launches --
+// before anything else touches the state.
+struct KmFront {
+    void *arena = nullptr; uint64_t arena_bytes = 0;          // to be zeroed ...
+    void *ps_arena = nullptr; uint64_t ps_zero_bytes = 0;     // ... and, with ranges, the head of the persistent launch's arena
+    // k_rgbw_init_cent (behind the zeroing: it writes into the arena)
+    uint64_t Ulist = 0; uint32_t K = 0, Kpad = 0, idbits = 0;
+    uint2 *cconst = nullptr; uint32_t *cent = nullptr, *cent_copy = nullptr, *moved_list = nullptr;
+    GIdx gx{nullptr, nullptr, 0}; const uint64_t *U_dev = nullptr;
+    // k_cell_totals / k_cell_scan
+    const uint32_t *cell_count = nullptr; DevBuf cell_tot; CellScanOut scan{};
+    // k_ps_ranges (ranges: there is a persistent launch)
+    bool ranges = false; uint32_t G = 0, budget = 0; uint32_t *cb = nullptr; PsDev *dev = nullptr; PsDevPtrs ptrs{};
+};
+int km_rgbw_create_deferred(Ctx *c, uint64_t Umax, uint32_t K, const cniic_kmeans_opts *opts, KmRgbwState **out, const uint32_t *cell_count_d,
+                            const void *gbits_d, const uint32_t *gprefix_d, uint64_t Ug, const uint64_t *points_dev, KmFront *front);
+int km_front_enqueue_split(Ctx *c, const KmFront &f);   // the fills and the four kernels, in create's own order
 
 struct CellBox { int32_t r0, g0, b0; };  // low corner of a cube of colours
 __device__ __forceinline__ CellBox super_box(uint32_t sup) {
