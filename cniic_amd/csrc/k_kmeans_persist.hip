@@ -17,6 +17,7 @@
 // Every spin is bounded by the wall clock and watches an abort word: a grid that is not resident at once (somebody else's kernel on the
 // CUs) ends with status `aborted`, the arrays the classic loop starts from are untouched, and km_rgbw_run falls back to it.
 #include <atomic>
+#include <type_traits>
 
 #include <hip/hip_ext.h>
 
@@ -498,9 +499,50 @@ struct PsArgs {
     PsCold *cold;                         // pinned
     uint64_t max_iters;
     uint32_t K, max_skip, agg_iters, test_abort_at, lds_budget;
+    uint32_t form;                        // kPsForm*: how the skip schedule's row test is sized (by what moved, but for the tests' CNIIC_TEST_PS_TRIPS / _GROUP)
     uint32_t clean_skip;                  // full schedule: cells none of whose old or new candidates moved are not swept (0: A/B measurements, CNIIC_KM_PS_CLEANSKIP)
     unsigned long long timeout_ticks;
 };
+
+// PsArgs::form.  kPsFormRows: the skip schedule's row test takes 4, 8 or 16 lanes per cell and ceil(nS / lanes) trips, chosen per iteration
+// (ps_row_group); without it (the tests' CNIIC_TEST_PS_TRIPS=fixed) 16 lanes and kMaxMovedSkip / 16 trips whatever moved.  Bits 4..6: log2
+// of a forced group width (CNIIC_TEST_PS_GROUP).
+constexpr uint32_t kPsFormRows = 1u, kPsFormGroupShift = 4u;
+
+// The row test's group width for an iteration with nS moved centroids in a block of C cells, as log2.  A wave tests 64 / L cells, so
+// ceil(C L / 64) waves have cells and the block's four SIMDs each issue for ceil(C L / 256) of them in turn -- the test is bound by
+// instruction issue, not by the passes of a wave (measured on the headline encode, NOTES AM: C = 119 .. 132, L = 4 / 8 / 16 forced for a
+// whole run: 1311.6 / 1320.8 / 1335.1 us).  A wave's pass costs its fixed part (record, cell box, pivot constants, ballot and queue:
+// kPsRowFixed), kPsRowTrip per trip of a lane through its ceil(nS / L) moved centroids and kPsRowChunk per four trips (issued together:
+// one wait for the chunk's reads), in units of a dozen wave instructions.  The cheapest of L = 4, 8, 16; the narrower group on a tie.
+constexpr uint32_t kPsRowFixed = 8, kPsRowTrip = 1, kPsRowChunk = 4;
+__device__ __forceinline__ uint32_t ps_row_group(uint32_t nS, uint32_t C) {
+    uint32_t best_lg = 2, best_cost = 0xffffffffu;
+#pragma unroll
+    for (uint32_t lg = 2; lg <= 4; lg++) {
+        const uint32_t simd_waves = ((C << lg) + 255u) >> 8, trips = (nS + (1u << lg) - 1u) >> lg;
+        const uint32_t cost = simd_waves * (kPsRowFixed + kPsRowTrip * trips + kPsRowChunk * ((trips + 3u) >> 2));
+        if (cost < best_cost) { best_cost = cost; best_lg = lg; }
+    }
+    return best_lg;
+}
+
+// T trips of a lane of the row test through the moved centroids j0, j0 + L, ... (their reads issued together): a moved centroid matters
+// to the cell if it was a candidate (its bit in the record's mask) or the cell's pivot no longer dominates it
+template <int T, uint32_t L>
+__device__ __forceinline__ bool ps_row_moved(const uint32_t *rec, const Dominance &dm, const uint32_t *mlist, const uint32_t *mcol, uint32_t j0, uint32_t nS) {
+    bool dv = false;
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        const uint32_t jj = j0 + L * (uint32_t)t;
+        if (jj < nS) {
+            const uint32_t mk = mlist[jj], mc = mcol[jj];
+            const bool in = ((rec[2 + (mk >> 5)] >> (mk & 31)) & 1u) != 0;
+            dv = dv | in | (dm.worst(mc) >= 0);
+        }
+    }
+    return dv;
+}
 
 __device__ __forceinline__ unsigned long long *ps_partials(PsBar *bar) {   // 3 x kPsPartWords sums, zero on entry
     return reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(bar) + kPsArenaPart);
@@ -514,9 +556,10 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     __shared__ uint32_t s_nS[kPsSlotsMax], s_lpiv[kPsSlotsMax], s_mcol[kMaxMovedSkip];
     __shared__ uint16_t s_ssup[kPsSlotsMax];
     __shared__ uint32_t s_cbase[kPsChunks + 1], s_cm0[kPsChunks], s_scan[kPsThreads / 64];
+    __shared__ uint32_t s_gcnt[3];   // iterations whose row test ran with 4, 8, 16 lanes per cell (block 0's go to PsExit)
     // (the static variables above, with room for their alignment: static + dynamic LDS stay inside a CU's 160 KiB.  The sum is written
     // out by hand: whoever adds a __shared__ variable adds it here too -- tools/kernel_regs.sh prints what the compiler counted)
-    static_assert(4 * (11 + 2 * kMaxMovedSkip + 2 * kPsSlotsMax + 2 * kPsChunks + 1 + kPsThreads / 64) + 8 * (4 + 5) + 2 * kPsSlotsMax + 64 <= kPsStaticMax, "the static LDS of k_rgbw_persist");
+    static_assert(4 * (11 + 3 + 2 * kMaxMovedSkip + 2 * kPsSlotsMax + 2 * kPsChunks + 1 + kPsThreads / 64) + 8 * (4 + 5) + 2 * kPsSlotsMax + 64 <= kPsStaticMax, "the static LDS of k_rgbw_persist");
     const uint32_t tid = threadIdx.x, K = a.K, G = gridDim.x;
     const int lane = tid & 63, wid = tid >> 6;
     unsigned long long *acc = lds;
@@ -541,6 +584,7 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     if (tid == 0) {
         s_cbase[0] = 0;
         s_moved = 0; s_evals = 0; s_nmoved = 0; s_reseed = 0; s_active = 0; s_mm[0] = s_mm[1] = s_mm[2] = s_mm[3] = 0ull; s_qn = 0; s_qhead = 0; s_Cres = 0; s_nslots = 0; s_rtot = 0ull; s_etot = 0ull;
+        s_gcnt[0] = s_gcnt[1] = s_gcnt[2] = 0;
     }
     __syncthreads();
     if (tid == 0)
@@ -706,27 +750,37 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
         } else {
             // ============================================================= SKIP schedule (at most max_skip centroids moved)
             // A cell none of whose candidates moved and whose pivot still dominates every moved centroid repeats all its decisions.  The
-            // test, a row of 16 lanes per cell; what fails it goes on the list and is worked on by a whole wave below.
-            for (uint32_t i0 = (uint32_t)wid_i * 4; i0 < C; i0 += kPsWaves * 4) {
-                const uint32_t i = i0 + row;
-                const bool ok = i < C;
-                const uint32_t *rec = recs + (size_t)kPsRecWords * (ok ? i : 0u);
-                const uint32_t r1 = rec[1], lp = r1 >> 24, c = ccell[ok ? i : 0u];
-                Dominance dm;
-                dm.set(cell_box(c), (1 << kCellShift) - 1, rec[0]);
-                bool dv = !(r1 & kPsComplete) && ((s_mm[lp >> 6] >> (lp & 63)) & 1ull) != 0ull;   // the list the mask came from lost its pivot
-#pragma unroll
-                for (int t = 0; t < 4; t++) {   // the lane's share of the moved centroids: ids and colours
-                    const uint32_t jj = l16 + 16u * t;
-                    if (jj < nS) {
-                        const uint32_t mk = s_mlist[jj], mc = s_mcol[jj];
-                        const bool in = ((rec[2 + (mk >> 5)] >> (mk & 31)) & 1u) != 0;
-                        dv = dv | in | (dm.worst(mc) >= 0);   // a moved centroid matters if it was a candidate or is no longer dominated by the pivot
+            // test, a group of lanes per cell; what fails it goes on the list and is worked on by a whole wave below.
+            // L = 4, 8 or 16 lanes per cell (ps_row_group), every lane its share of the moved centroids: ceil(nS / L) trips.
+            const uint32_t lg = (a.form >> kPsFormGroupShift) ? (a.form >> kPsFormGroupShift) : (a.form & kPsFormRows) ? ps_row_group(nS, C) : 4u;
+            const uint32_t lim = (a.form & kPsFormRows) ? nS : kMaxMovedSkip;
+            if (blockIdx.x == 0 && tid_i == 0) s_gcnt[lg - 2u]++;
+            auto row_test = [&](auto lgc) {
+                constexpr uint32_t LG = decltype(lgc)::value, L = 1u << LG, per = 64u >> LG;
+                const uint32_t grp = (uint32_t)lane_i >> LG, ll = (uint32_t)lane_i & (L - 1u);
+                for (uint32_t i0 = (uint32_t)wid_i * per; i0 < C; i0 += kPsWaves * per) {
+                    const uint32_t i = i0 + grp;
+                    const bool ok = i < C;
+                    const uint32_t *rec = recs + (size_t)kPsRecWords * (ok ? i : 0u);
+                    const uint32_t r1 = rec[1], lp = r1 >> 24, c = ccell[ok ? i : 0u];
+                    Dominance dm;
+                    dm.set(cell_box(c), (1 << kCellShift) - 1, rec[0]);
+                    bool dv = !(r1 & kPsComplete) && ((s_mm[lp >> 6] >> (lp & 63)) & 1ull) != 0ull;   // the list the mask came from lost its pivot
+                    // the lane's share of the moved centroids, four trips at a time (as a rule there are no more)
+                    for (uint32_t b0 = 0; b0 < lim; b0 += 4u * L) {
+                        const uint32_t left = (lim - b0 + L - 1u) >> LG;   // (block-uniform: a branch of the scalar unit)
+                        if (left >= 4u) dv = dv | ps_row_moved<4, L>(rec, dm, s_mlist, s_mcol, b0 + ll, nS);
+                        else if (left == 3u) dv = dv | ps_row_moved<3, L>(rec, dm, s_mlist, s_mcol, b0 + ll, nS);
+                        else if (left == 2u) dv = dv | ps_row_moved<2, L>(rec, dm, s_mlist, s_mcol, b0 + ll, nS);
+                        else dv = dv | ps_row_moved<1, L>(rec, dm, s_mlist, s_mcol, b0 + ll, nS);
                     }
+                    const unsigned long long bm = __ballot(dv && ok);   // the cell's verdict: any lane of its group
+                    if (ll == 0 && ((bm >> ((uint32_t)lane_i & ~(L - 1u))) & ((1ull << L) - 1ull))) queue[atomicAdd(&s_qn, 1u)] = (uint16_t)i;
                 }
-                const unsigned long long bm = __ballot(dv && ok);
-                if (l16 == 0 && ((bm >> (16 * row)) & 0xffffull)) queue[atomicAdd(&s_qn, 1u)] = (uint16_t)i;
-            }
+            };
+            if (lg == 2u) row_test(std::integral_constant<uint32_t, 2>{});
+            else if (lg == 3u) row_test(std::integral_constant<uint32_t, 3>{});
+            else row_test(std::integral_constant<uint32_t, 4>{});
         }
         __syncthreads();   // the work list is complete
         // ------------------------------------------------------------- sweeps: list entry wid, wid + 16, ... is this wave's
@@ -936,6 +990,7 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
                 sw->moved_last = changed; sw->reseeds = reseeds_total; sw->active = s_active; sw->pair_evals = evals_total; sw->iter = j; sw->done = 1;
                 PsExit *x = &a.cold->exit;
                 x->iter = j; x->moved_last = changed; x->reseeds = reseeds_total; x->active = s_active; x->pair_evals = evals_total;
+                x->group_iters[0] = s_gcnt[0]; x->group_iters[1] = s_gcnt[1]; x->group_iters[2] = s_gcnt[2];
             }
         }
         if (fin) break;   // converged (kmeans.rs:26-32) or the iteration cap: every block sees the same sums and leaves together
@@ -1066,6 +1121,12 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     a.K = s->K; a.max_skip = s->no_skip ? 0u : s->max_skip; a.agg_iters = kAggLaunches;
     a.test_abort_at = 0;
     if (const char *e = test_env("CNIIC_TEST_PS_ABORT_AT")) a.test_abort_at = (uint32_t)atoi(e);
+    a.form = kPsFormRows;
+    if (const char *e = test_env("CNIIC_TEST_PS_TRIPS")) if (strcmp(e, "fixed") == 0) a.form = 0u;
+    if (const char *e = test_env("CNIIC_TEST_PS_GROUP")) {
+        const int L = atoi(e);
+        if (L == 4 || L == 8 || L == 16) a.form |= (L == 4 ? 2u : L == 8 ? 3u : 4u) << kPsFormGroupShift;
+    }
     a.clean_skip = 1;
     if (const char *e = test_env("CNIIC_KM_PS_CLEANSKIP")) a.clean_skip = atoi(e) ? 1u : 0u;
     uint64_t tmo_ms = 2000;
@@ -1104,6 +1165,8 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
         kt.ms += ms; kt.launches += 1;
         KernelTime &ki = c->ktimes["kmeans_rgbw_persist_iters"];   // (launches: the iterations the launch ran, for per-iteration figures)
         ki.ms += ms; ki.launches += xh->iter;
+        static const char *const gnames[3] = {"kmeans_rgbw_persist_g4", "kmeans_rgbw_persist_g8", "kmeans_rgbw_persist_g16"};
+        for (int g = 0; g < 3; g++) c->ktimes[gnames[g]].launches += xh->group_iters[g];   // (marks: iterations whose row test ran with 4 / 8 / 16 lanes per cell; no duration)
     }
     *ran = true;
     return CNIIC_OK;

@@ -105,7 +105,7 @@ struct PsDev { uint32_t fail, pad; PsDevPtrs p; };   // fail: some block's cells
 constexpr uint32_t kPsArenaPart = (sizeof(PsBar) + 255u) & ~255u, kPsArenaFail = kPsArenaPart + ((3u * kPsPartWords * 8u + 255u) & ~255u), kPsArenaRng = kPsArenaFail + 256u;
 static_assert(sizeof(PsDev) <= 256, "PsDev has 256 bytes of the arena");
 constexpr uint32_t kPsStatusDone = 1, kPsStatusAborted = 2, kPsStatusRanges = 3;
-struct PsExit { uint32_t status, pad; uint64_t iter, moved_last, reseeds, active, pair_evals; };   // pinned: how the launch ended
+struct PsExit { uint32_t status, pad; uint64_t iter, moved_last, reseeds, active, pair_evals; uint32_t group_iters[3], pad2; };   // pinned: how the launch ended (group_iters: block 0's skip-schedule iterations with 4, 8, 16 lanes per cell)
 void launch_rgbw_assign_big(Ctx *c, const uint32_t *ckeys, const uint32_t *cweight, uint64_t U, uint32_t K, const uint32_t *cent, uint16_t *labels,
                             unsigned long long *partials, const KmDevState *st);
 struct PsSetup {                          // ps_decide's answer.  on: there is a persistent launch; then [zero_p, + zero_bytes) of its arena must be zeroed and
