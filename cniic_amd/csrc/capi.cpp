@@ -18,6 +18,7 @@
 #include "vor_small.hpp"
 #include "delta_small.hpp"
 #include "huf_small.hpp"
+#include "rle_small.hpp"
 
 using namespace cniic;
 
@@ -1322,7 +1323,7 @@ static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kme
 // CNIIC_TEST_HUF_SMALL_FLOOR_OFF=1.
 constexpr uint32_t kHufSmallFloorFew = 4;
 constexpr uint64_t kHufSmallFloorPxFew = 4096;
-static uint64_t huf_small_floor_px(uint64_t candidates, uint32_t) {
+static uint64_t huf_small_floor_px(uint64_t candidates, const CodecDesc &) {
     if (const char *e = test_env("CNIIC_TEST_HUF_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
     return candidates >= kHufSmallFloorFew ? ~0ull : kHufSmallFloorPxFew;
 }
@@ -1346,7 +1347,34 @@ static uint64_t vor_small_max_work(uint64_t candidates) {
     if (const char *e = test_env("CNIIC_TEST_VOR_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
     return candidates >= kVorSmallFloorMany ? ~0ull : candidates >= kVorSmallFloorFew ? kVorSmallFloorWorkSome : kVorSmallFloorWorkFew;
 }
-static uint64_t vor_small_floor_px(uint64_t candidates, uint32_t K) { return vor_small_max_work(candidates) / K; }   // (pixels x K <= the work)
+static uint64_t vor_small_floor_px(uint64_t candidates, const CodecDesc &d) { return vor_small_max_work(candidates) / d.arg; }   // (pixels x K <= the work)
+
+// The floor of the `hilbert(rle)` / `hilbert(rle(d))` route.  The route's call costs 0.08 - 0.10 ms before the kernel does anything a frame can
+// feel, the kernel's time is set by its heaviest frame (every frame has a CU of its own up to 256 frames: 0.04 - 0.05 ms up to 64 x 64;
+// 0.08 - 0.11 at 128 x 128 and 16384 x 1; 0.24 at 128 x 96, whose general-rectangle walk is most of it; 0.47 - 0.92 for photo-like frames of
+// 12 288 and 16 384 pixels at d = 16, where most starts run tens of f64 tests), what the workers cost grows with the number of frames.
+// Measured against the parent commit's library (tools/small_rle_probe.py, profiles/small_rle_probe.json; NOTES AN), d in {0, 4, 16, 441.7},
+// whole encode call, parent's time / this route's:
+//   1 frame:    0.59x .. 1.27x up to 64 x 64 (5 rows of 16 lost beyond the spreads, 4 won); 0.25x .. 1.15x above (20 of 24 lost)
+//   2 frames:   32 x 32 won (1.5x .. 2.2x), 64 x 64 won but for photo-like at d = 16 (0.76x, lost); above 4096 pixels 0.31x .. 0.97x
+//               (10 of 24 lost) but for d = 441.7, which tests nothing, at 128 x 128 and 16384 x 1 (1.5x .. 1.7x)
+//   4 frames:   up to 64 x 64 every row won (1.34x .. 3.1x; two of the 16 within the spreads, by one slow run of the parent's);
+//               above, 128 x 96 lost (0.56x .. 0.79x) and photo-like 128 x 128 at d = 16 lost (0.53x)
+//   8 frames:   up to 64 x 64 won (1.9x .. 4.4x); above, photo-like at d = 16 lost (0.75x, 0.77x), 128 x 96 at d = 0 tied (1.01x, 1.14x)
+//   16 frames:  up to 64 x 64 won (2.2x .. 6.3x); above, photo-like 128 x 96 at d = 16 lost (0.90x), 128 x 128 tied (0.94x), all else 1.58x and up
+//   32 frames:  every row won (1.22x .. 8.7x); 256: 6.9x .. 24x; 4096: 10x .. 29x
+// The route's time is flat up to 256 frames and the workers' grows, so a class that won with n frames wins with more.  So: in a call with
+// fewer than 4 candidate frames none takes the route; with 4 .. 31 those of at most 4096 pixels do (the largest size at which every d and
+// both contents won from 4 frames on); with 32 or more every candidate does.  That leaves with the workers some classes that would have
+// won (128 x 128 and 16384 x 1 at d <= 4 from 4 frames on, 1.35x .. 3.3x): the floor knows pixels, not contents, and d = 16 on photo-like
+// frames of those sizes lost up to 16 frames.  The testing library takes the floor away with CNIIC_TEST_RLE_SMALL_FLOOR_OFF=1.
+constexpr uint32_t kRleSmallFloorNone = 4;
+constexpr uint32_t kRleSmallFloorFew = 32;
+constexpr uint64_t kRleSmallFloorPxFew = 4096;
+static uint64_t rle_small_floor_px(uint64_t candidates, const CodecDesc &) {
+    if (const char *e = test_env("CNIIC_TEST_RLE_SMALL_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
+    return candidates >= kRleSmallFloorFew ? ~0ull : candidates >= kRleSmallFloorNone ? kRleSmallFloorPxFew : 0;
+}
 
 // A small-frame route of encode_frames.  A frame is a CANDIDATE when the route applies to the call and the frame has 1 .. max_px() pixels;
 // a candidate takes the route unless the floor or `takes` keeps it with the workers.  (max_px is a function, not its knobs' names: those
@@ -1354,7 +1382,7 @@ static uint64_t vor_small_floor_px(uint64_t candidates, uint32_t K) { return vor
 struct SmallRoute {
     bool (*applies)(const cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts);   // the codec, its argument, the call's options
     uint64_t (*max_px)();                                                                     // the route's bound under its _OFF and _MAX_PX knobs
-    uint64_t (*floor)(uint64_t candidates, uint32_t K);                                       // null, or: the most pixels of a frame in a call with so many candidates
+    uint64_t (*floor)(uint64_t candidates, const CodecDesc &d);                               // null, or: the most pixels of a frame in a call with so many candidates
     bool (*takes)(const cniic_ctx *c, const VarFrame &f);                                     // null, or: a veto on one frame
     int (*run)(cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
 };
@@ -1374,6 +1402,11 @@ static const SmallRoute kSmallRoutes[] = {
     {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *opts) { return d.kind == CODEC_HUFMAN && no_flags(opts); },
      [] { return small_route_max_px("CNIIC_TEST_HUF_SMALL_OFF", "CNIIC_TEST_HUF_SMALL_MAX_PX", kHufSmallMaxPx); }, huf_small_floor_px, nullptr,
      [](cniic_ctx *c, const CodecDesc &, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return huf_small_encode(c, fr, n); }},
+    // `hilbert(rle)` and `hilbert(rle(d))`, any d: not a frame whose size has an injected scan, which the workers follow
+    {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *) { return d.kind == CODEC_HILBERT_RLE; },
+     [] { return small_route_max_px("CNIIC_TEST_RLE_SMALL_OFF", "CNIIC_TEST_RLE_SMALL_MAX_PX", kRleSmallMaxPx); }, rle_small_floor_px,
+     [](const cniic_ctx *c, const VarFrame &f) { return !(c->scan_xy.p && c->scan_w == f.w && c->scan_h == f.h); },
+     [](cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return rle_small_encode(c, d.darg, fr, n); }},
 };
 
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
@@ -1397,7 +1430,7 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
         auto candidate = [&](const VarFrame &f) { const uint64_t px = (uint64_t)f.w * f.h; return px >= 1 && px <= max_px; };
         uint64_t candidates = 0;
         for (uint32_t j : order) candidates += candidate(fr[j]);
-        const uint64_t floor_px = r.floor ? r.floor(candidates, d.arg) : ~0ull;   // (the floor: few heavy frames -- the workers are faster)
+        const uint64_t floor_px = r.floor ? r.floor(candidates, d) : ~0ull;   // (the floor: few heavy frames -- the workers are faster)
         std::vector<VarFrame *> small;
         std::vector<uint32_t> rest;
         for (uint32_t j : order) {

@@ -15,6 +15,7 @@
 #include "delta_small.hpp"
 #include "delta_small_dec.hpp"
 #include "huf_small.hpp"
+#include "rle_small.hpp"
 #include "small_trie.hpp"
 
 #include <algorithm>
@@ -1308,6 +1309,40 @@ int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
     const uint64_t budget = test_budget(kHufSmallScratch);
     return for_chunks(fr, n, [&](const VarFrame &first) { return budget / huf_small_frame_bytes(frame_px(first)); },
                       [&](VarFrame *const *chunk, uint32_t cnt) { return delta_small_chunk(c, kSmallHuf, chunk, cnt); });
+}
+
+// ---- small `hilbert(rle)` / `hilbert(rle(d))` frames of a batch call, all at once (k_rle_small.hip)
+// A frame of the chunk whose largest frame has npx pixels takes its slot (rs_stride: a run per pixel), its row and its result row; the
+// chunks stay below 2 GiB (the testing library: below CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least).
+constexpr uint64_t kRleSmallScratch = 2ull << 30;
+static uint64_t rle_small_frame_bytes(uint64_t npx) { return rs_stride(npx) + sizeof(RleSmallRow) + sizeof(RleSmallResult); }
+
+static int rle_small_chunk(Ctx *c, double T, int mode, VarFrame *const *fr, uint32_t n) {
+    const uint64_t max_px = frame_px(*fr[0]);   // (largest first)
+    const uint64_t sstride = rs_stride(max_px);
+    std::vector<RleSmallRow> rows(n);
+    for (uint32_t i = 0; i < n; i++) rows[i] = RleSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
+    DevBuf scratch;
+    CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
+    std::vector<RleSmallResult> res;
+    CNIIC_TRY(run_rows(c, "rle_small_batch", rows, res, [&](const RleSmallRow *rows_d, RleSmallResult *res_d) {
+        return rle_small_run(c, rows_d, n, (uint32_t)max_px, T, mode, scratch.as<uint8_t>(), sstride, res_d);
+    }));
+    std::vector<SmallStream> streams(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t len = res[i].len;   // one record at least
+        if (len < 20 || len > sstride) return c->fail(CNIIC_ERR_HIP, "rle_small: a stream of %llu bytes in a slot of %llu", (unsigned long long)len, (unsigned long long)sstride);
+        streams[i] = SmallStream{i, fr[i], len};
+    }
+    return place_streams(c, scratch, sstride, n, streams, "rle_small_place");
+}
+
+int rle_small_encode(Ctx *c, double d, VarFrame *const *fr, uint32_t n) {
+    const double T = rla_threshold(d);   // (once per call)
+    const int mode = rs_mode(d, T);
+    const uint64_t budget = test_budget(kRleSmallScratch);
+    return for_chunks(fr, n, [&](const VarFrame &first) { return budget / rle_small_frame_bytes(frame_px(first)); },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return rle_small_chunk(c, T, mode, chunk, cnt); });
 }
 
 // ---- small voronoi(K) frames of a batch call, all at once (k_vor_small.hip)

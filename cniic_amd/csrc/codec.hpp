@@ -61,7 +61,10 @@ struct VarFrame {
 int cc_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
 int delta_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
 int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
+//   rle_small    `hilbert(rle)` and `hilbert(rle(d))`, any d, kRleSmallMaxPx: k_rle_small, from the pixels to the finished stream (rle_small.hpp); T(d) and the
+//                mode are found once per call; st stays zero; chunks: CNIIC_TEST_MEASURE_BUDGET
 int vor_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
+int rle_small_encode(Ctx *c, double d, VarFrame *const *fr, uint32_t n);
 
 // ---- output assembly
 // The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in

@@ -953,6 +953,14 @@ int delta_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32
 // the same for `hufman` (k_huf_small, the same body over the pixels' colours; huf_small.hpp): sstride >= hs_stride(max_px)
 int huf_small_run(Ctx *c, const DeltaSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint8_t *scratch_d, uint64_t sstride,
                   uint32_t *tmp_d, uint64_t tmp_px, DeltaSmallResult *res_d);
+// ---- k_rle_small.hip: `hilbert(rle)` / `hilbert(rle(d))` of small frames, one workgroup per frame (rle_small.hpp has the arithmetic and
+// the limits).  A row per frame: its pixels (device memory, any alignment).  Frame f's finished stream lands at scratch_d + f * sstride
+// (sstride >= rs_stride of the largest frame, a multiple of 16), its runs and its length in res_d[f].  T, mode: rla_threshold(d) and
+// rs_mode(d, T), the same for every frame of the launch.
+struct RleSmallRow { const uint8_t *src; uint32_t w, h; };
+struct RleSmallResult { uint32_t runs, len; };   // records, bytes of the stream
+int rle_small_run(Ctx *c, const RleSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, double T, int mode, uint8_t *scratch_d, uint64_t sstride,
+                  RleSmallResult *res_d);
 // ---- k_delta_small_dec.hip: the decode of small `delta` frames, one workgroup per frame (delta_small_dec.hpp has the arithmetic and the
 // limits).  A row per frame: its payload (device memory, any alignment; payload_bytes to the stream's end), where its w x h x 3 image goes
 // (device memory, any alignment) and its decoder as `leaves` words of left-aligned codes, ascending, and as many key | length << 27 words

@@ -38,6 +38,7 @@
 
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "rle_small.hpp"   // rla_accept, the threshold and the modes, shared with the small-frame route
 
 namespace cniic {
 
@@ -48,17 +49,6 @@ constexpr uint32_t kRlaWindow = kRlaPiece + kRlaMaxRun;   // 511: the pixels the
 constexpr uint32_t kRlaGroup = 64;                        // maps per composition
 constexpr uint32_t kRlaChunk = 4096;                      // k_rle.hip's flag chunk: 256 threads x 16 positions
 constexpr uint32_t kRlaPieces = kRlaChunk / kRlaPiece;    // 16
-
-// Approx::accept for a run of `count` pixels with channel sums s0 s1 s2 and the next pixel x (key r << 16 | g << 8 | b)
-__device__ __forceinline__ bool rla_accept(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t count, uint32_t x, double T) {
-#pragma clang fp contract(off)
-    const double c = (double)count;
-    const double d0 = (double)s0 / c - (double)((x >> 16) & 255u);
-    const double d1 = (double)s1 / c - (double)((x >> 8) & 255u);
-    const double d2 = (double)s2 / c - (double)(x & 255u);
-    const double s = (d0 * d0 + d1 * d1) + d2 * d2;
-    return s <= T;
-}
 
 // mode: 0 = the test (T >= 0), 1 = nothing is accepted (T < 0: d < 0 or NaN), 2 = everything is (T >= 3 * 255^2: no distance
 // reaches it -- avg_c and x_c lie in [0, 255], so each rounded square is <= 65025 and their rounded sum <= 195075)
@@ -250,23 +240,8 @@ __global__ __launch_bounds__(kRlaThreads) void k_rla_records(const uint8_t *__re
     for (uint32_t i = threadIdx.x; i < 3 * s_total; i += kRlaThreads) o[i] = s_rec[i];
 }
 
-// T(d): the largest double whose correctly rounded square root is <= d (binary search over the bit patterns of the non-negative
-// doubles, which sort as the values do; the host's sqrt is IEEE).  -1 for d < 0 or NaN: no distance is accepted.
-double rla_threshold(double d) {
-    if (!(d >= 0.0)) return -1.0;
-    if (std::isinf(d)) return d;
-    uint64_t lo = 0, hi = 0x7ff0000000000000ull;   // sqrt(lo) = 0 <= d; sqrt(+inf) > d
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        double v;
-        memcpy(&v, &mid, 8);
-        if (std::sqrt(v) <= d) lo = mid;
-        else hi = mid;
-    }
-    double t;
-    memcpy(&t, &lo, 8);
-    return t;
-}
+// T(d) (rle_small.hpp): the largest double whose correctly rounded square root is <= d; -1 for d < 0 or NaN
+double rla_threshold(double d) { return rla_threshold_of(d); }
 
 // The scan of the maps: level 0 = the pieces' maps, level l + 1 = level l's in groups of 64, up to a level of <= 64; then every
 // group's entry offset down the levels again.  (k_zipdict.hip chains its parse through the same maps.)
@@ -300,7 +275,7 @@ int rle_approx_plan(Ctx *c, const uint8_t *lin_d, uint64_t n, double d, RlePlan 
     const uint32_t npieces = (uint32_t)ceil_div(n, kRlaPiece);
     plan->nchunks = nchunks;
     const double T = rla_threshold(d);
-    const int mode = T < 0.0 ? 1 : T >= 3.0 * 255.0 * 255.0 ? 2 : 0;
+    const int mode = rla_mode(T);
     DevBuf L, maps0, chunk_runs, tot;
     RlaLevels levels;
     CNIIC_HIP_TRY(c, L.alloc(n));

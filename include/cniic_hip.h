@@ -112,7 +112,10 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * ran (a stream that does not fall into step), "hd_recheck" = the checks with a look at their result past the two blind ones, "hd_compact" =
  * 1 when the final write copied the kept symbols (k_hd_compact) and 0 when it decoded everything again; and the single decode
  * "hd_host_walk" = 1 when the host's node walk decoded the payload (an image below the GPU's minimum, a leaf deeper than 56, or a payload
- * the parallel decoder gave up with status 2). */
+ * the parallel decoder gave up with status 2).
+ * The small-frame route of `hilbert(rle)` / `hilbert(rle(d))` in cniic_codec_encode_batch_var and cniic_codec_measure_batch (described
+ * there): "rle_small_batch" = the duration of k_rle_small, with launches = the frames that took the route; "rle_small_place" = the copy of
+ * the finished streams to their destinations, one launch per chunk (none for host destinations). */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
@@ -588,7 +591,20 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
  * Stage timers: "vor_small_batch" = the duration of that kernel, with launches = the frames that took the route; "vor_small_place" = the
  * copy of the finished streams to out + f * stride.  stats[f].pair_evals counts what the route that ran evaluated -- on this route one
  * evaluation per point and iteration against its own centroid and K more for every point that was searched, on the workers what their
- * pruned search evaluated; the other four fields do not depend on the route. */
+ * pruned search evaluated; the other four fields do not depend on the route.
+ *
+ * SMALL `hilbert(rle)` and `hilbert(rle(d))` frames likewise, here and in cniic_codec_measure_batch, for any d (0, finite, +inf, negative,
+ * NaN): with DEVICE images every frame of 1 .. 16384 pixels is coded on ONE workgroup from its pixels to its finished stream -- the gather
+ * along the scan, the length of the run that would start at every position (the accept test of the single call bit for bit), the chain of
+ * true run starts, the rounded averages and the 12-byte records -- all such frames of the call in one launch, in chunks below 2 GiB of
+ * scratch whatever their number.  Larger frames, host images and a frame whose size has an injected scan (cniic_ctx_set_scan), which the
+ * workers follow, go to the worker contexts as above, and so do FEW or FEW LARGE
+ * frames (measured: the call and one CU are slower for them than the workers' whole chip): with n = the call's frames of 1 .. 16384 pixels,
+ * no frame takes the route for n < 4, those of at most 4096 pixels do for 4 <= n < 32, and every one for n >= 32.
+ * cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took shows in no output byte, status or message
+ * (CNIIC_ERR_CAPACITY with lens[f] = bytes needed and the frame's room untouched, as the single call); stats[f] stays zero.  Stage timers:
+ * "rle_small_batch" = the duration of that kernel, with launches = the frames that took the route; "rle_small_place" = the copy of the
+ * finished streams to out + f * stride; cniic_codec_measure_batch leaves both readable after its decode. */
 int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
                                      const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
                                      int32_t *rcs, cniic_kmeans_stats *stats);
