@@ -19,6 +19,7 @@
 #include "delta_small.hpp"
 #include "huf_small.hpp"
 #include "rle_small.hpp"
+#include "zd_small.hpp"
 
 using namespace cniic;
 
@@ -1376,6 +1377,35 @@ static uint64_t rle_small_floor_px(uint64_t candidates, const CodecDesc &) {
     return candidates >= kRleSmallFloorFew ? ~0ull : candidates >= kRleSmallFloorNone ? kRleSmallFloorPxFew : 0;
 }
 
+// The floor of the `zip(dict)` route.  The coder stays serial inside a frame: one workgroup needs 4.9 - 6.1 ms for a frame of 32 x 32,
+// 16 - 22 ms for 64 x 64, 46 - 54 ms for 128 x 96 and 60 - 73 ms for 128 x 128 or 16384 x 1 (k_zd_small's own duration, flat up to 32
+// frames; twice that with 256 frames of 12 288 pixels or more), where the host's walk on a worker needs 0.24 / 0.95 / 2.9 / 3.7 ms for one
+// such frame and 9.5 / 31 / 95 / 123 ms for 256.  Measured against the parent commit's library (tools/small_zip_probe.py,
+// profiles/small_zip_probe.json; NOTES AO), photo-like, uniform noise and photo-like with a flat band, whole encode call, parent's time /
+// this route's:
+//   1, 4, 8 frames:  every size lost (0.04x .. 0.10x; one row 0.40x by a slow run of the parent's)
+//   32 frames:       every size lost (0.19x .. 0.29x)
+//   256 frames:      32 x 32 won (1.62x .. 1.67x; the banded row within the spreads), 64 x 64 won (1.35x .. 1.60x); 128 x 96, 128 x 128 and
+//                    16384 x 1 lost (0.81x .. 0.87x; banded frames of these sizes, which the kernel gives up half-way, 0.59x)
+//   4096 frames:     32 x 32 won (4.1x .. 4.3x), 64 x 64 won (3.0x .. 3.1x); the larger sizes were not probed at this count
+// cniic_codec_measure_batch follows (256 frames: 1.27x .. 1.46x; 4096: 1.9x .. 2.4x).  So a frame is a candidate with at most 4096 pixels
+// -- the largest size that won -- and the candidates take the route in a call with 256 of them or more, the smallest probed count that
+// won; every other frame stays with the workers.  FLAT frames, every one of which the kernel hands back after 3.4 - 3.6 ms (14 - 22 ms
+// for 4096 of them), lose that attempt whatever the floor says, since it knows pixels and not contents: 256 flat frames of 32 x 32 0.62x
+// (9.4 ms against 5.8), of 64 x 64 0.85x, 4096 of them 0.87x and 0.94x.  The testing library takes the floor away, the pixel bound
+// included, with CNIIC_TEST_ZD_SMALL_FLOOR_OFF=1.
+constexpr uint32_t kZdSmallFloorFrames = 256;
+constexpr uint64_t kZdSmallFloorPx = 4096;
+static bool zd_small_floor_off() {
+    if (const char *e = test_env("CNIIC_TEST_ZD_SMALL_FLOOR_OFF")) return atoi(e) != 0;
+    return false;
+}
+static uint64_t zd_small_max_px() {
+    const uint64_t bound = small_route_max_px("CNIIC_TEST_ZD_SMALL_OFF", "CNIIC_TEST_ZD_SMALL_MAX_PX", kZdSmallMaxPx);
+    return zd_small_floor_off() ? bound : std::min(bound, kZdSmallFloorPx);
+}
+static uint64_t zd_small_floor_px(uint64_t candidates, const CodecDesc &) { return zd_small_floor_off() || candidates >= kZdSmallFloorFrames ? ~0ull : 0; }
+
 // A small-frame route of encode_frames.  A frame is a CANDIDATE when the route applies to the call and the frame has 1 .. max_px() pixels;
 // a candidate takes the route unless the floor or `takes` keeps it with the workers.  (max_px is a function, not its knobs' names: those
 // must not be in the release library, and small_route_max_px folds them away only as arguments of a call.)
@@ -1407,6 +1437,10 @@ static const SmallRoute kSmallRoutes[] = {
      [] { return small_route_max_px("CNIIC_TEST_RLE_SMALL_OFF", "CNIIC_TEST_RLE_SMALL_MAX_PX", kRleSmallMaxPx); }, rle_small_floor_px,
      [](const cniic_ctx *c, const VarFrame &f) { return !(c->scan_xy.p && c->scan_w == f.w && c->scan_h == f.h); },
      [](cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return rle_small_encode(c, d.darg, fr, n); }},
+    // `zip(dict)`, whatever the options hold (the single call ignores them for this codec); a frame the kernel gives up comes back handed_back
+    {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *) { return d.kind == CODEC_ZIP_DICT; },
+     zd_small_max_px, zd_small_floor_px, nullptr,
+     [](cniic_ctx *c, const CodecDesc &, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return zd_small_encode(c, fr, n); }},
 };
 
 static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
@@ -1444,6 +1478,14 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
         mine.swap(c->ktimes);
         CNIIC_TRY(rc);
         if (c->timers) for (const auto &e : mine) { kt[e.first].ms += e.second.ms; kt[e.first].launches += e.second.launches; }
+        // (a frame the route handed back joins the workers' frames, at its place in the order)
+        if (std::any_of(small.begin(), small.end(), [](const VarFrame *f) { return f->handed_back; })) {
+            std::vector<uint8_t> stays(n, 0);
+            for (uint32_t j : rest) stays[j] = 1;
+            for (VarFrame *f : small) if (f->handed_back) { stays[f - fr.data()] = 1; f->handed_back = false; }
+            rest.clear();
+            for (uint32_t j : order) if (stays[j]) rest.push_back(j);
+        }
         order.swap(rest);
     }
     const uint32_t nw = (uint32_t)order.size();

@@ -16,6 +16,7 @@
 #include "delta_small_dec.hpp"
 #include "huf_small.hpp"
 #include "rle_small.hpp"
+#include "zd_small.hpp"
 #include "small_trie.hpp"
 
 #include <algorithm>
@@ -1343,6 +1344,57 @@ int rle_small_encode(Ctx *c, double d, VarFrame *const *fr, uint32_t n) {
     const uint64_t budget = test_budget(kRleSmallScratch);
     return for_chunks(fr, n, [&](const VarFrame &first) { return budget / rle_small_frame_bytes(frame_px(first)); },
                       [&](VarFrame *const *chunk, uint32_t cnt) { return rle_small_chunk(c, T, mode, chunk, cnt); });
+}
+
+// ---- small `zip(dict)` frames of a batch call, all at once (k_zd_small.hip)
+// A frame of the chunk whose largest frame has npx pixels takes its slot (zs_stride: 4 bytes a pair), its trie table (8 bytes a slot, at
+// least two slots per byte of text), its row and its result row; the chunks stay below 1 GiB -- 235 frames of 16 384 pixels -- (the
+// testing library: below CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least).
+constexpr uint64_t kZdSmallScratch = 1ull << 30;
+static uint64_t zd_small_frame_bytes(uint64_t npx) {
+    const uint64_t N = zs_text_len((uint32_t)npx);
+    return zs_stride(N) + (8ull << zs_table_bits(N)) + sizeof(ZdSmallRow) + sizeof(ZdSmallResult);
+}
+// a stage mark that is a count, not a time
+static void stage_count(Ctx *c, const char *name, uint64_t n) {
+    if (c->timers && n) c->ktimes[name].launches += n;
+}
+
+static int zd_small_chunk(Ctx *c, uint32_t spec, uint32_t giveup, VarFrame *const *fr, uint32_t n) {
+    const uint64_t max_px = frame_px(*fr[0]);   // (largest first)
+    const uint64_t N = zs_text_len((uint32_t)max_px), sstride = zs_stride(N);
+    const uint32_t bits = zs_table_bits(N);
+    std::vector<ZdSmallRow> rows(n);
+    for (uint32_t i = 0; i < n; i++) rows[i] = ZdSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
+    DevBuf scratch, tables;
+    CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
+    CNIIC_HIP_TRY(c, tables.alloc(((uint64_t)n << bits) * sizeof(uint64_t)));
+    std::vector<ZdSmallResult> res;
+    CNIIC_TRY(run_rows(c, "zd_small_batch", rows, res, [&](const ZdSmallRow *rows_d, ZdSmallResult *res_d) {
+        return zd_small_run(c, rows_d, n, (uint32_t)max_px, spec, giveup, tables.as<uint64_t>(), bits, scratch.as<uint8_t>(), sstride, res_d);
+    }));
+    std::vector<SmallStream> streams;
+    uint64_t back = 0, finished = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        finished += res[i].finished;
+        if (res[i].verdict == kZsHandedBack) { fr[i]->handed_back = true; back++; continue; }
+        const uint64_t len = res[i].len;   // one pair at least
+        if (res[i].verdict != kZsOk || len < 4 || len != 4ull * res[i].pairs || len > sstride)
+            return c->fail(CNIIC_ERR_HIP, "zd_small: a stream of %llu bytes in a slot of %llu", (unsigned long long)len, (unsigned long long)sstride);
+        streams.push_back(SmallStream{i, fr[i], len});
+    }
+    stage_count(c, "zd_small_handback", back);
+    stage_count(c, "zd_small_finished", finished);
+    return place_streams(c, scratch, sstride, n, streams, "zd_small_place");
+}
+
+int zd_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
+    uint32_t giveup = kZsGiveUp;   // the testing library lowers both caps with one knob
+    if (const char *e = test_env("CNIIC_TEST_ZD_SMALL_CAP")) giveup = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kZsGiveUp);
+    const uint32_t spec = std::min(kZsSpecCap, giveup);
+    const uint64_t budget = test_budget(kZdSmallScratch);
+    return for_chunks(fr, n, [&](const VarFrame &first) { return budget / zd_small_frame_bytes(frame_px(first)); },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return zd_small_chunk(c, spec, giveup, chunk, cnt); });
 }
 
 // ---- small voronoi(K) frames of a batch call, all at once (k_vor_small.hip)

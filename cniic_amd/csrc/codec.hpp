@@ -43,6 +43,7 @@ struct VarFrame {
     int32_t rc = CNIIC_OK;
     cniic_kmeans_stats st{};
     std::string msg;
+    bool handed_back = false;       // a small-frame route gave the frame up: encode_frames sends it to the workers
 };
 // ---- the small-frame encode routes (codec.cpp; capi.cpp kSmallRoutes picks the frames)
 // Each codes n > 0 small frames (DEVICE images of 1 .. the route's bound pixels, largest first; all destinations host or all device memory)
@@ -65,6 +66,11 @@ int huf_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
 //                mode are found once per call; st stays zero; chunks: CNIIC_TEST_MEASURE_BUDGET
 int vor_small_encode(Ctx *c, uint32_t K, const cniic_kmeans_opts *opts, VarFrame *const *fr, uint32_t n);
 int rle_small_encode(Ctx *c, double d, VarFrame *const *fr, uint32_t n);
+//   zd_small     `zip(dict)`, kZdSmallMaxPx: k_zd_small, from the pixels to the finished stream (zd_small.hpp), a trie table per frame in the chunk's scratch
+//                (1 GiB; CNIIC_TEST_MEASURE_BUDGET); a frame with a match longer than kZsGiveUp bytes (the testing library: CNIIC_TEST_ZD_SMALL_CAP) comes back
+//                with handed_back set and nothing else filled in ("zd_small_handback": launches = such frames; "zd_small_finished": launches = walks the
+//                commit wave finished); st stays zero
+int zd_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
 
 // ---- output assembly
 // The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in

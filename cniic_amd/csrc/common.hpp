@@ -961,6 +961,15 @@ struct RleSmallRow { const uint8_t *src; uint32_t w, h; };
 struct RleSmallResult { uint32_t runs, len; };   // records, bytes of the stream
 int rle_small_run(Ctx *c, const RleSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, double T, int mode, uint8_t *scratch_d, uint64_t sstride,
                   RleSmallResult *res_d);
+// ---- k_zd_small.hip: `zip(dict)` of small frames, one workgroup per frame (zd_small.hpp has the arithmetic and the limits).  A row per
+// frame: its pixels (device memory, any alignment).  Frame f's finished stream lands at scratch_d + f * sstride (sstride >= zs_stride of
+// the largest frame's text, a multiple of 16), its trie in tables_d + (f << bits) (bits >= zs_table_bits of that text; zeroed here), its
+// pairs, its length and its verdict (kZsOk, or kZsHandedBack: a match longer than giveup bytes, nothing of the stream is valid) in
+// res_d[f].  spec: the bytes a speculating walk reads at most.
+struct ZdSmallRow { const uint8_t *src; uint32_t w, h; };
+struct ZdSmallResult { uint32_t pairs, len, verdict, finished; };   // ..., walks the commit finished behind the speculation's cap
+int zd_small_run(Ctx *c, const ZdSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t spec, uint32_t giveup, uint64_t *tables_d,
+                 uint32_t bits, uint8_t *scratch_d, uint64_t sstride, ZdSmallResult *res_d);
 // ---- k_delta_small_dec.hip: the decode of small `delta` frames, one workgroup per frame (delta_small_dec.hpp has the arithmetic and the
 // limits).  A row per frame: its payload (device memory, any alignment; payload_bytes to the stream's end), where its w x h x 3 image goes
 // (device memory, any alignment) and its decoder as `leaves` words of left-aligned codes, ascending, and as many key | length << 27 words

@@ -115,7 +115,11 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * the parallel decoder gave up with status 2).
  * The small-frame route of `hilbert(rle)` / `hilbert(rle(d))` in cniic_codec_encode_batch_var and cniic_codec_measure_batch (described
  * there): "rle_small_batch" = the duration of k_rle_small, with launches = the frames that took the route; "rle_small_place" = the copy of
- * the finished streams to their destinations, one launch per chunk (none for host destinations). */
+ * the finished streams to their destinations, one launch per chunk (none for host destinations).
+ * The small-frame route of `zip(dict)` there: "zd_small_batch" = the duration of k_zd_small (and of zeroing its trie tables), with
+ * launches = the frames that took the route; "zd_small_place" = the copy of the finished streams to their destinations, one launch per
+ * chunk; "zd_small_handback": launches = the frames of those the kernel gave up (a match longer than 1024 bytes) and the worker contexts
+ * coded; "zd_small_finished": launches = the walks the kernel's commit wave finished behind the speculating lanes' cap of 32 bytes. */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
@@ -604,7 +608,18 @@ int32_t cniic_codec_encode_batch(cniic_ctx *ctx, const char *expr, const cniic_k
  * cniic_codec_encode_batch (equal sizes) does not take the route.  Which route a frame took shows in no output byte, status or message
  * (CNIIC_ERR_CAPACITY with lens[f] = bytes needed and the frame's room untouched, as the single call); stats[f] stays zero.  Stage timers:
  * "rle_small_batch" = the duration of that kernel, with launches = the frames that took the route; "rle_small_place" = the copy of the
- * finished streams to out + f * stride; cniic_codec_measure_batch leaves both readable after its decode. */
+ * finished streams to out + f * stride; cniic_codec_measure_batch leaves both readable after its decode.
+ *
+ * SMALL `zip(dict)` frames likewise, here and in cniic_codec_measure_batch, whatever opts holds (the single call ignores it for this
+ * codec): with DEVICE images a frame of 1 .. 4096 pixels (the kernel itself takes 16384) is coded on ONE workgroup from its pixels to its finished
+ * stream -- the text is never written out, the dictionary's trie is a table of edges in device memory, and the coder's walks are speculated a window of 256
+ * text positions at a time and repaired from the entries the window itself made -- all such frames of the call in one launch, in chunks
+ * below 1 GiB of scratch.  A frame one of whose matches is longer than 1024 bytes (flat stretches: such a walk is one lane's chain of
+ * dependent loads) is given up by the kernel and coded by the worker contexts, as are host images and, measured, LARGER and FEW frames
+ * (one workgroup is slower for them than the workers' cores): the frames of at most 4096 pixels take the route when the call has 256 of
+ * them or more.  Which route a frame took shows in no output byte,
+ * status or message; stats[f] stays zero.  Stage timers: "zd_small_batch", "zd_small_place", "zd_small_handback" and "zd_small_finished"
+ * (above cniic_last_kernel_time). */
 int32_t cniic_codec_encode_batch_var(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
                                      const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
                                      int32_t *rcs, cniic_kmeans_stats *stats);
