@@ -26,6 +26,7 @@
 #include <functional>
 #include <memory>
 
+#include "decode_batch_plan.hpp"
 #include "huff_host.hpp"
 #include "kmeans_rgbw.hpp"
 #include "pal_bounds.hpp"
@@ -1094,16 +1095,6 @@ static int for_chunks(VarFrame *const *fr, uint32_t n, Fit frames_that_fit, Body
     return CNIIC_OK;
 }
 
-// The decode routes' chunks, whose items cost what they cost each: the end i1 of the chunk that starts at item i0 of n and takes items
-// while their cost(i) together stay within budget; the first always fits.
-template <class Cost>
-static size_t take_chunk(size_t i0, size_t n, uint64_t budget, Cost cost) {
-    size_t i1 = i0;
-    uint64_t need = 0;
-    while (i1 < n && (i1 == i0 || need + cost(i1) <= budget)) need += cost(i1++);
-    return i1;
-}
-
 // A chunk's rows go up, launch(rows, result rows) runs under the stage timer `timer` (launches = the rows), the result rows come down: one wait
 template <class Row, class Result, class Launch>
 static int run_rows(Ctx *c, const char *timer, const std::vector<Row> &rows, std::vector<Result> &res, Launch launch) {
@@ -1924,17 +1915,15 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
         CNIIC_TRY(stream_head(c, bytes, bytes_dev, nbytes, nbytes, &head));  // 16 + 19 K bytes: parsed on the host
         const uint8_t *hb = head.p;
         uint64_t K;
-        if (!get_u64(hb, nbytes, pos, K)) return c->fail(CNIIC_ERR_DECODE, "voronoi: truncated");
-        if (K > (nbytes - pos) / 19) return c->fail(CNIIC_ERR_DECODE, "voronoi: truncated centroid list");
-        std::vector<cniic_colorpos> cent(K);
-        for (uint64_t k = 0; k < K; k++) {
-            uint64_t l;
-            if (!get_u32(hb, nbytes, pos, cent[k].x) || !get_u32(hb, nbytes, pos, cent[k].y) ||
-                !get_u64(hb, nbytes, pos, l) || l != 3 || pos + 3 > nbytes)
-                return c->fail(CNIIC_ERR_DECODE, "voronoi: bad centroid");
-            memcpy(cent[k].rgb, hb + pos, 3);
-            cent[k].pad = 0;
-            pos += 3;
+        std::vector<cniic_colorpos> cent;
+        switch (vor_parse_head(hb, nbytes, pos, &K, [&](uint64_t k, uint32_t x, uint32_t y, uint8_t r, uint8_t g, uint8_t b) {
+                    if (!k) cent.reserve(K);
+                    cent.push_back(cniic_colorpos{x, y, {r, g, b}, 0});
+                })) {
+        case VorHead::Truncated: return c->fail(CNIIC_ERR_DECODE, "voronoi: truncated");
+        case VorHead::TruncatedList: return c->fail(CNIIC_ERR_DECODE, "voronoi: truncated centroid list");
+        case VorHead::BadCentroid: return c->fail(CNIIC_ERR_DECODE, "voronoi: bad centroid");
+        case VorHead::Ok: break;
         }
         if (!n) return CNIIC_OK;
         if (K == 0) return c->fail(CNIIC_ERR_DECODE, "voronoi: no centroids (min_by_key().unwrap(), clusterc.rs:184)");
@@ -1956,6 +1945,83 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
 
+// ------------------------------------------------------------------ decode of many streams: what the routes of a batch share
+// One cniic_codec_decode_batch call.  codec_decode_batch_route (at the end of this file) builds it once; every route takes it by reference.
+struct DecodeBatch {
+    Ctx *c;
+    const uint8_t *bytes; bool bytes_dev; uint64_t stride; const uint64_t *lens; uint32_t F;   // the streams: frame f at f * stride, lens[f] bytes of it
+    uint8_t *rgb; bool dst_dev; uint64_t img_stride; uint32_t *w, *h;                           // the images: frame f at f * img_stride
+    std::vector<uint8_t> &taken; std::vector<int32_t> &rcs; std::vector<std::string> &msgs;     // per frame: the route's, its status, its message
+    std::vector<uint8_t> off_route;   // tests (CNIIC_TEST_DECODE_BATCH_OFF=i,j,..): these frames through the single-stream decode
+    const uint8_t *stream(uint32_t f) const { return bytes + (uint64_t)f * stride; }
+    uint8_t *image(uint32_t f) const { return rgb + (uint64_t)f * img_stride; }
+    uint64_t view(uint32_t f) const { return std::min(lens[f], stride); }   // what a look at frame f alone may read of a batch in HBM
+    uint64_t pixels(uint32_t f) const { return (uint64_t)w[f] * h[f]; }
+    uint64_t image_bytes(uint32_t f) const { return pixels(f) * 3; }
+    void decode_error(uint32_t f, const char *msg) const { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = msg; }
+};
+
+// The streams of frames first .. last (ascending) in HBM: *base + f * stride is frame f's.  A batch in HBM is read where it lies; a host
+// batch goes up from the first frame to the last one's end, in one copy, into `keep`.
+static int streams_in_hbm(const DecodeBatch &b, uint32_t first, uint32_t last, DevBuf &keep, const uint8_t **base) {
+    *base = b.bytes;
+    if (b.bytes_dev) return CNIIC_OK;
+    const ByteSpan s = frames_span(first, last, b.stride, b.lens);
+    CNIIC_HIP_TRY(b.c, keep.alloc(s.hi - s.lo + 16));
+    CNIIC_HIP_TRY(b.c, hipMemcpyAsync(keep.p, b.bytes + s.lo, s.hi - s.lo, hipMemcpyHostToDevice, b.c->stream));
+    *base = keep.as<uint8_t>() - s.lo;
+    return CNIIC_OK;
+}
+
+// The images of a chunk's frames that cannot be written where the caller wants them: slots of one block in HBM (SlotLayout), and the two ways
+// the routes bring them down -- the whole block in one copy before the wait and a memcpy per frame behind it (down_block, put), or a copy
+// per frame (down_each).
+struct StagedImages {
+    SlotLayout lay;
+    DevBuf dev;
+    std::vector<uint8_t> host;
+    explicit StagedImages(size_t frames) : lay(frames) {}
+    void plan(size_t i, uint64_t bytes, bool needed) { lay.plan(i, bytes, needed); }
+    hipError_t alloc(Ctx *) { return lay.total ? dev.alloc(lay.total) : hipSuccess; }   // (nothing when no frame needed a slot)
+    uint8_t *dst(size_t i, uint8_t *own) const { return lay.has(i) ? dev.as<uint8_t>() + lay.at[i] : own; }
+    hipError_t down_block(Ctx *c) { host.resize(lay.total); return lay.total ? hipMemcpyAsync(host.data(), dev.p, lay.total, hipMemcpyDeviceToHost, c->stream) : hipSuccess; }
+    void put(size_t i, uint8_t *own, uint64_t n) const { if (lay.has(i)) memcpy(own, host.data() + lay.at[i], n); }
+    hipError_t down_each(Ctx *c, size_t i, uint8_t *own, uint64_t n, hipMemcpyKind kind) const {
+        return lay.has(i) ? hipMemcpyAsync(own, dev.as<uint8_t>() + lay.at[i], n, kind, c->stream) : hipSuccess;
+    }
+};
+
+// The heads: where the host reads frame f (head_p[f], head_n[f] bytes of it; nothing until a look has been taken).  A host batch is read
+// where it lies.  The heads of a batch in HBM come into the context's pinned block, c->pinned_huf, and that block has other users:
+// delta_small_decode assembles its upload block there, small_parse_dev its rows.  The order of the calls is what keeps them apart -- a
+// route runs only when the host's parse of the heads is done, and small_parse_dev reads rows[i].table before it calls delta_small_decode.
+constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
+struct Heads {
+    const DecodeBatch &b;
+    std::vector<const uint8_t *> head_p;
+    std::vector<uint64_t> head_n;
+    explicit Heads(const DecodeBatch &batch) : b(batch), head_p(batch.F), head_n(batch.F) {}
+    void in_place() { for (uint32_t f = 0; f < b.F; f++) { head_p[f] = b.stream(f); head_n[f] = b.lens[f]; } }
+    // the first W bytes of frames [f0, f1] into the pinned block, row f at (f - f0) W
+    int fetch(uint64_t W, uint32_t f0, uint32_t f1) {
+        Ctx *c = b.c;
+        const uint32_t F = b.F;
+        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(W * (f1 - f0 + 1), pinned_huf_want(W * (f1 - f0 + 1))));
+        uint8_t *ph = c->pinned_huf.as<uint8_t>();
+        const uint32_t last = F >= 2 ? std::min(f1, F - 2) : 0;   // (the batch's last frame may end before W bytes: a copy of its own)
+        if (F >= 2 && f0 <= last)
+            CNIIC_HIP_TRY(c, hipMemcpy2DAsync(ph, W, b.stream(f0), b.stride, W, last - f0 + 1, hipMemcpyDeviceToHost, c->stream));
+        if (f1 == F - 1) {
+            const uint64_t n1 = std::min(W, b.lens[F - 1]);
+            if (n1) CNIIC_HIP_TRY(c, hipMemcpyAsync(ph + (uint64_t)(F - 1 - f0) * W, b.stream(F - 1), n1, hipMemcpyDeviceToHost, c->stream));
+        }
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (uint32_t f = f0; f <= f1; f++) { head_p[f] = ph + (uint64_t)(f - f0) * W; head_n[f] = std::min(W, b.lens[f]); }
+        return CNIIC_OK;
+    }
+    bool dims(uint32_t f, uint32_t *fw, uint32_t *fh, uint64_t *pos) const { return frame_dims(head_p[f], head_n[f], fw, fh, pos); }
+};
+
 // ------------------------------------------------------------------ `hilbert(rle)` frames of a batch (whatever d they were written with)
 // The same 12-byte records at a fixed place behind the 8-byte header: nothing to parse.  A frame is taken when its header is there
 // (lens[f] >= 8), 0 < w h <= kRleBatchMaxPx and the image fits img_stride; the others are the caller's (its single decode answers for
@@ -1970,71 +2036,57 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
 constexpr size_t kBatchRouteFrames = 4096;          // frames per set of launches
 constexpr uint64_t kRleSetScratch = 2ull << 30;
 constexpr uint64_t kRleBatchMaxPx = 1ull << 18;   // 2^18 = 262 144 pixels: between the last size that won and the first that lost
-static int rle_decode_batch_route(Ctx *c, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, bool dst_dev,
-                                  uint64_t img_stride, uint32_t *w, uint32_t *h, const std::vector<const uint8_t *> &head_p, const std::vector<uint64_t> &head_n,
-                                  const std::vector<uint8_t> &off_route, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs, std::vector<std::string> &msgs) {
+static int rle_batch(DecodeBatch &b) {
+    Ctx *c = b.c;
+    Heads heads(b);   // the records follow the dimensions: the host reads those 8 bytes and nothing else
+    if (!b.bytes_dev) heads.in_place();
+    else if (b.stride >= 8 || b.F == 1) CNIIC_TRY(heads.fetch(8, 0, b.F - 1));   // (else headers that overlap: every frame to the single decode)
     std::vector<uint32_t> route;
-    for (uint32_t f = 0; f < F; f++) {
-        if (off_route[f] || lens[f] < 8) continue;
-        uint64_t pos = 0;
+    for (uint32_t f = 0; f < b.F; f++) {
+        if (b.off_route[f] || b.lens[f] < 8) continue;
+        uint64_t pos;
         uint32_t fw, fh;
-        if (!get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) continue;
-        const uint64_t n = (uint64_t)fw * fh;
-        if (!n || n > kRleBatchMaxPx || n * 3 > img_stride) continue;
-        w[f] = fw; h[f] = fh;
+        if (!heads.dims(f, &fw, &fh, &pos) || !dims_fit((uint64_t)fw * fh, kRleBatchMaxPx, b.img_stride)) continue;
+        b.w[f] = fw; b.h[f] = fh;
         route.push_back(f);
     }
     auto scratch_of = [&](uint32_t f) {   // offsets (4 bytes per record) + colours + a staged image, each rounded up
-        const uint64_t n = (uint64_t)w[f] * h[f];
-        return (lens[f] - 8) / 12 * 4 + 2 * ((n * 3 + 15) & ~15ull) + (bytes_dev ? 0 : lens[f]);
+        return (b.lens[f] - 8) / 12 * 4 + 2 * SlotLayout::room(b.image_bytes(f)) + (b.bytes_dev ? 0 : b.lens[f]);
     };
     for (size_t i0 = 0; i0 < route.size();) {
         const size_t i1 = take_chunk(i0, std::min(route.size(), i0 + kBatchRouteFrames), kRleSetScratch, [&](size_t i) { return scratch_of(route[i]); });
         const size_t S = i1 - i0;
-        // ---- the streams in HBM (a host batch: from the set's first frame to its last, in one copy), the colours and staged images
-        DevBuf up_d, lin_d, img_d;
-        const uint8_t *base = bytes;
-        if (!bytes_dev) {
-            const uint64_t lo = (uint64_t)route[i0] * stride, hi = (uint64_t)route[i1 - 1] * stride + lens[route[i1 - 1]];
-            CNIIC_HIP_TRY(c, up_d.alloc(hi - lo + 16));
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
-            base = up_d.as<uint8_t>() - lo;
-        }
+        // ---- the streams in HBM, the colours and staged images
+        DevBuf up_d, lin_d;
+        const uint8_t *base;
+        CNIIC_TRY(streams_in_hbm(b, route[i0], route[i1 - 1], up_d, &base));
         std::vector<RleBatchFrame> bf(S);
-        std::vector<uint64_t> img_at(S, ~0ull);
-        uint64_t lin_bytes = 0, img_bytes = 0;
+        SlotLayout lin(S);
+        StagedImages staged(S);
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
-            const uint64_t n = (uint64_t)w[f] * h[f], body = lens[f] - 8;
-            bf[i].rec_d = base + (uint64_t)f * stride + 8;
-            bf[i].R = body / 12; bf[i].tail_bytes = body % 12; bf[i].n = n;
-            lin_bytes += (n * 3 + 15) & ~15ull;
-            if (!dst_dev) { img_at[i] = img_bytes; img_bytes += (n * 3 + 15) & ~15ull; }
+            const uint64_t body = b.lens[f] - 8;
+            bf[i].rec_d = base + (uint64_t)f * b.stride + 8;
+            bf[i].R = body / 12; bf[i].tail_bytes = body % 12; bf[i].n = b.pixels(f);
+            lin.plan(i, b.image_bytes(f), true);
+            staged.plan(i, b.image_bytes(f), !b.dst_dev);
         }
-        CNIIC_HIP_TRY(c, lin_d.alloc(lin_bytes));
-        if (img_bytes) CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
-        uint64_t at = 0;
-        for (size_t i = 0; i < S; i++) { bf[i].lin_d = lin_d.as<uint8_t>() + at; at += (bf[i].n * 3 + 15) & ~15ull; }
+        CNIIC_HIP_TRY(c, lin_d.alloc(lin.total));
+        CNIIC_HIP_TRY(c, staged.alloc(c));
+        for (size_t i = 0; i < S; i++) bf[i].lin_d = lin_d.as<uint8_t>() + lin.at[i];
         RleBatchScratch keep;
         ScopedKernelTimer timer(c, "rle_dec_batch");
         CNIIC_TRY(rle_expand_batch_dev(c, bf, &keep));
-        for (size_t i = 0; i < S; i++) {   // follow the traversal (hilbertc.rs:58-61)
-            const uint32_t f = route[i0 + i];
-            uint8_t *dst = img_at[i] != ~0ull ? img_d.as<uint8_t>() + img_at[i] : rgb + (uint64_t)f * img_stride;
-            CNIIC_TRY(hilbert_scatter(c, bf[i].lin_d, w[f], h[f], dst));
-        }
+        for (size_t i = 0; i < S; i++)   // follow the traversal (hilbertc.rs:58-61)
+            CNIIC_TRY(hilbert_scatter(c, bf[i].lin_d, b.w[route[i0 + i]], b.h[route[i0 + i]], staged.dst(i, b.image(route[i0 + i]))));
         timer.stop(S);
-        for (size_t i = 0; i < S; i++) {
-            const uint32_t f = route[i0 + i];
-            if (img_at[i] != ~0ull)
-                CNIIC_HIP_TRY(c, hipMemcpyAsync(rgb + (uint64_t)f * img_stride, img_d.as<uint8_t>() + img_at[i], bf[i].n * 3, hipMemcpyDeviceToHost, c->stream));
-        }
+        for (size_t i = 0; i < S; i++) CNIIC_HIP_TRY(c, staged.down_each(c, i, b.image(route[i0 + i]), bf[i].n * 3, hipMemcpyDeviceToHost));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
         rle_expand_batch_status(bf, &keep);
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
-            taken[f] = 1;
-            if (bf[i].status) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "hilbert-rle: bad run record (assert!(count > 0) / unwrap, hilbertc.rs:327-328)"; }
+            b.taken[f] = 1;
+            if (bf[i].status) b.decode_error(f, "hilbert-rle: bad run record (assert!(count > 0) / unwrap, hilbertc.rs:327-328)");
         }
         i0 = i1;
     }
@@ -2084,44 +2136,36 @@ struct SmallDecKind {
 static const SmallDecKind kSmallDecDelta = {"delta_small_dec", "delta_small_dec_batch", "delta: cannot decode the difference stream", delta_small_dec_run, kDsdRange};
 static const SmallDecKind kSmallDecRgb = {"huf_small_dec", "huf_small_dec_batch", "Failed to decode symbol", huf_small_dec_run, kDsdUnsettled};
 // dev != nullptr: the routed frames' tables lie in HBM already ((*dev)[f]), and `tabs` is not looked at
-static int delta_small_decode(Ctx *c, const SmallDecKind &kind, const uint8_t *bytes, bool bytes_dev, uint64_t stride, const uint64_t *lens, uint8_t *rgb, bool dst_dev, uint64_t img_stride,
-                              const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route, const std::vector<std::vector<uint32_t>> &tabs,
-                              const std::vector<DeltaSmallDevTab> *dev, const std::vector<uint64_t> &pay, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
-                              std::vector<std::string> &msgs) {
+static int delta_small_decode(DecodeBatch &b, const SmallDecKind &kind, const std::vector<uint32_t> &route, const std::vector<std::vector<uint32_t>> &tabs,
+                              const std::vector<DeltaSmallDevTab> *dev, const std::vector<uint64_t> &pay) {
+    Ctx *c = b.c;
     uint32_t max_rounds = kDsdMaxRounds;
     if (const char *e = test_env("CNIIC_TEST_DELTA_SMALL_DEC_ROUNDS")) max_rounds = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kDsdMaxRounds);
     const uint64_t budget = test_budget(kDeltaSmallDecScratch);
-    auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
     auto tab_words = [&](uint32_t f) -> uint64_t { return dev ? 0 : tabs[f].size(); };
-    auto scratch_of = [&](uint32_t f) { return tab_words(f) * 4 + sizeof(DeltaSmallDecRow) + 4 + (dst_dev ? 0 : img_room(f)); };
+    auto scratch_of = [&](uint32_t f) { return tab_words(f) * 4 + sizeof(DeltaSmallDecRow) + 4 + (b.dst_dev ? 0 : SlotLayout::room(b.image_bytes(f))); };
     for (size_t i0 = 0; i0 < route.size();) {
         const size_t i1 = take_chunk(i0, route.size(), budget, [&](size_t i) { return scratch_of(route[i]); });
         const size_t S = i1 - i0;
-        // ---- the streams in HBM (a host batch: from the chunk's first frame to its last, in one copy)
-        DevBuf up_d, tab_d, img_d;
-        const uint8_t *base = bytes;
-        if (!bytes_dev) {
-            const uint64_t lo = (uint64_t)route[i0] * stride, hi = (uint64_t)route[i1 - 1] * stride + lens[route[i1 - 1]];
-            CNIIC_HIP_TRY(c, up_d.alloc(hi - lo + 16));
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
-            base = up_d.as<uint8_t>() - lo;
-        }
+        // ---- the streams in HBM
+        DevBuf up_d, tab_d;
+        const uint8_t *base;
+        CNIIC_TRY(streams_in_hbm(b, route[i0], route[i1 - 1], up_d, &base));
         // ---- one block for the rows, the status words and every frame's leaves; the staged images of a host destination
-        uint64_t words = 0, img_bytes = 0;
+        uint64_t words = 0;
         uint32_t max_px = 0;
-        for (size_t i = 0; i < S; i++) { words += tab_words(route[i0 + i]); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }
+        StagedImages staged(S);
+        std::vector<uint64_t> tab_word(S, 0);
+        for (size_t i = 0; i < S; i++) { tab_word[i] = words; words += tab_words(route[i0 + i]); staged.plan(i, b.image_bytes(route[i0 + i]), !b.dst_dev); }
         const uint64_t rows_at = 0, status_at = (S * sizeof(DeltaSmallDecRow) + 15) & ~15ull, tab_at = (status_at + S * 4 + 15) & ~15ull;
         // (assembled in the context's pinned block, which held the streams' heads until the decoders were parsed: nothing reads those any more)
         const uint64_t up_bytes = tab_at + words * 4;
         CNIIC_HIP_TRY(c, c->pinned_huf.reserve(up_bytes, pinned_huf_want(up_bytes)));
         uint8_t *up = c->pinned_huf.as<uint8_t>();
         CNIIC_HIP_TRY(c, tab_d.alloc(up_bytes));
-        if (img_bytes) CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
+        CNIIC_HIP_TRY(c, staged.alloc(c));
         DeltaSmallDecRow *rows = reinterpret_cast<DeltaSmallDecRow *>(up + rows_at);
-        std::vector<uint64_t> img_at(S, 0), tab_word(S, 0);
         std::vector<uint32_t> longest(S, 0);
-        uint64_t wat = 0, iat = 0;
-        for (size_t i = 0; i < S; i++) { tab_word[i] = wat; wat += tab_words(route[i0 + i]); }
         if (!dev)
             parallel_for((uint32_t)S, (uint32_t)std::min<size_t>(16, std::max<uint64_t>(1, words >> 16)), [&](uint32_t i, uint32_t) {
                 const std::vector<uint32_t> &t = tabs[route[i0 + i]];
@@ -2130,17 +2174,15 @@ static int delta_small_decode(Ctx *c, const SmallDecKind &kind, const uint8_t *b
             });
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
-            const uint32_t n = w[f] * h[f], L = dev ? (*dev)[f].leaves : (uint32_t)(tabs[f].size() / 2);
+            const uint32_t n = b.w[f] * b.h[f], L = dev ? (*dev)[f].leaves : (uint32_t)(tabs[f].size() / 2);
             DeltaSmallDecRow r;
-            r.payload = base + (uint64_t)f * stride + pay[f];
-            r.payload_bytes = dsd_stage_bytes(n, lens[f] - pay[f]);
+            r.payload = base + (uint64_t)f * b.stride + pay[f];
+            r.payload_bytes = dsd_stage_bytes(n, b.lens[f] - pay[f]);
             r.code = dev ? (*dev)[f].code : reinterpret_cast<const uint32_t *>(tab_d.as<uint8_t>() + tab_at) + tab_word[i];
             r.keylen = r.code + L;
-            r.leaves = L; r.w = w[f]; r.h = h[f]; r.max_len = dev ? (*dev)[f].max_len : longest[i];
-            r.dst = dst_dev ? rgb + (uint64_t)f * img_stride : img_d.as<uint8_t>() + iat;
+            r.leaves = L; r.w = b.w[f]; r.h = b.h[f]; r.max_len = dev ? (*dev)[f].max_len : longest[i];
+            r.dst = staged.dst(i, b.image(f));
             rows[i] = r;
-            img_at[i] = iat;
-            if (!dst_dev) iat += img_room(f);
             max_px = std::max(max_px, n);
         }
         memset(up + status_at, 0xff, S * 4);
@@ -2152,18 +2194,17 @@ static int delta_small_decode(Ctx *c, const SmallDecKind &kind, const uint8_t *b
             t.stop(S);
         }
         std::vector<uint32_t> st(S);
-        std::vector<uint8_t> imgs_h(img_bytes);
         CNIIC_HIP_TRY(c, hipMemcpyAsync(st.data(), tab_d.as<uint8_t>() + status_at, S * 4, hipMemcpyDeviceToHost, c->stream));
-        if (img_bytes) CNIIC_HIP_TRY(c, hipMemcpyAsync(imgs_h.data(), img_d.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, staged.down_block(c));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
             if (st[i] == kDsdUnsettled) continue;   // the caller's
             if (st[i] > kind.last_status) return c->fail(CNIIC_ERR_HIP, "%s: frame %u reported no status", kind.name, f);
-            taken[f] = 1;
-            if (st[i] == kDsdShort) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = kind.short_msg; }
-            else if (st[i] == kDsdRange) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "delta: colour out of range (hilbertc.rs:505)"; }
-            else if (!dst_dev) memcpy(rgb + (uint64_t)f * img_stride, imgs_h.data() + img_at[i], (uint64_t)w[f] * h[f] * 3);
+            b.taken[f] = 1;
+            if (st[i] == kDsdShort) b.decode_error(f, kind.short_msg);
+            else if (st[i] == kDsdRange) b.decode_error(f, "delta: colour out of range (hilbertc.rs:505)");
+            else staged.put(i, b.image(f), b.image_bytes(f));
         }
         i0 = i1;
     }
@@ -2208,16 +2249,15 @@ struct SmallParseKind {
 };
 static const SmallParseKind kSmallParseDelta = {6, &kSmallDecDelta, "delta_small_dec_parse", "delta_small_dec_parse_host", false};
 static const SmallParseKind kSmallParseRgb = {11, &kSmallDecRgb, "huf_small_dec_parse", "huf_small_dec_parse_host", true};
-static int small_parse_dev(Ctx *c, const SmallParseKind &kind, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, bool dst_dev,
-                           uint64_t img_stride, uint32_t *w, uint32_t *h, const std::vector<uint8_t> &off_route, uint64_t max_px, uint32_t floor, std::vector<uint8_t> &taken,
-                           std::vector<int32_t> &rcs, std::vector<std::string> &msgs, std::vector<uint32_t> &host) {
+static int small_parse_dev(DecodeBatch &b, const SmallParseKind &kind, uint64_t max_px, uint32_t floor, std::vector<uint32_t> &host) {
+    Ctx *c = b.c;
+    const uint32_t F = b.F;
     host.clear();
     std::vector<uint32_t> cands;
-    auto view = [&](uint32_t f) { return std::min(lens[f], stride); };
-    auto room_of = [&](uint32_t f) { return kind.sym_bytes == 6 ? st_leaves_room<6>(view(f)) : st_leaves_room<11>(view(f)); };
+    auto room_of = [&](uint32_t f) { return kind.sym_bytes == 6 ? st_leaves_room<6>(b.view(f)) : st_leaves_room<11>(b.view(f)); };
     auto everything = [&]() { host.resize(F); for (uint32_t f = 0; f < F; f++) host[f] = f; };
     const uint64_t longest_small = kind.rgb ? hs_stream_bytes(max_px, (uint64_t)kDeltaSmallMaxCodeLen * max_px) : ~0ull;
-    for (uint32_t f = 0; f < F; f++) if (!off_route[f] && lens[f] >= 8 && lens[f] <= longest_small && view(f) >= 8) cands.push_back(f);
+    for (uint32_t f = 0; f < F; f++) if (!b.off_route[f] && b.lens[f] >= 8 && b.lens[f] <= longest_small && b.view(f) >= 8) cands.push_back(f);
     if (kind.rgb && (cands.empty() || cands.size() < floor)) { everything(); return CNIIC_OK; }   // (the parse does not run: no stage of its)
     if (c->timers) { (void)c->ktimes[kind.timer]; (void)c->ktimes[kind.timer_host]; }
     if (cands.empty()) return CNIIC_OK;
@@ -2247,16 +2287,16 @@ static int small_parse_dev(Ctx *c, const SmallParseKind &kind, const uint8_t *by
             uint64_t wat = 0;
             for (size_t i = 0; i < S; i++) {
                 const uint32_t f = list[i0 + i];
-                rows[i].stream = bytes + (uint64_t)f * stride;
+                rows[i].stream = b.stream(f);
                 rows[i].table = tab0 + wat;
-                rows[i].bytes = view(f);
+                rows[i].bytes = b.view(f);
                 wat += 2ull * room_of(f);
-                longest = std::max(longest, view(f));
+                longest = std::max(longest, b.view(f));
             }
             CNIIC_HIP_TRY(c, hipMemcpyAsync(blk_d.p, rows, S * sizeof(SmallTrieRow), hipMemcpyHostToDevice, c->stream));
             {
                 ScopedKernelTimer t(c, kind.timer);
-                CNIIC_TRY(small_trie_run(c, kind.sym_bytes, blk_d.as<SmallTrieRow>(), (uint32_t)S, longest, (uint32_t)max_px, img_stride, scan ? c->scan_w : 0,
+                CNIIC_TRY(small_trie_run(c, kind.sym_bytes, blk_d.as<SmallTrieRow>(), (uint32_t)S, longest, (uint32_t)max_px, b.img_stride, scan ? c->scan_w : 0,
                                          scan ? c->scan_h : 0, reinterpret_cast<SmallTrieResult *>(blk_d.as<uint8_t>() + res_at)));
                 t.stop(0);
             }
@@ -2272,17 +2312,17 @@ static int small_parse_dev(Ctx *c, const SmallParseKind &kind, const uint8_t *by
                 if (r.verdict == kStSkipped) { handed += first && kind.rgb; continue; }   // (`delta`: the host's parse would not look at it either)
                 if (r.verdict != kStParsed) { back[f] = 1; handed += first; continue; }
                 parsed += first;
-                if (r.leaves == 0 || r.leaves > room_of(f) || r.max_len > kDeltaSmallMaxCodeLen || r.payload_at > view(f))
+                if (r.leaves == 0 || r.leaves > room_of(f) || r.max_len > kDeltaSmallMaxCodeLen || r.payload_at > b.view(f))
                     return c->fail(CNIIC_ERR_HIP, "small_trieparse: frame %u reported a decoder outside its stream", f);
-                if (r.leaves > 1 && r.payload_at >= lens[f]) continue;   // (symbols, and no payload: the single decode answers)
+                if (r.leaves > 1 && r.payload_at >= b.lens[f]) continue;   // (symbols, and no payload: the single decode answers)
                 if (!met) { late.push_back(f); continue; }
-                w[f] = r.w; h[f] = r.h;
+                b.w[f] = r.w; b.h[f] = r.h;
                 pay[f] = r.payload_at;
                 dev[f] = DeltaSmallDevTab{rows[i].table, r.leaves, r.max_len};
                 back[f] = 0;
                 route.push_back(f);
             }
-            if (!route.empty()) CNIIC_TRY(delta_small_decode(c, *kind.dec, bytes, true, stride, lens, rgb, dst_dev, img_stride, w, h, route, no_tabs, &dev, pay, taken, rcs, msgs));
+            if (!route.empty()) CNIIC_TRY(delta_small_decode(b, *kind.dec, route, no_tabs, &dev, pay));
             i0 = i1;
         }
         return CNIIC_OK;
@@ -2300,41 +2340,40 @@ static int small_parse_dev(Ctx *c, const SmallParseKind &kind, const uint8_t *by
 }
 
 // ------------------------------------------------------------------ small `voronoi` frames of a batch (k_vor_small.hip k_vor_small_dec)
-// codec_decode_batch_route has parsed the heads exactly as codec_decode does; what it hands over are the frames whose header and whole
+// voronoi_batch has parsed the heads exactly as codec_decode does; what it hands over are the frames whose header and whole
 // centroid list are there and well formed, with 1 <= K <= kVorSmallMaxK, 1 <= w h <= kVorSmallMaxPx and an image that fits img_stride:
 // cent[f] = where frame f's centroids start in `table` (three words each: x, y, 0xRRGGBB), Ks[f] = how many.  They are worked through in
 // chunks whose scratch -- the centroids, the rows, and for a host destination the staged images -- stays below the budget: per chunk one
 // copy up, ONE launch with a workgroup per slice of kVorSmallDecSlice pixels of a frame, for a host destination one copy down (a memcpy per frame then puts the images in place),
 // one wait.  Every routed frame decodes: there is no status to fetch.
 static uint64_t vor_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_VOR_SMALL_DEC_OFF", nullptr, kVorSmallMaxPx); }
-static int vor_small_decode(Ctx *c, uint8_t *rgb, bool dst_dev, uint64_t img_stride, const uint32_t *w, const uint32_t *h, const std::vector<uint32_t> &route,
-                            const std::vector<uint32_t> &table, const std::vector<uint64_t> &cent, const std::vector<uint32_t> &Ks, std::vector<uint8_t> &taken) {
+static int vor_small_decode(DecodeBatch &b, const std::vector<uint32_t> &route, const std::vector<uint32_t> &table, const std::vector<uint64_t> &cent,
+                            const std::vector<uint32_t> &Ks) {
+    Ctx *c = b.c;
+    const uint32_t *w = b.w, *h = b.h;
     const uint64_t budget = test_budget(kVorSmallScratch);
-    auto img_room = [&](uint32_t f) { return ((uint64_t)w[f] * h[f] * 3 + 15) & ~15ull; };
     auto slices_of = [&](uint32_t f) { return (w[f] * h[f] + kVorSmallDecSlice - 1) / kVorSmallDecSlice; };   // (a workgroup's share of a frame: k_vor_small.hip)
-    auto scratch_of = [&](uint32_t f) { return (uint64_t)Ks[f] * 12 + slices_of(f) * sizeof(VorSmallDecRow) + (dst_dev ? 0 : img_room(f)); };
+    auto scratch_of = [&](uint32_t f) { return (uint64_t)Ks[f] * 12 + slices_of(f) * sizeof(VorSmallDecRow) + (b.dst_dev ? 0 : SlotLayout::room(b.image_bytes(f))); };
     for (size_t i0 = 0; i0 < route.size();) {
         const size_t i1 = take_chunk(i0, route.size(), budget, [&](size_t i) { return scratch_of(route[i]); });
         const size_t S = i1 - i0;
-        uint64_t cents = 0, img_bytes = 0, slices = 0;
-        for (size_t i = 0; i < S; i++) { cents += Ks[route[i0 + i]]; slices += slices_of(route[i0 + i]); if (!dst_dev) img_bytes += img_room(route[i0 + i]); }
+        uint64_t cents = 0, slices = 0;
+        StagedImages staged(S);
+        for (size_t i = 0; i < S; i++) { cents += Ks[route[i0 + i]]; slices += slices_of(route[i0 + i]); staged.plan(i, b.image_bytes(route[i0 + i]), !b.dst_dev); }
         const uint64_t tab_at = (slices * sizeof(VorSmallDecRow) + 15) & ~15ull, up_bytes = tab_at + cents * 12;
         std::vector<uint8_t> up(up_bytes);
-        DevBuf up_d, img_d;
+        DevBuf up_d;
         CNIIC_HIP_TRY(c, up_d.alloc(up_bytes));
-        if (img_bytes) CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
+        CNIIC_HIP_TRY(c, staged.alloc(c));
         VorSmallDecRow *rows = reinterpret_cast<VorSmallDecRow *>(up.data());
-        std::vector<uint64_t> img_at(S, 0);
-        uint64_t cat = 0, iat = 0, rat = 0;
+        uint64_t cat = 0, rat = 0;
         uint32_t max_px = 0;
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
             memcpy(up.data() + tab_at + cat * 12, table.data() + 3 * cent[f], (size_t)Ks[f] * 12);
             for (uint32_t px0 = 0; px0 < w[f] * h[f]; px0 += kVorSmallDecSlice)
-                rows[rat++] = VorSmallDecRow{dst_dev ? rgb + (uint64_t)f * img_stride : img_d.as<uint8_t>() + iat, (uint32_t)cat, Ks[f], w[f], h[f], px0, 0u};
+                rows[rat++] = VorSmallDecRow{staged.dst(i, b.image(f)), (uint32_t)cat, Ks[f], w[f], h[f], px0, 0u};
             cat += Ks[f];
-            img_at[i] = iat;
-            if (!dst_dev) iat += img_room(f);
             max_px = std::max(max_px, w[f] * h[f]);
         }
         CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, up.data(), up_bytes, hipMemcpyHostToDevice, c->stream));
@@ -2343,30 +2382,235 @@ static int vor_small_decode(Ctx *c, uint8_t *rgb, bool dst_dev, uint64_t img_str
             CNIIC_TRY(vor_small_dec_run(c, up_d.as<VorSmallDecRow>(), (uint32_t)slices, max_px, reinterpret_cast<const uint32_t *>(up_d.as<uint8_t>() + tab_at)));
             t.stop(S);
         }
-        std::vector<uint8_t> imgs_h(img_bytes);
-        if (img_bytes) CNIIC_HIP_TRY(c, hipMemcpyAsync(imgs_h.data(), img_d.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, staged.down_block(c));
         CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < S; i++) {
             const uint32_t f = route[i0 + i];
-            taken[f] = 1;
-            if (!dst_dev) memcpy(rgb + (uint64_t)f * img_stride, imgs_h.data() + img_at[i], (uint64_t)w[f] * h[f] * 3);
+            b.taken[f] = 1;
+            staged.put(i, b.image(f), b.image_bytes(f));
         }
         i0 = i1;
     }
     return CNIIC_OK;
 }
 
-// ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
+// `voronoi`: a stream is its header and at most 16 + 19 K bytes of centroids.  The heads of streams in HBM come down in groups of as many
+// rows as the pinned block holds (never wider than the stride, the source pitch of the strided copy); a group is parsed before the
+// next one takes its place.  A frame is the route's when the single decode's parse (codec_decode) goes through on what was looked
+// at and the frame is small; every other frame is the caller's, with that decode's status and message.
+static int voronoi_batch(DecodeBatch &b) {
+    Heads heads(b);
+    std::vector<uint32_t> route, table, Ks(b.F, 0);
+    std::vector<uint64_t> cent(b.F, 0);
+    const uint64_t max_px = vor_small_dec_max_px();
+    auto classify = [&](uint32_t f) {
+        if (b.off_route[f]) return;
+        uint64_t pos, K;
+        uint32_t fw, fh;
+        if (!heads.dims(f, &fw, &fh, &pos) || !dims_fit((uint64_t)fw * fh, max_px, b.img_stride)) return;
+        const size_t at = table.size();
+        const VorHead v = vor_parse_head(heads.head_p[f], heads.head_n[f], pos, &K, [&](uint64_t, uint32_t x, uint32_t y, uint8_t r, uint8_t g, uint8_t bl) {
+            table.push_back(x); table.push_back(y);
+            table.push_back((uint32_t)r << 16 | (uint32_t)g << 8 | bl);
+        });
+        if (v != VorHead::Ok || !K || K > kVorSmallMaxK) { table.resize(at); return; }   // the caller's
+        b.w[f] = fw; b.h[f] = fh;
+        cent[f] = at / 3; Ks[f] = (uint32_t)K;
+        route.push_back(f);
+    };
+    if (b.bytes_dev) {
+        const uint64_t W = std::min<uint64_t>(vs_stream_len(kVorSmallMaxK), b.stride);
+        if (!W && b.F > 1) return CNIIC_OK;   // (streams on top of one another: every frame to the single decode)
+        const uint64_t Wf = W ? W : vs_stream_len(kVorSmallMaxK);   // (one frame: its stride does not matter)
+        const uint32_t group = (uint32_t)std::max<uint64_t>(1, kBatchHeadsMax / Wf);
+        for (uint32_t f0 = 0; f0 < b.F;) {
+            const uint32_t f1 = (uint32_t)std::min<uint64_t>((uint64_t)f0 + group, b.F) - 1;
+            CNIIC_TRY(heads.fetch(Wf, f0, f1));
+            for (uint32_t f = f0; f <= f1; f++) classify(f);
+            f0 = f1 + 1;
+        }
+    } else {
+        heads.in_place();
+        for (uint32_t f = 0; f < b.F; f++) classify(f);
+    }
+    if (route.empty()) return CNIIC_OK;
+    return vor_small_decode(b, route, table, cent, Ks);
+}
+
+// ------------------------------------------------------------------ `hufman`, `cluster-colors` and `delta` frames of a batch
+// The batched route of the RGB kinds (huff_decode_batch_dev): the frames of `route` (ascending), whose decoders are lts[f] and whose
+// payloads start at pay[f], in parts of kBatchRouteFrames.
+static int huffman_tail(DecodeBatch &b, const std::vector<uint32_t> &route, const std::vector<LeafTable> &lts, const std::vector<uint64_t> &pay) {
+    Ctx *c = b.c;
+    // ---- payloads in HBM, outputs in HBM (4-byte aligned)
+    DevBuf up_d;
+    const uint8_t *base;
+    CNIIC_TRY(streams_in_hbm(b, route.front(), route.back(), up_d, &base));
+    std::vector<HdBatchFrame> bf(route.size());
+    StagedImages staged(route.size());
+    for (size_t i = 0; i < route.size(); i++)
+        staged.plan(i, b.image_bytes(route[i]), !b.dst_dev || (reinterpret_cast<uintptr_t>(b.image(route[i])) & 3));
+    CNIIC_HIP_TRY(c, staged.alloc(c));
+    for (size_t i = 0; i < route.size(); i++) {
+        const uint32_t f = route[i];
+        bf[i].lt = &lts[f];
+        bf[i].payload = base + (uint64_t)f * b.stride + pay[f];
+        bf[i].payload_bytes = b.lens[f] - pay[f];
+        bf[i].nsyms = b.pixels(f);
+        bf[i].out_d = staged.dst(i, b.image(f));
+    }
+    for (size_t i0 = 0; i0 < bf.size(); i0 += kBatchRouteFrames) {   // (the frame is a grid dimension of the launches)
+        std::vector<HdBatchFrame> part(bf.begin() + i0, bf.begin() + std::min(bf.size(), i0 + kBatchRouteFrames));
+        CNIIC_TRY(huff_decode_batch_dev(c, part));
+        for (size_t i = 0; i < part.size(); i++) bf[i0 + i].status = part[i].status;
+    }
+    for (size_t i = 0; i < route.size(); i++) {
+        const uint32_t f = route[i];
+        if (bf[i].status == 2) continue;   // not settled: the caller's
+        b.taken[f] = 1;
+        if (bf[i].status == 1) { b.decode_error(f, "Failed to decode symbol"); continue; }
+        CNIIC_HIP_TRY(c, staged.down_each(c, i, b.image(f), b.image_bytes(f), b.dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    }
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+// What the host's parse makes of a frame: the caller's; on the route; the decoder runs past the head (a second look); a small RGB frame, on the workgroup-per-frame route
+enum class Cand : uint8_t { NotRouted, Batched, PastHead, SmallRgb };
+
 // The heads of all frames come to the host together (one strided copy for streams in HBM), every decoder is parsed there (up to 16
-// threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev); `hilbert(rle)` frames have
-// no decoder to parse and go to rle_decode_batch_route with their dimensions; `delta` frames of at most kDeltaSmallDecMaxPx pixels go to
-// delta_small_decode with their tables of leaves, a workgroup per frame (larger `delta` frames are the caller's).  Whatever this route does
-// not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more than 32
-// bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
+// threads), and the frames whose symbols are RGB keys decode in one set of launches (huff_decode_batch_dev); `delta` frames of at most
+// kDeltaSmallDecMaxPx pixels go to delta_small_decode with their tables of leaves, a workgroup per frame (larger `delta` frames are the
+// caller's).
 // `delta` streams that lie in device memory are parsed there first (small_parse_dev), and so are `hufman` and `cluster-colors` streams in
 // a call with at least kHufSmallDecFloorFrames frames short enough to be small; the heads and the host's parse below are then for the
 // frames that parse hands back, and for those alone.  Streams in host memory keep the host's parse: the bytes are where the parser is.
-constexpr uint64_t kBatchHeadsMax = 256ull << 20;   // pinned bytes the heads of one batch may take (a second look is cut to fit)
+static int huffman_batch(DecodeBatch &b, bool delta) {
+    Ctx *c = b.c;
+    const uint32_t F = b.F;
+    const uint64_t *lens = b.lens;
+    const uint64_t delta_max_px = delta ? delta_small_dec_max_px() : 0;
+    uint64_t rgb_max_px = delta ? 0 : huf_small_dec_max_px();   // small `hufman` / `cluster-colors` frames: a workgroup per frame (delta_small_decode)
+    // ---- 1. streams in device memory: the decoders of small frames are parsed there, and the host looks only at the frames that parse hands back
+    std::vector<uint32_t> all;
+    const SmallParseKind *parse = !b.bytes_dev ? nullptr : delta ? (delta_small_parse_off() ? nullptr : &kSmallParseDelta) : (rgb_max_px && !huf_small_parse_off() ? &kSmallParseRgb : nullptr);
+    if (parse) {
+        CNIIC_TRY(small_parse_dev(b, *parse, delta ? delta_max_px : rgb_max_px, delta ? 0 : huf_small_dec_floor(), all));
+        if (all.empty()) return CNIIC_OK;
+    } else {
+        all.resize(F);
+        for (uint32_t f = 0; f < F; f++) all[f] = f;
+    }
+    // ---- 2. the first look
+    Heads heads(b);
+    const std::vector<const uint8_t *> &head_p = heads.head_p;
+    const std::vector<uint64_t> &head_n = heads.head_n;
+    const uint32_t fa = all.front(), fb = all.back();   // (ascending)
+    if (b.bytes_dev) {
+        uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
+        for (uint32_t f : all) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
+        if (delta) W = std::min<uint64_t>(W, 8192);   // (what a single decode first looks at of a stream of a frame this route takes; a larger frame only shows its header)
+        // (never wider than the stride, which is the source pitch of the strided copy: a stride below a header's 8 bytes reads fewer,
+        // and every frame goes to the single decode)
+        W = std::min<uint64_t>(std::max<uint64_t>(8, std::min(W, kBatchHeadsMax / (fb - fa + 1))), b.stride);
+        if (W) CNIIC_TRY(heads.fetch(W, fa, fb));
+    } else {
+        heads.in_place();
+    }
+    // ---- 3. the floor: a call with few small frames keeps the batched route for them
+    if (rgb_max_px) {
+        uint32_t candidates = 0;
+        for (uint32_t f : all) {
+            uint64_t pos;
+            uint32_t fw, fh;
+            if (b.off_route[f] || !heads.dims(f, &fw, &fh, &pos)) continue;
+            candidates += (uint64_t)fw * fh >= 1 && (uint64_t)fw * fh <= rgb_max_px;
+        }
+        if (candidates < huf_small_dec_floor()) rgb_max_px = 0;
+    }
+    // ---- 4. the decoders, parsed on the host
+    std::vector<LeafTable> lts(delta ? 16 : F);   // (`delta`: one per parsing thread; a frame keeps its leaves in two words each, delta_tabs)
+    std::vector<std::vector<uint32_t>> delta_tabs(delta || rgb_max_px ? F : 0);   // (and of the small RGB frames)
+    std::vector<uint64_t> pay(F);      // where the payload starts
+    std::vector<uint64_t> npx(F, 0);   // the header's pixels, of a frame whose header was read
+    std::vector<Cand> cand(F, Cand::NotRouted);
+    auto classify = [&](uint32_t f, uint32_t thread) {
+        cand[f] = Cand::NotRouted;
+        if (b.off_route[f]) return;
+        uint64_t pos;
+        uint32_t fw, fh;
+        if (!heads.dims(f, &fw, &fh, &pos)) return;
+        const uint64_t n = (uint64_t)fw * fh;
+        if (!dims_fit(n, 0xffffffffull, b.img_stride)) return;
+        if (delta && (n > delta_max_px || (c->scan_xy.p && c->scan_w == fw && c->scan_h == fh))) return;   // (a size with an injected scan: the single decode follows it)
+        npx[f] = n;
+        LeafTable &lt = lts[delta ? thread : f];
+        if (!huff_parse_leaves(delta ? CNIIC_SYM_SIGNED : CNIIC_SYM_RGB, head_p[f], head_n[f], pos, lt)) { if (head_n[f] < lens[f]) cand[f] = Cand::PastHead; return; }
+        if (lt.too_deep || lt.max_len > (delta ? kDeltaSmallMaxCodeLen : 32u) || lt.n() >= (1u << 20) || (lt.n() > 1 && pos >= lens[f])) return;
+        const bool small_rgb = !delta && n <= rgb_max_px && lt.max_len <= kDeltaSmallMaxCodeLen;
+        if (delta || small_rgb) {   // codes left-aligned in 32 bits, then key | length << 27 (delta_small_dec.hpp; an RGB key has 24 bits)
+            const uint32_t L = (uint32_t)lt.n();
+            std::vector<uint32_t> &tab = delta_tabs[f];
+            tab.resize(2 * (size_t)L);
+            for (uint32_t i = 0; i < L; i++) { tab[i] = (uint32_t)(lt.code[i] >> 32); tab[L + i] = dsd_keylen(lt.key[i], lt.len[i]); }
+            if (small_rgb) lt = LeafTable();   // (the two words per leaf are all the route needs)
+        }
+        b.w[f] = fw; b.h[f] = fh;
+        pay[f] = pos;
+        cand[f] = small_rgb ? Cand::SmallRgb : Cand::Batched;
+    };
+    auto parse_all = [&](const std::vector<uint32_t> &which) {
+        parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t thread) { classify(which[i], thread); });
+    };
+    parse_all(all);
+    // (the frames of the workgroup-per-frame routes -- `delta`, and the RGB kinds' frames that are small by their headers -- apart from the others)
+    std::vector<uint32_t> again, again_small;
+    uint64_t W2 = 0, W2s = 0;
+    for (uint32_t f = 0; f < F; f++)
+        if (cand[f] == Cand::PastHead) {
+            const bool small = delta || (npx[f] && npx[f] <= rgb_max_px);
+            (small ? again_small : again).push_back(f);
+            (small ? W2s : W2) = std::max(small ? W2s : W2, std::min<uint64_t>(lens[f], 4ull << 20));
+        }
+    if (!again_small.empty()) {
+        // A small frame's decoder is most of its stream (`delta`: a leaf's 7 bytes against a code of a dozen bits; `hufman`: 12 bytes), so
+        // the second look is the rule, and 4096 frames of 128 x 128 would share kBatchHeadsMax at 64 KiB each, less than their decoders.  The
+        // frames are looked at again in groups of as many rows as the pinned block holds at the full width (the tables parsed from a group
+        // are the frames' own)
+        W2s = std::min(W2s, b.stride);
+        const uint64_t rows = std::max<uint64_t>(1, kBatchHeadsMax / std::max<uint64_t>(W2s, 1));
+        for (size_t g0 = 0; g0 < again_small.size();) {
+            size_t g1 = g0 + 1;
+            while (g1 < again_small.size() && (uint64_t)again_small[g1] - again_small[g0] + 1 <= rows) g1++;
+            const uint32_t f0 = again_small[g0], f1 = again_small[g1 - 1];
+            if (W2s > head_n[f0] || W2s > head_n[f1]) {
+                CNIIC_TRY(heads.fetch(W2s, f0, f1));
+                parse_all(std::vector<uint32_t>(again_small.begin() + g0, again_small.begin() + g1));
+            }
+            g0 = g1;
+        }
+    }
+    if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
+        const uint32_t f0 = again.front(), f1 = again.back();
+        W2 = std::min({W2, b.stride, kBatchHeadsMax / (f1 - f0 + 1)});
+        if (!again_small.empty() || W2 > head_n[f0] || W2 > head_n[f1]) {   // (the small frames' look has taken the pinned block since the first one)
+            CNIIC_TRY(heads.fetch(W2, f0, f1));
+            parse_all(again);
+        }
+    }
+    // ---- 5. the routes
+    std::vector<uint32_t> route, small_route;
+    for (uint32_t f = 0; f < F; f++) if (cand[f] == Cand::Batched) route.push_back(f); else if (cand[f] == Cand::SmallRgb) small_route.push_back(f);
+    if (!small_route.empty()) CNIIC_TRY(delta_small_decode(b, kSmallDecRgb, small_route, delta_tabs, nullptr, pay));
+    if (route.empty()) return CNIIC_OK;
+    if (delta) return delta_small_decode(b, kSmallDecDelta, route, delta_tabs, nullptr, pay);
+    return huffman_tail(b, route, lts, pay);
+}
+
+// ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
+// `hilbert(rle)` frames have no decoder to parse and go to rle_batch, `voronoi` frames to voronoi_batch, the others to huffman_batch.  Whatever
+// this route does not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more
+// than 32 bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
                              uint64_t img_stride, uint32_t *w, uint32_t *h, std::vector<uint8_t> &taken, std::vector<int32_t> &rcs,
                              std::vector<std::string> &msgs) {
@@ -2377,243 +2621,20 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         return CNIIC_OK;
     if (d.kind == CODEC_VORONOI && !vor_small_dec_max_px()) return CNIIC_OK;
     const bool delta = d.kind == CODEC_DELTA;
-    const uint64_t delta_max_px = delta ? delta_small_dec_max_px() : 0;
-    if (delta && !delta_max_px) return CNIIC_OK;
-    uint64_t rgb_max_px = delta ? 0 : huf_small_dec_max_px();   // small `hufman` / `cluster-colors` frames: a workgroup per frame (delta_small_decode)
-    const bool bytes_dev = is_device_ptr(bytes), dst_dev = is_device_ptr(rgb);
-    std::vector<uint8_t> off_route(F, 0);   // tests (CNIIC_TEST_DECODE_BATCH_OFF=i,j,..): these frames through the single-stream decode
+    if (delta && !delta_small_dec_max_px()) return CNIIC_OK;
+    DecodeBatch b{c, bytes, is_device_ptr(bytes), stride, lens, F, rgb, is_device_ptr(rgb), img_stride, w, h, taken, rcs, msgs, std::vector<uint8_t>(F, 0)};
     if (const char *e = test_env("CNIIC_TEST_DECODE_BATCH_OFF"))
         for (const char *q = e; *q;) {
             char *end = nullptr;
             const unsigned long v = strtoul(q, &end, 10);
             if (end == q) break;
-            if (v < F) off_route[v] = 1;
+            if (v < F) b.off_route[v] = 1;
             q = *end ? end + 1 : end;
         }
-    // ---- the heads: where the host reads frame f (head_p[f], head_n[f] bytes of it)
-    std::vector<const uint8_t *> head_p(F);
-    std::vector<uint64_t> head_n(F);
-    auto fetch = [&](uint64_t W, uint32_t f0, uint32_t f1) -> int {   // the first W bytes of frames [f0, f1] into the pinned block, row f at (f - f0) W
-        CNIIC_HIP_TRY(c, c->pinned_huf.reserve(W * (f1 - f0 + 1), pinned_huf_want(W * (f1 - f0 + 1))));
-        uint8_t *ph = c->pinned_huf.as<uint8_t>();
-        const uint32_t last = F >= 2 ? std::min(f1, F - 2) : 0;   // (the batch's last frame may end before W bytes: a copy of its own)
-        if (F >= 2 && f0 <= last)
-            CNIIC_HIP_TRY(c, hipMemcpy2DAsync(ph, W, bytes + (uint64_t)f0 * stride, stride, W, last - f0 + 1, hipMemcpyDeviceToHost, c->stream));
-        if (f1 == F - 1) {
-            const uint64_t n1 = std::min(W, lens[F - 1]);
-            if (n1) CNIIC_HIP_TRY(c, hipMemcpyAsync(ph + (uint64_t)(F - 1 - f0) * W, bytes + (uint64_t)(F - 1) * stride, n1, hipMemcpyDeviceToHost, c->stream));
-        }
-        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (uint32_t f = f0; f <= f1; f++) { head_p[f] = ph + (uint64_t)(f - f0) * W; head_n[f] = std::min(W, lens[f]); }
-        return CNIIC_OK;
-    };
-    if (d.kind == CODEC_HILBERT_RLE) {   // the records follow the dimensions: the host reads those 8 bytes and nothing else
-        if (bytes_dev) {
-            if (stride >= 8 || F == 1) CNIIC_TRY(fetch(8, 0, F - 1));
-            else for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes; head_n[f] = 0; }   // (headers that overlap: every frame to the single decode)
-        } else {
-            for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
-        }
-        return rle_decode_batch_route(c, bytes, bytes_dev, stride, lens, F, rgb, dst_dev, img_stride, w, h, head_p, head_n, off_route, taken, rcs, msgs);
-    }
-    if (d.kind == CODEC_VORONOI) {
-        // `voronoi`: a stream is its header and at most 16 + 19 K bytes of centroids.  The heads of streams in HBM come down in groups of as many
-        // rows as the pinned block holds (never wider than the stride, the source pitch of the strided copy); a group is parsed before the
-        // next one takes its place.  A frame is the route's when the single decode's parse (codec_decode) goes through on what was looked
-        // at and the frame is small; every other frame is the caller's, with that decode's status and message.
-        std::vector<uint32_t> route, table, Ks(F, 0);
-        std::vector<uint64_t> cent(F, 0);
-        const uint64_t max_px = vor_small_dec_max_px();
-        auto classify = [&](uint32_t f) {
-            if (off_route[f]) return;
-            const uint8_t *hb = head_p[f];
-            const uint64_t nb = head_n[f];
-            uint64_t pos = 0, K;
-            uint32_t fw, fh;
-            if (!get_u32(hb, nb, pos, fw) || !get_u32(hb, nb, pos, fh) || !get_u64(hb, nb, pos, K)) return;
-            const uint64_t n = (uint64_t)fw * fh;
-            if (!n || n > max_px || n * 3 > img_stride || !K || K > kVorSmallMaxK || K > (nb - pos) / 19) return;
-            const size_t at = table.size();
-            for (uint64_t k = 0; k < K; k++) {
-                uint32_t x, y;
-                uint64_t l;
-                if (!get_u32(hb, nb, pos, x) || !get_u32(hb, nb, pos, y) || !get_u64(hb, nb, pos, l) || l != 3 || pos + 3 > nb) { table.resize(at); return; }
-                table.push_back(x); table.push_back(y);
-                table.push_back((uint32_t)hb[pos] << 16 | (uint32_t)hb[pos + 1] << 8 | hb[pos + 2]);
-                pos += 3;
-            }
-            w[f] = fw; h[f] = fh;
-            cent[f] = at / 3; Ks[f] = (uint32_t)K;
-            route.push_back(f);
-        };
-        if (bytes_dev) {
-            const uint64_t W = std::min<uint64_t>(vs_stream_len(kVorSmallMaxK), stride);
-            if (!W && F > 1) return CNIIC_OK;   // (streams on top of one another: every frame to the single decode)
-            const uint64_t Wf = W ? W : vs_stream_len(kVorSmallMaxK);   // (one frame: its stride does not matter)
-            const uint32_t group = (uint32_t)std::max<uint64_t>(1, kBatchHeadsMax / Wf);
-            for (uint32_t f0 = 0; f0 < F;) {
-                const uint32_t f1 = (uint32_t)std::min<uint64_t>((uint64_t)f0 + group, F) - 1;
-                CNIIC_TRY(fetch(Wf, f0, f1));
-                for (uint32_t f = f0; f <= f1; f++) classify(f);
-                f0 = f1 + 1;
-            }
-        } else {
-            for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; classify(f); }
-        }
-        if (route.empty()) return CNIIC_OK;
-        return vor_small_decode(c, rgb, dst_dev, img_stride, w, h, route, table, cent, Ks, taken);
-    }
-    // streams in device memory: the decoders of small frames are parsed there, and the host looks only at the frames that parse hands back
-    std::vector<uint32_t> all;
-    const SmallParseKind *parse = !bytes_dev ? nullptr : delta ? (delta_small_parse_off() ? nullptr : &kSmallParseDelta) : (rgb_max_px && !huf_small_parse_off() ? &kSmallParseRgb : nullptr);
-    if (parse) {
-        CNIIC_TRY(small_parse_dev(c, *parse, bytes, stride, lens, F, rgb, dst_dev, img_stride, w, h, off_route, delta ? delta_max_px : rgb_max_px, delta ? 0 : huf_small_dec_floor(), taken,
-                                  rcs, msgs, all));
-        if (all.empty()) return CNIIC_OK;
-    } else {
-        all.resize(F);
-        for (uint32_t f = 0; f < F; f++) all[f] = f;
-    }
-    const uint32_t fa = all.front(), fb = all.back();   // (ascending)
-    if (bytes_dev) {
-        uint64_t W = 0;   // (as a single decode looks: 1/48 of the stream, 8 KiB at least, 4 MiB at most)
-        for (uint32_t f : all) W = std::max(W, std::min<uint64_t>(lens[f], std::min<uint64_t>(std::max<uint64_t>(lens[f] / 48, 8192), 4ull << 20)));
-        if (delta) W = std::min<uint64_t>(W, 8192);   // (what a single decode first looks at of a stream of a frame this route takes; a larger frame only shows its header)
-        // (never wider than the stride, which is the source pitch of the strided copy: a stride below a header's 8 bytes reads fewer,
-        // and every frame goes to the single decode)
-        W = std::min<uint64_t>(std::max<uint64_t>(8, std::min(W, kBatchHeadsMax / (fb - fa + 1))), stride);
-        if (W) CNIIC_TRY(fetch(W, fa, fb));
-        else for (uint32_t f = fa; f <= fb; f++) { head_p[f] = bytes; head_n[f] = 0; }
-    } else {
-        for (uint32_t f = 0; f < F; f++) { head_p[f] = bytes + (uint64_t)f * stride; head_n[f] = lens[f]; }
-    }
-    if (rgb_max_px) {   // (the floor: a call with few small frames keeps the batched route for them)
-        uint32_t candidates = 0;
-        for (uint32_t f : all) {
-            uint64_t pos = 0;
-            uint32_t fw, fh;
-            if (off_route[f] || !get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) continue;
-            candidates += (uint64_t)fw * fh >= 1 && (uint64_t)fw * fh <= rgb_max_px;
-        }
-        if (candidates < huf_small_dec_floor()) rgb_max_px = 0;
-    }
-    // ---- the decoders, parsed on the host
-    std::vector<LeafTable> lts(delta ? 16 : F);   // (`delta`: one per parsing thread; a frame keeps its leaves in two words each, delta_tabs)
-    std::vector<std::vector<uint32_t>> delta_tabs(delta || rgb_max_px ? F : 0);   // (and of the small RGB frames)
-    std::vector<uint64_t> pay(F);      // where the payload starts
-    std::vector<uint64_t> npx(F, 0);   // the header's pixels, of a frame whose header was read
-    std::vector<uint8_t> cand(F, 0);   // 1: on the route; 2: the decoder runs past the head (a second look); 3: a small RGB frame, on the workgroup-per-frame route
-    auto classify = [&](uint32_t f, uint32_t thread) {
-        cand[f] = 0;
-        if (off_route[f]) return;
-        uint64_t pos = 0;
-        uint32_t fw, fh;
-        if (!get_u32(head_p[f], head_n[f], pos, fw) || !get_u32(head_p[f], head_n[f], pos, fh)) return;
-        const uint64_t n = (uint64_t)fw * fh;
-        if (!n || n >= (1ull << 32) || n * 3 > img_stride) return;
-        if (delta && (n > delta_max_px || (c->scan_xy.p && c->scan_w == fw && c->scan_h == fh))) return;   // (a size with an injected scan: the single decode follows it)
-        npx[f] = n;
-        LeafTable &lt = lts[delta ? thread : f];
-        if (!huff_parse_leaves(delta ? CNIIC_SYM_SIGNED : CNIIC_SYM_RGB, head_p[f], head_n[f], pos, lt)) { if (head_n[f] < lens[f]) cand[f] = 2; return; }
-        if (lt.too_deep || lt.max_len > (delta ? kDeltaSmallMaxCodeLen : 32u) || lt.n() >= (1u << 20) || (lt.n() > 1 && pos >= lens[f])) return;
-        const bool small_rgb = !delta && n <= rgb_max_px && lt.max_len <= kDeltaSmallMaxCodeLen;
-        if (delta || small_rgb) {   // codes left-aligned in 32 bits, then key | length << 27 (delta_small_dec.hpp; an RGB key has 24 bits)
-            const uint32_t L = (uint32_t)lt.n();
-            std::vector<uint32_t> &tab = delta_tabs[f];
-            tab.resize(2 * (size_t)L);
-            for (uint32_t i = 0; i < L; i++) { tab[i] = (uint32_t)(lt.code[i] >> 32); tab[L + i] = dsd_keylen(lt.key[i], lt.len[i]); }
-            if (small_rgb) lt = LeafTable();   // (the two words per leaf are all the route needs)
-        }
-        w[f] = fw; h[f] = fh;
-        pay[f] = pos;
-        cand[f] = small_rgb ? 3 : 1;
-    };
-    auto parse_all = [&](const std::vector<uint32_t> &which) {
-        parallel_for((uint32_t)which.size(), (uint32_t)std::min<size_t>(16, which.size()), [&](uint32_t i, uint32_t thread) { classify(which[i], thread); });
-    };
-    parse_all(all);
-    // (the frames of the workgroup-per-frame routes -- `delta`, and the RGB kinds' frames that are small by their headers -- apart from the others)
-    std::vector<uint32_t> again, again_small;
-    uint64_t W2 = 0, W2s = 0;
-    for (uint32_t f = 0; f < F; f++)
-        if (cand[f] == 2) {
-            const bool small = delta || (npx[f] && npx[f] <= rgb_max_px);
-            (small ? again_small : again).push_back(f);
-            (small ? W2s : W2) = std::max(small ? W2s : W2, std::min<uint64_t>(lens[f], 4ull << 20));
-        }
-    if (!again_small.empty()) {
-        // A small frame's decoder is most of its stream (`delta`: a leaf's 7 bytes against a code of a dozen bits; `hufman`: 12 bytes), so
-        // the second look is the rule, and 4096 frames of 128 x 128 would share kBatchHeadsMax at 64 KiB each, less than their decoders.  The
-        // frames are looked at again in groups of as many rows as the pinned block holds at the full width (the tables parsed from a group
-        // are the frames' own)
-        W2s = std::min(W2s, stride);
-        const uint64_t rows = std::max<uint64_t>(1, kBatchHeadsMax / std::max<uint64_t>(W2s, 1));
-        for (size_t g0 = 0; g0 < again_small.size();) {
-            size_t g1 = g0 + 1;
-            while (g1 < again_small.size() && (uint64_t)again_small[g1] - again_small[g0] + 1 <= rows) g1++;
-            const uint32_t f0 = again_small[g0], f1 = again_small[g1 - 1];
-            if (W2s > head_n[f0] || W2s > head_n[f1]) {
-                CNIIC_TRY(fetch(W2s, f0, f1));
-                parse_all(std::vector<uint32_t>(again_small.begin() + g0, again_small.begin() + g1));
-            }
-            g0 = g1;
-        }
-    }
-    if (!again.empty()) {   // a second, longer look at the frames whose decoders ran past the first one (one strided copy again)
-        const uint32_t f0 = again.front(), f1 = again.back();
-        W2 = std::min({W2, stride, kBatchHeadsMax / (f1 - f0 + 1)});
-        if (!again_small.empty() || W2 > head_n[f0] || W2 > head_n[f1]) {   // (the small frames' look has taken the pinned block since the first one)
-            CNIIC_TRY(fetch(W2, f0, f1));
-            parse_all(again);
-        }
-    }
-    std::vector<uint32_t> route, small_route;
-    for (uint32_t f = 0; f < F; f++) if (cand[f] == 1) route.push_back(f); else if (cand[f] == 3) small_route.push_back(f);
-    if (!small_route.empty()) CNIIC_TRY(delta_small_decode(c, kSmallDecRgb, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, small_route, delta_tabs, nullptr, pay, taken, rcs, msgs));
-    if (route.empty()) return CNIIC_OK;
-    if (delta) return delta_small_decode(c, kSmallDecDelta, bytes, bytes_dev, stride, lens, rgb, dst_dev, img_stride, w, h, route, delta_tabs, nullptr, pay, taken, rcs, msgs);
-    // ---- payloads in HBM, outputs in HBM (4-byte aligned)
-    DevBuf up_d, img_d;
-    const uint8_t *base = bytes;
-    if (!bytes_dev) {   // the streams from the first frame on the route to the last, in one copy
-        const uint64_t lo = (uint64_t)route.front() * stride, hi = (uint64_t)route.back() * stride + lens[route.back()];
-        CNIIC_HIP_TRY(c, up_d.alloc(hi - lo + 16));
-        CNIIC_HIP_TRY(c, hipMemcpyAsync(up_d.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
-        base = up_d.as<uint8_t>() - lo;
-    }
-    std::vector<HdBatchFrame> bf(route.size());
-    std::vector<uint64_t> img_at(route.size(), ~0ull);
-    uint64_t img_bytes = 0;
-    for (size_t i = 0; i < route.size(); i++) {
-        const uint32_t f = route[i];
-        const uint64_t n = (uint64_t)w[f] * h[f];
-        uint8_t *dst = rgb + (uint64_t)f * img_stride;
-        if (!dst_dev || (reinterpret_cast<uintptr_t>(dst) & 3)) { img_at[i] = img_bytes; img_bytes += (n * 3 + 15) & ~15ull; }
-        bf[i].lt = &lts[f];
-        bf[i].payload = base + (uint64_t)f * stride + pay[f];
-        bf[i].payload_bytes = lens[f] - pay[f];
-        bf[i].nsyms = n;
-        bf[i].out_d = dst;
-    }
-    if (img_bytes) {
-        CNIIC_HIP_TRY(c, img_d.alloc(img_bytes));
-        for (size_t i = 0; i < route.size(); i++) if (img_at[i] != ~0ull) bf[i].out_d = img_d.as<uint8_t>() + img_at[i];
-    }
-    for (size_t i0 = 0; i0 < bf.size(); i0 += kBatchRouteFrames) {   // (the frame is a grid dimension of the launches)
-        std::vector<HdBatchFrame> part(bf.begin() + i0, bf.begin() + std::min(bf.size(), i0 + kBatchRouteFrames));
-        CNIIC_TRY(huff_decode_batch_dev(c, part));
-        for (size_t i = 0; i < part.size(); i++) bf[i0 + i].status = part[i].status;
-    }
-    for (size_t i = 0; i < route.size(); i++) {
-        const uint32_t f = route[i];
-        if (bf[i].status == 2) continue;   // not settled: the caller's
-        taken[f] = 1;
-        if (bf[i].status == 1) { rcs[f] = CNIIC_ERR_DECODE; msgs[f] = "Failed to decode symbol"; continue; }
-        if (img_at[i] != ~0ull)
-            CNIIC_HIP_TRY(c, hipMemcpyAsync(rgb + (uint64_t)f * img_stride, bf[i].out_d, (uint64_t)w[f] * h[f] * 3, dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    }
-    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return CNIIC_OK;
+    if (d.kind == CODEC_HILBERT_RLE) return rle_batch(b);
+    if (d.kind == CODEC_VORONOI) return voronoi_batch(b);
+    return huffman_batch(b, delta);
 }
 
 }  // namespace cniic
+
