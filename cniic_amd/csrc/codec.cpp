@@ -478,7 +478,7 @@ int cc_prepare(Ctx *c, uint32_t *table_counts_d, uint32_t K, const cniic_kmeans_
     return CNIIC_OK;
 }
 
-int cc_prepare_image(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t K, const cniic_kmeans_opts *opts, CcSession **out) {
+int cc_prepare_image(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t K, const cniic_kmeans_opts *opts, CcSession **out, bool may_stage) {
     if (K == 0) return c->fail(CNIIC_ERR_BAD_ARG, "cluster-colors(0)");
     auto s = std::make_unique<CcSession>();
     s->c = c; s->K = K; s->sp_mode = true;
@@ -499,7 +499,31 @@ int cc_prepare_image(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t K, con
         if (!fused && !strcmp(e, "require")) return c->fail(CNIIC_ERR_HIP, "cluster-colors: the fused set-up launches cannot clear the K-means arenas (CNIIC_TEST_CC_FRONT=require)");
         fused = fused && strcmp(e, "split") != 0;
     }
-    CNIIC_TRY(sp_front(c, &s->sp, front, ckeys, cweight, km_rgbw_labels_internal(s->km, nullptr), km_rgbw_is_wide(s->km), fused));
+    // With a persistent launch to come (narrow labels, this context's own CUs, no back-off) the distinct colours stay where the histogram
+    // staged them: the launch's set-up and the pixel labels read them there, and the emit into the K-means arrays runs only if somebody
+    // turns out to need the arrays (km_rgbw_need_arrays: the loop of launches behind a launch that gave up).
+    // (tests: CNIIC_TEST_CC_POINTS=arrays always emits; =require makes it an error when an encode that could have left the emit out emits)
+    bool staged = may_stage && fused && front.ranges;
+    if (const char *e = test_env("CNIIC_TEST_CC_POINTS")) {
+        if (!staged && may_stage && K <= 256 && !strcmp(e, "require"))
+            return c->fail(CNIIC_ERR_HIP, "cluster-colors: the K-means would read its points from the arrays (CNIIC_TEST_CC_POINTS=require)");
+        staged = staged && strcmp(e, "arrays") != 0;
+    }
+    if (staged) km_rgbw_points_from_staging(s->km, &s->sp, &front);
+    if (c->timers && staged) c->ktimes["cc_points_staged"].launches++;   // (stage timers: which route the call took; no duration)
+    if (staged) front.ptrs.count_dev = U_dev;
+    CNIIC_TRY(sp_front(c, &s->sp, front, ckeys, cweight, km_rgbw_labels_internal(s->km, nullptr), km_rgbw_is_wide(s->km), fused, !staged, !staged));
+    if (staged) {
+        // ... and nothing waits for the count either: the launch reads it where it lies (fewer colours than clusters: every block leaves
+        // at once), its copy to the host is enqueued BEHIND the launch (encode_cluster_colors) and looked at where the result is fetched
+        // (cc_finish: cc_count_arrive).  Until then U is the upper bound everything here is sized by.
+        s->U = Umax;
+        s->count_pending = true;
+        km_rgbw_count_stays_on_device(s->km, U_dev);
+        host_trace().mark("km_create + front enq");
+        *out = s.release();
+        return CNIIC_OK;
+    }
     CNIIC_TRY(sp_wait_count(c, &s->sp));
     s->U = s->sp.U;
     if (s->U / K == 0)
@@ -586,11 +610,25 @@ static bool palette_code(const uint8_t *cent, const Count *pixels, uint32_t K, u
     return true;
 }
 
+// a session whose colour count was left on the device (cc_prepare_image): the count's copy has been enqueued behind the K-means launch --
+// wait for it, refuse fewer colours than clusters as cc_prepare_image does, and tell the state
+static int cc_count_arrive(CcSession *s) {
+    if (!s->count_pending) return CNIIC_OK;
+    Ctx *c = s->c;
+    s->count_pending = false;
+    CNIIC_TRY(sp_wait_count(c, &s->sp));
+    s->U = s->sp.U;
+    if (s->U / s->K == 0)
+        return c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu distinct colours for %u clusters (src/kmeans.rs:68)", (unsigned long long)s->U, s->K);
+    return km_rgbw_set_points(s->km, s->U);
+}
+
 int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const uint32_t *local_counts_d, uint8_t *out,
               uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
     Ctx *c = s->c;
     const uint32_t K = s->K;
-    const uint64_t U = s->U, n = (uint64_t)w * h;
+    uint64_t U = s->U;   // (an upper bound while the count is on its way: cc_count_arrive below)
+    const uint64_t n = (uint64_t)w * h;
     KmRgbwState *km = s->km;
     std::vector<uint8_t> cent(3 * (size_t)K);
     std::vector<uint64_t> members(K), wsum(K);
@@ -614,6 +652,7 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
     if (s->sp_mode) {  // every pixel's label from the partition: no table of 2^24 entries, no random read
         uint32_t *cell_start, *ckeys, *cweight;
         km_rgbw_cell_arrays(km, &cell_start, &ckeys, &cweight);
+        if (s->local_points) CNIIC_TRY(km_rgbw_need_arrays(km));   // (the shared palette's sessions always have them: cc_image_create emits)
         if (s->local_points && K <= kPuPaletteWeights.words) {
             // shared palette: THIS image's pixels per cluster (below) -- asked for first, so that the answer travels while
             // the pixel labels are computed instead of stalling the stream after them
@@ -626,8 +665,15 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
             CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
             lw_early = true;
         }
-        if (fused) CNIIC_TRY(sp_part_labels(c, &s->sp, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, partlab, &look));
-        else CNIIC_TRY(sp_pixel_labels(c, &s->sp, rgb_d, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, pixlab.p));
+        // (a state whose arrays were not emitted: the partition's colours come from the staging, as its points did; behind a launch that
+        // gave up the arrays are there on the second attempt)
+        const bool staged = km_rgbw_arrays_pending(km);
+        if (fused) CNIIC_TRY(sp_part_labels(c, &s->sp, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, partlab, &look, staged));
+        else {
+            DevBuf pl;
+            CNIIC_TRY(sp_part_labels(c, &s->sp, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, pl, nullptr, staged));
+            CNIIC_TRY(sp_pixlab(c, &s->sp, rgb_d, pl.p, wide, pixlab.p));
+        }
     } else {
         CNIIC_HIP_TRY(c, lab_d.alloc(U * (wide ? 2 : 1)));
         CNIIC_TRY(km_rgbw_labels_canonical(km, lab_d.p));
@@ -636,6 +682,8 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
         CNIIC_TRY(pixel_labels(c, rgb_d, n, key2label.p, wide, pixlab.p));
     }
     host_trace().mark("labels + pixel labels enq");
+    CNIIC_TRY(cc_count_arrive(s));   // (the count's copy lies in the stream in front of the result block's: no wait of its own)
+    U = s->U;
     const int rc_res = km_rgbw_result_end(km, cent.data(), members.data(), wsum.data(), &st);
     if (rc_res == kKmRetry && attempt == 0) continue;
     CNIIC_TRY(rc_res);
@@ -655,6 +703,7 @@ int cc_finish(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_t h, const 
         if (s->sp_mode) {  // cell-major colours, labels and pixel counts of this image: any common order will do
             uint32_t *cell_start, *ckeys, *cweight;
             km_rgbw_cell_arrays(km, &cell_start, &ckeys, &cweight);
+            CNIIC_TRY(km_rgbw_need_arrays(km));
             CNIIC_TRY(local_cluster_weights(c, ckeys, km_rgbw_labels_internal(km, nullptr), wide, U, nullptr, K, lw.as<uint64_t>(), cweight));
         } else {
             CNIIC_TRY(local_cluster_weights(c, s->keys_d.as<uint32_t>(), lab_d.p, wide, U, local_counts_d, K, lw.as<uint64_t>(),
@@ -972,6 +1021,7 @@ static int finish_frames(CcSession *s, const uint8_t *rgb_d, uint32_t w, uint32_
     if (s->sp_mode) {
         uint32_t *cell_start, *ckeys, *cweight;
         km_rgbw_cell_arrays(km, &cell_start, &ckeys, &cweight);
+        CNIIC_TRY(km_rgbw_need_arrays(km));
         CNIIC_TRY(sp_pixel_labels(c, &s->sp, rgb_d, cell_start, ckeys, km_rgbw_labels_internal(km, nullptr), wide, pixlab.p));
         host_trace().mark("frames: pixel labels enqueued");
     } else {
@@ -1471,10 +1521,11 @@ static int encode_cluster_colors(Ctx *c, const uint8_t *rgb_d, uint32_t w, uint3
     if (n >= sp_min_pixels(c) && (reinterpret_cast<uintptr_t>(rgb_d) & 15) == 0 && !(opts && (opts->flags & CNIIC_KM_BRUTE_FORCE))) {
         if (c->timers) c->ktimes["cc_pixel_partition"].launches++;   // (stage timers: which route the call took; no duration)
         CcSession *raw = nullptr;
-        CNIIC_TRY(cc_prepare_image(c, rgb_d, n, K, opts, &raw));
+        CNIIC_TRY(cc_prepare_image(c, rgb_d, n, K, opts, &raw, /*may_stage=*/init_h == nullptr));   // (given centroids: the arrays as ever)
         std::unique_ptr<CcSession> s(raw);
         if (init_h) CNIIC_TRY(km_rgbw_set_centroids(s->km, init_h));
         CNIIC_TRY(km_rgbw_run(s->km, nullptr, /*may_defer=*/true));   // (cc_finish looks at how a persistent launch ended where it fetches the result)
+        if (s->count_pending) CNIIC_TRY(sp_enqueue_count(c, &s->sp));
         host_trace().mark("km_run");
         const int rc_all = cc_finish(s.get(), rgb_d, w, h, nullptr, out, cap, len, stats);
         if (rc_all == CNIIC_OK && cent_out_h) CNIIC_TRY(cc_palette(s.get(), cent_out_h, nullptr));

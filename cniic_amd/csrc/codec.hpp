@@ -157,6 +157,8 @@ struct CcSession {
     bool local_points = false;   // ... and the points of this session are this image's colours only
     SpPlan sp;                   // large images: the pixels partitioned by colour super-cell (k_points.hip) instead of the dense table
     bool sp_mode = false;
+    bool count_pending = false;  // cc_prepare_image did not wait for the colour count: U is an upper bound until cc_count_arrive (cc_finish) has run;
+                                 // the caller enqueues the count's copy (sp_enqueue_count) behind the K-means launch
     KmRgbwState *km = nullptr;
     ~CcSession();
 };
@@ -164,7 +166,8 @@ struct CcSession {
 int cc_prepare(Ctx *c, uint32_t *table_counts_d, uint32_t K, const cniic_kmeans_opts *opts, uint32_t shard, uint32_t nshards,
                void *partials_dev, CcSession **out, const uint32_t *occ_d = nullptr);
 // the same from the image itself, through the super-cell partition (no dense table; 16-byte aligned rgb_d)
-int cc_prepare_image(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t K, const cniic_kmeans_opts *opts, CcSession **out);
+int cc_prepare_image(Ctx *c, const uint8_t *rgb_d, uint64_t npx, uint32_t K, const cniic_kmeans_opts *opts, CcSession **out,
+                     bool may_stage = true /* the persistent K-means may read the histogram's staged colours (no emit into its arrays) */);
 // shared palette over several images, through the partition: begin (this image's pixels), the caller sums the occupancy of
 // all ranks (sp_occupancy), create (K-means state over this image's colours placed in the list of all colours)
 int cc_image_begin(Ctx *c, const uint8_t *rgb_d, uint64_t npx, CcSession **out);

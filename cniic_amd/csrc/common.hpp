@@ -592,7 +592,10 @@ struct SpPlan {
 int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan, bool hist_only = false);  // asynchronous: the count arrives with sp_wait_count
 struct KmFront;  // kmeans_rgbw.hpp: the K-means' set-up dispatches, left to the caller
 // behind sp_build(hist_only): the rest of it, the K-means' set-up and the emit, in three launches (fused) or as ever
-int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide, bool fused);
+int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide, bool fused,
+             bool emit = true /* false (fused only): no emit -- the persistent launch reads the staging, km_rgbw_points_from_staging */,
+             bool count_copy = true /* false (fused only): the count's copy is the caller's to enqueue, sp_enqueue_count */);
+int sp_enqueue_count(Ctx *c, SpPlan *plan);                               // the count's copy to the host and its event, behind what is enqueued
 bool sp_front_fits(const KmFront &f);
 int sp_wait_count(Ctx *c, SpPlan *plan);                                  // plan->U on the host (waits for its copy only)
 // distinct colours, counts, initial labels -> the K-means state's cell-major arrays; (gbits, gprefix, Ug): index of the point list
@@ -604,7 +607,8 @@ int sp_pixel_labels(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const uint
                     const void *labels_d, bool wide, void *pixlab_d);
 // ... in its two steps (partition order, then image order), and the second step fused with the Huffman pack for narrow labels (k_sp_pixpack)
 int sp_part_labels(Ctx *c, const SpPlan *plan, const uint32_t *cell_start_d, const uint32_t *ckeys_d, const void *labels_d, bool wide, DevBuf &partlab,
-                   DevBuf *look /* optional: sp_pixpack's ticket and look-back words, zeroed by the kernel */);
+                   DevBuf *look /* optional: sp_pixpack's ticket and look-back words, zeroed by the kernel */,
+                   bool staged = false /* the colours from plan's staging, not from ckeys_d (a state whose arrays were not emitted) */);
 int sp_pixlab(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const void *partlab_d, bool wide, void *pixlab_d);
 int sp_pixpack(Ctx *c, const SpPlan *plan, const void *partlab_d, DevBuf &look, const uint8_t *upl_h, uint32_t hdr_bytes, uint8_t *out_d, uint64_t *done_h);
 // the block cc_finish fills for sp_pixpack (pinned: kPuCcUpload; the kernel reads it there): the K <= 256 clusters' codes and lengths, the stream's header

@@ -22,6 +22,7 @@
 #include <hip/hip_ext.h>
 
 #include "kmeans_rgbw.hpp"
+#include "sp_keys.hpp"
 
 namespace cniic {
 
@@ -488,6 +489,7 @@ struct PsCold {
     const uint32_t *keys;                 // canonical point list (empty-cluster reseed) ...
     GIdx gx;                              // ... or the index of all occupied colours
     uint64_t seed, U;
+    const uint64_t *U_dev;                // when set: U is an upper bound, the count lies here (the host had not seen it when the launch was enqueued)
 };
 // ... and what only the set-up and the write-out need sits in the launch's arena in DEVICE memory (every block reads it on entry), written by
 // k_ps_ranges; the arena's parts lie at fixed offsets from its head, the barrier words: one pointer instead of four.
@@ -570,6 +572,10 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     uint2 *tab = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(lds) + kPsOffTab);
     uint32_t *Sent = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(lds) + kPsOffS);
     const PsDev *dev = reinterpret_cast<const PsDev *>(reinterpret_cast<const uint8_t *>(a.bar) + kPsArenaFail);
+    if (dev->p.count_dev && *dev->p.count_dev < K) {   // fewer points than clusters, and the host has not seen the count yet: it refuses when it does
+        if (blockIdx.x == 0 && tid == 0) { a.cold->exit.status = kPsStatusFew; __threadfence_system(); }
+        return;
+    }
     if (dev->fail) {   // (the same word for every block: nobody starts, nobody waits)
         if (blockIdx.x == 0 && tid == 0) { a.cold->exit.status = kPsStatusRanges; __threadfence_system(); }
         return;
@@ -658,14 +664,67 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
     __syncthreads();
     // ---- the block's points: colour, pixel count and the initial label (init_assignment, kmeans.rs:61-78) of every point of its cells,
     // as one packed word each, into LDS (the cells that fit) or the packed array in memory; a wave per cell, four loads in flight per array
-    {
+    if (dev->p.sbin) {
+        // ... from the histogram's staging (PsDevPtrs, kmeans_rgbw.hpp): the cell's entries lie where its bucket's do, plus the cell's
+        // place in the bucket; key and label are made here (what k_sp_emit writes into the arrays, sp_emit_body: k_points.hip).
+        // One trip to memory per cell, as from the arrays: nothing a cell's loads depend on is loaded inside the loop --
+        //   the buckets' offsets of ALL the wave's cells first, lane k <-> its k-th cell (two a lane: kPsMaxCells / kPsWaves = 128);
+        //   a colour's rank (gidx_rank) from the index words of its cell, which are known without the colour: key >> 6 is r | g | b[7:6],
+        //   so a cell's 512 colours lie in 64 words, lane (r & 7) << 3 | (g & 7) loads one and the colour's lane reads it across.
+        static_assert(kPsMaxCells <= 128 * kPsWaves, "two cells of a wave per lane");
+        const uint32_t Cres0 = s_Cres;
+        const uint32_t *sstart = dev->p.sstart, *scnt = dev->p.scnt, *cell_start = dev->p.cell_start;
+        const uint16_t *sbin = dev->p.sbin;
+        const unsigned long long *gbits = dev->p.gbits;
+        const uint32_t *gprefix = dev->p.gprefix;
+        uint32_t *heavy = dev->p.cweight_rw;
+        const uint32_t U = (uint32_t)*dev->p.U_dev, ppc = max(U / K, 1u);
+        const float rcp = 1.0f / (float)ppc;
+        uint32_t dl[2];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const uint32_t i = (uint32_t)wid + kPsWaves * ((uint32_t)lane + 64u * q);
+            const uint32_t bucket = i < C ? (uint32_t)ccell[i] >> 6 : 0u;
+            dl[q] = i < C ? sstart[bucket] - cell_start[bucket * 64] : 0u;
+        }
+        uint32_t kth = 0;
+        for (uint32_t i = wid; i < C; i += kPsWaves, kth++) {
+            const uint32_t s = cstart[i], n = cstart[i + 1] - s, gs = gstart[i], cid = ccell[i];
+            const uint32_t bucket = cid >> 6;
+            const uint32_t ss = gs + (uint32_t)__builtin_amdgcn_readlane((int)(kth < 64 ? dl[0] : dl[1]), (int)(kth & 63u));
+            const uint32_t cbk = cell_base_key(cid);
+            const uint32_t iw = ((((cbk >> 16) & 255u) + ((uint32_t)lane >> 3)) << 10) | ((((cbk >> 8) & 255u) + ((uint32_t)lane & 7u)) << 2) | ((cbk & 255u) >> 6);
+            const unsigned long long ib = gbits[iw];
+            const uint32_t ip = gprefix[iw];
+            for (uint32_t t0 = 0; t0 < n; t0 += 256) {
+                uint32_t kk[4], ww[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t t = t0 + u * 64 + lane;
+                    const bool in = t < n;
+                    kk[u] = in ? sp_key(bucket, sbin[ss + t]) : cbk;
+                    ww[u] = in ? scnt[ss + t] : 0u;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t t = t0 + u * 64 + lane;
+                    const int from = (int)((((kk[u] >> 16) & 7u) << 3) | ((kk[u] >> 8) & 7u));   // (every lane asks: a lane outside the cell's points for its base colour)
+                    const unsigned long long wb = __shfl(ib, from, 64);
+                    const uint32_t rank = (uint32_t)__shfl((int)ip, from, 64) + (uint32_t)__popcll(wb & ((1ull << (kk[u] & 63u)) - 1ull));
+                    if (t < n) {
+                        const uint32_t w = ps_pack(kk[u], ww[u], init_label24(rank, U, K, ppc, rcp));
+                        if (i < Cres0) pts[s + t] = w; else a.pk[gs + t] = w;
+                        if (ww[u] >= 255u) heavy[gs + t] = ww[u];   // (rare: the count a mover looks up, a.cweight, where the arrays have it)
+                    }
+                }
+            }
+        }
+    } else {
         const uint32_t Cres0 = s_Cres;
         const uint32_t *ckeys = dev->p.ckeys, *cweight = dev->p.cweight;
         const uint8_t *labels0 = dev->p.labels;
         for (uint32_t i = wid; i < C; i += kPsWaves) {
             const uint32_t s = cstart[i], n = cstart[i + 1] - s, gs = gstart[i];
-            const uint32_t cbk = cell_base_key(ccell[i]);
-            (void)cbk;
             for (uint32_t t0 = 0; t0 < n; t0 += 256) {
                 uint32_t kk[4], ww[4], ll[4];
 #pragma unroll
@@ -956,7 +1015,7 @@ __global__ __launch_bounds__(kPsThreads) void k_rgbw_persist(PsArgs a) {
             uint32_t ck;
             if (run[4] == 0) {
                 const PsCold *cd = a.cold;
-                const uint64_t ri = reseed_index(cd->seed, j - 1, k, cd->U);  // fake_clone of the stolen point
+                const uint64_t ri = reseed_index(cd->seed, j - 1, k, cd->U_dev ? *cd->U_dev : cd->U);  // fake_clone of the stolen point
                 const GIdx gx = cd->gx;
                 ck = gx.bits ? gidx_select(gx, ri) : cd->keys[ri];
                 atomicAdd(&s_reseed, 1u);
@@ -1117,6 +1176,7 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     a.bar = reinterpret_cast<PsBar *>(ar);   // (the sums, PsDev and the chunk boundaries behind it: ps_decide)
     cold->cconst_g = s->cconst.as<uint2>(); cold->cent_g = s->cent.as<uint32_t>(); cold->members_out = s->members_last.as<uint64_t>(); cold->wsum_out = s->wsum_last.as<uint64_t>();
     cold->keys = s->keys; cold->gx = s->gidx; cold->seed = s->seed; cold->U = s->gidx.bits ? s->gidx.U : s->U;
+    cold->U_dev = s->count_dev;
     a.st_rw = s->dstate.as<KmDevState>(); a.cold = cold; a.max_iters = s->max_iters;
     a.K = s->K; a.max_skip = s->no_skip ? 0u : s->max_skip; a.agg_iters = kAggLaunches;
     a.test_abort_at = 0;
@@ -1157,6 +1217,7 @@ int km_rgbw_run_persistent(KmRgbwState *s, bool *ran, bool may_defer) {
     s->run_stats.iterations = xh->iter; s->run_stats.moved_last = xh->moved_last; s->run_stats.empty_reseeds = xh->reseeds;
     s->run_stats.active = xh->active; s->run_stats.pair_evals = xh->pair_evals;
     s->run_stats_valid = true;
+    s->ps_done = true;
     if (s->profile) {
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
@@ -1181,10 +1242,13 @@ int km_rgbw_persistent_verdict(KmRgbwState *s, bool *retry) {
     s->ps_hold.reset();
     const PsExit *xh = &c->pinned_ps.as<const PsCold>()->exit;
     ps_learn(c, xh->status, test_env("CNIIC_TEST_PS_ABORT_AT") != nullptr);
+    if (xh->status == kPsStatusFew)
+        return c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: fewer distinct colours than %u clusters (src/kmeans.rs:68)", s->K);
     if (xh->status == kPsStatusDone) {
         s->run_stats.iterations = xh->iter; s->run_stats.moved_last = xh->moved_last; s->run_stats.empty_reseeds = xh->reseeds;
         s->run_stats.active = xh->active; s->run_stats.pair_evals = xh->pair_evals;
         s->run_stats_valid = true;
+        s->ps_done = true;
         return CNIIC_OK;
     }
     if (test_env("CNIIC_KM_PS_REQUIRE")) return c->fail(CNIIC_ERR_HIP, "kmeans_rgbw: the persistent launch ended with status %u (CNIIC_KM_PS_REQUIRE)", xh->status);

@@ -1476,6 +1476,35 @@ int km_front_enqueue_split(Ctx *c, const KmFront &f) {
 
 void km_rgbw_destroy(KmRgbwState *s) { delete s; }
 
+void km_rgbw_points_from_staging(KmRgbwState *s, const SpPlan *plan, KmFront *front) {
+    PsDevPtrs &p = front->ptrs;
+    p.sstart = plan->sstart.as<uint32_t>(); p.sbin = plan->sbin.as<uint16_t>(); p.scnt = plan->scnt.as<uint32_t>();
+    p.cell_start = s->cell_start.as<uint32_t>();
+    p.gbits = s->gidx.bits; p.gprefix = s->gidx.wprefix; p.U_dev = plan->total.as<uint64_t>();
+    p.cweight_rw = s->cweight.as<uint32_t>();
+    s->lazy_plan = plan;
+}
+bool km_rgbw_arrays_pending(const KmRgbwState *s) { return s->lazy_plan != nullptr; }
+void km_rgbw_count_stays_on_device(KmRgbwState *s, const uint64_t *count_dev) { s->count_dev = count_dev; }
+int km_rgbw_fetch_points(KmRgbwState *s) {
+    if (!s->count_dev) return CNIIC_OK;
+    Ctx *c = s->c;
+    uint64_t U = 0;
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(&U, s->count_dev, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return km_rgbw_set_points(s, U);
+}
+int km_rgbw_need_arrays(KmRgbwState *s) {
+    if (!s->lazy_plan) return CNIIC_OK;
+    Ctx *c = s->c;
+    if (s->ps_pending) return c->fail(CNIIC_ERR_BAD_ARG, "kmeans_rgbw: the cell-major arrays are asked for while the persistent launch's verdict is out");
+    const SpPlan *plan = s->lazy_plan;
+    s->lazy_plan = nullptr;
+    if (c->timers) c->ktimes["cc_points_arrays_on_demand"].launches++;   // (stage timers: which route the call took; no duration)
+    return sp_emit(c, plan, s->cell_start.as<uint32_t>(), s->ckeys.as<uint32_t>(), s->cweight.as<uint32_t>(), s->ps_done ? nullptr : s->labels.p, s->wide, s->K,
+                   s->gidx.bits, s->gidx.wprefix, s->gidx.U, plan->total.as<uint64_t>());
+}
+
 static int launch_update(KmRgbwState *s, int mode) {
     Ctx *c = s->c;
     hipLaunchKernelGGL(k_rgbw_update, dim3(1), dim3(256), 0, c->stream, s->partials, s->running.as<uint64_t>(), mode, s->keys,
@@ -1598,6 +1627,7 @@ static void launch_assign(KmRgbwState *s, hipEvent_t ev_start = nullptr, hipEven
 }
 
 int km_rgbw_assign(KmRgbwState *s) {
+    CNIIC_TRY(km_rgbw_need_arrays(s));
     Ctx *c = s->c;
     launch_assign(s);
     if (!s->cells) {
@@ -1717,6 +1747,8 @@ static int km_rgbw_run_loop(KmRgbwState *s, Comm *cm, bool may_defer) {
         CNIIC_TRY(km_rgbw_run_persistent(s, &ran, may_defer));
         if (ran) { timer.stop(s->run_stats.iterations); return CNIIC_OK; }
     }
+    CNIIC_TRY(km_rgbw_fetch_points(s));  // (a state whose count the persistent launch read on the device: the launches are sized by it)
+    CNIIC_TRY(km_rgbw_need_arrays(s));   // (a state whose points the persistent launch took from the staging: the launches read the arrays)
     for (;;) {
         for (int b = 0; b < batch; b++) {
             if (s->fused) {
@@ -1824,6 +1856,7 @@ static int km_rgbw_run_loop(KmRgbwState *s, Comm *cm, bool may_defer) {
 // pair per launch on the ctx stream).  Labels may move towards the fixed point of the current
 // centroids; the partial sums are left inconsistent, so the state must be discarded afterwards.
 int km_rgbw_time_assign(KmRgbwState *s, int reps, double *ms_per_launch) {
+    CNIIC_TRY(km_rgbw_need_arrays(s));
     Ctx *c = s->c;
     LaunchTimer lt;
     for (int i = 0; i <= reps; i++) {  // launch 0 is a warm-up
@@ -1859,6 +1892,7 @@ bool km_rgbw_is_wide(KmRgbwState *s) { return s->wide; }
 
 // u8/u16 labels in CANONICAL point order on the device (dst holds U entries)
 int km_rgbw_labels_canonical(KmRgbwState *s, void *dst_d) {
+    CNIIC_TRY(km_rgbw_need_arrays(s));
     Ctx *c = s->c;
     if (s->cells) {
         if (s->wide)
@@ -1887,6 +1921,7 @@ __global__ void k_export_labels(const LabelT *__restrict__ labels, const uint32_
 }
 
 int km_rgbw_export_labels(KmRgbwState *s, void *dst_d) {
+    CNIIC_TRY(km_rgbw_need_arrays(s));
     Ctx *c = s->c;
     if (!s->cells) return c->fail(CNIIC_ERR_BAD_ARG, "export_labels needs the cells path");
     ensure_wave_ranges(s);
@@ -1903,6 +1938,7 @@ int km_rgbw_export_labels(KmRgbwState *s, void *dst_d) {
 }
 
 int km_rgbw_import_labels(KmRgbwState *s, const void *src_d) {
+    CNIIC_TRY(km_rgbw_need_arrays(s));
     Ctx *c = s->c;
     CNIIC_HIP_TRY(c, hipMemcpyAsync(s->labels.p, src_d, s->U * (s->wide ? 2 : 1), hipMemcpyDeviceToDevice, c->stream));
     return CNIIC_OK;
@@ -1917,6 +1953,7 @@ int km_rgbw_set_points(KmRgbwState *s, uint64_t U, uint64_t Ulist) {
         return s->c->fail(CNIIC_ERR_TOO_FEW_POINTS, "kmeans: %llu points for %u clusters (src/kmeans.rs:68)", (unsigned long long)Ulist, s->K);
     s->U = U; s->hi = U;
     if (s->gidx.bits) s->gidx.U = Ulist;
+    s->count_dev = nullptr;
     return CNIIC_OK;
 }
 

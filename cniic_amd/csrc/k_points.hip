@@ -21,7 +21,17 @@
 //   k_cc_front_b   k_gidx_finish | k_cell_scan                 (the colour count's 8-byte copy to the host follows)
 //   k_cc_front_c   k_ps_ranges | k_rgbw_init_cent | k_sp_emit
 //   -- the roles being the bodies of these kernels, which every other caller (sp_build without hist_only, the shared palette's
-//   cc_image_create, CNIIC_TEST_CC_FRONT=split) launches one by one:
+//   cc_image_create, CNIIC_TEST_CC_FRONT=split) launches one by one.
+//   With a persistent K-means launch to come (K <= 256, the context's own CUs, no given centroids; not under CNIIC_TEST_CC_POINTS=arrays)
+//   the staged colours are NOT copied into the K-means arrays: the staging is cell-major already, so the launch's set-up reads it where
+//   it lies and makes key and initial label itself (k_kmeans_persist.hip, PsDevPtrs::sbin), and k_sp_partlab reads its colours there too.
+//   The chain is then
+//   k_cc_front_b   k_gidx_finish | k_cell_scan, which also writes the launch's chunk boundaries (ps_bounds.hpp: no bisection)
+//   k_cc_front_c   the fit check of those boundaries | k_rgbw_init_cent                      (no emit role, no count copy in between)
+//   k_rgbw_persist enqueued without the host having seen the colour count; the count's 8-byte copy follows the launch and is looked at
+//                  where the result block is fetched (cc_finish).  k_sp_emit runs only if the arrays are needed after all
+//                  (km_rgbw_need_arrays: the loop of launches behind a launch that gave up).
+//   The kernels' own stories:
 //   k_bits_prefix / k_gidx_finish   bitmap -> popcount prefix = GIdx: rank of a colour in the ascending list of all colours = the
 //                  reference's point order, used for init_assignment / init_centroids / the reseed index
 //   (km_rgbw_create: arena fill, k_rgbw_init_cent, k_cell_totals, k_cell_scan, arena fill, k_ps_ranges)
@@ -41,10 +51,11 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "kmeans_rgbw.hpp"
+#include "sp_keys.hpp"
 
 namespace cniic {
 
-constexpr uint32_t kSpBuckets = 512;           // super-cells: r[7:5] g[7:5] b[7:5]
+constexpr uint32_t kSpBuckets = 512;          // super-cells: r[7:5] g[7:5] b[7:5]
 constexpr uint32_t kSpBins = 1u << 15;         // colours of a super-cell
 constexpr uint32_t kSpChunk = 1u << 16;        // pixels per chunk: a position inside a run fits 16 bits
 constexpr int kSpThreads = 1024;
@@ -52,20 +63,7 @@ constexpr uint32_t kSpSliceMin = 1u << 17;     // k_sp_partlab: entries per slic
 constexpr uint32_t kSpSlices = 8;              // ... and slices per bucket, at most
 constexpr uint32_t kSpWaves = kSpThreads / 64;
 
-__device__ __forceinline__ uint32_t sp_bucket(uint32_t key) {
-    return (((key >> 21) & 7u) << 6) | (((key >> 13) & 7u) << 3) | ((key >> 5) & 7u);
-}
-// colour inside its super-cell, cell-major: cell within the super-cell (cell_of's low 6 bits) << 9 | colour within the cell
-__device__ __forceinline__ uint32_t sp_bin(uint32_t key) {
-    const uint32_t r = (key >> 16) & 31u, g = (key >> 8) & 31u, b = key & 31u;
-    return ((r >> 3) << 13) | ((g >> 3) << 11) | ((b >> 3) << 9) | ((r & 7u) << 6) | ((g & 7u) << 3) | (b & 7u);
-}
-__device__ __forceinline__ uint32_t sp_key(uint32_t bucket, uint32_t bin) {
-    const uint32_t r = (((bucket >> 6) & 7u) << 5) | (((bin >> 13) & 3u) << 3) | ((bin >> 6) & 7u);
-    const uint32_t g = (((bucket >> 3) & 7u) << 5) | (((bin >> 11) & 3u) << 3) | ((bin >> 3) & 7u);
-    const uint32_t b = ((bucket & 7u) << 5) | (((bin >> 9) & 3u) << 3) | (bin & 7u);
-    return (r << 16) | (g << 8) | b;
-}
+// (sp_bucket, sp_bin, sp_key: sp_keys.hpp)
 
 // exclusive scan of 512 values held one per thread by threads 0..511 of a 1024-thread block; all threads call
 __device__ __forceinline__ uint32_t scan512(uint32_t v, uint32_t *wsum) { return block_exclusive_scan<kSpThreads>(v, wsum); }
@@ -342,6 +340,7 @@ __device__ __forceinline__ void sp_emit_body(uint32_t bucket, uint32_t first, co
             if (i >= n) continue;
             em.ckeys[q0 + i] = key[t];
             em.cweight[q0 + i] = cnt[t];
+            if (!em.labels) continue;   // (km_rgbw_need_arrays behind a finished run: the labels hold its result)
             const uint32_t lab = init_label24(rank[t], U, em.K, ppc, rcp);  // init_assignment kmeans.rs:61-78
             if (em.wide) static_cast<uint16_t *>(em.labels)[q0 + i] = (uint16_t)lab;
             else static_cast<uint8_t *>(em.labels)[q0 + i] = (uint8_t)lab;
@@ -367,6 +366,8 @@ __global__ __launch_bounds__(256) void k_bits_prefix(const unsigned long long *_
 //   A  k_bits_prefix | k_cell_totals | the zeroing of the K-means arena and of the head of the persistent launch's arena
 //   B  k_gidx_finish | k_cell_scan                                   (the colour count is copied to the host behind B)
 //   C  k_ps_ranges (block 0: dispatched first, ONE block as ever) | k_rgbw_init_cent | k_sp_emit, a 1024-thread block per bucket
+//      (the persistent launch reading the staging itself: B's cell scan has written the boundaries, block 0 only checks that every
+//      block's cells fit its LDS, and there is no emit role)
 // No role reads what another role of its own launch writes, and no block waits for another: the order is the stream's.
 constexpr uint32_t kFrontPrefixBlocks = 256;                    // blocks of 256 threads: k_bits_prefix's / k_gidx_finish's grid
 constexpr uint32_t kFrontCellBlocks = kCellGroups / 4;          // ... and four groups of 64 cells to a block, a wave each
@@ -402,7 +403,9 @@ __global__ __launch_bounds__(256) void k_cc_front_b(FrontB a) {
     else cell_scan_body((b - kFrontPrefixBlocks) * 4 + (threadIdx.x >> 6), threadIdx.x & 63u, a.cell_count, a.cell_tot, a.scan, kCellFixedCost, kCellSweepCost);
 }
 struct FrontC {
-    uint32_t ranges, cent_blocks;                               // blocks of the first two roles (ranges: 0 or 1); the buckets' follow
+    uint32_t ranges, cent_blocks;                               // blocks of the first two roles (ranges: 0 or 1); the buckets' follow (none when
+                                                                // the persistent launch takes its points from the staging itself)
+    uint32_t fit_only;                                          // the boundaries are there (B's cell scan wrote them): the ranges role checks the fit
     const uint32_t *ne_cost, *ne_count; uint32_t G, budget; uint32_t *cb; PsDev *dev; PsDevPtrs ptrs;
     uint64_t Ulist; uint32_t K, Kpad, idbits; uint2 *cconst; uint32_t *cent, *cent_copy, *moved_list; const uint64_t *U_dev; GIdx cgx;
     const uint32_t *sstart; const uint16_t *sbin; const uint32_t *scnt; SpEmit em;
@@ -410,7 +413,8 @@ struct FrontC {
 __global__ __launch_bounds__(kSpThreads) void k_cc_front_c(FrontC a) {
     const uint32_t b = blockIdx.x;
     if (b < a.ranges) {
-        ps_ranges_body(a.ne_cost, a.ne_count, a.G, a.budget, a.cb, a.dev, a.ptrs);
+        if (a.fit_only) ps_fit_body(a.G, a.budget, a.cb, a.dev, a.ptrs);
+        else ps_ranges_body(a.ne_cost, a.ne_count, a.G, a.budget, a.cb, a.dev, a.ptrs);
     } else if (b < a.ranges + a.cent_blocks) {
         rgbw_init_cent_body((b - a.ranges) * kSpThreads + threadIdx.x, nullptr, a.Ulist, a.K, a.Kpad, a.idbits, a.cconst, a.cent, a.cgx, a.cent_copy,
                             a.moved_list, a.U_dev);
@@ -426,7 +430,8 @@ template <typename LabelT>
 __global__ __launch_bounds__(kSpThreads) void k_sp_partlab(const uint16_t *__restrict__ part, const uint32_t *__restrict__ bstart,
                                                            const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ ckeys,
                                                            const LabelT *__restrict__ labels, LabelT *__restrict__ partlab,
-                                                           unsigned long long *__restrict__ look = nullptr, uint32_t look_words = 0) {
+                                                           unsigned long long *__restrict__ look, uint32_t look_words,
+                                                           const uint32_t *__restrict__ sstart, const uint16_t *__restrict__ sbin) {
     extern __shared__ __align__(16) uint8_t sp_lds[];
     LabelT *lut = reinterpret_cast<LabelT *>(sp_lds);
     // (the ticket, the give-up word and the look-back words of the k_sp_pixpack behind this kernel start at zero: no dispatch of their own)
@@ -448,7 +453,12 @@ __global__ __launch_bounds__(kSpThreads) void k_sp_partlab(const uint16_t *__res
         if (s >= e) return;
     }
     const uint32_t q0 = cell_start[bucket * 64], q1 = cell_start[bucket * 64 + 64];
-    for (uint32_t i = q0 + threadIdx.x; i < q1; i += kSpThreads) lut[sp_bin(ckeys[i])] = labels[i];
+    if (sbin) {   // the bucket's colours as the histogram staged them (no ckeys: the K-means took its points from the staging too)
+        const uint32_t s0 = sstart[bucket];
+        for (uint32_t i = q0 + threadIdx.x; i < q1; i += kSpThreads) lut[sbin[s0 + (i - q0)]] = labels[i];
+    } else {
+        for (uint32_t i = q0 + threadIdx.x; i < q1; i += kSpThreads) lut[sp_bin(ckeys[i])] = labels[i];
+    }
     __syncthreads();
     sp_for_entries(part, s, e, [&](uint64_t i, uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t m) {
         if (m == 1) { partlab[i] = lut[a]; return; }
@@ -779,7 +789,7 @@ int sp_build(Ctx *c, const uint8_t *rgb_d, uint64_t npx, SpPlan *plan, bool hist
 // the bitmap, the copy of the colour count with its event, the state's set-up dispatches and the emit into its arrays (the point list is
 // the image's own: plan's bitmap).  fused: the three launches k_cc_front_a / b / c; else the kernels and fills one by one, as sp_build,
 // km_rgbw_create and sp_emit enqueue them.
-int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide, bool fused) {
+int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t *cweight_d, void *labels_d, bool wide, bool fused, bool emit, bool count_copy) {
     DevBuf blocktot;   // (lives until everything here is enqueued: the pool hands memory out again in stream order)
     CNIIC_HIP_TRY(c, blocktot.alloc(256 * 4));
     const uint64_t *U_dev = plan->total.as<uint64_t>();
@@ -806,17 +816,19 @@ int sp_front(Ctx *c, SpPlan *plan, const KmFront &f, uint32_t *ckeys_d, uint32_t
     FrontB b{};
     b.wprefix = a.wprefix; b.blocktot = a.blocktot; b.total = plan->total.as<uint64_t>();
     b.cell_count = f.cell_count; b.cell_tot = a.cell_tot; b.scan = f.scan;
+    const bool direct = !emit && f.ranges;   // (with the staged points: the cell scan writes the chunk boundaries, no bisection in C)
+    if (direct) { b.scan.cb = f.cb; b.scan.NC = f.G * kPsChunks; }
     hipLaunchKernelGGL(k_cc_front_b, dim3(kFrontPrefixBlocks + kFrontCellBlocks), dim3(256), 0, c->stream, b);
     CNIIC_HIP_TRY(c, hipGetLastError());
-    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
-    CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
+    if (count_copy) CNIIC_TRY(sp_enqueue_count(c, plan));
     FrontC k{};
+    k.fit_only = direct ? 1u : 0u;
     k.ranges = f.ranges ? 1u : 0u; k.cent_blocks = (uint32_t)ceil_div(f.Kpad, kSpThreads);
     k.ne_cost = f.scan.ne_cost; k.ne_count = f.scan.ne_count; k.G = f.G; k.budget = f.budget; k.cb = f.cb; k.dev = f.dev; k.ptrs = f.ptrs;
     k.Ulist = f.Ulist; k.K = f.K; k.Kpad = f.Kpad; k.idbits = f.idbits; k.cconst = f.cconst; k.cent = f.cent; k.cent_copy = f.cent_copy;
     k.moved_list = f.moved_list; k.U_dev = f.U_dev; k.cgx = f.gx;
     k.sstart = plan->sstart.as<uint32_t>(); k.sbin = plan->sbin.as<uint16_t>(); k.scnt = plan->scnt.as<uint32_t>(); k.em = em;
-    hipLaunchKernelGGL(k_cc_front_c, dim3(k.ranges + k.cent_blocks + kSpBuckets), dim3(kSpThreads), 0, c->stream, k);
+    hipLaunchKernelGGL(k_cc_front_c, dim3(k.ranges + k.cent_blocks + (emit ? kSpBuckets : 0u)), dim3(kSpThreads), 0, c->stream, k);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }
@@ -826,6 +838,11 @@ bool sp_front_fits(const KmFront &f) {
     return ok(f.arena, f.arena_bytes) && (!f.ranges || ok(f.ps_arena, f.ps_zero_bytes));
 }
 
+int sp_enqueue_count(Ctx *c, SpPlan *plan) {
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(c->pinned_u.as<uint64_t>() + kPuSpCount.at, plan->total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipEventRecord(c->u_ev, c->stream));
+    return CNIIC_OK;
+}
 int sp_wait_count(Ctx *c, SpPlan *plan) {
     CNIIC_HIP_TRY(c, hipEventSynchronize(c->u_ev));
     plan->U = c->pinned_u.as<uint64_t>()[kPuSpCount.at];
@@ -861,7 +878,9 @@ int sp_occupancy(Ctx *c, const SpPlan *plan, uint32_t *occ_d) {
 // labels_d: the K-means' final cell-major labels -> partlab: label of every pixel in partition order.  look (optional, narrow labels): the
 // ticket and look-back words of sp_pixpack, allocated here and zeroed by the kernel
 int sp_part_labels(Ctx *c, const SpPlan *plan, const uint32_t *cell_start_d, const uint32_t *ckeys_d, const void *labels_d, bool wide, DevBuf &partlab,
-                   DevBuf *look) {
+                   DevBuf *look, bool staged) {
+    const uint32_t *sstart = staged ? plan->sstart.as<uint32_t>() : nullptr;
+    const uint16_t *sbin = staged ? plan->sbin.as<uint16_t>() : nullptr;
     const uint64_t lb = wide ? 2 : 1;
     CNIIC_HIP_TRY(c, partlab.alloc(plan->npx * lb + 16));
     const uint32_t look_words = look ? plan->nchunks + kLookHead : 0;
@@ -870,11 +889,11 @@ int sp_part_labels(Ctx *c, const SpPlan *plan, const uint32_t *cell_start_d, con
     if (wide)
         hipLaunchKernelGGL(k_sp_partlab<uint16_t>, grid, dim3(kSpThreads), (size_t)kSpBins * 2, c->stream, plan->part.as<uint16_t>(),
                            plan->bstart.as<uint32_t>(), cell_start_d, ckeys_d, static_cast<const uint16_t *>(labels_d), partlab.as<uint16_t>(),
-                           (unsigned long long *)nullptr, 0u);
+                           (unsigned long long *)nullptr, 0u, sstart, sbin);
     else
         hipLaunchKernelGGL(k_sp_partlab<uint8_t>, grid, dim3(kSpThreads), (size_t)kSpBins, c->stream, plan->part.as<uint16_t>(),
                            plan->bstart.as<uint32_t>(), cell_start_d, ckeys_d, static_cast<const uint8_t *>(labels_d), partlab.as<uint8_t>(),
-                           look ? look->as<unsigned long long>() : nullptr, look_words);
+                           look ? look->as<unsigned long long>() : nullptr, look_words, sstart, sbin);
     CNIIC_HIP_TRY(c, hipGetLastError());
     return CNIIC_OK;
 }
@@ -897,7 +916,7 @@ int sp_pixlab(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const void *part
 int sp_pixel_labels(Ctx *c, const SpPlan *plan, const uint8_t *rgb_d, const uint32_t *cell_start_d, const uint32_t *ckeys_d,
                     const void *labels_d, bool wide, void *pixlab_d) {
     DevBuf partlab;
-    CNIIC_TRY(sp_part_labels(c, plan, cell_start_d, ckeys_d, labels_d, wide, partlab, nullptr));
+    CNIIC_TRY(sp_part_labels(c, plan, cell_start_d, ckeys_d, labels_d, wide, partlab, nullptr, false));
     return sp_pixlab(c, plan, rgb_d, partlab.p, wide, pixlab_d);
 }
 

@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "ps_bounds.hpp"
 
 namespace cniic {
 
@@ -73,6 +74,14 @@ struct KmRgbwState {
     bool started = false;        // an assign has been enqueued (or the persistent launch): too late for km_rgbw_set_centroids
     DevBuf given;                // km_rgbw_set_centroids: the caller's K centroids as 0xRRGGBB words, and the host copy the upload reads
     std::vector<uint32_t> given_h;
+    // ckeys / cweight / labels have not been written: the persistent launch reads the staged colours of lazy_plan (PsDevPtrs::sbin), and
+    // whoever else wants the arrays asks km_rgbw_need_arrays first (the classic loop after a launch that gave up, above all)
+    const SpPlan *lazy_plan = nullptr;
+    // U (and gidx.U) is still the upper bound the state was created with: the count lies at count_dev and the host has not looked.  The
+    // persistent launch reads it there; km_rgbw_set_points ends this (cc_finish, where the count's copy arrives -- or, before the loop of
+    // launches, km_rgbw_fetch_points)
+    const uint64_t *count_dev = nullptr;
+    bool ps_done = false;        // the persistent launch ran to its end: labels holds the result
 };
 
 // ---- k_kmeans_persist.hip: the LDS of a block and what the launch shares with its set-up
@@ -100,11 +109,19 @@ struct PsDevPtrs {                        // what only the launch's set-up and w
     uint8_t *labels;                      // cell-major labels: the initial assignment on entry, the result on a regular exit
     const uint32_t *ne_cell, *ne_start;   // compacted non-empty cells: id, first position
     const uint2 *cconst0;                 // the initial centroids (k_rgbw_init_cent)
+    // The large cluster-colors encode (cc_prepare_image) gives the points a second source, sbin set: the histogram's staged (bin, count)
+    // pairs (k_sp_hist, k_points.hip), which lie in cell-major order already -- bucket b's entries at sstart[b] + (i - cell_start[64 b]) --
+    // so nothing copies them into ckeys / cweight / labels first: the set-up makes key and initial label itself (sp_key, gidx_rank,
+    // init_label24 with the count of colours at U_dev) and leaves in cweight_rw only the counts a packed word cannot hold.
+    const uint32_t *sstart; const uint16_t *sbin; const uint32_t *scnt; const uint32_t *cell_start;
+    const unsigned long long *gbits; const uint32_t *gprefix; const uint64_t *U_dev;
+    uint32_t *cweight_rw;
+    const uint64_t *count_dev;            // set: the host enqueued the launch without having seen the count (fewer than K: every block leaves at once)
 };
 struct PsDev { uint32_t fail, pad; PsDevPtrs p; };   // fail: some block's cells do not fit its LDS (k_ps_ranges): no block starts
 constexpr uint32_t kPsArenaPart = (sizeof(PsBar) + 255u) & ~255u, kPsArenaFail = kPsArenaPart + ((3u * kPsPartWords * 8u + 255u) & ~255u), kPsArenaRng = kPsArenaFail + 256u;
 static_assert(sizeof(PsDev) <= 256, "PsDev has 256 bytes of the arena");
-constexpr uint32_t kPsStatusDone = 1, kPsStatusAborted = 2, kPsStatusRanges = 3;
+constexpr uint32_t kPsStatusDone = 1, kPsStatusAborted = 2, kPsStatusRanges = 3, kPsStatusFew = 4;   // (Few: fewer points than clusters, seen by the launch itself)
 struct PsExit { uint32_t status, pad; uint64_t iter, moved_last, reseeds, active, pair_evals; uint32_t group_iters[3], pad2; };   // pinned: how the launch ended (group_iters: block 0's skip-schedule iterations with 4, 8, 16 lanes per cell)
 void launch_rgbw_assign_big(Ctx *c, const uint32_t *ckeys, const uint32_t *cweight, uint64_t U, uint32_t K, const uint32_t *cent, uint16_t *labels,
                             unsigned long long *partials, const KmDevState *st);
@@ -164,12 +181,26 @@ __device__ __forceinline__ void cell_totals_body(uint32_t grp, uint32_t lane, co
     const uint32_t ne = (uint32_t)__popcll(__ballot(v != 0));
     if (lane == 0) { tot[grp] = make_uint2(sum, ne); tot[kCellGroups + grp] = make_uint2(sweeps, 0u); }
 }
-struct CellScanOut { uint32_t *cell_start, *cursor, *ne_cell, *ne_start, *ne_cost, *ne_count; };
+// (cb, when set: the persistent launch's NC + 1 chunk boundaries as well, every cell those that fall on it -- ps_bounds.hpp; what
+// k_ps_ranges bisects for, word for word)
+struct CellScanOut { uint32_t *cell_start, *cursor, *ne_cell, *ne_start, *ne_cost, *ne_count; uint32_t *cb; uint32_t NC; };
 __device__ __forceinline__ void cell_scan_body(uint32_t grp, uint32_t lane, const uint32_t *__restrict__ cell_count, const uint2 *__restrict__ tot,
                                                const CellScanOut &o, uint32_t fixed_cost, uint32_t sweep_cost) {
     // cost of a cell in the full schedule's split: fixed_cost + points if sweep_cost == 0, else fixed_cost + sweep_cost * sweeps
-    uint32_t ps = 0, pn = 0, pw = 0;
-    for (uint32_t g = lane; g < grp; g += 64) { const uint2 t = tot[g]; ps += t.x; pn += t.y; pw += tot[kCellGroups + g].x; }
+    uint32_t ps = 0, pn = 0, pw = 0, an = 0, aw = 0, ap = 0;   // (a*: over all the groups, for the total cost the boundaries are cut from)
+    if (o.cb) {
+        static_assert(kCellGroups % 64 == 0, "every lane looks at the same number of groups");
+#pragma unroll
+        for (uint32_t g0 = 0; g0 < kCellGroups; g0 += 64) {   // (the loads of all trips issued together)
+            const uint32_t g = g0 + lane;
+            const uint2 t = tot[g];
+            const uint32_t w = tot[kCellGroups + g].x;
+            ap += t.x; an += t.y; aw += w;
+            if (g < grp) { ps += t.x; pn += t.y; pw += w; }
+        }
+    } else {
+        for (uint32_t g = lane; g < grp; g += 64) { const uint2 t = tot[g]; ps += t.x; pn += t.y; pw += tot[kCellGroups + g].x; }
+    }
     const uint32_t base = wave_reduce_sum(ps), nbase = wave_reduce_sum(pn), wbase = wave_reduce_sum(pw);
     const uint32_t cell = grp * 64 + lane, v = cell_count[cell], sw = (v + 64 * kSweep - 1) / (64 * kSweep);
     const uint32_t start = base + wave_inclusive_scan(v) - v, swb = wbase + wave_inclusive_scan(sw) - sw;
@@ -179,6 +210,17 @@ __device__ __forceinline__ void cell_scan_body(uint32_t grp, uint32_t lane, cons
     if (v) {
         const uint32_t m = nbase + (uint32_t)__popcll(nzm & ((1ull << lane) - 1ull));
         o.ne_cell[m] = cell; o.ne_start[m] = start; o.ne_cost[m] = (sweep_cost ? swb * sweep_cost : start) + m * fixed_cost;
+    }
+    if (o.cb) {
+        const uint32_t Mall = wave_reduce_sum(an);
+        const uint64_t total = (sweep_cost ? wave_reduce_sum(aw) * sweep_cost : wave_reduce_sum(ap)) + Mall * fixed_cost;   // = ne_cost[M], the u32 the last lane writes
+        if (v) {
+            const uint32_t m = nbase + (uint32_t)__popcll(nzm & ((1ull << lane) - 1ull));
+            const uint32_t mine = (sweep_cost ? swb * sweep_cost : start) + m * fixed_cost, next = mine + (sweep_cost ? sw * sweep_cost : v) + fixed_cost;   // ne_cost[m], ne_cost[m + 1]
+            if (m == 0) { const PsBoundRun r = ps_bounds_upto(mine, total, o.NC); for (uint32_t j = 0; j < r.count; j++) o.cb[r.first + j] = 0u; }
+            const PsBoundRun r = ps_bounds_between(mine, next, total, o.NC);
+            for (uint32_t j = 0; j < r.count; j++) o.cb[r.first + j] = m + 1;
+        }
     }
     if (grp == kCellGroups - 1 && lane == 63) {
         const uint32_t U = start + v, M = nbase + (uint32_t)__popcll(nzm);
@@ -205,7 +247,7 @@ __device__ __forceinline__ void ps_ranges_body(const uint32_t *__restrict__ ne_c
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const uint32_t g = g0 + r * blockDim.x;
-            c_lo[r] = total * min(g, NC) / NC;
+            c_lo[r] = ps_bound_target(total, g, NC);
             a[r] = 0; b[r] = g <= NC ? M : 0u;   // first cell whose cost prefix is >= c_lo
         }
         bool more = true;
@@ -232,6 +274,21 @@ __device__ __forceinline__ void ps_ranges_body(const uint32_t *__restrict__ ne_c
     }
 }
 
+// ... and what is left of it when the cell scan has written the boundaries (CellScanOut::cb): the launch's pointers and the fit check, a
+// block's 2 x kPsChunks boundaries asked for together.  Any number of threads of ONE block.
+__device__ __forceinline__ void ps_fit_body(uint32_t G, uint32_t dyn_bytes, const uint32_t *__restrict__ cb, PsDev *__restrict__ dev, const PsDevPtrs &ptrs) {
+    if (threadIdx.x == 0) dev->p = ptrs;
+    for (uint32_t g = threadIdx.x; g < G; g += blockDim.x) {
+        uint32_t lo[kPsChunks], hi[kPsChunks];
+#pragma unroll
+        for (uint32_t r = 0; r < kPsChunks; r++) { lo[r] = cb[r * G + g]; hi[r] = cb[r * G + g + 1]; }
+        uint32_t C = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < kPsChunks; r++) C += hi[r] - lo[r];
+        if (C > kPsMaxCells || kPsOffCell + ps_cell_bytes(C) > dyn_bytes) atomicAdd(&dev->fail, 1u);
+    }
+}
+
 // What km_rgbw_create leaves to its caller when asked to (points_follow only): the set-up dispatches it would enqueue, described
 // instead.  The caller enqueues them -- as the roles of k_cc_front_* or, km_front_enqueue_split, as the kernels create itself launches --
 // before anything else touches the state.
@@ -250,6 +307,15 @@ struct KmFront {
 int km_rgbw_create_deferred(Ctx *c, uint64_t Umax, uint32_t K, const cniic_kmeans_opts *opts, KmRgbwState **out, const uint32_t *cell_count_d,
                             const void *gbits_d, const uint32_t *gprefix_d, uint64_t Ug, const uint64_t *points_dev, KmFront *front);
 int km_front_enqueue_split(Ctx *c, const KmFront &f);   // the fills and the four kernels, in create's own order
+// cc_prepare_image, with a persistent launch to come: the cell-major arrays are not written -- the launch takes its points from plan's
+// staging (front->ptrs is completed here), and plan outlives the state's last use of it
+void km_rgbw_points_from_staging(KmRgbwState *s, const SpPlan *plan, KmFront *front);
+bool km_rgbw_arrays_pending(const KmRgbwState *s);
+void km_rgbw_count_stays_on_device(KmRgbwState *s, const uint64_t *count_dev);   // (in the place of km_rgbw_set_points, until the count has arrived)
+int km_rgbw_fetch_points(KmRgbwState *s);   // a state that still waits for its count: fetches it, now, and sets the points
+// the arrays after all: k_sp_emit, once, on the state's stream (the labels only while they do not hold a result).  Not while a
+// deferred launch's verdict is out.
+int km_rgbw_need_arrays(KmRgbwState *s);
 
 struct CellBox { int32_t r0, g0, b0; };  // low corner of a cube of colours
 __device__ __forceinline__ CellBox super_box(uint32_t sup) {
