@@ -1570,8 +1570,8 @@ static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t
     if (!frames) return CNIIC_OK;
     if (!bytes || !lens || !rgb || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "codec_decode_batch: null argument");
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the streams on this context's stream is done
-    // `hufman` / `cluster-colors` / `hilbert(rle)` and small `delta` frames: decoded together (codec_decode_batch_route; "delta_small_dec_batch" counts
-    // the `delta` frames its one launch was given); the rest, each on its own on the workers
+    // `hufman` / `cluster-colors` / `hilbert(rle)` and small `delta`, `voronoi` and `zip(dict)` frames: decoded together (codec_decode_batch_route;
+    // "delta_small_dec_batch" counts the `delta` frames its one launch was given); the rest, each on its own on the workers
     std::vector<uint8_t> taken;
     std::vector<int32_t> status;
     std::vector<std::string> msg;

@@ -17,6 +17,7 @@
 #include "huf_small.hpp"
 #include "rle_small.hpp"
 #include "zd_small.hpp"
+#include "zd_small_dec.hpp"
 #include "small_trie.hpp"
 
 #include <algorithm>
@@ -2488,6 +2489,157 @@ static int voronoi_batch(DecodeBatch &b) {
     return vor_small_decode(b, route, table, cent, Ks);
 }
 
+// ------------------------------------------------------------------ small `zip(dict)` frames of a batch (k_zd_small_dec.hip)
+// The host reads the head of every stream -- kZdDecHead bytes, 16 pairs -- and finds what zip_dict_dims finds on it (zsd_head_dims); a frame is a candidate when the head
+// spells the 8 bytes of the dimensions, 1 <= w h <= kZdSmallDecMaxPx, the image fits img_stride and (in a call of several frames) the
+// stream ends before the next one starts.  Every other frame is the caller's, with the single decode's status and message.  The candidates
+// at or below the floor's pixel bound for their count (zd_small_dec_floor_px) are worked through in chunks whose scratch -- rows, result
+// rows, for a host batch the streams and for a host destination the staged images -- stays below 1 GiB (the testing library: below
+// CNIIC_TEST_MEASURE_BUDGET bytes, a frame at least): per chunk one copy up, one launch per SIZE CLASS of dynamic LDS (a frame's offsets and
+// image, and its pair words where they fit beside them; the classes keep one large frame from sizing the LDS of every workgroup, so that
+// small frames share a CU), one copy down, one wait.  A frame the kernel hands back (pairs behind the cap, more than kZsdRounds generations,
+// a byte behind more than kZsdHops pairs) is the caller's.
+//
+// The floor.  Measured against the parent commit's library (tools/small_zip_probe.py --calls decode, profiles/small_zip_dec_probe.json; NOTES
+// AR), photo-like, uniform noise and flat frames in device memory, whole decode call, medians of 5, parent's time / this route's; a class
+// takes the route only where this build's slowest run beat the parent's fastest for all three contents:
+//   1 frame:      32 x 32 1.04x .. 1.32x (the flat row's ranges touch); every larger size lost (0.13x .. 0.62x): one workgroup needs 0.13 ..
+//                 0.63 ms for 4096 .. 16 384 pixels, a worker 0.09 .. 0.29 ms
+//   8 frames:     32 x 32 won (3.6x .. 4.0x), 64 x 64 won (1.85x .. 2.4x); 128 x 96, 128 x 128 and 16384 x 1 did not (0.44x .. 1.24x, no row clear)
+//   32 frames:    every size won: 8.0x .. 8.7x, 4.0x .. 4.7x, and 1.11x .. 2.4x for 12 288 and 16 384 pixels (flat frames the closest: 0.712 ms at
+//                 the slowest against 0.762 at the parent's fastest)
+//   256 frames:   every size won (6.1x .. 33x);  4096 frames: 32 x 32 46x .. 55x, 64 x 64 28x .. 32x (larger sizes not probed at this count)
+// Host memory on both sides follows (64 x 64: 0.5x .. 0.6x, 1.3x .. 1.8x, 2.4x .. 3.0x, 5.8x .. 6.8x, 1.5x .. 3.3x at 1, 8, 32, 256, 4096 frames).
+// So: fewer than kZdSmallDecFloorFew candidates stay with the workers; from there on the candidates of at most kZdSmallDecFloorPxFew
+// pixels take the route, and from kZdSmallDecFloorMany candidates on all of them.  Counts between the probed ones keep the lower class's
+// bound.  The floor knows pixels, not contents.  The testing library takes it away with CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF=1.
+constexpr uint64_t kZdDecHead = 64;
+static_assert(kZdDecHead == 4 * kZsdHeadPairs, "the head is the pairs zsd_head_dims looks at");
+constexpr uint64_t kZdSmallDecScratch = 1ull << 30;
+constexpr uint32_t kZsdLdsClasses[] = {16u << 10, 32u << 10, 64u << 10};   // and zd_small_dec_lds_max()
+static uint64_t zd_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_ZD_SMALL_DEC_OFF", "CNIIC_TEST_ZD_SMALL_DEC_MAX_PX", kZdSmallDecMaxPx); }
+// a cap the testing library may lower, never raise
+inline uint32_t test_lower_cap(const char *env, uint32_t bound) {
+    if (const char *e = test_env(env)) return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), bound);
+    return bound;
+}
+constexpr uint32_t kZdSmallDecFloorFew = 8, kZdSmallDecFloorMany = 32;
+constexpr uint64_t kZdSmallDecFloorPxFew = 4096, kZdSmallDecFloorPxMany = 16384;
+static uint64_t zd_small_dec_floor_px(uint64_t candidates) {
+    if (const char *e = test_env("CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
+    return candidates >= kZdSmallDecFloorMany ? kZdSmallDecFloorPxMany : candidates >= kZdSmallDecFloorFew ? kZdSmallDecFloorPxFew : 0;
+}
+static int zip_dict_batch(DecodeBatch &b) {
+    Ctx *c = b.c;
+    const uint64_t max_px = zd_small_dec_max_px();
+    Heads heads(b);
+    std::vector<uint32_t> cand, cw, ch;
+    auto classify = [&](uint32_t f) {
+        if (b.off_route[f] || (b.F > 1 && b.stride < b.lens[f])) return;
+        uint32_t fw = 0, fh = 0;
+        if (!zsd_head_dims(heads.head_p[f], std::min(heads.head_n[f], kZdDecHead), &fw, &fh)) return;   // (zip_dict_dims on the same bytes, without its table)
+        if (!dims_fit((uint64_t)fw * fh, max_px, b.img_stride)) return;
+        cand.push_back(f); cw.push_back(fw); ch.push_back(fh);
+    };
+    if (b.bytes_dev) {
+        const uint64_t W = b.F == 1 ? kZdDecHead : std::min(kZdDecHead, b.stride);   // (a look is never wider than the stride)
+        if (!W) return CNIIC_OK;
+        const uint32_t group = (uint32_t)(kBatchHeadsMax / W);
+        for (uint32_t f0 = 0; f0 < b.F;) {
+            const uint32_t f1 = (uint32_t)std::min<uint64_t>((uint64_t)f0 + group, b.F) - 1;
+            CNIIC_TRY(heads.fetch(W, f0, f1));
+            for (uint32_t f = f0; f <= f1; f++) classify(f);
+            f0 = f1 + 1;
+        }
+    } else {
+        heads.in_place();
+        for (uint32_t f = 0; f < b.F; f++) classify(f);
+    }
+    const uint64_t floor_px = zd_small_dec_floor_px(cand.size());
+    std::vector<uint32_t> route;
+    for (size_t i = 0; i < cand.size(); i++) {
+        if ((uint64_t)cw[i] * ch[i] > floor_px) continue;
+        b.w[cand[i]] = cw[i]; b.h[cand[i]] = ch[i];
+        route.push_back(cand[i]);
+    }
+    if (route.empty()) return CNIIC_OK;
+
+    const uint32_t max_pairs = test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_MAX_PAIRS", kZsdMaxPairs), hops = test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_HOPS", kZsdHops),
+                   rounds = test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_ROUNDS", kZsdRounds);
+    const uint32_t lds_max = zd_small_dec_lds_max();
+    const uint64_t budget = test_budget(kZdSmallDecScratch);
+    auto pairs_of = [&](uint32_t f) { return (uint32_t)std::min<uint64_t>(b.lens[f] / 4, max_pairs); };
+    auto scratch_of = [&](uint32_t f) {
+        return sizeof(ZdSmallDecRow) + sizeof(ZdSmallDecResult) + (b.dst_dev ? 0 : SlotLayout::room(b.image_bytes(f))) + (b.bytes_dev ? 0 : b.lens[f]);
+    };
+    for (size_t i0 = 0; i0 < route.size();) {
+        const size_t i1 = take_chunk(i0, route.size(), budget, [&](size_t i) { return scratch_of(route[i]); });
+        const size_t S = i1 - i0;
+        DevBuf up_d, rows_d, res_d;
+        const uint8_t *base;
+        CNIIC_TRY(streams_in_hbm(b, route[i0], route[i1 - 1], up_d, &base));
+        StagedImages staged(S);
+        for (size_t i = 0; i < S; i++) staged.plan(i, b.image_bytes(route[i0 + i]), !b.dst_dev);
+        CNIIC_HIP_TRY(c, staged.alloc(c));
+        // ---- a row per frame, by size class: what the frame needs of LDS, with its pair words where they fit as well
+        std::vector<uint32_t> lds(S), order(S);
+        std::vector<uint8_t> stage_pairs(S);
+        for (size_t i = 0; i < S; i++) {
+            const uint32_t f = route[i0 + i], plain = zsd_lds_bytes(pairs_of(f), (uint32_t)b.pixels(f));
+            stage_pairs[i] = plain + 4 * pairs_of(f) <= lds_max;
+            const uint32_t want = plain + (stage_pairs[i] ? 4 * pairs_of(f) : 0);
+            lds[i] = lds_max;
+            for (int k = 2; k >= 0; k--) if (want <= kZsdLdsClasses[k]) lds[i] = kZsdLdsClasses[k];
+            order[i] = (uint32_t)i;
+        }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return lds[x] < lds[y]; });
+        std::vector<ZdSmallDecRow> rows(S);
+        for (size_t j = 0; j < S; j++) {
+            const size_t i = order[j];
+            const uint32_t f = route[i0 + i];
+            rows[j] = ZdSmallDecRow{base + (uint64_t)f * b.stride, staged.dst(i, b.image(f)), b.lens[f], pairs_of(f), b.w[f], b.h[f], stage_pairs[i]};
+        }
+        CNIIC_HIP_TRY(c, rows_d.alloc(S * sizeof(ZdSmallDecRow)));
+        CNIIC_HIP_TRY(c, res_d.alloc(S * sizeof(ZdSmallDecResult)));
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), S * sizeof(ZdSmallDecRow), hipMemcpyHostToDevice, c->stream));
+        {
+            ScopedKernelTimer t(c, "zd_small_dec_batch");
+            for (size_t j0 = 0; j0 < S;) {
+                size_t j1 = j0 + 1;
+                while (j1 < S && lds[order[j1]] == lds[order[j0]]) j1++;
+                CNIIC_TRY(zd_small_dec_run(c, rows_d.as<ZdSmallDecRow>() + j0, (uint32_t)(j1 - j0), lds[order[j0]] & ~15u, hops, rounds, res_d.as<ZdSmallDecResult>() + j0));
+                j0 = j1;
+            }
+            t.stop(S);
+        }
+        std::vector<ZdSmallDecResult> res(S);
+        CNIIC_HIP_TRY(c, hipMemcpyAsync(res.data(), res_d.p, S * sizeof(ZdSmallDecResult), hipMemcpyDeviceToHost, c->stream));
+        CNIIC_HIP_TRY(c, staged.down_block(c));
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        uint64_t back = 0;
+        for (size_t j = 0; j < S; j++) {
+            const size_t i = order[j];
+            const uint32_t f = route[i0 + i];
+            const ZdSmallDecResult &r = res[j];
+            char text[160];
+            switch (r.verdict) {
+            case kZsdOk: b.taken[f] = 1; staged.put(i, b.image(f), b.image_bytes(f)); continue;
+            case kZsdHandedBack: back++; continue;   // the caller's
+            case kZsdBadSymbol: snprintf(text, sizeof text, "zip-dict: pair %llu uses a symbol that has not been handed out", (unsigned long long)r.a); break;
+            case kZsdDangling: snprintf(text, sizeof text, "zip-dict: a first symbol without a second at the end of the stream"); break;
+            case kZsdShort: snprintf(text, sizeof text, "zip-dict: the text ends after %llu of %llu bytes", (unsigned long long)r.a, (unsigned long long)r.b); break;
+            case kZsdBadRecord: snprintf(text, sizeof text, "zip-dict: pixel %llu is not a record of 3 bytes (ser.rs:216-221)", (unsigned long long)r.a); break;
+            default: return c->fail(CNIIC_ERR_HIP, "zd_small_dec: verdict %u", r.verdict);
+            }
+            b.taken[f] = 1;
+            b.decode_error(f, text);
+        }
+        stage_count(c, "zd_small_dec_handback", back);
+        i0 = i1;
+    }
+    return CNIIC_OK;
+}
+
 // ------------------------------------------------------------------ `hufman`, `cluster-colors` and `delta` frames of a batch
 // The batched route of the RGB kinds (huff_decode_batch_dev): the frames of `route` (ascending), whose decoders are lts[f] and whose
 // payloads start at pay[f], in parts of kBatchRouteFrames.
@@ -2659,7 +2811,8 @@ static int huffman_batch(DecodeBatch &b, bool delta) {
 }
 
 // ------------------------------------------------------------------ decode of many streams (cniic_codec_decode_batch)
-// `hilbert(rle)` frames have no decoder to parse and go to rle_batch, `voronoi` frames to voronoi_batch, the others to huffman_batch.  Whatever
+// `hilbert(rle)` frames have no decoder to parse and go to rle_batch, `voronoi` frames to voronoi_batch, `zip(dict)` frames to zip_dict_batch, the others to
+// huffman_batch.  Whatever
 // this route does not take -- another codec, a malformed or oversized header, a decoder longer than the head that was looked at, codes of more
 // than 32 bits, a frame that has not settled -- is left to the caller, which decodes it on its own (codec_decode): same bytes, same status.
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,
@@ -2668,9 +2821,11 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     taken.assign(F, 0);
     rcs.assign(F, CNIIC_OK);
     msgs.assign(F, std::string());
-    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE && d.kind != CODEC_DELTA && d.kind != CODEC_VORONOI))
+    if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE && d.kind != CODEC_DELTA && d.kind != CODEC_VORONOI &&
+               d.kind != CODEC_ZIP_DICT))
         return CNIIC_OK;
     if (d.kind == CODEC_VORONOI && !vor_small_dec_max_px()) return CNIIC_OK;
+    if (d.kind == CODEC_ZIP_DICT && !zd_small_dec_max_px()) return CNIIC_OK;
     const bool delta = d.kind == CODEC_DELTA;
     if (delta && !delta_small_dec_max_px()) return CNIIC_OK;
     DecodeBatch b{c, bytes, is_device_ptr(bytes), stride, lens, F, rgb, is_device_ptr(rgb), img_stride, w, h, taken, rcs, msgs, std::vector<uint8_t>(F, 0)};
@@ -2684,6 +2839,7 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         }
     if (d.kind == CODEC_HILBERT_RLE) return rle_batch(b);
     if (d.kind == CODEC_VORONOI) return voronoi_batch(b);
+    if (d.kind == CODEC_ZIP_DICT) return zip_dict_batch(b);
     return huffman_batch(b, delta);
 }
 

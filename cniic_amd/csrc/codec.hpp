@@ -138,7 +138,8 @@ int encode_zip_back_batch(Ctx *c, const uint8_t *rgb, const uint64_t *img_off, c
 int decode_zip_back_batch(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, uint64_t img_stride, uint32_t *w,
                           uint32_t *h, int32_t *rcs);
 
-// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames of a batch decoded together (stream f at bytes + f *
+// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames and the small `delta`, `voronoi` and `zip(dict)`
+// frames of a batch decoded together (stream f at bytes + f *
 // stride, lens[f] bytes; image f to rgb + f * img_stride).  taken[f] = 1: frame f was decoded here (rcs[f], msgs[f], w[f], h[f]); 0: the
 // caller decodes it on its own (codec_decode).
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,

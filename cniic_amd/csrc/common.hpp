@@ -974,6 +974,16 @@ struct ZdSmallRow { const uint8_t *src; uint32_t w, h; };
 struct ZdSmallResult { uint32_t pairs, len, verdict, finished; };   // ..., walks the commit finished behind the speculation's cap
 int zd_small_run(Ctx *c, const ZdSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t spec, uint32_t giveup, uint64_t *tables_d,
                  uint32_t bits, uint8_t *scratch_d, uint64_t sstride, ZdSmallResult *res_d);
+// ---- k_zd_small_dec.hip: the decode of small `zip(dict)` frames, one workgroup per frame from its pairs to its pixels (zd_small_dec.hpp
+// has the arithmetic, the limits and the verdicts).  A row per frame: its stream (device memory, any alignment; len bytes, of which the
+// kernel looks at `pairs` = min(len / 4, the pair cap) pairs), where its w x h x 3 image goes (device memory, any alignment; written whole
+// and only with verdict kZsdOk), and whether the pair words are staged in LDS (the host says so where they fit).  lds_bytes: dynamic LDS of
+// the launch, at least every row's zsd_lds_bytes(pairs, w h) + 4 pairs where staged, a multiple of 16, zd_small_dec_lds_max() at most.
+// res_d[f]: the verdict and the numbers of its message (kZsdBadSymbol: a = the pair; kZsdShort: a of b bytes; kZsdBadRecord: a = the pixel).
+struct ZdSmallDecRow { const uint8_t *stream; uint8_t *dst; uint64_t len; uint32_t pairs, w, h, staged; };
+struct ZdSmallDecResult { uint32_t verdict, a, b, pad; };
+uint32_t zd_small_dec_lds_max();
+int zd_small_dec_run(Ctx *c, const ZdSmallDecRow *rows_d, uint32_t frames, uint32_t lds_bytes, uint32_t hops, uint32_t rounds, ZdSmallDecResult *res_d);
 // ---- k_delta_small_dec.hip: the decode of small `delta` frames, one workgroup per frame (delta_small_dec.hpp has the arithmetic and the
 // limits).  A row per frame: its payload (device memory, any alignment; payload_bytes to the stream's end), where its w x h x 3 image goes
 // (device memory, any alignment) and its decoder as `leaves` words of left-aligned codes, ascending, and as many key | length << 27 words

@@ -119,7 +119,11 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * The small-frame route of `zip(dict)` there: "zd_small_batch" = the duration of k_zd_small (and of zeroing its trie tables), with
  * launches = the frames that took the route; "zd_small_place" = the copy of the finished streams to their destinations, one launch per
  * chunk; "zd_small_handback": launches = the frames of those the kernel gave up (a match longer than 1024 bytes) and the worker contexts
- * coded; "zd_small_finished": launches = the walks the kernel's commit wave finished behind the speculating lanes' cap of 32 bytes. */
+ * coded; "zd_small_finished": launches = the walks the kernel's commit wave finished behind the speculating lanes' cap of 32 bytes.
+ * The small-frame decode route of `zip(dict)` in cniic_codec_decode_batch and cniic_codec_measure_batch (described there):
+ * "zd_small_dec_batch" = the duration of k_zd_small_dec, with launches = the frames it was given; "zd_small_dec_handback": launches = the
+ * frames of those the kernel handed back (pairs behind its cap of 24 576, 64 or more generations, a byte behind more than 64 pairs)
+ * and the worker contexts decoded. */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
@@ -753,7 +757,26 @@ int32_t cniic_codec_decode(cniic_ctx *ctx, const char *expr, const uint8_t *byte
  * a truncated or malformed centroid, w h = 0, an image that does not fit, a head cut by a stride below the stream's length -- goes to
  * the worker contexts as above, with the single decode's status and message.  Which route a frame took shows in no output byte, status
  * or message.  Stage timer: "vor_small_dec_batch" = the duration of that kernel, with launches = the frames it was given;
- * cniic_codec_measure_batch leaves it readable beside the encode's "vor_small_batch".  (A decode evaluates no K-means: no pair_evals.) */
+ * cniic_codec_measure_batch leaves it readable beside the encode's "vor_small_batch".  (A decode evaluates no K-means: no pair_evals.)
+ *
+ * SMALL `zip(dict)` frames of a decode, here and in cniic_codec_measure_batch: the host reads the first 64 bytes -- 16 pairs -- of every
+ * stream, and a frame whose head spells the 8 bytes of the dimensions, with 1 .. 16384 pixels, an image that fits img_stride and (in a
+ * call of several frames) a stream that ends before the next one starts, is a candidate.  The decode of this coder is not serial: pair k
+ * hands out symbol 0x100 + k whatever it holds, so a symbol is the text of an earlier pair, which already lies in the output.  A
+ * candidate is decoded on ONE workgroup, from its pairs to its pixels: the pairs' lengths in rounds over the pairs they are made of,
+ * their offsets as a saturating prefix sum, then every byte of the text by a binary search for its pair and hops from pair to pair down
+ * to a literal -- no text is written out -- the records checked, the image assembled in the CU's LDS and stored whole, with 16-byte
+ * stores where the address allows and not a byte outside its 3 w h.  All such frames of a chunk of scratch go in one launch per size
+ * class of LDS (16, 32, 64 KiB, and up to a CU's 160), so that small frames share a CU.  The reader is lazy, as the single decode's:
+ * nothing behind the pair that completes the text is looked at.  A frame with more than 24 576 pairs before its text is complete, with
+ * pairs nested 64 or more generations deep, or with a byte that lies behind more than 64 pairs is handed back to the worker contexts,
+ * as is every frame that is no candidate; they get the single decode's status and message, and so does a frame that fails on this
+ * route, with the one difference that it leaves its 3 w h destination bytes untouched.  Host or device memory on either side, at any
+ * alignment.  The floor, measured against the worker contexts: a call with fewer than 8 candidates keeps them all on the workers, one
+ * with 8 .. 31 gives the route its candidates of at most 4096 pixels, one with 32 or more gives it all of them.  Which route a frame took
+ * shows in no output byte, dimension, status or message.  Stage timers: "zd_small_dec_batch" = the duration of the kernel's launches,
+ * with launches = the frames it was given; "zd_small_dec_handback" = no time, launches = the frames of those it handed back;
+ * cniic_codec_measure_batch leaves both readable beside the encode's "zd_small_batch". */
 int32_t cniic_codec_decode_batch(cniic_ctx *ctx, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens,
                                  uint32_t frames, uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* bench::compute_error (src/bench.rs:95-104): MSE between two RGB8 images. */

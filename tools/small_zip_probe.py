@@ -12,7 +12,13 @@ with min - max beside them, and the digests of the streams and of the measured r
 A further child runs `this` with the stage timers on and records the duration of k_zd_small ("zd_small_batch"), of the placing copy
 ("zd_small_place"), the frames handed back to the workers ("zd_small_handback") and the walks the commit wave finished
 ("zd_small_finished").  --sizes / --frames / --kinds narrow the sweep; --max-px skips the cases of more pixels in all (the workers need
-seconds for 4096 frames of 16 384 pixels)."""
+seconds for 4096 frames of 16 384 pixels).
+
+--calls decode times cniic_codec_decode_batch of the streams the encode wrote (the small-frame decode route, k_zd_small_dec.hip): `this` runs
+under CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF=1 as well, `route_off` under CNIIC_TEST_ZD_SMALL_DEC_OFF=1, the stage child records
+"zd_small_dec_batch" and "zd_small_dec_handback", and a digest of all decoded images must agree between the variants.  --host decodes from
+and into host memory.  `clear` in a decode cell: this build's slowest run beats the other's fastest -- the ranges do not overlap -- which
+is what the route's floor is set from (`lost`: the other way round)."""
 import argparse
 import hashlib
 import json
@@ -28,9 +34,10 @@ sys.path.insert(0, ROOT)
 SIZES = ((32, 32), (64, 64), (128, 96), (128, 128), (16384, 1))
 FRAMES = (1, 4, 8, 32, 256, 4096)
 KINDS = ("photo", "uniform", "flat", "band")
-STAGES = ("zd_small_batch", "zd_small_place", "zd_small_handback", "zd_small_finished")
+STAGES = ("zd_small_batch", "zd_small_place", "zd_small_handback", "zd_small_finished", "zd_small_dec_batch", "zd_small_dec_handback")
 OFF, FLOOR_OFF = "CNIIC_TEST_ZD_SMALL_OFF", "CNIIC_TEST_ZD_SMALL_FLOOR_OFF"
-CALLS = ("encode", "measure")
+DEC_OFF, DEC_FLOOR_OFF = "CNIIC_TEST_ZD_SMALL_DEC_OFF", "CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF"
+CALLS = ("encode", "measure", "decode")
 EXPR = "zip(dict)"
 
 
@@ -70,22 +77,35 @@ def child(a):
 
             def measure():
                 res["m"] = ctx.measure_batch(EXPR, src, offs, ws, hs)
-            calls = dict(encode=encode, measure=measure)
+
+            def decode():
+                if "img" not in res:
+                    lens = res["e"][1]
+                    if a.host:
+                        import numpy as np
+                        res["img"], res["streams"] = np.zeros(nb * F + 16, np.uint8), enc.cpu().numpy()
+                    else:
+                        res["img"], res["streams"] = torch.zeros(nb * F + 16, dtype=torch.uint8, device=dev), enc
+                    res["lens"] = lens
+                res["d"] = ctx.decode_batch(EXPR, res["streams"], stride, res["lens"], F, res["img"], nb)
+            calls = dict(encode=encode, measure=measure, decode=decode)
             name = "%s %dx%d x%d" % (kind, w, h, F)
             if a.stages:
                 got = {}
                 encode()
+                decode()
                 ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
-                encode()
-                for s in STAGES:
-                    ms, cnt = ctx.kernel_time(s)
-                    if cnt or ms:
-                        got[s] = dict(ms=round(ms, 3), launches=cnt)
+                for call in (encode, decode):
+                    call()
+                    for s in STAGES:
+                        ms, cnt = ctx.kernel_time(s)
+                        if cnt or ms:
+                            got[s] = dict(ms=round(ms, 3), launches=cnt)
                 ctx.set_opt(_lib.OPT_STAGE_TIMERS, None)
                 out[name] = got
                 continue
             row = {}
-            timed = a.calls.split(",") if a.calls else CALLS
+            timed = a.calls.split(",") if a.calls else CALLS[:2]
             for which in CALLS:
                 if which not in timed:
                     if which == "encode":
@@ -110,6 +130,10 @@ def child(a):
                 dg.update(host[f * stride:f * stride + (lens[f] if rcs[f] == 0 else 0)].tobytes())
                 if "m" in res:
                     dg.update(repr((res["m"][1][f]["compressed_size"], res["m"][1][f]["error"])).encode())
+            if "d" in res:
+                img = res["img"] if a.host else res["img"].cpu().numpy()
+                dg.update(img[:nb * F].tobytes())
+                dg.update(repr(res["d"]).encode())
             out[name] = dict(ms=row, digest=dg.hexdigest()[:16], failed=sum(r != 0 for r in rcs), pairs=sum(lens) // 4)
             print("[probe child] %s" % name, file=sys.stderr, flush=True)
             del enc, src
@@ -127,7 +151,8 @@ def main():
     ap.add_argument("--frames")
     ap.add_argument("--kinds")
     ap.add_argument("--max-px", type=int, default=0, help="skip the cases of more pixels in all")
-    ap.add_argument("--calls", help="the calls to time, of encode,measure")
+    ap.add_argument("--calls", help="the calls to time, of encode,measure,decode (default: encode,measure)")
+    ap.add_argument("--host", action="store_true", help="decode from and into host memory")
     ap.add_argument("--variants", help="of this,route_off,other (this is always run)")
     ap.add_argument("--floor", action="store_true", help="`this` keeps the route's floor")
     ap.add_argument("--timeout", type=int, default=1100)
@@ -136,8 +161,8 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a)
-    this_env = {"CNIIC_USE_TESTING_LIB": "1"} if a.floor else {"CNIIC_USE_TESTING_LIB": "1", FLOOR_OFF: "1"}
-    variants = [("this", this_env), ("route_off", {"CNIIC_USE_TESTING_LIB": "1", OFF: "1"})]
+    this_env = {"CNIIC_USE_TESTING_LIB": "1"} if a.floor else {"CNIIC_USE_TESTING_LIB": "1", FLOOR_OFF: "1", DEC_FLOOR_OFF: "1"}
+    variants = [("this", this_env), ("route_off", {"CNIIC_USE_TESTING_LIB": "1", OFF: "1", DEC_OFF: "1"})]
     if a.against:
         variants.append(("other", {"CNIIC_LIB_FILE": a.against}))
     if a.variants:
@@ -146,9 +171,11 @@ def main():
     for k in ("sizes", "frames", "kinds", "calls"):
         if getattr(a, k):
             base += ["--" + k, getattr(a, k)]
+    if a.host:
+        base.append("--host")
 
     def run(env_add, extra=()):
-        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", OFF, FLOOR_OFF)}
+        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", OFF, FLOOR_OFF, DEC_OFF, DEC_FLOOR_OFF)}
         env.update(env_add)
         r = subprocess.run(base + list(extra), stdout=subprocess.PIPE, text=True, timeout=a.timeout, env=env)   # (a child's progress lines go to stderr as they come)
         if r.returncode != 0:
@@ -184,6 +211,8 @@ def main():
                 o = tri(got["other"][k]["ms"][c])
                 sp = (cell["this"][2] - cell["this"][1]) + (o[2] - o[1])
                 cell.update(other=o, x=round(o[0] / cell["this"][0], 3), slower=bool(o[0] + sp < cell["this"][0]), faster=bool(cell["this"][0] + sp < o[0]))
+                if c == "decode":
+                    cell.update(clear=bool(cell["this"][2] < o[1]), lost=bool(o[2] < cell["this"][1]))
             row[c] = cell
         row["same"] = all(got[who][k]["digest"] == v["digest"] for who in ("route_off", "other") if who in got)
         print(json.dumps(row), flush=True)
