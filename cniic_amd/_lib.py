@@ -167,6 +167,9 @@ PROTOTYPES = {
     "cniic_zip_dict_dims": (_I32, [_PTR, _U64, _PTR, _PTR]),
     "cniic_hilbert_zip_encode": (_I32, [_PTR, _PTR, _U32, _U32, _PTR, _U64, _PTR]),
     "cniic_hilbert_zip_decode": (_I32, [_PTR, _PTR, _U64, _PTR, _U64, _PTR, _PTR]),
+    "cniic_hilbert_zip_encode_batch_var": (_I32, [_PTR, _PTR, _PTR, _PTR, _PTR, _U32, _PTR, _U64, _PTR, _PTR]),
+    "cniic_hilbert_zip_decode_batch": (_I32, [_PTR, _PTR, _U64, _PTR, _U32, _PTR, _U64, _PTR, _PTR, _PTR]),
+    "cniic_hilbert_zip_measure_batch": (_I32, [_PTR, _PTR, _PTR, _PTR, _PTR, _U32, _PTR, _PTR, _U64, _PTR]),
     "cniic_zip_back_encode": (_I32, [_PTR, _PTR, _U64, _PTR, _U64, _PTR]),
     "cniic_zip_back_decode": (_I32, [_PTR, _PTR, _U64, _PTR, _U64, _PTR]),
     "cniic_zip_back_dims": (_I32, [_PTR, _U64, _PTR, _PTR]),
@@ -592,6 +595,38 @@ class Context:
         if raw.size >= 8:
             dims = int.from_bytes(raw[0:4].tobytes(), "little"), int.from_bytes(raw[4:8].tobytes(), "little")
         return self._decode_image(dims, allow, self._L.cniic_hilbert_zip_decode, self.h, _ptr(raw), raw.size)
+
+    def hilbert_zip_decode_into(self, data, nbytes, out, cap=None, allow=()):
+        """cniic_hilbert_zip_decode with caller-owned buffers (device tensors, numpy arrays or addresses) -> (rc, w, h)"""
+        cw, ch = C.c_uint32(0), C.c_uint32(0)
+        rc = self._check(self._L.cniic_hilbert_zip_decode(self.h, _ptr(data), nbytes, _ptr(out), _count(out) if cap is None else cap, C.byref(cw), C.byref(ch)), allow)
+        return rc, cw.value, ch.value
+
+    def hilbert_zip_encode_batch_var(self, images, offs, ws, hs, out, stride, allow=()):
+        """cniic_hilbert_zip_encode_batch_var: the layout of encode_batch_var -> (rc, list of lengths, list of per-image status codes)"""
+        F = len(offs)
+        n = max(F, 1)
+        lens, rcs = (C.c_uint64 * n)(), (C.c_int32 * n)()
+        rc = self._check(self._L.cniic_hilbert_zip_encode_batch_var(self.h, _ptr(images), _array(C.c_uint64, offs, F), _array(C.c_uint32, ws, F),
+                                                                    _array(C.c_uint32, hs, F), F, _ptr(out), stride, lens, rcs), allow)
+        return rc, [int(lens[f]) for f in range(F)], [int(rcs[f]) for f in range(F)]
+
+    def hilbert_zip_decode_batch(self, streams, stride, lens, F, out, img_stride, allow=()):
+        """cniic_hilbert_zip_decode_batch: the layout of decode_batch -> (rc, list of widths, list of heights, list of per-frame status codes)"""
+        n = max(F, 1)
+        ws, hs, rcs = (C.c_uint32 * n)(), (C.c_uint32 * n)(), (C.c_int32 * n)()
+        rc = self._check(self._L.cniic_hilbert_zip_decode_batch(self.h, _ptr(streams), stride, _array(C.c_uint64, lens, F), F, _ptr(out), img_stride,
+                                                                ws, hs, rcs), allow)
+        return rc, [int(ws[f]) for f in range(F)], [int(hs[f]) for f in range(F)], [int(rcs[f]) for f in range(F)]
+
+    def hilbert_zip_measure_batch(self, images, offs, ws, hs, out=None, stride=0, allow=()):
+        """cniic_hilbert_zip_measure_batch: measure_batch for Hilbert { compress: Zip } -> (rc, list of row dicts, list of stream lengths)"""
+        F = len(offs)
+        n = max(F, 1)
+        rows, lens = (MeasureRow * n)(), (C.c_uint64 * n)()
+        rc = self._check(self._L.cniic_hilbert_zip_measure_batch(self.h, _ptr(images), _array(C.c_uint64, offs, F), _array(C.c_uint32, ws, F),
+                                                                 _array(C.c_uint32, hs, F), F, rows, _ptr(out), stride, lens), allow)
+        return rc, [rows[f].as_dict() for f in range(F)], [int(lens[f]) for f in range(F)]
 
     # ---- the look-back coder
     def zip_back_encode(self, data, n=None, out=None, allow=()):

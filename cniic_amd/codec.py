@@ -193,7 +193,8 @@ class HilbertRleApprox(Codec):
 class HilbertZip(Codec):
     """Hilbert { compress: Zip } (src/codec/hilbertc.rs:27-29,47-49,67-77): the dimensions, then the dictionary coder over the 11-byte
     records of the pixels in scan order.  `hilbert(zip)` is not an expression of this library: encode and decode go through
-    cniic_hilbert_zip_encode / cniic_hilbert_zip_decode."""
+    cniic_hilbert_zip_encode / cniic_hilbert_zip_decode, batches and measure through cniic_hilbert_zip_encode_batch_var / _decode_batch /
+    _measure_batch."""
 
     def __init__(self, ctx=None):
         self.expr = None
@@ -208,14 +209,71 @@ class HilbertZip(Codec):
         rc, img = self.ctx.hilbert_zip_decode(data, allow=(_lib.DECODE,))
         return img if rc == _lib.OK else None
 
+    DECODE_BATCH_BYTES = 256 << 20   # host memory one cniic_hilbert_zip_decode_batch call's images may take (a frame that claims more goes alone)
+
+    def encode_batch(self, imgs, allow=(), **kw):
+        """the streams of a list of HxWx3 images of any sizes, in one call (cniic_hilbert_zip_encode_batch_var); None for an image that
+        cannot be encoded.  The per-image options of encode (w, h, out) make a loop of single calls, as before."""
+        if len(imgs) == 0:
+            return []
+        if kw:
+            return [self.encode(im, allow=allow, **kw) for im in imgs]
+        buf, offs, ws, hs = self._packed(imgs)
+        stride = (max(8 + 22 * w * h + 4 for w, h in zip(ws, hs)) + 3) & ~3   # (two symbols a byte of text at most)
+        out = np.empty(stride * len(offs), np.uint8)
+        rc, lens, rcs = self.ctx.hilbert_zip_encode_batch_var(buf, offs, ws, hs, out, stride, allow=self.ENCODE_FAILURES + tuple(allow))
+        return [out[f * stride:f * stride + lens[f]].tobytes() if rcs[f] == _lib.OK else None for f in range(len(offs))]
+
     def decode_batch(self, streams):
-        return [self.decode(s) for s in streams]
+        """the images of a list of streams (cniic_hilbert_zip_decode_batch); None where a stream does not decode.  The sizes are what the
+        streams claim, so the list goes in calls whose images take at most DECODE_BATCH_BYTES of host memory together, smallest claims
+        first; a stream that claims more than that on its own is decoded alone (one image's allocation, as the single call makes)."""
+        streams = [bytes(s) for s in streams]
+        if not streams:
+            return []
 
-    def encode_batch(self, imgs, **kw):
-        return [self.encode(im, **kw) for im in imgs]
+        def claim(s):   # bytes of the image the stream's dimensions ask for; 1 where they ask for none that can be decoded
+            if len(s) < 8:
+                return 1
+            n = int.from_bytes(s[0:4], "little") * int.from_bytes(s[4:8], "little")
+            return 3 * n if 0 < n <= (1 << 28) else 1
 
-    def measure(self, imgs, **kw):
-        raise NotImplementedError("hilbert-zip has no expression: cniic_codec_measure_batch cannot name it")
+        imgs = [None] * len(streams)
+        order = sorted(range(len(streams)), key=lambda f: claim(streams[f]))
+        at = 0
+        while at < len(order):
+            img_stride = claim(streams[order[at]])
+            if img_stride > self.DECODE_BATCH_BYTES:
+                imgs[order[at]] = self.decode(streams[order[at]])
+                at += 1
+                continue
+            end = at + 1
+            while end < len(order) and claim(streams[order[end]]) * (end + 1 - at) <= self.DECODE_BATCH_BYTES:
+                end += 1
+            part = [streams[f] for f in order[at:end]]
+            img_stride = claim(part[-1])
+            stride = max(max(len(s) for s in part), 1)
+            blob = np.zeros(stride * len(part), np.uint8)
+            for j, s in enumerate(part):
+                blob[j * stride:j * stride + len(s)] = np.frombuffer(s, np.uint8)
+            out = np.zeros(img_stride * len(part), np.uint8)
+            rc, ws, hs, rcs = self.ctx.hilbert_zip_decode_batch(blob, stride, [len(s) for s in part], len(part), out, img_stride,
+                                                                allow=(_lib.DECODE, _lib.CAPACITY))
+            for j, f in enumerate(order[at:end]):
+                if rcs[j] == _lib.OK:
+                    imgs[f] = out[j * img_stride:j * img_stride + 3 * ws[j] * hs[j]].reshape(hs[j], ws[j], 3).copy()
+            at = end
+        return imgs
+
+    def measure(self, imgs, seed=0, max_iters=0, flags=0, allow=()):
+        """bench::measure_all's loop over a list of images of any sizes (cniic_hilbert_zip_measure_batch): a list of dicts with the
+        reference's CSV columns compressed_size, compression_ratio, error (bench.rs:68-75) plus rc (and lossless_mismatch, kmeans).
+        seed, max_iters and flags are Codec.measure's K-means options: taken, and without meaning for this codec."""
+        if len(imgs) == 0:
+            return []
+        buf, offs, ws, hs = self._packed(imgs)
+        rc, rows, _ = self.ctx.hilbert_zip_measure_batch(buf, offs, ws, hs, allow=self.ENCODE_FAILURES + (_lib.DECODE,) + tuple(allow))
+        return rows
 
     def name(self):
         return "hilbert-zip"      # hilbertc.rs:85

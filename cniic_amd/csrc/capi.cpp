@@ -19,6 +19,7 @@
 #include "delta_small.hpp"
 #include "huf_small.hpp"
 #include "rle_small.hpp"
+#include "hz_small.hpp"
 #include "zd_small.hpp"
 
 using namespace cniic;
@@ -1058,8 +1059,18 @@ int32_t cniic_codec_is_lossless(const char *expr) {
     return codec_is_lossless(d) ? 1 : 0;
 }
 
-static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+static int32_t decode_batch_locked(cniic_ctx *c, const CodecDesc &d, const char *who, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
                                    uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs_out);
+
+// one image under a descriptor, the context's mutex held (the batch engines' workers: the expression was parsed once, by the call)
+static int32_t encode_desc_locked(cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
+                                  uint8_t *out, uint64_t cap, uint64_t *len, cniic_kmeans_stats *stats) {
+    c->ktimes.clear();
+    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode: null argument");
+    In<uint8_t> in;
+    CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
+    return codec_encode(c, d, in.d, w, h, opts, out, cap, len, stats);
+}
 
 // cniic_codec_encode / cniic_codec_encode_opts, the context's mutex held
 static int32_t encode_locked(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, uint32_t w, uint32_t h,
@@ -1067,10 +1078,7 @@ static int32_t encode_locked(cniic_ctx *c, const char *expr, const cniic_kmeans_
     c->ktimes.clear();
     CodecDesc d;
     if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
-    if (!len || (!rgb && (uint64_t)w * h) || !out) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode: null argument");
-    In<uint8_t> in;
-    CNIIC_TRY(in.bind(c, rgb, (uint64_t)w * h * 3));
-    return codec_encode(c, d, in.d, w, h, opts, out, cap, len, stats);
+    return encode_desc_locked(c, d, opts, rgb, w, h, out, cap, len, stats);
 }
 
 int32_t cniic_codec_encode(cniic_ctx *c, const char *expr, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap,
@@ -1286,7 +1294,7 @@ int32_t cniic_codec_encode_batch(cniic_ctx *c, const char *expr, const cniic_kme
 // cluster-colors and the 16-byte tile reads of `delta` (same bytes, slower routes): it is copied into the worker's aligned scratch
 // first, so that a frame costs what it costs alone at an aligned address wherever it lies in the caller's buffer.  (A host image is
 // staged into fresh, aligned HBM by the single call already.)
-static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kmeans_opts *opts, bool src_dev, VarFrame &fr) {
+static int32_t encode_var_frame(cniic_ctx *wk, const CodecDesc &d, const cniic_kmeans_opts *opts, bool src_dev, VarFrame &fr) {
     LOCK(wk);
     const uint64_t npx = (uint64_t)fr.w * fr.h;
     if (npx >= (1ull << 32)) return wk->fail(CNIIC_ERR_BAD_ARG, "image too large");   // (codec_encode's answer, before anything is staged)
@@ -1300,7 +1308,7 @@ static int32_t encode_var_frame(cniic_ctx *wk, const char *expr, const cniic_kme
         CNIIC_HIP_TRY(wk, hipMemcpyAsync(wk->batch_stage.p, src, npx * 3, hipMemcpyDeviceToDevice, wk->stream));
         src = wk->batch_stage.as<uint8_t>();
     }
-    const int32_t rc = encode_locked(wk, expr, opts, src, fr.w, fr.h, fr.out, fr.cap, &fr.len, &fr.st);
+    const int32_t rc = encode_desc_locked(wk, d, opts, src, fr.w, fr.h, fr.out, fr.cap, &fr.len, &fr.st);
     if (stage && wk->timers) wk->ktimes["batch_stage"].launches++;
     return rc;
 }
@@ -1406,6 +1414,30 @@ static uint64_t zd_small_max_px() {
 }
 static uint64_t zd_small_floor_px(uint64_t candidates, const CodecDesc &) { return zd_small_floor_off() || candidates >= kZdSmallFloorFrames ? ~0ull : 0; }
 
+// The floor of the Hilbert { compress: Zip } route: NO class of calls takes it in the release library.  The rule is the decode route's (codec.cpp):
+// a class, defined by frame count and pixel bound, takes the route only where the route's slowest run beat the workers' fastest for
+// photo-like, noise AND flat frames -- and the floor knows pixels, not contents.  Measured against this build with the route off (the worker
+// contexts) and against the parent commit's library, which can only loop over cniic_hilbert_zip_encode on one context
+// (tools/small_zip_probe.py --codec hilbert-zip, profiles/small_hz_probe.json; NOTES AS), whole encode call, medians of 5, this route / the
+// workers.  The coder is `zip(dict)`'s, serial inside a frame: one workgroup needs 4.7 - 5.0 ms for a frame of 32 x 32, 15 - 18 ms for 64 x 64,
+// 43 - 50 ms for 128 x 96 and 56 - 66 ms for 128 x 128 or 16384 x 1.
+//   1 .. 32 frames:  every size and content lost (4.3 - 66 ms against 0.2 - 23 ms)
+//   256 frames:      photo-like and noise: 32 x 32 won (5.0 ms against 9.6 - 9.9), 64 x 64 won (16.8 - 18.7 against 30.1 - 34.3), 128 x 96,
+//                    128 x 128 and 16384 x 1 did not (103 - 136 ms against 92 - 134).  FLAT frames, every one of which the kernel hands back
+//                    after 3.3 - 3.7 ms, lost: 32 x 32 9.3 - 9.4 ms against 5.4 - 5.7, 64 x 64 24.5 - 27.1 against 20.4 - 20.8
+//   4096 frames:     photo-like and noise: 32 x 32 won (31.1 - 33.3 ms against 143 - 146), 64 x 64 won (141 - 148 against 459 - 479).  Flat
+//                    frames lost again: 32 x 32 103 - 104 ms against 87 - 90, 64 x 64 325 - 327 against 302 - 310
+// So no probed class is clear for all three contents, and every frame stays with the workers.  What that leaves on the table: 1.6x - 4.6x
+// for calls of 256 and more photo-like or noise frames of at most 4096 pixels; what it avoids: 0.6x - 0.9x for flat ones.  A check of the
+// content cheap enough to go in front of the kernel would change this; none is built.  The route is reached with
+// CNIIC_TEST_HZ_SMALL_FLOOR_OFF=1 (the testing library), which the tests and the probe set.
+static bool hz_small_floor_off() {
+    if (const char *e = test_env("CNIIC_TEST_HZ_SMALL_FLOOR_OFF")) return atoi(e) != 0;
+    return false;
+}
+static uint64_t hz_small_max_px() { return small_route_max_px("CNIIC_TEST_HZ_SMALL_OFF", "CNIIC_TEST_HZ_SMALL_MAX_PX", kHzSmallMaxPx); }
+static uint64_t hz_small_floor_px(uint64_t, const CodecDesc &) { return hz_small_floor_off() ? ~0ull : 0; }
+
 // A small-frame route of encode_frames.  A frame is a CANDIDATE when the route applies to the call and the frame has 1 .. max_px() pixels;
 // a candidate takes the route unless the floor or `takes` keeps it with the workers.  (max_px is a function, not its knobs' names: those
 // must not be in the release library, and small_route_max_px folds them away only as arguments of a call.)
@@ -1441,9 +1473,15 @@ static const SmallRoute kSmallRoutes[] = {
     {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *) { return d.kind == CODEC_ZIP_DICT; },
      zd_small_max_px, zd_small_floor_px, nullptr,
      [](cniic_ctx *c, const CodecDesc &, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return zd_small_encode(c, fr, n); }},
+    // Hilbert { compress: Zip } (the internal kind of cniic_hilbert_zip_encode_batch_var): not a frame whose size has an injected scan, which the
+    // workers follow; a frame the kernel gives up comes back handed_back
+    {[](const cniic_ctx *, const CodecDesc &d, const cniic_kmeans_opts *) { return d.kind == CODEC_HILBERT_ZIP; },
+     hz_small_max_px, hz_small_floor_px,
+     [](const cniic_ctx *c, const VarFrame &f) { return !(c->scan_xy.p && c->scan_w == f.w && c->scan_h == f.h); },
+     [](cniic_ctx *c, const CodecDesc &, const cniic_kmeans_opts *, VarFrame *const *fr, uint32_t n) { return hz_small_encode(c, fr, n); }},
 };
 
-static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
+static int32_t encode_frames(cniic_ctx *c, const CodecDesc &d, const cniic_kmeans_opts *opts, std::vector<VarFrame> &fr, bool src_dev, const char *who) {
     const uint32_t n = (uint32_t)fr.size();
     if (!n) return CNIIC_OK;
     std::vector<uint32_t> order(n);
@@ -1456,8 +1494,7 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
     });
     std::map<std::string, KernelTime> kt;
     // ---- the small frames of a codec that has a route for them, together
-    CodecDesc d;
-    const bool routable = src_dev && parse_codec(expr, &d);
+    const bool routable = src_dev;
     for (const SmallRoute &r : kSmallRoutes) {
         if (!routable || !r.applies(c, d, opts)) continue;
         const uint64_t max_px = r.max_px();
@@ -1506,7 +1543,7 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
     parallel_for(nw, S, [&](uint32_t j, uint32_t i) {
         cniic_ctx *wk = c->batch_workers[i].get();
         VarFrame &f = fr[order[j]];
-        f.rc = encode_var_frame(wk, expr, opts, src_dev, f);
+        f.rc = encode_var_frame(wk, d, opts, src_dev, f);
         if (f.rc != CNIIC_OK) f.msg = wk->err;
         if (c->timers) {
             std::lock_guard<std::mutex> lk(kt_mu);
@@ -1518,22 +1555,19 @@ static int32_t encode_frames(cniic_ctx *c, const char *expr, const cniic_kmeans_
     return CNIIC_OK;
 }
 
-int32_t cniic_codec_encode_batch_var(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
-                                     const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
-                                     int32_t *rcs, cniic_kmeans_stats *stats) {
-    LOCK(c);
-    c->ktimes.clear();
-    CodecDesc d;
-    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+// cniic_codec_encode_batch_var under a descriptor, the context's mutex held (who: the entry point's name in its messages)
+static int32_t encode_batch_var_locked(cniic_ctx *c, const CodecDesc &d, const char *who, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                       const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs,
+                                       cniic_kmeans_stats *stats) {
     if (!frames) return CNIIC_OK;
-    if (!rgb || !img_off || !w || !h || !out || !lens) return c->fail(CNIIC_ERR_BAD_ARG, "codec_encode_batch_var: null argument");
+    if (!rgb || !img_off || !w || !h || !out || !lens) return c->fail(CNIIC_ERR_BAD_ARG, "%s: null argument", who);
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
     std::vector<VarFrame> fr(frames);
     for (uint32_t f = 0; f < frames; f++) {
         fr[f].src = rgb + img_off[f]; fr[f].w = w[f]; fr[f].h = h[f];
         fr[f].out = out + (uint64_t)f * stride; fr[f].cap = stride;
     }
-    CNIIC_TRY(encode_frames(c, expr, opts, fr, is_device_ptr(rgb), "codec_encode_batch_var"));
+    CNIIC_TRY(encode_frames(c, d, opts, fr, is_device_ptr(rgb), who));
     std::vector<int32_t> status(frames);
     std::vector<std::string> msg(frames);
     for (uint32_t f = 0; f < frames; f++) {
@@ -1543,6 +1577,25 @@ int32_t cniic_codec_encode_batch_var(cniic_ctx *c, const char *expr, const cniic
         msg[f].swap(fr[f].msg);
     }
     return fold_status(c, status.data(), msg.data(), frames, rcs);
+}
+
+int32_t cniic_codec_encode_batch_var(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                     const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens,
+                                     int32_t *rcs, cniic_kmeans_stats *stats) {
+    LOCK(c);
+    c->ktimes.clear();
+    CodecDesc d;
+    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    return encode_batch_var_locked(c, d, "codec_encode_batch_var", opts, rgb, img_off, w, h, frames, out, stride, lens, rcs, stats);
+}
+
+// Hilbert { compress: Zip } of many images: the same engine under the internal descriptor (no options, no statistics)
+static const CodecDesc kHilbertZipDesc = {CODEC_HILBERT_ZIP, 0, 0.0};
+int32_t cniic_hilbert_zip_encode_batch_var(cniic_ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t frames, uint8_t *out,
+                                           uint64_t stride, uint64_t *lens, int32_t *rcs) {
+    LOCK(c);
+    c->ktimes.clear();
+    return encode_batch_var_locked(c, kHilbertZipDesc, "hilbert_zip_encode_batch_var", nullptr, rgb, img_off, w, h, frames, out, stride, lens, rcs, nullptr);
 }
 
 int32_t cniic_codec_decode(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w,
@@ -1558,17 +1611,32 @@ int32_t cniic_codec_decode(cniic_ctx *c, const char *expr, const uint8_t *bytes,
 int32_t cniic_codec_decode_batch(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
                                  uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs) {
     LOCK(c);
-    return decode_batch_locked(c, expr, bytes, stride, lens, frames, rgb, img_stride, w, h, rcs, nullptr);
-}
-
-// cniic_codec_decode_batch, the context's mutex held (msgs_out: every frame's own message)
-static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
-                                   uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs_out) {
     c->ktimes.clear();
     CodecDesc d;
     if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    return decode_batch_locked(c, d, "codec_decode_batch", bytes, stride, lens, frames, rgb, img_stride, w, h, rcs, nullptr);
+}
+
+int32_t cniic_hilbert_zip_decode_batch(cniic_ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames, uint8_t *rgb, uint64_t img_stride,
+                                       uint32_t *w, uint32_t *h, int32_t *rcs) {
+    LOCK(c);
+    return decode_batch_locked(c, kHilbertZipDesc, "hilbert_zip_decode_batch", bytes, stride, lens, frames, rgb, img_stride, w, h, rcs, nullptr);
+}
+
+// one stream under a descriptor on a worker context (cniic_codec_decode without the parse)
+static int32_t decode_desc(cniic_ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!bytes || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "codec_decode: null argument");
+    return codec_decode(c, d, bytes, n, rgb, cap, w, h);
+}
+
+// cniic_codec_decode_batch under a descriptor, the context's mutex held (who: the entry point's name in its messages; msgs_out: every frame's own message)
+static int32_t decode_batch_locked(cniic_ctx *c, const CodecDesc &d, const char *who, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+                                   uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs_out) {
+    c->ktimes.clear();
     if (!frames) return CNIIC_OK;
-    if (!bytes || !lens || !rgb || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "codec_decode_batch: null argument");
+    if (!bytes || !lens || !rgb || !w || !h) return c->fail(CNIIC_ERR_BAD_ARG, "%s: null argument", who);
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the streams on this context's stream is done
     // `hufman` / `cluster-colors` / `hilbert(rle)` and small `delta`, `voronoi` and `zip(dict)` frames: decoded together (codec_decode_batch_route;
     // "delta_small_dec_batch" counts the `delta` frames its one launch was given); the rest, each on its own on the workers
@@ -1579,12 +1647,12 @@ static int32_t decode_batch_locked(cniic_ctx *c, const char *expr, const uint8_t
     std::vector<uint32_t> rest;
     for (uint32_t f = 0; f < frames; f++) if (!taken[f]) rest.push_back(f);
     if (!rest.empty()) {
-        const uint32_t S = batch_workers_ready(c, (uint32_t)rest.size(), "codec_decode_batch");
+        const uint32_t S = batch_workers_ready(c, (uint32_t)rest.size(), who);
         if (!S) return CNIIC_ERR_HIP;
         parallel_for((uint32_t)rest.size(), S, [&](uint32_t j, uint32_t i) {
             cniic_ctx *wk = c->batch_workers[i].get();
             const uint32_t f = rest[j];
-            status[f] = cniic_codec_decode(wk, expr, bytes + (uint64_t)f * stride, lens[f], rgb + (uint64_t)f * img_stride, img_stride, &w[f], &h[f]);
+            status[f] = decode_desc(wk, d, bytes + (uint64_t)f * stride, lens[f], rgb + (uint64_t)f * img_stride, img_stride, &w[f], &h[f]);
             if (status[f] != CNIIC_OK) msg[f] = wk->err;
         });
     }
@@ -1756,7 +1824,7 @@ static uint64_t measure_budget() {
 static uint64_t measure_stream_room(uint64_t npx) { return (64 + npx * 16 + (1ull << 16) + 3) & ~3ull; }
 
 struct MeasureJob {
-    cniic_ctx *c; const char *expr; const cniic_kmeans_opts *opts; bool lossless, src_dev;
+    cniic_ctx *c; CodecDesc d; const char *who, *who_decode; const cniic_kmeans_opts *opts; bool lossless, src_dev;
     const uint8_t *rgb; const uint64_t *img_off; const uint32_t *w, *h;
     cniic_measure_row *rows; uint8_t *out; uint64_t stride; uint64_t *lens;
     std::vector<std::string> msg;
@@ -1788,14 +1856,14 @@ struct MeasureJob {
             fr[j].src = a_base + a_off[j]; fr[j].w = w[which[j]]; fr[j].h = h[which[j]];
             fr[j].out = sbuf.as<uint8_t>() + room * j; fr[j].cap = room;
         }
-        CNIIC_TRY(encode_frames(c, expr, opts, fr, true, "codec_measure_batch"));
+        CNIIC_TRY(encode_frames(c, d, opts, fr, true, who));
         std::map<std::string, KernelTime> enc_kt;   // (the decode below starts its stage times afresh: the encode's are added back)
         if (c->timers) enc_kt = c->ktimes;
         for (uint32_t j = 0; j < n; j++) slen[j] = fr[j].rc == CNIIC_OK ? fr[j].len : 0;
         std::vector<uint32_t> w2(n), h2(n);
         std::vector<int32_t> drc(n, CNIIC_OK);
         std::vector<std::string> dmsg;
-        (void)decode_batch_locked(c, expr, sbuf.as<uint8_t>(), room, slen.data(), n, ibuf.as<uint8_t>(), img_stride, w2.data(), h2.data(), drc.data(), &dmsg);
+        (void)decode_batch_locked(c, d, who_decode, sbuf.as<uint8_t>(), room, slen.data(), n, ibuf.as<uint8_t>(), img_stride, w2.data(), h2.data(), drc.data(), &dmsg);
         if (dmsg.size() != n) return CNIIC_ERR_HIP;   // (the batch as a whole failed: the message is the context's)
         for (const auto &e : enc_kt) { c->ktimes[e.first].ms += e.second.ms; c->ktimes[e.first].launches += e.second.launches; }
         for (uint32_t j = 0; j < n; j++) {
@@ -1834,17 +1902,13 @@ struct MeasureJob {
     }
 };
 
-int32_t cniic_codec_measure_batch(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
-                                  const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows, uint8_t *out, uint64_t stride,
-                                  uint64_t *lens) {
-    LOCK(c);
-    c->ktimes.clear();
-    CodecDesc d;
-    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+// cniic_codec_measure_batch under a descriptor, the context's mutex held (who: the entry point's name in its messages)
+static int32_t measure_batch_locked(cniic_ctx *c, const CodecDesc &d, const char *who, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                    const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens) {
     if (!frames) return CNIIC_OK;
-    if (!rgb || !img_off || !w || !h || !rows) return c->fail(CNIIC_ERR_BAD_ARG, "codec_measure_batch: null argument");
+    if (!rgb || !img_off || !w || !h || !rows) return c->fail(CNIIC_ERR_BAD_ARG, "%s: null argument", who);
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
-    MeasureJob job{c, expr, opts, codec_is_lossless(d), is_device_ptr(rgb), rgb, img_off, w, h, rows, out, stride, lens, std::vector<std::string>(frames)};
+    MeasureJob job{c, d, who, d.kind == CODEC_HILBERT_ZIP ? "hilbert_zip_decode_batch" : "codec_decode_batch", opts, codec_is_lossless(d), is_device_ptr(rgb), rgb, img_off, w, h, rows, out, stride, lens, std::vector<std::string>(frames)};
     const double nan = std::numeric_limits<double>::quiet_NaN();
     std::vector<uint32_t> order, big;
     for (uint32_t f = 0; f < frames; f++) {
@@ -1891,6 +1955,23 @@ int32_t cniic_codec_measure_batch(cniic_ctx *c, const char *expr, const cniic_km
     std::vector<int32_t> status(frames);
     for (uint32_t f = 0; f < frames; f++) status[f] = rows[f].rc;
     return fold_status(c, status.data(), job.msg.data(), frames, nullptr);
+}
+
+int32_t cniic_codec_measure_batch(cniic_ctx *c, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
+                                  const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows, uint8_t *out, uint64_t stride,
+                                  uint64_t *lens) {
+    LOCK(c);
+    c->ktimes.clear();
+    CodecDesc d;
+    if (!parse_codec(expr, &d)) return c->fail(CNIIC_ERR_BAD_ARG, "Malformed codec argument: %s", expr ? expr : "(null)");
+    return measure_batch_locked(c, d, "codec_measure_batch", opts, rgb, img_off, w, h, frames, rows, out, stride, lens);
+}
+
+int32_t cniic_hilbert_zip_measure_batch(cniic_ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                        cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens) {
+    LOCK(c);
+    c->ktimes.clear();
+    return measure_batch_locked(c, kHilbertZipDesc, "hilbert_zip_measure_batch", nullptr, rgb, img_off, w, h, frames, rows, out, stride, lens);
 }
 
 int32_t cniic_synth_image(cniic_ctx *c, int32_t kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *rgb) {

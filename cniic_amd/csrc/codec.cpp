@@ -16,6 +16,7 @@
 #include "delta_small_dec.hpp"
 #include "huf_small.hpp"
 #include "rle_small.hpp"
+#include "hz_small.hpp"
 #include "zd_small.hpp"
 #include "zd_small_dec.hpp"
 #include "small_trie.hpp"
@@ -167,12 +168,13 @@ std::string codec_name(const CodecDesc &d) {
     case CODEC_DELTA: return "delta";                                     // hilbertc.rs:433-435
     case CODEC_HILBERT_RLE: return d.darg == 0.0 ? "hilbert-rle" : "hilbert-rle-approx_" + rust_f64_display(d.darg);  // hilbertc.rs:80-86
     case CODEC_ZIP_DICT: return "zip-dict";                               // zipc.rs:50-55
+    case CODEC_HILBERT_ZIP: return "hilbert-zip";                         // hilbertc.rs:80-86
     }
     return "";
 }
 
 bool codec_is_lossless(const CodecDesc &d) {   // (hilbertc.rs:88-93: RLE(d) is lossless iff d == 0.0 -- NaN is not)
-    return d.kind == CODEC_HUFMAN || d.kind == CODEC_DELTA || d.kind == CODEC_ZIP_DICT || (d.kind == CODEC_HILBERT_RLE && d.darg == 0.0);
+    return d.kind == CODEC_HUFMAN || d.kind == CODEC_DELTA || d.kind == CODEC_ZIP_DICT || d.kind == CODEC_HILBERT_ZIP || (d.kind == CODEC_HILBERT_RLE && d.darg == 0.0);
 }
 
 // F streams at a fixed distance (cc_finish_frames): assembled where the caller wants them when that is 4-byte aligned device memory,
@@ -1397,14 +1399,31 @@ static uint64_t zd_small_frame_bytes(uint64_t npx) {
     const uint64_t N = zs_text_len((uint32_t)npx);
     return zs_stride(N) + (8ull << zs_table_bits(N)) + sizeof(ZdSmallRow) + sizeof(ZdSmallResult);
 }
+// the same for Hilbert { compress: Zip }: 11 bytes of text a pixel, and the 8 bytes of the head in the slot (hz_small.hpp)
+static uint64_t hz_small_frame_bytes(uint64_t npx) {
+    const uint64_t N = hz_text_len((uint32_t)npx);
+    return hz_stride(N) + (8ull << zs_table_bits(N)) + sizeof(ZdSmallRow) + sizeof(ZdSmallResult);
+}
 // a stage mark that is a count, not a time
 static void stage_count(Ctx *c, const char *name, uint64_t n) {
     if (c->timers && n) c->ktimes[name].launches += n;
 }
 
-static int zd_small_chunk(Ctx *c, uint32_t spec, uint32_t giveup, VarFrame *const *fr, uint32_t n) {
+// The two codecs of the route (k_zd_small.hip: one body, two text kinds) differ on the host by the text's length, the slot, the launch and the names
+struct SmallZipKind {
+    const char *name, *t_batch, *t_place, *t_handback, *t_finished;
+    uint32_t (*text_len)(uint32_t npx);
+    uint64_t (*stride)(uint64_t N);
+    uint64_t (*frame_bytes)(uint64_t npx);
+    int (*run)(Ctx *, const ZdSmallRow *, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t *, uint32_t, uint8_t *, uint64_t, ZdSmallResult *);
+    uint32_t head;   // bytes of the stream in front of the pairs
+};
+static const SmallZipKind kSmallZipDict = {"zd_small", "zd_small_batch", "zd_small_place", "zd_small_handback", "zd_small_finished", zs_text_len, zs_stride, zd_small_frame_bytes, zd_small_run, 0};
+static const SmallZipKind kSmallHilbertZip = {"hz_small", "hz_small_batch", "hz_small_place", "hz_small_handback", "hz_small_finished", hz_text_len, hz_stride, hz_small_frame_bytes, hz_small_run, kHzHead};
+
+static int zd_small_chunk(Ctx *c, const SmallZipKind &kind, uint32_t spec, uint32_t giveup, VarFrame *const *fr, uint32_t n) {
     const uint64_t max_px = frame_px(*fr[0]);   // (largest first)
-    const uint64_t N = zs_text_len((uint32_t)max_px), sstride = zs_stride(N);
+    const uint64_t N = kind.text_len((uint32_t)max_px), sstride = kind.stride(N);
     const uint32_t bits = zs_table_bits(N);
     std::vector<ZdSmallRow> rows(n);
     for (uint32_t i = 0; i < n; i++) rows[i] = ZdSmallRow{fr[i]->src, fr[i]->w, fr[i]->h};
@@ -1412,8 +1431,8 @@ static int zd_small_chunk(Ctx *c, uint32_t spec, uint32_t giveup, VarFrame *cons
     CNIIC_HIP_TRY(c, scratch.alloc(sstride * n + 16));
     CNIIC_HIP_TRY(c, tables.alloc(((uint64_t)n << bits) * sizeof(uint64_t)));
     std::vector<ZdSmallResult> res;
-    CNIIC_TRY(run_rows(c, "zd_small_batch", rows, res, [&](const ZdSmallRow *rows_d, ZdSmallResult *res_d) {
-        return zd_small_run(c, rows_d, n, (uint32_t)max_px, spec, giveup, tables.as<uint64_t>(), bits, scratch.as<uint8_t>(), sstride, res_d);
+    CNIIC_TRY(run_rows(c, kind.t_batch, rows, res, [&](const ZdSmallRow *rows_d, ZdSmallResult *res_d) {
+        return kind.run(c, rows_d, n, (uint32_t)max_px, spec, giveup, tables.as<uint64_t>(), bits, scratch.as<uint8_t>(), sstride, res_d);
     }));
     std::vector<SmallStream> streams;
     uint64_t back = 0, finished = 0;
@@ -1421,23 +1440,28 @@ static int zd_small_chunk(Ctx *c, uint32_t spec, uint32_t giveup, VarFrame *cons
         finished += res[i].finished;
         if (res[i].verdict == kZsHandedBack) { fr[i]->handed_back = true; back++; continue; }
         const uint64_t len = res[i].len;   // one pair at least
-        if (res[i].verdict != kZsOk || len < 4 || len != 4ull * res[i].pairs || len > sstride)
-            return c->fail(CNIIC_ERR_HIP, "zd_small: a stream of %llu bytes in a slot of %llu", (unsigned long long)len, (unsigned long long)sstride);
+        if (res[i].verdict != kZsOk || len < kind.head + 4 || len != kind.head + 4ull * res[i].pairs || len > sstride)
+            return c->fail(CNIIC_ERR_HIP, "%s: a stream of %llu bytes in a slot of %llu", kind.name, (unsigned long long)len, (unsigned long long)sstride);
         streams.push_back(SmallStream{i, fr[i], len});
     }
-    stage_count(c, "zd_small_handback", back);
-    stage_count(c, "zd_small_finished", finished);
-    return place_streams(c, scratch, sstride, n, streams, "zd_small_place");
+    stage_count(c, kind.t_handback, back);
+    stage_count(c, kind.t_finished, finished);
+    return place_streams(c, scratch, sstride, n, streams, kind.t_place);
 }
 
-int zd_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) {
-    uint32_t giveup = kZsGiveUp;   // the testing library lowers both caps with one knob
-    if (const char *e = test_env("CNIIC_TEST_ZD_SMALL_CAP")) giveup = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kZsGiveUp);
+// the give-up cap of a call: the testing library lowers both caps with one knob (never above the kernel's own)
+static uint32_t small_zip_giveup(const char *e) { return e ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), kZsGiveUp) : kZsGiveUp; }
+static int small_zip_encode(Ctx *c, const SmallZipKind &kind, uint32_t giveup, VarFrame *const *fr, uint32_t n) {
     const uint32_t spec = std::min(kZsSpecCap, giveup);
     const uint64_t budget = test_budget(kZdSmallScratch);
-    return for_chunks(fr, n, [&](const VarFrame &first) { return budget / zd_small_frame_bytes(frame_px(first)); },
-                      [&](VarFrame *const *chunk, uint32_t cnt) { return zd_small_chunk(c, spec, giveup, chunk, cnt); });
+    return for_chunks(fr, n, [&](const VarFrame &first) { return budget / kind.frame_bytes(frame_px(first)); },
+                      [&](VarFrame *const *chunk, uint32_t cnt) { return zd_small_chunk(c, kind, spec, giveup, chunk, cnt); });
 }
+
+int zd_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) { return small_zip_encode(c, kSmallZipDict, small_zip_giveup(test_env("CNIIC_TEST_ZD_SMALL_CAP")), fr, n); }
+
+// ---- small Hilbert { compress: Zip } frames of a batch call, all at once (k_hz_small in k_zd_small.hip): the chunk above under the other kind
+int hz_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n) { return small_zip_encode(c, kSmallHilbertZip, small_zip_giveup(test_env("CNIIC_TEST_HZ_SMALL_CAP")), fr, n); }
 
 // ---- small voronoi(K) frames of a batch call, all at once (k_vor_small.hip)
 // A chunk's scratch is a slot per frame for the stream (16 + 19 K bytes, rounded up to 16), its row and its result row; the chunks stay
@@ -1737,6 +1761,7 @@ int codec_encode(Ctx *c, const CodecDesc &d, const uint8_t *rgb_d, uint32_t w, u
     case CODEC_DELTA: return encode_delta(c, rgb_d, w, h, out, cap, len);
     case CODEC_HILBERT_RLE: return encode_hilbert_rle(c, d.darg, rgb_d, w, h, out, cap, len);
     case CODEC_ZIP_DICT: return encode_zip_dict(c, rgb_d, w, h, out, cap, len);
+    case CODEC_HILBERT_ZIP: return encode_hilbert_zip(c, rgb_d, w, h, out, cap, len);
     }
     return c->fail(CNIIC_ERR_BAD_ARG, "unknown codec");
 }
@@ -1795,6 +1820,7 @@ constexpr uint64_t kTrieSecondLook = 512ull << 10;   // bytes of a `delta` strea
 int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbytes, uint8_t *rgb_out, uint64_t cap,
                  uint32_t *w, uint32_t *h) {
     if (d.kind == CODEC_ZIP_DICT) return decode_zip_dict(c, bytes, nbytes, rgb_out, cap, w, h);   // (its dimensions are inside the compressed text)
+    if (d.kind == CODEC_HILBERT_ZIP) return decode_hilbert_zip(c, bytes, nbytes, rgb_out, cap, w, h);   // (lenient: its own rules from the dimensions on)
     const bool bytes_dev = is_device_ptr(bytes);
     StreamHead head;
     // (the serialised decoder of a Huffman stream is at most a few per cent of it, for the images these codecs are meant for)
@@ -1963,6 +1989,7 @@ int codec_decode(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t nbyt
         return CNIIC_OK;
     }
     case CODEC_ZIP_DICT: break;   // (taken above)
+    case CODEC_HILBERT_ZIP: break;
     case CODEC_VORONOI: {  // clusterc.rs:168-189
         CNIIC_TRY(stream_head(c, bytes, bytes_dev, nbytes, nbytes, &head));  // 16 + 19 K bytes: parsed on the host
         const uint8_t *hb = head.p;
@@ -2529,20 +2556,76 @@ static uint64_t zd_small_dec_floor_px(uint64_t candidates) {
     if (const char *e = test_env("CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
     return candidates >= kZdSmallDecFloorMany ? kZdSmallDecFloorPxMany : candidates >= kZdSmallDecFloorFew ? kZdSmallDecFloorPxFew : 0;
 }
-static int zip_dict_batch(DecodeBatch &b) {
+// The two codecs of the route (k_zd_small_dec.hip: one body, two text kinds).  Hilbert { compress: Zip } (cniic_hilbert_zip_decode_batch)
+// differs on the host in this: the dimensions are the stream's first 8 bytes, raw, and the pairs follow them; a frame whose size has an
+// injected scan is the caller's (its single decode follows the injection); the lenient verdicts of hz_small.hpp.  Its floor is
+// hz_small_dec_floor_px below, measured for this codec.  (The knobs are functions, not names: the names must not be in the release library.)
+static_assert(kHzdOk == kZsdOk && kHzdHandedBack == kZsdHandedBack && kHzdBadSymbol == kZsdBadSymbol && kHzdDangling == kZsdDangling, "one set of verdicts for both kinds");
+struct SmallZipDecKind {
+    bool hilbert;
+    const char *name, *t_batch, *t_handback;
+    uint64_t (*max_px)();
+    uint64_t (*floor_px)(uint64_t candidates);
+    uint32_t (*max_pairs)();
+    uint32_t (*hops)();
+    uint32_t (*rounds)();
+    uint32_t (*lds_max)();
+    int (*run)(Ctx *, const ZdSmallDecRow *, uint32_t, uint32_t, uint32_t, uint32_t, ZdSmallDecResult *);
+};
+static const SmallZipDecKind kSmallDecZipDict = {
+    false, "zd_small_dec", "zd_small_dec_batch", "zd_small_dec_handback", zd_small_dec_max_px, zd_small_dec_floor_px,
+    [] { return test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_MAX_PAIRS", kZsdMaxPairs); }, [] { return test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_HOPS", kZsdHops); },
+    [] { return test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_ROUNDS", kZsdRounds); }, zd_small_dec_lds_max, zd_small_dec_run};
+
+// The floor of the Hilbert { compress: Zip } decode route.  Measured against this build with the route off (the worker contexts) and against
+// the parent commit's library, which can only loop over cniic_hilbert_zip_decode on one context (tools/small_zip_probe.py --codec hilbert-zip,
+// profiles/small_hz_probe.json; NOTES AS), photo-like, uniform noise and flat frames in device memory, whole decode call, medians of 5; a class
+// takes the route only where this route's slowest run beat the workers' fastest for all three contents:
+//   1 frame:      32 x 32 0.08 - 0.10 ms against 0.09 - 0.11 (the flat row's ranges touch); every larger size lost (0.17 - 0.93 ms against 0.09 - 0.30)
+//   4 frames:     32 x 32 won (0.09 - 0.10 ms against 0.21 - 0.35), 64 x 64 won (0.17 - 0.22 against 0.23 - 0.31; flat frames the closest: 0.22
+//                 at the slowest against 0.26 at the workers' fastest); the larger sizes lost (0.61 - 0.94 against 0.21 - 0.53)
+//   8 frames:     32 x 32 won (0.09 - 0.10 against 0.35 - 0.40), 64 x 64 won (0.17 - 0.21 against 0.36 - 0.54); 12 288 and 16 384 pixels did not
+//                 (0.61 - 0.94 against 0.31 - 0.58 and one slow run of 2.8)
+//   32 frames:    up to 64 x 64 won (4x - 9x); 128 x 128 and 16384 x 1 won (0.62 - 0.74 against 0.80 - 1.43), 128 x 96 did not: its general
+//                 walk makes the kernel 0.86 - 0.94 ms, and flat frames decode in 0.91 - 1.05 on the workers
+//   256 frames:   every size won (6x - 40x);  4096 frames: 32 x 32 1.4 - 1.6 ms against 80 - 93, 64 x 64 2.9 - 3.5 against 77 - 89 (larger sizes
+//                 not probed at this count)
+// The kernel's time is set by its heaviest frame; the workers' grows with the count, so a class that won with n frames wins with more.
+// So: fewer than kHzSmallDecFloorFew candidates stay with the workers; from there on the candidates of at most kHzSmallDecFloorPxFew
+// pixels take the route, and from kHzSmallDecFloorMany on all of them (a floor knows pixels, not shapes: 12 288 pixels lost at 32 frames,
+// so 16 384 waits for 256).  The testing library takes the floor away with CNIIC_TEST_HZ_SMALL_DEC_FLOOR_OFF=1.
+constexpr uint32_t kHzSmallDecFloorFew = 4, kHzSmallDecFloorMany = 256;
+constexpr uint64_t kHzSmallDecFloorPxFew = 4096, kHzSmallDecFloorPxMany = 16384;
+static uint64_t hz_small_dec_max_px() { return small_route_max_px("CNIIC_TEST_HZ_SMALL_DEC_OFF", "CNIIC_TEST_HZ_SMALL_DEC_MAX_PX", kHzSmallMaxPx); }
+static uint64_t hz_small_dec_floor_px(uint64_t candidates) {
+    if (const char *e = test_env("CNIIC_TEST_HZ_SMALL_DEC_FLOOR_OFF")) if (atoi(e) != 0) return ~0ull;
+    return candidates >= kHzSmallDecFloorMany ? kHzSmallDecFloorPxMany : candidates >= kHzSmallDecFloorFew ? kHzSmallDecFloorPxFew : 0;
+}
+static const SmallZipDecKind kSmallDecHilbertZip = {
+    true, "hz_small_dec", "hz_small_dec_batch", "hz_small_dec_handback", hz_small_dec_max_px, hz_small_dec_floor_px,
+    [] { return test_lower_cap("CNIIC_TEST_HZ_SMALL_DEC_MAX_PAIRS", kZsdMaxPairs); }, [] { return test_lower_cap("CNIIC_TEST_HZ_SMALL_DEC_HOPS", kZsdHops); },
+    [] { return test_lower_cap("CNIIC_TEST_HZ_SMALL_DEC_ROUNDS", kZsdRounds); }, hz_small_dec_lds_max, hz_small_dec_run};
+
+static int zip_dict_batch(DecodeBatch &b, const SmallZipDecKind &kind) {
     Ctx *c = b.c;
-    const uint64_t max_px = zd_small_dec_max_px();
+    const uint64_t max_px = kind.max_px();
+    const uint64_t head = kind.hilbert ? kHzHead : 0;   // bytes of a stream in front of its pairs
     Heads heads(b);
     std::vector<uint32_t> cand, cw, ch;
     auto classify = [&](uint32_t f) {
         if (b.off_route[f] || (b.F > 1 && b.stride < b.lens[f])) return;
         uint32_t fw = 0, fh = 0;
-        if (!zsd_head_dims(heads.head_p[f], std::min(heads.head_n[f], kZdDecHead), &fw, &fh)) return;   // (zip_dict_dims on the same bytes, without its table)
+        if (kind.hilbert) {
+            uint64_t pos;
+            if (b.lens[f] < kHzHead || !heads.dims(f, &fw, &fh, &pos)) return;
+            if (c->scan_xy.p && c->scan_w == fw && c->scan_h == fh) return;   // (a size with an injected scan: the single decode follows it)
+        } else if (!zsd_head_dims(heads.head_p[f], std::min(heads.head_n[f], kZdDecHead), &fw, &fh)) return;   // (zip_dict_dims on the same bytes, without its table)
         if (!dims_fit((uint64_t)fw * fh, max_px, b.img_stride)) return;
         cand.push_back(f); cw.push_back(fw); ch.push_back(fh);
     };
     if (b.bytes_dev) {
-        const uint64_t W = b.F == 1 ? kZdDecHead : std::min(kZdDecHead, b.stride);   // (a look is never wider than the stride)
+        const uint64_t look = kind.hilbert ? kHzHead : kZdDecHead;
+        const uint64_t W = b.F == 1 ? look : std::min(look, b.stride);   // (a look is never wider than the stride)
         if (!W) return CNIIC_OK;
         const uint32_t group = (uint32_t)(kBatchHeadsMax / W);
         for (uint32_t f0 = 0; f0 < b.F;) {
@@ -2555,7 +2638,7 @@ static int zip_dict_batch(DecodeBatch &b) {
         heads.in_place();
         for (uint32_t f = 0; f < b.F; f++) classify(f);
     }
-    const uint64_t floor_px = zd_small_dec_floor_px(cand.size());
+    const uint64_t floor_px = kind.floor_px(cand.size());
     std::vector<uint32_t> route;
     for (size_t i = 0; i < cand.size(); i++) {
         if ((uint64_t)cw[i] * ch[i] > floor_px) continue;
@@ -2564,11 +2647,10 @@ static int zip_dict_batch(DecodeBatch &b) {
     }
     if (route.empty()) return CNIIC_OK;
 
-    const uint32_t max_pairs = test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_MAX_PAIRS", kZsdMaxPairs), hops = test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_HOPS", kZsdHops),
-                   rounds = test_lower_cap("CNIIC_TEST_ZD_SMALL_DEC_ROUNDS", kZsdRounds);
-    const uint32_t lds_max = zd_small_dec_lds_max();
+    const uint32_t max_pairs = kind.max_pairs(), hops = kind.hops(), rounds = kind.rounds();
+    const uint32_t lds_max = kind.lds_max();
     const uint64_t budget = test_budget(kZdSmallDecScratch);
-    auto pairs_of = [&](uint32_t f) { return (uint32_t)std::min<uint64_t>(b.lens[f] / 4, max_pairs); };
+    auto pairs_of = [&](uint32_t f) { return (uint32_t)std::min<uint64_t>((b.lens[f] - head) / 4, max_pairs); };
     auto scratch_of = [&](uint32_t f) {
         return sizeof(ZdSmallDecRow) + sizeof(ZdSmallDecResult) + (b.dst_dev ? 0 : SlotLayout::room(b.image_bytes(f))) + (b.bytes_dev ? 0 : b.lens[f]);
     };
@@ -2597,17 +2679,17 @@ static int zip_dict_batch(DecodeBatch &b) {
         for (size_t j = 0; j < S; j++) {
             const size_t i = order[j];
             const uint32_t f = route[i0 + i];
-            rows[j] = ZdSmallDecRow{base + (uint64_t)f * b.stride, staged.dst(i, b.image(f)), b.lens[f], pairs_of(f), b.w[f], b.h[f], stage_pairs[i]};
+            rows[j] = ZdSmallDecRow{base + (uint64_t)f * b.stride + head, staged.dst(i, b.image(f)), b.lens[f] - head, pairs_of(f), b.w[f], b.h[f], stage_pairs[i]};
         }
         CNIIC_HIP_TRY(c, rows_d.alloc(S * sizeof(ZdSmallDecRow)));
         CNIIC_HIP_TRY(c, res_d.alloc(S * sizeof(ZdSmallDecResult)));
         CNIIC_HIP_TRY(c, hipMemcpyAsync(rows_d.p, rows.data(), S * sizeof(ZdSmallDecRow), hipMemcpyHostToDevice, c->stream));
         {
-            ScopedKernelTimer t(c, "zd_small_dec_batch");
+            ScopedKernelTimer t(c, kind.t_batch);
             for (size_t j0 = 0; j0 < S;) {
                 size_t j1 = j0 + 1;
                 while (j1 < S && lds[order[j1]] == lds[order[j0]]) j1++;
-                CNIIC_TRY(zd_small_dec_run(c, rows_d.as<ZdSmallDecRow>() + j0, (uint32_t)(j1 - j0), lds[order[j0]] & ~15u, hops, rounds, res_d.as<ZdSmallDecResult>() + j0));
+                CNIIC_TRY(kind.run(c, rows_d.as<ZdSmallDecRow>() + j0, (uint32_t)(j1 - j0), lds[order[j0]] & ~15u, hops, rounds, res_d.as<ZdSmallDecResult>() + j0));
                 j0 = j1;
             }
             t.stop(S);
@@ -2629,12 +2711,12 @@ static int zip_dict_batch(DecodeBatch &b) {
             case kZsdDangling: snprintf(text, sizeof text, "zip-dict: a first symbol without a second at the end of the stream"); break;
             case kZsdShort: snprintf(text, sizeof text, "zip-dict: the text ends after %llu of %llu bytes", (unsigned long long)r.a, (unsigned long long)r.b); break;
             case kZsdBadRecord: snprintf(text, sizeof text, "zip-dict: pixel %llu is not a record of 3 bytes (ser.rs:216-221)", (unsigned long long)r.a); break;
-            default: return c->fail(CNIIC_ERR_HIP, "zd_small_dec: verdict %u", r.verdict);
+            default: return c->fail(CNIIC_ERR_HIP, "%s: verdict %u", kind.name, r.verdict);
             }
             b.taken[f] = 1;
             b.decode_error(f, text);
         }
-        stage_count(c, "zd_small_dec_handback", back);
+        stage_count(c, kind.t_handback, back);
         i0 = i1;
     }
     return CNIIC_OK;
@@ -2822,10 +2904,11 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
     rcs.assign(F, CNIIC_OK);
     msgs.assign(F, std::string());
     if (!F || (d.kind != CODEC_HUFMAN && d.kind != CODEC_CLUSTER_COLORS && d.kind != CODEC_HILBERT_RLE && d.kind != CODEC_DELTA && d.kind != CODEC_VORONOI &&
-               d.kind != CODEC_ZIP_DICT))
+               d.kind != CODEC_ZIP_DICT && d.kind != CODEC_HILBERT_ZIP))
         return CNIIC_OK;
     if (d.kind == CODEC_VORONOI && !vor_small_dec_max_px()) return CNIIC_OK;
     if (d.kind == CODEC_ZIP_DICT && !zd_small_dec_max_px()) return CNIIC_OK;
+    if (d.kind == CODEC_HILBERT_ZIP && !hz_small_dec_max_px()) return CNIIC_OK;
     const bool delta = d.kind == CODEC_DELTA;
     if (delta && !delta_small_dec_max_px()) return CNIIC_OK;
     DecodeBatch b{c, bytes, is_device_ptr(bytes), stride, lens, F, rgb, is_device_ptr(rgb), img_stride, w, h, taken, rcs, msgs, std::vector<uint8_t>(F, 0)};
@@ -2839,7 +2922,8 @@ int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, u
         }
     if (d.kind == CODEC_HILBERT_RLE) return rle_batch(b);
     if (d.kind == CODEC_VORONOI) return voronoi_batch(b);
-    if (d.kind == CODEC_ZIP_DICT) return zip_dict_batch(b);
+    if (d.kind == CODEC_ZIP_DICT) return zip_dict_batch(b, kSmallDecZipDict);
+    if (d.kind == CODEC_HILBERT_ZIP) return zip_dict_batch(b, kSmallDecHilbertZip);
     return huffman_batch(b, delta);
 }
 

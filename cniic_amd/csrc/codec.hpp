@@ -7,7 +7,9 @@
 
 namespace cniic {
 
-enum CodecKind { CODEC_HUFMAN = 1, CODEC_CLUSTER_COLORS = 2, CODEC_VORONOI = 3, CODEC_DELTA = 4, CODEC_HILBERT_RLE = 5, CODEC_ZIP_DICT = 6 };
+// CODEC_HILBERT_ZIP is internal: Hilbert { compress: Zip } is no expression here (parse_codec never produces it, and the entry points that take an
+// expression do not know it); cniic_hilbert_zip_*_batch* make the descriptor themselves and drive the batch engines with it.
+enum CodecKind { CODEC_HUFMAN = 1, CODEC_CLUSTER_COLORS = 2, CODEC_VORONOI = 3, CODEC_DELTA = 4, CODEC_HILBERT_RLE = 5, CODEC_ZIP_DICT = 6, CODEC_HILBERT_ZIP = 7 };
 
 struct CodecDesc {
     int      kind;
@@ -71,6 +73,10 @@ int rle_small_encode(Ctx *c, double d, VarFrame *const *fr, uint32_t n);
 //                with handed_back set and nothing else filled in ("zd_small_handback": launches = such frames; "zd_small_finished": launches = walks the
 //                commit wave finished); st stays zero
 int zd_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
+//   hz_small     Hilbert { compress: Zip } (CODEC_HILBERT_ZIP), kHzSmallMaxPx: k_hz_small, zd_small's kernel body over the text of hz_small.hpp (the pixels in scan
+//                order, no dimensions; the 8 raw bytes of the dimensions in front of the pairs); the same scratch, caps (CNIIC_TEST_HZ_SMALL_CAP) and marks
+//                ("hz_small_handback", "hz_small_finished"); st stays zero
+int hz_small_encode(Ctx *c, VarFrame *const *fr, uint32_t n);
 
 // ---- output assembly
 // The encoded stream (host-built header + device-packed payload) is assembled in HBM: directly in
@@ -138,8 +144,8 @@ int encode_zip_back_batch(Ctx *c, const uint8_t *rgb, const uint64_t *img_off, c
 int decode_zip_back_batch(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, uint64_t img_stride, uint32_t *w,
                           uint32_t *h, int32_t *rcs);
 
-// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames and the small `delta`, `voronoi` and `zip(dict)`
-// frames of a batch decoded together (stream f at bytes + f *
+// cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames and the small `delta`, `voronoi`, `zip(dict)`
+// and (cniic_hilbert_zip_decode_batch) Hilbert { compress: Zip } frames of a batch decoded together (stream f at bytes + f *
 // stride, lens[f] bytes; image f to rgb + f * img_stride).  taken[f] = 1: frame f was decoded here (rcs[f], msgs[f], w[f], h[f]); 0: the
 // caller decodes it on its own (codec_decode).
 int codec_decode_batch_route(Ctx *c, const CodecDesc &d, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb,

@@ -974,6 +974,10 @@ struct ZdSmallRow { const uint8_t *src; uint32_t w, h; };
 struct ZdSmallResult { uint32_t pairs, len, verdict, finished; };   // ..., walks the commit finished behind the speculation's cap
 int zd_small_run(Ctx *c, const ZdSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t spec, uint32_t giveup, uint64_t *tables_d,
                  uint32_t bits, uint8_t *scratch_d, uint64_t sstride, ZdSmallResult *res_d);
+// the same for Hilbert { compress: Zip } (k_hz_small, hz_small.hpp): sstride >= hz_stride, bits >= zs_table_bits of the largest frame's 11 n
+// bytes of text; the stream in the slot is the 8 raw bytes of the dimensions and the pairs, len = 8 + 4 pairs
+int hz_small_run(Ctx *c, const ZdSmallRow *rows_d, uint32_t frames, uint32_t max_px /* of the largest frame */, uint32_t spec, uint32_t giveup, uint64_t *tables_d,
+                 uint32_t bits, uint8_t *scratch_d, uint64_t sstride, ZdSmallResult *res_d);
 // ---- k_zd_small_dec.hip: the decode of small `zip(dict)` frames, one workgroup per frame from its pairs to its pixels (zd_small_dec.hpp
 // has the arithmetic, the limits and the verdicts).  A row per frame: its stream (device memory, any alignment; len bytes, of which the
 // kernel looks at `pairs` = min(len / 4, the pair cap) pairs), where its w x h x 3 image goes (device memory, any alignment; written whole
@@ -984,6 +988,11 @@ struct ZdSmallDecRow { const uint8_t *stream; uint8_t *dst; uint64_t len; uint32
 struct ZdSmallDecResult { uint32_t verdict, a, b, pad; };
 uint32_t zd_small_dec_lds_max();
 int zd_small_dec_run(Ctx *c, const ZdSmallDecRow *rows_d, uint32_t frames, uint32_t lds_bytes, uint32_t hops, uint32_t rounds, ZdSmallDecResult *res_d);
+// the same for Hilbert { compress: Zip } (k_hz_small_dec, hz_small.hpp): stream / len are the PAIRS behind the 8 raw bytes of the dimensions,
+// w and h what those bytes say; the verdicts are kHzdOk (the image is written whole, zeros where the text gives no colour), kHzdHandedBack,
+// kHzdBadSymbol (a = the pair) and kHzdDangling; lds_bytes is hz_small_dec_lds_max() at most
+uint32_t hz_small_dec_lds_max();
+int hz_small_dec_run(Ctx *c, const ZdSmallDecRow *rows_d, uint32_t frames, uint32_t lds_bytes, uint32_t hops, uint32_t rounds, ZdSmallDecResult *res_d);
 // ---- k_delta_small_dec.hip: the decode of small `delta` frames, one workgroup per frame (delta_small_dec.hpp has the arithmetic and the
 // limits).  A row per frame: its payload (device memory, any alignment; payload_bytes to the stream's end), where its w x h x 3 image goes
 // (device memory, any alignment) and its decoder as `leaves` words of left-aligned codes, ascending, and as many key | length << 27 words

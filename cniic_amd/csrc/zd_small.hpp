@@ -47,6 +47,8 @@ CNIIC_ZS_HD uint8_t zs_text_byte(uint32_t i, uint32_t w, uint32_t h, const uint8
     const uint32_t j = i - 8, p = j / 11, r = j - 11 * p;
     return r == 0 ? 3 : r < 8 ? 0 : pixels[3 * p + (r - 8)];
 }
+// A text kind is a type with N, the text's length, and operator[](i), its byte i: the walks, the commit and the inserts below take any
+// (ZsText here; HzText of hz_small.hpp, the text of Hilbert { compress: Zip }).
 struct ZsText {
     const uint8_t *px;
     uint32_t w, h, N;
@@ -103,13 +105,14 @@ CNIIC_ZS_HD uint32_t zs_claim(uint64_t *tab, uint32_t bits, uint32_t key, uint64
 // ---- a walk (DictEncoder::find_symbol, dict.rs:96-136) from text position q: `depth` bytes read so far, standing on `node`; (sym, len) the
 // deepest symbol on the way.  open: the walk has not ended yet (it ends where the node has no child for the next byte, or with the text).
 struct ZsWalk { uint32_t sym, len, node, depth, open; };
-CNIIC_ZS_HD ZsWalk zs_walk_begin(const ZsText &t, uint32_t q) {
+template <class Text>
+CNIIC_ZS_HD ZsWalk zs_walk_begin(const Text &t, uint32_t q) {
     const uint32_t b = t[q];
     return ZsWalk{b, 1u, 1u + b, 1u, 1u};
 }
 // goes on until the walk ends or has read `stop` bytes
-template <class Mem>
-CNIIC_ZS_HD void zs_walk(const uint64_t *tab, uint32_t bits, const ZsText &t, uint32_t q, uint32_t stop, ZsWalk &s) {
+template <class Mem, class Text>
+CNIIC_ZS_HD void zs_walk(const uint64_t *tab, uint32_t bits, const Text &t, uint32_t q, uint32_t stop, ZsWalk &s) {
     while (s.open) {
         if (q + s.depth >= t.N) { s.open = 0; break; }
         if (s.depth >= stop) break;
@@ -124,8 +127,8 @@ CNIIC_ZS_HD void zs_walk(const uint64_t *tab, uint32_t bits, const ZsText &t, ui
 }
 
 // ---- TrieMap::insert (dict.rs:308-323) of text[start, start + len), len >= 2, with symbol sym; any number of them at once
-template <class Mem>
-CNIIC_ZS_HD void zs_insert(uint64_t *tab, uint32_t bits, const ZsText &t, uint32_t start, uint32_t len, uint32_t sym) {
+template <class Mem, class Text>
+CNIIC_ZS_HD void zs_insert(uint64_t *tab, uint32_t bits, const Text &t, uint32_t start, uint32_t len, uint32_t sym) {
     uint32_t node = 1u + t[start];
     for (uint32_t j = 1; j < len; j++) {
         uint64_t v = 0;
@@ -167,7 +170,8 @@ CNIIC_ZS_HD uint32_t zs_need(const ZsState &st) { return st.have1 ? st.mid : st.
 
 // The longest entry of the list among those that lane `lane` of `lanes` looks at (entries lane, lane + lanes, ...) that is longer than
 // `len` and spells the text at q: its length << 16 | its symbol, or 0.
-CNIIC_ZS_HD uint64_t zs_repair_lane(const ZsText &t, const ZsWindow &win, uint32_t nlist, uint32_t q, uint32_t len, uint32_t lane, uint32_t lanes) {
+template <class Text>
+CNIIC_ZS_HD uint64_t zs_repair_lane(const Text &t, const ZsWindow &win, uint32_t nlist, uint32_t q, uint32_t len, uint32_t lane, uint32_t lanes) {
     uint64_t best = 0;
     for (uint32_t e = lane; e < nlist; e += lanes) {
         const uint32_t el = win.e_len[e], es = win.e_start[e];
@@ -182,8 +186,8 @@ CNIIC_ZS_HD uint64_t zs_repair_lane(const ZsText &t, const ZsWindow &win, uint32
 // The commit of one window: DictEncoder::next_pair from zs_need(st) on, while the needed position lies in [base, base + W) and the list
 // has room.  Every lane of the committing wave calls it with the same arguments (the host: one call); Lanes::best(f) is the maximum of
 // f(lane) over the lanes, Lanes::first() is true on the one lane that writes the pairs.  out: the frame's stream, 4-byte aligned.
-template <class Mem, class Lanes>
-CNIIC_ZS_HD void zs_commit(const uint64_t *tab, uint32_t bits, const ZsText &t, const ZsWindow &win, uint32_t base, uint32_t W, uint32_t limit, uint32_t giveup,
+template <class Mem, class Lanes, class Text>
+CNIIC_ZS_HD void zs_commit(const uint64_t *tab, uint32_t bits, const Text &t, const ZsWindow &win, uint32_t base, uint32_t W, uint32_t limit, uint32_t giveup,
                            uint32_t *out, ZsState &st) {
     st.nlist = 0;
     for (;;) {

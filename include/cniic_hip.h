@@ -123,7 +123,12 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * The small-frame decode route of `zip(dict)` in cniic_codec_decode_batch and cniic_codec_measure_batch (described there):
  * "zd_small_dec_batch" = the duration of k_zd_small_dec, with launches = the frames it was given; "zd_small_dec_handback": launches = the
  * frames of those the kernel handed back (pairs behind its cap of 24 576, 64 or more generations, a byte behind more than 64 pairs)
- * and the worker contexts decoded. */
+ * and the worker contexts decoded.
+ * The small-frame routes of Hilbert { compress: Zip } in cniic_hilbert_zip_encode_batch_var, cniic_hilbert_zip_decode_batch and
+ * cniic_hilbert_zip_measure_batch (described there) report the same marks under their own names: "hz_small_batch" = the duration of
+ * k_hz_small (and of zeroing its trie tables), with launches = the frames given to the kernel; "hz_small_place"; "hz_small_handback";
+ * "hz_small_finished"; "hz_small_dec_batch" = the duration of k_hz_small_dec, with launches = the frames it was given;
+ * "hz_small_dec_handback".  No call that takes an expression reports any of them. */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
@@ -507,8 +512,9 @@ int32_t cniic_huf_size(int32_t sym_kind, const uint64_t *counts, uint64_t n, uin
  * codec; hilbertc.rs:341-397 for the last two: rle(<f64>) takes what Rust's f64::from_str takes -- "4", "+4", "4.", ".5", "1e-3",
  * "inf", "-infinity", "nan" -- and its name() is "hilbert-rle" for d == 0, else "hilbert-rle-approx_" + d as Rust's Display prints
  * it, which can be longer than 300 characters), "zip(dict)" (zipc.rs:62-80: exactly that; name() "zip-dict", lossless; zip(back) and
- * hilbert(zip) are built, but are not expressions here: cniic_zip_back_image_encode / cniic_hilbert_zip_encode and their kin below).  Every entry point below that
- * takes an expression takes all of them.  The dimensions of a zip(dict) stream are inside its compressed text: cniic_zip_dict_dims.
+ * hilbert(zip) are built, but are not expressions here and every entry point that takes an expression rejects them: they have entry points
+ * of their own, single and batched -- cniic_zip_back_image_encode, cniic_hilbert_zip_encode and their kin below).  Every entry point below
+ * that takes an expression takes all of the expressions listed.  The dimensions of a zip(dict) stream are inside its compressed text: cniic_zip_dict_dims.
  * cniic_codec_parse describes a codec as (kind, u32 argument), which cannot carry the f64: it answers CNIIC_ERR_BAD_ARG for
  * hilbert(rle(d)) with d != 0.  cniic_codec_parse_f64 takes every expression; darg is d (0 for d == 0.0 and -0.0, for `hilbert(rle)`
  * and for the other codecs).  Any out-parameter may be NULL. */
@@ -658,6 +664,31 @@ int32_t cniic_zip_dict_dims(const uint8_t *bytes, uint64_t n, uint32_t *w, uint3
  * before it gives up: what is malformed behind such a record is not reported here).  Host or device buffers. */
 int32_t cniic_hilbert_zip_encode(cniic_ctx *ctx, const uint8_t *rgb, uint32_t w, uint32_t h, uint8_t *out, uint64_t cap, uint64_t *len);
 int32_t cniic_hilbert_zip_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *rgb, uint64_t cap, uint32_t *w, uint32_t *h);
+/* The harness's many-images loop (src/bench.rs:24-35; its measure_all loop body :41-60 for the third call) for Hilbert { compress: Zip }
+ * (hilbertc.rs:27-29,47-49,58-62,73-77), the codec behind the reference Makefile's output/hilbert-zip.csv: the layouts, HOST arrays,
+ * per-frame rcs, return of the first failure, frames == 0 and stage-timer sums of cniic_codec_encode_batch_var, cniic_codec_decode_batch
+ * and cniic_codec_measure_batch (described there), without expr, opts and stats.
+ * Stream f, lens[f] and rcs[f] are byte for byte what cniic_hilbert_zip_encode gives for image f alone (CNIIC_ERR_CAPACITY with lens[f] =
+ * bytes needed and the frame's room untouched); image f, w[f], h[f] and rcs[f] are what cniic_hilbert_zip_decode gives for stream f alone,
+ * with its lenient rules: colours the text does not reach stay zero, and so do the colours from the first record on whose length is not 3;
+ * a malformed pair inside the needed 11 w h bytes is CNIIC_ERR_DECODE; nothing behind the pair that completes the last record is looked
+ * at.  A frame that fails leaves the others as they are.  The measure call's rows are encode -> decode -> cniic_mse of every frame alone.
+ * Small frames: DEVICE images of 1 .. 16 384 pixels whose size has no injected scan (cniic_ctx_set_scan: those stay with the worker
+ * contexts, which follow the injection) are coded together, a workgroup per frame (k_hz_small: zip(dict)'s small-frame kernel over this
+ * codec's text), and streams of such frames are decoded together (k_hz_small_dec); a frame the kernels give up (a match longer than 1024
+ * bytes; pairs behind the cap of 24 576, 64 or more generations, a byte behind more than 64 pairs) is handed back to the workers.  The
+ * floors from which the routes are taken were measured for this codec against the worker contexts (NOTES AS), under one rule: a class of
+ * calls takes a route only where it beat the workers for photo-like, noise and flat frames alike.  The decode route takes the streams of at
+ * most 4096 pixels from 4 candidate streams on and every routed size from 256 on.  The ENCODE route is taken by no class: flat frames, which
+ * its kernel hands back, lost to the workers at every probed count (photo-like and noise frames of at most 4096 pixels won 1.6x - 4.6x from
+ * 256 frames on), so in this library every image is coded by the worker contexts and the "hz_small_batch" marks are never reported; the
+ * testing library reaches the route.  Which route a frame
+ * took shows in no output byte, dimension, status or message.  Stage timers: "hz_small_batch", "hz_small_place", "hz_small_handback",
+ * "hz_small_finished", "hz_small_dec_batch", "hz_small_dec_handback" (cniic_last_kernel_time). */
+int32_t cniic_hilbert_zip_encode_batch_var(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h,
+                                           uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs);
+int32_t cniic_hilbert_zip_decode_batch(cniic_ctx *ctx, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
+                                       uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
 /* The look-back coder on plain bytes (zip::zip_back_encode / zip_back_decode, src/zip/back.rs:5-21).  The stream is what the reference
  * writes: symbols headed by a little-endian u16 (bit 15 the kind, the low 15 bits len) -- explicit, len literal bytes behind it, or
  * look-back, a little-endian u16 `back` behind it: min(len, back) bytes from `back` bytes before the end of the text so far.  Encode
@@ -810,6 +841,10 @@ typedef struct {
 int32_t cniic_codec_measure_batch(cniic_ctx *ctx, const char *expr, const cniic_kmeans_opts *opts, const uint8_t *rgb, const uint64_t *img_off,
                                   const uint32_t *w, const uint32_t *h, uint32_t frames, cniic_measure_row *rows,
                                   uint8_t *out, uint64_t stride, uint64_t *lens);
+/* The same for Hilbert { compress: Zip } (bench.rs:41-60 with that codec; described at cniic_hilbert_zip_encode_batch_var): row f equals
+ * cniic_hilbert_zip_encode -> cniic_hilbert_zip_decode -> cniic_mse of image f alone; rows[f].kmeans stays zero. */
+int32_t cniic_hilbert_zip_measure_batch(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                        cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens);
 
 /* ------------------------------------------------------------------ surfaces: what a decoder or a crop hands over <-> packed RGB24 */
 /* Every call above takes packed RGB24, rows back to back; the reference takes an image::DynamicImage and begins with px.to_rgb() per

@@ -18,7 +18,13 @@ seconds for 4096 frames of 16 384 pixels).
 under CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF=1 as well, `route_off` under CNIIC_TEST_ZD_SMALL_DEC_OFF=1, the stage child records
 "zd_small_dec_batch" and "zd_small_dec_handback", and a digest of all decoded images must agree between the variants.  --host decodes from
 and into host memory.  `clear` in a decode cell: this build's slowest run beats the other's fastest -- the ranges do not overlap -- which
-is what the route's floor is set from (`lost`: the other way round)."""
+is what the route's floor is set from (`lost`: the other way round).
+
+--codec hilbert-zip probes Hilbert { compress: Zip } instead: cniic_hilbert_zip_encode_batch_var, cniic_hilbert_zip_measure_batch and
+cniic_hilbert_zip_decode_batch (k_hz_small, k_hz_small_dec) under the CNIIC_TEST_HZ_SMALL_* knobs, the stages "hz_small_*".  A library that
+has no such calls -- the parent commit's, which is the yardstick -- runs the loop of cniic_hilbert_zip_encode / cniic_hilbert_zip_decode
+(and cniic_mse for measure) over the same device buffers on one context, which is all it can do.  Every cell carries `clear` / `lost` against that yardstick, and
+`route_off_range` with `clear_of_route_off` / `lost_to_route_off` against this build's own workers, which is what the floors are set from."""
 import argparse
 import hashlib
 import json
@@ -39,6 +45,9 @@ OFF, FLOOR_OFF = "CNIIC_TEST_ZD_SMALL_OFF", "CNIIC_TEST_ZD_SMALL_FLOOR_OFF"
 DEC_OFF, DEC_FLOOR_OFF = "CNIIC_TEST_ZD_SMALL_DEC_OFF", "CNIIC_TEST_ZD_SMALL_DEC_FLOOR_OFF"
 CALLS = ("encode", "measure", "decode")
 EXPR = "zip(dict)"
+HZ_STAGES = ("hz_small_batch", "hz_small_place", "hz_small_handback", "hz_small_finished", "hz_small_dec_batch", "hz_small_dec_handback")
+HZ_OFF, HZ_FLOOR_OFF = "CNIIC_TEST_HZ_SMALL_OFF", "CNIIC_TEST_HZ_SMALL_FLOOR_OFF"
+HZ_DEC_OFF, HZ_DEC_FLOOR_OFF = "CNIIC_TEST_HZ_SMALL_DEC_OFF", "CNIIC_TEST_HZ_SMALL_DEC_FLOOR_OFF"
 
 
 def cases(a):
@@ -48,12 +57,71 @@ def cases(a):
     return [(w, h, F, kind) for kind in kinds for (w, h) in sizes for F in frames if not a.max_px or w * h * F <= a.max_px]
 
 
+def hz_calls(ctx, src, offs, ws, hs, enc, stride, res, host, dev):
+    """encode / measure / decode of Hilbert { compress: Zip }: the batch calls where the library has them, else the loop of single calls"""
+    import ctypes as C
+    import numpy as np
+    import torch
+    L, F = ctx._L, len(offs)
+    batched = hasattr(L, "cniic_hilbert_zip_encode_batch_var")
+    nb = 3 * ws[0] * hs[0]
+    p_src, p_enc = src.data_ptr(), enc.data_ptr()
+    L.cniic_hilbert_zip_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.cniic_hilbert_zip_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+
+    def encode_loop(dst, dst_stride):
+        lens, rcs, ln = [], [], C.c_uint64(0)
+        for f in range(F):
+            rcs.append(L.cniic_hilbert_zip_encode(ctx.h, p_src + offs[f], ws[f], hs[f], dst + f * dst_stride, dst_stride, C.byref(ln)))
+            lens.append(ln.value)
+        return next((r for r in rcs if r), 0), lens, rcs, None
+
+    def decode_loop(streams, lens, img, img_stride):
+        cw, ch, rcs = C.c_uint32(0), C.c_uint32(0), []
+        for f in range(F):
+            rcs.append(L.cniic_hilbert_zip_decode(ctx.h, streams + f * stride, lens[f], img + f * img_stride, img_stride, C.byref(cw), C.byref(ch)))
+        return next((r for r in rcs if r), 0), list(ws), list(hs), rcs
+
+    def encode():
+        res["e"] = ctx.hilbert_zip_encode_batch_var(src, offs, ws, hs, enc, stride) + (None,) if batched else encode_loop(p_enc, stride)
+
+    def measure():
+        if batched:
+            res["m"] = ctx.hilbert_zip_measure_batch(src, offs, ws, hs)
+            return
+        if "mbuf" not in res:
+            res["mbuf"] = (torch.zeros(stride * F, dtype=torch.uint8, device=dev), torch.zeros(nb * F + 16, dtype=torch.uint8, device=dev))
+        sbuf, ibuf = res["mbuf"]
+        rc, lens, rcs, _ = encode_loop(sbuf.data_ptr(), stride)
+        decode_loop(sbuf.data_ptr(), lens, ibuf.data_ptr(), nb)
+        rows = []
+        for f in range(F):
+            rows.append(dict(compressed_size=lens[f], error=ctx.mse(src[offs[f]:offs[f] + nb], ibuf[f * nb:(f + 1) * nb])))
+        res["m"] = (rc, rows, lens)
+
+    def decode():
+        if "img" not in res:
+            if host:
+                res["img"], res["streams"] = np.zeros(nb * F + 16, np.uint8), enc.cpu().numpy()
+            else:
+                res["img"], res["streams"] = torch.zeros(nb * F + 16, dtype=torch.uint8, device=dev), enc
+            res["lens"] = res["e"][1]
+        if batched:
+            res["d"] = ctx.hilbert_zip_decode_batch(res["streams"], stride, res["lens"], F, res["img"], nb)
+        else:
+            at = lambda x: x.ctypes.data if host else x.data_ptr()
+            res["d"] = decode_loop(at(res["streams"]), res["lens"], at(res["img"]), nb)
+    return dict(encode=encode, measure=measure, decode=decode)
+
+
 def child(a):
     import torch
     import cniic_amd
     from cniic_amd import _lib, synth
     dev = torch.device("cuda", 0)
     out = {}
+    hz = a.codec == "hilbert-zip"
+    stage_names = HZ_STAGES if hz else STAGES
     with cniic_amd.Context(0) as ctx:
         for w, h, F, kind in cases(a):
             n, nb = w * h, 3 * w * h
@@ -88,7 +156,8 @@ def child(a):
                         res["img"], res["streams"] = torch.zeros(nb * F + 16, dtype=torch.uint8, device=dev), enc
                     res["lens"] = lens
                 res["d"] = ctx.decode_batch(EXPR, res["streams"], stride, res["lens"], F, res["img"], nb)
-            calls = dict(encode=encode, measure=measure, decode=decode)
+            calls = hz_calls(ctx, src, offs, ws, hs, enc, stride, res, a.host, dev) if hz else dict(encode=encode, measure=measure, decode=decode)
+            encode, decode = calls["encode"], calls["decode"]
             name = "%s %dx%d x%d" % (kind, w, h, F)
             if a.stages:
                 got = {}
@@ -97,7 +166,7 @@ def child(a):
                 ctx.set_opt(_lib.OPT_STAGE_TIMERS, 1)
                 for call in (encode, decode):
                     call()
-                    for s in STAGES:
+                    for s in stage_names:
                         ms, cnt = ctx.kernel_time(s)
                         if cnt or ms:
                             got[s] = dict(ms=round(ms, 3), launches=cnt)
@@ -122,7 +191,7 @@ def child(a):
                     torch.cuda.synchronize()
                     ts.append(round((time.perf_counter() - t) * 1e3, 3))
                 row[which] = ts
-            rc, lens, rcs, sts = res["e"]
+            rc, lens, rcs = res["e"][:3]
             host = enc.cpu().numpy()
             dg = hashlib.sha256()
             for f in range(F):
@@ -153,6 +222,7 @@ def main():
     ap.add_argument("--max-px", type=int, default=0, help="skip the cases of more pixels in all")
     ap.add_argument("--calls", help="the calls to time, of encode,measure,decode (default: encode,measure)")
     ap.add_argument("--host", action="store_true", help="decode from and into host memory")
+    ap.add_argument("--codec", default="zip-dict", choices=("zip-dict", "hilbert-zip"), help="zip-dict: the expression zip(dict); hilbert-zip: Hilbert { compress: Zip }'s own calls")
     ap.add_argument("--variants", help="of this,route_off,other (this is always run)")
     ap.add_argument("--floor", action="store_true", help="`this` keeps the route's floor")
     ap.add_argument("--timeout", type=int, default=1100)
@@ -161,13 +231,15 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a)
-    this_env = {"CNIIC_USE_TESTING_LIB": "1"} if a.floor else {"CNIIC_USE_TESTING_LIB": "1", FLOOR_OFF: "1", DEC_FLOOR_OFF: "1"}
-    variants = [("this", this_env), ("route_off", {"CNIIC_USE_TESTING_LIB": "1", OFF: "1", DEC_OFF: "1"})]
+    hz = a.codec == "hilbert-zip"
+    off, floor_off, dec_off, dec_floor_off = (HZ_OFF, HZ_FLOOR_OFF, HZ_DEC_OFF, HZ_DEC_FLOOR_OFF) if hz else (OFF, FLOOR_OFF, DEC_OFF, DEC_FLOOR_OFF)
+    this_env = {"CNIIC_USE_TESTING_LIB": "1"} if a.floor else {"CNIIC_USE_TESTING_LIB": "1", floor_off: "1", dec_floor_off: "1"}
+    variants = [("this", this_env), ("route_off", {"CNIIC_USE_TESTING_LIB": "1", off: "1", dec_off: "1"})]
     if a.against:
         variants.append(("other", {"CNIIC_LIB_FILE": a.against}))
     if a.variants:
         variants = [v for v in variants if v[0] == "this" or v[0] in a.variants.split(",")]
-    base = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup), "--max-px", str(a.max_px)]
+    base = [sys.executable, os.path.abspath(__file__), "--child", "--codec", a.codec, "--reps", str(a.reps), "--warmup", str(a.warmup), "--max-px", str(a.max_px)]
     for k in ("sizes", "frames", "kinds", "calls"):
         if getattr(a, k):
             base += ["--" + k, getattr(a, k)]
@@ -175,7 +247,7 @@ def main():
         base.append("--host")
 
     def run(env_add, extra=()):
-        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", OFF, FLOOR_OFF, DEC_OFF, DEC_FLOOR_OFF)}
+        env = {k: v for k, v in os.environ.items() if k not in ("CNIIC_LIB_FILE", "CNIIC_USE_TESTING_LIB", OFF, FLOOR_OFF, DEC_OFF, DEC_FLOOR_OFF, HZ_OFF, HZ_FLOOR_OFF, HZ_DEC_OFF, HZ_DEC_FLOOR_OFF)}
         env.update(env_add)
         r = subprocess.run(base + list(extra), stdout=subprocess.PIPE, text=True, timeout=a.timeout, env=env)   # (a child's progress lines go to stderr as they come)
         if r.returncode != 0:
@@ -206,12 +278,15 @@ def main():
                 continue
             cell = dict(this=tri(v["ms"][c]))
             if "route_off" in got:
-                cell["route_off"] = tri(got["route_off"][k]["ms"][c])[0]
+                ro = tri(got["route_off"][k]["ms"][c])
+                cell["route_off"] = ro[0]
+                if hz:   # the floor of this codec is set against the workers of this build: the ranges, and whether they lie apart
+                    cell.update(route_off_range=ro[1:], clear_of_route_off=bool(cell["this"][2] < ro[1]), lost_to_route_off=bool(ro[2] < cell["this"][1]))
             if "other" in got:
                 o = tri(got["other"][k]["ms"][c])
                 sp = (cell["this"][2] - cell["this"][1]) + (o[2] - o[1])
                 cell.update(other=o, x=round(o[0] / cell["this"][0], 3), slower=bool(o[0] + sp < cell["this"][0]), faster=bool(cell["this"][0] + sp < o[0]))
-                if c == "decode":
+                if c == "decode" or hz:
                     cell.update(clear=bool(cell["this"][2] < o[1]), lost=bool(o[2] < cell["this"][1]))
             row[c] = cell
         row["same"] = all(got[who][k]["digest"] == v["digest"] for who in ("route_off", "other") if who in got)
