@@ -11,8 +11,14 @@
 //     windowed   when the longest entry has at most 255 bytes: k_rle_approx.hip's route -- k_zd_maps turns every 256 positions into a
 //                map (entry offset -> entry offset of the next piece, by pointer doubling in LDS), rla_chain_entries scans the maps,
 //                k_zd_marks follows every piece from its entry, a lane per piece
-//     plain      otherwise (a flat stretch of the image made an entry of thousands of bytes): k_zd_walk, one block that follows
-//                the chain through windows of 4096 lengths staged in LDS.  Merely correct: one lane walks.
+//     hybrid     otherwise (a flat stretch of the image made an entry of thousands of bytes), zd_chain.hpp: the pieces that hold a
+//                length above 255 -- the BREAK pieces, k_zd_break_flags + rle_offsets number them -- keep their exits wide (k_zd_maps_wide),
+//                the other pieces' maps are scanned as above, k_zd_break_table carries every (break, entry) through the kept levels
+//                of that scan to the next break piece, k_zd_break_walk follows the table (one lane, one step per break piece the parse
+//                enters), k_zd_break_patch turns every entered break into a constant map and the pieces its jump flies over into
+//                identities that k_zd_marks skips, and the maps are scanned again.  No break piece in the tail: the windowed kernels alone.
+//     plain      more break pieces than kZcMaxBreaks (the side tables: 1.5 KiB each): k_zd_walk, one block that follows the chain
+//                through windows of 4096 lengths staged in LDS.  Merely correct: one lane walks.
 //   compaction   k_zd_count / rle_offsets / k_zd_emit: the symbols at the marked positions, in order, as u16; 0xFFFF behind an
 //                odd number of them (next_pair's (symbol1, ZIP_SPECIAL_EOF), dict.rs:81-86)
 //
@@ -24,6 +30,7 @@
 // Positions are 64-bit throughout: 8 + 11 w h passes 2^32 from w h = 3.9 10^8 on.
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "zd_chain.hpp"
 
 namespace cniic {
 
@@ -33,6 +40,7 @@ constexpr uint32_t kZdPer = 16;                     // positions per thread of t
 constexpr uint32_t kZdChunk = kZdThreads * kZdPer;  // 4096
 constexpr uint32_t kZdDecPer = 8;                   // symbols per thread of the decoder's sums
 constexpr uint32_t kZdDecChunk = kZdThreads * kZdDecPer;
+static_assert(kZdPiece == kZcPiece && kZdThreads == (int)kZcPiece && kZcMaxEntry == kZdMaxEntry && kZcMaxBreaks < (1u << 24), "zd_chain.hpp restates these");
 
 // ---------------------------------------------------------------- the 11-byte records (ser.rs:164-172,210-214)
 // text = [w h as u32 LE when dims] then per pixel: u64 LE 3, r, g, b.  A lane per text byte.
@@ -98,15 +106,98 @@ __global__ __launch_bounds__(kZdThreads) void k_zd_maps(const uint32_t *__restri
     maps[(size_t)blockIdx.x * kZdPiece + t] = (uint8_t)(nx - kZdPiece);   // <= 254
 }
 
-// a lane per piece: the parse starts it holds, from its entry
+// a lane per piece: the parse starts it holds, from its entry (skip: the pieces a long match flies over, or null)
 __global__ __launch_bounds__(kZdThreads) void k_zd_marks(const uint32_t *__restrict__ len, uint64_t M, const uint8_t *__restrict__ ent, uint32_t npieces,
-                                                         uint8_t *__restrict__ mark) {
+                                                         const uint8_t *__restrict__ skip, uint8_t *__restrict__ mark) {
     const uint32_t piece = blockIdx.x * kZdThreads + threadIdx.x;
     if (piece >= npieces) return;
+    if (skip && skip[piece]) return;
     const uint64_t base = (uint64_t)piece * kZdPiece;
     for (uint32_t p = ent[piece]; p < kZdPiece && base + p < M;) {
         mark[base + p] = 1;
         p += len[base + p];
+    }
+}
+
+// ---------------------------------------------------------------- encode: the chain, hybrid (zd_chain.hpp)
+// a wave per piece: does it hold a length above 255?
+__global__ __launch_bounds__(kZdThreads) void k_zd_break_flags(const uint32_t *__restrict__ len, uint64_t M, uint32_t npieces, uint32_t *__restrict__ flags) {
+    const uint32_t piece = blockIdx.x * (kZdThreads / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (piece >= npieces) return;   // (whole waves)
+    const uint64_t base = (uint64_t)piece * kZdPiece;
+    bool any = false;
+#pragma unroll
+    for (uint32_t k = 0; k < kZdPiece / 64; k++) {
+        const uint64_t r = base + 64 * k + lane;
+        if (r < M) any |= zc_is_break(len[r]);
+    }
+    const bool brk = __ballot(any) != 0;
+    if (lane == 0) flags[piece] = brk ? 1u : 0u;
+}
+
+// k_zd_maps with any length: a break piece (number before[piece]) writes its 256 exits as u16 -- one 512-byte row -- and a dummy map
+__global__ __launch_bounds__(kZdThreads) void k_zd_maps_wide(const uint32_t *__restrict__ len, uint64_t M, const uint32_t *__restrict__ flags,
+                                                             const uint64_t *__restrict__ before, uint8_t *__restrict__ maps,
+                                                             uint16_t *__restrict__ exits, uint32_t *__restrict__ brk_piece) {
+    __shared__ uint16_t s_nx[kZdPiece];
+    const uint32_t t = threadIdx.x;
+    const uint64_t r = (uint64_t)blockIdx.x * kZdPiece + t;
+    uint32_t nx = zc_exit_first(t, r < M, r < M ? len[r] : 1u);   // <= 255 + 32768
+    s_nx[t] = (uint16_t)nx;
+    __syncthreads();
+    for (int k = 0; k < kZcRounds; k++) {
+        nx = zc_exit_round(nx, s_nx);
+        __syncthreads();
+        s_nx[t] = (uint16_t)nx;
+        __syncthreads();
+    }
+    if (flags[blockIdx.x]) {
+        const uint64_t b = before[blockIdx.x];
+        maps[(size_t)blockIdx.x * kZdPiece + t] = 0;
+        exits[b * kZdPiece + t] = (uint16_t)nx;
+        if (t == 0) brk_piece[b] = blockIdx.x;
+    } else {
+        maps[(size_t)blockIdx.x * kZdPiece + t] = (uint8_t)(nx - kZdPiece);   // <= 254
+    }
+}
+
+// a lane per (break, entry): the next break piece that chain stands in, and its entry there.  All lanes are independent; each is a
+// chain of dependent one-byte loads (zc_range: at most 128 per level), so the grid is what hides them.
+__global__ __launch_bounds__(kZdThreads) void k_zd_break_table(ZcLevels lv, const uint16_t *__restrict__ exits, const uint32_t *__restrict__ brk_piece,
+                                                               const uint64_t *__restrict__ before, uint32_t npieces, uint64_t M, uint32_t B, uint32_t *__restrict__ table) {
+    const size_t at = (size_t)blockIdx.x * kZdPiece + threadIdx.x;
+    table[at] = zc_table_entry(lv, brk_piece[blockIdx.x], exits[at], npieces, M, before, brk_piece, B);
+}
+
+// one lane: the break pieces the parse enters and its entry offset in each.  Every step moves to a later break, and the loop has B steps.
+__global__ __launch_bounds__(64) void k_zd_break_walk(ZcLevels lv, const uint32_t *__restrict__ table, const uint32_t *__restrict__ brk_piece,
+                                                      const uint64_t *__restrict__ before, uint32_t npieces, uint64_t M, uint32_t B, uint8_t *__restrict__ entered,
+                                                      uint8_t *__restrict__ entry, uint32_t *__restrict__ count) {
+    if (threadIdx.x) return;
+    uint32_t st = zc_next_break(lv, 0, 0, npieces, M, before, brk_piece, B), n = 0;
+    for (uint32_t step = 0; step < B && st != kZcEnd; step++) {
+        const uint32_t b = zc_brk(st), e = zc_entry(st);
+        if (b >= B) break;
+        entered[b] = 1;
+        entry[b] = (uint8_t)e;
+        n++;
+        st = zc_walk_next(table[(size_t)b * kZdPiece + e], b, B);
+    }
+    *count = n;
+}
+
+// a block per break piece that was entered: its map becomes the constant of its landing, the pieces flown over the identity (and `skip`)
+__global__ __launch_bounds__(kZdThreads) void k_zd_break_patch(const uint16_t *__restrict__ exits, const uint32_t *__restrict__ brk_piece,
+                                                               const uint8_t *__restrict__ entered, const uint8_t *__restrict__ entry, uint32_t npieces,
+                                                               uint8_t *__restrict__ maps, uint8_t *__restrict__ skip) {
+    if (!entered[blockIdx.x]) return;
+    const uint32_t j = brk_piece[blockIdx.x], t = threadIdx.x;
+    if (j >= npieces) return;
+    const uint32_t x = exits[(size_t)blockIdx.x * kZdPiece + entry[blockIdx.x]];
+    maps[(size_t)j * kZdPiece + t] = zc_patch_map(true, x, t);
+    for (uint32_t p = j + 1, end = zc_flown_end(j, x, npieces); p < end; p++) {   // (< 129 pieces)
+        maps[(size_t)p * kZdPiece + t] = zc_patch_map(false, x, t);
+        if (t == 0) skip[p] = 1;
     }
 }
 
@@ -271,6 +362,111 @@ int zd_unserialize(Ctx *c, const uint8_t *rec_d, uint64_t npx, uint8_t *px_d, ui
     return CNIIC_OK;
 }
 
+// the stages of the hybrid chain as marks of their own (stage timers only): events between the launches, read at the end
+struct ZdStageMarks {
+    Ctx *c;
+    std::vector<std::pair<const char *, hipEvent_t>> ev;
+    explicit ZdStageMarks(Ctx *ctx) : c(ctx) { mark(nullptr); }
+    ~ZdStageMarks() { for (auto &e : ev) (void)hipEventDestroy(e.second); }
+    void mark(const char *ends) {   // `ends`: the stage that ends here
+        if (!c->timers) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, c->stream);
+        ev.emplace_back(ends, e);
+    }
+    void finish(const char *whole) {
+        if (ev.size() < 2) return;
+        (void)hipEventSynchronize(ev.back().second);
+        float ms = 0.f;
+        for (size_t i = 1; i < ev.size(); i++) {
+            if (hipEventElapsedTime(&ms, ev[i - 1].second, ev[i].second) == hipSuccess) c->ktimes[ev[i].first].ms += ms;
+            c->ktimes[ev[i].first].launches += 1;
+        }
+        if (hipEventElapsedTime(&ms, ev.front().second, ev.back().second) == hipSuccess) c->ktimes[whole].ms += ms;
+        c->ktimes[whole].launches += 1;
+    }
+};
+
+static uint32_t zd_max_breaks() {
+    uint32_t bound = kZcMaxBreaks;
+    if (const char *e = test_env("CNIIC_TEST_ZD_CHAIN_MAX_BREAKS")) bound = (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), bound);   // (lowers, never raises)
+    return bound;
+}
+
+// The chain of a text with an entry above 255 bytes, zd_chain.hpp's way.  *ran = false: more break pieces than the bound (or the
+// testing library's CNIIC_TEST_ZD_CHAIN=walk), nothing is marked and the caller walks.
+static int zd_chain_hybrid(Ctx *c, const uint32_t *len_d, uint64_t M, uint32_t npieces, uint8_t *mark_d, bool *ran) {
+    *ran = false;
+    if (const char *e = test_env("CNIIC_TEST_ZD_CHAIN")) if (strcmp(e, "walk") == 0) return CNIIC_OK;
+    ZdStageMarks stages(c);
+    DevBuf flags, before, tot, maps0, exits, brk_piece, table, entered, skip, count;
+    RlaLevels levels, levels2;
+    CNIIC_HIP_TRY(c, flags.alloc((uint64_t)npieces * 4));
+    CNIIC_HIP_TRY(c, before.alloc((uint64_t)npieces * 8));
+    CNIIC_HIP_TRY(c, tot.alloc(8));
+    hipLaunchKernelGGL(k_zd_break_flags, dim3((uint32_t)ceil_div(npieces, kZdThreads / 64)), dim3(kZdThreads), 0, c->stream, len_d, M, npieces, flags.as<uint32_t>());
+    CNIIC_TRY(rle_offsets(c, flags.as<uint32_t>(), npieces, before.as<uint64_t>(), tot.as<uint64_t>()));
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    uint64_t B64 = 0;
+    CNIIC_HIP_TRY(c, hipMemcpyAsync(&B64, tot.p, 8, hipMemcpyDeviceToHost, c->stream));
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (B64 > zd_max_breaks()) return CNIIC_OK;
+    const uint32_t B = (uint32_t)B64;
+    stages.mark("zd_hy_breaks");
+    CNIIC_HIP_TRY(c, maps0.alloc((uint64_t)npieces * kZdPiece));
+    const uint8_t *ent = nullptr, *skip_d = nullptr;
+    uint32_t n_entered = 0;
+    if (!B) {   // long entries, none of which matches in the tail: the windowed kernels alone
+        hipLaunchKernelGGL(k_zd_maps, dim3(npieces), dim3(kZdThreads), 0, c->stream, len_d, M, maps0.as<uint8_t>());
+        stages.mark("zd_hy_maps");
+        CNIIC_TRY(rla_chain_entries(c, maps0.as<uint8_t>(), npieces, &levels, &ent));
+        stages.mark("zd_hy_scan");
+    } else {
+        CNIIC_HIP_TRY(c, exits.alloc((uint64_t)B * kZdPiece * 2));
+        CNIIC_HIP_TRY(c, table.alloc((uint64_t)B * kZdPiece * 4));
+        CNIIC_HIP_TRY(c, brk_piece.alloc((uint64_t)B * 4));
+        CNIIC_HIP_TRY(c, entered.alloc((uint64_t)B * 2));   // entered[B], then the entries
+        CNIIC_HIP_TRY(c, skip.alloc(npieces));
+        CNIIC_HIP_TRY(c, count.alloc(4));
+        CNIIC_HIP_TRY(c, hipMemsetAsync(entered.p, 0, (uint64_t)B * 2, c->stream));
+        CNIIC_HIP_TRY(c, hipMemsetAsync(skip.p, 0, npieces, c->stream));
+        hipLaunchKernelGGL(k_zd_maps_wide, dim3(npieces), dim3(kZdThreads), 0, c->stream, len_d, M, (const uint32_t *)flags.as<uint32_t>(),
+                           (const uint64_t *)before.as<uint64_t>(), maps0.as<uint8_t>(), exits.as<uint16_t>(), brk_piece.as<uint32_t>());
+        stages.mark("zd_hy_maps");
+        CNIIC_TRY(rla_chain_entries(c, maps0.as<uint8_t>(), npieces, &levels, &ent));
+        stages.mark("zd_hy_scan");
+        ZcLevels lv{};
+        lv.n = (uint32_t)levels.maps.size();
+        if (lv.n > kZcMaxLevels) return c->fail(CNIIC_ERR_BAD_ARG, "zip-dict: text too long");
+        lv.maps[0] = maps0.as<uint8_t>();
+        for (uint32_t l = 1; l < lv.n; l++) lv.maps[l] = levels.maps[l].as<uint8_t>();
+        hipLaunchKernelGGL(k_zd_break_table, dim3(B), dim3(kZdThreads), 0, c->stream, lv, (const uint16_t *)exits.as<uint16_t>(),
+                           (const uint32_t *)brk_piece.as<uint32_t>(), (const uint64_t *)before.as<uint64_t>(), npieces, M, B, table.as<uint32_t>());
+        stages.mark("zd_hy_table");
+        hipLaunchKernelGGL(k_zd_break_walk, dim3(1), dim3(64), 0, c->stream, lv, (const uint32_t *)table.as<uint32_t>(), (const uint32_t *)brk_piece.as<uint32_t>(),
+                           (const uint64_t *)before.as<uint64_t>(), npieces, M, B, entered.as<uint8_t>(), entered.as<uint8_t>() + B, count.as<uint32_t>());
+        stages.mark("zd_hy_walk");
+        hipLaunchKernelGGL(k_zd_break_patch, dim3(B), dim3(kZdThreads), 0, c->stream, (const uint16_t *)exits.as<uint16_t>(), (const uint32_t *)brk_piece.as<uint32_t>(),
+                           (const uint8_t *)entered.as<uint8_t>(), (const uint8_t *)entered.as<uint8_t>() + B, npieces, maps0.as<uint8_t>(), skip.as<uint8_t>());
+        CNIIC_TRY(rla_chain_entries(c, maps0.as<uint8_t>(), npieces, &levels2, &ent));
+        stages.mark("zd_hy_patch");
+        skip_d = skip.as<uint8_t>();
+        if (c->timers) CNIIC_HIP_TRY(c, hipMemcpyAsync(&n_entered, count.p, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    hipLaunchKernelGGL(k_zd_marks, dim3((uint32_t)ceil_div(npieces, kZdThreads)), dim3(kZdThreads), 0, c->stream, len_d, M, ent, npieces, skip_d, mark_d);
+    CNIIC_HIP_TRY(c, hipGetLastError());
+    stages.mark("zd_hy_marks");
+    if (c->timers) {
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        stages.finish("zd_chain_hybrid");
+        c->ktimes["zd_chain_breaks"].launches += B;
+        c->ktimes["zd_chain_entered"].launches += n_entered;
+    }
+    *ran = true;
+    return CNIIC_OK;
+}
+
 int zd_frozen_plan(Ctx *c, const uint8_t *text_d, uint64_t N, uint64_t P0, const ZdEdge *table_h, uint32_t bits, uint64_t max_entry, ZdFrozen *plan) {
     const uint64_t M = N - P0;
     plan->M = M;
@@ -307,11 +503,15 @@ int zd_frozen_plan(Ctx *c, const uint8_t *text_d, uint64_t N, uint64_t P0, const
             const uint8_t *ent = nullptr;
             CNIIC_TRY(rla_chain_entries(c, maps0.as<uint8_t>(), npieces, &levels, &ent));
             hipLaunchKernelGGL(k_zd_marks, dim3((uint32_t)ceil_div(npieces, kZdThreads)), dim3(kZdThreads), 0, c->stream, (const uint32_t *)len.as<uint32_t>(), M,
-                               ent, npieces, plan->mark.as<uint8_t>());
+                               ent, npieces, (const uint8_t *)nullptr, plan->mark.as<uint8_t>());
             CNIIC_HIP_TRY(c, hipGetLastError());
         } else {
-            hipLaunchKernelGGL(k_zd_walk, dim3(1), dim3(kZdThreads), 0, c->stream, (const uint32_t *)len.as<uint32_t>(), M, plan->mark.as<uint8_t>());
-            CNIIC_HIP_TRY(c, hipGetLastError());
+            bool hybrid = false;
+            CNIIC_TRY(zd_chain_hybrid(c, (const uint32_t *)len.as<uint32_t>(), M, npieces, plan->mark.as<uint8_t>(), &hybrid));
+            if (!hybrid) {
+                hipLaunchKernelGGL(k_zd_walk, dim3(1), dim3(kZdThreads), 0, c->stream, (const uint32_t *)len.as<uint32_t>(), M, plan->mark.as<uint8_t>());
+                CNIIC_HIP_TRY(c, hipGetLastError());
+            }
         }
         timer.stop();
     }

@@ -128,7 +128,14 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * cniic_hilbert_zip_measure_batch (described there) report the same marks under their own names: "hz_small_batch" = the duration of
  * k_hz_small (and of zeroing its trie tables), with launches = the frames given to the kernel; "hz_small_place"; "hz_small_handback";
  * "hz_small_finished"; "hz_small_dec_batch" = the duration of k_hz_small_dec, with launches = the frames it was given;
- * "hz_small_dec_handback".  No call that takes an expression reports any of them. */
+ * "hz_small_dec_handback".  No call that takes an expression reports any of them.
+ * The chain of a `zip(dict)` / hilbert-zip encode whose longest entry has more than 255 bytes ("zd_chain_plain", launches = 1 whichever way
+ * it ran) adds three marks when it ran as the hybrid chain (k_zipdict.hip, zd_chain.hpp) and none when the one-block walk ran:
+ * "zd_chain_hybrid" = the duration of its launches, launches = 1; "zd_chain_breaks" (no duration): launches = the break pieces, i.e. the
+ * 256-position pieces behind the fill end that hold a match of more than 255 bytes; "zd_chain_entered" (no duration): launches = the break
+ * pieces the parse enters.  Its stages, in order, each with launches = 1: "zd_hy_breaks" (flags and their numbering), "zd_hy_maps",
+ * "zd_hy_scan", "zd_hy_table", "zd_hy_walk", "zd_hy_patch" (patch and second scan), "zd_hy_marks"; a text without a break piece has no
+ * table, walk and patch. */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
@@ -651,7 +658,9 @@ int32_t cniic_hilbert_rle_approx_encode(cniic_ctx *ctx, double d, const uint8_t 
  * second.  0xFFFF is legal anywhere; a single byte behind the last whole pair ends the stream.  No memory is allocated from a size a
  * stream claims before the lengths have been summed and held against cap.
  * Stage timers (cniic_last_kernel_time): "zd_fill_host", "zd_table_host", "zd_match", "zd_chain" or "zd_chain_plain" (the longest
- * entry has more than 255 bytes), "zd_compact"; "zd_prefix_host", "zd_scan", "zd_copy"; the codecs add "zd_serialize". */
+ * entry has more than 255 bytes; with "zd_chain_hybrid", "zd_chain_breaks" and "zd_chain_entered" when the hybrid chain carried the
+ * parse across the long matches, without them when the one-block walk did: more than 174 082 break pieces), "zd_compact";
+ * "zd_prefix_host", "zd_scan", "zd_copy"; the codecs add "zd_serialize". */
 int32_t cniic_zip_dict_encode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
 int32_t cniic_zip_dict_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
 /* The dimensions of a zip(dict) stream: the first 8 bytes of its text, decoded from its first pairs.  HOST memory, no context.
