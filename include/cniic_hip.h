@@ -135,7 +135,12 @@ int32_t     cniic_ctx_get_opt(cniic_ctx *ctx, int32_t opt, uint64_t *value);
  * 256-position pieces behind the fill end that hold a match of more than 255 bytes; "zd_chain_entered" (no duration): launches = the break
  * pieces the parse enters.  Its stages, in order, each with launches = 1: "zd_hy_breaks" (flags and their numbering), "zd_hy_maps",
  * "zd_hy_scan", "zd_hy_table", "zd_hy_walk", "zd_hy_patch" (patch and second scan), "zd_hy_marks"; a text without a break piece has no
- * table, walk and patch. */
+ * table, walk and patch.
+ * The repaint of a single `voronoi` decode (and of the frames a batch call leaves to its workers) marks the kernel it took (launches
+ * only, no duration): "vor_paint_tiles" = 1 when the tile-pruned kernel painted (1 <= K <= 4096, sides up to 16 384, every centroid
+ * coordinate below 16 384), "vor_paint_brute" = 1 when the brute-force kernel did; "vor_paint_overflow": launches = the 64 x 32-pixel
+ * tiles of the tiled kernel whose kept list outgrew its 256 entries and that were painted by brute force (it exists, with 0, whenever
+ * the tiled kernel ran). */
 int32_t     cniic_last_kernel_time(cniic_ctx *ctx, const char *which, double *ms, uint64_t *launches);
 
 /* ------------------------------------------------------------------ H1: utils::count_freqs */
