@@ -177,6 +177,7 @@ PROTOTYPES = {
     "cniic_zip_back_image_decode": (_I32, [_PTR, _PTR, _U64, _PTR, _U64, _PTR, _PTR]),
     "cniic_zip_back_image_encode_batch_var": (_I32, [_PTR, _PTR, _PTR, _PTR, _PTR, _U32, _PTR, _U64, _PTR, _PTR]),
     "cniic_zip_back_image_decode_batch": (_I32, [_PTR, _PTR, _U64, _PTR, _U32, _PTR, _U64, _PTR, _PTR, _PTR]),
+    "cniic_zip_back_image_measure_batch": (_I32, [_PTR, _PTR, _PTR, _PTR, _PTR, _U32, _PTR, _PTR, _U64, _PTR]),
     "cniic_hilbert_linearize_count": (_I32, [_I32, _U32, _U32, _PTR]),
     "cniic_hilbert_linearize_as": (_I32, [_PTR, _I32, _PTR, _U32, _U32, _PTR, _U64, _PTR]),
     "cniic_channel_diff_hist": (_I32, [_PTR, _PTR, _U64, _PTR]),
@@ -683,6 +684,15 @@ class Context:
         rc = self._check(self._L.cniic_zip_back_image_decode_batch(self.h, _ptr(streams), stride, _array(C.c_uint64, lens, F), F, _ptr(out), img_stride,
                                                                    ws, hs, rcs), allow)
         return rc, [int(ws[f]) for f in range(F)], [int(hs[f]) for f in range(F)], [int(rcs[f]) for f in range(F)]
+
+    def zip_back_measure_batch(self, images, offs, ws, hs, out=None, stride=0, allow=()):
+        """cniic_zip_back_image_measure_batch: measure_batch for Zip::Back -> (rc, list of row dicts, list of stream lengths)"""
+        F = len(offs)
+        n = max(F, 1)
+        rows, lens = (MeasureRow * n)(), (C.c_uint64 * n)()
+        rc = self._check(self._L.cniic_zip_back_image_measure_batch(self.h, _ptr(images), _array(C.c_uint64, offs, F), _array(C.c_uint32, ws, F),
+                                                                    _array(C.c_uint32, hs, F), F, rows, _ptr(out), stride, lens), allow)
+        return rc, [rows[f].as_dict() for f in range(F)], [int(lens[f]) for f in range(F)]
 
     def encode_batch(self, expr, frames, w, h, F, out, stride, seed=0, max_iters=0, flags=0, allow=()):
         """cniic_codec_encode_batch: F images (one contiguous [F][h][w][3] buffer), each encoded on its own (its own palette), image f's

@@ -285,7 +285,8 @@ class HilbertZip(Codec):
 class ZipBack(Codec):
     """Zip::Back (src/codec/zipc.rs:14-48): the look-back coder (src/zip/back.rs) over the dimensions and the 11-byte records of the
     pixels, row by row.  `zip(back)` is not an expression of this library: encode and decode go through cniic_zip_back_image_encode /
-    cniic_zip_back_image_decode, batches through cniic_zip_back_image_encode_batch_var / _decode_batch (one workgroup per image).
+    cniic_zip_back_image_decode, batches through cniic_zip_back_image_encode_batch_var / _decode_batch (one workgroup per image),
+    measure through cniic_zip_back_image_measure_batch.
     encode raises CniicError(UNSUPPORTED) for an image on which the reference panics (a flat stretch of about 3000 pixels)."""
 
     def __init__(self, ctx=None):
@@ -331,8 +332,15 @@ class ZipBack(Codec):
         return [out[f * img_stride:f * img_stride + 3 * ws[f] * hs[f]].reshape(hs[f], ws[f], 3).copy() if rcs[f] == _lib.OK else None
                 for f in range(len(streams))]
 
-    def measure(self, imgs, **kw):
-        raise NotImplementedError("zip-back has no expression: cniic_codec_measure_batch cannot name it")
+    def measure(self, imgs, seed=0, max_iters=0, flags=0, allow=()):
+        """bench::measure_all's loop over a list of images of any sizes in ONE call (cniic_zip_back_image_measure_batch): a list of dicts
+        with the reference's CSV columns compressed_size, compression_ratio, error (bench.rs:68-75) plus rc (and lossless_mismatch,
+        kmeans).  seed, max_iters and flags are Codec.measure's K-means options: taken, and without meaning for this codec."""
+        if len(imgs) == 0:
+            return []
+        buf, offs, ws, hs = self._packed(imgs)
+        rc, rows, _ = self.ctx.zip_back_measure_batch(buf, offs, ws, hs, allow=(_lib.BAD_ARG, _lib.UNSUPPORTED, _lib.DECODE) + tuple(allow))
+        return rows
 
     def name(self):
         return "zip-back"         # zipc.rs:53

@@ -1974,6 +1974,105 @@ int32_t cniic_hilbert_zip_measure_batch(cniic_ctx *c, const uint8_t *rgb, const 
     return measure_batch_locked(c, kHilbertZipDesc, "hilbert_zip_measure_batch", nullptr, rgb, img_off, w, h, frames, rows, out, stride, lens);
 }
 
+// Zip::Back has no CodecDesc, so its folder has a chunk loop of its own over the codec's batch calls (zipback.cpp).  A frame's scratch:
+// its stream with room for the worst case, the encoder's and the decoder's text (8 + 11 w h bytes each), the decoded image, and the
+// image itself when it comes from host memory.  No stream outgrows zb_stream_bound, so no frame is ever encoded twice.
+static int32_t zip_back_measure_chunk(cniic_ctx *c, const std::vector<uint32_t> &which, bool src_dev, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w,
+                                      const uint32_t *h, cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens, std::vector<std::string> &msg) {
+    const uint32_t n = (uint32_t)which.size();
+    const uint64_t npx0 = (uint64_t)w[which[0]] * h[which[0]];
+    const uint64_t room = (zb_stream_bound(8 + 11 * npx0) + 15) & ~15ull, img_stride = std::max<uint64_t>(16, (npx0 * 3 + 15) & ~15ull);
+    DevBuf sbuf, ibuf, hbuf;
+    CNIIC_HIP_TRY(c, sbuf.alloc(room * n));
+    CNIIC_HIP_TRY(c, ibuf.alloc(img_stride * n));
+    std::vector<uint64_t> a_off(n), b_off(n), npx(n), slen(n);
+    std::vector<uint32_t> wv(n), hv(n), w2(n), h2(n);
+    const uint8_t *a_base = rgb;
+    if (!src_dev) CNIIC_HIP_TRY(c, hbuf.alloc(img_stride * n));
+    for (uint32_t j = 0; j < n; j++) {
+        wv[j] = w[which[j]]; hv[j] = h[which[j]];
+        b_off[j] = img_stride * j;
+        a_off[j] = src_dev ? img_off[which[j]] : img_stride * j;
+        const uint64_t bytes = (uint64_t)wv[j] * hv[j] * 3;
+        if (!src_dev && bytes) CNIIC_HIP_TRY(c, hipMemcpyAsync(hbuf.as<uint8_t>() + a_off[j], rgb + img_off[which[j]], bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    if (!src_dev) {
+        CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        a_base = hbuf.as<uint8_t>();
+    }
+    std::vector<int32_t> erc(n, CNIIC_OK), drc(n, CNIIC_OK);
+    std::vector<std::string> emsg, dmsg;
+    const int32_t e = encode_zip_back_batch(c, a_base, a_off.data(), wv.data(), hv.data(), n, sbuf.as<uint8_t>(), room, slen.data(), erc.data(), &emsg);
+    if (emsg.size() != n) return e;   // (the batch as a whole failed: the message is the context's)
+    std::vector<uint64_t> dlen(n);
+    for (uint32_t j = 0; j < n; j++) dlen[j] = erc[j] == CNIIC_OK ? slen[j] : 0;
+    const int32_t d = decode_zip_back_batch(c, sbuf.as<uint8_t>(), room, dlen.data(), n, ibuf.as<uint8_t>(), img_stride, w2.data(), h2.data(), drc.data(), &dmsg);
+    if (dmsg.size() != n) return d;
+    for (uint32_t j = 0; j < n; j++) npx[j] = erc[j] == CNIIC_OK && drc[j] == CNIIC_OK ? (uint64_t)wv[j] * hv[j] : 0;
+    std::vector<double> err(n);
+    CNIIC_TRY(mse_batch_var_locked(c, a_base, a_off.data(), ibuf.as<uint8_t>(), b_off.data(), npx.data(), n, err.data()));
+    const bool out_dev = out && is_device_ptr(out);
+    for (uint32_t j = 0; j < n; j++) {
+        const uint32_t f = which[j];
+        cniic_measure_row &r = rows[f];
+        r.rc = erc[j] != CNIIC_OK ? erc[j] : drc[j];
+        msg[f] = erc[j] != CNIIC_OK ? emsg[j] : dmsg[j];
+        if (r.rc != CNIIC_OK) continue;
+        r.compressed_size = slen[j];
+        if (lens) lens[f] = slen[j];
+        r.compression_ratio = (double)slen[j] / ((double)((uint64_t)wv[j] * hv[j]) * 24.0) * 100.0;
+        r.error = err[j];
+        r.lossless_mismatch = err[j] != 0.0;
+        if (!out) continue;
+        if (slen[j] > stride) {
+            r.rc = CNIIC_ERR_CAPACITY;
+            char buf[160];
+            snprintf(buf, sizeof buf, "measure: stream of frame %u is %llu bytes, %llu between streams", f, (unsigned long long)slen[j], (unsigned long long)stride);
+            msg[f] = buf;
+        } else if (slen[j]) {
+            CNIIC_HIP_TRY(c, hipMemcpyAsync(out + (uint64_t)f * stride, sbuf.as<uint8_t>() + room * j, slen[j], out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CNIIC_OK;
+}
+
+int32_t cniic_zip_back_image_measure_batch(cniic_ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t frames,
+                                           cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens) {
+    LOCK(c);
+    c->ktimes.clear();
+    if (!frames) return CNIIC_OK;
+    if (!rgb || !img_off || !w || !h || !rows) return c->fail(CNIIC_ERR_BAD_ARG, "zip_back_image_measure_batch: null argument");
+    CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));   // whatever produced the images on this context's stream is done
+    const bool src_dev = is_device_ptr(rgb);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<std::string> msg(frames);
+    std::vector<uint32_t> order;
+    for (uint32_t f = 0; f < frames; f++) {
+        memset(&rows[f], 0, sizeof rows[f]);
+        rows[f].compression_ratio = rows[f].error = nan;
+        if (lens) lens[f] = 0;
+        if ((uint64_t)w[f] * h[f] >= (1ull << 32)) { rows[f].rc = CNIIC_ERR_BAD_ARG; msg[f] = "image too large"; continue; }
+        order.push_back(f);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const uint64_t px = (uint64_t)w[x] * h[x], py = (uint64_t)w[y] * h[y];
+        return px != py ? px > py : w[x] != w[y] ? w[x] > w[y] : x < y;
+    });
+    // chunks of the list, largest frames first: as many frames as the budget holds at the size of the chunk's first (one at least)
+    const uint64_t budget = measure_budget();
+    for (size_t i = 0; i < order.size();) {
+        const uint64_t npx0 = (uint64_t)w[order[i]] * h[order[i]];
+        const uint64_t per = zb_stream_bound(8 + 11 * npx0) + 16 + 2 * (8 + 11 * npx0 + 255) + (src_dev ? 1 : 2) * std::max<uint64_t>(16, (npx0 * 3 + 15) & ~15ull);
+        const size_t n = (size_t)std::min<uint64_t>(order.size() - i, std::max<uint64_t>(1, budget / per));
+        CNIIC_TRY(zip_back_measure_chunk(c, std::vector<uint32_t>(order.begin() + i, order.begin() + i + n), src_dev, rgb, img_off, w, h, rows, out, stride, lens, msg));
+        i += n;
+    }
+    std::vector<int32_t> status(frames);
+    for (uint32_t f = 0; f < frames; f++) status[f] = rows[f].rc;
+    return fold_status(c, status.data(), msg.data(), frames, nullptr);
+}
+
 int32_t cniic_synth_image(cniic_ctx *c, int32_t kind, uint64_t seed, uint32_t w, uint32_t h, uint8_t *rgb) {
     LOCK(c);
     const uint64_t n = (uint64_t)w * h;

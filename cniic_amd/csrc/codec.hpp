@@ -138,11 +138,12 @@ int zip_back_encode_text(Ctx *c, const uint8_t *text_d, uint64_t n, uint8_t *out
 int zip_back_decode_bytes(Ctx *c, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);    // the whole text; bytes / out: host or device
 // host memory: the first 8 bytes of the text of a stream of `total` bytes, of which the first `avail` are at bytes (64 are always enough)
 int zip_back_dims(const uint8_t *bytes, uint64_t avail, uint64_t total, uint32_t *w, uint32_t *h);
-// the layouts of cniic_codec_encode_batch_var / cniic_codec_decode_batch; rgb, out, bytes: host or device; the other arrays on the host
+// the layouts of cniic_codec_encode_batch_var / cniic_codec_decode_batch; rgb, out, bytes: host or device; the other arrays on the host;
+// msgs (optional): every frame's message, empty where it went well (cniic_zip_back_image_measure_batch folds them by frame)
 int encode_zip_back_batch(Ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride,
-                          uint64_t *lens, int32_t *rcs);
+                          uint64_t *lens, int32_t *rcs, std::vector<std::string> *msgs = nullptr);
 int decode_zip_back_batch(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, uint64_t img_stride, uint32_t *w,
-                          uint32_t *h, int32_t *rcs);
+                          uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs = nullptr);
 
 // cniic_codec_decode_batch's device route: the `hufman` / `cluster-colors` / `hilbert(rle)` frames and the small `delta`, `voronoi`, `zip(dict)`
 // and (cniic_hilbert_zip_decode_batch) Hilbert { compress: Zip } frames of a batch decoded together (stream f at bytes + f *

@@ -835,6 +835,22 @@ inline uint64_t zb_text_bound(uint64_t n) { return n < (1ull << 48) ? (n / 4 + 1
 inline uint64_t zb_stream_bound(uint64_t n) { return n + n / 4 + 16; }
 int zb_encode_streams(Ctx *c, const ZbStream *streams_h, uint32_t F, ZbState *states_h);   // to the end of every stream (syncs)
 int zb_decode_streams(Ctx *c, const ZbStream *streams_h, uint32_t F, ZbState *states_h);
+// k_zipback_par.hip: one stream decoded by the whole GPU (zb_par.hpp), to the state k_zb_decode would leave; in / out: HBM, 1 <= n < 2^32.
+// handed: the stream is the serial kernel's after all (min(made, cap) of 2^32 or more, or text tables above kZbParScratchMax; pointers
+// left after round_cap <= 32 jump rounds)
+// and what lies below cap is to be written again.  zb_par_stream_scratch: the bytes of its tables before the text's are known.
+// the classes that take it: calls of ONE stream, streams of 512 KiB or more.  Measured (profiles/zip_back_probe.json, NOTES AW): single
+// decodes of photo-like and noise images from 462 993 / 510 257 bytes of stream (256 x 256) to 7.5 / 8.1 MB (1024 x 1024) ran in
+// 0.39 - 1.5 ms against the serial walk's 61 - 1087 ms, the ranges of 5 runs far apart for both contents.  Calls of 8, 32 and 100
+// streams of 148 - 450 KB won too (2.8 / 11 / 35 ms against 52 / 59 / 64) but were measured on photo-like frames only, and shorter
+// streams not at all: they stay with the serial kernel.
+constexpr uint32_t kZbParMaxStreams = 1;
+constexpr uint64_t kZbParFloorBytes = 512 << 10;
+// a stream whose tables (9 B per stream byte) would take more than this stays serial; one whose text tables (8 B per text byte below
+// cap) would is handed back
+constexpr uint64_t kZbParScratchMax = 8ull << 30;
+uint64_t zb_par_stream_scratch(uint64_t n);
+int zb_par_decode_stream(Ctx *c, const ZbStream &s, uint32_t round_cap, ZbState *st, uint32_t *rounds, bool *handed);
 
 // ---- k_linearize.hip: hilbert.rs:10-32 linearize_rect / _small / _large, and the per-channel difference histogram of a linear stream ----
 int linearize_count(int32_t method, uint32_t w, uint32_t h, uint64_t *npx);   // host only: pixels the method yields (CNIIC_LIN_*)

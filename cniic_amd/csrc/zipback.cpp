@@ -22,10 +22,12 @@ Verdict verdict(int32_t rc, const char *fmt, ...) {
 }
 
 // the call's answer from its frames': the first failure and its message
-int first_failure(Ctx *c, const std::vector<Verdict> &v, int32_t *rcs) {
+int first_failure(Ctx *c, const std::vector<Verdict> &v, int32_t *rcs, std::vector<std::string> *msgs) {
     int rc = CNIIC_OK;
+    if (msgs) msgs->assign(v.size(), std::string());
     for (size_t f = 0; f < v.size(); f++) {
         if (rcs) rcs[f] = v[f].rc;
+        if (msgs) (*msgs)[f] = v[f].msg;
         if (rc == CNIIC_OK && v[f].rc != CNIIC_OK) rc = c->fail(v[f].rc, "%s", v[f].msg.c_str());
     }
     return rc;
@@ -81,6 +83,19 @@ int encode_jobs(Ctx *c, std::vector<EncJob> &jobs) {
 // One stream of a decode call: bytes_d[0, n) in HBM, its text to out_d[0, cap) in HBM, whole symbols while fewer than need are there.
 struct DecJob { const uint8_t *bytes_d = nullptr; uint64_t n = 0, need = 0; uint8_t *out_d = nullptr; uint64_t cap = 0; uint64_t made = 0; Verdict v; };
 
+// The floor of the whole-GPU decode (k_zipback_par.hip), in stream bytes, for a call of `streams` streams: a stream below it is walked by
+// the serial kernel.  kZbParMaxStreams / kZbParFloorBytes (common.hpp) are the classes tools/zip_back_probe.py found clear of the serial
+// walk for photo-like and noise alike (NOTES AW): calls of one stream of 512 KiB or more.  The testing library can turn the route off
+// (CNIIC_TEST_ZB_PAR_OFF=1; a run with CNIIC_TEST_ZB_SLICE set counts the serial kernel's launches and takes it off too) and lower the
+// floor (CNIIC_TEST_ZB_PAR_MIN, bytes, for calls of any number of streams; never higher).
+uint64_t zb_par_floor(uint32_t streams) {
+    if (const char *e = test_env("CNIIC_TEST_ZB_PAR_OFF")) if (atoi(e) != 0) return ~0ull;
+    if (test_env("CNIIC_TEST_ZB_SLICE")) return ~0ull;
+    uint64_t floor = streams <= kZbParMaxStreams ? kZbParFloorBytes : ~0ull;
+    if (const char *e = test_env("CNIIC_TEST_ZB_PAR_MIN")) floor = std::min<uint64_t>(floor, strtoull(e, nullptr, 10));
+    return floor;
+}
+
 int decode_jobs(Ctx *c, std::vector<DecJob> &jobs) {
     std::vector<ZbStream> streams;
     std::vector<uint32_t> who;
@@ -90,7 +105,35 @@ int decode_jobs(Ctx *c, std::vector<DecJob> &jobs) {
         who.push_back(j);
     }
     std::vector<ZbState> states(streams.size());
-    CNIIC_TRY(zb_decode_streams(c, streams.data(), (uint32_t)streams.size(), states.data()));
+    // the whole-GPU route (k_zipback_par.hip), a stream at a time; what it does not take, or hands back, is the serial kernel's
+    std::vector<uint32_t> serial;
+    const uint64_t floor = zb_par_floor((uint32_t)streams.size());
+    uint32_t round_cap = 32;
+    if (const char *e = test_env("CNIIC_TEST_ZB_PAR_ROUNDS")) round_cap = std::min<uint32_t>(round_cap, (uint32_t)strtoul(e, nullptr, 10));
+    uint64_t decoded = 0, handed_back = 0, rounds_all = 0;
+    {
+        ScopedKernelTimer timer(c, "zb_par_decode");
+        for (uint32_t i = 0; i < streams.size(); i++) {
+            const ZbStream &s = streams[i];
+            if (s.n < floor || s.n < 1 || s.n >= (1ull << 32) || zb_par_stream_scratch(s.n) > kZbParScratchMax) { serial.push_back(i); continue; }
+            uint32_t rounds = 0;
+            bool handed = false;
+            CNIIC_TRY(zb_par_decode_stream(c, s, round_cap, &states[i], &rounds, &handed));
+            rounds_all += rounds;
+            if (handed) { handed_back++; serial.push_back(i); } else decoded++;
+        }
+        if (decoded + handed_back) timer.stop(decoded);
+    }
+    if (c->timers && decoded + handed_back) { c->ktimes["zb_par_handback"].launches += handed_back; c->ktimes["zb_par_rounds"].launches += rounds_all; }
+    if (serial.size() == streams.size()) {
+        CNIIC_TRY(zb_decode_streams(c, streams.data(), (uint32_t)streams.size(), states.data()));
+    } else if (!serial.empty()) {
+        std::vector<ZbStream> rest(serial.size());
+        std::vector<ZbState> rest_states(serial.size());
+        for (uint32_t i = 0; i < serial.size(); i++) rest[i] = streams[serial[i]];
+        CNIIC_TRY(zb_decode_streams(c, rest.data(), (uint32_t)rest.size(), rest_states.data()));
+        for (uint32_t i = 0; i < serial.size(); i++) states[serial[i]] = rest_states[i];
+    }
     for (uint32_t i = 0; i < who.size(); i++) {
         DecJob &job = jobs[who[i]];
         const ZbState &st = states[i];
@@ -196,7 +239,7 @@ int zip_back_dims(const uint8_t *bytes, uint64_t avail, uint64_t total, uint32_t
 
 // ---------------------------------------------------------------- Zip::Back (zipc.rs:14-48), a folder at a time
 int encode_zip_back_batch(Ctx *c, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t F, uint8_t *out, uint64_t stride,
-                          uint64_t *lens, int32_t *rcs) {
+                          uint64_t *lens, int32_t *rcs, std::vector<std::string> *msgs) {
     std::vector<EncJob> jobs(F);
     std::vector<In<uint8_t>> img(F);
     std::vector<uint64_t> text_at(F, 0);
@@ -224,11 +267,11 @@ int encode_zip_back_batch(Ctx *c, const uint8_t *rgb, const uint64_t *img_off, c
     CNIIC_TRY(encode_jobs(c, jobs));
     std::vector<Verdict> v(F);
     for (uint32_t f = 0; f < F; f++) { lens[f] = jobs[f].len; v[f] = jobs[f].v; }
-    return first_failure(c, v, rcs);
+    return first_failure(c, v, rcs, msgs);
 }
 
 int decode_zip_back_batch(Ctx *c, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t F, uint8_t *rgb, uint64_t img_stride, uint32_t *w,
-                          uint32_t *h, int32_t *rcs) {
+                          uint32_t *h, int32_t *rcs, std::vector<std::string> *msgs) {
     std::vector<DecJob> jobs(F);
     DevBuf store, text, img_d;
     std::vector<const uint8_t *> at;
@@ -293,7 +336,7 @@ int decode_zip_back_batch(Ctx *c, const uint8_t *bytes, uint64_t stride, const u
     CNIIC_HIP_TRY(c, hipStreamSynchronize(c->stream));
     std::vector<Verdict> v(F);
     for (uint32_t f = 0; f < F; f++) v[f] = jobs[f].v;
-    return first_failure(c, v, rcs);
+    return first_failure(c, v, rcs, msgs);
 }
 
 }  // namespace cniic

@@ -716,7 +716,17 @@ int32_t cniic_hilbert_zip_decode_batch(cniic_ctx *ctx, const uint8_t *bytes, uin
  * symbol that stands for no byte (explicit of length 0, look-back with len or back 0: Decoder::next then answers None, :657-664);
  * CNIIC_ERR_DECODE where the reference panics: an explicit symbol with fewer than len bytes behind it (:97), a `back` greater than the
  * text so far (:466).  No memory is allocated from a size a stream claims.
- * Stage timers (cniic_last_kernel_time): "zb_encode", "zb_decode" (launches = the slices); the codec adds "zb_serialize", "zb_rebuild". */
+ * Stage timers (cniic_last_kernel_time): "zb_encode", "zb_decode" (launches = the slices); the codec adds "zb_serialize", "zb_rebuild".
+ * The decode is not inherently serial, and a second route decodes ONE stream with the whole GPU (k_zipback_par.hip): the symbol starts
+ * by pointer doubling over next(p), the text positions by a 64-bit prefix sum, the first event in stream order by a minimum, and the
+ * text -- a forest, since a copy of min(len, back) bytes never reaches itself -- by at most 32 jump rounds over a source pointer per
+ * text byte below cap.  Status, *len, every byte below cap and both messages are the serial walk's.  Streams of 2^32 bytes or more,
+ * texts with 2^32 bytes or more below cap, and streams whose tables (9 bytes per stream byte, 8 per text byte below cap) pass 8 GiB
+ * are walked serially.
+ * Stage timers: "zb_par_decode" (the route's launches; launches = the streams it decoded), "zb_par_handback" (no time; launches = the
+ * streams it gave back to the serial walk after starting on them), "zb_par_rounds" (no time; launches = jump rounds run, summed);
+ * "zb_decode" keeps its meaning for the streams the serial kernel walks.  Which calls take the route (one stream of 512 KiB or more):
+ * at cniic_zip_back_image_decode_batch below. */
 int32_t cniic_zip_back_encode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
 int32_t cniic_zip_back_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *len);
 /* The dimensions of a zip-back stream: the first 8 bytes of its text, decoded from its first symbols (they lie within the first 64
@@ -733,11 +743,23 @@ int32_t cniic_zip_back_image_decode(cniic_ctx *ctx, const uint8_t *bytes, uint64
  * decoded image f at rgb + f * img_stride; img_off, w, h, lens, rcs: HOST arrays).  Every frame is one workgroup of the same launches,
  * whatever their number; stream, lens[f] and rcs[f] are what the single call gives for frame f, and a frame that fails (UNSUPPORTED,
  * CAPACITY with lens[f] = bytes needed, DECODE) leaves the others as they are.  rcs may be NULL; the call returns the first failure
- * (lowest f) with its message in cniic_last_error; frames == 0 returns CNIIC_OK. */
+ * (lowest f) with its message in cniic_last_error; frames == 0 returns CNIIC_OK.
+ * Which decode calls take the whole-GPU route (cniic_zip_back_decode, cniic_zip_back_image_decode, cniic_zip_back_image_decode_batch
+ * alike; a class of calls is (streams in the call that can be decoded, stream length), and it takes the route only where 5 runs of it
+ * lay clear of 5 runs of the serial walk for photo-like AND noise; profiles/zip_back_probe.json, NOTES.md AW):
+ *   1 stream, 512 KiB of stream or more     the route.  Measured from 463 / 510 KB (256 x 256, photo-like / noise) to 7.5 / 8.1 MB
+ *                                           (1024 x 1024): 0.39 - 1.5 ms against the serial walk's 61 - 1087 ms
+ *   1 stream below 512 KiB                  serial: not measured
+ *   2 streams or more                       serial.  8 / 32 / 100 photo-like frames of 148 - 450 KB won (2.8 / 11 / 35 ms against
+ *                                           52 / 59 / 64), one stream after the other, but no noise folder was measured
+ * The route's tables are not part of cniic_zip_back_image_measure_batch's chunk budget: a chunk of several frames decodes serially;
+ * a chunk of ONE frame (an image too large to share a chunk) takes the route, and its tables -- 9 bytes per stream byte, 8 per text
+ * byte, each part at most 8 GiB -- come on top of the budget while that frame is decoded. */
 int32_t cniic_zip_back_image_encode_batch_var(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h,
                                               uint32_t frames, uint8_t *out, uint64_t stride, uint64_t *lens, int32_t *rcs);
 int32_t cniic_zip_back_image_decode_batch(cniic_ctx *ctx, const uint8_t *bytes, uint64_t stride, const uint64_t *lens, uint32_t frames,
                                           uint8_t *rgb, uint64_t img_stride, uint32_t *w, uint32_t *h, int32_t *rcs);
+/* (One call for a whole folder's encode -> decode -> MSE: cniic_zip_back_image_measure_batch, below beside cniic_hilbert_zip_measure_batch.) */
 /* Codec::decode: CNIIC_ERR_DECODE where the reference returns None / panics.  zip(dict): the reader is lazy (zipc.rs:28-36) -- exactly
  * 8 + 11 w h bytes of text are pulled, whole pairs as they are needed, and nothing behind the pair that completes the last pixel is
  * looked at; fewer bytes, or a pixel record whose length is not 3, is CNIIC_ERR_DECODE. */
@@ -859,6 +881,18 @@ int32_t cniic_codec_measure_batch(cniic_ctx *ctx, const char *expr, const cniic_
  * cniic_hilbert_zip_encode -> cniic_hilbert_zip_decode -> cniic_mse of image f alone; rows[f].kmeans stays zero. */
 int32_t cniic_hilbert_zip_measure_batch(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h, uint32_t frames,
                                         cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens);
+/* The body of bench::measure_all's loop (src/bench.rs:28-76) for a whole folder of Zip::Back in ONE call: the arguments, layouts, HOST
+ * arrays and rows (cniic_measure_row) of cniic_hilbert_zip_measure_batch.  Row f equals cniic_zip_back_image_encode ->
+ * cniic_zip_back_image_decode -> cniic_mse of image f alone; rows[f].kmeans stays zero.  Streams, texts and decoded images stay in HBM
+ * between the three steps.  The folder is worked through largest image first in chunks of at most 2 GiB of scratch HBM (per frame:
+ * the stream with room for the worst case, the encoder's and the decoder's text at 11 B/px, the decoded image, and the image itself
+ * when it comes from host memory; an image that needs more on its own is a chunk of its own).  A frame the reference panics on
+ * (CNIIC_ERR_UNSUPPORTED, back.rs:45) has its rc set, compressed_size = 0 and compression_ratio = error = NaN, and the others go on;
+ * the call returns the first failure (lowest f) with its message in cniic_last_error; frames == 0 returns CNIIC_OK.
+ * out / stride / lens may be NULL / 0 / NULL; with out, stream f is copied to out + f * stride (host or device memory) if it fits,
+ * otherwise that row's rc is CNIIC_ERR_CAPACITY (its measurements are still filled in) and lens[f] says what it needs. */
+int32_t cniic_zip_back_image_measure_batch(cniic_ctx *ctx, const uint8_t *rgb, const uint64_t *img_off, const uint32_t *w, const uint32_t *h,
+                                           uint32_t frames, cniic_measure_row *rows, uint8_t *out, uint64_t stride, uint64_t *lens);
 
 /* ------------------------------------------------------------------ surfaces: what a decoder or a crop hands over <-> packed RGB24 */
 /* Every call above takes packed RGB24, rows back to back; the reference takes an image::DynamicImage and begins with px.to_rgb() per

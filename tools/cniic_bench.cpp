@@ -12,7 +12,8 @@
 // Images run one per worker thread, each with its own cniic_ctx (the reference uses rayon, bench.rs:24-28).
 //   cniic_bench --codec=<expr> --one-call <image>...
 // loads all the images first (back to back in one device buffer) and hands the whole loop to ONE cniic_codec_measure_batch: the same
-// CSV, rows in argument order, the same exit status.
+// CSV, rows in argument order, the same exit status.  --codec='hilbert(zip)' and --codec='zip(back)', which are no expressions of the
+// library, go through their codecs' own calls (output/hilbert-zip.csv, output/zip-back.csv).
 //   cniic_bench --special=hilbert <image>...
 // the reference's other command (main.rs:23-55): per image the three linearisations of src/hilbert.rs:10-32 as CSV, one pixel per row, in
 // output/<file stem>.rect.hilbert.csv, .small.hilbert.csv and .large.hilbert.csv (under_output, main.rs:91-96: only the last extension
@@ -132,6 +133,8 @@ static bool parse_synth(const std::string &s, Image &im) {  // synth:P:4096x4096
 // Hilbert { compress: Zip } is no expression of the library (its parser rejects hilbert(zip), as it rejects zip(back)): the tool takes the
 // reference's spelling itself and goes through the codec's own calls, cniic_hilbert_zip_*_batch*
 static bool is_hilbert_zip(const std::string &expr) { return expr == "hilbert(zip)"; }
+// Zip::Back likewise: cniic_zip_back_image_* (name "zip-back", zipc.rs:53; lossless, :57-59)
+static bool is_zip_back(const std::string &expr) { return expr == "zip(back)"; }
 
 // --one-call: bench::measure_all's loop (bench.rs:24-83) as one cniic_codec_measure_batch over all the images
 static int run_one_call(const std::string &expr, const char *name, const std::vector<std::string> &paths, FILE *csv) {
@@ -165,12 +168,13 @@ static int run_one_call(const std::string &expr, const char *name, const std::ve
     }
     std::vector<cniic_measure_row> rows(F);
     auto t0 = std::chrono::steady_clock::now();
-    const bool hz = is_hilbert_zip(expr);
+    const bool hz = is_hilbert_zip(expr), zb = is_zip_back(expr);
     const int rc = hz ? cniic_hilbert_zip_measure_batch(ctx, (const uint8_t *)dimg, off.data(), w.data(), h.data(), F, rows.data(), nullptr, 0, nullptr)
+                   : zb ? cniic_zip_back_image_measure_batch(ctx, (const uint8_t *)dimg, off.data(), w.data(), h.data(), F, rows.data(), nullptr, 0, nullptr)
                       : cniic_codec_measure_batch(ctx, expr.c_str(), nullptr, (const uint8_t *)dimg, off.data(), w.data(), h.data(), F, rows.data(), nullptr, 0, nullptr);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc != CNIIC_OK) fprintf(stderr, "first failure: %s\n", cniic_last_error(ctx));
-    const bool lossless = hz || cniic_codec_is_lossless(expr.c_str()) == 1;
+    const bool lossless = hz || zb || cniic_codec_is_lossless(expr.c_str()) == 1;
     bool wrote_header = false;
     uint64_t npx_all = 0;
     for (uint32_t f = 0; f < F; f++) {
@@ -239,15 +243,16 @@ static int run_special_hilbert(const std::vector<std::string> &paths) {
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "--special=hilbert")) return run_special_hilbert(std::vector<std::string>(argv + 2, argv + argc));
     if (argc < 3 || strncmp(argv[1], "--codec=", 8) != 0) {
-        fprintf(stderr, "Usage: cniic_bench --codec=<codec> [--one-call] [<img file>..]\nAvailable codecs:\n  hufman\n  cluster-colors(<ncolors>)\n  voronoi(<k>)\n  delta\n  hilbert(rle)\n  hilbert(rle(<d>))\n  zip(dict)\n  hilbert(zip)\n");
+        fprintf(stderr, "Usage: cniic_bench --codec=<codec> [--one-call] [<img file>..]\nAvailable codecs:\n  hufman\n  cluster-colors(<ncolors>)\n  voronoi(<k>)\n  delta\n  hilbert(rle)\n  hilbert(rle(<d>))\n  zip(dict)\n  zip(back)\n  hilbert(zip)\n");
         return 2;
     }
     const std::string expr = argv[1] + 8;
     char name[64];
-    const bool hz = is_hilbert_zip(expr);
+    const bool hz = is_hilbert_zip(expr), zb = is_zip_back(expr);
     if (hz) snprintf(name, sizeof name, "hilbert-zip");   // hilbertc.rs:85
+    else if (zb) snprintf(name, sizeof name, "zip-back");   // zipc.rs:53
     else if (cniic_codec_name(expr.c_str(), name, sizeof name) != CNIIC_OK) { fprintf(stderr, "Malformed codec argument: %s\n", expr.c_str()); return 2; }
-    const bool lossless = hz || cniic_codec_is_lossless(expr.c_str()) == 1;   // :92
+    const bool lossless = hz || zb || cniic_codec_is_lossless(expr.c_str()) == 1;   // hilbertc.rs:92, zipc.rs:57-59
     mkdir("output", 0755);
     const std::string csv_path = std::string("output/") + name + ".csv";
     FILE *csv = fopen(csv_path.c_str(), "w");
@@ -286,12 +291,13 @@ int main(int argc, char **argv) {
                 else cniic_memcpy(ctx, dimg, im.rgb.data(), npx * 3);
                 uint64_t distinct = 0;  // (outside the timed encode: the algorithmic bytes of cluster-colors depend on it)
                 if (strncmp(name, "cluster-colors", 14) == 0) cniic_hist_rgb24(ctx, (const uint8_t *)dimg, npx, nullptr, nullptr, 0, &distinct);
-                std::vector<uint8_t> data(64 + npx * 16 + (1 << 16));
+                std::vector<uint8_t> data(64 + npx * 16 + (1 << 16));   // (zip-back's worst case is 13.75 B/px + 26)
                 uint64_t len = 0;
                 cniic_kmeans_stats st{};
                 auto t0 = std::chrono::steady_clock::now();
                 const uint64_t off0 = 0;
                 int rc = hz ? cniic_hilbert_zip_encode_batch_var(ctx, (const uint8_t *)dimg, &off0, &im.w, &im.h, 1, data.data(), data.size(), &len, nullptr)
+                         : zb ? cniic_zip_back_image_encode(ctx, (const uint8_t *)dimg, im.w, im.h, data.data(), data.size(), &len)
                             : cniic_codec_encode(ctx, expr.c_str(), (const uint8_t *)dimg, im.w, im.h, data.data(), data.size(), &len, &st);
                 double enc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                 if (rc != CNIIC_OK) { fail("encode"); cniic_dev_free(ctx, dimg); continue; }
@@ -301,6 +307,7 @@ int main(int argc, char **argv) {
                 cniic_dev_alloc(ctx, npx * 3, &dback);
                 uint32_t w2 = 0, h2 = 0;
                 rc = hz ? cniic_hilbert_zip_decode_batch(ctx, data.data(), data.size(), &len, 1, (uint8_t *)dback, npx * 3, &w2, &h2, nullptr)
+                     : zb ? cniic_zip_back_image_decode(ctx, data.data(), len, (uint8_t *)dback, npx * 3, &w2, &h2)
                         : cniic_codec_decode(ctx, expr.c_str(), data.data(), len, (uint8_t *)dback, npx * 3, &w2, &h2);
                 if (rc != CNIIC_OK) { fail("Could not decode the image"); cniic_dev_free(ctx, dimg); cniic_dev_free(ctx, dback); continue; }
                 double mse = 0;
@@ -317,6 +324,7 @@ int main(int argc, char **argv) {
                 else if (!strcmp(name, "delta")) algo += 11.0 * npx;
                 else if (!strcmp(name, "hilbert-rle")) algo += 6.0 * npx;
                 else if (!strcmp(name, "hilbert-zip")) algo += 3.0 * npx + 3.0 * npx + 2.0 * 11.0 * npx;   // the gather, the scan-ordered pixels, the text written and read
+                else if (!strcmp(name, "zip-back")) algo += 3.0 * npx + 2.0 * 11.0 * npx;   // the pixels, the text written and read
                 else if (!strncmp(name, "voronoi", 7)) algo += 7.0 * npx * (double)st.iterations;
                 else algo += 7.0 * npx + 10.0 * (double)distinct * (double)st.iterations;
                 const double gbps = algo / (enc_ms * 1e-3) / 1e9;
